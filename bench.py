@@ -3,7 +3,11 @@
 1 M hashes, default tolerance 0.35 -> 350, one MI355X), plus the DCT-hash throughput on 64x64 frame stacks
 (configs[2]) reported in the same JSON line under "hash", and the named legs below.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run times the headline alone: set-up, W warm-up steps, K timed steps, the one JSON line.  --full adds every named leg
+below, the CPU baselines and (N > 1) the single-process form; their size flags only take effect with --full.
+--dump-outputs DIR writes the MatchGroups of the last timed step to DIR as float64 arrays (dump_outputs).
 
 N > 1 runs one rank per GPU over RCCL.  Launched by torch.distributed.run (RANK in the environment) this process IS a
 rank; launched plainly it starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process
@@ -18,7 +22,7 @@ per-rank shards,) duration windows + tile list, the distance kernel, hit downloa
 greedy grouping.  value = hash pairs admitted by the reference's duration windows / wall time, whole job.
 Scaling of the headline is weak: the database grows as sqrt(N) so the pairs PER GPU stay fixed (~5e11).
 
-Named legs in the same line (sizes are flags, so tests run them small):
+Named legs in the same line, --full only (sizes are flags, so tests run them small):
   c4_10m_sharded   BASELINE configs[3]: all-pairs search() over 10 M hashes, database sharded over the N ranks, one
                    all-gather, row tiles round-robin (strong scaling; at N = 1 also reported as "ten_million")
   c5_end_to_end    BASELINE configs[4]: 1 M candidate + 100 k reference clips of 16 x 64 x 64 hashed per rank, hashes
@@ -491,6 +495,25 @@ def finish_line(out):
     return json.dumps(out)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, groups):
+    """--dump-outputs: the MatchGroups search() returned in the last timed step, as CSR arrays of float64 (indices < 2^53 are exact):
+    groups_offsets.npy [G + 1] and groups_members.npy, group g = members[offsets[g]:offsets[g + 1]] in the order search() returned.
+    The inputs are seeded, so two builds can be compared file for file.  Past DUMP_MAX_BYTES only every k-th group is written."""
+    every = 1
+    while 8 * (len(groups[::every]) + 1 + sum(len(g) for g in groups[::every])) > DUMP_MAX_BYTES:
+        every *= 2
+    groups = groups[::every]
+    offsets = np.zeros(len(groups) + 1, np.float64)
+    offsets[1:] = np.cumsum([len(g) for g in groups])
+    members = np.array([i for g in groups for i in g], np.float64)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "groups_offsets.npy"), offsets)
+    np.save(os.path.join(path, "groups_members.npy"), members)
+
+
 def free_port():
     import socket
 
@@ -531,7 +554,7 @@ def single_process_leg(args, timeout_s=600):
     Returns the dict carried as "single_process"; failures are reported, never raised."""
     import signal
 
-    cmd = [sys.executable, os.path.abspath(__file__), "--single-process", "--gpus", str(args.gpus), "--steps", str(args.steps),
+    cmd = [sys.executable, os.path.abspath(__file__), "--single-process", "--full", "--gpus", str(args.gpus), "--steps", str(args.steps),
            "--warmup", str(args.warmup), "--n-hashes", str(args.n_hashes), "--tolerance", str(args.tolerance),
            "--hash-clips", "0", "--c4-hashes", str(args.c4_hashes)]
     t0 = time.perf_counter()
@@ -632,12 +655,13 @@ def run_single_process(args):
         for k in set(devices):
             torch.cuda.synchronize(k)
 
-    per_dev, n_groups = [], None
+    per_dev, n_groups, last_groups = [], None, None
 
     def step():
-        nonlocal n_groups
+        nonlocal n_groups, last_groups
         groups = eng.search_self_shards(pw, pd, sizes, tol_int)
         n_groups = len(groups)
+        last_groups = groups
         per_dev.append([eng.device_stats(k) for k in range(G)])
 
     for _ in range(args.warmup):
@@ -652,6 +676,8 @@ def run_single_process(args):
     sync_all()
     dt = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_groups)
     backend = os.environ.get("VDF_SEARCH_BACKEND", "mfma")
     # the roofline describes ONE device's kernel: the slowest slot of each step
     slow = [max(st, key=lambda q: q["kernel_ms"]) for st in per_dev]
@@ -747,7 +773,14 @@ def main():
                     help="N > 1: do not run the C ABI's single-process form after the ranks")
     ap.add_argument("--single-process", action="store_true",
                     help="N > 1 inside ONE process through vdf_ctx_create_multi (no torch.distributed)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the named legs, the CPU baselines and (N > 1) the single-process form; without it only the headline runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the MatchGroups of the last timed step to DIR (dump_outputs)")
     args = ap.parse_args()
+    if not args.full:  # the headline alone: every leg off whatever its size flag says
+        args.hash_clips = args.c4_hashes = args.c5_cands = args.dup_heavy = args.cache_entries = 0
+        args.windowed = args.valu_leg = args.refs_leg = args.sp_leg = False
+        args.no_cpu_baseline = True
     if args.single_process:
         return run_single_process(args)
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -818,10 +851,11 @@ def main():
 
     kernel_ms = []
     n_groups = None
+    last_groups = None
     launches, suspects = [], []
 
     def step():
-        nonlocal n_groups
+        nonlocal n_groups, last_groups
         full_w, full_d = vd.all_gather_database(shard_w, shard_d, force=use_dist)
         groups = vd.search_self_sharded(eng, full_w, full_d, tol_int, stream=stream)
         st = eng.last_stats()
@@ -831,6 +865,7 @@ def main():
         suspects.append(eng.last_timing()["suspects"])
         if rank == 0:
             n_groups = len(groups)
+            last_groups = groups
 
     import gc
 
@@ -851,6 +886,8 @@ def main():
         dt = time.perf_counter() - t0
     gc.enable()
     dt = max_over_ranks(dt)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_groups)
 
     backend = os.environ.get("VDF_SEARCH_BACKEND", "mfma")
     roofline, extra, dtype = search_roofline(backend, kernel_ms)

@@ -182,3 +182,21 @@ def test_synthetic_cache_generator_round_trips():
     assert np.array_equal(c["hashes"], hashes) and np.array_equal(c["durations"], dur) and planted == 50
     assert c["paths"][0].startswith("/srv/media/lib_") and len(set(c["paths"])) == 5000
     assert all(int(np.unpackbits((hashes[i] ^ hashes[i + 1]).view(np.uint8)).sum()) <= 350 for i in range(0, 4900, 100))
+
+
+def test_dump_outputs_writes_the_groups_as_csr_and_stays_under_its_bound(tmp_path, monkeypatch):
+    """--dump-outputs: group g is members[offsets[g]:offsets[g + 1]], float64; past DUMP_MAX_BYTES a fixed every-k-th sample of whole groups."""
+    import numpy as np
+
+    groups = [[0, 5], [1, 2, 9], [3, 4], [6, 7, 8, 10]]
+    bench.dump_outputs(str(tmp_path / "a"), groups)
+    offsets, members = np.load(tmp_path / "a" / "groups_offsets.npy"), np.load(tmp_path / "a" / "groups_members.npy")
+    assert offsets.dtype == members.dtype == np.float64
+    assert [list(members[int(a):int(b)]) for a, b in zip(offsets[:-1], offsets[1:])] == groups
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 8)
+    bench.dump_outputs(str(tmp_path / "b"), groups)
+    offsets, members = np.load(tmp_path / "b" / "groups_offsets.npy"), np.load(tmp_path / "b" / "groups_members.npy")
+    assert 8 * (len(offsets) + len(members)) <= 8 * 8
+    assert [list(members[int(a):int(b)]) for a, b in zip(offsets[:-1], offsets[1:])] == [[0, 5], [3, 4]]
+    bench.dump_outputs(str(tmp_path / "c"), [])
+    assert list(np.load(tmp_path / "c" / "groups_offsets.npy")) == [0.0] and len(np.load(tmp_path / "c" / "groups_members.npy")) == 0

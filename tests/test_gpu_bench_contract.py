@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("backend", ["mfma", "valu"])
 def test_bench_emits_the_contract_line(backend):
     env = dict(os.environ, VDF_SEARCH_BACKEND=backend)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--full",
                           "--n-hashes", "30000", "--hash-clips", "3000", "--hash-hd-clips", "20", "--ten-million", "200000",
                           "--c5-cands", "4000", "--c5-refs", "400", "--dup-heavy", "40000", "--cache-entries", "30000"], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -87,3 +87,30 @@ def test_bench_emits_the_contract_line(backend):
         assert "x_of_hbm_model" in d["hbm_operand_stream_model"] and "frac" not in d["hbm_operand_stream_model"]
     else:
         assert "valu_backend" not in d
+
+
+def test_plain_run_times_the_headline_alone_and_dumps_its_groups(tmp_path):
+    """Without --full: the headline only (no leg, no CPU baseline), --steps timed steps, and --dump-outputs writes the MatchGroups of the
+    last timed step - the groups the oracle finds over the same seeded database."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+    from oracle import vdf_oracle as orc
+
+    n = 30000
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--n-hashes", str(n),
+                          "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "pairs/s" and d["config"]["n_hashes"] == n
+    for k in ("cpu_baseline", "hash", "windowed", "valu_backend", "refs_c5_shape", "c4_10m_sharded", "ten_million", "c5_end_to_end",
+              "dup_heavy", "cache_ingest", "single_process"):
+        assert k not in d, k
+    offsets = np.load(tmp_path / "dump" / "groups_offsets.npy")
+    members = np.load(tmp_path / "dump" / "groups_members.npy")
+    assert offsets.dtype == members.dtype == np.float64 and len(offsets) == d["match_groups"] + 1 and offsets[-1] == len(members)
+    got = [[int(x) for x in members[int(a):int(b)]] for a, b in zip(offsets[:-1], offsets[1:])]
+    assert got == orc.search_self_sorted(bench.make_hashes(n, 20250613), np.zeros(n, np.uint32), d["config"]["tolerance_int"])

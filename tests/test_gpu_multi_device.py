@@ -240,7 +240,7 @@ def _bench(extra, timeout=1500):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "VDF_DIST_BACKEND"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--hash-clips", "2000",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--full", "--hash-clips", "2000",
                           "--hash-hd-clips", "0", "--no-cpu-baseline", "--no-windowed", "--no-valu", "--no-refs", "--cache-entries", "0"] + extra,
                          capture_output=True, text=True, timeout=timeout, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

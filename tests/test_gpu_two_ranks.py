@@ -21,7 +21,7 @@ ROOT = os.path.dirname(HERE)
 def _bench(extra, env_extra=None):
     env = dict(os.environ, **(env_extra or {}))
     env.pop("RANK", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--hash-clips", "2000",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--full", "--hash-clips", "2000",
                           "--hash-hd-clips", "0", "--c4-hashes", "60000", "--c5-cands", "3000", "--c5-refs", "300", "--dup-heavy", "0", "--cache-entries", "0",
                           "--no-cpu-baseline", "--no-windowed", "--no-valu", "--no-refs"] + extra,
                          capture_output=True, text=True, timeout=900, env=env)

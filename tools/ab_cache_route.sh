@@ -2,7 +2,7 @@
 # bench.py's cache_ingest leg (10 M entries) with the path order on the device (default) and on the host (VDF_NO_DEVICE_PATH_ORDER, the route
 # before round 6).   bash tools/ab_cache_route.sh <out_dir under gpurun_out>
 O=gpurun_out/${1:-ab_cache}; mkdir -p $O
-B="python bench.py --steps 1 --warmup 1 --no-cpu-baseline --hash-clips 0 --no-windowed --c4-hashes 0 --c5-cands 0 --dup-heavy 0 --no-valu --no-refs"
+B="python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --hash-clips 0 --no-windowed --c4-hashes 0 --c5-cands 0 --dup-heavy 0 --no-valu --no-refs"
 for rep in 1 2; do
   for v in device host; do
     if [ $v = host ]; then export VDF_NO_DEVICE_PATH_ORDER=1; else unset VDF_NO_DEVICE_PATH_ORDER; fi
