@@ -61,8 +61,9 @@ def batch(g, w, h, budget_mb):
     return n, fr
 
 
-# sizes by the resize family the default dispatch gives them (csrc/resize_dispatch.cpp): persistent one-tile (64 x 64 and
-# smaller), fused per-clip (width off a multiple of 16), tiled <= 256 x 128, short-wide streams, chunk / per-wave / K-split streams, whole-line
+# sizes by the resize family the default dispatch gives them (csrc/resize_dispatch.cpp: plan_hash; checked entry by entry on
+# the CPU by tests/cpp/resize_dispatch_main.cpp): persistent one-tile (64 x 64 and smaller; width off a multiple of 16: the last clip through the
+# per-clip kernel), tiled <= 256 x 128, short-wide streams, chunk / per-wave / K-split streams
 HASH_SIZES = [(64, 64), (64, 48), (48, 36), (32, 32), (47, 33), (80, 48), (96, 64), (128, 72), (128, 128), (100, 60), (160, 90), (176, 144),
               (256, 128), (256, 144), (224, 126), (320, 180), (426, 240), (480, 270), (640, 360), (854, 480), (1024, 576), (1280, 720),
               (1366, 768), (1920, 1080), (2560, 1440), (3840, 2160), (100, 300), (1920, 64), (720, 576), (1440, 1080)]

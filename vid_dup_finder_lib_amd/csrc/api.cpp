@@ -588,112 +588,79 @@ int ensure_cos_table(vdf_ctx *ctx, hipStream_t stream)
 
 constexpr size_t kMaxClipsPerLaunch = 256 * 1024;  // x 16 frames x 256 threads stays under HIP's 2^32 work-item grid limit
 
-int hash_device_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w,
-                       uint32_t h, size_t frame_stride, size_t clip_stride, uint64_t *d_out, uint32_t *d_dc,
-                       hipStream_t stream)
-{
-    if (n_clips > kMaxClipsPerLaunch) {
-        for (size_t c0 = 0; c0 < n_clips; c0 += kMaxClipsPerLaunch) {
-            const size_t nb = std::min(kMaxClipsPerLaunch, n_clips - c0);
-            int rc = hash_device_locked(ctx, d_frames + c0 * clip_stride, nb, frames_per_clip, w, h, frame_stride,
-                                        clip_stride, d_out + c0 * VDF_HASH_WORDS, d_dc ? d_dc + c0 : nullptr, stream);
-            if (rc) return rc;
-        }
-        return VDF_OK;
-    }
-    if (frames_per_clip < VDF_DCT_SIZE) return fail(ctx, VDF_E_NOT_ENOUGH_FRAMES, "fewer than 16 frames per clip");
-    if (w == 0 || h == 0) return fail(ctx, VDF_E_BAD_DIMS, "zero frame dimension");
-    if (frame_stride < (size_t)w * h) return fail(ctx, VDF_E_INVAL, "frame_stride smaller than a frame");
-    if (n_clips == 0) return VDF_OK;
-    if (n_clips > 0x7FFFFFFull) return fail(ctx, VDF_E_INVAL, "too many clips in one call");
-    if (!d_frames || !d_out) return fail(ctx, VDF_E_INVAL, "null pointer");
-    VDF_HIP(ctx, hipSetDevice(ctx->device));
+// One launch's worth of a hash call: at most kMaxClipsPerLaunch clips of it.
+struct HashJob {
+    const uint8_t *d_frames;
+    size_t n_clips;
+    uint32_t w, h;
+    size_t frame_stride, clip_stride;
+    uint64_t *d_out;
+    uint32_t *d_dc;
+    hipStream_t stream;
+    vdf::HashCall call() const { return vdf::HashCall{d_frames, w, h, frame_stride, clip_stride, n_clips}; }
+    const uint8_t *buf_end() const { return d_frames + (n_clips - 1) * clip_stride + (VDF_DCT_SIZE - 1) * frame_stride + (size_t)w * h; }
+    HashJob clips(size_t c0, size_t n) const
     {
-        int rc0 = ensure_cos_table(ctx, stream);
-        if (rc0) return rc0;
+        return HashJob{d_frames + c0 * clip_stride, n, w, h, frame_stride, clip_stride, d_out + c0 * VDF_HASH_WORDS, d_dc ? d_dc + c0 : nullptr, stream};
     }
-    const bool direct = (w == VDF_DCT_SIZE && h == VDF_DCT_SIZE && ((uintptr_t)d_frames % 16) == 0 &&
-                         frame_stride % 16 == 0 && clip_stride % 16 == 0);
-    if (direct) {
-        VDF_HIP(ctx, vdf::launch_dct_hash(d_frames, clip_stride, frame_stride, n_clips, ctx->cos_table.as<double>(),
-                                          d_out, d_dc, stream));
-        return VDF_OK;
+};
+
+// Every hash entry: the argument checks, in the order their error codes are reported, then the call as launches of at most
+// kMaxClipsPerLaunch clips: one(first clip, clips)
+template <class One> int checked_launches(vdf_ctx *ctx, const HashJob &j, uint32_t frames_per_clip, One one)
+{
+    if (frames_per_clip < VDF_DCT_SIZE) return fail(ctx, VDF_E_NOT_ENOUGH_FRAMES, "fewer than 16 frames per clip");
+    if (j.w == 0 || j.h == 0) return fail(ctx, VDF_E_BAD_DIMS, "zero frame dimension");
+    if (j.frame_stride < (size_t)j.w * j.h) return fail(ctx, VDF_E_INVAL, "frame_stride smaller than a frame");
+    if (j.n_clips == 0) return VDF_OK;
+    if (!j.d_frames || !j.d_out) return fail(ctx, VDF_E_INVAL, "null pointer");
+    for (size_t c0 = 0; c0 < j.n_clips; c0 += kMaxClipsPerLaunch)
+        if (int rc = one(c0, std::min(kMaxClipsPerLaunch, j.n_clips - c0))) return rc;
+    return VDF_OK;
+}
+
+vdf::HashKnobs hash_knobs(const vdf_ctx *ctx)
+{
+    return vdf::HashKnobs{ctx->resize_mode, ctx->wavestream_knob, ctx->hash_no_persistent != 0, ctx->no_rowcrop, ctx->rowcrop_all, ctx->no_boxstream,
+                          ctx->no_smallcrop, ctx->lb_host_plan, ctx->no_lb_fused};
+}
+
+// mv null: the launch's clips name their vertical tables themselves (ROWCROP and box launches)
+vdf::MfmaResizeArgs resize_args(const vdf_ctx *ctx, const DeviceMfmaTable *mh, const DeviceMfmaTable *mv)
+{
+    vdf::MfmaResizeArgs a{};
+    a.bh = mh->operand.p;
+    a.bias_h = mh->bias.as<int32_t>();
+    a.prec_h = mh->host.precision;
+    a.n_kt = mh->host.n_tiles;
+    if (!mh->host.band_meta.empty()) {
+        a.band_meta = mh->meta.as<int32_t>();
+        a.band_stride = mh->host.band_stride;
     }
-    const int need_h = (w != VDF_DCT_SIZE), need_v = (h != VDF_DCT_SIZE);
+    if (mv) {
+        a.av = mv->operand.p;
+        a.bias_v = mv->bias.as<int32_t>();
+        a.prec_v = mv->host.precision;
+        a.n_rg = mv->host.n_tiles;
+    }
+    a.persistent_wgs_per_cu = ctx->hash_wgs_per_cu;
+    return a;
+}
+
+int dct_hash_of_small(vdf_ctx *ctx, const HashJob &j)
+{
+    VDF_HIP(ctx, vdf::launch_dct_hash(ctx->small.as<uint8_t>(), 4096, 256, j.n_clips, ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream));
+    return VDF_OK;
+}
+
+// scalar fixed-point resize (any coefficient range)
+int hash_scalar(vdf_ctx *ctx, const HashJob &j)
+{
+    const int need_h = (j.w != VDF_DCT_SIZE), need_v = (j.h != VDF_DCT_SIZE);
     int rc = VDF_OK;
-    const uint8_t *buf_end = d_frames + (n_clips - 1) * clip_stride + (VDF_DCT_SIZE - 1) * frame_stride + (size_t)w * h;
-    if (ctx->resize_mode != 1) {
-        // Resize on the matrix cores (exact i8 x i8 -> i32): small frames fuse the DCT into the same kernel.
-        // frames taller than two 64-row groups go to the per-frame kernel; its whole-line form is the default
-        // (round 5: except the wide, short ones that stream faster - resize_short_prefers_stream - where they are eligible to)
-        // (and the narrow ones of up to 256 rows that the tiled persistent kernel serves better than the stream kernels - resize_tall_prefers_tiled)
-        const bool fused = ctx->resize_mode == 3 ||
-                           (ctx->resize_mode == 0 && (h + 63) / 64 <= 2 &&
-                            !(vdf::resize_short_prefers_stream(w, h) &&
-                              vdf::resize_stream_eligible(d_frames, w, h, frame_stride, clip_stride, ctx->wavestream_knob))) ||
-                           (ctx->resize_mode == 0 && !ctx->hash_no_persistent && vdf::resize_tall_prefers_tiled(w, h));
-        // tightly packed frames stream linearly through LDS where that is the faster form (resize_stream_eligible)
-        bool streamed = !fused && (ctx->resize_mode == 0 || ctx->resize_mode == 5) &&
-                        vdf::resize_stream_eligible(d_frames, w, h, frame_stride, clip_stride, ctx->wavestream_knob);
-        DeviceMfmaTable *mh = nullptr;
-        if (streamed && vdf::resize_stream_wants_band(w, ctx->wavestream_knob)) {  // wide frames: the horizontal table in band form
-            mh = mfma_table(ctx, w, vdf::kMfmaLayoutHorizontalBand, stream, &rc);
-            if (rc) return rc;
-            if (!mh->host.ok) { streamed = false; mh = nullptr; }
-        }
-        // frames wider than the per-wave buffers (1920 columns): the K-split form, table in registers (measured against the
-        // whole-line kernel: 3840 wide 5.6 -> 6.7 TB/s, 2560 5.5 -> 6.2, 2000 3.6 -> 5.8, 2048 level)
-        const bool ksplit = !fused && ((ctx->resize_mode == 0 && !streamed && w > 1920) || ctx->resize_mode == 6) &&
-                            vdf::resize_ksplit_eligible(d_frames, w, h, frame_stride, clip_stride);
-        if (ksplit) { streamed = false; mh = nullptr; }
-        const bool wide = !fused && !streamed && !ksplit;
-        if (!mh) mh = mfma_table(ctx, w, vdf::kMfmaLayoutHorizontal, stream, &rc);
-        if (rc) return rc;
-        DeviceMfmaTable *mv = mfma_table(ctx, h, wide ? vdf::kMfmaLayoutVerticalWide : vdf::kMfmaLayoutVertical, stream, &rc);
-        if (rc) return rc;
-        if (mh->host.ok && mv->host.ok) {
-            vdf::MfmaResizeArgs a{};
-            a.bh = mh->operand.p;
-            a.av = mv->operand.p;
-            a.bias_h = mh->bias.as<int32_t>();
-            a.bias_v = mv->bias.as<int32_t>();
-            a.prec_h = mh->host.precision;
-            a.prec_v = mv->host.precision;
-            a.n_kt = mh->host.n_tiles;
-            a.n_rg = mv->host.n_tiles;
-            if (!mh->host.band_meta.empty()) {
-                a.band_meta = mh->meta.as<int32_t>();
-                a.band_stride = mh->host.band_stride;
-            }
-            a.no_persistent = ctx->hash_no_persistent;
-            a.persistent_wgs_per_cu = ctx->hash_wgs_per_cu;
-            a.wavestream_knob = ctx->wavestream_knob;
-            if (fused) {
-                VDF_HIP(ctx, vdf::launch_resize_dct_fused(d_frames, n_clips, w, h, frame_stride, clip_stride, buf_end, a,
-                                                          ctx->cos_table.as<double>(), d_out, d_dc, stream));
-                return VDF_OK;
-            }
-            VDF_HIP(ctx, ctx->small.reserve(n_clips * 4096));
-            if (ksplit) {
-                VDF_HIP(ctx, vdf::launch_resize_mfma_frames_ksplit(d_frames, n_clips, w, h, frame_stride, clip_stride, a,
-                                                                   ctx->small.as<uint8_t>(), stream));
-            } else if (streamed) {
-                VDF_HIP(ctx, vdf::launch_resize_mfma_frames_stream(d_frames, n_clips, w, h, frame_stride, clip_stride, a,
-                                                                   ctx->small.as<uint8_t>(), stream));
-            } else {
-                VDF_HIP(ctx, vdf::launch_resize_mfma_frames(d_frames, n_clips, w, h, frame_stride, clip_stride, buf_end, a,
-                                                            ctx->small.as<uint8_t>(), wide, stream));
-            }
-            VDF_HIP(ctx, vdf::launch_dct_hash(ctx->small.as<uint8_t>(), 4096, 256, n_clips,
-                                              ctx->cos_table.as<double>(), d_out, d_dc, stream));
-            return VDF_OK;
-        }
-        if (ctx->resize_mode != 0) return fail(ctx, VDF_E_BAD_DIMS, "coefficients do not fit the i8 split");
-    }
-    // scalar fixed-point fallback (any coefficient range)
-    DeviceAxisTable *th = need_h ? axis_table(ctx, w, stream, &rc) : nullptr;
+    DeviceAxisTable *th = need_h ? axis_table(ctx, j.w, j.stream, &rc) : nullptr;
     if (rc) return rc;
-    DeviceAxisTable *tv = need_v ? axis_table(ctx, h, stream, &rc) : nullptr;
+    DeviceAxisTable *tv = need_v ? axis_table(ctx, j.h, j.stream, &rc) : nullptr;
     if (rc) return rc;
     int32_t y_first = 0, tmp_rows = VDF_DCT_SIZE;
     if (need_v) {
@@ -701,13 +668,284 @@ int hash_device_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, ui
         tmp_rows = tv->host.start[VDF_DCT_SIZE - 1] + tv->host.size[VDF_DCT_SIZE - 1] - y_first;
     }
     if ((size_t)tmp_rows * 16 > 64 * 1024) return fail(ctx, VDF_E_BAD_DIMS, "frame height above 4096 is not supported by the scalar resize kernel");
-    VDF_HIP(ctx, ctx->small.reserve(n_clips * 4096));
-    VDF_HIP(ctx, vdf::launch_resize_generic(d_frames, n_clips, w, h, frame_stride, clip_stride, dev_view(th),
-                                            dev_view(tv), need_h, need_v, y_first, tmp_rows,
-                                            ctx->small.as<uint8_t>(), stream));
-    VDF_HIP(ctx, vdf::launch_dct_hash(ctx->small.as<uint8_t>(), 4096, 256, n_clips, ctx->cos_table.as<double>(),
-                                      d_out, d_dc, stream));
+    VDF_HIP(ctx, ctx->small.reserve(j.n_clips * 4096));
+    VDF_HIP(ctx, vdf::launch_resize_generic(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, dev_view(th), dev_view(tv), need_h, need_v,
+                                            y_first, tmp_rows, ctx->small.as<uint8_t>(), j.stream));
+    return dct_hash_of_small(ctx, j);
+}
+
+// Plan (resize_dispatch.h: plan_hash), fetch the tables the plan names, launch its route.
+int hash_launch(vdf_ctx *ctx, const HashJob &j)
+{
+    using vdf::HashRoute;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_cos_table(ctx, j.stream);
+    if (rc) return rc;
+    const vdf::HashKnobs knobs = hash_knobs(ctx);
+    vdf::HashPlan plan = vdf::plan_hash(j.call(), knobs);
+    DeviceMfmaTable *mh = nullptr, *mv = nullptr;
+    // a table that does not fit is what the plan could not know: plan again with that fact (the second one ends in kScalar or kRefused)
+    while (plan.route != HashRoute::kDirect16 && plan.route != HashRoute::kScalar && plan.route != HashRoute::kRefused) {
+        mh = mfma_table(ctx, j.w, plan.layout_h, j.stream, &rc);
+        if (rc) return rc;
+        if (!mh->host.ok && plan.layout_h == vdf::kMfmaLayoutHorizontalBand) { plan = vdf::plan_hash(j.call(), knobs, vdf::TableFit::kNoBand); continue; }
+        mv = mfma_table(ctx, j.h, plan.layout_v, j.stream, &rc);
+        if (rc) return rc;
+        if (mh->host.ok && mv->host.ok) break;
+        plan = vdf::plan_hash(j.call(), knobs, vdf::TableFit::kNoPlain);
+    }
+    uint8_t *small = nullptr;
+    if (plan.route == HashRoute::kChunkStream || plan.route == HashRoute::kWaveStream || plan.route == HashRoute::kKsplit || plan.route == HashRoute::kWholeLine) {
+        VDF_HIP(ctx, ctx->small.reserve(j.n_clips * 4096));
+        small = ctx->small.as<uint8_t>();
+    }
+    switch (plan.route) {
+    case HashRoute::kRefused: return fail(ctx, VDF_E_BAD_DIMS, "coefficients do not fit the i8 split");
+    case HashRoute::kScalar: return hash_scalar(ctx, j);
+    case HashRoute::kDirect16:
+        VDF_HIP(ctx, vdf::launch_dct_hash(j.d_frames, j.clip_stride, j.frame_stride, j.n_clips, ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream));
+        return VDF_OK;
+    case HashRoute::kPersistentOneTile:
+    case HashRoute::kTiled:
+    case HashRoute::kPerClipFused:
+        VDF_HIP(ctx, vdf::launch_resize_dct_fused(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, j.buf_end(), resize_args(ctx, mh, mv), plan,
+                                                  ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream));
+        return VDF_OK;
+    case HashRoute::kChunkStream:
+    case HashRoute::kWaveStream:
+        VDF_HIP(ctx, vdf::launch_resize_mfma_frames_stream(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, resize_args(ctx, mh, mv), plan, small, j.stream));
+        break;
+    case HashRoute::kKsplit:
+        VDF_HIP(ctx, vdf::launch_resize_mfma_frames_ksplit(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, resize_args(ctx, mh, mv), plan, small, j.stream));
+        break;
+    case HashRoute::kWholeLine:
+        VDF_HIP(ctx, vdf::launch_resize_mfma_frames(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, j.buf_end(), resize_args(ctx, mh, mv), small, j.stream));
+        break;
+    }
+    return dct_hash_of_small(ctx, j);
+}
+
+int hash_device_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w,
+                       uint32_t h, size_t frame_stride, size_t clip_stride, uint64_t *d_out, uint32_t *d_dc,
+                       hipStream_t stream)
+{
+    const HashJob all{d_frames, n_clips, w, h, frame_stride, clip_stride, d_out, d_dc, stream};
+    return checked_launches(ctx, all, frames_per_clip, [&](size_t c0, size_t n) { return hash_launch(ctx, all.clips(c0, n)); });
+}
+
+// The tables that the descriptors of one launch name, by (box size, axis): each is fetched, and gets its entry, where a box first asks for it.
+// Arrays over the sizes, not a map: 20 000 clips were 0.19 ms of host time through a map, with the GPU idle behind the wait for the boxes;
+// w + 1 and h + 1 slots are small at every supported size.
+struct LaunchTables {
+    int layout_h, layout_v;
+    std::vector<int32_t> at_h, at_v;            // [size] -> entry, -1 = not asked for yet
+    std::vector<const DeviceMfmaTable *> used;  // [entry]
+    LaunchTables(uint32_t w, uint32_t h, int lh, int lv) : layout_h(lh), layout_v(lv), at_h(w + 1, -1), at_v(h + 1, -1) {}
+    // -1: *rc is set, or (*rc == VDF_OK) the table does not fit the i8 split
+    int32_t entry(vdf_ctx *ctx, uint32_t size, bool vertical, hipStream_t stream, int *rc)
+    {
+        int32_t &at = (vertical ? at_v : at_h)[size];
+        if (at >= 0) return at;
+        const DeviceMfmaTable *t = mfma_table(ctx, size, vertical ? layout_v : layout_h, stream, rc);
+        if (*rc || !t->host.ok) return -1;
+        used.push_back(t);
+        return at = (int32_t)used.size() - 1;
+    }
+    vdf::CropTableEntry crop_entry(size_t i) const { return vdf::CropTableEntry{used[i]->operand.p, used[i]->bias.as<int32_t>(), used[i]->host.n_tiles, used[i]->host.precision}; }
+    vdf::CropStreamTable stream_entry(size_t i) const
+    {
+        const DeviceMfmaTable *t = used[i];
+        return vdf::CropStreamTable{t->operand.p, t->bias.as<int32_t>(), t->host.band_meta.empty() ? nullptr : t->meta.as<int32_t>(), t->host.n_tiles,
+                                    t->host.precision, t->host.band_stride, 0};
+    }
+};
+
+int no_split_table(vdf_ctx *ctx) { return fail(ctx, VDF_E_BAD_DIMS, "crop box size whose coefficients do not fit the i8 split"); }
+
+// Small frames: ONE pass over the boxes - check, table entries by box size, descriptors written straight into the pinned staging - then one
+// upload and one launch that resizes, transforms and hashes (resize_dct_hash_cropped_small_kernel).
+int hash_cropped_small(vdf_ctx *ctx, const HashJob &j, const uint32_t *crops)
+{
+    const uint32_t w = j.w, h = j.h;
+    const size_t nd = j.n_clips * sizeof(vdf::CropClipDesc), off = (nd + 63) & ~size_t(63);
+    if (!ctx->pin_desc.reserve(off + ((size_t)w + h + 2) * sizeof(vdf::CropTableEntry))) return fail(ctx, VDF_E_OOM, "host staging for the crop descriptors");
+    vdf::CropClipDesc *dsc = ctx->pin_desc.as<vdf::CropClipDesc>();
+    vdf::CropTableEntry *ent = reinterpret_cast<vdf::CropTableEntry *>(ctx->pin_desc.as<char>() + off);
+    LaunchTables tabs(w, h, vdf::kMfmaLayoutHorizontal, vdf::kMfmaLayoutVertical);
+    int rc = VDF_OK;
+    for (size_t c = 0; c < j.n_clips; c++) {
+        const uint32_t l = crops[4 * c], r = crops[4 * c + 1], t = crops[4 * c + 2], b = crops[4 * c + 3];
+        if ((uint64_t)l + r >= w || (uint64_t)t + b >= h) return fail(ctx, VDF_E_INVAL, "crop box leaves no pixels");  // crop.rs:21-22
+        const uint32_t bw = w - l - r, bh = h - t - b;
+        const int32_t ih = tabs.entry(ctx, bw, false, j.stream, &rc), iv = ih < 0 ? -1 : tabs.entry(ctx, bh, true, j.stream, &rc);
+        if (iv < 0) return rc ? rc : no_split_table(ctx);
+        dsc[c] = vdf::CropClipDesc{l, t, bw, bh, (uint32_t)ih, (uint32_t)iv, (uint32_t)c, 0u};
+    }
+    for (size_t i = 0; i < tabs.used.size(); i++) ent[i] = tabs.crop_entry(i);
+    if ((rc = upload(ctx, ctx->crop_desc2, dsc, nd, j.stream))) return rc;
+    if ((rc = upload(ctx, ctx->crop_tables2, ent, std::max<size_t>(tabs.used.size(), 1) * sizeof(vdf::CropTableEntry), j.stream))) return rc;
+    VDF_HIP(ctx, hipEventRecord(ctx->ev_mid, j.stream));
+    VDF_HIP(ctx, vdf::launch_resize_dct_cropped_small(j.d_frames, j.n_clips, w, j.frame_stride, j.clip_stride, j.buf_end(), ctx->crop_desc2.as<vdf::CropClipDesc>(),
+                                                      ctx->crop_tables2.as<vdf::CropTableEntry>(), ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream));
+    // the staging is read by the two copies: they must have run before the next call on this context rewrites it (the kernel stays queued)
+    VDF_HIP(ctx, hipEventSynchronize(ctx->ev_mid));
     return VDF_OK;
+}
+
+// The host descriptors of a planned cropped call (resize_dispatch.h: CropPlan), part by part.
+struct CropDescs {
+    const DeviceMfmaTable *rows_mh = nullptr;      // the ROWCROP launch's horizontal table
+    std::vector<const DeviceMfmaTable *> group_mh;  // each box launch's band table
+    std::vector<size_t> group_first;                // ... and its first entry of row_clips
+    std::vector<vdf::CropStreamClip> row_clips, gather_clips;  // the ROWCROP launch's clips, then every box launch's; the gather stream kernel's
+    std::vector<vdf::CropStreamTable> row_tables, gather_tables;
+    std::vector<vdf::CropClipDesc> line_clips;  // the whole-line cropped kernel's
+    std::vector<vdf::CropTableEntry> line_tables;
+};
+
+vdf::CropStreamClip stream_clip(const HashJob &j, const uint32_t *crops, uint32_t c)
+{
+    vdf::CropStreamClip q{};
+    q.x0 = crops[4 * c]; q.y0 = crops[4 * c + 2]; q.w = j.w - q.x0 - crops[4 * c + 1]; q.h = j.h - q.y0 - crops[4 * c + 3]; q.src_clip = c;
+    return q;
+}
+
+// Fetches the tables and builds the descriptors of every part.  *again: a table does not fit - what the plan could not know is noted in *fit,
+// and the caller plans again.
+int build_crop_descs(vdf_ctx *ctx, const HashJob &j, const uint32_t *crops, const vdf::CropPlan &plan, vdf::CropTableFit *fit, CropDescs *d, bool *again)
+{
+    int rc = VDF_OK;
+    *d = CropDescs();
+    *again = true;
+    if (plan.rows_kernel.route != vdf::HashRoute::kRefused) {
+        d->rows_mh = mfma_table(ctx, j.w, plan.rows_kernel.layout_h, j.stream, &rc);
+        if (rc) return rc;
+        if (!d->rows_mh->host.ok) { fit->rows_table = false; return VDF_OK; }
+    }
+    for (const vdf::CropBoxGroup &g : plan.groups) {
+        const DeviceMfmaTable *mh = mfma_table(ctx, g.box_w, vdf::kMfmaLayoutHorizontalBand, j.stream, &rc);
+        if (rc) return rc;
+        if (!mh->host.ok || !vdf::resize_wavestream_table_fits(g.waves, mh->host.band_stride)) { fit->ranges_without_table.push_back(vdf::crop_range_key(g.x0, g.box_w)); return VDF_OK; }
+        d->group_mh.push_back(mh);
+    }
+    // full-width boxes and the boxes of a column range: rows y0 .. y0 + h at the frame's pitch, a vertical table per box height
+    LaunchTables row_tabs(j.w, j.h, vdf::kMfmaLayoutHorizontal, vdf::kMfmaLayoutVertical);
+    const auto append_rows = [&](const std::vector<uint32_t> &ids) -> bool {
+        for (uint32_t c : ids) {
+            vdf::CropStreamClip q = stream_clip(j, crops, c);
+            q.wp = j.w;
+            const int32_t iv = row_tabs.entry(ctx, q.h, true, j.stream, &rc);
+            if (iv < 0) return false;
+            q.v_table = (uint32_t)iv;
+            d->row_clips.push_back(q);
+        }
+        return true;
+    };
+    bool rows_ok = append_rows(plan.rows);
+    for (const vdf::CropBoxGroup &g : plan.groups) {
+        d->group_first.push_back(d->row_clips.size());
+        rows_ok = rows_ok && append_rows(g.ids);
+    }
+    if (rc) return rc;
+    if (!rows_ok) { fit->height_tables = false; return VDF_OK; }
+    for (size_t i = 0; i < row_tabs.used.size(); i++) d->row_tables.push_back(row_tabs.stream_entry(i));
+    if (plan.rest_gather) {  // gathered boxes: LDS pitch and chunk geometry per box, the horizontal table in band form
+        LaunchTables tabs(j.w, j.h, vdf::kMfmaLayoutHorizontalBand, vdf::kMfmaLayoutVertical);
+        for (uint32_t c : plan.rest) {
+            vdf::CropStreamClip q = stream_clip(j, crops, c);
+            q.nb = vdf::resize_cropped_stream_blocks(q.w, q.x0, j.w, plan.gather_cls, &q.wp);
+            q.step_rows = 4096u / q.wp;
+            q.step_x = 4096u - q.step_rows * q.wp;
+            q.n_chunks = (q.h + 16 * q.nb - 1) / (16 * q.nb);
+            const int32_t ih = tabs.entry(ctx, q.w, false, j.stream, &rc), iv = ih < 0 ? -1 : tabs.entry(ctx, q.h, true, j.stream, &rc);
+            if (rc) return rc;
+            if (iv < 0) { fit->gather_tables = false; return VDF_OK; }
+            q.h_table = (uint32_t)ih; q.v_table = (uint32_t)iv;
+            d->gather_clips.push_back(q);
+        }
+        for (size_t i = 0; i < tabs.used.size(); i++) d->gather_tables.push_back(tabs.stream_entry(i));
+    } else {  // frames at least 1.5 windows wide read whole 128-byte lines (resize_row_quads)
+        LaunchTables tabs(j.w, j.h, vdf::kMfmaLayoutHorizontal, j.w >= 192 ? vdf::kMfmaLayoutVerticalWide : vdf::kMfmaLayoutVertical);
+        for (uint32_t c : plan.rest) {
+            const vdf::CropStreamClip q = stream_clip(j, crops, c);
+            const int32_t ih = tabs.entry(ctx, q.w, false, j.stream, &rc), iv = ih < 0 ? -1 : tabs.entry(ctx, q.h, true, j.stream, &rc);
+            if (iv < 0) return rc ? rc : no_split_table(ctx);
+            d->line_clips.push_back(vdf::CropClipDesc{q.x0, q.y0, q.w, q.h, (uint32_t)ih, (uint32_t)iv, c, 0u});
+        }
+        for (size_t i = 0; i < tabs.used.size(); i++) d->line_tables.push_back(tabs.crop_entry(i));
+    }
+    *again = false;
+    return VDF_OK;
+}
+
+template <class Clip, class Table>
+int upload_descs(vdf_ctx *ctx, const std::vector<Clip> &clips, const std::vector<Table> &tables, DevBuf &bd, DevBuf &bt, hipStream_t stream)
+{
+    int rc = upload(ctx, bd, clips.data(), clips.size() * sizeof(Clip), stream);
+    return rc ? rc : upload(ctx, bt, tables.data(), tables.size() * sizeof(Table), stream);
+}
+
+// Uploads the descriptors, launches every part, then dct_hash over the whole batch.
+int launch_crop_parts(vdf_ctx *ctx, const HashJob &j, const vdf::CropPlan &plan, const CropDescs &d)
+{
+    int rc = VDF_OK;
+    if (!d.row_clips.empty() && (rc = upload_descs(ctx, d.row_clips, d.row_tables, ctx->crop_desc, ctx->crop_tables, j.stream))) return rc;
+    if (plan.rest_gather) {
+        if ((rc = upload_descs(ctx, d.gather_clips, d.gather_tables, ctx->crop_desc2, ctx->crop_tables2, j.stream))) return rc;
+    } else if (!plan.rest.empty()) {
+        // through pinned staging (consumed by the time of the wait below): a descriptor per clip is 0.6 MB for 20 000 small clips
+        const size_t nd = d.line_clips.size() * sizeof(vdf::CropClipDesc), nt = d.line_tables.size() * sizeof(vdf::CropTableEntry), off = (nd + 63) & ~size_t(63);
+        if (!ctx->pin_desc.reserve(off + nt)) return fail(ctx, VDF_E_OOM, "host staging for the crop descriptors");
+        std::memcpy(ctx->pin_desc.p, d.line_clips.data(), nd);
+        std::memcpy(ctx->pin_desc.as<char>() + off, d.line_tables.data(), nt);
+        if ((rc = upload(ctx, ctx->crop_desc2, ctx->pin_desc.p, nd, j.stream))) return rc;
+        if ((rc = upload(ctx, ctx->crop_tables2, ctx->pin_desc.as<char>() + off, nt, j.stream))) return rc;
+    }
+    VDF_HIP(ctx, hipStreamSynchronize(j.stream));  // the host vectors go out of scope with this call
+    VDF_HIP(ctx, ctx->small.reserve(j.n_clips * 4096));
+    uint8_t *small = ctx->small.as<uint8_t>();
+    const vdf::CropStreamClip *row_clips = ctx->crop_desc.as<vdf::CropStreamClip>();
+    const vdf::CropStreamTable *row_tables = ctx->crop_tables.as<vdf::CropStreamTable>();
+    if (plan.rows_kernel.route == vdf::HashRoute::kKsplit)
+        VDF_HIP(ctx, vdf::launch_resize_mfma_frames_ksplit(j.d_frames, plan.rows.size(), j.w, j.h, j.frame_stride, j.clip_stride, resize_args(ctx, d.rows_mh, nullptr),
+                                                           plan.rows_kernel, small, j.stream, row_clips, row_tables));
+    else if (!plan.rows.empty())
+        VDF_HIP(ctx, vdf::launch_resize_mfma_frames_stream(j.d_frames, plan.rows.size(), j.w, j.h, j.frame_stride, j.clip_stride, resize_args(ctx, d.rows_mh, nullptr),
+                                                           plan.rows_kernel, small, j.stream, row_clips, row_tables));
+    for (size_t i = 0; i < plan.groups.size(); i++) {
+        const vdf::CropBoxGroup &g = plan.groups[i];
+        VDF_HIP(ctx, vdf::launch_resize_mfma_box_wavestream(j.d_frames, g.ids.size(), j.w, j.h, j.frame_stride, j.clip_stride, resize_args(ctx, d.group_mh[i], nullptr),
+                                                            g.x0, g.box_w, g.waves, row_clips + d.group_first[i], row_tables, small, j.stream));
+    }
+    if (plan.rest_gather)
+        VDF_HIP(ctx, vdf::launch_resize_mfma_cropped_stream(j.d_frames, plan.rest.size(), j.w, j.h, j.frame_stride, j.clip_stride, ctx->crop_desc2.as<vdf::CropStreamClip>(),
+                                                            ctx->crop_tables2.as<vdf::CropStreamTable>(), plan.gather_cls, plan.gather_shift, small, j.stream));
+    else if (!plan.rest.empty())
+        VDF_HIP(ctx, vdf::launch_resize_mfma_cropped(j.d_frames, plan.rest.size(), j.w, j.frame_stride, j.clip_stride, j.buf_end(), ctx->crop_desc2.as<vdf::CropClipDesc>(),
+                                                     ctx->crop_tables2.as<vdf::CropTableEntry>(), small, j.w >= 192, j.stream));
+    return dct_hash_of_small(ctx, j);
+}
+
+int hash_cropped_launch(vdf_ctx *ctx, const HashJob &j, const uint32_t *crops)
+{
+    bool any = false;
+    if (crops)
+        for (size_t i = 0; i < j.n_clips * 4 && !any; i++) any = crops[i] != 0;
+    if (!any) return hash_launch(ctx, j);  // the common case, before any planning: the fused / persistent kernels
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_cos_table(ctx, j.stream);
+    if (rc) return rc;
+    const vdf::HashKnobs knobs = hash_knobs(ctx);
+    vdf::CropTableFit fit;
+    vdf::CropPlan plan;
+    CropDescs descs;
+    for (bool again = true; again;) {  // (every further round has one more fact in `fit`, and there are finitely many)
+        plan = vdf::plan_cropped(j.call(), knobs, crops, fit);
+        if (plan.kind == vdf::CropPlan::kBadBox) return fail(ctx, VDF_E_INVAL, "crop box leaves no pixels");
+        if (plan.kind == vdf::CropPlan::kSmall) return hash_cropped_small(ctx, j, crops);
+        if ((rc = build_crop_descs(ctx, j, crops, plan, &fit, &descs, &again))) return rc;
+    }
+    return launch_crop_parts(ctx, j, plan, descs);
 }
 
 // Hash clips whose crop boxes (HOST array [n_clips][4] = left, right, top, bottom; null = no crop) are read in place.
@@ -715,393 +953,52 @@ int hash_cropped_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, u
                         uint32_t h, size_t frame_stride, size_t clip_stride, const uint32_t *crops, uint64_t *d_out,
                         uint32_t *d_dc, hipStream_t stream)
 {
-    if (n_clips > kMaxClipsPerLaunch) {
-        for (size_t c0 = 0; c0 < n_clips; c0 += kMaxClipsPerLaunch) {
-            const size_t nb = std::min(kMaxClipsPerLaunch, n_clips - c0);
-            int rc = hash_cropped_locked(ctx, d_frames + c0 * clip_stride, nb, frames_per_clip, w, h, frame_stride,
-                                         clip_stride, crops ? crops + 4 * c0 : nullptr, d_out + c0 * VDF_HASH_WORDS,
-                                         d_dc ? d_dc + c0 : nullptr, stream);
-            if (rc) return rc;
-        }
-        return VDF_OK;
-    }
-    bool any = false;
-    if (crops)
-        for (size_t i = 0; i < n_clips * 4 && !any; i++) any = crops[i] != 0;
-    if (!any)  // the common case: the fused / persistent kernels
-        return hash_device_locked(ctx, d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, d_out, d_dc, stream);
-    if (frames_per_clip < VDF_DCT_SIZE) return fail(ctx, VDF_E_NOT_ENOUGH_FRAMES, "fewer than 16 frames per clip");
-    if (w == 0 || h == 0) return fail(ctx, VDF_E_BAD_DIMS, "zero frame dimension");
-    if (frame_stride < (size_t)w * h) return fail(ctx, VDF_E_INVAL, "frame_stride smaller than a frame");
-    if (!d_frames || !d_out) return fail(ctx, VDF_E_INVAL, "null pointer");
-    if (n_clips > 0x7FFFFFFull) return fail(ctx, VDF_E_INVAL, "too many clips in one call");
-    VDF_HIP(ctx, hipSetDevice(ctx->device));
-    {
-        int rc0 = ensure_cos_table(ctx, stream);
-        if (rc0) return rc0;
-    }
-    // Three kernels read crop boxes in place; a call is dealt out between the first two by box shape, clip by clip (each entry of a
-    // launch names its clip of the batch: CropStreamClip::src_clip), and one dct_hash launch follows over the whole batch:
-    //  * ROWCROP stream kernels - full-width boxes (top / bottom bars only: a 2.39 : 1 film in a 16 : 9 frame, the commonest letterbox;
-    //    clips without bars among them are boxes of the whole frame).  The box is a contiguous range of rows at the frame's own pitch,
-    //    so it streams like a shorter frame: the kernel the uncropped call would take at that width (per-wave, chunk or K-split form)
-    //    with a per-clip first row, height and vertical table.
-    //  * the cropped stream kernel - boxes with side bars (pillarboxed clips): rows x0 .. x0 + w of the box go through LDS by gather
-    //    DMA.  Also full-width boxes where no ROWCROP kernel applies and the pitch is not a multiple of the 128-byte line.
-    //    Measured, detect + crop + hash against the whole-line kernel below: 854x480 1.68 -> 1.24 ms per 1000 clips, 720x576 1.42 -> 1.14,
-    //    426x240 x4000 1.85 -> 1.33, 1366x768 x500 2.19 -> 1.95; pillarboxed 1920x1080 x1000 crop + hash 7.7 -> 5.5 ms, 1280x720 x2000
-    //    6.4 -> 3.9, 1536x864 4.5 -> 2.9, 640x360 x4000 3.4 -> 2.5; 1024 wide 3.5 -> 3.8: stays (gpurun_out/r03pb).
-    //  * the whole-line cropped kernel (below) - everything else: misaligned buffers, frames that do not end on 16 bytes, short frames,
-    //    boxes whose tables do not fit the i8 split, VDF_RESIZE_MODE=4.
-    const bool tall = (h + 63) / 64 > 2, ends16 = ((uint64_t)w * h) % 16 == 0 && (uint64_t)w * h < (1ull << 31);
-    // small frames (round 5): one workgroup per CLIP, a wave per four frames, resize + DCT (resize_dct_hash_cropped_small_kernel) - plain vertical layout
-    const bool small_crop = !tall && w <= 256 && ctx->resize_mode == 0 && !ctx->no_smallcrop;
-    if (small_crop) {
-        // Small frames: ONE pass over the boxes - check, table entries by box size (arrays, not a map: 20 000 clips were 0.19 ms of host time in
-        // the general plan below, with the GPU idle behind the wait for the boxes), descriptors written straight into the pinned staging -
-        // then one upload and one launch that resizes, transforms and hashes (resize_dct_hash_cropped_small_kernel).
-        const size_t nd = n_clips * sizeof(vdf::CropClipDesc), off = (nd + 63) & ~size_t(63);
-        if (!ctx->pin_desc.reserve(off + ((size_t)w + h + 2) * sizeof(vdf::CropTableEntry))) return fail(ctx, VDF_E_OOM, "host staging for the crop descriptors");
-        vdf::CropClipDesc *dsc = ctx->pin_desc.as<vdf::CropClipDesc>();
-        vdf::CropTableEntry *ent = reinterpret_cast<vdf::CropTableEntry *>(ctx->pin_desc.as<char>() + off);
-        std::vector<int32_t> at_h(w + 1, -1), at_v(h + 1, -1);
-        uint32_t n_ent = 0;
-        int rc = VDF_OK;
-        auto entry = [&](uint32_t size, bool vertical) -> int32_t {
-            DeviceMfmaTable *t = mfma_table(ctx, size, vertical ? vdf::kMfmaLayoutVertical : vdf::kMfmaLayoutHorizontal, stream, &rc);
-            if (rc) return -1;
-            if (!t->host.ok) { rc = fail(ctx, VDF_E_BAD_DIMS, "crop box size whose coefficients do not fit the i8 split"); return -1; }
-            ent[n_ent] = vdf::CropTableEntry{t->operand.p, t->bias.as<int32_t>(), t->host.n_tiles, t->host.precision};
-            return (int32_t)n_ent++;
-        };
-        for (size_t c = 0; c < n_clips; c++) {
-            const uint32_t l = crops[4 * c], r = crops[4 * c + 1], t = crops[4 * c + 2], b = crops[4 * c + 3];
-            if ((uint64_t)l + r >= w || (uint64_t)t + b >= h) return fail(ctx, VDF_E_INVAL, "crop box leaves no pixels");  // crop.rs:21-22
-            const uint32_t bw = w - l - r, bh = h - t - b;
-            if (at_h[bw] < 0 && (at_h[bw] = entry(bw, false)) < 0) return rc;
-            if (at_v[bh] < 0 && (at_v[bh] = entry(bh, true)) < 0) return rc;
-            dsc[c] = vdf::CropClipDesc{l, t, bw, bh, (uint32_t)at_h[bw], (uint32_t)at_v[bh], (uint32_t)c, 0u};
-        }
-        if ((rc = upload(ctx, ctx->crop_desc2, dsc, nd, stream))) return rc;
-        if ((rc = upload(ctx, ctx->crop_tables2, ent, std::max<size_t>(n_ent, 1) * sizeof(vdf::CropTableEntry), stream))) return rc;
-        VDF_HIP(ctx, hipEventRecord(ctx->ev_mid, stream));
-        const uint8_t *buf_end = d_frames + (n_clips - 1) * clip_stride + (VDF_DCT_SIZE - 1) * frame_stride + (size_t)w * h;
-        VDF_HIP(ctx, vdf::launch_resize_dct_cropped_small(d_frames, n_clips, w, frame_stride, clip_stride, buf_end, ctx->crop_desc2.as<vdf::CropClipDesc>(),
-                                                          ctx->crop_tables2.as<vdf::CropTableEntry>(), ctx->cos_table.as<double>(), d_out, d_dc, stream));
-        // the staging is read by the two copies: they must have run before the next call on this context rewrites it (the kernel stays queued)
-        VDF_HIP(ctx, hipEventSynchronize(ctx->ev_mid));
-        return VDF_OK;
-    }
-    std::vector<uint32_t> rows_clips, side_clips;  // by box shape
-    for (size_t c = 0; c < n_clips; c++) {
-        const uint32_t l = crops[4 * c], r = crops[4 * c + 1], t = crops[4 * c + 2], b = crops[4 * c + 3];
-        if ((uint64_t)l + r >= w || (uint64_t)t + b >= h) return fail(ctx, VDF_E_INVAL, "crop box leaves no pixels");  // crop.rs:21-22
-        (l == 0 && r == 0 ? rows_clips : side_clips).push_back((uint32_t)c);
-    }
-    // -- can the full-width boxes take a ROWCROP kernel, and which?
-    bool row_stream = false, row_ksplit = false, row_band = false;
-    DeviceMfmaTable *row_mh = nullptr;
-    if (ctx->resize_mode == 0 && tall && !rows_clips.empty() && (vdf::resize_rowcrop_streams(w) || ctx->rowcrop_all) && !ctx->no_rowcrop) {
-        row_stream = vdf::resize_stream_eligible(d_frames, w, h, frame_stride, clip_stride, ctx->wavestream_knob);
-        row_band = row_stream && vdf::resize_stream_wants_band(w, ctx->wavestream_knob);
-        row_ksplit = !row_stream && w > 1920 && vdf::resize_ksplit_eligible(d_frames, w, h, frame_stride, clip_stride);
-        if (row_stream || row_ksplit) {
-            int rc = VDF_OK;
-            row_mh = mfma_table(ctx, w, row_band ? vdf::kMfmaLayoutHorizontalBand : vdf::kMfmaLayoutHorizontal, stream, &rc);
-            if (rc) return rc;
-            if (!row_mh->host.ok) row_mh = nullptr;
-        }
-    }
-    // -- can boxes take the cropped stream kernel?
-    int stream_cls = 0;
-    const bool crop_stream_ok = tall && ends16 && (((uintptr_t)d_frames | frame_stride | clip_stride) & 3) == 0 &&
-                                (ctx->resize_mode == 0 || ctx->resize_mode == 5) && vdf::resize_cropped_stream_class(w, &stream_cls);
-    // descriptors of a ROWCROP launch over `ids`; false: some box's vertical table does not fit the i8 split
-    std::vector<vdf::CropStreamClip> rsc, ssc;
-    std::vector<vdf::CropStreamTable> rst, sst;
-    std::map<uint32_t, uint32_t> vindex;  // box height -> entry of rst
-    auto append_rows = [&](const std::vector<uint32_t> &ids, int *rc) -> bool {  // (appends: a call may hold several ROWCROP launches)
-        const size_t first = rsc.size();
-        rsc.resize(first + ids.size(), vdf::CropStreamClip{});
-        for (size_t i = 0; i < ids.size(); i++) {
-            const uint32_t c = ids[i], t = crops[4 * c + 2], b = crops[4 * c + 3];
-            vdf::CropStreamClip &q = rsc[first + i];
-            q.x0 = crops[4 * c]; q.y0 = t; q.w = w - crops[4 * c] - crops[4 * c + 1]; q.h = h - t - b; q.wp = w; q.src_clip = c;
-            auto it = vindex.find(q.h);
-            if (it == vindex.end()) {
-                DeviceMfmaTable *tv = mfma_table(ctx, q.h, vdf::kMfmaLayoutVertical, stream, rc);
-                if (*rc || !tv->host.ok) return false;
-                rst.push_back(vdf::CropStreamTable{tv->operand.p, tv->bias.as<int32_t>(), nullptr, tv->host.n_tiles, tv->host.precision, 0, 0});
-                it = vindex.emplace(q.h, (uint32_t)rst.size() - 1).first;
-            }
-            q.v_table = it->second;
-        }
-        return true;
-    };
-    // descriptors of a cropped-stream launch over `ids`; false: a box does not fit the kernel (tables, blocks per chunk)
-    bool need_shift = (w & 3u) != 0;
-    auto build_stream = [&](const std::vector<uint32_t> &ids, int *rc) -> bool {
-        std::map<uint64_t, uint32_t> sindex;  // (size * 2 + vertical) -> entry
-        ssc.assign(ids.size(), vdf::CropStreamClip{});
-        sst.clear();
-        auto stream_entry = [&](uint32_t size, bool vertical, uint32_t *at) -> bool {
-            const uint64_t key = (uint64_t)size * 2 + (vertical ? 1 : 0);
-            auto it = sindex.find(key);
-            if (it != sindex.end()) { *at = it->second; return true; }
-            DeviceMfmaTable *t = mfma_table(ctx, size, vertical ? vdf::kMfmaLayoutVertical : vdf::kMfmaLayoutHorizontalBand, stream, rc);
-            if (*rc || !t->host.ok) return false;
-            sst.push_back(vdf::CropStreamTable{t->operand.p, t->bias.as<int32_t>(), vertical ? nullptr : t->meta.as<int32_t>(), t->host.n_tiles,
-                                               t->host.precision, t->host.band_stride, 0});
-            *at = sindex[key] = (uint32_t)sst.size() - 1;
-            return true;
-        };
-        for (size_t i = 0; i < ids.size(); i++) {
-            const uint32_t c = ids[i], l = crops[4 * c], r = crops[4 * c + 1], t = crops[4 * c + 2], b = crops[4 * c + 3];
-            vdf::CropStreamClip &q = ssc[i];
-            q.x0 = l; q.y0 = t; q.w = w - l - r; q.h = h - t - b; q.src_clip = c;
-            q.nb = vdf::resize_cropped_stream_blocks(q.w, q.x0, w, stream_cls, &q.wp);
-            need_shift = need_shift || (q.x0 & 3u) != 0;
-            if (q.nb == 0 || (q.nb < 2 && q.h > 16)) return false;  // one block per chunk would leave three of the four waves idle
-            q.step_rows = 4096u / q.wp;
-            q.step_x = 4096u - q.step_rows * q.wp;
-            q.n_chunks = (q.h + 16 * q.nb - 1) / (16 * q.nb);
-            if (!stream_entry(q.w, false, &q.h_table) || !stream_entry(q.h, true, &q.v_table)) return false;
-        }
-        return true;
-    };
-    auto upload_desc = [&](const std::vector<vdf::CropStreamClip> &sc, const std::vector<vdf::CropStreamTable> &st, DevBuf &bd, DevBuf &bt) -> int {
-        int rc = upload(ctx, bd, sc.data(), sc.size() * sizeof(vdf::CropStreamClip), stream);
-        if (rc == VDF_OK) rc = upload(ctx, bt, st.data(), st.size() * sizeof(vdf::CropStreamTable), stream);
-        return rc;
-    };
-    auto launch_rows = [&](size_t first, size_t n_sub, DevBuf &bd, DevBuf &bt) -> int {
-        vdf::MfmaResizeArgs a{};
-        a.bh = row_mh->operand.p;
-        a.bias_h = row_mh->bias.as<int32_t>();
-        a.prec_h = row_mh->host.precision;
-        a.n_kt = row_mh->host.n_tiles;
-        a.wavestream_knob = ctx->wavestream_knob;
-        if (row_band) {
-            a.band_meta = row_mh->meta.as<int32_t>();
-            a.band_stride = row_mh->host.band_stride;
-        }
-        if (row_ksplit)
-            VDF_HIP(ctx, vdf::launch_resize_mfma_frames_ksplit(d_frames, n_sub, w, h, frame_stride, clip_stride, a, ctx->small.as<uint8_t>(), stream,
-                                                               bd.as<vdf::CropStreamClip>() + first, bt.as<vdf::CropStreamTable>()));
-        else
-            VDF_HIP(ctx, vdf::launch_resize_mfma_frames_stream(d_frames, n_sub, w, h, frame_stride, clip_stride, a, ctx->small.as<uint8_t>(), stream,
-                                                               bd.as<vdf::CropStreamClip>() + first, bt.as<vdf::CropStreamTable>()));
-        return VDF_OK;
-    };
-    // boxes with side bars that share their column range: the per-wave kernel gathers the box (one launch per distinct range)
-    struct BoxGroup { uint32_t x0, bw; std::vector<uint32_t> ids; DeviceMfmaTable *mh; size_t first; };
-    auto launch_box = [&](const BoxGroup &g, DevBuf &bd, DevBuf &bt) -> int {
-        vdf::MfmaResizeArgs a{};
-        a.bh = g.mh->operand.p;
-        a.bias_h = g.mh->bias.as<int32_t>();
-        a.prec_h = g.mh->host.precision;
-        a.n_kt = g.mh->host.n_tiles;
-        a.band_meta = g.mh->meta.as<int32_t>();
-        a.band_stride = g.mh->host.band_stride;
-        a.wavestream_knob = ctx->wavestream_knob;
-        VDF_HIP(ctx, vdf::launch_resize_mfma_box_wavestream(d_frames, g.ids.size(), w, h, frame_stride, clip_stride, a, g.x0, g.bw,
-                                                            bd.as<vdf::CropStreamClip>() + g.first, bt.as<vdf::CropStreamTable>(),
-                                                            ctx->small.as<uint8_t>(), stream));
-        return VDF_OK;
-    };
-    auto launch_stream = [&](size_t n_sub, DevBuf &bd, DevBuf &bt) -> int {
-        VDF_HIP(ctx, vdf::launch_resize_mfma_cropped_stream(d_frames, n_sub, w, h, frame_stride, clip_stride, bd.as<vdf::CropStreamClip>(),
-                                                            bt.as<vdf::CropStreamTable>(), stream_cls, need_shift, ctx->small.as<uint8_t>(), stream));
-        return VDF_OK;
-    };
-    auto uploads_done = [&]() -> int {
-        VDF_HIP(ctx, hipStreamSynchronize(stream));  // the host vectors go out of scope with this call
-        VDF_HIP(ctx, ctx->small.reserve(n_clips * 4096));
-        return VDF_OK;
-    };
-    auto finish = [&]() -> int {
-        VDF_HIP(ctx, vdf::launch_dct_hash(ctx->small.as<uint8_t>(), 4096, 256, n_clips, ctx->cos_table.as<double>(), d_out, d_dc, stream));
-        return VDF_OK;
-    };
-    // -- the whole-line cropped kernel, over `ids` (all clips, or the side-bar boxes of a mixed call whose full-width boxes stream)
-    std::vector<vdf::CropClipDesc> desc;
-    std::vector<vdf::CropTableEntry> entries;
-    const bool wide = w >= 192;  // frames at least 1.5 windows wide read whole 128-byte lines (resize_row_quads)
-    auto build_lines = [&](const std::vector<uint32_t> &ids, int *rc) -> bool {
-        std::map<uint64_t, uint32_t> index;  // (size * 2 + vertical) -> entry
-        desc.assign(ids.size(), vdf::CropClipDesc{});
-        entries.clear();
-        auto entry_for = [&](uint32_t size, bool vertical, uint32_t *at) -> bool {
-            const uint64_t key = (uint64_t)size * 2 + (vertical ? 1 : 0);
-            auto it = index.find(key);
-            if (it != index.end()) { *at = it->second; return true; }
-            DeviceMfmaTable *t = mfma_table(ctx, size, !vertical ? vdf::kMfmaLayoutHorizontal : wide ? vdf::kMfmaLayoutVerticalWide : vdf::kMfmaLayoutVertical, stream, rc);
-            if (*rc) return false;
-            if (!t->host.ok) { *rc = fail(ctx, VDF_E_BAD_DIMS, "crop box size whose coefficients do not fit the i8 split"); return false; }
-            entries.push_back(vdf::CropTableEntry{t->operand.p, t->bias.as<int32_t>(), t->host.n_tiles, t->host.precision});
-            *at = index[key] = (uint32_t)entries.size() - 1;
-            return true;
-        };
-        for (size_t i = 0; i < ids.size(); i++) {
-            const uint32_t c = ids[i], l = crops[4 * c], r = crops[4 * c + 1], t = crops[4 * c + 2], b = crops[4 * c + 3];
-            vdf::CropClipDesc &q = desc[i];
-            q.x0 = l; q.y0 = t; q.w = w - l - r; q.h = h - t - b; q.src_clip = c;
-            if (!entry_for(q.w, false, &q.h_table) || !entry_for(q.h, true, &q.v_table)) return false;
-        }
-        return true;
-    };
-    const uint8_t *buf_end = d_frames + (n_clips - 1) * clip_stride + (VDF_DCT_SIZE - 1) * frame_stride + (size_t)w * h;
-    auto launch_lines = [&](size_t n_sub, DevBuf &bd, DevBuf &bt) -> int {
-        VDF_HIP(ctx, vdf::launch_resize_mfma_cropped(d_frames, n_sub, w, frame_stride, clip_stride, buf_end, bd.as<vdf::CropClipDesc>(),
-                                                     bt.as<vdf::CropTableEntry>(), ctx->small.as<uint8_t>(), wide, stream));
-        return VDF_OK;
-    };
-    auto upload_lines = [&](DevBuf &bd, DevBuf &bt) -> int {
-        // through pinned staging (consumed by the time uploads_done() returns): a descriptor per clip is 0.6 MB for 20 000 small clips
-        const size_t nd = desc.size() * sizeof(vdf::CropClipDesc), nt = entries.size() * sizeof(vdf::CropTableEntry), off = (nd + 63) & ~size_t(63);
-        if (!ctx->pin_desc.reserve(off + nt)) return fail(ctx, VDF_E_OOM, "host staging for the crop descriptors");
-        std::memcpy(ctx->pin_desc.p, desc.data(), nd);
-        std::memcpy(ctx->pin_desc.as<char>() + off, entries.data(), nt);
-        int rc = upload(ctx, bd, ctx->pin_desc.p, nd, stream);
-        if (rc == VDF_OK) rc = upload(ctx, bt, ctx->pin_desc.as<char>() + off, nt, stream);
-        return rc;
-    };
-    // ---- the plan: who goes where
-    int rc = VDF_OK;
-    std::vector<uint32_t> rows_part, rest;
-    (row_mh ? rows_part : rest) = rows_clips;
-    std::vector<BoxGroup> boxes;
-    if (ctx->resize_mode == 0 && tall && ends16 && (((uintptr_t)d_frames | frame_stride | clip_stride) & 15) == 0 && !side_clips.empty() &&
-        !ctx->no_boxstream && !ctx->no_rowcrop) {
-        std::map<uint64_t, size_t> by_range;  // (x0, width) -> group
-        std::vector<BoxGroup> cand;
-        for (uint32_t c : side_clips) {
-            const uint32_t l = crops[4 * c], bw = w - l - crops[4 * c + 1];
-            auto it = by_range.find(((uint64_t)l << 32) | bw);
-            if (it == by_range.end()) {
-                it = by_range.emplace(((uint64_t)l << 32) | bw, cand.size()).first;
-                cand.push_back(BoxGroup{l, bw, {}, nullptr, 0});
-            }
-            cand[it->second].ids.push_back(c);
-        }
-        for (BoxGroup &g : cand) {
-            const int nw = vdf::resize_wavestream_waves_box(w, g.x0, g.bw, ctx->wavestream_knob);
-            // (a launch per range: ranges shared by fewer than four clips - a launch would leave most CUs idle - and the ranges beyond sixteen
-            // are left to the gather kernel)
-            if (nw && g.ids.size() >= 4 && boxes.size() < 16) {
-                g.mh = mfma_table(ctx, g.bw, vdf::kMfmaLayoutHorizontalBand, stream, &rc);
-                if (rc) return rc;
-                if (g.mh->host.ok && vdf::resize_wavestream_table_fits(nw, g.mh->host.band_stride)) { boxes.push_back(std::move(g)); continue; }
-            }
-            rest.insert(rest.end(), g.ids.begin(), g.ids.end());
-        }
-    } else {
-        rest.insert(rest.end(), side_clips.begin(), side_clips.end());
-    }
-    bool planned = !rows_part.empty() || !boxes.empty();
-    if (planned) {
-        planned = append_rows(rows_part, &rc);
-        for (BoxGroup &g : boxes) {
-            g.first = rsc.size();
-            planned = planned && append_rows(g.ids, &rc);
-        }
-        if (rc) return rc;
-    }
-    if (!planned) {  // nothing streams per clip: the whole call through one general kernel
-        rest.resize(n_clips);
-        for (size_t c = 0; c < n_clips; c++) rest[c] = (uint32_t)c;
-        rows_part.clear();
-        boxes.clear();
-    }
-    // the general kernel for the rest: the cropped stream kernel for side-bar boxes at every pitch but 1024 and for full-width boxes where the
-    // pitch is not line-aligned (measured above), else the whole-line kernel
-    bool rest_stream = false;
-    if (!rest.empty()) {
-        bool rest_has_side = false;
-        for (uint32_t c : rest) rest_has_side = rest_has_side || crops[4 * c] != 0 || crops[4 * c + 1] != 0;
-        if (crop_stream_ok && (ctx->resize_mode == 5 || (rest_has_side ? w != 1024 : w % 128 != 0))) rest_stream = build_stream(rest, &rc);
-        if (rc) return rc;
-        if (!rest_stream && !build_lines(rest, &rc)) return rc ? rc : fail(ctx, VDF_E_BAD_DIMS, "crop box");
-    }
-    if (planned && (rc = upload_desc(rsc, rst, ctx->crop_desc, ctx->crop_tables))) return rc;
-    if (!rest.empty() && (rc = rest_stream ? upload_desc(ssc, sst, ctx->crop_desc2, ctx->crop_tables2) : upload_lines(ctx->crop_desc2, ctx->crop_tables2))) return rc;
-    if ((rc = uploads_done())) return rc;
-    if (!rows_part.empty() && (rc = launch_rows(0, rows_part.size(), ctx->crop_desc, ctx->crop_tables))) return rc;
-    for (const BoxGroup &g : boxes)
-        if ((rc = launch_box(g, ctx->crop_desc, ctx->crop_tables))) return rc;
-    if (!rest.empty() && (rc = rest_stream ? launch_stream(rest.size(), ctx->crop_desc2, ctx->crop_tables2) : launch_lines(rest.size(), ctx->crop_desc2, ctx->crop_tables2)))
-        return rc;
-    return finish();
+    const HashJob all{d_frames, n_clips, w, h, frame_stride, clip_stride, d_out, d_dc, stream};
+    return checked_launches(ctx, all, frames_per_clip, [&](size_t c0, size_t n) { return hash_cropped_launch(ctx, all.clips(c0, n), crops ? crops + 4 * c0 : nullptr); });
 }
 
-int letterbox_hash_device_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip,
-                                 uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride, uint64_t *d_out,
-                                 uint32_t *d_dc, uint32_t *out_crops, hipStream_t stream, uint32_t *d_out_crops)
+// Small frames: the boxes stay on the device.  No copy to the host, no wait, no host loop over the clips between the launches; out_crops is
+// filled by one copy queued behind them and waited for at the END of the call (d_out_crops: no wait at all).
+int letterbox_small(vdf_ctx *ctx, const HashJob &j, uint32_t frames_per_clip, const vdf::LetterboxPlan &plan, const BoxTableSet *set, uint32_t *out_crops,
+                    uint32_t *d_crops)
 {
-    if (frames_per_clip < VDF_DCT_SIZE) return fail(ctx, VDF_E_NOT_ENOUGH_FRAMES, "fewer than 16 frames per clip");
-    if (w == 0 || h == 0) return fail(ctx, VDF_E_BAD_DIMS, "zero frame dimension");
-    if (frame_stride < (size_t)w * h) return fail(ctx, VDF_E_INVAL, "frame_stride smaller than a frame");
-    if (n_clips == 0) return VDF_OK;
-    if (!d_frames || !d_out) return fail(ctx, VDF_E_INVAL, "null pointer");
-    if (n_clips > kMaxClipsPerLaunch) {
-        for (size_t c0 = 0; c0 < n_clips; c0 += kMaxClipsPerLaunch) {
-            const size_t nb = std::min(kMaxClipsPerLaunch, n_clips - c0);
-            int rc = letterbox_hash_device_locked(ctx, d_frames + c0 * clip_stride, nb, frames_per_clip, w, h,
-                                                  frame_stride, clip_stride, d_out + c0 * VDF_HASH_WORDS,
-                                                  d_dc ? d_dc + c0 : nullptr, out_crops ? out_crops + 4 * c0 : nullptr,
-                                                  stream, d_out_crops ? d_out_crops + 4 * c0 : nullptr);
-            if (rc) return rc;
-        }
-        return VDF_OK;
+    const size_t n_fused = j.n_clips - plan.n_tail;
+    if (n_fused)
+        VDF_HIP(ctx, vdf::launch_letterbox_hash_small(j.d_frames, n_fused, j.w, j.h, j.frame_stride, j.clip_stride, set->blob.p, ctx->cos_table.as<double>(),
+                                                      j.d_out, j.d_dc, d_crops, ctx->hash_wgs_per_cu_set ? ctx->hash_wgs_per_cu : 0, j.stream));
+    if (plan.n_tail) {
+        const HashJob tail = j.clips(n_fused, plan.n_tail);
+        VDF_HIP(ctx, ctx->crop_work.reserve(vdf::letterbox_work_bytes(tail.n_clips, frames_per_clip)));
+        VDF_HIP(ctx, vdf::launch_letterbox(tail.d_frames, tail.n_clips, frames_per_clip, j.w, j.h, j.frame_stride, j.clip_stride, d_crops + 4 * n_fused,
+                                           ctx->crop_work.as<uint32_t>(), j.stream, ctx->lb_side_strips));
+        VDF_HIP(ctx, vdf::launch_resize_dct_cropped_small_boxes(tail.d_frames, tail.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, j.buf_end(), d_crops + 4 * n_fused,
+                                                                set->entries.as<vdf::CropTableEntry>(), ctx->cos_table.as<double>(), tail.d_out, tail.d_dc, j.stream));
     }
+    if (out_crops) {
+        if (!ctx->pin_crops.reserve(j.n_clips * 16)) return fail(ctx, VDF_E_OOM, "host staging for the crop boxes");
+        VDF_HIP(ctx, hipMemcpyAsync(ctx->pin_crops.p, d_crops, j.n_clips * 16, hipMemcpyDeviceToHost, j.stream));
+        VDF_HIP(ctx, hipEventRecord(ctx->ev_mid, j.stream));
+        VDF_HIP(ctx, hipEventSynchronize(ctx->ev_mid));  // everything of this call is queued: the wait costs the GPU nothing
+        std::memcpy(out_crops, ctx->pin_crops.p, j.n_clips * 16);
+    }
+    return VDF_OK;
+}
+
+int letterbox_launch(vdf_ctx *ctx, const HashJob &j, uint32_t frames_per_clip, uint32_t *out_crops, uint32_t *d_out_crops)
+{
     VDF_HIP(ctx, hipSetDevice(ctx->device));
-    // Small frames (round 6): the boxes never visit the host.  Every box size's tables are resident (box_table_set), so
-    //  * frames of at most 64 x 64 take ONE kernel that detects, crops, resizes, transforms and hashes (letterbox_resize_dct_hash_small_kernel);
-    //    the clips within 64 bytes of the buffer's end (the last one, as a rule) take the route below for its careful loader;
-    //  * other small frames: the two detect kernels, then the one-workgroup-per-clip kernel reads each clip's box where they left it.
-    // No copy to the host, no wait, no host loop over the clips between the launches; out_crops is filled by one copy queued behind them
-    // and waited for at the END of the call (d_out_crops: no wait at all).
-    const bool small_frames = (h + 63) / 64 <= 2 && w <= 256 && ctx->resize_mode == 0 && !ctx->no_smallcrop && !ctx->lb_host_plan &&
-                              n_clips <= 0x7FFFFFFull;
-    if (small_frames) {
-        int rc = ensure_cos_table(ctx, stream);
+    uint32_t *d_crops = d_out_crops;  // (the detect writes straight into the caller's d_out_crops when given)
+    if (!d_crops) {
+        VDF_HIP(ctx, ctx->crops.reserve(j.n_clips * 16));
+        d_crops = ctx->crops.as<uint32_t>();
+    }
+    const vdf::LetterboxPlan plan = vdf::plan_letterbox(j.call(), hash_knobs(ctx));
+    if (plan.small_frames) {  // every box size's tables are resident (box_table_set), so the kernels find a box's tables by its size
+        int rc = ensure_cos_table(ctx, j.stream);
         if (rc) return rc;
-        BoxTableSet *set = box_table_set(ctx, w, h, stream, &rc);
+        const BoxTableSet *set = box_table_set(ctx, j.w, j.h, j.stream, &rc);
         if (rc) return rc;
-        if (set->usable) {
-            uint32_t *d_crops = d_out_crops;
-            if (!d_crops) {
-                VDF_HIP(ctx, ctx->crops.reserve(n_clips * 16));
-                d_crops = ctx->crops.as<uint32_t>();
-            }
-            const uint8_t *buf_end = d_frames + (n_clips - 1) * clip_stride + (VDF_DCT_SIZE - 1) * frame_stride + (size_t)w * h;
-            size_t n_fused = 0;
-            if (set->one_tile && !ctx->no_lb_fused) {
-                // clip c's loads stay inside the buffer iff it ends at least 64 bytes before the last clip does: (n - 1 - c) * clip_stride >= 64
-                const size_t n_tail = clip_stride == 0 ? n_clips : std::min<size_t>(n_clips, (64 + clip_stride - 1) / clip_stride);
-                n_fused = n_clips - n_tail;
-                VDF_HIP(ctx, vdf::launch_letterbox_hash_small(d_frames, n_fused, w, h, frame_stride, clip_stride, set->blob.p, ctx->cos_table.as<double>(),
-                                                              d_out, d_dc, d_crops, ctx->hash_wgs_per_cu_set ? ctx->hash_wgs_per_cu : 0, stream));
-            }
-            if (n_fused < n_clips) {
-                const size_t nr = n_clips - n_fused;
-                const uint8_t *fr = d_frames + n_fused * clip_stride;
-                VDF_HIP(ctx, ctx->crop_work.reserve(vdf::letterbox_work_bytes(nr, frames_per_clip)));
-                VDF_HIP(ctx, vdf::launch_letterbox(fr, nr, frames_per_clip, w, h, frame_stride, clip_stride, d_crops + 4 * n_fused,
-                                                   ctx->crop_work.as<uint32_t>(), stream, ctx->lb_side_strips));
-                VDF_HIP(ctx, vdf::launch_resize_dct_cropped_small_boxes(fr, nr, w, h, frame_stride, clip_stride, buf_end, d_crops + 4 * n_fused,
-                                                                        set->entries.as<vdf::CropTableEntry>(), ctx->cos_table.as<double>(),
-                                                                        d_out + n_fused * VDF_HASH_WORDS, d_dc ? d_dc + n_fused : nullptr, stream));
-            }
-            if (out_crops) {
-                if (!ctx->pin_crops.reserve(n_clips * 16)) return fail(ctx, VDF_E_OOM, "host staging for the crop boxes");
-                VDF_HIP(ctx, hipMemcpyAsync(ctx->pin_crops.p, d_crops, n_clips * 16, hipMemcpyDeviceToHost, stream));
-                VDF_HIP(ctx, hipEventRecord(ctx->ev_mid, stream));
-                VDF_HIP(ctx, hipEventSynchronize(ctx->ev_mid));  // everything of this call is queued: the wait costs the GPU nothing
-                std::memcpy(out_crops, ctx->pin_crops.p, n_clips * 16);
-            }
-            return VDF_OK;
-        }
+        if (set->usable) return letterbox_small(ctx, j, frames_per_clip, plan, set, out_crops, d_crops);
     }
     // (Cutting a large batch into chunks whose detect passes run on a second stream under the resize of the chunks before them was
     // built and measured in round 5 - profiles/r05_letterbox_ab.txt: the resize kernels fill every CU's LDS, so the walkers only got in
@@ -1109,23 +1006,28 @@ int letterbox_hash_device_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n
     // against 5.32.  The detect pass was made faster instead: csrc/cropdetect.hip.)
     // Larger frames: which kernel a box takes (row-range stream, column-range stream, gather, whole-line) and the tables of its size are
     // decided per box SHAPE on the host - tables for every box size of a 1080p frame would be 50 MB and a second of host time per frame size -
-    // so the boxes come down once and the call waits for the detect.  (The detect writes straight into the caller's d_out_crops when given.)
-    uint32_t *d_crops = d_out_crops;
-    if (!d_crops) {
-        VDF_HIP(ctx, ctx->crops.reserve(n_clips * 16));
-        d_crops = ctx->crops.as<uint32_t>();
-    }
-    VDF_HIP(ctx, ctx->crop_work.reserve(vdf::letterbox_work_bytes(n_clips, frames_per_clip)));
-    VDF_HIP(ctx, vdf::launch_letterbox(d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, d_crops, ctx->crop_work.as<uint32_t>(),
-                                       stream, ctx->lb_side_strips));
+    // so the boxes come down once and the call waits for the detect.
+    VDF_HIP(ctx, ctx->crop_work.reserve(vdf::letterbox_work_bytes(j.n_clips, frames_per_clip)));
+    VDF_HIP(ctx, vdf::launch_letterbox(j.d_frames, j.n_clips, frames_per_clip, j.w, j.h, j.frame_stride, j.clip_stride, d_crops, ctx->crop_work.as<uint32_t>(),
+                                       j.stream, ctx->lb_side_strips));
     // (pinned: a pageable destination makes the copy synchronous and slow - 0.3 MB for 20 000 clips)
-    if (!ctx->pin_crops.reserve(n_clips * 16)) return fail(ctx, VDF_E_OOM, "host staging for the crop boxes");
+    if (!ctx->pin_crops.reserve(j.n_clips * 16)) return fail(ctx, VDF_E_OOM, "host staging for the crop boxes");
     uint32_t *crops = ctx->pin_crops.as<uint32_t>();
-    VDF_HIP(ctx, hipMemcpyAsync(crops, d_crops, n_clips * 16, hipMemcpyDeviceToHost, stream));
-    VDF_HIP(ctx, hipEventRecord(ctx->ev_wait, stream));
+    VDF_HIP(ctx, hipMemcpyAsync(crops, d_crops, j.n_clips * 16, hipMemcpyDeviceToHost, j.stream));
+    VDF_HIP(ctx, hipEventRecord(ctx->ev_wait, j.stream));
     if (int rcw = wait_event(ctx, ctx->ev_wait)) return rcw;  // (behind the frames' upload when they come from the host: milliseconds)
-    if (out_crops) std::memcpy(out_crops, crops, n_clips * 16);
-    return hash_cropped_locked(ctx, d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, crops, d_out, d_dc, stream);
+    if (out_crops) std::memcpy(out_crops, crops, j.n_clips * 16);
+    return hash_cropped_launch(ctx, j, crops);
+}
+
+int letterbox_hash_device_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip,
+                                 uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride, uint64_t *d_out,
+                                 uint32_t *d_dc, uint32_t *out_crops, hipStream_t stream, uint32_t *d_out_crops)
+{
+    const HashJob all{d_frames, n_clips, w, h, frame_stride, clip_stride, d_out, d_dc, stream};
+    return checked_launches(ctx, all, frames_per_clip, [&](size_t c0, size_t n) {
+        return letterbox_launch(ctx, all.clips(c0, n), frames_per_clip, out_crops ? out_crops + 4 * c0 : nullptr, d_out_crops ? d_out_crops + 4 * c0 : nullptr);
+    });
 }
 
 

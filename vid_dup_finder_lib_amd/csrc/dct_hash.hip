@@ -1310,6 +1310,28 @@ __global__ __launch_bounds__(64 * NW) void resize_mfma_frame_wavestream_kernel(c
     }
 }
 
+static int cu_count()  // of the current device; the persistent and stream kernels size their grids by it
+{
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return cus;
+}
+
+// LAUNCH(MODE, ROWCROP): MODE by the pitch and the box's first column, ROWCROP when clips carry row ranges
+#define VDF_BY_MODE_AND_ROWCROP(LAUNCH)        \
+    do {                                       \
+        if (clips) {                           \
+            if (mode == 0) LAUNCH(0, true);    \
+            else if (mode == 1) LAUNCH(1, true);  \
+            else LAUNCH(2, true);              \
+        } else {                               \
+            if (mode == 0) LAUNCH(0, false);   \
+            else if (mode == 1) LAUNCH(1, false); \
+            else LAUNCH(2, false);             \
+        }                                      \
+    } while (0)
+
 static void launch_stream_mode(uint32_t grid, hipStream_t stream, const uint8_t *frames, uint32_t w, uint32_t h,
                                size_t frame_stride, size_t clip_stride, uint32_t n_frames, const MfmaResizeTables &T,
                                uint32_t nb, uint8_t *small, const CropStreamClip *clips, const CropStreamTable *tables)
@@ -1319,20 +1341,11 @@ static void launch_stream_mode(uint32_t grid, hipStream_t stream, const uint8_t 
 #define VDF_CS_LAUNCH(M, RC)                                                                                                               \
     hipLaunchKernelGGL((resize_mfma_frame_stream_kernel<kStreamBufS, kStreamTabS, M, RC>), dim3(grid), dim3(256), 0, stream, frames, w, h, \
                        frame_stride, clip_stride, n_frames, T, nb, wp, small, clips, tables)
-    if (clips) {  // per-clip row ranges
-        if (mode == 0) VDF_CS_LAUNCH(0, true);
-        else if (mode == 1) VDF_CS_LAUNCH(1, true);
-        else VDF_CS_LAUNCH(2, true);
-    } else {
-        if (mode == 0) VDF_CS_LAUNCH(0, false);
-        else if (mode == 1) VDF_CS_LAUNCH(1, false);
-        else VDF_CS_LAUNCH(2, false);
-    }
+    VDF_BY_MODE_AND_ROWCROP(VDF_CS_LAUNCH);
 #undef VDF_CS_LAUNCH
 }
 
-// per-wave block streams: NW by the (box) width (resize_wavestream_waves), MODE by the pitch and the box's first column, ROWCROP when clips
-// carry row ranges
+// per-wave block streams: NW by the (box) width (resize_wavestream_waves)
 template <int NW, int BUF, int TAB>
 static void launch_wavestream_nw(uint32_t grid, hipStream_t stream, const uint8_t *frames, uint32_t w, uint32_t h, size_t frame_stride,
                                  size_t clip_stride, uint32_t n_frames, const MfmaResizeTables &T, uint8_t *small,
@@ -1341,70 +1354,62 @@ static void launch_wavestream_nw(uint32_t grid, hipStream_t stream, const uint8_
 #define VDF_WS_LAUNCH(M, RC)                                                                                                              \
     hipLaunchKernelGGL((resize_mfma_frame_wavestream_kernel<NW, BUF, TAB, M, RC>), dim3(grid), dim3(64 * NW), 0, stream, frames, w, h, \
                        frame_stride, clip_stride, n_frames, T, wp, small, clips, tables, x0)
-    if (clips) {
-        if (mode == 0) VDF_WS_LAUNCH(0, true);
-        else if (mode == 1) VDF_WS_LAUNCH(1, true);
-        else VDF_WS_LAUNCH(2, true);
-    } else {
-        if (mode == 0) VDF_WS_LAUNCH(0, false);
-        else if (mode == 1) VDF_WS_LAUNCH(1, false);
-        else VDF_WS_LAUNCH(2, false);
-    }
+    VDF_BY_MODE_AND_ROWCROP(VDF_WS_LAUNCH);
 #undef VDF_WS_LAUNCH
 }
 
 // w = the frames' pitch; box_w / x0 = the column range every clip of the launch keeps (box_w == w, x0 == 0: whole rows)
 static hipError_t launch_wavestream(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride,
                                     const MfmaResizeArgs &a, const CropStreamClip *clips, const CropStreamTable *tables, uint8_t *small,
-                                    hipStream_t stream, uint32_t box_w, uint32_t x0)
+                                    hipStream_t stream, uint32_t box_w, uint32_t x0, int nw)
 {
-    const int nw = resize_wavestream_waves_box(w, x0, box_w, a.wavestream_knob);
-    if (n_clips * 16 > 0xFFFFFFFFull || (uint64_t)w * h >= (1ull << 31) || !a.band_meta || nw == 0 || (box_w != w && !clips) || (uint64_t)x0 + box_w > w)
+    if (n_clips * 16 > 0xFFFFFFFFull || (uint64_t)w * h >= (1ull << 31) || !a.band_meta || (box_w != w && !clips) || (uint64_t)x0 + box_w > w)
         return hipErrorInvalidValue;
-    if (!resize_wavestream_table_fits(nw, a.band_stride)) return hipErrorInvalidValue;
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const uint32_t n_frames = (uint32_t)(n_clips * 16), grid = std::min<uint32_t>(n_frames, (uint32_t)cus);
-    const MfmaResizeTables T = make_tables(a);
     int mode = 0;
     const uint32_t wp = box_stream_pitch(w, x0, box_w, &mode);
-    if (nw == 3) launch_wavestream_nw<3, kWaveStreamBuf3, kWaveStreamTabBytes>(grid, stream, frames, w, h, frame_stride, clip_stride, n_frames, T, small, clips, tables, wp, mode, x0);
-    else if (nw == 4) launch_wavestream_nw<4, kWaveStreamBuf, kWaveStreamTabBytes>(grid, stream, frames, w, h, frame_stride, clip_stride, n_frames, T, small, clips, tables, wp, mode, x0);
-    else if (nw == 5) launch_wavestream_nw<5, kWaveStreamBuf5, kWaveStreamTabMid>(grid, stream, frames, w, h, frame_stride, clip_stride, n_frames, T, small, clips, tables, wp, mode, x0);
-    else if (nw == 6) launch_wavestream_nw<6, kWaveStreamBuf6, kWaveStreamTabSmall>(grid, stream, frames, w, h, frame_stride, clip_stride, n_frames, T, small, clips, tables, wp, mode, x0);
-    else launch_wavestream_nw<8, kWaveStreamBuf8, kWaveStreamTabSmall>(grid, stream, frames, w, h, frame_stride, clip_stride, n_frames, T, small, clips, tables, wp, mode, x0);
+    // the planned wave count's buffers hold a block, its table array the band table
+    if (((16u * wp + 1023u) & ~1023u) + 128u > (uint32_t)wavestream_buf_bytes(nw) || !resize_wavestream_table_fits(nw, a.band_stride)) return hipErrorInvalidValue;
+    const int cus = cu_count();
+    const uint32_t n_frames = (uint32_t)(n_clips * 16), grid = std::min<uint32_t>(n_frames, (uint32_t)cus);
+    const MfmaResizeTables T = make_tables(a);
+#define VDF_WS_NW(NW, BUF, TAB) \
+    case NW: launch_wavestream_nw<NW, BUF, TAB>(grid, stream, frames, w, h, frame_stride, clip_stride, n_frames, T, small, clips, tables, wp, mode, x0); break
+    switch (nw) {
+        VDF_WS_NW(3, kWaveStreamBuf3, kWaveStreamTabBytes);
+        VDF_WS_NW(4, kWaveStreamBuf, kWaveStreamTabBytes);
+        VDF_WS_NW(5, kWaveStreamBuf5, kWaveStreamTabMid);
+        VDF_WS_NW(6, kWaveStreamBuf6, kWaveStreamTabSmall);
+        VDF_WS_NW(8, kWaveStreamBuf8, kWaveStreamTabSmall);
+    }
+#undef VDF_WS_NW
     return hipGetLastError();
 }
 
 hipError_t launch_resize_mfma_box_wavestream(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h, size_t frame_stride,
-                                             size_t clip_stride, const MfmaResizeArgs &a, uint32_t x0, uint32_t box_w, const CropStreamClip *clips,
-                                             const CropStreamTable *tables, uint8_t *small, hipStream_t stream)
+                                             size_t clip_stride, const MfmaResizeArgs &a, uint32_t x0, uint32_t box_w, int waves,
+                                             const CropStreamClip *clips, const CropStreamTable *tables, uint8_t *small, hipStream_t stream)
 {
     if (n_clips == 0) return hipSuccess;
     if (!clips || !tables) return hipErrorInvalidValue;
-    return launch_wavestream(frames, n_clips, w, h, frame_stride, clip_stride, a, clips, tables, small, stream, box_w, x0);
+    return launch_wavestream(frames, n_clips, w, h, frame_stride, clip_stride, a, clips, tables, small, stream, box_w, x0, waves);
 }
 
 hipError_t launch_resize_mfma_frames_stream(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h,
-                                            size_t frame_stride, size_t clip_stride, const MfmaResizeArgs &a,
+                                            size_t frame_stride, size_t clip_stride, const MfmaResizeArgs &a, const HashPlan &plan,
                                             uint8_t *small, hipStream_t stream, const CropStreamClip *clips,
                                             const CropStreamTable *tables)
 {
     if (n_clips == 0) return hipSuccess;
-    uint32_t nb = 0;
-    const int cls = stream_class(w, &nb);
-    if (n_clips * 16 > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (plan.route == HashRoute::kWaveStream)
+        return launch_wavestream(frames, n_clips, w, h, frame_stride, clip_stride, a, clips, tables, small, stream, w, 0, plan.waves);
+    // the chunk form (two workgroups per CU): the whole plain table in the S class's array, chunks of plan.nb blocks in its buffers
+    if (plan.route != HashRoute::kChunkStream || n_clips * 16 > 0xFFFFFFFFull || a.band_meta || a.n_kt > kStreamTabS || plan.nb == 0 ||
+        plan.nb > stream_blocks_per_chunk(stream_pitch(w), kStreamBufS))
+        return hipErrorInvalidValue;
+    const int cus = cu_count();
     const uint32_t n_frames = (uint32_t)(n_clips * 16);
-    if (resize_stream_wants_band(w, a.wavestream_knob) != (a.band_meta != nullptr)) return hipErrorInvalidValue;  // the caller picks the table form by resize_stream_wants_band
-    if (resize_wavestream_applies(w, a.wavestream_knob))
-        return launch_wavestream(frames, n_clips, w, h, frame_stride, clip_stride, a, clips, tables, small, stream, w, 0);
-    if (cls != 1 || a.band_meta) return hipErrorInvalidValue;  // the chunk form serves the S class only (frames up to 512 wide, two workgroups per CU)
     launch_stream_mode(std::min<uint32_t>(n_frames, (uint32_t)cus * 2u), stream, frames, w, h, frame_stride, clip_stride, n_frames, make_tables(a),
-                       nb, small, clips, tables);
+                       plan.nb, small, clips, tables);
     return hipGetLastError();
 }
 
@@ -1598,40 +1603,30 @@ __global__ __launch_bounds__(256) void resize_mfma_frame_ksplit_kernel(const uin
 }
 
 hipError_t launch_resize_mfma_frames_ksplit(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h,
-                                            size_t frame_stride, size_t clip_stride, const MfmaResizeArgs &a,
+                                            size_t frame_stride, size_t clip_stride, const MfmaResizeArgs &a, const HashPlan &plan,
                                             uint8_t *small, hipStream_t stream, const CropStreamClip *clips,
                                             const CropStreamTable *tables)
 {
     if (n_clips == 0) return hipSuccess;
     uint32_t wp = 0;
-    const uint32_t nb = ksplit_geometry(w, &wp);
-    if (n_clips * 16 > 0xFFFFFFFFull || nb == 0 || a.n_kt > 64 || a.band_meta) return hipErrorInvalidValue;
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const uint32_t nb = plan.nb, fits = ksplit_geometry(w, &wp);  // chunks of the planned blocks at the kernel's LDS pitch must fit its buffers
+    if (plan.route != HashRoute::kKsplit || n_clips * 16 > 0xFFFFFFFFull || nb == 0 || nb > fits || a.n_kt > 64 || a.band_meta) return hipErrorInvalidValue;
+    const int cus = cu_count();
     const uint32_t n_frames = (uint32_t)(n_clips * 16);
     const dim3 grid(std::min<uint32_t>(n_frames, (uint32_t)cus));
-    if (clips) {  // per-clip row ranges
-        if (a.n_kt <= 16)
-            hipLaunchKernelGGL((resize_mfma_frame_ksplit_kernel<4, true>), grid, dim3(256), 0, stream, frames, w, h, frame_stride, clip_stride,
-                               n_frames, make_tables(a), nb, wp, small, clips, tables);
-        else if (a.n_kt <= 32)
-            hipLaunchKernelGGL((resize_mfma_frame_ksplit_kernel<8, true>), grid, dim3(256), 0, stream, frames, w, h, frame_stride, clip_stride,
-                               n_frames, make_tables(a), nb, wp, small, clips, tables);
-        else
-            hipLaunchKernelGGL((resize_mfma_frame_ksplit_kernel<16, true>), grid, dim3(256), 0, stream, frames, w, h, frame_stride, clip_stride,
-                               n_frames, make_tables(a), nb, wp, small, clips, tables);
-        return hipGetLastError();
-    }
-    if (a.n_kt <= 16)
-        hipLaunchKernelGGL((resize_mfma_frame_ksplit_kernel<4>), grid, dim3(256), 0, stream, frames, w, h, frame_stride, clip_stride,
-                           n_frames, make_tables(a), nb, wp, small);
-    else if (a.n_kt <= 32)
-        hipLaunchKernelGGL((resize_mfma_frame_ksplit_kernel<8>), grid, dim3(256), 0, stream, frames, w, h, frame_stride, clip_stride,
-                           n_frames, make_tables(a), nb, wp, small);
-    else
-        hipLaunchKernelGGL((resize_mfma_frame_ksplit_kernel<16>), grid, dim3(256), 0, stream, frames, w, h, frame_stride, clip_stride,
-                           n_frames, make_tables(a), nb, wp, small);
+#define VDF_KS_LAUNCH(MAXT)                                                                                                                 \
+    do {                                                                                                                                     \
+        if (clips) /* per-clip row ranges */                                                                                                 \
+            hipLaunchKernelGGL((resize_mfma_frame_ksplit_kernel<MAXT, true>), grid, dim3(256), 0, stream, frames, w, h, frame_stride,        \
+                               clip_stride, n_frames, make_tables(a), nb, wp, small, clips, tables);                                         \
+        else                                                                                                                                 \
+            hipLaunchKernelGGL((resize_mfma_frame_ksplit_kernel<MAXT>), grid, dim3(256), 0, stream, frames, w, h, frame_stride, clip_stride, \
+                               n_frames, make_tables(a), nb, wp, small);                                                                     \
+    } while (0)
+    if (a.n_kt <= 16) VDF_KS_LAUNCH(4);  // tiles per wave: a quarter of the table's
+    else if (a.n_kt <= 32) VDF_KS_LAUNCH(8);
+    else VDF_KS_LAUNCH(16);
+#undef VDF_KS_LAUNCH
     return hipGetLastError();
 }
 
@@ -1894,9 +1889,7 @@ hipError_t launch_resize_mfma_cropped_stream(const uint8_t *frames, size_t n_cli
 {
     if (n_clips == 0) return hipSuccess;
     if (n_clips * 16 > 0xFFFFFFFFull || (uint64_t)pitch * frame_rows >= (1ull << 31)) return hipErrorInvalidValue;
-    int dev = 0, cus = 256;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const int cus = cu_count();
     const uint32_t n_frames = (uint32_t)(n_clips * 16), frame_bytes = pitch * frame_rows;
     const dim3 grid_s(std::min<uint32_t>(n_frames, (uint32_t)cus * 2u)), grid_m(std::min<uint32_t>(n_frames, (uint32_t)cus));
 #define VDF_LAUNCH_CROPPED(BUF, TAB, SH, GRID)                                                                              \
@@ -2456,9 +2449,8 @@ hipError_t launch_letterbox_hash_small(const uint8_t *frames, size_t n_clips, ui
 {
     if (n_clips == 0) return hipSuccess;
     if (w > 64 || h > 64 || n_clips > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    int dev = 0, cus = 256, per_cu = 3;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    int per_cu = 3;
+    const int cus = cu_count();
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, letterbox_resize_dct_hash_small_kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 3;
     if (wgs_per_cu > 0) per_cu = std::min(per_cu, wgs_per_cu);
     const uint32_t grid = (uint32_t)std::min<size_t>(n_clips, (size_t)cus * (size_t)per_cu);
@@ -2498,89 +2490,64 @@ static MfmaResizeTables make_tables(const MfmaResizeArgs &a)
 }
 
 hipError_t launch_resize_dct_fused(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h, size_t frame_stride,
-                                   size_t clip_stride, const uint8_t *buf_end, const MfmaResizeArgs &a,
+                                   size_t clip_stride, const uint8_t *buf_end, const MfmaResizeArgs &a, const HashPlan &plan,
                                    const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare,
                                    hipStream_t stream)
 {
     if (n_clips == 0) return hipSuccess;
-    // The persistent kernels load 16 bytes at a time without looking at the buffer's end.  With W % 16 == 0 no load crosses a row's end; with any other
-    // width a row's last load runs up to 15 bytes into what follows - the next row, frame or clip, all inside the buffer, at zero coefficients -
-    // except behind the LAST clip: that one goes to the one-workgroup-per-clip kernel and its careful loader (round 5).
-    const bool persistent_ok = n_clips <= 0xFFFFFFFFull && !a.no_persistent && a.n_kt <= 4 && a.n_rg <= 4;
-    // (clips that overlap or repeat - clip_stride below 16, e.g. 0: one clip hashed n times - end within 15 bytes of the buffer's end more than
-    // once: then no clip may take the unchecked loads, and all of them go to the one-workgroup-per-clip kernel below)
-    const bool tail = persistent_ok && w % 16 != 0 && n_clips >= 2 && clip_stride >= 16;  // the last clip apart
-    const bool inside = w % 16 == 0 || tail;
-    const size_t n_all = n_clips;
-    if (tail) n_clips -= 1;
-    const auto last_clip = [&]() -> hipError_t {
-        if (!tail) return hipGetLastError();
-        const uint8_t *f = frames + (n_all - 1) * clip_stride;
-        uint64_t *oh = out_hashes + (n_all - 1) * 16;
-        uint32_t *od = out_dontcare ? out_dontcare + (n_all - 1) : nullptr;
+    const bool per_clip = plan.route == HashRoute::kPerClipFused;
+    // the persistent kernels: a 32-bit clip count, tiles within their register arrays, and no unchecked load past the buffer's end (plan_fused)
+    if (!per_clip && (n_clips > 0xFFFFFFFFull || a.n_kt > 4 || a.n_rg > 4 || !(w % 16 == 0 || (plan.last_clip_apart && n_clips >= 2 && clip_stride >= 16))))
+        return hipErrorInvalidValue;
+    // the one-workgroup-per-clip kernel and its careful loader: every clip of its route, or the last clip of a persistent launch
+    const auto per_clip_launch = [&](const uint8_t *f, size_t n, uint64_t *oh, uint32_t *od) {
         if (a.n_kt == 1 && a.n_rg == 1)
-            hipLaunchKernelGGL(resize_dct_hash_fused_kernel<true>, dim3(1), dim3(256), 0, stream, f, w, h, frame_stride, clip_stride, buf_end,
+            hipLaunchKernelGGL(resize_dct_hash_fused_kernel<true>, dim3((uint32_t)n), dim3(256), 0, stream, f, w, h, frame_stride, clip_stride, buf_end,
                                make_tables(a), cos_table, oh, od);
         else
-            hipLaunchKernelGGL(resize_dct_hash_fused_kernel<false>, dim3(1), dim3(256), 0, stream, f, w, h, frame_stride, clip_stride, buf_end,
+            hipLaunchKernelGGL(resize_dct_hash_fused_kernel<false>, dim3((uint32_t)n), dim3(256), 0, stream, f, w, h, frame_stride, clip_stride, buf_end,
                                make_tables(a), cos_table, oh, od);
-        return hipGetLastError();
     };
-    if (a.n_kt == 1 && a.n_rg == 1 && inside && n_clips <= 0xFFFFFFFFull && !a.no_persistent) {
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        const uint32_t grid = (uint32_t)std::min<size_t>(n_clips, (size_t)cus * a.persistent_wgs_per_cu);
-        if (w == 64 && h == 64)
-            hipLaunchKernelGGL(resize_dct_hash_persistent_kernel<true>, dim3(grid), dim3(256), 0, stream, frames, w, h,
-                               frame_stride, clip_stride, make_tables(a), cos_table, out_hashes, out_dontcare,
-                               (uint32_t)n_clips);
-        else
-            hipLaunchKernelGGL(resize_dct_hash_persistent_kernel<false>, dim3(grid), dim3(256), 0, stream, frames, w, h,
-                               frame_stride, clip_stride, make_tables(a), cos_table, out_hashes, out_dontcare,
-                               (uint32_t)n_clips);
-    } else if (a.n_kt <= 4 && a.n_rg <= 4 && inside && n_clips <= 0xFFFFFFFFull && !a.no_persistent) {
-        // up to 128 x 128: units of eight loads per lane in flight, persistent
-        int dev = 0, cus = 256;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-#define VDF_TILED(KERNEL)                                                                                                       \
-    do {                                                                                                                         \
-        int per_cu = 3;                                                                                                          \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERNEL, 256, 0) != hipSuccess || per_cu < 1) per_cu = 3;       \
-        const uint32_t grid = (uint32_t)std::min<size_t>(n_clips, (size_t)cus * (size_t)per_cu);                                 \
-        hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), 0, stream, frames, w, h, frame_stride, clip_stride, make_tables(a),    \
-                           cos_table, out_hashes, out_dontcare, (uint32_t)n_clips);                                              \
-    } while (0)
-        if (a.n_rg > 2) {  // 129 ... 256 rows: four row groups (the fourth may be empty)
-            if (a.n_kt == 4) VDF_TILED((resize_dct_hash_tiled_kernel<4, 4, 2>));
-            else if (a.n_kt == 3) VDF_TILED((resize_dct_hash_tiled_kernel<3, 4, 3>));
-            else if (a.n_kt == 2) VDF_TILED((resize_dct_hash_tiled_kernel<2, 4, 2>));
-            else VDF_TILED((resize_dct_hash_tiled_kernel<1, 4, 3>));
-        } else if (a.n_kt == 4 && a.n_rg == 2) VDF_TILED((resize_dct_hash_tiled_kernel<4, 2, 2>));
-        else if (a.n_kt == 4) VDF_TILED((resize_dct_hash_tiled_kernel<4, 1, 2>));
-        else if (a.n_kt == 3 && a.n_rg == 2) VDF_TILED((resize_dct_hash_tiled_kernel<3, 2, 3>));
-        else if (a.n_kt == 3) VDF_TILED((resize_dct_hash_tiled_kernel<3, 1, 3>));
-        else if (a.n_kt == 2 && a.n_rg == 2) VDF_TILED((resize_dct_hash_tiled_kernel<2, 2, 3>));
-        else if (a.n_kt == 2) VDF_TILED((resize_dct_hash_tiled_kernel<2, 1, 1>));
-        else VDF_TILED((resize_dct_hash_tiled_kernel<1, 2, 1>));
+    const size_t n_all = n_clips;
+    if (plan.last_clip_apart) n_clips -= 1;
+    const int cus = cu_count();
+#define VDF_PERSISTENT(KERNEL, PER_CU)                                                                                                            \
+    hipLaunchKernelGGL(KERNEL, dim3((uint32_t)std::min<size_t>(n_clips, (size_t)cus * (size_t)(PER_CU))), dim3(256), 0, stream, frames, w, h, \
+                       frame_stride, clip_stride, make_tables(a), cos_table, out_hashes, out_dontcare, (uint32_t)n_clips)
+#define VDF_TILED(NKT, NRG)                                                                                                                   \
+    case NKT * 8 + NRG: {                                                                                                                     \
+        int per_cu = 3;                                                                                                                       \
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resize_dct_hash_tiled_kernel<NKT, NRG, tiled_waves(NKT, NRG)>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 3; \
+        VDF_PERSISTENT((resize_dct_hash_tiled_kernel<NKT, NRG, tiled_waves(NKT, NRG)>), per_cu);                                              \
+        break;                                                                                                                                \
+    }
+    if (per_clip) {
+        per_clip_launch(frames, n_clips, out_hashes, out_dontcare);
+    } else if (plan.route == HashRoute::kPersistentOneTile) {
+        if (a.n_kt != 1 || a.n_rg != 1 || (plan.full_tile && (w != 64 || h != 64))) return hipErrorInvalidValue;
+        if (plan.full_tile) VDF_PERSISTENT(resize_dct_hash_persistent_kernel<true>, a.persistent_wgs_per_cu);
+        else VDF_PERSISTENT(resize_dct_hash_persistent_kernel<false>, a.persistent_wgs_per_cu);
+    } else if (plan.route == HashRoute::kTiled && a.n_kt == plan.n_kt && (plan.tiled_nrg == 4 ? a.n_rg > 2 : a.n_rg == plan.tiled_nrg)) {
+        switch (plan.n_kt * 8 + plan.tiled_nrg) {
+            VDF_TILED(4, 4) VDF_TILED(3, 4) VDF_TILED(2, 4) VDF_TILED(1, 4) VDF_TILED(4, 2) VDF_TILED(4, 1) VDF_TILED(3, 2) VDF_TILED(3, 1)
+            VDF_TILED(2, 2) VDF_TILED(2, 1) VDF_TILED(1, 2)
+            default: return hipErrorInvalidValue;
+        }
+    } else {
+        return hipErrorInvalidValue;
+    }
 #undef VDF_TILED
-    } else if (a.n_kt == 1 && a.n_rg == 1)
-        hipLaunchKernelGGL(resize_dct_hash_fused_kernel<true>, dim3((uint32_t)n_clips), dim3(256), 0, stream, frames, w,
-                           h, frame_stride, clip_stride, buf_end, make_tables(a), cos_table, out_hashes, out_dontcare);
-    else
-        hipLaunchKernelGGL(resize_dct_hash_fused_kernel<false>, dim3((uint32_t)n_clips), dim3(256), 0, stream, frames,
-                           w, h, frame_stride, clip_stride, buf_end, make_tables(a), cos_table, out_hashes,
-                           out_dontcare);
-    return last_clip();
+#undef VDF_PERSISTENT
+    if (plan.last_clip_apart)
+        per_clip_launch(frames + (n_all - 1) * clip_stride, 1, out_hashes + (n_all - 1) * 16, out_dontcare ? out_dontcare + (n_all - 1) : nullptr);
+    return hipGetLastError();
 }
 
 hipError_t launch_resize_mfma_frames(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h,
                                      size_t frame_stride, size_t clip_stride, const uint8_t *buf_end,
-                                     const MfmaResizeArgs &a, uint8_t *small, bool wide, hipStream_t stream)
+                                     const MfmaResizeArgs &a, uint8_t *small, hipStream_t stream)
 {
     if (n_clips == 0) return hipSuccess;
-    if (!wide) return hipErrorInvalidValue;  // round 3: the per-frame 16 x 64 B kernel is gone (dominated at every size, profiles/r03_resize_sweep.txt)
     // a.av is in kMfmaLayoutVerticalWide order
     hipLaunchKernelGGL(resize_mfma_frame_wide_kernel, dim3((uint32_t)(n_clips * 16)), dim3(256), 0, stream, frames, w,
                        h, frame_stride, clip_stride, buf_end, make_tables(a), small);

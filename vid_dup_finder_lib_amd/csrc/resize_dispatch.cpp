@@ -1,5 +1,8 @@
 #include "resize_dispatch.h"
 
+#include <algorithm>
+#include <map>
+
 namespace vdf {
 
 uint32_t stream_pitch(uint32_t w)
@@ -34,8 +37,7 @@ int stream_class(uint32_t w, uint32_t *nb)
 static bool wavestream_fits(uint32_t w, int nw)
 {
     const uint32_t need = ((16u * stream_pitch(w) + 1023u) & ~1023u) + 128u;  // a DMA instruction fills whole KBs
-    const int buf = nw == 3 ? kWaveStreamBuf3 : nw == 4 ? kWaveStreamBuf : nw == 5 ? kWaveStreamBuf5 : nw == 6 ? kWaveStreamBuf6 : nw == 8 ? kWaveStreamBuf8 : 0;
-    return need <= (uint32_t)buf && w >= 256;
+    return need <= (uint32_t)wavestream_buf_bytes(nw) && w >= 256;
 }
 
 int resize_wavestream_waves(uint32_t w, int knob)
@@ -81,10 +83,8 @@ int resize_wavestream_waves_box(uint32_t frame_w, uint32_t x0, uint32_t box_w, i
     if (knob < 0 || box_w < 513) return 0;  // narrower boxes: the gather kernel with two workgroups per CU
     int mode = 0;
     const uint32_t need = ((16u * box_stream_pitch(frame_w, x0, box_w, &mode) + 1023u) & ~1023u) + 128u;
-    for (int nw : {8, 6, 5, 4, 3}) {
-        const int buf = nw == 3 ? kWaveStreamBuf3 : nw == 4 ? kWaveStreamBuf : nw == 5 ? kWaveStreamBuf5 : nw == 6 ? kWaveStreamBuf6 : kWaveStreamBuf8;
-        if (need <= (uint32_t)buf) return nw;
-    }
+    for (int nw : {8, 6, 5, 4, 3})
+        if (need <= (uint32_t)wavestream_buf_bytes(nw)) return nw;
     return 0;
 }
 
@@ -182,6 +182,169 @@ uint32_t resize_cropped_stream_blocks(uint32_t crop_w, uint32_t x0, uint32_t pit
     if (x0 == 0 && crop_w == pitch && pitch % 16 == 0 && pitch % 256 != 0) p = pitch;
     *wp = p;
     return stream_blocks_per_chunk(p, cls == 1 ? kStreamBufS : kStreamBufM);
+}
+
+static bool aligned16(const HashCall &c) { return ((uintptr_t)c.base | c.frame_stride | c.clip_stride) % 16 == 0; }
+
+// a stream route's values: the per-wave form (band table, nw waves) where the width takes it, else the chunk form; the K-split form
+static void route_stream(HashPlan &p, uint32_t w, int nw)
+{
+    p.route = nw ? HashRoute::kWaveStream : HashRoute::kChunkStream;
+    p.layout_h = nw ? kMfmaLayoutHorizontalBand : kMfmaLayoutHorizontal;
+    p.waves = nw;
+    if (!nw) stream_class(w, &p.nb);
+}
+static void route_ksplit(HashPlan &p, uint32_t w)
+{
+    uint32_t wp = 0;
+    p.route = HashRoute::kKsplit;
+    p.nb = ksplit_geometry(w, &wp);
+}
+
+// The fused family (one kernel resizes, transforms and hashes).  The persistent kernels load 16 bytes at a time without looking at the buffer's
+// end.  With W % 16 == 0 no load crosses a row's end; with any other width a row's last load runs up to 15 bytes into what follows - the next row,
+// frame or clip, all inside the buffer, at zero coefficients - except behind the LAST clip: that one goes to the one-workgroup-per-clip kernel and
+// its careful loader (round 5).
+static void plan_fused(const HashCall &c, const HashKnobs &k, HashPlan &p)
+{
+    const bool persistent_ok = !k.hash_no_persistent && p.n_kt <= 4 && p.n_rg <= 4;
+    // (clips that overlap or repeat - clip_stride below 16, e.g. 0: one clip hashed n times - end within 15 bytes of the buffer's end more than
+    // once: then no clip may take the unchecked loads, and all of them go to the one-workgroup-per-clip kernel)
+    p.last_clip_apart = persistent_ok && c.w % 16 != 0 && c.n_clips >= 2 && c.clip_stride >= 16;
+    if (!persistent_ok || !(c.w % 16 == 0 || p.last_clip_apart)) {
+        p.route = HashRoute::kPerClipFused;
+    } else if (p.n_kt == 1 && p.n_rg == 1) {
+        p.route = HashRoute::kPersistentOneTile;
+        p.full_tile = c.w == 64 && c.h == 64;
+    } else {  // up to 256 x 256: units of eight loads per lane in flight, persistent; 129 ... 256 rows: four row groups (the fourth may be empty)
+        p.route = HashRoute::kTiled;
+        p.tiled_nrg = p.n_rg > 2 ? 4 : p.n_rg;
+        p.waves = tiled_waves(p.n_kt, p.tiled_nrg);
+    }
+}
+
+HashPlan plan_hash(const HashCall &c, const HashKnobs &k, TableFit fit)
+{
+    HashPlan p;
+    p.n_kt = (int)((c.w + 63) / 64);
+    p.n_rg = (int)((c.h + 63) / 64);
+    if (c.w == 16 && c.h == 16 && aligned16(c)) { p.route = HashRoute::kDirect16; return p; }  // the resize is a copy
+    if (k.resize_mode == 1) { p.route = HashRoute::kScalar; return p; }
+    // tables that do not fit the i8 split: the scalar fixed-point kernel (any coefficient range); a forced mode refuses
+    if (fit == TableFit::kNoPlain) { p.route = k.resize_mode == 0 ? HashRoute::kScalar : HashRoute::kRefused; return p; }
+    // Resize on the matrix cores (exact i8 x i8 -> i32): small frames fuse the DCT into the same kernel.
+    // frames taller than two 64-row groups go to the per-frame kernels; the whole-line form is the default
+    // (round 5: except the wide, short ones that stream faster - resize_short_prefers_stream - where they are eligible to)
+    // (and the narrow ones of up to 256 rows that the tiled persistent kernel serves better than the stream kernels - resize_tall_prefers_tiled)
+    const bool eligible = resize_stream_eligible(c.base, c.w, c.h, c.frame_stride, c.clip_stride, k.wavestream_knob);
+    const bool fused = k.resize_mode == 3 || (k.resize_mode == 0 && p.n_rg <= 2 && !(resize_short_prefers_stream(c.w, c.h) && eligible)) ||
+                       (k.resize_mode == 0 && !k.hash_no_persistent && resize_tall_prefers_tiled(c.w, c.h));
+    if (fused) { plan_fused(c, k, p); return p; }
+    // tightly packed frames stream linearly through LDS where that is the faster form (resize_stream_eligible); wide frames take the horizontal
+    // table in band form (= the per-wave form), and leave the stream form where that table does not fit
+    const int nw = resize_wavestream_waves(c.w, k.wavestream_knob);
+    const bool streamed = (k.resize_mode == 0 || k.resize_mode == 5) && eligible && !(nw != 0 && fit == TableFit::kNoBand);
+    // frames wider than the per-wave buffers (1920 columns): the K-split form, table in registers (measured against the
+    // whole-line kernel: 3840 wide 5.6 -> 6.7 TB/s, 2560 5.5 -> 6.2, 2000 3.6 -> 5.8, 2048 level)
+    const bool ksplit = ((k.resize_mode == 0 && !streamed && c.w > 1920) || k.resize_mode == 6) &&
+                        resize_ksplit_eligible(c.base, c.w, c.h, c.frame_stride, c.clip_stride);
+    if (ksplit) route_ksplit(p, c.w);
+    else if (streamed) route_stream(p, c.w, nw);
+    else { p.route = HashRoute::kWholeLine; p.layout_v = kMfmaLayoutVerticalWide; }
+    return p;
+}
+
+CropPlan plan_cropped(const HashCall &c, const HashKnobs &k, const uint32_t *crops, const CropTableFit &fit)
+{
+    CropPlan p;
+    const uint32_t w = c.w, h = c.h;
+    const auto bad_box = [&](size_t i) { return (uint64_t)crops[4 * i] + crops[4 * i + 1] >= w || (uint64_t)crops[4 * i + 2] + crops[4 * i + 3] >= h; };  // crop.rs:21-22
+    const bool tall = (h + 63) / 64 > 2, ends16 = ((uint64_t)w * h) % 16 == 0 && (uint64_t)w * h < (1ull << 31);
+    // small frames (round 5): one workgroup per CLIP, a wave per four frames, resize + DCT (resize_dct_hash_cropped_small_kernel); it checks
+    // the boxes in its own single pass over them
+    if (!tall && w <= 256 && k.resize_mode == 0 && !k.no_smallcrop) { p.kind = CropPlan::kSmall; return p; }
+    // Three kernels read crop boxes in place; a call is dealt out between the first two by box shape, clip by clip (each entry of a
+    // launch names its clip of the batch: CropStreamClip::src_clip), and one dct_hash launch follows over the whole batch:
+    //  * ROWCROP stream kernels - full-width boxes (top / bottom bars only: a 2.39 : 1 film in a 16 : 9 frame, the commonest letterbox;
+    //    clips without bars among them are boxes of the whole frame).  The box is a contiguous range of rows at the frame's own pitch,
+    //    so it streams like a shorter frame: the kernel the uncropped call would take at that width (per-wave, chunk or K-split form)
+    //    with a per-clip first row, height and vertical table.
+    //  * the cropped stream kernel - boxes with side bars (pillarboxed clips): rows x0 .. x0 + w of the box go through LDS by gather
+    //    DMA.  Also full-width boxes where no ROWCROP kernel applies and the pitch is not a multiple of the 128-byte line.
+    //    Measured, detect + crop + hash against the whole-line kernel below: 854x480 1.68 -> 1.24 ms per 1000 clips, 720x576 1.42 -> 1.14,
+    //    426x240 x4000 1.85 -> 1.33, 1366x768 x500 2.19 -> 1.95; pillarboxed 1920x1080 x1000 crop + hash 7.7 -> 5.5 ms, 1280x720 x2000
+    //    6.4 -> 3.9, 1536x864 4.5 -> 2.9, 640x360 x4000 3.4 -> 2.5; 1024 wide 3.5 -> 3.8: stays (gpurun_out/r03pb).
+    //  * the whole-line cropped kernel - everything else: misaligned buffers, frames that do not end on 16 bytes, short frames,
+    //    boxes whose tables do not fit the i8 split, VDF_RESIZE_MODE=4.
+    std::vector<uint32_t> side;
+    for (size_t i = 0; i < c.n_clips; i++) {
+        if (bad_box(i)) { p.kind = CropPlan::kBadBox; return p; }
+        (crops[4 * i] == 0 && crops[4 * i + 1] == 0 ? p.rows : side).push_back((uint32_t)i);
+    }
+    // -- can the full-width boxes take a ROWCROP kernel, and which?
+    if (k.resize_mode == 0 && tall && !p.rows.empty() && (resize_rowcrop_streams(w) || k.rowcrop_all) && !k.no_rowcrop && fit.rows_table && fit.height_tables) {
+        if (resize_stream_eligible(c.base, w, h, c.frame_stride, c.clip_stride, k.wavestream_knob)) route_stream(p.rows_kernel, w, resize_wavestream_waves(w, k.wavestream_knob));
+        else if (w > 1920 && resize_ksplit_eligible(c.base, w, h, c.frame_stride, c.clip_stride)) route_ksplit(p.rows_kernel, w);
+    }
+    if (p.rows_kernel.route == HashRoute::kRefused) p.rest.swap(p.rows);
+    // -- boxes with side bars that share their column range: the per-wave kernel gathers the box (one launch per distinct range)
+    if (k.resize_mode == 0 && tall && ends16 && aligned16(c) && !side.empty() && !k.no_boxstream && !k.no_rowcrop && fit.height_tables) {
+        std::map<uint64_t, size_t> by_range;  // (x0, width) -> group
+        std::vector<CropBoxGroup> cand;
+        for (uint32_t i : side) {
+            const uint32_t l = crops[4 * i], bw = w - l - crops[4 * i + 1];
+            auto it = by_range.find(crop_range_key(l, bw));
+            if (it == by_range.end()) {
+                it = by_range.emplace(crop_range_key(l, bw), cand.size()).first;
+                cand.push_back(CropBoxGroup{l, bw, resize_wavestream_waves_box(w, l, bw, k.wavestream_knob), {}});
+            }
+            cand[it->second].ids.push_back(i);
+        }
+        for (CropBoxGroup &g : cand) {
+            // (a launch per range: ranges shared by fewer than four clips - a launch would leave most CUs idle - and the ranges beyond sixteen
+            // are left to the gather kernel)
+            const bool no_table = std::find(fit.ranges_without_table.begin(), fit.ranges_without_table.end(), crop_range_key(g.x0, g.box_w)) != fit.ranges_without_table.end();
+            if (g.waves && g.ids.size() >= kMinCropBoxGroupClips && p.groups.size() < kMaxCropBoxGroups && !no_table) p.groups.push_back(std::move(g));
+            else p.rest.insert(p.rest.end(), g.ids.begin(), g.ids.end());
+        }
+    } else {
+        p.rest.insert(p.rest.end(), side.begin(), side.end());
+    }
+    if (p.rows.empty() && p.groups.empty()) {  // nothing streams per clip: the whole call through one general kernel
+        p.rows_kernel = HashPlan();
+        p.rest.resize(c.n_clips);
+        for (size_t i = 0; i < c.n_clips; i++) p.rest[i] = (uint32_t)i;
+    }
+    // the general kernel for the rest: the cropped stream kernel for side-bar boxes at every pitch but 1024 and for full-width boxes where the
+    // pitch is not line-aligned (measured above) - if every box fits its chunk buffers - else the whole-line kernel
+    bool rest_has_side = false;
+    for (uint32_t i : p.rest) rest_has_side = rest_has_side || crops[4 * i] != 0 || crops[4 * i + 1] != 0;
+    p.rest_gather = !p.rest.empty() && fit.gather_tables && tall && ends16 && (((uintptr_t)c.base | c.frame_stride | c.clip_stride) & 3) == 0 &&
+                    (k.resize_mode == 0 || k.resize_mode == 5) && resize_cropped_stream_class(w, &p.gather_cls) &&
+                    (k.resize_mode == 5 || (rest_has_side ? w != 1024 : w % 128 != 0));
+    p.gather_shift = (w & 3u) != 0;
+    for (size_t j = 0; j < p.rest.size() && p.rest_gather; j++) {
+        const uint32_t i = p.rest[j], x0 = crops[4 * i], bw = w - x0 - crops[4 * i + 1], bh = h - crops[4 * i + 2] - crops[4 * i + 3];
+        uint32_t wp = 0;
+        const uint32_t nb = resize_cropped_stream_blocks(bw, x0, w, p.gather_cls, &wp);
+        p.gather_shift = p.gather_shift || (x0 & 3u) != 0;
+        if (nb == 0 || (nb < 2 && bh > 16)) p.rest_gather = false;  // one block per chunk would leave three of the four waves idle
+    }
+    return p;
+}
+
+LetterboxPlan plan_letterbox(const HashCall &c, const HashKnobs &k)
+{
+    // Small frames (round 6): the boxes never visit the host.  Every box size's tables are resident, so
+    //  * frames of at most 64 x 64 take ONE kernel that detects, crops, resizes, transforms and hashes (letterbox_resize_dct_hash_small_kernel);
+    //    the clips within 64 bytes of the buffer's end (the last one, as a rule) take the route below for its careful loader;
+    //  * other small frames: the two detect kernels, then the one-workgroup-per-clip kernel reads each clip's box where they left it.
+    LetterboxPlan p{};
+    p.small_frames = (c.h + 63) / 64 <= 2 && c.w <= 256 && k.resize_mode == 0 && !k.no_smallcrop && !k.lb_host_plan;
+    p.one_tile = p.small_frames && c.w <= 64 && c.h <= 64 && !k.no_lb_fused;
+    // clip i's loads stay inside the buffer iff it ends at least 64 bytes before the last clip does: (n - 1 - i) * clip_stride >= 64
+    p.n_tail = !p.one_tile || c.clip_stride == 0 ? c.n_clips : std::min<size_t>(c.n_clips, (64 + c.clip_stride - 1) / c.clip_stride);
+    return p;
 }
 
 }  // namespace vdf

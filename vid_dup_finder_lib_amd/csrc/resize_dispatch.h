@@ -58,6 +58,7 @@ bool resize_wavestream_applies(uint32_t w, int knob = 0);
 // copy of whole rows, 1 gather, 2 gather + the operand shift for rows that start off a dword), and the wave count (0: not this kernel)
 uint32_t box_stream_pitch(uint32_t frame_w, uint32_t x0, uint32_t box_w, int *mode);
 int resize_wavestream_waves_box(uint32_t frame_w, uint32_t x0, uint32_t box_w, int knob = 0);
+constexpr int wavestream_buf_bytes(int nw) { return nw == 3 ? kWaveStreamBuf3 : nw == 4 ? kWaveStreamBuf : nw == 5 ? kWaveStreamBuf5 : nw == 6 ? kWaveStreamBuf6 : nw == 8 ? kWaveStreamBuf8 : 0; }
 bool resize_wavestream_table_fits(int nw, int band_stride);  // does a band table of that stride (bytes per output) fit the nw-wave kernel's table array
 // Clips whose crop boxes are full-width (top / bottom bars only): do the ROWCROP instantiations of the stream kernels beat the general
 // cropped kernels at this frame width?  (measured; the frame must also pass resize_stream_eligible / resize_ksplit_eligible)
@@ -78,5 +79,70 @@ bool resize_ksplit_eligible(const uint8_t *frames, uint32_t w, uint32_t h, size_
 // pitch and the blocks per chunk (a full-width box at a pitch without 16-way conflicts keeps the frame's pitch: linear DMA)
 bool resize_cropped_stream_class(uint32_t pitch, int *cls);
 uint32_t resize_cropped_stream_blocks(uint32_t crop_w, uint32_t x0, uint32_t pitch, int cls, uint32_t *wp);
+
+// ---- The planner: which kernel hashes a call.  Pure host arithmetic over the call and the context's knobs; api.cpp
+// fetches the tables a plan names and switches on its route, the launchers of dct_hash.hip switch on its values.  tests/cpp/resize_dispatch_main.cpp
+// enumerates it: every route's preconditions hold for every width, and the documented sizes land on the documented kernels.
+struct HashKnobs {  // copied from vdf_ctx (vdf_ctx.h says which VDF_* variable sets each)
+    int resize_mode = 0, wavestream_knob = 0;
+    bool hash_no_persistent = false, no_rowcrop = false, rowcrop_all = false, no_boxstream = false, no_smallcrop = false, lb_host_plan = false,
+         no_lb_fused = false;
+};
+struct HashCall {
+    const uint8_t *base;  // for its alignment only
+    uint32_t w, h;
+    size_t frame_stride, clip_stride, n_clips;
+};
+// one value per row of DESIGN.md 4.1; kRefused: a forced mode whose tables do not fit the i8 split (VDF_E_BAD_DIMS)
+enum class HashRoute { kRefused, kDirect16, kPersistentOneTile, kTiled, kPerClipFused, kChunkStream, kWaveStream, kKsplit, kWholeLine, kScalar };
+// What a plan cannot know before the tables are built; the caller plans again with what it found.
+enum class TableFit { kAll, kNoBand /* the width's band table does not fit */, kNoPlain /* a plain table does not fit the i8 split */ };
+struct HashPlan {
+    HashRoute route = HashRoute::kRefused;
+    int layout_h = kMfmaLayoutHorizontal, layout_v = kMfmaLayoutVertical;  // the MFMA tables to fetch (none: kDirect16, kScalar, kRefused)
+    int n_kt = 0, n_rg = 0;        // 64-column / 64-row tiles of the frame
+    int tiled_nrg = 0, waves = 0;  // kTiled: the <NKT = n_kt, NRG, WAVES> instantiation; kWaveStream: waves per workgroup
+    uint32_t nb = 0;               // kChunkStream / kKsplit: 16-row blocks per chunk
+    bool full_tile = false;        // kPersistentOneTile: exactly 64 x 64 (the <FULL> instantiation)
+    bool last_clip_apart = false;  // the persistent kernels: the last clip goes through the per-clip kernel and its careful loader
+};
+HashPlan plan_hash(const HashCall &c, const HashKnobs &k, TableFit fit = TableFit::kAll);
+
+// resize_dct_hash_tiled_kernel<NKT, NRG, WAVES>: WAVES (the second __launch_bounds__ argument) by [NKT - 1][NRG = 1, 2, 4]; measured
+// (profiles/r05_short_frames.txt).  0: no such instantiation (one tile is the persistent kernel's).
+constexpr int kTiledWaves[4][3] = {{0, 1, 3}, {1, 3, 2}, {3, 3, 3}, {2, 2, 2}};
+constexpr int tiled_waves(int nkt, int nrg) { return kTiledWaves[nkt - 1][nrg == 4 ? 2 : nrg - 1]; }
+
+// Cropped calls (crops: HOST array [n_clips][4] = left, right, top, bottom, not all zero).  Small frames take one kernel; otherwise every clip
+// goes to exactly one part: full-width boxes on a ROWCROP launch, side-bar boxes that share a column range on per-wave box launches, the rest
+// on one general kernel (the gather stream kernel or the whole-line cropped kernel).
+struct CropTableFit {  // what building the tables showed; the caller plans again with each fact it finds
+    bool rows_table = true;     // the frame width's horizontal table in the ROWCROP launch's layout fits
+    bool height_tables = true;  // every box height's vertical table fits (false: the whole call through one general kernel)
+    bool gather_tables = true;  // the tables of the rest's boxes fit the gather stream kernel
+    std::vector<uint64_t> ranges_without_table;  // crop_range_key of the column ranges whose band table does not fit (the i8 split, or that wave count's array)
+};
+constexpr uint64_t crop_range_key(uint32_t x0, uint32_t box_w) { return ((uint64_t)x0 << 32) | box_w; }
+struct CropBoxGroup { uint32_t x0, box_w; int waves; std::vector<uint32_t> ids; };
+constexpr size_t kMaxCropBoxGroups = 16, kMinCropBoxGroupClips = 4;
+struct CropPlan {
+    enum Kind { kBadBox /* a box leaves no pixels */, kSmall /* resize_dct_hash_cropped_small_kernel */, kParts } kind = kParts;
+    HashPlan rows_kernel;              // the ROWCROP launch: kChunkStream, kWaveStream or kKsplit; kRefused = none
+    std::vector<uint32_t> rows;        // its clips
+    std::vector<CropBoxGroup> groups;  // per-wave box launches, one per column range
+    std::vector<uint32_t> rest;        // the general kernel's clips
+    bool rest_gather = false;          // resize_mfma_cropped_stream_kernel, else resize_mfma_cropped_kernel
+    int gather_cls = 0;                // its buffer class (resize_cropped_stream_class)
+    bool gather_shift = false;         // some row of some box of the rest starts off a dword boundary
+};
+CropPlan plan_cropped(const HashCall &c, const HashKnobs &k, const uint32_t *crops, const CropTableFit &fit = CropTableFit());
+
+// The letterbox entry: small frames keep their boxes on the device; everything else detects, copies the boxes down and takes plan_cropped.
+struct LetterboxPlan {
+    bool small_frames;   // (needs the frame size's BoxTableSet to be usable, else the host route)
+    bool one_tile;       // ... of at most 64 x 64: the fused detect + hash kernel for all but the last n_tail clips
+    size_t n_tail;       // clips within 64 bytes of the buffer's end: the device-box route and its careful loader
+};
+LetterboxPlan plan_letterbox(const HashCall &c, const HashKnobs &k);
 
 }  // namespace vdf

@@ -94,31 +94,33 @@ struct MfmaResizeArgs {  // device pointers to the MFMA-layout tables (resize_ta
     int32_t prec_h, prec_v, n_kt, n_rg;
     const int32_t *band_meta = nullptr;  // bh in band form (resize_tables.h): kt_lo[16], nt[16] on the device
     int32_t band_stride = 0;
-    int32_t no_persistent = 0;         // debugging: force the one-clip-per-workgroup fused kernel
     int32_t persistent_wgs_per_cu = 3; // resident workgroups per CU for the persistent kernel
-    int32_t wavestream_knob = 0;       // vdf_ctx::wavestream_knob (resize_dispatch.h): the launcher must decide as the caller did
 };
+// The launchers take the route and its values from the plan (resize_dispatch.h: plan_hash) and only guard their kernels' preconditions.
+// plan.route = kPersistentOneTile, kTiled or kPerClipFused
 hipError_t launch_resize_dct_fused(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h, size_t frame_stride,
-                                   size_t clip_stride, const uint8_t *buf_end, const MfmaResizeArgs &a,
+                                   size_t clip_stride, const uint8_t *buf_end, const MfmaResizeArgs &a, const HashPlan &plan,
                                    const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare,
                                    hipStream_t stream);
+// the whole-line kernel (a.av in kMfmaLayoutVerticalWide order)
 hipError_t launch_resize_mfma_frames(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h,
                                      size_t frame_stride, size_t clip_stride, const uint8_t *buf_end,
-                                     const MfmaResizeArgs &a, uint8_t *small, bool wide, hipStream_t stream);
+                                     const MfmaResizeArgs &a, uint8_t *small, hipStream_t stream);
 // linear-stream form for tightly packed frames whose width is a multiple of 16 but not of the 128-byte line
-// (a.av in kMfmaLayoutVertical order); resize_stream_eligible says whether a call qualifies
+// (a.av in kMfmaLayoutVertical order); plan.route = kChunkStream (a.bh plain, plan.nb blocks per chunk) or kWaveStream (a.bh in band form,
+// plan.waves waves per workgroup)
 // clips / tables (both or neither): per-clip row ranges - clip c contributes rows y0 .. y0 + h of its frames (full-width crop
 // boxes: top / bottom letterbox bars), resized with vertical table entry v_table; a.av / a.bias_v / a.prec_v / a.n_rg are then unused
 struct CropStreamClip;
 struct CropStreamTable;
 hipError_t launch_resize_mfma_frames_stream(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h,
-                                            size_t frame_stride, size_t clip_stride, const MfmaResizeArgs &a,
+                                            size_t frame_stride, size_t clip_stride, const MfmaResizeArgs &a, const HashPlan &plan,
                                             uint8_t *small, hipStream_t stream, const CropStreamClip *clips = nullptr,
                                             const CropStreamTable *tables = nullptr);
 // K-split form for wide frames (1024..4096 columns, a multiple of 16): horizontal table in registers, a.bh in plain
-// kMfmaLayoutHorizontal form, a.av in kMfmaLayoutVertical order
+// kMfmaLayoutHorizontal form, a.av in kMfmaLayoutVertical order; plan.route = kKsplit, plan.nb blocks per chunk
 hipError_t launch_resize_mfma_frames_ksplit(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h,
-                                            size_t frame_stride, size_t clip_stride, const MfmaResizeArgs &a,
+                                            size_t frame_stride, size_t clip_stride, const MfmaResizeArgs &a, const HashPlan &plan,
                                             uint8_t *small, hipStream_t stream, const CropStreamClip *clips = nullptr,
                                             const CropStreamTable *tables = nullptr);
 // ---- letterbox crop detection + cropped resize -------------------------------------------
@@ -152,10 +154,10 @@ hipError_t launch_resize_mfma_cropped_stream(const uint8_t *frames, size_t n_cli
                                              const CropStreamTable *tables, int cls, bool shift, uint8_t *small,
                                              hipStream_t stream);  // shift: some row of some box starts off a dword boundary
 // crop boxes that share their column range (x0, box_w; e.g. the 4 : 3 picture of every pillarboxed clip in a 16 : 9 batch): the per-wave
-// stream kernel gathers the box's bytes of each row; a = the band table of box_w; per-clip rows as in the ROWCROP launches
+// stream kernel gathers the box's bytes of each row; a = the band table of box_w; waves = the group's (CropBoxGroup); per-clip rows as in the ROWCROP launches
 hipError_t launch_resize_mfma_box_wavestream(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h, size_t frame_stride,
-                                             size_t clip_stride, const MfmaResizeArgs &a, uint32_t x0, uint32_t box_w, const CropStreamClip *clips,
-                                             const CropStreamTable *tables, uint8_t *small, hipStream_t stream);
+                                             size_t clip_stride, const MfmaResizeArgs &a, uint32_t x0, uint32_t box_w, int waves,
+                                             const CropStreamClip *clips, const CropStreamTable *tables, uint8_t *small, hipStream_t stream);
 // work: scratch of letterbox_work_bytes(n_clips, frames_per_clip) bytes (the list of frames whose side bars a second pass walks)
 size_t letterbox_work_bytes(size_t n_clips, uint32_t frames_per_clip);
 // side_strips: 0 = by frame height (32 column strips per pass from 512 rows, 16 from 256, else 8), 16 = at most 16 (VDF_LB_NC16: A/B runs)
