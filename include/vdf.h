@@ -204,6 +204,34 @@ int vdf_hash_frames_u8_letterbox(vdf_ctx *ctx, const uint8_t *frames, size_t n_c
                                  uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride, uint64_t *out_hashes,
                                  uint32_t *out_crops, uint32_t *out_dontcare);
 
+/* ---- clips of DIFFERENT frame sizes in one call ----------------------------------------------------
+ * A library holds dozens of resolutions and its files arrive in any order.  All clips of a call live in ONE
+ * buffer of buf_bytes bytes and name their place by offset: every address is checked against that buffer on
+ * the host, over all clips, before anything is queued (a rejected call launches nothing).  Clip i's hash lands
+ * at out_hashes + 16 i (out_dontcare[i]), whatever order the kernels take the clips in.  Rows are tightly
+ * packed (w bytes apart); the crop box is read in place, as in vdf_hash_frames_u8_cropped_device.
+ * Errors, in this order, each message naming the first offending clip: frames_per_clip < 16 ->
+ * VDF_E_NOT_ENOUGH_FRAMES; a zero dimension -> VDF_E_BAD_DIMS; frame_stride < w*h -> VDF_E_INVAL; a box that
+ * leaves no pixels -> VDF_E_INVAL; offset + 15*frame_stride + w*h > buf_bytes -> VDF_E_INVAL; a box size whose
+ * coefficients do not fit the i8 split -> VDF_E_BAD_DIMS.
+ * Clips that all share (w, h, frame_stride) at offsets one positive step apart take exactly the kernels of
+ * vdf_hash_frames_u8[_cropped]_device.  A multi-GPU context refuses both calls with VDF_E_INVAL. */
+typedef struct vdf_clip {      /* 40 bytes */
+    uint64_t offset;           /* first byte of frame 0, relative to the buffer */
+    uint64_t frame_stride;     /* bytes between frames, >= w*h */
+    uint32_t w;
+    uint32_t h;
+    uint32_t crop_left;        /* the four edge offsets of the crop box (crop.rs:3-10), in the order of the `crops` arrays above; */
+    uint32_t crop_right;       /* all zero = whole frame */
+    uint32_t crop_top;
+    uint32_t crop_bottom;
+} vdf_clip;
+int vdf_hash_clips_u8(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips,
+                      uint32_t frames_per_clip, uint64_t *out_hashes, uint32_t *out_dontcare);
+/* clips: HOST array.  The call returns once the descriptors have left the host; the hashes are ordered on `stream`. */
+int vdf_hash_clips_u8_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips,
+                             uint32_t frames_per_clip, uint64_t *d_out_hashes, uint32_t *d_out_dontcare, void *stream);
+
 /* ---- search(): replaces Search::search_self, search_algorithm.rs:81-171 (hot loop :150-156) --
  * hashes: n x 16 words, durations: n, both in sorted order.  tol_int from vdf_tolerance_int().
  * Groups come back exactly as search() builds them (video_dup_finder.rs:7-13): members = hits in
@@ -355,6 +383,19 @@ int vdf_hash_queue_stats(vdf_hash_queue *q, uint64_t *n_batches, uint64_t *n_cli
  * second batch was collected and launched while the first was still running). */
 int vdf_hash_queue_in_flight_max(vdf_hash_queue *q, uint32_t *out);
 void vdf_hash_queue_destroy(vdf_hash_queue *q);
+
+/* The same queue for clips of ANY frame size: one queue serves a whole library, whatever resolutions its files have.
+ * A batch closes when max_batch clips joined, when the next clip would not fit the slot's staging_bytes of pinned
+ * memory, or when its first caller has waited max_wait_us; the batch is hashed by one vdf_hash_clips_u8 call.
+ * slots_per_gpu: batches in the making per GPU, 0 = 2, at most 16.  frames = 16 gray frames of w x h, tightly packed;
+ * blocks until the hash is there.  A clip of more than staging_bytes (16 * w * h) -> VDF_E_INVAL. */
+typedef struct vdf_hash_queue_mixed vdf_hash_queue_mixed;
+int vdf_hash_queue_create_mixed(vdf_ctx *ctx, size_t staging_bytes, uint32_t max_batch, uint32_t max_wait_us,
+                                uint32_t slots_per_gpu, vdf_hash_queue_mixed **out);
+int vdf_hash_queue_mixed_submit(vdf_hash_queue_mixed *q, const uint8_t *frames, uint32_t w, uint32_t h, uint64_t *out_hash);
+int vdf_hash_queue_mixed_stats(vdf_hash_queue_mixed *q, uint64_t *n_batches, uint64_t *n_clips);
+int vdf_hash_queue_mixed_in_flight_max(vdf_hash_queue_mixed *q, uint32_t *out);
+void vdf_hash_queue_mixed_destroy(vdf_hash_queue_mixed *q);
 
 /* ---- the app's Sorting::Distance key (vid_dup_finder_app/src/app/search_output.rs:43-60) ----------
  * out_max[g] = max hamming distance over all pairs of group g's contained paths: its members (indices

@@ -15,14 +15,14 @@ OUT = os.path.join(ROOT, "rust", "vdf-sys", "src", "lib.rs")
 
 SCALARS = {"int": "c_int", "uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int32_t": "i32", "int64_t": "i64", "size_t": "usize",
            "double": "f64", "float": "f32", "long long": "c_longlong", "unsigned long long": "c_ulonglong", "char": "c_char", "void": "c_void"}
-OPAQUE = ("vdf_ctx", "vdf_hash_queue")
+OPAQUE = ("vdf_ctx", "vdf_hash_queue", "vdf_hash_queue_mixed")
 
 # one line of context per group of entry points (the header has the contracts; this is the map from the crate's side)
 GROUPS = [
     ("context", r"vdf_ctx_|vdf_last_error|vdf_version|vdf_live_"),
     ("host helpers: hamming_distance (video_hash.rs:190-192,311-317), the tolerance cast (search_algorithm.rs:64,82), window counts",
      r"vdf_hamming_u1024|vdf_tolerance_int|vdf_count_pairs_|vdf_groups_free|vdf_buffer_free"),
-    ("VideoHash::from_frames (video_hash.rs:45-73) and Cropdetect::Letterbox in front of it (video_hash_builder.rs:188-212)", r"vdf_hash_frames_|vdf_cropdetect_"),
+    ("VideoHash::from_frames (video_hash.rs:45-73) and Cropdetect::Letterbox in front of it (video_hash_builder.rs:188-212)", r"vdf_hash_frames_|vdf_hash_clips_|vdf_cropdetect_"),
     ("search() / search_with_references() (video_dup_finder.rs:7-46 over search_algorithm.rs:63-185)", r"vdf_search_self$|vdf_search_refs$"),
     ("device-resident building blocks: sharding over processes, Search::sort on the device, the host replay", r"vdf_search_(self|refs)_device|vdf_bitmap_or|vdf_sort_|vdf_apply_|vdf_row_tile|vdf_replay_|vdf_groups_finish|vdf_groups_from"),
     ("multi-GPU contexts: shards already resident on the devices", r"_shards$"),

@@ -83,6 +83,12 @@ class VdfCacheSearchTiming(C.Structure):
                 ("map_ms", C.c_float), ("total_ms", C.c_float)]
 
 
+class VdfClip(C.Structure):
+    """One clip of a vdf_hash_clips_u8[_device] call: 40 bytes (the numpy twin is CLIP_DTYPE)."""
+    _fields_ = [("offset", C.c_uint64), ("frame_stride", C.c_uint64), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("crop_left", C.c_uint32), ("crop_right", C.c_uint32), ("crop_top", C.c_uint32), ("crop_bottom", C.c_uint32)]
+
+
 AGREE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64))
 OR_BITMAP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -140,6 +146,9 @@ SIGNATURES = {
                                                             C.c_void_p]),
     "vdf_hash_frames_u8_letterbox": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vdf_hash_clips_u8": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vdf_hash_clips_u8_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
     "vdf_sort_order_paths": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]),
     "vdf_search_self": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(VdfGroups)]),
     "vdf_search_refs": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -177,6 +186,11 @@ SIGNATURES = {
     "vdf_hash_queue_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vdf_hash_queue_in_flight_max": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "vdf_hash_queue_destroy": (None, [C.c_void_p]),
+    "vdf_hash_queue_create_mixed": (C.c_int, [_ctx, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "vdf_hash_queue_mixed_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "vdf_hash_queue_mixed_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vdf_hash_queue_mixed_in_flight_max": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "vdf_hash_queue_mixed_destroy": (None, [C.c_void_p]),
     "vdf_groups_max_distance": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(VdfGroups),
                                           C.c_void_p]),
     "vdf_cache_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(VdfCacheSoa)]),

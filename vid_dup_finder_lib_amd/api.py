@@ -413,9 +413,12 @@ def search_with_references(ref_hashes: Iterable[VideoHash], new_hashes: Iterable
 def hash_frame_stacks(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int],
                       engine: Optional[Engine] = None) -> List[VideoHash]:
     """Batched VideoHash.from_frames: frames [n_clips, n_frames >= 16, H, W] u8 -> one VideoHash per clip
-    (the batching a caller of VideoHashBuilder::hash would do to feed the GPU; SURVEY.md section 8f N2)."""
+    (the batching a caller of VideoHashBuilder::hash would do to feed the GPU; SURVEY.md section 8f N2).
+    frames may also be a LIST of [n_frames >= 16, H, W] stacks of different frame sizes (files arrive in whatever resolution they
+    have): they are hashed by one call all the same (Engine.hash_clips)."""
     try:
-        words = (engine or default_engine()).hash_frames(frames)
+        eng = engine or default_engine()
+        words = eng.hash_clips(frames) if isinstance(frames, (list, tuple)) else eng.hash_frames(frames)
     except VdfError as e:
         if e.code == _capi.VDF_E_NOT_ENOUGH_FRAMES:
             raise NotEnoughFrames() from e
@@ -427,7 +430,8 @@ def gen_hashes(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int]
                cropdetect: Cropdetect = Cropdetect.LETTERBOX, engine: Optional[Engine] = None) -> List[VideoHash]:
     """The part of `gen_hash` after decode (video_hash_builder.rs:214-223) for a batch of clips:
     crop_video_frames(cropdetect) -- default Letterbox, like CreationOptions::default (:55-63) -- then
-    VideoHash::from_frames.  frames [n_clips, n_frames >= 16, H, W] u8.  Detection (frames 0 and 8,
+    VideoHash::from_frames.  frames [n_clips, n_frames >= 16, H, W] u8 (with Cropdetect.NONE also a list of stacks of different frame
+    sizes: hash_frame_stacks).  Detection (frames 0 and 8,
     video_frames_gray.rs:201-210) and the cropped resize both run on the GPU; no cropped copies are made."""
     if cropdetect == Cropdetect.NONE:
         return hash_frame_stacks(frames, src_paths, durations, engine)

@@ -586,7 +586,7 @@ int ensure_cos_table(vdf_ctx *ctx, hipStream_t stream)
     return VDF_OK;
 }
 
-constexpr size_t kMaxClipsPerLaunch = 256 * 1024;  // x 16 frames x 256 threads stays under HIP's 2^32 work-item grid limit
+using vdf::kMaxClipsPerLaunch;  // (resize_dispatch.h: the mixed planner cuts its parts by it too)
 
 // One launch's worth of a hash call: at most kMaxClipsPerLaunch clips of it.
 struct HashJob {
@@ -955,6 +955,110 @@ int hash_cropped_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, u
 {
     const HashJob all{d_frames, n_clips, w, h, frame_stride, clip_stride, d_out, d_dc, stream};
     return checked_launches(ctx, all, frames_per_clip, [&](size_t c0, size_t n) { return hash_cropped_launch(ctx, all.clips(c0, n), crops ? crops + 4 * c0 : nullptr); });
+}
+
+// ---- clips of different frame sizes in one call (include/vdf.h: vdf_hash_clips_u8[_device]) ------------------------------------------------------
+static_assert(sizeof(vdf_clip) == sizeof(vdf::MixedClip) && offsetof(vdf_clip, offset) == offsetof(vdf::MixedClip, offset) &&
+              offsetof(vdf_clip, frame_stride) == offsetof(vdf::MixedClip, frame_stride) && offsetof(vdf_clip, w) == offsetof(vdf::MixedClip, w) &&
+              offsetof(vdf_clip, h) == offsetof(vdf::MixedClip, h) && offsetof(vdf_clip, crop_left) == offsetof(vdf::MixedClip, crop) &&
+              offsetof(vdf_clip, crop_bottom) == offsetof(vdf::MixedClip, crop) + 12, "the planner reads vdf_clip as vdf::MixedClip");
+
+int mixed_check_failed(vdf_ctx *ctx, const vdf::MixedCheck &c)
+{
+    const std::string at = " (clip " + std::to_string(c.clip) + ")";
+    switch (c.error) {
+    case vdf::MixedError::kNotEnoughFrames: return fail(ctx, VDF_E_NOT_ENOUGH_FRAMES, "fewer than 16 frames per clip");
+    case vdf::MixedError::kZeroDim: return fail(ctx, VDF_E_BAD_DIMS, "zero frame dimension" + at);
+    case vdf::MixedError::kStrideBelowFrame: return fail(ctx, VDF_E_INVAL, "frame_stride smaller than a frame" + at);
+    case vdf::MixedError::kEmptyBox: return fail(ctx, VDF_E_INVAL, "crop box leaves no pixels" + at);
+    case vdf::MixedError::kOutOfBuffer: return fail(ctx, VDF_E_INVAL, "clip reaches past the end of the buffer" + at);
+    case vdf::MixedError::kNone: break;
+    }
+    return VDF_OK;
+}
+
+// The mixed parts: table entries by box size, every descriptor through the pinned staging in ONE upload for the whole call (so no launch of
+// the call rewrites staging another launch's upload still reads), then the launches of the plan and the DCT of the per-frame parts.
+int hash_mixed_launch(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf::MixedPlan &plan, uint64_t *d_out, uint32_t *d_dc, hipStream_t stream)
+{
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_cos_table(ctx, stream);
+    if (rc) return rc;
+    const size_t n = plan.descs.size(), nd = n * sizeof(vdf::MixedClipDesc), off = (nd + 63) & ~size_t(63);
+    const size_t max_entries = 2 * ((size_t)plan.max_w + plan.max_h + 2);
+    if (!ctx->pin_desc.reserve(off + max_entries * sizeof(vdf::CropTableEntry))) return fail(ctx, VDF_E_OOM, "host staging for the clip descriptors");
+    vdf::MixedClipDesc *dsc = ctx->pin_desc.as<vdf::MixedClipDesc>();
+    vdf::CropTableEntry *ent = reinterpret_cast<vdf::CropTableEntry *>(ctx->pin_desc.as<char>() + off);
+    // two sets: the whole-line part reads its vertical tables in another k order
+    LaunchTables plain(plan.max_w, plan.max_h, vdf::kMfmaLayoutHorizontal, vdf::kMfmaLayoutVertical), wide(plan.max_w, plan.max_h, vdf::kMfmaLayoutHorizontal, vdf::kMfmaLayoutVerticalWide);
+    for (const vdf::MixedLaunch &l : plan.launches) {
+        LaunchTables &tabs = l.part == vdf::MixedPart::kWideLines ? wide : plain;
+        for (size_t i = l.first; i < l.first + l.count; i++) {
+            vdf::MixedClipDesc d = plan.descs[i];
+            const int32_t ih = tabs.entry(ctx, d.bw, false, stream, &rc), iv = ih < 0 ? -1 : tabs.entry(ctx, d.bh, true, stream, &rc);
+            if (iv < 0) return rc ? rc : fail(ctx, VDF_E_BAD_DIMS, "box size whose coefficients do not fit the i8 split (clip " + std::to_string(d.out_index) + ")");
+            d.h_table = (uint32_t)ih; d.v_table = (uint32_t)iv;
+            dsc[i] = d;
+        }
+    }
+    const size_t n_plain = plain.used.size(), n_entries = n_plain + wide.used.size();
+    if (n_entries > max_entries) return fail(ctx, VDF_E_INVAL, "table index of a mixed call outgrew its staging");  // (cannot happen: one entry per size and axis)
+    for (size_t i = 0; i < n_plain; i++) ent[i] = plain.crop_entry(i);
+    for (size_t i = n_plain; i < n_entries; i++) ent[i] = wide.crop_entry(i - n_plain);
+    for (const vdf::MixedLaunch &l : plan.launches)
+        for (size_t i = l.first; i < l.first + l.count; i++) {
+            if (l.part == vdf::MixedPart::kWideLines) { dsc[i].h_table += (uint32_t)n_plain; dsc[i].v_table += (uint32_t)n_plain; }
+            if (dsc[i].h_table >= n_entries || dsc[i].v_table >= n_entries || dsc[i].out_index >= n) return fail(ctx, VDF_E_INVAL, "descriptor names a table or an output that is not there");
+        }
+    const size_t n_frames_part = n - plan.n_small;
+    VDF_HIP(ctx, ctx->small.reserve(std::max<size_t>(n_frames_part, 1) * 4096));
+    if ((rc = upload(ctx, ctx->crop_desc2, dsc, nd, stream))) return rc;
+    if ((rc = upload(ctx, ctx->crop_tables2, ent, n_entries * sizeof(vdf::CropTableEntry), stream))) return rc;
+    VDF_HIP(ctx, hipEventRecord(ctx->ev_mid, stream));
+    const vdf::MixedClipDesc *d_desc = ctx->crop_desc2.as<vdf::MixedClipDesc>();
+    const vdf::CropTableEntry *d_tab = ctx->crop_tables2.as<vdf::CropTableEntry>();
+    const uint8_t *buf_end = d_buf + buf_bytes;
+    uint8_t *small = ctx->small.as<uint8_t>();
+    hipError_t e = hipSuccess;
+    for (const vdf::MixedLaunch &l : plan.launches) {
+        if (e != hipSuccess) break;
+        if (l.part == vdf::MixedPart::kSmall) {
+            e = vdf::launch_mixed_small(d_buf, buf_end, d_desc + l.first, l.count, d_tab, ctx->cos_table.as<double>(), d_out, d_dc, stream);
+        } else {
+            uint8_t *slot0 = small + (l.first - plan.n_small) * 4096;
+            e = vdf::launch_mixed_frames(d_buf, buf_end, d_desc + l.first, l.count, d_tab, l.part == vdf::MixedPart::kWideLines, slot0, stream);
+            if (e == hipSuccess) e = vdf::launch_dct_hash_indexed(slot0, d_desc + l.first, l.count, ctx->cos_table.as<double>(), d_out, d_dc, stream);
+        }
+    }
+    // the staging is read by the two copies: they must have run before the next call on this context rewrites it (the kernels stay queued)
+    const hipError_t ew = hipEventSynchronize(ctx->ev_mid);
+    if (e != hipSuccess) return fail_hip(ctx, e, "mixed hash launch");
+    VDF_HIP(ctx, ew);
+    return VDF_OK;
+}
+
+int hash_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                      uint64_t *d_out, uint32_t *d_dc, hipStream_t stream)
+{
+    if (n_clips && !clips) return fail(ctx, VDF_E_INVAL, "null pointer");
+    if (n_clips > 0xFFFFFFFFull) return fail(ctx, VDF_E_INVAL, "more than 2^32 - 1 clips in one call");
+    const vdf::MixedClip *mc = reinterpret_cast<const vdf::MixedClip *>(clips);
+    const vdf::MixedCheck chk = vdf::check_mixed(mc, n_clips, frames_per_clip, buf_bytes);
+    if (chk.error != vdf::MixedError::kNone) return mixed_check_failed(ctx, chk);
+    if (n_clips == 0) return VDF_OK;
+    if (!d_buf || !d_out) return fail(ctx, VDF_E_INVAL, "null pointer");
+    const vdf::MixedPlan plan = vdf::plan_mixed(mc, n_clips, hash_knobs(ctx));
+    if (plan.kind == vdf::MixedPlan::kUniform) {  // one size, evenly spaced: exactly the uniform call
+        std::vector<uint32_t> crops;
+        if (plan.cropped) {
+            crops.resize(n_clips * 4);
+            for (size_t i = 0; i < n_clips; i++) std::memcpy(&crops[4 * i], mc[i].crop, 16);
+        }
+        const HashJob all{d_buf + plan.offset0, n_clips, mc[0].w, mc[0].h, (size_t)mc[0].frame_stride, (size_t)plan.clip_stride, d_out, d_dc, stream};
+        return checked_launches(ctx, all, frames_per_clip,
+                                [&](size_t c0, size_t n) { return hash_cropped_launch(ctx, all.clips(c0, n), plan.cropped ? crops.data() + 4 * c0 : nullptr); });
+    }
+    return hash_mixed_launch(ctx, d_buf, buf_bytes, plan, d_out, d_dc, stream);
 }
 
 // Small frames: the boxes stay on the device.  No copy to the host, no wait, no host loop over the clips between the launches; out_crops is
@@ -1496,6 +1600,24 @@ int vdf_hash_frames_u8_cropped_device(vdf_ctx *ctx, const uint8_t *d_frames, siz
     VDF_SINGLE_DEVICE_ONLY(ctx);
     return hash_cropped_locked(ctx, d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, crops,
                                d_out_hashes, d_out_dontcare, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int vdf_hash_clips_u8_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                             uint64_t *d_out_hashes, uint32_t *d_out_dontcare, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    VDF_SINGLE_DEVICE_ONLY(ctx);
+    return hash_clips_locked(ctx, d_buf, buf_bytes, clips, n_clips, frames_per_clip, d_out_hashes, d_out_dontcare, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int vdf_hash_clips_u8(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                      uint64_t *out_hashes, uint32_t *out_dontcare)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_hash_clips_u8 takes a single-device context");
+    return hash_clips_host_locked(ctx, buf, buf_bytes, clips, n_clips, frames_per_clip, out_hashes, out_dontcare);
 }
 
 int vdf_hash_frames_u8_letterbox_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip,

@@ -2473,6 +2473,197 @@ hipError_t launch_resize_mfma_cropped(const uint8_t *frames, size_t n_clips, uin
     return hipGetLastError();
 }
 
+// ---- clips of different frame sizes in one launch (vdf_hash_clips_u8[_device]) -----------------------------------------------------------------
+// The cropped kernels above with ONE change: where a clip starts, its row pitch and its frame stride come from the clip's descriptor
+// (MixedClipDesc: a byte offset into the one buffer all clips of the call live in) instead of from kernel arguments.  Loaders, tables, the
+// careful-loader tests and the one-tile fast path are the same code; `buf_end` is the end of that one buffer, so 16-byte loads that run past a
+// row still land in the buffer (another clip's bytes, at zero coefficients) everywhere but at its very end.  The host has checked every
+// descriptor against the buffer (resize_dispatch.cpp: check_mixed) and every table index against the uploaded entries before the launch.
+__device__ __forceinline__ MfmaResizeTables mixed_tables(const CropTableEntry &th, const CropTableEntry &tv)
+{
+    MfmaResizeTables T;
+    T.bh = reinterpret_cast<const v4i *>(th.operand);
+    T.av = reinterpret_cast<const v4i *>(tv.operand);
+    T.bias_h = th.bias;
+    T.bias_v = tv.bias;
+    T.prec_h = th.precision;
+    T.prec_v = tv.precision;
+    T.n_kt = th.n_tiles;
+    T.n_rg = tv.n_tiles;
+    T.band_meta = nullptr;
+    T.band_stride = 0;
+    return T;
+}
+
+// Small frames (at most 256 columns, 128 rows): resize_dct_hash_cropped_small_kernel's body - one workgroup per clip, a wave per four frames,
+// the DCT in the same workgroup; the hash goes to the clip's place in the CALL (d.out_index), whichever launch of the call this is.
+__global__ __launch_bounds__(256) void resize_dct_hash_mixed_small_kernel(const uint8_t *__restrict__ buf, const uint8_t *buf_end,
+                                                                          const MixedClipDesc *__restrict__ desc,
+                                                                          const CropTableEntry *__restrict__ tables,
+                                                                          const double *__restrict__ cos_table,
+                                                                          uint64_t *__restrict__ out_hashes,
+                                                                          uint32_t *__restrict__ out_dontcare)
+{
+    __shared__ DctShared sh;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, r16 = lane & 15;
+    if (tid < 32) sh.words[tid] = 0u;
+    const MixedClipDesc d = desc[blockIdx.x];
+    const MfmaResizeTables T = mixed_tables(tables[d.h_table], tables[d.v_table]);
+    const size_t pitch = d.pitch, frame_stride = (size_t)d.frame_stride;
+    v4i bias_v;
+#pragma unroll
+    for (int r = 0; r < 4; r++) bias_v[r] = T.bias_v[4 * g + r];
+    const uint8_t *clip0 = buf + (size_t)d.offset + (size_t)d.y0 * pitch + d.x0;  // (64-bit throughout: offsets pass 2^32 in a large buffer)
+    if (T.n_kt == 1 && T.n_rg == 1 && clip0 + 15 * frame_stride + (size_t)d.bh * pitch + 64 <= buf_end) {  // workgroup-uniform
+        const v4i x80 = {(int)0x80808080, (int)0x80808080, (int)0x80808080, (int)0x80808080};
+        v4i px[4][4];
+        const bool col_ok = 16u * g < d.bw;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint8_t *src = clip0 + (size_t)(4 * wave + q) * frame_stride;
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+                const uint32_t row = 16u * m + r16;
+                px[q][m] = (v4i){0, 0, 0, 0};
+                if (row < d.bh && col_ok) px[q][m] = load_pixels16<false>(src + (size_t)row * pitch + 16u * g, buf_end);
+            }
+        }
+        const v4i bh = T.bh[lane], bl = T.bh[64 + lane], avh = T.av[lane], avl = T.av[64 + lane];
+        const int32_t bias_h = T.bias_h[r16];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            v4i b;
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+                const v4i a = px[q][m] ^ x80;
+                v4i ah = {0, 0, 0, 0}, al = {bias_h, bias_h, bias_h, bias_h};
+                ah = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, bh, ah, 0, 0, 0);
+                al = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, bl, al, 0, 0, 0);
+                b[m] = (int)finalize4(ah, al, T.prec_h);
+            }
+            v4i vh = {0, 0, 0, 0}, vl = bias_v;
+            vh = __builtin_amdgcn_mfma_i32_16x16x64_i8(avh, b, vh, 0, 0, 0);
+            vl = __builtin_amdgcn_mfma_i32_16x16x64_i8(avl, b, vl, 0, 0, 0);
+            sh.cube[(4 * wave + q) * 64 + g * 16 + r16] = finalize4(vh, vl, T.prec_v);
+        }
+        __syncthreads();
+        dct_hash_block(sh, (const_f64_ptr)(uintptr_t)cos_table, d.out_index, out_hashes, out_dontcare);
+        return;
+    }
+#pragma unroll 1
+    for (uint32_t q = 0; q < 4; q++) {
+        const uint32_t f = 4 * wave + q;
+        const uint8_t *src = clip0 + (size_t)f * frame_stride;
+        v4i vh = {0, 0, 0, 0}, vl = bias_v;
+        // the careful-loader test of the cropped kernel, with the clip's own geometry against the one buffer's end (wave-uniform)
+        if (src + (size_t)d.bh * pitch + 64 > buf_end) resize_row_groups<true>(src, d.bw, d.bh, buf_end, T, 0, 1, vh, vl, pitch);
+        else resize_row_groups<false>(src, d.bw, d.bh, buf_end, T, 0, 1, vh, vl, pitch);
+        sh.cube[f * 64 + g * 16 + r16] = finalize4(vh, vl, T.prec_v);
+    }
+    __syncthreads();
+    dct_hash_block(sh, (const_f64_ptr)(uintptr_t)cos_table, d.out_index, out_hashes, out_dontcare);
+}
+
+// Everything else: resize_mfma_cropped_kernel<WIDE>'s body - one workgroup per frame; the 16 x 16 frame goes to slot blockIdx.x of `small`
+// (the launcher passes the launch's first slot), and dct_hash_indexed_kernel takes it from there to the clip's place in the call.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void resize_mfma_mixed_kernel(const uint8_t *__restrict__ buf, const uint8_t *buf_end,
+                                                                const MixedClipDesc *__restrict__ desc,
+                                                                const CropTableEntry *__restrict__ tables, uint8_t *__restrict__ small)
+{
+    __shared__ int32_t s_part[3][2][64][4];
+    const size_t clip = blockIdx.x >> 4;
+    const uint32_t f = blockIdx.x & 15;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, r16 = lane & 15;
+    const MixedClipDesc d = desc[clip];
+    const MfmaResizeTables T = mixed_tables(tables[d.h_table], tables[d.v_table]);
+    const size_t pitch = d.pitch;
+    v4i vh = {0, 0, 0, 0}, vl = {0, 0, 0, 0};
+    const uint8_t *src = buf + (size_t)d.offset + (size_t)f * (size_t)d.frame_stride + (size_t)d.y0 * pitch + d.x0;
+    if (WIDE) {  // whole-line loads (vertical tables in kMfmaLayoutVerticalWide order)
+        const int n_q = (int)((d.bh + 31) / 32), q0 = n_q * (int)wave / 4, q1 = n_q * ((int)wave + 1) / 4;
+        if (src + (size_t)d.bh * pitch + 128 > buf_end) resize_row_quads<true>(src, d.bw, d.bh, buf_end, T, q0, q1, vh, vl, pitch);
+        else resize_row_quads<false>(src, d.bw, d.bh, buf_end, T, q0, q1, vh, vl, pitch);
+    } else {
+        const int n_blk = (int)((d.bh + 15) / 16), b0 = n_blk * (int)wave / 4, b1 = n_blk * ((int)wave + 1) / 4;
+        if (src + (size_t)d.bh * pitch + 64 > buf_end) resize_row_blocks<true>(src, d.bw, d.bh, buf_end, T, b0, b1, vh, vl, pitch);
+        else resize_row_blocks<false>(src, d.bw, d.bh, buf_end, T, b0, b1, vh, vl, pitch);
+    }
+    if (wave > 0) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) { s_part[wave - 1][0][lane][r] = vh[r]; s_part[wave - 1][1][lane][r] = vl[r]; }
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            vl[r] += T.bias_v[4 * g + r];
+#pragma unroll
+            for (int w = 0; w < 3; w++) { vh[r] += s_part[w][0][lane][r]; vl[r] += s_part[w][1][lane][r]; }
+        }
+        const uint32_t px = finalize4(vh, vl, T.prec_v) ^ 0x80808080u;
+        uint8_t *dst = small + (clip * 16 + f) * 256;
+#pragma unroll
+        for (int r = 0; r < 4; r++) dst[(4 * g + r) * 16 + r16] = (uint8_t)(px >> (8 * r));
+    }
+}
+
+// dct_hash_kernel for the 16 x 16 frames of a mixed launch: cube blockIdx.x of `small` (tightly packed) -> the hash of clip
+// desc[blockIdx.x].out_index of the call.
+__global__ __launch_bounds__(256) void dct_hash_indexed_kernel(const uint8_t *__restrict__ small, const MixedClipDesc *__restrict__ desc,
+                                                               const double *__restrict__ cos_table, uint64_t *__restrict__ out_hashes,
+                                                               uint32_t *__restrict__ out_dontcare)
+{
+    __shared__ DctShared sh;
+    const uint32_t tid = threadIdx.x;
+    if (tid < 32) sh.words[tid] = 0u;
+    {
+        const uint32_t t = tid >> 4, g = (tid >> 2) & 3, xq = tid & 3;
+        const uint8_t *src = small + (size_t)blockIdx.x * 4096 + (size_t)t * 256 + (4 * g) * 16 + 4 * xq;
+        uint32_t row[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) row[r] = *reinterpret_cast<const uint32_t *>(src + r * 16) ^ 0x80808080u;
+#pragma unroll
+        for (int c = 0; c < 4; c++) {
+            uint32_t w = 0;
+#pragma unroll
+            for (int r = 0; r < 4; r++) w |= ((row[r] >> (8 * c)) & 255u) << (8 * r);
+            sh.cube[t * 64 + g * 16 + 4 * xq + c] = w;
+        }
+    }
+    __syncthreads();
+    dct_hash_block(sh, (const_f64_ptr)(uintptr_t)cos_table, desc[blockIdx.x].out_index, out_hashes, out_dontcare);
+}
+
+hipError_t launch_mixed_small(const uint8_t *buf, const uint8_t *buf_end, const MixedClipDesc *desc, size_t n_clips, const CropTableEntry *tables,
+                              const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream)
+{
+    if (n_clips == 0) return hipSuccess;
+    if (n_clips > kMaxClipsPerLaunch) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(resize_dct_hash_mixed_small_kernel, dim3((uint32_t)n_clips), dim3(256), 0, stream, buf, buf_end, desc, tables, cos_table, out_hashes,
+                       out_dontcare);
+    return hipGetLastError();
+}
+
+hipError_t launch_mixed_frames(const uint8_t *buf, const uint8_t *buf_end, const MixedClipDesc *desc, size_t n_clips, const CropTableEntry *tables,
+                               bool wide, uint8_t *small, hipStream_t stream)
+{
+    if (n_clips == 0) return hipSuccess;
+    if (n_clips > kMaxClipsPerLaunch) return hipErrorInvalidValue;  // x 16 frames x 256 threads: below 2^32 work items
+    if (wide) hipLaunchKernelGGL(resize_mfma_mixed_kernel<true>, dim3((uint32_t)(n_clips * 16)), dim3(256), 0, stream, buf, buf_end, desc, tables, small);
+    else hipLaunchKernelGGL(resize_mfma_mixed_kernel<false>, dim3((uint32_t)(n_clips * 16)), dim3(256), 0, stream, buf, buf_end, desc, tables, small);
+    return hipGetLastError();
+}
+
+hipError_t launch_dct_hash_indexed(const uint8_t *small, const MixedClipDesc *desc, size_t n_clips, const double *cos_table, uint64_t *out_hashes,
+                                   uint32_t *out_dontcare, hipStream_t stream)
+{
+    if (n_clips == 0) return hipSuccess;
+    if (n_clips > kMaxClipsPerLaunch) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dct_hash_indexed_kernel, dim3((uint32_t)n_clips), dim3(256), 0, stream, small, desc, cos_table, out_hashes, out_dontcare);
+    return hipGetLastError();
+}
+
 static MfmaResizeTables make_tables(const MfmaResizeArgs &a)
 {
     MfmaResizeTables T;

@@ -203,4 +203,131 @@ int hash_host_locked(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32
     return VDF_OK;
 }
 
+// Clips of different frame sizes from host memory (vdf_hash_clips_u8).  The clips are REPACKED while they are staged: only the 16 frames of
+// w * h bytes go into the pinned buffer (strides squeezed out), every clip starts on a 64-byte boundary, and the staged buffer ends in 128
+// zeroed bytes, so that no clip of it sits at the buffer's end and the careful loader is never the common case.  The device call gets the
+// STAGED descriptors and the STAGED size - never the caller's buf_bytes.  A batch is what fits one staging buffer (a larger clip goes alone,
+// through a buffer grown for it); two buffers: the threads fill batch b + 1 while batch b crosses the link.
+// Clips of a megabyte and more whose frames already lie back to back need no gather: they go from the caller's memory straight to their
+// staged place on the device (hipMemcpyAsync from pageable memory, which the runtime stages through its own pinned buffers at the link's
+// rate - the finding behind hash_host_locked's direct path; VDF_HOST_DIRECT=0 sends them through the library's staging too).
+constexpr size_t kStagedTailSlack = 128, kStagedClipAlign = 64, kDirectClipBytes = 1u << 20;
+
+int hash_clips_host_locked(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                           uint64_t *out_hashes, uint32_t *out_dontcare)
+{
+    if (n_clips && !clips) return fail(ctx, VDF_E_INVAL, "null pointer");
+    const vdf::MixedCheck chk = vdf::check_mixed(reinterpret_cast<const vdf::MixedClip *>(clips), n_clips, frames_per_clip, buf_bytes);
+    if (chk.error != vdf::MixedError::kNone) return mixed_check_failed(ctx, chk);
+    if (n_clips == 0) return VDF_OK;
+    if (!buf || !out_hashes) return fail(ctx, VDF_E_INVAL, "null pointer");
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t capacity = ctx->host_chunk_bytes;
+    const auto clip_bytes = [](const vdf_clip &c) { return (size_t)c.w * c.h * VDF_DCT_SIZE; };
+    const auto staged_bytes = [&](const vdf_clip &c) { return (clip_bytes(c) + kStagedClipAlign - 1) & ~(kStagedClipAlign - 1); };
+    const auto direct = [&](const vdf_clip &c) { return ctx->host_direct && c.frame_stride == (uint64_t)c.w * c.h && clip_bytes(c) >= kDirectClipBytes; };
+    struct Batch { size_t c0, n, bytes, pinned; };  // bytes: all clips, staged; pinned: those of them that go through the pinned buffer
+    std::vector<Batch> batches;
+    for (size_t c = 0; c < n_clips;) {
+        Batch b{c, 0, 0, 0};
+        do {
+            b.bytes += staged_bytes(clips[c]);
+            if (!direct(clips[c])) b.pinned += staged_bytes(clips[c]);
+            b.n++; c++;
+        } while (c < n_clips && b.bytes + staged_bytes(clips[c]) + kStagedTailSlack <= capacity);
+        batches.push_back(b);
+    }
+    DevBuf *d_frames[2] = {&ctx->frames, &ctx->frames2}, *d_hash[2] = {&ctx->out_hashes, &ctx->out_hashes2}, *d_dc[2] = {&ctx->out_dc, &ctx->out_dc2};
+    CopyPool *pool = pool_of(ctx);
+    hipStream_t s = ctx->stream;
+    std::vector<vdf_clip> staged[2];
+    std::vector<uint32_t> gathered[2];  // the batch's clips that go through the pinned buffer
+    // writes the staged descriptors of batch b - gathered clips first, [0, pinned), direct ones behind them - and fills pinned buffer b & 1
+    // (its previous batch has left it: the caller waited for ev_done)
+    const auto fill = [&](size_t b) -> int {
+        const Batch &B = batches[b];
+        const int slot = (int)(b & 1);
+        std::vector<vdf_clip> &sd = staged[slot];
+        std::vector<uint32_t> &ix = gathered[slot];
+        sd.assign(clips + B.c0, clips + B.c0 + B.n);
+        ix.clear();
+        size_t at = 0, at_direct = B.pinned;
+        for (size_t i = 0; i < B.n; i++) {
+            size_t &place = direct(sd[i]) ? at_direct : at;
+            if (!direct(sd[i])) ix.push_back((uint32_t)i);
+            sd[i].offset = place;
+            sd[i].frame_stride = (uint64_t)sd[i].w * sd[i].h;
+            place += staged_bytes(sd[i]);
+        }
+        if (B.pinned == 0) return VDF_OK;
+        if (!ctx->pin[slot].reserve(std::max(capacity, B.pinned))) return fail(ctx, VDF_E_OOM, "pinned staging buffer");
+        uint8_t *dst = ctx->pin[slot].as<uint8_t>();
+        pool->run([&](int t, int n) {  // one frame per step, dealt round-robin
+            for (size_t k = (size_t)t; k < ix.size() * VDF_DCT_SIZE; k += (size_t)n) {
+                const size_t i = ix[k / VDF_DCT_SIZE], f = k % VDF_DCT_SIZE;
+                const vdf_clip &src = clips[B.c0 + i];
+                const size_t fbytes = (size_t)src.w * src.h;
+                std::memcpy(dst + sd[i].offset + f * fbytes, buf + src.offset + f * src.frame_stride, fbytes);
+                if (f == VDF_DCT_SIZE - 1) std::memset(dst + sd[i].offset + VDF_DCT_SIZE * fbytes, 0, staged_bytes(src) - VDF_DCT_SIZE * fbytes);
+            }
+        });
+        return VDF_OK;
+    };
+    const auto copy_out = [&](size_t b) {  // results of batch b: pinned -> caller arrays (its ev_done has been waited for)
+        const Batch &B = batches[b];
+        const uint8_t *src = ctx->pin_out[b & 1].as<uint8_t>();
+        std::memcpy(out_hashes + B.c0 * VDF_HASH_WORDS, src, B.n * VDF_HASH_WORDS * 8);
+        if (out_dontcare) std::memcpy(out_dontcare + B.c0, src + B.n * VDF_HASH_WORDS * 8, B.n * 4);
+    };
+    int rc = fill(0);
+    if (rc) return rc;
+    for (size_t b = 0; b < batches.size(); b++) {
+        const Batch &B = batches[b];
+        const int slot = (int)(b & 1);
+        const size_t total = B.bytes + kStagedTailSlack;
+        VDF_HIP(ctx, d_frames[slot]->reserve(total));
+        VDF_HIP(ctx, d_hash[slot]->reserve(B.n * VDF_HASH_WORDS * 8));
+        VDF_HIP(ctx, d_dc[slot]->reserve(B.n * 4));
+        if (!ctx->pin_out[slot].reserve(B.n * (VDF_HASH_WORDS * 8 + 4))) return fail(ctx, VDF_E_OOM, "pinned result buffer");
+        uint8_t *dev = d_frames[slot]->as<uint8_t>();
+        // a bulk transfer holds the device's link mutex until its frames are over (see hash_host_locked)
+        std::unique_lock<std::mutex> turn(link_mutex(ctx->device), std::defer_lock);
+        if (!ctx->no_link_turns && total >= (1u << 20)) turn.lock();
+        if (B.pinned) VDF_HIP(ctx, hipMemcpyAsync(dev, ctx->pin[slot].p, B.pinned, hipMemcpyHostToDevice, s));
+        VDF_HIP(ctx, hipMemsetAsync(dev + B.bytes, 0, kStagedTailSlack, s));
+        if (b + 1 < batches.size()) {  // the next batch is staged while this one crosses the link
+            if (b >= 1) {              // ... into the other buffer: batch b - 1 must be through, results included
+                if (int rcw = wait_event(ctx, ctx->ev_done[slot ^ 1])) return rcw;
+                copy_out(b - 1);
+            }
+            if ((rc = fill(b + 1))) return rc;
+        }
+        for (size_t i = 0; i < B.n; i++)  // (pageable source: the call returns when the bytes have left the caller's memory)
+            if (direct(clips[B.c0 + i]))  // (the caller's descriptor: the staged one has lost its stride)
+                VDF_HIP(ctx, hipMemcpyAsync(dev + staged[slot][i].offset, buf + clips[B.c0 + i].offset, clip_bytes(clips[B.c0 + i]), hipMemcpyHostToDevice, s));
+        VDF_HIP(ctx, hipEventRecord(ctx->ev_copy[0], s));
+        if (turn.owns_lock()) {
+            const int rcw = wait_event(ctx, ctx->ev_copy[0]);
+            turn.unlock();
+            if (rcw) return rcw;
+        }
+        uint32_t *dc = out_dontcare ? d_dc[slot]->as<uint32_t>() : nullptr;
+        // the STAGED descriptors against the STAGED size
+        if ((rc = hash_clips_locked(ctx, dev, total, staged[slot].data(), B.n, VDF_DCT_SIZE, d_hash[slot]->as<uint64_t>(), dc, s))) return rc;
+        uint8_t *po = ctx->pin_out[slot].as<uint8_t>();
+        VDF_HIP(ctx, hipMemcpyAsync(po, d_hash[slot]->p, B.n * VDF_HASH_WORDS * 8, hipMemcpyDeviceToHost, s));
+        if (dc) VDF_HIP(ctx, hipMemcpyAsync(po + B.n * VDF_HASH_WORDS * 8, dc, B.n * 4, hipMemcpyDeviceToHost, s));
+        VDF_HIP(ctx, hipEventRecord(ctx->ev_done[slot], s));
+    }
+    // what has not been copied out yet: the last two batches (the loop fetches batch b - 1 only when it stages batch b + 1)
+    const size_t nb = batches.size();
+    if (nb >= 2) {
+        if (int rcw = wait_event(ctx, ctx->ev_done[(nb - 2) & 1])) return rcw;
+        copy_out(nb - 2);
+    }
+    if (int rcw = wait_event(ctx, ctx->ev_done[(nb - 1) & 1])) return rcw;
+    copy_out(nb - 1);
+    return VDF_OK;
+}
+
 }  // namespace vdf_impl

@@ -347,4 +347,74 @@ LetterboxPlan plan_letterbox(const HashCall &c, const HashKnobs &k)
     return p;
 }
 
+// ---- clips of different frame sizes in one call ------------------------------------------------------------------------------------------
+MixedCheck check_mixed(const MixedClip *clips, size_t n, uint32_t frames_per_clip, uint64_t buf_bytes)
+{
+    if (frames_per_clip < 16) return {MixedError::kNotEnoughFrames, 0};
+    for (size_t i = 0; i < n; i++)
+        if (clips[i].w == 0 || clips[i].h == 0) return {MixedError::kZeroDim, i};
+    for (size_t i = 0; i < n; i++)
+        if (clips[i].frame_stride < (uint64_t)clips[i].w * clips[i].h) return {MixedError::kStrideBelowFrame, i};
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t *c = clips[i].crop;
+        if ((uint64_t)c[0] + c[1] >= clips[i].w || (uint64_t)c[2] + c[3] >= clips[i].h) return {MixedError::kEmptyBox, i};  // crop.rs:21-22
+    }
+    for (size_t i = 0; i < n; i++) {  // the last byte of frame 15, in 128 bits: no offset or stride a caller can write wraps the sum
+        const unsigned __int128 end = (unsigned __int128)clips[i].offset + (unsigned __int128)15 * clips[i].frame_stride + (uint64_t)clips[i].w * clips[i].h;
+        if (end > buf_bytes) return {MixedError::kOutOfBuffer, i};
+    }
+    return {};
+}
+
+MixedPart mixed_part_of(uint32_t w, uint32_t h, const HashKnobs &k)
+{
+    if (w <= 256 && (h + 63) / 64 <= 2 && k.resize_mode == 0 && !k.no_smallcrop) return MixedPart::kSmall;  // CropPlan::kSmall's rule
+    return w < 192 ? MixedPart::kLines : MixedPart::kWideLines;  // as launch_crop_parts picks the whole-line form
+}
+
+MixedPlan plan_mixed(const MixedClip *clips, size_t n, const HashKnobs &k)
+{
+    MixedPlan p;
+    if (n == 0) return p;
+    bool uniform = true;
+    const uint64_t step = n > 1 ? clips[1].offset - clips[0].offset : 16 * clips[0].frame_stride;
+    for (size_t i = 0; i < n; i++) {
+        const MixedClip &c = clips[i];
+        p.cropped = p.cropped || (c.crop[0] | c.crop[1] | c.crop[2] | c.crop[3]) != 0;
+        uniform = uniform && c.w == clips[0].w && c.h == clips[0].h && c.frame_stride == clips[0].frame_stride;
+        // offsets ascend by one positive step (equal or descending offsets are no clip_stride the uniform launchers know)
+        if (i > 0) uniform = uniform && c.offset > clips[i - 1].offset && c.offset - clips[i - 1].offset == step;
+    }
+    if (uniform) {
+        p.kind = MixedPlan::kUniform;
+        p.offset0 = clips[0].offset;
+        p.clip_stride = step;
+        return p;
+    }
+    p.kind = MixedPlan::kMixed;
+    p.descs.reserve(n);
+    const MixedPart order[3] = {MixedPart::kSmall, MixedPart::kLines, MixedPart::kWideLines};
+    for (MixedPart part : order) {
+        const size_t first = p.descs.size();
+        for (size_t i = 0; i < n; i++) {
+            const MixedClip &c = clips[i];
+            if (mixed_part_of(c.w, c.h, k) != part) continue;
+            MixedClipDesc d{};
+            d.offset = c.offset;
+            d.frame_stride = c.frame_stride;
+            d.x0 = c.crop[0]; d.y0 = c.crop[2];
+            d.bw = c.w - c.crop[0] - c.crop[1]; d.bh = c.h - c.crop[2] - c.crop[3];
+            d.h_table = d.bw; d.v_table = d.bh;
+            d.out_index = (uint32_t)i;
+            d.pitch = c.w;
+            p.max_w = std::max(p.max_w, d.bw); p.max_h = std::max(p.max_h, d.bh);
+            p.descs.push_back(d);
+        }
+        if (part == MixedPart::kSmall) p.n_small = p.descs.size();
+        for (size_t at = first; at < p.descs.size(); at += kMaxClipsPerLaunch)
+            p.launches.push_back(MixedLaunch{part, at, std::min(kMaxClipsPerLaunch, p.descs.size() - at)});
+    }
+    return p;
+}
+
 }  // namespace vdf

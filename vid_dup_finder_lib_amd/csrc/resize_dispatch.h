@@ -145,4 +145,64 @@ struct LetterboxPlan {
 };
 LetterboxPlan plan_letterbox(const HashCall &c, const HashKnobs &k);
 
+// ---- Clips of different frame sizes in one call (vdf_hash_clips_u8[_device]; DESIGN.md 4.1 "mixed sizes") ----------------------------------
+// All clips live in ONE buffer of buf_bytes bytes and name their place by offset, so the loaders' one rule - loads may run past a row into
+// the rest of the buffer, only the buffer's end takes the careful loader - holds unchanged, and every address is checked here, on the host,
+// before anything is queued.  tests/cpp/mixed_plan_main.cpp walks every descriptor's address envelope on the CPU.
+constexpr size_t kMaxClipsPerLaunch = 256 * 1024;  // x 16 frames x 256 threads stays under HIP's 2^32 work-item grid limit
+struct MixedClip {  // = vdf_clip (include/vdf.h; api.cpp asserts the layout)
+    uint64_t offset, frame_stride;
+    uint32_t w, h;
+    uint32_t crop[4];  // left, right, top, bottom
+};
+// What the mixed kernels read per clip.  h_table / v_table: the planner leaves the BOX sizes (bw, bh) there; the caller replaces them by the
+// entries of the tables it uploads (api.cpp: hash_mixed_launch).
+struct MixedClipDesc {
+    uint64_t offset;        // first byte of frame 0, relative to the buffer
+    uint64_t frame_stride;  // bytes between frames
+    uint32_t x0, y0, bw, bh;
+    uint32_t h_table, v_table;
+    uint32_t out_index;     // the clip's position in the caller's array: where its hash goes (a launch covers a subset of the call)
+    uint32_t pitch;         // bytes between rows = the frame's width
+};
+static_assert(sizeof(MixedClipDesc) == 48 && sizeof(MixedClipDesc) % 16 == 0, "descriptors are read as whole 16-byte pieces");
+static_assert(offsetof(MixedClipDesc, offset) == 0 && offsetof(MixedClipDesc, frame_stride) == 8 && offsetof(MixedClipDesc, x0) == 16 &&
+              offsetof(MixedClipDesc, y0) == 20 && offsetof(MixedClipDesc, bw) == 24 && offsetof(MixedClipDesc, bh) == 28 &&
+              offsetof(MixedClipDesc, h_table) == 32 && offsetof(MixedClipDesc, v_table) == 36 && offsetof(MixedClipDesc, out_index) == 40 &&
+              offsetof(MixedClipDesc, pitch) == 44, "MixedClipDesc layout");
+static_assert(sizeof(MixedClip) == 40, "vdf_clip layout");
+
+// The argument checks, in the order their codes are reported (as checked_launches): over ALL clips before anything is queued.
+enum class MixedError { kNone, kNotEnoughFrames, kZeroDim, kStrideBelowFrame, kEmptyBox, kOutOfBuffer };
+struct MixedCheck { MixedError error = MixedError::kNone; size_t clip = 0; };
+MixedCheck check_mixed(const MixedClip *clips, size_t n, uint32_t frames_per_clip, uint64_t buf_bytes);
+
+// Which kernel reads a clip, by its FRAME size (the rules of plan_cropped): small = one workgroup per clip with the DCT fused
+// (resize_dct_hash_mixed_small_kernel), lines / wide lines = one workgroup per frame (resize_mfma_mixed_kernel<false / true>, the latter
+// with the vertical table in kMfmaLayoutVerticalWide order).
+enum class MixedPart { kSmall, kLines, kWideLines };
+MixedPart mixed_part_of(uint32_t w, uint32_t h, const HashKnobs &k);
+constexpr uint32_t mixed_loader_overrun(MixedPart p) { return p == MixedPart::kWideLines ? 128u : 64u; }  // the careful-loader tests' margin
+// The kernels' own careful-loader expression for frame f of a descriptor, in offsets: true = that frame takes the careful loader.
+// (dct_hash.hip: src + bh * pitch + overrun > buf_end with src = buf + offset + f * frame_stride + y0 * pitch + x0)
+inline bool mixed_frame_is_careful(const MixedClipDesc &d, MixedPart p, uint32_t f, uint64_t buf_bytes)
+{
+    return d.offset + (uint64_t)f * d.frame_stride + (uint64_t)d.y0 * d.pitch + d.x0 + (uint64_t)d.bh * d.pitch + mixed_loader_overrun(p) > buf_bytes;
+}
+struct MixedLaunch { MixedPart part; size_t first, count; };  // descs[first .. first + count)
+struct MixedPlan {
+    enum Kind { kUniform, kMixed } kind = kMixed;
+    // kUniform: one frame size, one frame stride, offsets in arithmetic progression: today's hash_launch / hash_cropped_launch on
+    // (base + offset0, clip_stride) - the same kernels, words and speed
+    uint64_t offset0 = 0, clip_stride = 0;
+    bool cropped = false;  // some clip has a box
+    // kMixed: descriptors part by part (small, lines, wide lines), each part cut into launches of at most kMaxClipsPerLaunch clips
+    std::vector<MixedClipDesc> descs;
+    std::vector<MixedLaunch> launches;
+    size_t n_small = 0;           // descs[n_small ..): the clips whose 16 x 16 frames go through ctx->small, slot = index - n_small
+    uint32_t max_w = 0, max_h = 0;  // the largest box sizes: what the table index is sized by
+};
+// clips have passed check_mixed; n <= 2^32 - 1 (out_index is 32 bits)
+MixedPlan plan_mixed(const MixedClip *clips, size_t n, const HashKnobs &k);
+
 }  // namespace vdf

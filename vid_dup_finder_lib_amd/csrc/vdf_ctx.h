@@ -284,6 +284,13 @@ int search_refs_resident(vdf_ctx *ctx, size_t n_cand, const std::vector<size_t> 
 int letterbox_hash_device_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip,
                                  uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride, uint64_t *d_out,
                                  uint32_t *d_dc, uint32_t *out_crops, hipStream_t stream, uint32_t *d_out_crops = nullptr);
+// clips of different frame sizes in one buffer (include/vdf.h: vdf_hash_clips_u8[_device]): checks every clip, then the uniform launchers or
+// the mixed kernels (api.cpp); the host form repacks the clips into pinned staging batch by batch (hash_host.cpp)
+int hash_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                      uint64_t *d_out, uint32_t *d_dc, hipStream_t stream);
+int hash_clips_host_locked(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                           uint64_t *out_hashes, uint32_t *out_dontcare);
+int mixed_check_failed(vdf_ctx *ctx, const vdf::MixedCheck &c);  // reports a check_mixed finding with its status code
 void destroy_copy_pool(vdf_ctx *ctx);
 bool is_sorted_u32(const uint32_t *d, size_t n);
 

@@ -185,6 +185,18 @@ hipError_t launch_letterbox_hash_small(const uint8_t *frames, size_t n_clips, ui
 hipError_t launch_resize_mfma_cropped(const uint8_t *frames, size_t n_clips, uint32_t pitch, size_t frame_stride,
                                       size_t clip_stride, const uint8_t *buf_end, const CropClipDesc *desc,
                                       const CropTableEntry *tables, uint8_t *small, bool wide, hipStream_t stream);
+// ---- clips of different frame sizes in one call (vdf_hash_clips_u8[_device]) --------------------------------------------------------------
+// desc: DEVICE MixedClipDesc (resize_dispatch.h, where the host-only planner fills them and asserts the layout the kernels read), this launch's
+// first; h_table / v_table index `tables`.  buf_end = buf + buf_bytes of the ONE buffer every clip's offset is relative to.  At most
+// kMaxClipsPerLaunch clips per launch.
+hipError_t launch_mixed_small(const uint8_t *buf, const uint8_t *buf_end, const MixedClipDesc *desc, size_t n_clips, const CropTableEntry *tables,
+                              const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream);
+// small: this launch's first 4 KB slot; wide: whole-line loads, vertical tables in kMfmaLayoutVerticalWide order
+hipError_t launch_mixed_frames(const uint8_t *buf, const uint8_t *buf_end, const MixedClipDesc *desc, size_t n_clips, const CropTableEntry *tables,
+                               bool wide, uint8_t *small, hipStream_t stream);
+// slot i of small -> the hash of clip desc[i].out_index
+hipError_t launch_dct_hash_indexed(const uint8_t *small, const MixedClipDesc *desc, size_t n_clips, const double *cos_table, uint64_t *out_hashes,
+                                   uint32_t *out_dontcare, hipStream_t stream);
 // ---- Search::sort on the device (sort_order.hip) ----------------------------------------------------------------
 // perm_out = the stable order by (duration, path rank); rank nullable (all paths equal).  scratch from sort_order_scratch_bytes.
 size_t sort_order_scratch_bytes(uint32_t n, bool with_rank);

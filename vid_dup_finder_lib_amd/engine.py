@@ -15,6 +15,9 @@ from . import _capi
 from ._capi import HASH_WORDS, VdfError, VdfGroups, VdfHit, VdfSearchStats, VdfSearchTiming
 
 UINT32_MAX = 0xFFFFFFFF
+# vdf_clip as a numpy record (include/vdf.h): offset, frame_stride, w, h, crop = left, right, top, bottom
+CLIP_DTYPE = np.dtype([("offset", np.uint64), ("frame_stride", np.uint64), ("w", np.uint32), ("h", np.uint32), ("crop", np.uint32, (4,))])
+assert CLIP_DTYPE.itemsize == C.sizeof(_capi.VdfClip) == 40
 
 
 def _groups_to_lists(g: VdfGroups) -> List[Tuple[int, List[int]]]:
@@ -190,6 +193,40 @@ class Engine:
         cs = fs * frames_per_clip if clip_stride is None else clip_stride
         self._check(self.lib.vdf_hash_frames_u8_device(self.ctx, d_frames, n_clips, frames_per_clip, w, h, fs, cs,
                                                        d_out, d_dontcare or None, stream or None))
+
+    def hash_clips(self, stacks: Sequence[np.ndarray], crops=None, want_dontcare: bool = False):
+        """Clips of DIFFERENT frame sizes in one call (vdf_hash_clips_u8): stacks = a list of [>= 16, H, W] u8 arrays, each with its own
+        H and W; crops (optional) = [n, 4] u32 left, right, top, bottom per clip.  -> hashes [n, 16] u64 [, dontcare [n] u32], in the
+        order of the list.  Raises VdfError(VDF_E_NOT_ENOUGH_FRAMES) when a stack has fewer than 16 frames."""
+        stacks = [np.ascontiguousarray(s, dtype=np.uint8) for s in stacks]
+        n = len(stacks)
+        if any(s.ndim != 3 for s in stacks):
+            raise ValueError("every clip must be [n_frames, H, W]")
+        nf = min((s.shape[0] for s in stacks), default=16)
+        clips = np.zeros(n, CLIP_DTYPE)
+        at = 0
+        for i, s in enumerate(stacks):
+            clips[i]["offset"], clips[i]["frame_stride"], clips[i]["w"], clips[i]["h"] = at, s.shape[1] * s.shape[2], s.shape[2], s.shape[1]
+            at += (min(s.shape[0], 16) * s.shape[1] * s.shape[2] + 63) & ~63
+        if crops is not None:
+            clips["crop"] = np.asarray(crops, dtype=np.uint32).reshape(n, 4)
+        buf = np.zeros(max(at, 1), np.uint8)
+        for i, s in enumerate(stacks):
+            flat = s[:16].reshape(-1)
+            buf[int(clips[i]["offset"]):int(clips[i]["offset"]) + flat.size] = flat
+        out = np.zeros((n, HASH_WORDS), np.uint64)
+        dc = np.zeros(n, np.uint32) if want_dontcare else None
+        self._check(self.lib.vdf_hash_clips_u8(self.ctx, buf.ctypes.data, buf.size, clips.ctypes.data, n, nf, out.ctypes.data,
+                                               dc.ctypes.data if want_dontcare else None))
+        return (out, dc) if want_dontcare else out
+
+    def hash_clips_device(self, d_buf: int, buf_bytes: int, clips: np.ndarray, d_out: int, d_dontcare: int = 0,
+                          frames_per_clip: int = 16, stream: int = 0):
+        """vdf_hash_clips_u8_device: clips = HOST array of CLIP_DTYPE records (offsets relative to d_buf), every address checked against
+        buf_bytes before anything is queued; clip i's hash goes to d_out + 128 i, ordered on `stream`."""
+        c = np.ascontiguousarray(clips, dtype=CLIP_DTYPE)
+        self._check(self.lib.vdf_hash_clips_u8_device(self.ctx, d_buf, int(buf_bytes), c.ctypes.data if c.size else None, c.size,
+                                                      int(frames_per_clip), d_out, d_dontcare or None, stream or None))
 
     def hash_frames_letterbox(self, frames: np.ndarray, want_dontcare: bool = False):
         """crop_video_frames(Cropdetect::Letterbox) + from_frames (video_hash_builder.rs:188-223) for a batch:
@@ -511,6 +548,50 @@ class HashQueue:
     def close(self):
         if getattr(self, "q", None):
             self.engine.lib.vdf_hash_queue_destroy(self.q)
+            self.q = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MixedHashQueue:
+    """HashQueue for clips of ANY frame size (vdf_hash_queue_mixed_*): one queue serves a whole library.  A batch closes at max_batch clips,
+    at staging_bytes of frames, or when its first caller has waited max_wait_us."""
+
+    def __init__(self, engine: Engine, staging_bytes: int = 64 << 20, max_batch: int = 256, max_wait_us: int = 2000, slots_per_gpu: int = 0):
+        self.engine = engine
+        q = C.c_void_p()
+        engine._check(engine.lib.vdf_hash_queue_create_mixed(engine.ctx, int(staging_bytes), int(max_batch), int(max_wait_us),
+                                                             int(slots_per_gpu), C.byref(q)))
+        self.q = q
+
+    def submit(self, frames: np.ndarray) -> np.ndarray:
+        """frames [>=16, H, W] u8 -> hash [16] u64.  Blocks; releases the GIL while waiting."""
+        f = np.ascontiguousarray(frames[:16], dtype=np.uint8)
+        if f.ndim != 3 or f.shape[0] != 16:
+            raise ValueError("a clip is at least 16 frames of [H, W]")
+        out = np.zeros(HASH_WORDS, np.uint64)
+        rc = self.engine.lib.vdf_hash_queue_mixed_submit(self.q, f.ctypes.data, f.shape[2], f.shape[1], out.ctypes.data)
+        if rc != 0:
+            raise VdfError(rc, "mixed hash queue: clip of %d x %d refused or its batch failed" % (f.shape[2], f.shape[1]))
+        return out
+
+    def stats(self):
+        nb, nc = C.c_uint64(0), C.c_uint64(0)
+        self.engine.lib.vdf_hash_queue_mixed_stats(self.q, C.byref(nb), C.byref(nc))
+        return int(nb.value), int(nc.value)
+
+    def in_flight_max(self) -> int:
+        v = C.c_uint32(0)
+        self.engine.lib.vdf_hash_queue_mixed_in_flight_max(self.q, C.byref(v))
+        return int(v.value)
+
+    def close(self):
+        if getattr(self, "q", None):
+            self.engine.lib.vdf_hash_queue_mixed_destroy(self.q)
             self.q = None
 
     def __del__(self):
