@@ -231,6 +231,23 @@ int vdf_hash_clips_u8(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const 
 /* clips: HOST array.  The call returns once the descriptors have left the host; the hashes are ordered on `stream`. */
 int vdf_hash_clips_u8_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips,
                              uint32_t frames_per_clip, uint64_t *d_out_hashes, uint32_t *d_out_dontcare, void *stream);
+/* Cropdetect::Letterbox on clips of different frame sizes: detection on per-clip descriptors (frames 0 and 8 of every clip, the rules of
+ * vdf_cropdetect_letterbox_device), then the mixed hash on the detected boxes.  The letterbox calls take the whole frame, as the reference does:
+ * after the errors above, in their order, a clip whose four crop fields are not all zero -> VDF_E_INVAL ("caller-supplied crop box in a
+ * letterbox call", naming the first such clip).  Every check runs before anything is queued.  Clips that share (w, h, frame_stride) at
+ * offsets one positive step apart take exactly the route of vdf_cropdetect_letterbox_device / vdf_hash_frames_u8_letterbox_device.
+ * The hash calls WAIT for their detect (the kernel per box shape is chosen on the host, as for large frames above); a detected box size
+ * whose coefficients do not fit the i8 split -> VDF_E_BAD_DIMS, reported after the detect, and no hash is written.  A multi-GPU context
+ * refuses all three with VDF_E_INVAL. */
+/* boxes only: d_crops DEVICE [n_clips][4] l, r, t, b, ordered on stream; only queues work */
+int vdf_cropdetect_letterbox_clips_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips,
+                                          uint32_t frames_per_clip, uint32_t *d_crops, void *stream);
+/* detect + crop + hash; out_crops HOST [n_clips][4], nullable; the call waits for its detect, the hashes are ordered on stream */
+int vdf_hash_clips_u8_letterbox_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips,
+                                       uint32_t frames_per_clip, uint64_t *d_out_hashes, uint32_t *d_out_dontcare,
+                                       uint32_t *out_crops, void *stream);
+int vdf_hash_clips_u8_letterbox(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips,
+                                uint32_t frames_per_clip, uint64_t *out_hashes, uint32_t *out_crops, uint32_t *out_dontcare);
 
 /* ---- search(): replaces Search::search_self, search_algorithm.rs:81-171 (hot loop :150-156) --
  * hashes: n x 16 words, durations: n, both in sorted order.  tol_int from vdf_tolerance_int().
@@ -392,7 +409,14 @@ void vdf_hash_queue_destroy(vdf_hash_queue *q);
 typedef struct vdf_hash_queue_mixed vdf_hash_queue_mixed;
 int vdf_hash_queue_create_mixed(vdf_ctx *ctx, size_t staging_bytes, uint32_t max_batch, uint32_t max_wait_us,
                                 uint32_t slots_per_gpu, vdf_hash_queue_mixed **out);
+/* The same queue with Cropdetect::Letterbox: a batch is hashed by one vdf_hash_clips_u8_letterbox call. */
+int vdf_hash_queue_create_mixed_letterbox(vdf_ctx *ctx, size_t staging_bytes, uint32_t max_batch, uint32_t max_wait_us,
+                                          uint32_t slots_per_gpu, vdf_hash_queue_mixed **out);
 int vdf_hash_queue_mixed_submit(vdf_hash_queue_mixed *q, const uint8_t *frames, uint32_t w, uint32_t h, uint64_t *out_hash);
+/* either kind of mixed queue; out_crop (nullable): the clip's box l, r, t, b - a plain queue writes zeros.  vdf_hash_queue_mixed_submit on a
+ * letterbox queue hashes with letterbox and drops the box. */
+int vdf_hash_queue_mixed_submit_crop(vdf_hash_queue_mixed *q, const uint8_t *frames, uint32_t w, uint32_t h,
+                                     uint64_t *out_hash, uint32_t *out_crop);
 int vdf_hash_queue_mixed_stats(vdf_hash_queue_mixed *q, uint64_t *n_batches, uint64_t *n_clips);
 int vdf_hash_queue_mixed_in_flight_max(vdf_hash_queue_mixed *q, uint32_t *out);
 void vdf_hash_queue_mixed_destroy(vdf_hash_queue_mixed *q);

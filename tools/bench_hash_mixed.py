@@ -2,6 +2,7 @@
 """Clips of different frame sizes: the mixed call (vdf_hash_clips_u8[_device]) against what a caller could do before it existed.
 
     python tools/bench_hash_mixed.py [--parent-lib tools/_libvdf_parent.so] [--out profiles/hash_mixed.txt]
+    python tools/bench_hash_mixed.py --letterbox [--out profiles/hash_mixed_letterbox.txt]     (Cropdetect::Letterbox: see letterbox_main below)
 
 Two workloads:
   small   20 000 clips drawn evenly from 48x36, 64x64, 96x96, 128x96, 160x90, device-resident in one buffer, in random order
@@ -143,6 +144,223 @@ def child(args):
     print(json.dumps({"leg": args.leg, "workload": args.workload, "n": n, "frame_bytes": frame_bytes, "times_s": times, "gather_s": gather_s}))
 
 
+# ---- --letterbox: detect + crop + hash on clips of different frame sizes (vdf_hash_clips_u8_letterbox[_device]) -----------------------------------
+# The same two workloads with bars (random depth up to 0.3 of each axis, base 0..39, noise 0..5, on a coarse picture), and for each the new call beside
+#   boxes    (a) vdf_hash_clips_u8[_device] with the true boxes passed in: the difference is what detection costs
+#   sorted   (b) the clips gathered by size, then one uniform letterbox call per size (gather timed apart)
+#   perclip  (c) one uniform letterbox call per clip
+#   detect   the detect call alone (small workload): vdf_cropdetect_letterbox_clips_device
+# Device workload: the calls go to the process's current stream between two events (the device part) inside a host clock that ends in a
+# synchronise (the whole call).  Host workload: host clock only.  Median of REPEATS after one warm-up.  All legs must give the same words.
+def bars_pool(rng, w, h, k=8):
+    pool = np.zeros((k, 16, h, w), np.uint8)
+    for j in range(k):
+        coarse = rng.integers(60, 200, size=(16, (h + 7) // 8, (w + 7) // 8), dtype=np.uint8)
+        pic = np.repeat(np.repeat(coarse, 8, axis=1), 8, axis=2)[:, :h, :w] + rng.integers(0, 24, size=(16, h, w), dtype=np.uint8)
+        l, r = (int(rng.integers(0, max(1, int(w * 0.3)))) for _ in range(2))
+        t, b = (int(rng.integers(0, max(1, int(h * 0.3)))) for _ in range(2))
+        base = int(rng.integers(0, 40))
+        bar = (base + rng.integers(0, 6, size=(16, h, w))).astype(np.uint8)
+        mask = np.zeros((h, w), bool)
+        mask[:t] = True; mask[h - b:] = b > 0; mask[:, :l] = True
+        if r:
+            mask[:, w - r:] = True
+        pool[j] = np.where(mask[None], bar, pic)
+    return pool.reshape(k, -1)
+
+
+def letterbox_child(args):
+    import torch
+
+    lib = C.CDLL(args.lib)
+    lib.vdf_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    lib.vdf_last_error.restype = C.c_char_p
+    lib.vdf_last_error.argtypes = [C.c_void_p]
+    V = C.c_void_p
+    uni = [V, V, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t]
+    lib.vdf_hash_frames_u8_letterbox_device.argtypes = uni + [V, V, V, V]
+    lib.vdf_hash_frames_u8_letterbox.argtypes = uni + [V, V, V]
+    cl = [V, V, C.c_size_t, V, C.c_size_t, C.c_uint32]
+    lib.vdf_hash_clips_u8.argtypes = cl + [V, V]
+    lib.vdf_hash_clips_u8_device.argtypes = cl + [V, V, V]
+    lib.vdf_hash_clips_u8_letterbox.argtypes = cl + [V, V, V]
+    lib.vdf_hash_clips_u8_letterbox_device.argtypes = cl + [V, V, V, V]
+    lib.vdf_cropdetect_letterbox_clips_device.argtypes = cl + [V, V]
+    ctx = C.c_void_p()
+    assert lib.vdf_ctx_create(0, C.byref(ctx)) == 0
+
+    def ok(rc):
+        assert rc == 0, (rc, lib.vdf_last_error(ctx))
+
+    n = args.clips
+    pick, recs, total = workload(args.workload, n)
+    sizes = SMALL if args.workload == "small" else LARGE
+    frame_bytes = int(sum(16 * int(r["w"]) * int(r["h"]) for r in recs))
+    rng = np.random.default_rng(4)
+    pool = {k: bars_pool(rng, w, h) for k, (w, h) in enumerate(sizes)}
+    buf = np.zeros(total, np.uint8)
+    for i, k in enumerate(pick):
+        o = int(recs[i]["offset"])
+        buf[o:o + pool[k].shape[1]] = pool[k][i % 8]
+    by_size = [np.nonzero(pick == k)[0] for k in range(len(sizes))]
+    out = np.zeros((n, 16), np.uint64)
+    crops = np.zeros((n, 4), np.uint32)
+    leg = args.leg
+    wall, dev, gather_s = [], [], 0.0
+    if args.workload == "small":
+        d_buf = torch.from_numpy(buf).cuda()
+        d_out = torch.zeros((n, 16), dtype=torch.int64, device="cuda")
+        d_crops = torch.zeros((n, 4), dtype=torch.int32, device="cuda")
+        stream = torch.cuda.current_stream().cuda_stream
+        torch.cuda.synchronize()
+        boxed = recs.copy()
+        if leg == "boxes":  # the true boxes, from the detect call, before anything is timed
+            ok(lib.vdf_cropdetect_letterbox_clips_device(ctx, d_buf.data_ptr(), total, recs.ctypes.data, n, 16, d_crops.data_ptr(), stream))
+            torch.cuda.synchronize()
+            boxed["crop"] = d_crops.cpu().numpy().view(np.uint32)
+        d_sorted, d_outs = [], []
+        if leg == "sorted":
+            t0 = time.perf_counter()
+            d_sorted = [torch.cat([d_buf[int(recs[i]["offset"]):int(recs[i]["offset"]) + 16 * w * h] for i in by_size[k]]) for k, (w, h) in enumerate(sizes)]
+            torch.cuda.synchronize()
+            gather_s = time.perf_counter() - t0
+            d_outs = [torch.zeros((len(ix), 16), dtype=torch.int64, device="cuda") for ix in by_size]
+        sorted_crops = [np.zeros((len(ix), 4), np.uint32) for ix in by_size]
+        one_crop = np.zeros(4, np.uint32)
+
+        def run():
+            if leg == "mixed":
+                ok(lib.vdf_hash_clips_u8_letterbox_device(ctx, d_buf.data_ptr(), total, recs.ctypes.data, n, 16, d_out.data_ptr(), None, crops.ctypes.data, stream))
+            elif leg == "boxes":
+                ok(lib.vdf_hash_clips_u8_device(ctx, d_buf.data_ptr(), total, boxed.ctypes.data, n, 16, d_out.data_ptr(), None, stream))
+            elif leg == "detect":
+                ok(lib.vdf_cropdetect_letterbox_clips_device(ctx, d_buf.data_ptr(), total, recs.ctypes.data, n, 16, d_crops.data_ptr(), stream))
+            elif leg == "sorted":
+                for k, (w, h) in enumerate(sizes):
+                    ok(lib.vdf_hash_frames_u8_letterbox_device(ctx, d_sorted[k].data_ptr(), len(by_size[k]), 16, w, h, w * h, 16 * w * h, d_outs[k].data_ptr(), None,
+                                                               sorted_crops[k].ctypes.data, stream))
+            else:
+                for i in range(n):
+                    w, h = int(recs[i]["w"]), int(recs[i]["h"])
+                    ok(lib.vdf_hash_frames_u8_letterbox_device(ctx, d_buf.data_ptr() + int(recs[i]["offset"]), 1, 16, w, h, w * h, 16 * w * h, d_out.data_ptr() + 128 * i,
+                                                               None, one_crop.ctypes.data, stream))
+
+        for r in range(REPEATS + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e0.record()
+            run()
+            e1.record()
+            torch.cuda.synchronize()
+            if r:
+                wall.append(time.perf_counter() - t0)
+                dev.append(e0.elapsed_time(e1) * 1e-3)
+        if leg == "sorted":
+            for k, ix in enumerate(by_size):
+                out[ix] = d_outs[k].cpu().numpy().view(np.uint64)
+        elif leg != "detect":
+            out[:] = d_out.cpu().numpy().view(np.uint64)
+    else:
+        boxed = recs.copy()
+        sorted_bufs, outs = [], [np.zeros((len(ix), 16), np.uint64) for ix in by_size]
+        sorted_crops = [np.zeros((len(ix), 4), np.uint32) for ix in by_size]
+        if leg == "boxes":
+            ok(lib.vdf_hash_clips_u8_letterbox(ctx, buf.ctypes.data, total, recs.ctypes.data, n, 16, out.ctypes.data, crops.ctypes.data, None))
+            boxed["crop"] = crops
+        if leg == "sorted":
+            t0 = time.perf_counter()
+            for k, (w, h) in enumerate(sizes):
+                sorted_bufs.append(np.concatenate([buf[int(recs[i]["offset"]):int(recs[i]["offset"]) + 16 * w * h] for i in by_size[k]]))
+            gather_s = time.perf_counter() - t0
+
+        def run():
+            if leg == "mixed":
+                ok(lib.vdf_hash_clips_u8_letterbox(ctx, buf.ctypes.data, total, recs.ctypes.data, n, 16, out.ctypes.data, crops.ctypes.data, None))
+            elif leg == "boxes":
+                ok(lib.vdf_hash_clips_u8(ctx, buf.ctypes.data, total, boxed.ctypes.data, n, 16, out.ctypes.data, None))
+            elif leg == "sorted":
+                for k, (w, h) in enumerate(sizes):
+                    ok(lib.vdf_hash_frames_u8_letterbox(ctx, sorted_bufs[k].ctypes.data, len(by_size[k]), 16, w, h, w * h, 16 * w * h, outs[k].ctypes.data,
+                                                        sorted_crops[k].ctypes.data, None))
+            else:
+                for i in range(n):
+                    w, h = int(recs[i]["w"]), int(recs[i]["h"])
+                    ok(lib.vdf_hash_frames_u8_letterbox(ctx, buf.ctypes.data + int(recs[i]["offset"]), 1, 16, w, h, w * h, 16 * w * h, out.ctypes.data + 128 * i,
+                                                        crops.ctypes.data + 16 * i, None))
+
+        for r in range(REPEATS + 1):
+            t0 = time.perf_counter()
+            run()
+            if r:
+                wall.append(time.perf_counter() - t0)
+        if leg == "sorted":
+            for k, ix in enumerate(by_size):
+                out[ix] = outs[k]
+    lib.vdf_ctx_destroy.argtypes = [C.c_void_p]
+    lib.vdf_ctx_destroy(ctx)
+    np.save(args.words, out)
+    print(json.dumps({"leg": leg, "workload": args.workload, "n": n, "frame_bytes": frame_bytes, "times_s": wall, "device_s": dev, "gather_s": gather_s}))
+
+
+def letterbox_main(args):
+    own = os.path.join(ROOT, "vid_dup_finder_lib_amd", "libvdf_hip.so")
+    os.makedirs(args.tmp, exist_ok=True)
+    out_path = args.out if args.out != os.path.join(ROOT, "profiles", "hash_mixed.txt") else os.path.join(ROOT, "profiles", "hash_mixed_letterbox.txt")
+    lines = ["# tools/bench_hash_mixed.py --letterbox: detect + crop + hash on clips of different frame sizes, ONE vdf_hash_clips_u8_letterbox[_device] call (`mixed`) beside",
+             "#   boxes = vdf_hash_clips_u8[_device] with the true boxes passed in; sorted = one uniform letterbox call per size after a gather; perclip = one per clip;",
+             "#   detect = vdf_cropdetect_letterbox_clips_device alone",
+             "# wall = host clock around the call(s) and a synchronise, device = between two events on the calls' stream; median of %d repeats after one warm-up (min .. max)" % REPEATS]
+    med_of = {}
+    failed = False
+    for wl, n in (("small", args.n_small), ("large", args.n_large)):
+        ref = None
+        lines.append("# %s: %d clips with bars, %s" % (wl, n, "device-resident, one buffer, random order" if wl == "small" else "pageable host memory"))
+        for leg in (("mixed", "boxes", "detect", "sorted", "perclip", "mixed") if wl == "small" else ("mixed", "boxes", "sorted", "perclip", "mixed")):
+            wpath = os.path.join(args.tmp, "mixed_lb_words_%s_%s.npy" % (wl, leg))
+            cmd = [sys.executable, os.path.abspath(__file__), "--letterbox", "--leg", leg, "--workload", wl, "--clips", str(n), "--lib", own, "--words", wpath]
+            p = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+            if p.returncode != 0:
+                lines.append("%-8s FAILED rc %d: %s" % (leg, p.returncode, p.stderr.strip().splitlines()[-1] if p.stderr.strip() else ""))
+                failed = True
+                if p.returncode < 0 or p.returncode in (124, 134, 137, 139):
+                    break  # a crashed leg: start nothing more on the GPU
+                continue
+            r = json.loads(p.stdout.strip().splitlines()[-1])
+            t = sorted(r["times_s"])
+            med = t[len(t) // 2]
+            med_of.setdefault((wl, leg), med)
+            unit, div = ("TB/s", 1e12) if wl == "small" else ("GB/s", 1e9)
+            line = "%-8s wall %9.3f ms (%8.3f .. %8.3f)  %7.2f %s of frame bytes" % (leg, med * 1e3, t[0] * 1e3, t[-1] * 1e3, r["frame_bytes"] / med / div, unit)
+            if r["device_s"]:
+                d = sorted(r["device_s"])
+                line += "   device %9.3f ms (%8.3f .. %8.3f)" % (d[len(d) // 2] * 1e3, d[0] * 1e3, d[-1] * 1e3)
+            if leg == "sorted":
+                line += "   [+ %.1f ms to gather the clips by size, once]" % (r["gather_s"] * 1e3)
+            lines.append(line)
+            w = np.load(wpath)
+            os.remove(wpath)
+            if leg != "detect":
+                if ref is not None and not np.array_equal(ref, w):
+                    lines.append("%-8s WORDS DIFFER from the first leg" % leg)
+                    failed = True
+                ref = w if ref is None else ref
+        for other in ("boxes", "sorted", "perclip"):
+            if (wl, "mixed") in med_of and (wl, other) in med_of:
+                lines.append("# %s: %s / mixed = %.2f" % (wl, other, med_of[(wl, other)] / med_of[(wl, "mixed")]))
+    if ("small", "mixed") in med_of and ("small", "perclip") in med_of:
+        ratio = med_of[("small", "perclip")] / med_of[("small", "mixed")]
+        gate = ratio >= 10.0
+        lines.append("# GATE (small: perclip / mixed >= 10): %.1f  %s" % (ratio, "ok" if gate else "FAILED"))
+        failed = failed or not gate
+    else:
+        failed = True
+    text = "\n".join(lines) + "\n"
+    print(text)
+    open(out_path, "w").write(text)
+    return 1 if failed else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=None, help="the parent commit's libvdf_hip.so for the sorted and per-clip legs (default: this library)")
@@ -153,7 +371,10 @@ def main():
     for a in ("--leg", "--workload", "--lib", "--words"):  # a child's leg
         ap.add_argument(a)
     ap.add_argument("--clips", type=int)
+    ap.add_argument("--letterbox", action="store_true", help="the Cropdetect::Letterbox comparison (default --out: profiles/hash_mixed_letterbox.txt)")
     args = ap.parse_args()
+    if args.letterbox:
+        return letterbox_child(args) if args.leg else letterbox_main(args)
     if args.leg:
         return child(args)
     own = os.path.join(ROOT, "vid_dup_finder_lib_amd", "libvdf_hip.so")
@@ -190,4 +411,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

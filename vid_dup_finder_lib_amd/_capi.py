@@ -149,6 +149,10 @@ SIGNATURES = {
     "vdf_hash_clips_u8": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vdf_hash_clips_u8_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
+    "vdf_cropdetect_letterbox_clips_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vdf_hash_clips_u8_letterbox_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]),
+    "vdf_hash_clips_u8_letterbox": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vdf_sort_order_paths": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_int)]),
     "vdf_search_self": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(VdfGroups)]),
     "vdf_search_refs": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -188,6 +192,8 @@ SIGNATURES = {
     "vdf_hash_queue_destroy": (None, [C.c_void_p]),
     "vdf_hash_queue_create_mixed": (C.c_int, [_ctx, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
     "vdf_hash_queue_mixed_submit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "vdf_hash_queue_create_mixed_letterbox": (C.c_int, [_ctx, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "vdf_hash_queue_mixed_submit_crop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vdf_hash_queue_mixed_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "vdf_hash_queue_mixed_in_flight_max": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "vdf_hash_queue_mixed_destroy": (None, [C.c_void_p]),

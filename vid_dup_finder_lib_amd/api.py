@@ -430,15 +430,16 @@ def gen_hashes(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int]
                cropdetect: Cropdetect = Cropdetect.LETTERBOX, engine: Optional[Engine] = None) -> List[VideoHash]:
     """The part of `gen_hash` after decode (video_hash_builder.rs:214-223) for a batch of clips:
     crop_video_frames(cropdetect) -- default Letterbox, like CreationOptions::default (:55-63) -- then
-    VideoHash::from_frames.  frames [n_clips, n_frames >= 16, H, W] u8 (with Cropdetect.NONE also a list of stacks of different frame
-    sizes: hash_frame_stacks).  Detection (frames 0 and 8,
+    VideoHash::from_frames.  frames [n_clips, n_frames >= 16, H, W] u8, or a LIST of [n_frames >= 16, H, W] stacks of different frame
+    sizes (Engine.hash_clips_letterbox; with Cropdetect.NONE hash_frame_stacks).  Detection (frames 0 and 8,
     video_frames_gray.rs:201-210) and the cropped resize both run on the GPU; no cropped copies are made."""
     if cropdetect == Cropdetect.NONE:
         return hash_frame_stacks(frames, src_paths, durations, engine)
     if cropdetect != Cropdetect.LETTERBOX:
         raise VidProc("Cropdetect::Motion is not supported by the accelerated path")
     try:
-        words, _crops = (engine or default_engine()).hash_frames_letterbox(frames)
+        eng = engine or default_engine()
+        words, _crops = eng.hash_clips_letterbox(frames) if isinstance(frames, (list, tuple)) else eng.hash_frames_letterbox(frames)
     except VdfError as e:
         if e.code == _capi.VDF_E_NOT_ENOUGH_FRAMES:
             raise NotEnoughFrames() from e
@@ -450,14 +451,19 @@ def gen_hashes(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int]
 
 def cropdetect_letterbox(frames: np.ndarray, engine: Optional[Engine] = None) -> List[Crop]:
     """cropdetect_letterbox (vid_dup_finder_common/src/video_frames_gray.rs:201-210) for a batch of clips on the GPU: frames
-    [n_clips, n_frames >= 16, H, W] u8 -> the union (crop.rs:53-68) of the letterbox crops of frames 0 and 8 of each clip."""
+    [n_clips, n_frames >= 16, H, W] u8 (or a list of [n_frames >= 16, H, W] stacks of different frame sizes) -> the union (crop.rs:53-68) of the letterbox crops of frames 0 and 8 of each clip."""
+    mixed = isinstance(frames, (list, tuple))
     try:
-        _words, crops = (engine or default_engine()).hash_frames_letterbox(frames)
+        eng = engine or default_engine()
+        _words, crops = eng.hash_clips_letterbox(frames) if mixed else eng.hash_frames_letterbox(frames)
     except VdfError as e:
         if e.code == _capi.VDF_E_NOT_ENOUGH_FRAMES:
             raise NotEnoughFrames() from e
         if e.code == _capi.VDF_E_BAD_DIMS:
             raise VidProc(str(e)) from e
         raise
+    crops = np.asarray(crops).reshape(-1, 4)
+    if mixed:
+        return [Crop.from_abi((int(np.shape(s)[2]), int(np.shape(s)[1])), c) for s, c in zip(frames, crops)]
     h, w = int(frames.shape[2]), int(frames.shape[3])
-    return [Crop.from_abi((w, h), c) for c in np.asarray(crops).reshape(-1, 4)]
+    return [Crop.from_abi((w, h), c) for c in crops]

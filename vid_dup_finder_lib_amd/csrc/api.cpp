@@ -972,6 +972,7 @@ int mixed_check_failed(vdf_ctx *ctx, const vdf::MixedCheck &c)
     case vdf::MixedError::kStrideBelowFrame: return fail(ctx, VDF_E_INVAL, "frame_stride smaller than a frame" + at);
     case vdf::MixedError::kEmptyBox: return fail(ctx, VDF_E_INVAL, "crop box leaves no pixels" + at);
     case vdf::MixedError::kOutOfBuffer: return fail(ctx, VDF_E_INVAL, "clip reaches past the end of the buffer" + at);
+    case vdf::MixedError::kCropGiven: return fail(ctx, VDF_E_INVAL, "caller-supplied crop box in a letterbox call" + at);
     case vdf::MixedError::kNone: break;
     }
     return VDF_OK;
@@ -1132,6 +1133,91 @@ int letterbox_hash_device_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n
     return checked_launches(ctx, all, frames_per_clip, [&](size_t c0, size_t n) {
         return letterbox_launch(ctx, all.clips(c0, n), frames_per_clip, out_crops ? out_crops + 4 * c0 : nullptr, d_out_crops ? d_out_crops + 4 * c0 : nullptr);
     });
+}
+
+// ---- letterbox detection on clips of different frame sizes (include/vdf.h: vdf_cropdetect_letterbox_clips_device, vdf_hash_clips_u8_letterbox[_device]) ----
+// The checks of both calls, in the order their codes are reported; *plan is valid when VDF_OK comes back and n_clips != 0.
+static int letterbox_clips_plan(vdf_ctx *ctx, const void *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip, const void *out,
+                                vdf::LetterboxMixedPlan *plan)
+{
+    if (n_clips && !clips) return fail(ctx, VDF_E_INVAL, "null pointer");
+    if (n_clips > 0xFFFFFFFFull) return fail(ctx, VDF_E_INVAL, "more than 2^32 - 1 clips in one call");
+    const vdf::MixedClip *mc = reinterpret_cast<const vdf::MixedClip *>(clips);
+    const vdf::MixedCheck chk = vdf::check_mixed(mc, n_clips, frames_per_clip, buf_bytes);
+    if (chk.error != vdf::MixedError::kNone) return mixed_check_failed(ctx, chk);
+    *plan = vdf::plan_letterbox_mixed(mc, n_clips, hash_knobs(ctx));
+    if (plan->kind == vdf::LetterboxMixedPlan::kCropGiven) return mixed_check_failed(ctx, vdf::MixedCheck{vdf::MixedError::kCropGiven, plan->bad_clip});
+    if (n_clips && (!d_buf || !out)) return fail(ctx, VDF_E_INVAL, "null pointer");
+    return VDF_OK;
+}
+
+// The detect passes of a kMixed plan: descriptors through the pinned staging in one upload, then the plan's launches.  The staging is free
+// again when this returns (the upload has run; the kernels stay queued).
+static int letterbox_clips_detect(vdf_ctx *ctx, const uint8_t *d_buf, const vdf::LetterboxMixedPlan &plan, size_t n_clips, uint32_t *d_crops, hipStream_t stream)
+{
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nd = plan.descs.size() * sizeof(vdf::LetterboxProbeDesc);
+    if (plan.descs.size() != n_clips) return fail(ctx, VDF_E_INVAL, "letterbox plan does not cover the call");  // (cannot happen: one descriptor per clip)
+    if (!ctx->pin_desc.reserve(nd)) return fail(ctx, VDF_E_OOM, "host staging for the clip descriptors");
+    std::memcpy(ctx->pin_desc.p, plan.descs.data(), nd);
+    if (int rc = upload(ctx, ctx->crop_desc, ctx->pin_desc.p, nd, stream)) return rc;
+    VDF_HIP(ctx, hipEventRecord(ctx->ev_mid, stream));
+    VDF_HIP(ctx, ctx->crop_work.reserve(plan.work_bytes));
+    const hipError_t e = vdf::launch_letterbox_mixed(d_buf, ctx->crop_desc.as<vdf::LetterboxProbeDesc>(), plan.launches.data(), plan.launches.size(), n_clips, d_crops,
+                                                     ctx->crop_work.as<uint32_t>(), stream);
+    const hipError_t ew = hipEventSynchronize(ctx->ev_mid);
+    if (e != hipSuccess) return fail_hip(ctx, e, "mixed letterbox launch");
+    VDF_HIP(ctx, ew);
+    return VDF_OK;
+}
+
+int cropdetect_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                            uint32_t *d_crops, hipStream_t stream)
+{
+    vdf::LetterboxMixedPlan plan;
+    if (int rc = letterbox_clips_plan(ctx, d_buf, buf_bytes, clips, n_clips, frames_per_clip, d_crops, &plan)) return rc;
+    if (n_clips == 0) return VDF_OK;
+    if (plan.kind == vdf::LetterboxMixedPlan::kUniform) {  // one size, evenly spaced: exactly vdf_cropdetect_letterbox_device
+        VDF_HIP(ctx, hipSetDevice(ctx->device));
+        const uint8_t *base = d_buf + plan.offset0;
+        VDF_HIP(ctx, ctx->crop_work.reserve(vdf::letterbox_work_bytes(std::min(kMaxClipsPerLaunch, n_clips), frames_per_clip)));
+        for (size_t c0 = 0; c0 < n_clips; c0 += kMaxClipsPerLaunch)
+            VDF_HIP(ctx, vdf::launch_letterbox(base + c0 * plan.clip_stride, std::min(kMaxClipsPerLaunch, n_clips - c0), frames_per_clip, clips[0].w, clips[0].h,
+                                               (size_t)clips[0].frame_stride, (size_t)plan.clip_stride, d_crops + 4 * c0, ctx->crop_work.as<uint32_t>(), stream,
+                                               ctx->lb_side_strips));
+        return VDF_OK;
+    }
+    return letterbox_clips_detect(ctx, d_buf, plan, n_clips, d_crops, stream);
+}
+
+// detect, boxes down (the call waits for its detect, as the uniform call does for large frames), then the mixed hash call on the detected boxes
+int letterbox_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                           uint64_t *d_out, uint32_t *d_dc, uint32_t *out_crops, hipStream_t stream)
+{
+    vdf::LetterboxMixedPlan plan;
+    if (int rc = letterbox_clips_plan(ctx, d_buf, buf_bytes, clips, n_clips, frames_per_clip, d_out, &plan)) return rc;
+    if (n_clips == 0) return VDF_OK;
+    if (plan.kind == vdf::LetterboxMixedPlan::kUniform)  // exactly vdf_hash_frames_u8_letterbox_device
+        return letterbox_hash_device_locked(ctx, d_buf + plan.offset0, n_clips, frames_per_clip, clips[0].w, clips[0].h, (size_t)clips[0].frame_stride,
+                                            (size_t)plan.clip_stride, d_out, d_dc, out_crops, stream);
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    VDF_HIP(ctx, ctx->crops.reserve(n_clips * 16));
+    uint32_t *d_crops = ctx->crops.as<uint32_t>();
+    if (int rc = letterbox_clips_detect(ctx, d_buf, plan, n_clips, d_crops, stream)) return rc;
+    if (!ctx->pin_crops.reserve(n_clips * 16)) return fail(ctx, VDF_E_OOM, "host staging for the crop boxes");
+    const uint32_t *crops = ctx->pin_crops.as<uint32_t>();
+    VDF_HIP(ctx, hipMemcpyAsync(ctx->pin_crops.p, d_crops, n_clips * 16, hipMemcpyDeviceToHost, stream));
+    VDF_HIP(ctx, hipEventRecord(ctx->ev_wait, stream));
+    if (int rcw = wait_event(ctx, ctx->ev_wait)) return rcw;
+    if (out_crops) std::memcpy(out_crops, crops, n_clips * 16);
+    std::vector<vdf_clip> boxed(clips, clips + n_clips);
+    for (size_t i = 0; i < n_clips; i++) {
+        boxed[i].crop_left = crops[4 * i]; boxed[i].crop_right = crops[4 * i + 1];
+        boxed[i].crop_top = crops[4 * i + 2]; boxed[i].crop_bottom = crops[4 * i + 3];
+    }
+    // check_mixed + plan_mixed + hash_mixed_launch, unchanged: a detected box that leaves no pixels or a box size without an i8 table is reported here,
+    // after the detect, and no hash is written
+    return hash_clips_locked(ctx, d_buf, buf_bytes, boxed.data(), n_clips, frames_per_clip, d_out, d_dc, stream);
 }
 
 
@@ -1618,6 +1704,34 @@ int vdf_hash_clips_u8(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const 
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_hash_clips_u8 takes a single-device context");
     return hash_clips_host_locked(ctx, buf, buf_bytes, clips, n_clips, frames_per_clip, out_hashes, out_dontcare);
+}
+
+int vdf_cropdetect_letterbox_clips_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                                          uint32_t *d_crops, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    VDF_SINGLE_DEVICE_ONLY(ctx);
+    return cropdetect_clips_locked(ctx, d_buf, buf_bytes, clips, n_clips, frames_per_clip, d_crops, stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int vdf_hash_clips_u8_letterbox_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                                       uint64_t *d_out_hashes, uint32_t *d_out_dontcare, uint32_t *out_crops, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    VDF_SINGLE_DEVICE_ONLY(ctx);
+    return letterbox_clips_locked(ctx, d_buf, buf_bytes, clips, n_clips, frames_per_clip, d_out_hashes, d_out_dontcare, out_crops,
+                                  stream ? (hipStream_t)stream : ctx->stream);
+}
+
+int vdf_hash_clips_u8_letterbox(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                                uint64_t *out_hashes, uint32_t *out_crops, uint32_t *out_dontcare)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_hash_clips_u8_letterbox takes a single-device context");
+    return hash_clips_host_locked(ctx, buf, buf_bytes, clips, n_clips, frames_per_clip, out_hashes, out_dontcare, 1, out_crops);
 }
 
 int vdf_hash_frames_u8_letterbox_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip,

@@ -461,18 +461,14 @@ __device__ __forceinline__ bool columns_narrow(const uint8_t *__restrict__ f, ui
 // work: 64 sub-lists (one shared counter took 40 000 same-address atomics 0.6 ms when every 64 x 64 clip of a batch had side bars): counts[64],
 // then 64 x cap entries {frame index (clip * n_probe + probe), top, bottom, left | right << 1 first-strip flags}; frame i appends to sub-list
 // i % 64, so cap = ceil(frames / 64) entries always suffice.
-constexpr uint32_t kWorkLists = 64;
-__global__ __launch_bounds__(256, 8) void letterbox_kernel(const uint8_t *__restrict__ frames, uint32_t W, uint32_t H,
-                                                        size_t frame_stride, size_t clip_stride, uint32_t n_probe,
-                                                        uint32_t tol, uint32_t *__restrict__ crops, uint32_t *__restrict__ work)
+constexpr uint32_t kWorkLists = kLetterboxWorkLists;
+// The per-frame work of pass 1, shared by the uniform kernel (frame base, W and H from its arguments) and the mixed kernel (from the clip's
+// descriptor).  f, W, H and tol must be wave-uniform (SGPRs); frame = this frame's index in the launch, n_frames = frames of the launch;
+// clip_crops = the four words of the frame's clip.  Every load stays inside [f, f + W * H) (DESIGN.md 4.2 has the audit).
+__device__ __forceinline__ void letterbox_frame_pass1(const uint8_t *__restrict__ f, uint32_t W, uint32_t H, uint32_t tol, uint32_t frame, uint32_t n_frames,
+                                                      uint32_t *__restrict__ clip_crops, uint32_t *__restrict__ work, uint32_t (*s_hist)[256],
+                                                      uint32_t (*s_hist4)[4 * 256], uint32_t *s_edge, uint32_t *s_prog)
 {
-    __shared__ uint32_t s_hist[4][256];
-    __shared__ uint32_t s_hist4[2][4 * 256];  // the row walkers' four-strip batches
-    __shared__ uint32_t s_edge[4];
-    __shared__ uint32_t s_prog[4];  // strips each walker has confirmed so far
-    const size_t clip = blockIdx.x / n_probe;
-    const uint32_t probe = blockIdx.x % n_probe;  // frame 8 * probe
-    const uint8_t *f = frames + clip * clip_stride + (size_t)(8 * probe) * frame_stride;
     // (readfirstlane: the wave index is uniform, and saying so keeps every per-wave LDS address - histograms, s_prog, s_edge - in SGPRs; as a
     // per-lane value they cost the 64-register budget of eight waves per SIMD four VGPRs it did not have: 4 spills to scratch until round 5)
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -522,16 +518,119 @@ __global__ __launch_bounds__(256, 8) void letterbox_kernel(const uint8_t *__rest
     const bool deferred = (l | r) != 0 && (uint64_t)t + b < H && (uint64_t)l + r < W;
     if (deferred) {
         if (threadIdx.x == 0) {
-            const uint32_t k = blockIdx.x % kWorkLists, cap = (gridDim.x + kWorkLists - 1) / kWorkLists;
+            const uint32_t k = frame % kWorkLists, cap = (n_frames + kWorkLists - 1) / kWorkLists;
             const uint32_t at = atomicAdd(&work[k], 1u);
             uint32_t *e = work + kWorkLists + 4 * ((size_t)k * cap + at);
-            e[0] = blockIdx.x; e[1] = t; e[2] = b; e[3] = l | (r << 1);
+            e[0] = frame; e[1] = t; e[2] = b; e[3] = l | (r << 1);
         }
     } else if (threadIdx.x < 4) {
         // video_frames_gray.rs:119-127: converging edges (e.g. a uniform frame) mean "no crop"
         const bool ok = (long long)W - l - r >= 1 && (long long)H - t - b >= 1;
-        atomicMin(&crops[clip * 4 + threadIdx.x], ok ? s_edge[threadIdx.x] : 0u);  // union = per-edge minimum
+        atomicMin(&clip_crops[threadIdx.x], ok ? s_edge[threadIdx.x] : 0u);  // union = per-edge minimum
     }
+}
+
+__global__ __launch_bounds__(256, 8) void letterbox_kernel(const uint8_t *__restrict__ frames, uint32_t W, uint32_t H,
+                                                        size_t frame_stride, size_t clip_stride, uint32_t n_probe,
+                                                        uint32_t tol, uint32_t *__restrict__ crops, uint32_t *__restrict__ work)
+{
+    __shared__ uint32_t s_hist[4][256];
+    __shared__ uint32_t s_hist4[2][4 * 256];  // the row walkers' four-strip batches
+    __shared__ uint32_t s_edge[4];
+    __shared__ uint32_t s_prog[4];  // strips each walker has confirmed so far
+    const size_t clip = blockIdx.x / n_probe;
+    const uint32_t probe = blockIdx.x % n_probe;  // frame 8 * probe
+    const uint8_t *f = frames + clip * clip_stride + (size_t)(8 * probe) * frame_stride;
+    letterbox_frame_pass1(f, W, H, tol, blockIdx.x, gridDim.x, crops + clip * 4, work, s_hist, s_hist4, s_edge, s_prog);
+}
+
+// A clip's descriptor as wave-uniform values: the address depends on the workgroup alone, and readfirstlane says so where the compiler does not
+// see it - W, H, the frame base and the strides then sit in SGPRs, as the uniform kernels' arguments do (per-lane they would cost pass 1 the
+// registers its eight waves per SIMD do not have).
+struct ProbeFrame { const uint8_t *f; uint32_t W, H, slot; };
+__device__ __forceinline__ uint32_t uniform_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t uniform_u64(uint64_t v) { return (uint64_t)uniform_u32((uint32_t)v) | ((uint64_t)uniform_u32((uint32_t)(v >> 32)) << 32); }
+__device__ __forceinline__ ProbeFrame probe_frame(const uint8_t *__restrict__ buf, const LetterboxProbeDesc *__restrict__ desc, uint32_t frame)
+{
+    const LetterboxProbeDesc *d = desc + frame / kLetterboxProbes;
+    const uint64_t offset = uniform_u64(d->offset), frame_stride = uniform_u64(d->frame_stride);
+    return ProbeFrame{buf + offset + (size_t)(8 * (frame % kLetterboxProbes)) * frame_stride, uniform_u32(d->w), uniform_u32(d->h), uniform_u32(d->slot)};
+}
+
+// Pass 1 on clips of different frame sizes: workgroup i probes frame 8 (i % 2) of the clip of descriptor i / 2.
+__global__ __launch_bounds__(256, 8) void cropdetect_mixed_kernel(const uint8_t *__restrict__ buf, const LetterboxProbeDesc *__restrict__ desc, uint32_t tol,
+                                                              uint32_t *__restrict__ crops, uint32_t *__restrict__ work)
+{
+    __shared__ uint32_t s_hist[4][256];
+    __shared__ uint32_t s_hist4[2][4 * 256];
+    __shared__ uint32_t s_edge[4];
+    __shared__ uint32_t s_prog[4];
+    const ProbeFrame p = probe_frame(buf, desc, blockIdx.x);
+    letterbox_frame_pass1(p.f, p.W, p.H, tol, blockIdx.x, gridDim.x, crops + (size_t)p.slot * 4, work, s_hist, s_hist4, s_edge, s_prog);
+}
+
+// The per-frame work of pass 2 (shared like pass 1's): the left / right walkers of one work-list entry, then the frame's four edges are final.
+// f, W, H, tol, t, b, flags (the entry's first-strip bits) wave-uniform.
+template <int kColumnBatch>
+__device__ __forceinline__ void letterbox_frame_sides(const uint8_t *__restrict__ f, uint32_t W, uint32_t H, uint32_t tol, uint32_t t, uint32_t b, uint32_t flags,
+                                                      uint32_t *__restrict__ clip_crops, uint32_t (*s_histn)[kColumnBatch / 2 * 256 + 64], uint32_t *s_edge,
+                                                      uint32_t *s_prog)
+{
+    const uint32_t wave = threadIdx.x >> 6, first = (flags >> wave) & 1u;
+    const bool right = wave == 1;
+    uint32_t *hist = s_histn[wave];
+    if (threadIdx.x < 2) s_prog[threadIdx.x] = (flags >> threadIdx.x) & 1u;
+    __syncthreads();
+    auto publish = [&](uint32_t n) {
+        if ((threadIdx.x & 63) == 0) __atomic_store_n(&s_prog[wave], n, __ATOMIC_RELAXED);
+    };
+    auto converged = [&]() {
+        const uint32_t l = __atomic_load_n(&s_prog[0], __ATOMIC_RELAXED), r = __atomic_load_n(&s_prog[1], __ATOMIC_RELAXED);
+        return __builtin_amdgcn_readfirstlane((int)((uint64_t)l + r >= W)) != 0;
+    };
+    uint32_t n = first;
+    if (first) {
+        bool walking = true;
+        // Aligned probes for bars (columns_narrow), where rows and frame are line-aligned: a window of 128 bytes, after its first
+        // failure 64, after that the counted 32-column batches for good.  The window that holds strip n starts at or before it: the strips
+        // in front of n inside it were accepted already, and if they are not constant columns (a noisy bar) the probe just fails.
+        // (W is a multiple of the window, so a window that starts inside a row ends inside it.)
+        const uint32_t align = (uint32_t)(reinterpret_cast<uintptr_t>(f) | W);  // rows start where the frame does, W bytes apart
+        uint32_t probe = kColumnBatch != 32 ? 0u : (align & 127u) == 0 ? 128u : (align & 63u) == 0 ? 64u : 0u;
+        while (walking && n + kColumnBatch <= W && H < 65536u && !converged()) {
+            if (probe) {
+                const uint32_t edge = right ? W - n : n;                                              // first column not yet accepted (left) / one past it (right)
+                const uint32_t a = right ? (edge + probe - 1) / probe * probe - probe : edge / probe * probe;  // the aligned window that holds it
+                const bool clean = probe == 128u ? columns_narrow<128>(f, W, H, a, tol) : columns_narrow<64>(f, W, H, a, tol);
+                if (clean) {
+                    n = right ? W - a : a + probe;
+                    publish(n);
+                    continue;
+                }
+                probe = probe == 128u ? 64u : 0u;
+                continue;
+            }
+            // a batch of narrow columns (a bar, clean or noisy) is accepted without a histogram; the batch where the picture begins fails
+            // this at its first row group and is counted
+            const uint32_t x0 = right ? W - n - kColumnBatch : n;
+            const uint32_t got = columns_narrow<kColumnBatch>(f, W, H, x0, tol) ? (uint32_t)kColumnBatch
+                                                                               : column_strips<kColumnBatch>(f, W, H, x0, right, tol, s_histn[wave]);
+            n += got;
+            publish(n);
+            walking = got == (uint32_t)kColumnBatch;
+        }
+        if (walking)
+            while (n < W && !converged() && strip_is_letterbox(right ? f + (W - n - 1) : f + n, W, H, tol, hist)) publish(++n);
+    }
+    if ((threadIdx.x & 63) == 0) s_edge[wave] = n;
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const uint32_t l = s_edge[0], r = s_edge[1];
+        const uint32_t edge[4] = {l, r, t, b};
+        const bool ok = (long long)W - l - r >= 1 && (long long)H - t - b >= 1;
+        atomicMin(&clip_crops[threadIdx.x], ok ? edge[threadIdx.x] : 0u);
+    }
+    __syncthreads();  // s_edge / s_prog are rewritten for the next entry
 }
 
 // Pass 2: the frames with side bars.  Persistent workgroups of two waves (left / right walker) take entries off the work list and walk
@@ -546,74 +645,42 @@ __global__ __launch_bounds__(128) void letterbox_sides_kernel(const uint8_t *__r
     __shared__ uint32_t s_edge[2];
     __shared__ uint32_t s_prog[2];
     // workgroup b serves sub-list b % 64 from entry b / 64 in steps of gridDim.x / 64 (the grid is a multiple of 64)
-    const uint32_t wave = threadIdx.x >> 6, list = blockIdx.x % kWorkLists, cap = (n_frames + kWorkLists - 1) / kWorkLists;
+    const uint32_t list = blockIdx.x % kWorkLists, cap = (n_frames + kWorkLists - 1) / kWorkLists;
     const uint32_t n_work = work[list];
-    const bool right = wave == 1;
-    uint32_t *hist = s_histn[wave];
     for (uint32_t at = blockIdx.x / kWorkLists; at < n_work; at += gridDim.x / kWorkLists) {
         const uint32_t *e = work + kWorkLists + 4 * ((size_t)list * cap + at);
-        const uint32_t frame = e[0], t = e[1], b = e[2], first = (e[3] >> wave) & 1u;
+        const uint32_t frame = e[0];
         const size_t clip = frame / n_probe;
         const uint8_t *f = frames + clip * clip_stride + (size_t)(8 * (frame % n_probe)) * frame_stride;
-        if (threadIdx.x < 2) s_prog[threadIdx.x] = (e[3] >> threadIdx.x) & 1u;
-        __syncthreads();
-        auto publish = [&](uint32_t n) {
-            if ((threadIdx.x & 63) == 0) __atomic_store_n(&s_prog[wave], n, __ATOMIC_RELAXED);
-        };
-        auto converged = [&]() {
-            const uint32_t l = __atomic_load_n(&s_prog[0], __ATOMIC_RELAXED), r = __atomic_load_n(&s_prog[1], __ATOMIC_RELAXED);
-            return __builtin_amdgcn_readfirstlane((int)((uint64_t)l + r >= W)) != 0;
-        };
-        uint32_t n = first;
-        if (first) {
-            bool walking = true;
-            // Aligned probes for bars (columns_narrow), where rows and frame are line-aligned: a window of 128 bytes, after its first
-            // failure 64, after that the counted 32-column batches for good.  The window that holds strip n starts at or before it: the strips
-            // in front of n inside it were accepted already, and if they are not constant columns (a noisy bar) the probe just fails.
-            const uint32_t align = (uint32_t)(reinterpret_cast<uintptr_t>(f) | W);  // rows start where the frame does, W bytes apart
-            uint32_t probe = kColumnBatch != 32 ? 0u : (align & 127u) == 0 ? 128u : (align & 63u) == 0 ? 64u : 0u;
-            while (walking && n + kColumnBatch <= W && H < 65536u && !converged()) {
-                if (probe) {
-                    const uint32_t edge = right ? W - n : n;                                              // first column not yet accepted (left) / one past it (right)
-                    const uint32_t a = right ? (edge + probe - 1) / probe * probe - probe : edge / probe * probe;  // the aligned window that holds it
-                    const bool clean = probe == 128u ? columns_narrow<128>(f, W, H, a, tol) : columns_narrow<64>(f, W, H, a, tol);
-                    if (clean) {
-                        n = right ? W - a : a + probe;
-                        publish(n);
-                        continue;
-                    }
-                    probe = probe == 128u ? 64u : 0u;
-                    continue;
-                }
-                // a batch of narrow columns (a bar, clean or noisy) is accepted without a histogram; the batch where the picture begins fails
-                // this at its first row group and is counted
-                const uint32_t x0 = right ? W - n - kColumnBatch : n;
-                const uint32_t got = columns_narrow<kColumnBatch>(f, W, H, x0, tol) ? (uint32_t)kColumnBatch
-                                                                                   : column_strips<kColumnBatch>(f, W, H, x0, right, tol, s_histn[wave]);
-                n += got;
-                publish(n);
-                walking = got == (uint32_t)kColumnBatch;
-            }
-            if (walking)
-                while (n < W && !converged() && strip_is_letterbox(right ? f + (W - n - 1) : f + n, W, H, tol, hist)) publish(++n);
-        }
-        if ((threadIdx.x & 63) == 0) s_edge[wave] = n;
-        __syncthreads();
-        if (threadIdx.x < 4) {
-            const uint32_t l = s_edge[0], r = s_edge[1];
-            const uint32_t edge[4] = {l, r, t, b};
-            const bool ok = (long long)W - l - r >= 1 && (long long)H - t - b >= 1;
-            atomicMin(&crops[clip * 4 + threadIdx.x], ok ? edge[threadIdx.x] : 0u);
-        }
-        __syncthreads();  // s_edge / s_prog are rewritten for the next entry
+        letterbox_frame_sides<kColumnBatch>(f, W, H, tol, e[1], e[2], e[3], crops + clip * 4, s_histn, s_edge, s_prog);
+    }
+}
+
+// Pass 2 on clips of different frame sizes: the same work list (entries name the frame's index in the launch), the frame from its descriptor.
+// cap = ceil(n_frames / 64) and the entries below the sub-list's count are what pass 1 of the same launch wrote: frame < n_frames.
+template <int kColumnBatch>
+__global__ __launch_bounds__(128) void cropdetect_sides_mixed_kernel(const uint8_t *__restrict__ buf, const LetterboxProbeDesc *__restrict__ desc, uint32_t tol,
+                                                                    uint32_t *__restrict__ crops, const uint32_t *__restrict__ work, uint32_t n_frames)
+{
+    __shared__ uint32_t s_histn[2][kColumnBatch / 2 * 256 + 64];
+    __shared__ uint32_t s_edge[2];
+    __shared__ uint32_t s_prog[2];
+    const uint32_t list = blockIdx.x % kWorkLists, cap = (n_frames + kWorkLists - 1) / kWorkLists;
+    const uint32_t n_work = min(uniform_u32(work[list]), cap);
+    for (uint32_t at = blockIdx.x / kWorkLists; at < n_work; at += gridDim.x / kWorkLists) {
+        const uint32_t *e = work + kWorkLists + 4 * ((size_t)list * cap + at);
+        const uint32_t frame = uniform_u32(e[0]);
+        if (frame >= n_frames) continue;  // (wave- and workgroup-uniform)
+        const ProbeFrame p = probe_frame(buf, desc, frame);
+        letterbox_frame_sides<kColumnBatch>(p.f, p.W, p.H, tol, uniform_u32(e[1]), uniform_u32(e[2]), uniform_u32(e[3]), crops + (size_t)p.slot * 4, s_histn, s_edge,
+                                            s_prog);
     }
 }
 
 size_t letterbox_work_bytes(size_t n_clips, uint32_t frames_per_clip)
 {
     const uint32_t nf = frames_per_clip < VDF_DCT_SIZE ? frames_per_clip : VDF_DCT_SIZE;
-    const size_t frames = n_clips * ((nf + 7) / 8), cap = (frames + kWorkLists - 1) / kWorkLists;
-    return (kWorkLists + 4 * kWorkLists * cap) * sizeof(uint32_t);
+    return letterbox_work_list_bytes(n_clips * ((nf + 7) / 8));
 }
 
 hipError_t launch_letterbox(const uint8_t *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h,
@@ -649,6 +716,39 @@ hipError_t launch_letterbox(const uint8_t *frames, size_t n_clips, uint32_t fram
         hipLaunchKernelGGL(letterbox_sides_kernel<8>, dim3(grid_for(16)), dim3(128), 0, stream, frames, w, h, frame_stride, clip_stride, n_probe, 16u, crops,
                            work, n_frames);
     return hipGetLastError();
+}
+
+hipError_t launch_letterbox_mixed(const uint8_t *buf, const LetterboxProbeDesc *d_desc, const LetterboxMixedLaunch *launches, size_t n_launches, size_t n_clips,
+                                  uint32_t *crops, uint32_t *work, hipStream_t stream)
+{
+    if (n_clips == 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(crops, 0xFF, n_clips * 4 * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    for (size_t i = 0; i < n_launches; i++) {
+        const LetterboxMixedLaunch &l = launches[i];
+        if (l.count == 0 || l.count > kMaxClipsPerLaunch) return hipErrorInvalidValue;
+        uint32_t *list = work + l.work_offset / sizeof(uint32_t);  // this launch's own work list
+        const LetterboxProbeDesc *d = d_desc + l.first;
+        const uint32_t n_frames = (uint32_t)(l.count * kLetterboxProbes);
+        e = hipMemsetAsync(list, 0, kWorkLists * sizeof(uint32_t), stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(cropdetect_mixed_kernel, dim3(n_frames), dim3(256), 0, stream, buf, d, 16u, crops, list);
+        auto grid_for = [&](uint32_t per_cu) {  // as launch_letterbox
+            const size_t want = std::min<size_t>(n_frames, (size_t)cus * per_cu);
+            return (uint32_t)((want + kWorkLists - 1) / kWorkLists * kWorkLists);
+        };
+        if (l.column_batch == 32)
+            hipLaunchKernelGGL(cropdetect_sides_mixed_kernel<32>, dim3(grid_for(4)), dim3(128), 0, stream, buf, d, 16u, crops, list, n_frames);
+        else if (l.column_batch == 16)
+            hipLaunchKernelGGL(cropdetect_sides_mixed_kernel<16>, dim3(grid_for(9)), dim3(128), 0, stream, buf, d, 16u, crops, list, n_frames);
+        else
+            hipLaunchKernelGGL(cropdetect_sides_mixed_kernel<8>, dim3(grid_for(16)), dim3(128), 0, stream, buf, d, 16u, crops, list, n_frames);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 }  // namespace vdf

@@ -214,11 +214,13 @@ int hash_host_locked(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32
 constexpr size_t kStagedTailSlack = 128, kStagedClipAlign = 64, kDirectClipBytes = 1u << 20;
 
 int hash_clips_host_locked(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
-                           uint64_t *out_hashes, uint32_t *out_dontcare)
+                           uint64_t *out_hashes, uint32_t *out_dontcare, int letterbox, uint32_t *out_crops)
 {
     if (n_clips && !clips) return fail(ctx, VDF_E_INVAL, "null pointer");
     const vdf::MixedCheck chk = vdf::check_mixed(reinterpret_cast<const vdf::MixedClip *>(clips), n_clips, frames_per_clip, buf_bytes);
     if (chk.error != vdf::MixedError::kNone) return mixed_check_failed(ctx, chk);
+    for (size_t i = 0; letterbox && i < n_clips; i++)  // the letterbox call takes whole frames (the staged descriptors keep the caller's boxes)
+        if (clips[i].crop_left | clips[i].crop_right | clips[i].crop_top | clips[i].crop_bottom) return mixed_check_failed(ctx, vdf::MixedCheck{vdf::MixedError::kCropGiven, i});
     if (n_clips == 0) return VDF_OK;
     if (!buf || !out_hashes) return fail(ctx, VDF_E_INVAL, "null pointer");
     VDF_HIP(ctx, hipSetDevice(ctx->device));
@@ -313,7 +315,11 @@ int hash_clips_host_locked(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, c
         }
         uint32_t *dc = out_dontcare ? d_dc[slot]->as<uint32_t>() : nullptr;
         // the STAGED descriptors against the STAGED size
-        if ((rc = hash_clips_locked(ctx, dev, total, staged[slot].data(), B.n, VDF_DCT_SIZE, d_hash[slot]->as<uint64_t>(), dc, s))) return rc;
+        if (letterbox)
+            rc = letterbox_clips_locked(ctx, dev, total, staged[slot].data(), B.n, VDF_DCT_SIZE, d_hash[slot]->as<uint64_t>(), dc, out_crops ? out_crops + 4 * B.c0 : nullptr, s);
+        else
+            rc = hash_clips_locked(ctx, dev, total, staged[slot].data(), B.n, VDF_DCT_SIZE, d_hash[slot]->as<uint64_t>(), dc, s);
+        if (rc) return rc;
         uint8_t *po = ctx->pin_out[slot].as<uint8_t>();
         VDF_HIP(ctx, hipMemcpyAsync(po, d_hash[slot]->p, B.n * VDF_HASH_WORDS * 8, hipMemcpyDeviceToHost, s));
         if (dc) VDF_HIP(ctx, hipMemcpyAsync(po + B.n * VDF_HASH_WORDS * 8, dc, B.n * 4, hipMemcpyDeviceToHost, s));

@@ -7,6 +7,8 @@
 //   * a clip of more than staging_bytes is refused (VDF_E_INVAL) without touching a slot.
 // The leader hashes its batch with ONE vdf_hash_clips_u8 call on the slot's context: the clips sit in the slot's staging one after the
 // other, each on a 64-byte boundary.  The slots per GPU are a parameter of the create call; this file reads no environment variable.
+// A letterbox queue (vdf_hash_queue_create_mixed_letterbox) hashes its batches with vdf_hash_clips_u8_letterbox instead and hands every
+// caller its clip's box as well.
 #include <chrono>
 #include <condition_variable>
 #include <cstdlib>
@@ -18,6 +20,10 @@
 #include <hip/hip_runtime.h>
 
 #include "vdf_ctx.h"
+
+// Weak: only a letterbox queue reaches it, so a program that never makes one (the plain queue's stand-alone test) links without a definition.
+extern "C" int vdf_hash_clips_u8_letterbox(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                                           uint64_t *out_hashes, uint32_t *out_crops, uint32_t *out_dontcare) __attribute__((weak));
 
 namespace {
 
@@ -32,6 +38,7 @@ struct Slot {
     uint8_t *staging = nullptr;  // pinned host memory, staging_bytes
     bool pinned = false;
     std::vector<uint64_t> hashes;
+    std::vector<uint32_t> crops;  // a letterbox queue: the batch's boxes
     std::vector<vdf_clip> clips;
     enum { COLLECTING, RUNNING, DRAINING } state = COLLECTING;
     uint32_t count = 0, ready = 0, remaining = 0;
@@ -51,6 +58,7 @@ size_t aligned_clip_bytes(uint32_t w, uint32_t h) { return ((size_t)w * h * VDF_
 struct vdf_hash_queue_mixed {
     size_t staging_bytes = 0, largest_clip = 0;  // the slots' staging (a multiple of 64); the caller's limit as given
     uint32_t max_batch = 0, max_wait_us = 0;
+    bool letterbox = false;
     std::vector<Slot> slots;
     size_t cur = 0;  // the slot new arrivals join
     std::mutex mu;
@@ -72,13 +80,15 @@ void vdf_hash_queue_mixed_destroy(vdf_hash_queue_mixed *q)
     delete q;
 }
 
-int vdf_hash_queue_create_mixed(vdf_ctx *ctx, size_t staging_bytes, uint32_t max_batch, uint32_t max_wait_us, uint32_t slots_per_gpu,
-                                vdf_hash_queue_mixed **out)
+static int create_queue(vdf_ctx *ctx, size_t staging_bytes, uint32_t max_batch, uint32_t max_wait_us, uint32_t slots_per_gpu, bool letterbox,
+                        vdf_hash_queue_mixed **out)
 {
     if (!ctx || !out || staging_bytes == 0 || max_batch == 0 || slots_per_gpu > 16) return VDF_E_INVAL;
     *out = nullptr;
+    if (letterbox && !vdf_hash_clips_u8_letterbox) return VDF_E_INVAL;  // (a program linked without the letterbox call)
     vdf_hash_queue_mixed *q = new (std::nothrow) vdf_hash_queue_mixed();
     if (!q) return VDF_E_OOM;
+    q->letterbox = letterbox;
     q->staging_bytes = (staging_bytes + kAlign - 1) & ~(kAlign - 1);
     q->largest_clip = staging_bytes;
     q->max_batch = max_batch; q->max_wait_us = max_wait_us;
@@ -102,13 +112,26 @@ int vdf_hash_queue_create_mixed(vdf_ctx *ctx, size_t staging_bytes, uint32_t max
         }
         s.hashes.resize((size_t)max_batch * VDF_HASH_WORDS);
         s.clips.resize(max_batch);
+        if (letterbox) s.crops.resize((size_t)max_batch * 4);
     }
     *out = q;
     return VDF_OK;
 }
 
-// frames: 16 gray frames of w x h, tightly packed.  Blocks until hashed.
-int vdf_hash_queue_mixed_submit(vdf_hash_queue_mixed *q, const uint8_t *frames, uint32_t w, uint32_t h, uint64_t *out_hash)
+int vdf_hash_queue_create_mixed(vdf_ctx *ctx, size_t staging_bytes, uint32_t max_batch, uint32_t max_wait_us, uint32_t slots_per_gpu,
+                                vdf_hash_queue_mixed **out)
+{
+    return create_queue(ctx, staging_bytes, max_batch, max_wait_us, slots_per_gpu, false, out);
+}
+
+int vdf_hash_queue_create_mixed_letterbox(vdf_ctx *ctx, size_t staging_bytes, uint32_t max_batch, uint32_t max_wait_us, uint32_t slots_per_gpu,
+                                          vdf_hash_queue_mixed **out)
+{
+    return create_queue(ctx, staging_bytes, max_batch, max_wait_us, slots_per_gpu, true, out);
+}
+
+// frames: 16 gray frames of w x h, tightly packed.  Blocks until hashed.  out_crop (nullable): the clip's box, zeros from a plain queue.
+int vdf_hash_queue_mixed_submit_crop(vdf_hash_queue_mixed *q, const uint8_t *frames, uint32_t w, uint32_t h, uint64_t *out_hash, uint32_t *out_crop)
 {
     if (!q || !frames || !out_hash || w == 0 || h == 0) return VDF_E_INVAL;
     const size_t clip_bytes = (size_t)w * h * VDF_DCT_SIZE, need = aligned_clip_bytes(w, h);
@@ -159,7 +182,8 @@ int vdf_hash_queue_mixed_submit(vdf_hash_queue_mixed *q, const uint8_t *frames, 
         q->in_flight++;
         if (q->in_flight > q->in_flight_max) q->in_flight_max = q->in_flight;
         lk.unlock();
-        const int rc = vdf_hash_clips_u8(s.ctx, s.staging, used, s.clips.data(), n, VDF_DCT_SIZE, s.hashes.data(), nullptr);
+        const int rc = q->letterbox ? vdf_hash_clips_u8_letterbox(s.ctx, s.staging, used, s.clips.data(), n, VDF_DCT_SIZE, s.hashes.data(), s.crops.data(), nullptr)
+                                    : vdf_hash_clips_u8(s.ctx, s.staging, used, s.clips.data(), n, VDF_DCT_SIZE, s.hashes.data(), nullptr);
         lk.lock();
         q->in_flight--;
         s.batch_rc = rc;
@@ -175,6 +199,10 @@ int vdf_hash_queue_mixed_submit(vdf_hash_queue_mixed *q, const uint8_t *frames, 
     }
     const int rc = s.batch_rc;
     if (rc == VDF_OK) std::memcpy(out_hash, s.hashes.data() + (size_t)my * VDF_HASH_WORDS, VDF_HASH_WORDS * 8);
+    if (rc == VDF_OK && out_crop) {
+        if (q->letterbox) std::memcpy(out_crop, s.crops.data() + (size_t)my * 4, 16);
+        else std::memset(out_crop, 0, 16);
+    }
     if (--s.remaining == 0) {  // last one out reopens the slot
         s.count = 0;
         s.ready = 0;
@@ -188,6 +216,11 @@ int vdf_hash_queue_mixed_submit(vdf_hash_queue_mixed *q, const uint8_t *frames, 
             for (uint32_t i = 0; i < wake; i++) q->cv_free.notify_one();
     }
     return rc;
+}
+
+int vdf_hash_queue_mixed_submit(vdf_hash_queue_mixed *q, const uint8_t *frames, uint32_t w, uint32_t h, uint64_t *out_hash)
+{
+    return vdf_hash_queue_mixed_submit_crop(q, frames, w, h, out_hash, nullptr);
 }
 
 int vdf_hash_queue_mixed_stats(vdf_hash_queue_mixed *q, uint64_t *n_batches, uint64_t *n_clips)

@@ -417,4 +417,44 @@ MixedPlan plan_mixed(const MixedClip *clips, size_t n, const HashKnobs &k)
     return p;
 }
 
+LetterboxMixedPlan plan_letterbox_mixed(const MixedClip *clips, size_t n, const HashKnobs &)
+{
+    LetterboxMixedPlan p;
+    for (size_t i = 0; i < n; i++)
+        if ((clips[i].crop[0] | clips[i].crop[1] | clips[i].crop[2] | clips[i].crop[3]) != 0) {
+            p.kind = LetterboxMixedPlan::kCropGiven;
+            p.bad_clip = i;
+            return p;
+        }
+    if (n == 0) return p;
+    bool uniform = true;  // plan_mixed's rule
+    const uint64_t step = n > 1 ? clips[1].offset - clips[0].offset : 16 * clips[0].frame_stride;
+    for (size_t i = 0; i < n; i++) {
+        const MixedClip &c = clips[i];
+        uniform = uniform && c.w == clips[0].w && c.h == clips[0].h && c.frame_stride == clips[0].frame_stride;
+        if (i > 0) uniform = uniform && c.offset > clips[i - 1].offset && c.offset - clips[i - 1].offset == step;
+    }
+    if (uniform) {
+        p.kind = LetterboxMixedPlan::kUniform;
+        p.offset0 = clips[0].offset;
+        p.clip_stride = step;
+        return p;
+    }
+    p.descs.reserve(n);
+    for (int batch : {8, 16, 32}) {
+        const size_t first = p.descs.size();
+        for (size_t i = 0; i < n; i++) {
+            const MixedClip &c = clips[i];
+            if (letterbox_column_batch(c.h) != batch) continue;
+            p.descs.push_back(LetterboxProbeDesc{c.offset, c.frame_stride, c.w, c.h, (uint32_t)i, 0u});
+        }
+        for (size_t at = first; at < p.descs.size(); at += kMaxClipsPerLaunch) {
+            const size_t count = std::min(kMaxClipsPerLaunch, p.descs.size() - at);
+            p.launches.push_back(LetterboxMixedLaunch{batch, at, count, p.work_bytes});
+            p.work_bytes += letterbox_work_list_bytes(count * kLetterboxProbes);
+        }
+    }
+    return p;
+}
+
 }  // namespace vdf

@@ -173,7 +173,7 @@ static_assert(offsetof(MixedClipDesc, offset) == 0 && offsetof(MixedClipDesc, fr
 static_assert(sizeof(MixedClip) == 40, "vdf_clip layout");
 
 // The argument checks, in the order their codes are reported (as checked_launches): over ALL clips before anything is queued.
-enum class MixedError { kNone, kNotEnoughFrames, kZeroDim, kStrideBelowFrame, kEmptyBox, kOutOfBuffer };
+enum class MixedError { kNone, kNotEnoughFrames, kZeroDim, kStrideBelowFrame, kEmptyBox, kOutOfBuffer, kCropGiven /* the letterbox calls only: plan_letterbox_mixed */ };
 struct MixedCheck { MixedError error = MixedError::kNone; size_t clip = 0; };
 MixedCheck check_mixed(const MixedClip *clips, size_t n, uint32_t frames_per_clip, uint64_t buf_bytes);
 
@@ -204,5 +204,48 @@ struct MixedPlan {
 };
 // clips have passed check_mixed; n <= 2^32 - 1 (out_index is 32 bits)
 MixedPlan plan_mixed(const MixedClip *clips, size_t n, const HashKnobs &k);
+
+// ---- Letterbox detection on clips of different frame sizes (vdf_cropdetect_letterbox_clips_device, vdf_hash_clips_u8_letterbox[_device]) -------
+// What the mixed detect kernels (cropdetect.hip: cropdetect_mixed_kernel, cropdetect_sides_mixed_kernel) read per CLIP: both probed frames
+// (0 and 8) of a clip share one descriptor.  Probe p's frame starts at buf + offset + 8 p frame_stride; its rows are w bytes apart.
+struct LetterboxProbeDesc {
+    uint64_t offset;        // first byte of frame 0, relative to the buffer
+    uint64_t frame_stride;  // bytes between frames
+    uint32_t w, h;
+    uint32_t slot;          // the clip's position in the caller's array: its box is crops[4 slot ..]
+    uint32_t reserved;      // 0
+};
+static_assert(sizeof(LetterboxProbeDesc) == 32 && sizeof(LetterboxProbeDesc) % 16 == 0, "descriptors are read as whole 16-byte pieces");
+static_assert(offsetof(LetterboxProbeDesc, offset) == 0 && offsetof(LetterboxProbeDesc, frame_stride) == 8 && offsetof(LetterboxProbeDesc, w) == 16 &&
+              offsetof(LetterboxProbeDesc, h) == 20 && offsetof(LetterboxProbeDesc, slot) == 24 && offsetof(LetterboxProbeDesc, reserved) == 28,
+              "LetterboxProbeDesc layout");
+constexpr uint32_t kLetterboxProbes = 2;      // frames 0 and 8: the mixed call requires 16 frames per clip
+constexpr uint32_t kLetterboxWorkLists = 64;  // pass 1 appends frame i to sub-list i % 64 of its launch's work list
+// bytes of one work list for `frames` probed frames: 64 counters, then 64 sub-lists of cap = ceil(frames / 64) entries of four words
+constexpr size_t letterbox_work_list_bytes(size_t frames)
+{
+    return (kLetterboxWorkLists + 4 * kLetterboxWorkLists * ((frames + kLetterboxWorkLists - 1) / kLetterboxWorkLists)) * sizeof(uint32_t);
+}
+// the column batch of pass 2 by frame height, as launch_letterbox chooses it (speed only: the crops are exact for every batch)
+constexpr int letterbox_column_batch(uint32_t h) { return h >= 512 ? 32 : h >= 256 ? 16 : 8; }
+struct LetterboxMixedLaunch {
+    int column_batch;     // 8, 16 or 32: the cropdetect_sides_mixed_kernel instantiation
+    size_t first, count;  // descs[first .. first + count): 2 count workgroups in pass 1
+    size_t work_offset;   // bytes from the start of the work buffer to this launch's own work list
+};
+struct LetterboxMixedPlan {
+    enum Kind { kUniform, kMixed, kCropGiven /* a clip came with a crop box: VDF_E_INVAL */ } kind = kMixed;
+    size_t bad_clip = 0;  // kCropGiven: the first such clip
+    // kUniform: one frame size, one frame stride, offsets one positive step apart: today's uniform letterbox route on (base + offset0, clip_stride)
+    uint64_t offset0 = 0, clip_stride = 0;
+    // kMixed: one descriptor per clip, class by class (column batch 8, 16, 32), each class cut into launches of at most kMaxClipsPerLaunch clips;
+    // every launch has its own work list, so no frame is walked by two classes
+    std::vector<LetterboxProbeDesc> descs;
+    std::vector<LetterboxMixedLaunch> launches;
+    size_t work_bytes = 0;  // all work lists
+};
+// clips have passed check_mixed; n <= 2^32 - 1.  The letterbox calls take the whole frame as the reference does: a caller-supplied crop box is
+// refused (MixedError::kCropGiven), after every error of check_mixed.
+LetterboxMixedPlan plan_letterbox_mixed(const MixedClip *clips, size_t n, const HashKnobs &k);
 
 }  // namespace vdf

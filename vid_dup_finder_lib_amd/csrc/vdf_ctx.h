@@ -289,7 +289,10 @@ int letterbox_hash_device_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n
 int hash_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
                       uint64_t *d_out, uint32_t *d_dc, hipStream_t stream);
 int hash_clips_host_locked(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
-                           uint64_t *out_hashes, uint32_t *out_dontcare);
+                           uint64_t *out_hashes, uint32_t *out_dontcare, int letterbox = 0, uint32_t *out_crops = nullptr);
+// the same with Cropdetect::Letterbox first (vdf_hash_clips_u8_letterbox[_device]): detect on per-clip descriptors, the boxes down, the mixed hash on them
+int letterbox_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                           uint64_t *d_out, uint32_t *d_dc, uint32_t *out_crops, hipStream_t stream);
 int mixed_check_failed(vdf_ctx *ctx, const vdf::MixedCheck &c);  // reports a check_mixed finding with its status code
 void destroy_copy_pool(vdf_ctx *ctx);
 bool is_sorted_u32(const uint32_t *d, size_t n);

@@ -174,6 +174,10 @@ hipError_t launch_resize_dct_cropped_small_boxes(const uint8_t *frames, size_t n
                                                  size_t clip_stride, const uint8_t *buf_end, const uint32_t *boxes,
                                                  const CropTableEntry *tables, const double *cos_table, uint64_t *out_hashes,
                                                  uint32_t *out_dontcare, hipStream_t stream);
+// The same two passes on clips of different frame sizes (resize_dispatch.h: plan_letterbox_mixed gives descriptors, launches and the size of `work`).
+// d_desc: DEVICE descriptors, every probed frame inside the buffer (check_mixed); crops: DEVICE [n_clips][4], every slot of the plan written.
+hipError_t launch_letterbox_mixed(const uint8_t *buf, const LetterboxProbeDesc *d_desc, const LetterboxMixedLaunch *launches, size_t n_launches, size_t n_clips,
+                                  uint32_t *crops, uint32_t *work, hipStream_t stream);
 // frames of at most 64 x 64: detect + crop + resize + DCT + hash in one persistent kernel (dct_hash.hip: letterbox_resize_dct_hash_small_kernel).
 // Every clip's 16-byte loads must stay inside the caller's buffer: the caller keeps the clips within 64 bytes of its end out of this launch.
 // box_tables: the set's tables at kSmallBoxTableStride bytes each, in the order above: operand hi | lo (2 x 1024 B), bias[16], precision.

@@ -194,10 +194,9 @@ class Engine:
         self._check(self.lib.vdf_hash_frames_u8_device(self.ctx, d_frames, n_clips, frames_per_clip, w, h, fs, cs,
                                                        d_out, d_dontcare or None, stream or None))
 
-    def hash_clips(self, stacks: Sequence[np.ndarray], crops=None, want_dontcare: bool = False):
-        """Clips of DIFFERENT frame sizes in one call (vdf_hash_clips_u8): stacks = a list of [>= 16, H, W] u8 arrays, each with its own
-        H and W; crops (optional) = [n, 4] u32 left, right, top, bottom per clip.  -> hashes [n, 16] u64 [, dontcare [n] u32], in the
-        order of the list.  Raises VdfError(VDF_E_NOT_ENOUGH_FRAMES) when a stack has fewer than 16 frames."""
+    @staticmethod
+    def _pack_stacks(stacks: Sequence[np.ndarray]):
+        """The stacks of a mixed call one after the other in one buffer, every clip on a 64-byte boundary: (buffer, CLIP_DTYPE records, frames)."""
         stacks = [np.ascontiguousarray(s, dtype=np.uint8) for s in stacks]
         n = len(stacks)
         if any(s.ndim != 3 for s in stacks):
@@ -208,12 +207,51 @@ class Engine:
         for i, s in enumerate(stacks):
             clips[i]["offset"], clips[i]["frame_stride"], clips[i]["w"], clips[i]["h"] = at, s.shape[1] * s.shape[2], s.shape[2], s.shape[1]
             at += (min(s.shape[0], 16) * s.shape[1] * s.shape[2] + 63) & ~63
-        if crops is not None:
-            clips["crop"] = np.asarray(crops, dtype=np.uint32).reshape(n, 4)
         buf = np.zeros(max(at, 1), np.uint8)
         for i, s in enumerate(stacks):
             flat = s[:16].reshape(-1)
             buf[int(clips[i]["offset"]):int(clips[i]["offset"]) + flat.size] = flat
+        return buf, clips, nf
+
+    def hash_clips_letterbox(self, stacks: Sequence[np.ndarray], want_dontcare: bool = False):
+        """crop_video_frames(Cropdetect::Letterbox) + from_frames for clips of DIFFERENT frame sizes in one call (vdf_hash_clips_u8_letterbox):
+        stacks = a list of [>= 16, H, W] u8 arrays -> (hashes [n, 16] u64, crops [n, 4] u32 = l, r, t, b [, dontcare [n] u32]), in the order
+        of the list."""
+        buf, clips, nf = self._pack_stacks(stacks)
+        n = len(clips)
+        out = np.zeros((n, HASH_WORDS), np.uint64)
+        crops = np.zeros((n, 4), np.uint32)
+        dc = np.zeros(n, np.uint32) if want_dontcare else None
+        self._check(self.lib.vdf_hash_clips_u8_letterbox(self.ctx, buf.ctypes.data, buf.size, clips.ctypes.data, n, nf, out.ctypes.data,
+                                                         crops.ctypes.data, dc.ctypes.data if want_dontcare else None))
+        return (out, crops, dc) if want_dontcare else (out, crops)
+
+    def hash_clips_letterbox_device(self, d_buf: int, buf_bytes: int, clips: np.ndarray, d_out: int, d_dontcare: int = 0,
+                                    frames_per_clip: int = 16, stream: int = 0) -> np.ndarray:
+        """vdf_hash_clips_u8_letterbox_device: clips = HOST array of CLIP_DTYPE records with all-zero crop fields; returns the detected boxes
+        [n, 4] u32 (the call waits for its detect); clip i's hash goes to d_out + 128 i, ordered on `stream`."""
+        c = np.ascontiguousarray(clips, dtype=CLIP_DTYPE)
+        crops = np.zeros((c.size, 4), np.uint32)
+        self._check(self.lib.vdf_hash_clips_u8_letterbox_device(self.ctx, d_buf, int(buf_bytes), c.ctypes.data if c.size else None, c.size,
+                                                                int(frames_per_clip), d_out, d_dontcare or None, crops.ctypes.data, stream or None))
+        return crops
+
+    def cropdetect_letterbox_clips_device(self, d_buf: int, buf_bytes: int, clips: np.ndarray, d_crops: int, frames_per_clip: int = 16,
+                                          stream: int = 0):
+        """vdf_cropdetect_letterbox_clips_device: the boxes of clips of different frame sizes, left on the device (d_crops: [n, 4] u32),
+        ordered on `stream`; only queues work."""
+        c = np.ascontiguousarray(clips, dtype=CLIP_DTYPE)
+        self._check(self.lib.vdf_cropdetect_letterbox_clips_device(self.ctx, d_buf, int(buf_bytes), c.ctypes.data if c.size else None, c.size,
+                                                                   int(frames_per_clip), d_crops, stream or None))
+
+    def hash_clips(self, stacks: Sequence[np.ndarray], crops=None, want_dontcare: bool = False):
+        """Clips of DIFFERENT frame sizes in one call (vdf_hash_clips_u8): stacks = a list of [>= 16, H, W] u8 arrays, each with its own
+        H and W; crops (optional) = [n, 4] u32 left, right, top, bottom per clip.  -> hashes [n, 16] u64 [, dontcare [n] u32], in the
+        order of the list.  Raises VdfError(VDF_E_NOT_ENOUGH_FRAMES) when a stack has fewer than 16 frames."""
+        buf, clips, nf = self._pack_stacks(stacks)
+        n = len(clips)
+        if crops is not None:
+            clips["crop"] = np.asarray(crops, dtype=np.uint32).reshape(n, 4)
         out = np.zeros((n, HASH_WORDS), np.uint64)
         dc = np.zeros(n, np.uint32) if want_dontcare else None
         self._check(self.lib.vdf_hash_clips_u8(self.ctx, buf.ctypes.data, buf.size, clips.ctypes.data, n, nf, out.ctypes.data,
@@ -561,15 +599,20 @@ class MixedHashQueue:
     """HashQueue for clips of ANY frame size (vdf_hash_queue_mixed_*): one queue serves a whole library.  A batch closes at max_batch clips,
     at staging_bytes of frames, or when its first caller has waited max_wait_us."""
 
-    def __init__(self, engine: Engine, staging_bytes: int = 64 << 20, max_batch: int = 256, max_wait_us: int = 2000, slots_per_gpu: int = 0):
+    def __init__(self, engine: Engine, staging_bytes: int = 64 << 20, max_batch: int = 256, max_wait_us: int = 2000, slots_per_gpu: int = 0,
+                 letterbox: bool = False):
         self.engine = engine
+        self.letterbox = bool(letterbox)
         q = C.c_void_p()
-        engine._check(engine.lib.vdf_hash_queue_create_mixed(engine.ctx, int(staging_bytes), int(max_batch), int(max_wait_us),
-                                                             int(slots_per_gpu), C.byref(q)))
+        create = engine.lib.vdf_hash_queue_create_mixed_letterbox if self.letterbox else engine.lib.vdf_hash_queue_create_mixed
+        engine._check(create(engine.ctx, int(staging_bytes), int(max_batch), int(max_wait_us), int(slots_per_gpu), C.byref(q)))
         self.q = q
 
-    def submit(self, frames: np.ndarray) -> np.ndarray:
-        """frames [>=16, H, W] u8 -> hash [16] u64.  Blocks; releases the GIL while waiting."""
+    def submit(self, frames: np.ndarray):
+        """frames [>=16, H, W] u8 -> hash [16] u64; a letterbox queue: (hash, crop (l, r, t, b)), as HashQueue.submit.  Blocks; releases the
+        GIL while waiting."""
+        if self.letterbox:
+            return self.submit_crop(frames)
         f = np.ascontiguousarray(frames[:16], dtype=np.uint8)
         if f.ndim != 3 or f.shape[0] != 16:
             raise ValueError("a clip is at least 16 frames of [H, W]")
@@ -578,6 +621,18 @@ class MixedHashQueue:
         if rc != 0:
             raise VdfError(rc, "mixed hash queue: clip of %d x %d refused or its batch failed" % (f.shape[2], f.shape[1]))
         return out
+
+    def submit_crop(self, frames: np.ndarray):
+        """vdf_hash_queue_mixed_submit_crop on either kind of queue: (hash [16] u64, crop (l, r, t, b)); a plain queue's crop is all zero."""
+        f = np.ascontiguousarray(frames[:16], dtype=np.uint8)
+        if f.ndim != 3 or f.shape[0] != 16:
+            raise ValueError("a clip is at least 16 frames of [H, W]")
+        out = np.zeros(HASH_WORDS, np.uint64)
+        crop = np.zeros(4, np.uint32)
+        rc = self.engine.lib.vdf_hash_queue_mixed_submit_crop(self.q, f.ctypes.data, f.shape[2], f.shape[1], out.ctypes.data, crop.ctypes.data)
+        if rc != 0:
+            raise VdfError(rc, "mixed hash queue: clip of %d x %d refused or its batch failed" % (f.shape[2], f.shape[1]))
+        return out, tuple(int(x) for x in crop)
 
     def stats(self):
         nb, nc = C.c_uint64(0), C.c_uint64(0)

@@ -201,6 +201,36 @@ public:
         return out;
     }
 
+    // ... with Cropdetect::Letterbox first, the builder's default (vdf_hash_clips_u8_letterbox); crops_out (optional): l, r, t, b per clip
+    static std::vector<VideoHash> from_frame_stacks_letterbox(const std::vector<FrameStack> &stacks, std::vector<std::array<uint32_t, 4>> *crops_out = nullptr,
+                                                              Context *ctx_opt = nullptr)
+    {
+        Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+        std::vector<vdf_clip> clips(stacks.size());
+        size_t at = 0;
+        for (size_t i = 0; i < stacks.size(); i++) {
+            clips[i] = vdf_clip{at, (uint64_t)stacks[i].w * stacks[i].h, stacks[i].w, stacks[i].h, 0, 0, 0, 0};
+            at += ((size_t)VDF_DCT_SIZE * stacks[i].w * stacks[i].h + 63) & ~(size_t)63;
+        }
+        std::vector<uint8_t> packed(at);
+        for (size_t i = 0; i < stacks.size(); i++)
+            std::copy(stacks[i].frames, stacks[i].frames + (size_t)VDF_DCT_SIZE * stacks[i].w * stacks[i].h, packed.begin() + (size_t)clips[i].offset);
+        std::vector<uint64_t> words(stacks.size() * VDF_HASH_WORDS);
+        std::vector<std::array<uint32_t, 4>> crops(stacks.size());
+        const int rc = vdf_hash_clips_u8_letterbox(ctx.get(), packed.data(), packed.size(), clips.data(), clips.size(), VDF_DCT_SIZE, words.data(),
+                                                   crops.empty() ? nullptr : crops[0].data(), nullptr);
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+        std::vector<VideoHash> out;
+        for (size_t i = 0; i < stacks.size(); i++) {
+            std::array<uint64_t, VDF_HASH_WORDS> h;
+            std::copy(words.begin() + i * VDF_HASH_WORDS, words.begin() + (i + 1) * VDF_HASH_WORDS, h.begin());
+            out.emplace_back(h, stacks[i].src_path, stacks[i].duration);
+        }
+        if (crops_out) *crops_out = std::move(crops);
+        return out;
+    }
+
     const std::string &src_path() const { return src_path_; }
     uint32_t duration() const { return duration_; }
     uint32_t hamming_distance(const VideoHash &o) const { return vdf_hamming_u1024(hash_.data(), o.hash_.data()); }
