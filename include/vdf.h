@@ -249,6 +249,55 @@ int vdf_hash_clips_u8_letterbox_device(vdf_ctx *ctx, const uint8_t *d_buf, size_
 int vdf_hash_clips_u8_letterbox(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips,
                                 uint32_t frames_per_clip, uint64_t *out_hashes, uint32_t *out_crops, uint32_t *out_dontcare);
 
+/* ---- mirrored, flipped and reversed duplicates from ONE hash pass -------------------------------------
+ * The reference cannot see through a horizontal mirror or a flip (vid_dup_finder_lib/src/lib.rs:102-111).  Here the hash of the
+ * flipped clip follows from the clip's own hash: the quantised resize tables are mirror-symmetric and the DCT's first step is
+ * x[i] +- x[15 - i], so flipping the clip along W, along H or in time multiplies coefficient (kt, kx, ky) by (-1)^kx, (-1)^ky or
+ * (-1)^kt - bit for bit, up to the sign of zero.  The hash keeps coef > 0.0, so all that is missing is where the
+ * coefficients are exactly zero - the ZERO PLANE Z: 16 words per clip, bit i set iff coefficient i == 0.0 (bits 1000 ... 1023 are 0,
+ * and H & Z == 0).  Then, with variant v: bit 0 = mirror along W, bit 1 = flip along H, bit 2 = reverse the 16 frames used, and
+ *     M_v[i] = 1 iff i < 1000 and ((v & 1) kx + ((v >> 1) & 1) ky + ((v >> 2) & 1) kt) is odd,   i = 100 kt + 10 kx + ky,
+ *     H_v = (H ^ M_v) & ~Z
+ * is exactly the hash the plain call gives for the flipped frames.  Exact zeros are not rare (a static clip has 900).
+ *
+ * The planes calls are the plain calls plus out_zero (n_clips x 16 words, required): same checks in the same order, same kernel
+ * route for the same input, out_hashes bit-identical to the plain call's.  An axis size whose resize table is not its own mirror
+ * image would be refused with VDF_E_BAD_DIMS (none is, for 1 ... 4200; the call asks per size).  The clips calls take crop boxes in
+ * their descriptors, so they are also the letterboxed form - detect with the calls above, pass the boxes in - and a variant of a
+ * cropped clip is the flip of the CROPPED clip.  A multi-GPU context refuses all four with VDF_E_INVAL.
+ * The app's hash cache has no room for the plane: hashes loaded from a cache cannot be flipped. */
+int vdf_hash_frames_u8_planes(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w,
+                              uint32_t h, size_t frame_stride, size_t clip_stride, uint64_t *out_hashes,
+                              uint32_t *out_dontcare, uint64_t *out_zero);
+int vdf_hash_frames_u8_planes_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip,
+                                     uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride, uint64_t *d_out_hashes,
+                                     uint32_t *d_out_dontcare, uint64_t *d_out_zero, void *stream);
+int vdf_hash_clips_u8_planes(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips,
+                             uint32_t frames_per_clip, uint64_t *out_hashes, uint32_t *out_dontcare, uint64_t *out_zero);
+int vdf_hash_clips_u8_planes_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips,
+                                    uint32_t frames_per_clip, uint64_t *d_out_hashes, uint32_t *d_out_dontcare,
+                                    uint64_t *d_out_zero, void *stream);
+/* H_v of one hash (host only, no context): hash, zero, out = 16 words each (out may alias hash).  variant > 7 or a null pointer ->
+ * VDF_E_INVAL; variant 0 is the identity on a hash of the planes calls. */
+int vdf_hash_variant(const uint64_t *hash, const uint64_t *zero, uint32_t variant, uint64_t *out);
+/* The same for n resident hashes: d_out (n x 16 words, not d_hashes or d_zero) ordered on stream.  Single-device contexts. */
+int vdf_hash_variants_device(vdf_ctx *ctx, const uint64_t *d_hashes, const uint64_t *d_zero, size_t n, uint32_t variant,
+                             uint64_t *d_out, void *stream);
+/* Which entries look like the MIRROR of which: for every variant v whose bit is set in variant_mask (bits 1 ... 7; bit 0 or a bit
+ * above 7 -> VDF_E_INVAL) the library derives V_v = the variant-v hashes on the device and runs the reference search
+ * (vdf_search_refs: search_one's +-5% windows, search_algorithm.rs:63-77,173-185) with V_v as the references and the plain hashes
+ * as the candidates, both carrying the same durations.  hashes / zero / durations: n entries in sorted order.  The pair (r, r) - a
+ * clip against its own mirror (a static or symmetric clip is its own mirror) - is dropped, and so are references left without a
+ * match.  out: the caller's array of 8 vdf_groups, indexed by v; out[v] of a requested v is in the reference-search shape
+ * (ref_index = r, members ascending): "the variant v of r looks like these".  The others are zeroed.  Release each with
+ * vdf_groups_free().  A pair may be reported from both sides (r in a's group and a in r's); and where coefficients are exactly zero
+ * d(v(a), b) and d(a, v(b)) can differ (the zero plane of a clears bits of v(a) that b may have set), so near the tolerance it
+ * may be reported from one side only.  Single-device contexts. */
+int vdf_search_variants(vdf_ctx *ctx, const uint64_t *hashes, const uint64_t *zero, const uint32_t *durations, size_t n,
+                        uint32_t tol_int, uint32_t variant_mask, vdf_groups *out /* [8] */);
+int vdf_search_variants_device(vdf_ctx *ctx, const uint64_t *d_hashes, const uint64_t *d_zero, const uint32_t *d_durations,
+                               size_t n, uint32_t tol_int, uint32_t variant_mask, vdf_groups *out /* [8] */, void *stream);
+
 /* ---- search(): replaces Search::search_self, search_algorithm.rs:81-171 (hot loop :150-156) --
  * hashes: n x 16 words, durations: n, both in sorted order.  tol_int from vdf_tolerance_int().
  * Groups come back exactly as search() builds them (video_dup_finder.rs:7-13): members = hits in

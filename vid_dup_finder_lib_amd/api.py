@@ -18,10 +18,10 @@ import numpy as np
 
 from . import _capi
 from ._capi import DEFAULT_SEARCH_TOLERANCE, HASH_BITS, HASH_WORDS, TOLERANCE_SCALING_FACTOR, VdfError
-from .engine import Engine, hamming_distance_words, tolerance_int
+from .engine import Engine, hamming_distance_words, hash_variant, tolerance_int
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
-           "search_with_references", "default_engine", "hash_frame_stacks", "rust_path_key", "sort_order",
+           "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "rust_path_key", "sort_order",
            "DEFAULT_SEARCH_TOLERANCE", "TOLERANCE_SCALING_FACTOR"]
 
 
@@ -51,6 +51,14 @@ class Cropdetect(enum.Enum):
     NONE = "none"
     LETTERBOX = "letterbox"
     MOTION = "motion"
+
+
+class Flip(enum.IntFlag):
+    """Which way a clip is flipped: X = mirrored along the width, Y = flipped along the height, T = its 16 frames reversed; any
+    combination (the `variant` of include/vdf.h: vdf_hash_variant)."""
+    X = 1
+    Y = 2
+    T = 4
 
 
 class Crop:
@@ -207,16 +215,31 @@ def sort_order(hashes: Sequence["VideoHash"], engine: Optional[Engine] = None) -
 # ---- VideoHash (video_hash.rs:26-32) ----------------------------------------------------------------
 class VideoHash:
     """hash: 16 x u64 (1024 bits, Lsb0; bits 1000..1023 are zero when built from frames),
-    src_path, duration in seconds."""
+    src_path, duration in seconds.
+    zero (optional, not in the reference): the clip's zero plane, 16 x u64 with bit i set iff DCT coefficient i is exactly 0.0 -
+    what flipped() needs.  Hashes made with zero_plane=True carry it; the hash cache's wire format has no room for it, so hashes
+    loaded from a cache cannot be flipped.  It takes no part in comparisons or ordering."""
 
-    __slots__ = ("hash", "_src_path", "_duration")
+    __slots__ = ("hash", "_src_path", "_duration", "zero")
 
-    def __init__(self, hash_words=None, src_path="", duration: int = 0):
+    def __init__(self, hash_words=None, src_path="", duration: int = 0, zero=None):
         if hash_words is None:
             hash_words = np.zeros(HASH_WORDS, np.uint64)  # Default, video_hash.rs:34-42
         self.hash = np.ascontiguousarray(hash_words, dtype=np.uint64).reshape(HASH_WORDS).copy()
         self._src_path = src_path
         self._duration = int(duration)
+        self.zero = None if zero is None else np.ascontiguousarray(zero, dtype=np.uint64).reshape(HASH_WORDS).copy()
+
+    def flipped(self, flip) -> "VideoHash":
+        """The VideoHash the same pipeline gives for the flipped clip (Flip.X: mirrored, Flip.Y: upside down, Flip.T: reversed, or any
+        combination), derived from this hash and its zero plane alone - bit for bit what hashing the flipped frames gives.  Same path
+        and duration; the zero plane of a flipped clip is the clip's own."""
+        if self.zero is None:
+            raise VidProc("this VideoHash carries no zero plane (hash with zero_plane=True; hashes loaded from a cache have none)")
+        v = int(flip)
+        if not 0 <= v <= 7:
+            raise ValueError("flip must be a combination of Flip.X, Flip.Y, Flip.T")
+        return VideoHash(hash_variant(self.hash, self.zero, v), self._src_path, self._duration, self.zero)
 
     @classmethod
     def from_frames(cls, frames: Iterable[np.ndarray], src_path, duration: int,
@@ -262,10 +285,10 @@ class VideoHash:
 
     # test_util-style constructors (video_hash.rs:240-308) that need no RNG
     def with_duration(self, duration: int) -> "VideoHash":
-        return VideoHash(self.hash, self._src_path, duration)
+        return VideoHash(self.hash, self._src_path, duration, self.zero)
 
     def with_src_path(self, src_path) -> "VideoHash":
-        return VideoHash(self.hash, src_path, self._duration)
+        return VideoHash(self.hash, src_path, self._duration, self.zero)
 
     @classmethod
     def full_hash(cls, name) -> "VideoHash":
@@ -410,12 +433,56 @@ def search_with_references(ref_hashes: Iterable[VideoHash], new_hashes: Iterable
             for r, ms in res]
 
 
+def search_flipped(hashes: Iterable[VideoHash], tolerance: float, flips: Sequence = (Flip.X,), engine: Optional[Engine] = None) -> dict:
+    """Mirrored / flipped / reversed duplicates, which the reference cannot see (vid_dup_finder_lib/src/lib.rs:102-111):
+    {flip: [MatchGroup]} for every flip of `flips`.  A group's reference is the path of an entry r, its duplicates the paths of the
+    entries whose hash is within `tolerance` of the hash of r FLIPPED, inside r's +-5 % duration window (search_one's, as
+    search_with_references); r itself is never among them, and entries whose flip matches nothing have no group.  Groups are in
+    Search::sort order of their reference.  A pair usually shows from both sides (a in the group of b and b in the group of a).
+    Every hash needs its zero plane (zero_plane=True when hashing), else VidProc."""
+    hashes = list(hashes)
+    flips = [Flip(int(f)) for f in flips]
+    if any(not 1 <= int(f) <= 7 for f in flips):
+        raise ValueError("flips are non-empty combinations of Flip.X, Flip.Y, Flip.T")
+    if any(h.zero is None for h in hashes):
+        raise VidProc("search_flipped needs the zero plane of every hash (hash with zero_plane=True)")
+    if not hashes or not flips:
+        return {f: [] for f in flips}
+    engine = engine or default_engine()
+    order = sort_order(hashes, engine)
+    words, dur = _soa(hashes, order)
+    zero = np.stack([hashes[i].zero for i in order])
+    mask = 0
+    for f in flips:
+        mask |= 1 << int(f)
+    res = engine.search_variants_sorted(words, zero, dur, tolerance_int(tolerance), mask)
+    return {f: [MatchGroup.new_with_reference(hashes[order[r]].src_path(), [hashes[order[m]].src_path() for m in ms]) for r, ms in res[int(f)]]
+            for f in flips}
+
+
+def _with_planes(call):
+    try:
+        return call()
+    except VdfError as e:
+        if e.code == _capi.VDF_E_NOT_ENOUGH_FRAMES:
+            raise NotEnoughFrames() from e
+        if e.code == _capi.VDF_E_BAD_DIMS:
+            raise VidProc(str(e)) from e
+        raise
+
+
 def hash_frame_stacks(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int],
-                      engine: Optional[Engine] = None) -> List[VideoHash]:
+                      engine: Optional[Engine] = None, zero_plane: bool = False) -> List[VideoHash]:
     """Batched VideoHash.from_frames: frames [n_clips, n_frames >= 16, H, W] u8 -> one VideoHash per clip
     (the batching a caller of VideoHashBuilder::hash would do to feed the GPU; SURVEY.md section 8f N2).
     frames may also be a LIST of [n_frames >= 16, H, W] stacks of different frame sizes (files arrive in whatever resolution they
-    have): they are hashed by one call all the same (Engine.hash_clips)."""
+    have): they are hashed by one call all the same (Engine.hash_clips).
+    zero_plane: the hashes also carry their zero plane (VideoHash.zero; Engine.hash_frames_planes / hash_clips_planes), so that
+    VideoHash.flipped and search_flipped work on them; the hash words are the same."""
+    if zero_plane:
+        eng = engine or default_engine()
+        words, zero = _with_planes(lambda: eng.hash_clips_planes(frames) if isinstance(frames, (list, tuple)) else eng.hash_frames_planes(frames))
+        return [VideoHash(words[i], src_paths[i], durations[i], zero[i]) for i in range(len(words))]
     try:
         eng = engine or default_engine()
         words = eng.hash_clips(frames) if isinstance(frames, (list, tuple)) else eng.hash_frames(frames)
@@ -427,16 +494,27 @@ def hash_frame_stacks(frames: np.ndarray, src_paths: Sequence, durations: Sequen
 
 
 def gen_hashes(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int],
-               cropdetect: Cropdetect = Cropdetect.LETTERBOX, engine: Optional[Engine] = None) -> List[VideoHash]:
+               cropdetect: Cropdetect = Cropdetect.LETTERBOX, engine: Optional[Engine] = None, zero_plane: bool = False) -> List[VideoHash]:
     """The part of `gen_hash` after decode (video_hash_builder.rs:214-223) for a batch of clips:
     crop_video_frames(cropdetect) -- default Letterbox, like CreationOptions::default (:55-63) -- then
     VideoHash::from_frames.  frames [n_clips, n_frames >= 16, H, W] u8, or a LIST of [n_frames >= 16, H, W] stacks of different frame
     sizes (Engine.hash_clips_letterbox; with Cropdetect.NONE hash_frame_stacks).  Detection (frames 0 and 8,
-    video_frames_gray.rs:201-210) and the cropped resize both run on the GPU; no cropped copies are made."""
+    video_frames_gray.rs:201-210) and the cropped resize both run on the GPU; no cropped copies are made.
+    zero_plane: the hashes also carry their zero plane (see hash_frame_stacks); with LETTERBOX the boxes are detected by the letterbox
+    call and the planes call then hashes the clips on those boxes, so a flip is the flip of the CROPPED clip."""
     if cropdetect == Cropdetect.NONE:
-        return hash_frame_stacks(frames, src_paths, durations, engine)
+        return hash_frame_stacks(frames, src_paths, durations, engine, zero_plane)
     if cropdetect != Cropdetect.LETTERBOX:
         raise VidProc("Cropdetect::Motion is not supported by the accelerated path")
+    if zero_plane:
+        eng = engine or default_engine()
+        stacks = list(frames)
+
+        def both():
+            _words, crops = eng.hash_clips_letterbox(stacks) if isinstance(frames, (list, tuple)) else eng.hash_frames_letterbox(frames)
+            return eng.hash_clips_planes(stacks, crops=crops)
+        words, zero = _with_planes(both)
+        return [VideoHash(words[i], src_paths[i], durations[i], zero[i]) for i in range(len(words))]
     try:
         eng = engine or default_engine()
         words, _crops = eng.hash_clips_letterbox(frames) if isinstance(frames, (list, tuple)) else eng.hash_frames_letterbox(frames)

@@ -38,7 +38,8 @@ vdf_ctx::~vdf_ctx()
     DevBuf *all[] = {&row_lo, &row_hi, &tile_lo, &tile_hi, &tile_first, &tile_count, &tile_offset, &counters,
                      &hits, &perm, &matched, &exp_cols, &exp_rows, &pop_cols, &pop_rows, &cand, &group_cmin, &group_offset, &group_blocks, &up_hashes,
                      &up_dur, &up_ref_hashes, &up_ref_dur, &small, &frames, &frames2, &out_hashes, &out_hashes2, &out_dc,
-                     &out_dc2, &cos_table, &crops, &crop_desc, &crop_tables, &crop_desc2, &crop_tables2, &crop_work, &sort_scratch, &sort_scratch_pub, &hits2, &hit_bitmaps, &bitmap_gather};
+                     &out_dc2, &cos_table, &crops, &crop_desc, &crop_tables, &crop_desc2, &crop_tables2, &crop_work, &sort_scratch, &sort_scratch_pub, &hits2, &hit_bitmaps, &bitmap_gather,
+                     &out_zero, &out_zero2, &up_zero, &variant_hashes};
     for (DevBuf *b : all) b->release();
     for (PinBuf &b : pin) b.release();
     for (PinBuf &b : pin_out) b.release();
@@ -597,11 +598,13 @@ struct HashJob {
     uint64_t *d_out;
     uint32_t *d_dc;
     hipStream_t stream;
+    uint64_t *d_zero = nullptr;  // the zero planes, or none
     vdf::HashCall call() const { return vdf::HashCall{d_frames, w, h, frame_stride, clip_stride, n_clips}; }
     const uint8_t *buf_end() const { return d_frames + (n_clips - 1) * clip_stride + (VDF_DCT_SIZE - 1) * frame_stride + (size_t)w * h; }
     HashJob clips(size_t c0, size_t n) const
     {
-        return HashJob{d_frames + c0 * clip_stride, n, w, h, frame_stride, clip_stride, d_out + c0 * VDF_HASH_WORDS, d_dc ? d_dc + c0 : nullptr, stream};
+        return HashJob{d_frames + c0 * clip_stride, n, w, h, frame_stride, clip_stride, d_out + c0 * VDF_HASH_WORDS, d_dc ? d_dc + c0 : nullptr, stream,
+                       d_zero ? d_zero + c0 * VDF_HASH_WORDS : nullptr};
     }
 };
 
@@ -649,7 +652,7 @@ vdf::MfmaResizeArgs resize_args(const vdf_ctx *ctx, const DeviceMfmaTable *mh, c
 
 int dct_hash_of_small(vdf_ctx *ctx, const HashJob &j)
 {
-    VDF_HIP(ctx, vdf::launch_dct_hash(ctx->small.as<uint8_t>(), 4096, 256, j.n_clips, ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream));
+    VDF_HIP(ctx, vdf::launch_dct_hash(ctx->small.as<uint8_t>(), 4096, 256, j.n_clips, ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream, j.d_zero));
     return VDF_OK;
 }
 
@@ -703,13 +706,13 @@ int hash_launch(vdf_ctx *ctx, const HashJob &j)
     case HashRoute::kRefused: return fail(ctx, VDF_E_BAD_DIMS, "coefficients do not fit the i8 split");
     case HashRoute::kScalar: return hash_scalar(ctx, j);
     case HashRoute::kDirect16:
-        VDF_HIP(ctx, vdf::launch_dct_hash(j.d_frames, j.clip_stride, j.frame_stride, j.n_clips, ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream));
+        VDF_HIP(ctx, vdf::launch_dct_hash(j.d_frames, j.clip_stride, j.frame_stride, j.n_clips, ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream, j.d_zero));
         return VDF_OK;
     case HashRoute::kPersistentOneTile:
     case HashRoute::kTiled:
     case HashRoute::kPerClipFused:
         VDF_HIP(ctx, vdf::launch_resize_dct_fused(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, j.buf_end(), resize_args(ctx, mh, mv), plan,
-                                                  ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream));
+                                                  ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream, j.d_zero));
         return VDF_OK;
     case HashRoute::kChunkStream:
     case HashRoute::kWaveStream:
@@ -727,9 +730,9 @@ int hash_launch(vdf_ctx *ctx, const HashJob &j)
 
 int hash_device_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w,
                        uint32_t h, size_t frame_stride, size_t clip_stride, uint64_t *d_out, uint32_t *d_dc,
-                       hipStream_t stream)
+                       hipStream_t stream, uint64_t *d_zero)
 {
-    const HashJob all{d_frames, n_clips, w, h, frame_stride, clip_stride, d_out, d_dc, stream};
+    const HashJob all{d_frames, n_clips, w, h, frame_stride, clip_stride, d_out, d_dc, stream, d_zero};
     return checked_launches(ctx, all, frames_per_clip, [&](size_t c0, size_t n) { return hash_launch(ctx, all.clips(c0, n)); });
 }
 
@@ -786,7 +789,7 @@ int hash_cropped_small(vdf_ctx *ctx, const HashJob &j, const uint32_t *crops)
     if ((rc = upload(ctx, ctx->crop_tables2, ent, std::max<size_t>(tabs.used.size(), 1) * sizeof(vdf::CropTableEntry), j.stream))) return rc;
     VDF_HIP(ctx, hipEventRecord(ctx->ev_mid, j.stream));
     VDF_HIP(ctx, vdf::launch_resize_dct_cropped_small(j.d_frames, j.n_clips, w, j.frame_stride, j.clip_stride, j.buf_end(), ctx->crop_desc2.as<vdf::CropClipDesc>(),
-                                                      ctx->crop_tables2.as<vdf::CropTableEntry>(), ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream));
+                                                      ctx->crop_tables2.as<vdf::CropTableEntry>(), ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream, j.d_zero));
     // the staging is read by the two copies: they must have run before the next call on this context rewrites it (the kernel stays queued)
     VDF_HIP(ctx, hipEventSynchronize(ctx->ev_mid));
     return VDF_OK;
@@ -980,7 +983,8 @@ int mixed_check_failed(vdf_ctx *ctx, const vdf::MixedCheck &c)
 
 // The mixed parts: table entries by box size, every descriptor through the pinned staging in ONE upload for the whole call (so no launch of
 // the call rewrites staging another launch's upload still reads), then the launches of the plan and the DCT of the per-frame parts.
-int hash_mixed_launch(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf::MixedPlan &plan, uint64_t *d_out, uint32_t *d_dc, hipStream_t stream)
+int hash_mixed_launch(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf::MixedPlan &plan, uint64_t *d_out, uint32_t *d_dc, hipStream_t stream,
+                      uint64_t *d_zero)
 {
     VDF_HIP(ctx, hipSetDevice(ctx->device));
     int rc = ensure_cos_table(ctx, stream);
@@ -1024,11 +1028,11 @@ int hash_mixed_launch(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, cons
     for (const vdf::MixedLaunch &l : plan.launches) {
         if (e != hipSuccess) break;
         if (l.part == vdf::MixedPart::kSmall) {
-            e = vdf::launch_mixed_small(d_buf, buf_end, d_desc + l.first, l.count, d_tab, ctx->cos_table.as<double>(), d_out, d_dc, stream);
+            e = vdf::launch_mixed_small(d_buf, buf_end, d_desc + l.first, l.count, d_tab, ctx->cos_table.as<double>(), d_out, d_dc, stream, d_zero);
         } else {
             uint8_t *slot0 = small + (l.first - plan.n_small) * 4096;
             e = vdf::launch_mixed_frames(d_buf, buf_end, d_desc + l.first, l.count, d_tab, l.part == vdf::MixedPart::kWideLines, slot0, stream);
-            if (e == hipSuccess) e = vdf::launch_dct_hash_indexed(slot0, d_desc + l.first, l.count, ctx->cos_table.as<double>(), d_out, d_dc, stream);
+            if (e == hipSuccess) e = vdf::launch_dct_hash_indexed(slot0, d_desc + l.first, l.count, ctx->cos_table.as<double>(), d_out, d_dc, stream, d_zero);
         }
     }
     // the staging is read by the two copies: they must have run before the next call on this context rewrites it (the kernels stay queued)
@@ -1039,7 +1043,7 @@ int hash_mixed_launch(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, cons
 }
 
 int hash_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
-                      uint64_t *d_out, uint32_t *d_dc, hipStream_t stream)
+                      uint64_t *d_out, uint32_t *d_dc, hipStream_t stream, uint64_t *d_zero)
 {
     if (n_clips && !clips) return fail(ctx, VDF_E_INVAL, "null pointer");
     if (n_clips > 0xFFFFFFFFull) return fail(ctx, VDF_E_INVAL, "more than 2^32 - 1 clips in one call");
@@ -1055,11 +1059,11 @@ int hash_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, cons
             crops.resize(n_clips * 4);
             for (size_t i = 0; i < n_clips; i++) std::memcpy(&crops[4 * i], mc[i].crop, 16);
         }
-        const HashJob all{d_buf + plan.offset0, n_clips, mc[0].w, mc[0].h, (size_t)mc[0].frame_stride, (size_t)plan.clip_stride, d_out, d_dc, stream};
+        const HashJob all{d_buf + plan.offset0, n_clips, mc[0].w, mc[0].h, (size_t)mc[0].frame_stride, (size_t)plan.clip_stride, d_out, d_dc, stream, d_zero};
         return checked_launches(ctx, all, frames_per_clip,
                                 [&](size_t c0, size_t n) { return hash_cropped_launch(ctx, all.clips(c0, n), plan.cropped ? crops.data() + 4 * c0 : nullptr); });
     }
-    return hash_mixed_launch(ctx, d_buf, buf_bytes, plan, d_out, d_dc, stream);
+    return hash_mixed_launch(ctx, d_buf, buf_bytes, plan, d_out, d_dc, stream, d_zero);
 }
 
 // Small frames: the boxes stay on the device.  No copy to the host, no wait, no host loop over the clips between the launches; out_crops is
@@ -1704,6 +1708,202 @@ int vdf_hash_clips_u8(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const 
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_hash_clips_u8 takes a single-device context");
     return hash_clips_host_locked(ctx, buf, buf_bytes, clips, n_clips, frames_per_clip, out_hashes, out_dontcare);
+}
+
+// ---- the zero plane and the flipped hashes (include/vdf.h) -------------------------------------------------------------
+// The derivation rests on the resize table of every axis the call resizes being its own mirror image: asked once per size, refused otherwise.
+static int planes_axis_ok(vdf_ctx *ctx, uint32_t size)
+{
+    auto it = ctx->axis_symmetric.find(size);
+    if (it == ctx->axis_symmetric.end()) it = ctx->axis_symmetric.emplace(size, vdf::axis_table_mirror_symmetric(size)).first;
+    if (it->second) return VDF_OK;
+    return fail(ctx, VDF_E_BAD_DIMS, "the resize table of axis size " + std::to_string(size) + " is not mirror-symmetric: no zero plane for this size");
+}
+
+// the plain call's checks in the plain call's order, then the plane's own; *run: there is something to hash
+static int planes_frames_checks(vdf_ctx *ctx, const void *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h, size_t frame_stride,
+                                const void *out_hashes, const void *out_zero, bool *run)
+{
+    *run = false;
+    if (frames_per_clip < VDF_DCT_SIZE) return fail(ctx, VDF_E_NOT_ENOUGH_FRAMES, "fewer than 16 frames per clip");
+    if (w == 0 || h == 0) return fail(ctx, VDF_E_BAD_DIMS, "zero frame dimension");
+    if (frame_stride < (size_t)w * h) return fail(ctx, VDF_E_INVAL, "frame_stride smaller than a frame");
+    if (n_clips == 0) return VDF_OK;
+    if (!frames || !out_hashes || !out_zero) return fail(ctx, VDF_E_INVAL, "null pointer");
+    if (int rc = planes_axis_ok(ctx, w)) return rc;
+    if (int rc = planes_axis_ok(ctx, h)) return rc;
+    *run = true;
+    return VDF_OK;
+}
+
+static int planes_clips_checks(vdf_ctx *ctx, const void *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
+                               const void *out_hashes, const void *out_zero, bool *run)
+{
+    *run = false;
+    if (n_clips && !clips) return fail(ctx, VDF_E_INVAL, "null pointer");
+    if (n_clips > 0xFFFFFFFFull) return fail(ctx, VDF_E_INVAL, "more than 2^32 - 1 clips in one call");
+    const vdf::MixedCheck chk = vdf::check_mixed(reinterpret_cast<const vdf::MixedClip *>(clips), n_clips, frames_per_clip, buf_bytes);
+    if (chk.error != vdf::MixedError::kNone) return mixed_check_failed(ctx, chk);
+    if (n_clips == 0) return VDF_OK;
+    if (!buf || !out_hashes || !out_zero) return fail(ctx, VDF_E_INVAL, "null pointer");
+    for (size_t i = 0; i < n_clips; i++) {  // the BOX is what is resized (check_mixed: it leaves pixels)
+        if (int rc = planes_axis_ok(ctx, clips[i].w - clips[i].crop_left - clips[i].crop_right)) return rc;
+        if (int rc = planes_axis_ok(ctx, clips[i].h - clips[i].crop_top - clips[i].crop_bottom)) return rc;
+    }
+    *run = true;
+    return VDF_OK;
+}
+
+int vdf_hash_frames_u8_planes_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip,
+                                     uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride, uint64_t *d_out_hashes,
+                                     uint32_t *d_out_dontcare, uint64_t *d_out_zero, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    VDF_SINGLE_DEVICE_ONLY(ctx);
+    bool run;
+    if (int rc = planes_frames_checks(ctx, d_frames, n_clips, frames_per_clip, w, h, frame_stride, d_out_hashes, d_out_zero, &run)) return rc;
+    if (!run) return VDF_OK;
+    return hash_device_locked(ctx, d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, d_out_hashes, d_out_dontcare,
+                              stream ? (hipStream_t)stream : ctx->stream, d_out_zero);
+}
+
+int vdf_hash_frames_u8_planes(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w,
+                              uint32_t h, size_t frame_stride, size_t clip_stride, uint64_t *out_hashes,
+                              uint32_t *out_dontcare, uint64_t *out_zero)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_hash_frames_u8_planes takes a single-device context");
+    bool run;
+    if (int rc = planes_frames_checks(ctx, frames, n_clips, frames_per_clip, w, h, frame_stride, out_hashes, out_zero, &run)) return rc;
+    if (!run) return VDF_OK;
+    return hash_host_locked(ctx, frames, n_clips, w, h, frame_stride, clip_stride, 0, out_hashes, nullptr, out_dontcare, out_zero);
+}
+
+int vdf_hash_clips_u8_planes_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips,
+                                    uint32_t frames_per_clip, uint64_t *d_out_hashes, uint32_t *d_out_dontcare,
+                                    uint64_t *d_out_zero, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    VDF_SINGLE_DEVICE_ONLY(ctx);
+    bool run;
+    if (int rc = planes_clips_checks(ctx, d_buf, buf_bytes, clips, n_clips, frames_per_clip, d_out_hashes, d_out_zero, &run)) return rc;
+    if (!run) return VDF_OK;
+    return hash_clips_locked(ctx, d_buf, buf_bytes, clips, n_clips, frames_per_clip, d_out_hashes, d_out_dontcare, stream ? (hipStream_t)stream : ctx->stream,
+                             d_out_zero);
+}
+
+int vdf_hash_clips_u8_planes(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips,
+                             uint32_t frames_per_clip, uint64_t *out_hashes, uint32_t *out_dontcare, uint64_t *out_zero)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_hash_clips_u8_planes takes a single-device context");
+    bool run;
+    if (int rc = planes_clips_checks(ctx, buf, buf_bytes, clips, n_clips, frames_per_clip, out_hashes, out_zero, &run)) return rc;
+    if (!run) return VDF_OK;
+    return hash_clips_host_locked(ctx, buf, buf_bytes, clips, n_clips, frames_per_clip, out_hashes, out_dontcare, 0, nullptr, out_zero);
+}
+
+int vdf_hash_variant(const uint64_t *hash, const uint64_t *zero, uint32_t variant, uint64_t *out)
+{
+    if (!hash || !zero || !out || variant >= vdf::kHashVariants) return VDF_E_INVAL;
+    for (int k = 0; k < VDF_HASH_WORDS; k++) out[k] = (hash[k] ^ vdf::kVariantMasks.m[variant][k]) & ~zero[k];
+    return VDF_OK;
+}
+
+int vdf_hash_variants_device(vdf_ctx *ctx, const uint64_t *d_hashes, const uint64_t *d_zero, size_t n, uint32_t variant,
+                             uint64_t *d_out, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    VDF_SINGLE_DEVICE_ONLY(ctx);
+    if (variant >= vdf::kHashVariants) return fail(ctx, VDF_E_INVAL, "variant above 7");
+    if (n == 0) return VDF_OK;
+    if (!d_hashes || !d_zero || !d_out) return fail(ctx, VDF_E_INVAL, "null pointer");
+    if (d_out == d_hashes || d_out == d_zero) return fail(ctx, VDF_E_INVAL, "the variants are not made in place");
+    if (n >= 0xFFFFFFFFull) return fail(ctx, VDF_E_INVAL, "more than 2^32-1 hashes");
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    VDF_HIP(ctx, vdf::launch_hash_variants(d_hashes, d_zero, n, &variant, 1, d_out, stream ? (hipStream_t)stream : ctx->stream));
+    return VDF_OK;
+}
+
+// One reference search per requested variant: V_v (derived into the context's scratch) against the plain hashes, the same durations on both
+// sides; (r, r) dropped on the host, where the hit list is grouped anyway.
+static int search_variants_locked(vdf_ctx *ctx, const uint64_t *d_hashes, const uint64_t *d_zero, const uint32_t *d_durations, size_t n,
+                                  uint32_t tol_int, uint32_t variant_mask, vdf_groups *out, hipStream_t s)
+{
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    VDF_HIP(ctx, ctx->variant_hashes.reserve(n * VDF_HASH_WORDS * 8));
+    uint64_t *d_var = ctx->variant_hashes.as<uint64_t>();
+    std::vector<vdf_hit> kept;
+    for (uint32_t v = 1; v < vdf::kHashVariants; v++) {
+        if (!(variant_mask >> v & 1u)) continue;
+        VDF_HIP(ctx, vdf::launch_hash_variants(d_hashes, d_zero, n, &v, 1, d_var, s));
+        uint64_t n_hits = 0, capacity = ctx->hit_capacity;
+        int rc = VDF_OK;
+        for (int attempt = 0; attempt < 6; attempt++) {  // every hit is output: size the list up (search_refs_resident)
+            rc = search_refs_device_locked(ctx, d_hashes, d_durations, n, d_var, d_durations, n, tol_int, 0, nullptr, capacity, &n_hits, s, &ctx->host_hits);
+            if (rc == VDF_E_OVERFLOW && n_hits > capacity) { capacity = n_hits; continue; }
+            break;
+        }
+        if (rc) return rc;
+        kept.clear();
+        const vdf_hit *hits = ctx->host_hits.data();
+        for (uint64_t i = 0; i < n_hits; i++)
+            if (hits[i].row != hits[i].col) kept.push_back(hits[i]);
+        if ((rc = vdf_groups_from_ref_hits(kept.data(), kept.size(), &out[v]))) return fail(ctx, rc, "grouping the hits of a variant");
+    }
+    return VDF_OK;
+}
+
+static int search_variants_checks(vdf_ctx *ctx, const void *hashes, const void *zero, const void *durations, size_t n, uint32_t variant_mask)
+{
+    if ((variant_mask & ~0xFEu) != 0) return fail(ctx, VDF_E_INVAL, "variant_mask takes bits 1 ... 7");
+    if (n && (!hashes || !zero || !durations)) return fail(ctx, VDF_E_INVAL, "null pointer");
+    if (n >= 0xFFFFFFFFull) return fail(ctx, VDF_E_INVAL, "more than 2^32-1 hashes");
+    return VDF_OK;
+}
+
+static void free_variant_groups(vdf_groups *out)
+{
+    for (uint32_t v = 0; v < vdf::kHashVariants; v++) vdf_groups_free(&out[v]);
+}
+
+int vdf_search_variants_device(vdf_ctx *ctx, const uint64_t *d_hashes, const uint64_t *d_zero, const uint32_t *d_durations,
+                               size_t n, uint32_t tol_int, uint32_t variant_mask, vdf_groups *out, void *stream)
+{
+    if (!ctx || !out) return VDF_E_INVAL;
+    std::memset(out, 0, vdf::kHashVariants * sizeof *out);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    VDF_SINGLE_DEVICE_ONLY(ctx);
+    if (int rc = search_variants_checks(ctx, d_hashes, d_zero, d_durations, n, variant_mask)) return rc;
+    if (n == 0) return VDF_OK;
+    const int rc = search_variants_locked(ctx, d_hashes, d_zero, d_durations, n, tol_int, variant_mask, out, stream ? (hipStream_t)stream : ctx->stream);
+    if (rc) free_variant_groups(out);
+    return rc;
+}
+
+int vdf_search_variants(vdf_ctx *ctx, const uint64_t *hashes, const uint64_t *zero, const uint32_t *durations, size_t n,
+                        uint32_t tol_int, uint32_t variant_mask, vdf_groups *out)
+{
+    if (!ctx || !out) return VDF_E_INVAL;
+    std::memset(out, 0, vdf::kHashVariants * sizeof *out);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_search_variants takes a single-device context");
+    if (int rc = search_variants_checks(ctx, hashes, zero, durations, n, variant_mask)) return rc;
+    if (n == 0) return VDF_OK;
+    if (!is_sorted_u32(durations, n)) return fail(ctx, VDF_E_INVAL, "durations are not ascending: pass the arrays in Search::sort order");
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = upload(ctx, ctx->up_hashes, hashes, n * VDF_HASH_WORDS * 8, ctx->stream);
+    if (rc == VDF_OK) rc = upload(ctx, ctx->up_zero, zero, n * VDF_HASH_WORDS * 8, ctx->stream);
+    if (rc == VDF_OK) rc = upload(ctx, ctx->up_dur, durations, n * 4, ctx->stream);
+    if (rc == VDF_OK)
+        rc = search_variants_locked(ctx, ctx->up_hashes.as<uint64_t>(), ctx->up_zero.as<uint64_t>(), ctx->up_dur.as<uint32_t>(), n, tol_int, variant_mask, out, ctx->stream);
+    if (rc) free_variant_groups(out);
+    return rc;
 }
 
 int vdf_cropdetect_letterbox_clips_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,

@@ -171,11 +171,38 @@ struct DctShared {
     __attribute__((aligned(16))) uint32_t cube[16 * 64];
 };
 
+// The zero plane's 32 ballot words and where the planes go: LDS of the PLANES instantiations only - a kernel that never reaches
+// this function allocates nothing for it, so DctShared and every plain instantiation stay what they were.
+// `out`: the kernels park their out_zero argument here once (zero_plane_begin) and dct_hash_block reads it back where it stores the plane, so
+// the pointer holds no scalar registers through a persistent loop - the tiled kernels spill scalars into vector lanes as it is, and two more
+// pushed two of their PLANES forms over the vector registers of three workgroups per CU.
+struct ZeroPlaneShared {
+    uint32_t words[32];
+    uint64_t *out;
+};
+__device__ __forceinline__ ZeroPlaneShared &zero_plane_shared()
+{
+    __shared__ ZeroPlaneShared zp;
+    return zp;
+}
+// at a kernel's start, in front of the barrier behind which it first calls dct_hash_block
+template <bool PLANES> __device__ __forceinline__ void zero_plane_begin(uint64_t *out_zero)
+{
+    if constexpr (PLANES) {
+        if (threadIdx.x == 32) zero_plane_shared().out = out_zero;
+    }
+}
+
 // 256 threads: 3-D DCT-II of the clip in sh.cube (f64), sign test, ballot pack.  Pass order y, x, t (the
 // reference's order, raw_dct_ops.rs:118-132).  Caller has filled sh.cube and sh.cosv and synchronised.
+// PLANES: also the clip's zero plane - bit i set iff coefficient i == 0.0 (either sign of zero) - to out_zero + 16 * clip: one more ballot
+// per kt, OR-assembled like the hash words; out_zero comes from zero_plane_begin.  A compile-time switch: the plain form has none of it.
+template <bool PLANES = false>
 __device__ __forceinline__ void dct_hash_block(DctShared &sh, const_f64_ptr cosv, size_t clip,
                                                uint64_t *__restrict__ out_hashes, uint32_t *__restrict__ out_dontcare)
 {
+    uint32_t *zw = nullptr;
+    if constexpr (PLANES) zw = zero_plane_shared().words;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     DctTw cm;  // wave-uniform constants (scalar loads): cos_table[256 ..] = t16, t8, t4, h in this order
 #pragma unroll
@@ -207,6 +234,9 @@ __device__ __forceinline__ void dct_hash_block(DctShared &sh, const_f64_ptr cosv
         dct16_pruned(v, ox, cm);
     } else if (tid >= 192 && tid < 224) {
         sh.words[tid - 192] = 0u;  // idle lanes clear the ballot words (previous clip's words were read two barriers ago)
+    }
+    if constexpr (PLANES) {
+        if (tid >= 224) zw[tid - 224] = 0u;  // (the same ordering: read behind the last barrier of the previous clip, OR-ed two barriers on)
     }
     __syncthreads();  // every row of b has been read: c may overwrite it
     if (tid < 160) {
@@ -242,6 +272,23 @@ __device__ __forceinline__ void dct_hash_block(DctShared &sh, const_f64_ptr cosv
             atomicOr(&sh.words[wi + 1], (hi << sh_l) | (sh_l ? lo >> (32u - sh_l) : 0u));
             if (sh_l && wi + 2 < 32) atomicOr(&sh.words[wi + 2], hi >> (32u - sh_l));
         }
+        if constexpr (PLANES) {
+            // a pass of its own behind the hash words': `piece` is dead by now, so the plane's piece takes its registers - the persistent
+            // kernels have none to spare (launch bounds of three workgroups per CU)
+            unsigned long long zpiece = 0;
+#pragma unroll
+            for (int kt = 0; kt < 10; kt++) {
+                const unsigned long long zeros = __builtin_amdgcn_ballot_w64(live && o[kt] == 0.0);  // +0.0 and -0.0
+                if (lane == (uint32_t)kt) zpiece = zeros;
+            }
+            if (lane < 10) {
+                const uint32_t off = 100u * lane + 64u * wave, wi = off >> 5, sh_l = off & 31u;
+                const uint32_t zlo = (uint32_t)zpiece, zhi = (uint32_t)(zpiece >> 32);
+                atomicOr(&zw[wi], zlo << sh_l);
+                atomicOr(&zw[wi + 1], (zhi << sh_l) | (sh_l ? zlo >> (32u - sh_l) : 0u));
+                if (sh_l && wi + 2 < 32) atomicOr(&zw[wi + 2], zhi >> (32u - sh_l));
+            }
+        }
         if (lane == 0) sh.dc[wave] = dc;
     }
     __syncthreads();
@@ -249,19 +296,28 @@ __device__ __forceinline__ void dct_hash_block(DctShared &sh, const_f64_ptr cosv
         const unsigned long long w = (unsigned long long)sh.words[2 * tid] | ((unsigned long long)sh.words[2 * tid + 1] << 32);
         out_hashes[clip * 16 + tid] = w;
     }
+    if constexpr (PLANES) {
+        if (tid >= 16 && tid < 32) {
+            const uint32_t k = tid - 16;
+            zero_plane_shared().out[clip * 16 + k] = (unsigned long long)zw[2 * k] | ((unsigned long long)zw[2 * k + 1] << 32);
+        }
+    }
     if (out_dontcare && tid == 0) out_dontcare[clip] = sh.dc[0] + sh.dc[1];
 }
 
 // 16 x 16 x 16 u8 cubes (row-major frames) -> hashes.  The cube is re-laid into sh.cube's dword layout.
+// (PLANES, here and in the kernels below: the zero plane as well - dct_hash_block; out_zero is read by no plain instantiation.)
+template <bool PLANES>
 __global__ __launch_bounds__(256) void dct_hash_kernel(const uint8_t *__restrict__ small, size_t clip_stride,
                                                        size_t frame_stride, const double *__restrict__ cos_table,
                                                        uint64_t *__restrict__ out_hashes,
-                                                       uint32_t *__restrict__ out_dontcare)
+                                                       uint32_t *__restrict__ out_dontcare, uint64_t *__restrict__ out_zero)
 {
     __shared__ DctShared sh;
     const size_t clip = blockIdx.x;
     const uint32_t tid = threadIdx.x;
     if (tid < 32) sh.words[tid] = 0u;
+    zero_plane_begin<PLANES>(out_zero);
     {
         // thread (t, g, xq): rows 4g..4g+3, columns 4xq..4xq+3 of frame t -> a 4x4 byte transpose in registers
         const uint32_t t = tid >> 4, g = (tid >> 2) & 3, xq = tid & 3;
@@ -278,7 +334,7 @@ __global__ __launch_bounds__(256) void dct_hash_kernel(const uint8_t *__restrict
         }
     }
     __syncthreads();
-    dct_hash_block(sh, (const_f64_ptr)(uintptr_t)cos_table, clip, out_hashes, out_dontcare);
+    dct_hash_block<PLANES>(sh, (const_f64_ptr)(uintptr_t)cos_table, clip, out_hashes, out_dontcare);
 }
 
 // ---- resize on the matrix cores -----------------------------------------------------------------
@@ -465,16 +521,17 @@ __device__ __forceinline__ void resize_row_blocks(const uint8_t *__restrict__ sr
 // DCT runs in the same kernel: HBM traffic = the frames once + 128 B of hash.
 // ONE_TILE (W, H <= 64): the wave's 16 pixel loads (4 frames x 4 row blocks, 16 KB) are all issued before the
 // first MFMA so a workgroup keeps its whole 64 KB clip in flight; tables stay in registers.
-template <bool ONE_TILE>
+template <bool ONE_TILE, bool PLANES>
 __global__ __launch_bounds__(256) void resize_dct_hash_fused_kernel(
     const uint8_t *__restrict__ frames, uint32_t W, uint32_t H, size_t frame_stride, size_t clip_stride,
     const uint8_t *buf_end, MfmaResizeTables T, const double *__restrict__ cos_table,
-    uint64_t *__restrict__ out_hashes, uint32_t *__restrict__ out_dontcare)
+    uint64_t *__restrict__ out_hashes, uint32_t *__restrict__ out_dontcare, uint64_t *__restrict__ out_zero)
 {
     __shared__ DctShared sh;
     const size_t clip = blockIdx.x;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, r16 = lane & 15;
     if (tid < 32) sh.words[tid] = 0u;
+    zero_plane_begin<PLANES>(out_zero);
     const uint8_t *clip_base = frames + clip * clip_stride;
     // only the last frames of the buffer can see a 16-byte load cross its end (wave-uniform test)
     const bool careful = clip_base + 15 * frame_stride + (size_t)W * H + 64 > buf_end;
@@ -525,7 +582,7 @@ __global__ __launch_bounds__(256) void resize_dct_hash_fused_kernel(
         }
     }
     __syncthreads();
-    dct_hash_block(sh, (const_f64_ptr)(uintptr_t)cos_table, clip, out_hashes, out_dontcare);
+    dct_hash_block<PLANES>(sh, (const_f64_ptr)(uintptr_t)cos_table, clip, out_hashes, out_dontcare);
 }
 
 // Persistent form of the ONE_TILE fused kernel (W, H <= 64, W % 16 == 0 so no load crosses the buffer end):
@@ -533,15 +590,16 @@ __global__ __launch_bounds__(256) void resize_dct_hash_fused_kernel(
 // resize has consumed the current pixels, so HBM streams underneath the DCT instead of after it.
 // FULL = W == H == 64: every lane's loads are in range, so the zero fill and the per-lane predicates (exec-mask
 // juggling, 58 register moves per wave and clip) disappear.
-template <bool FULL>
+template <bool FULL, bool PLANES>
 __global__ __launch_bounds__(256) void resize_dct_hash_persistent_kernel(
     const uint8_t *__restrict__ frames, uint32_t W, uint32_t H, size_t frame_stride, size_t clip_stride,
     MfmaResizeTables T, const double *__restrict__ cos_table, uint64_t *__restrict__ out_hashes,
-    uint32_t *__restrict__ out_dontcare, uint32_t n_clips)
+    uint32_t *__restrict__ out_dontcare, uint32_t n_clips, uint64_t *__restrict__ out_zero)
 {
     __shared__ DctShared sh;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, r16 = lane & 15;
     if (tid < 32) sh.words[tid] = 0u;
+    zero_plane_begin<PLANES>(out_zero);
     v4i bias_v;
 #pragma unroll
     for (int r = 0; r < 4; r++) bias_v[r] = T.bias_v[4 * g + r];
@@ -615,7 +673,7 @@ __global__ __launch_bounds__(256) void resize_dct_hash_persistent_kernel(
         if (tid < 16) out_hashes[(size_t)clip * 16 + tid] = sh.cube[tid * 64];
         __syncthreads();
 #else
-        dct_hash_block(sh, (const_f64_ptr)(uintptr_t)cos_table, clip, out_hashes, out_dontcare);
+        dct_hash_block<PLANES>(sh, (const_f64_ptr)(uintptr_t)cos_table, clip, out_hashes, out_dontcare);
 #endif
         clip = next;
     }
@@ -633,11 +691,11 @@ __global__ __launch_bounds__(256) void resize_dct_hash_persistent_kernel(
 // two-tile shapes, which fit anyway, it changed their schedule for the worse: 80 x 48 5.3 -> 4.1 TB/s, 32 x 128 5.7 -> 3.8)
 // Three or four K tiles (129 ... 256 columns): a unit is TWO of the four 16-row blocks of a row group (2 x NKT loads); the block results wait
 // in `b` for the row group's second unit, whose end is the vertical product.
-template <int NKT, int NRG, int WAVES>
+template <int NKT, int NRG, int WAVES, bool PLANES>
 __global__ __launch_bounds__(256, WAVES) void resize_dct_hash_tiled_kernel(
     const uint8_t *__restrict__ frames, uint32_t W, uint32_t H, size_t frame_stride, size_t clip_stride,
     MfmaResizeTables T, const double *__restrict__ cos_table, uint64_t *__restrict__ out_hashes,
-    uint32_t *__restrict__ out_dontcare, uint32_t n_clips)
+    uint32_t *__restrict__ out_dontcare, uint32_t n_clips, uint64_t *__restrict__ out_zero)
 {
     constexpr int MU = NKT > 2 ? 2 : 4;                 // 16-row blocks per unit
     constexpr int RGU = NKT == 1 && NRG >= 2 ? 2 : 1;   // row groups per unit: two where a row group is only four loads
@@ -649,6 +707,7 @@ __global__ __launch_bounds__(256, WAVES) void resize_dct_hash_tiled_kernel(
     __shared__ DctShared sh;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, r16 = lane & 15;
     if (tid < 32) sh.words[tid] = 0u;
+    zero_plane_begin<PLANES>(out_zero);
     v4i bias_v;
 #pragma unroll
     for (int r = 0; r < 4; r++) bias_v[r] = T.bias_v[4 * g + r];
@@ -734,7 +793,7 @@ __global__ __launch_bounds__(256, WAVES) void resize_dct_hash_tiled_kernel(
         }
         __builtin_amdgcn_s_setprio(0);
         __syncthreads();
-        dct_hash_block(sh, (const_f64_ptr)(uintptr_t)cos_table, clip, out_hashes, out_dontcare);
+        dct_hash_block<PLANES>(sh, (const_f64_ptr)(uintptr_t)cos_table, clip, out_hashes, out_dontcare);
         clip = next;
     }
 }
@@ -1915,11 +1974,15 @@ hipError_t launch_resize_generic(const uint8_t *frames, size_t n_clips, uint32_t
 }
 
 hipError_t launch_dct_hash(const uint8_t *small, size_t small_clip_stride, size_t small_frame_stride, size_t n_clips,
-                           const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream)
+                           const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream, uint64_t *out_zero)
 {
     if (n_clips == 0) return hipSuccess;
-    hipLaunchKernelGGL(dct_hash_kernel, dim3((uint32_t)n_clips), dim3(256), 0, stream, small, small_clip_stride,
-                       small_frame_stride, cos_table, out_hashes, out_dontcare);
+    if (out_zero)
+        hipLaunchKernelGGL(dct_hash_kernel<true>, dim3((uint32_t)n_clips), dim3(256), 0, stream, small, small_clip_stride,
+                           small_frame_stride, cos_table, out_hashes, out_dontcare, out_zero);
+    else
+        hipLaunchKernelGGL(dct_hash_kernel<false>, dim3((uint32_t)n_clips), dim3(256), 0, stream, small, small_clip_stride,
+                           small_frame_stride, cos_table, out_hashes, out_dontcare, out_zero);
     return hipGetLastError();
 }
 
@@ -1991,7 +2054,7 @@ __global__ __launch_bounds__(256) void resize_mfma_cropped_kernel(const uint8_t 
 // left it (`boxes`, device memory) and finds the tables of that box size in the per-(W, H) set of ALL box sizes (`tables`: horizontal
 // table of box width bw at [bw], vertical of box height bh at [pitch + 1 + bh]; api.cpp: box_table_set), so nothing of the detect's result visits the host
 // between the two launches (the reference crops and hashes in one pass per clip: video_hash_builder.rs:188-204).
-template <bool DEVICE_BOX>
+template <bool DEVICE_BOX, bool PLANES>
 __global__ __launch_bounds__(256) void resize_dct_hash_cropped_small_kernel(const uint8_t *__restrict__ frames, uint32_t pitch,
                                                                             size_t frame_stride, size_t clip_stride,
                                                                             const uint8_t *buf_end,
@@ -2000,11 +2063,13 @@ __global__ __launch_bounds__(256) void resize_dct_hash_cropped_small_kernel(cons
                                                                             const double *__restrict__ cos_table,
                                                                             uint64_t *__restrict__ out_hashes,
                                                                             uint32_t *__restrict__ out_dontcare,
-                                                                            const uint32_t *__restrict__ boxes, uint32_t frame_rows)
+                                                                            const uint32_t *__restrict__ boxes, uint32_t frame_rows,
+                                                                            uint64_t *__restrict__ out_zero)
 {
     __shared__ DctShared sh;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, r16 = lane & 15;
     if (tid < 32) sh.words[tid] = 0u;
+    zero_plane_begin<PLANES>(out_zero);
     CropClipDesc d;
     if (DEVICE_BOX) {
         const uint4 b = reinterpret_cast<const uint4 *>(boxes)[blockIdx.x];  // left, right, top, bottom (the detect never leaves an empty box)
@@ -2064,7 +2129,7 @@ __global__ __launch_bounds__(256) void resize_dct_hash_cropped_small_kernel(cons
             sh.cube[(4 * wave + q) * 64 + g * 16 + r16] = finalize4(vh, vl, T.prec_v);
         }
         __syncthreads();
-        dct_hash_block(sh, (const_f64_ptr)(uintptr_t)cos_table, d.src_clip, out_hashes, out_dontcare);
+        dct_hash_block<PLANES>(sh, (const_f64_ptr)(uintptr_t)cos_table, d.src_clip, out_hashes, out_dontcare);
         return;
     }
 #pragma unroll 1
@@ -2079,17 +2144,21 @@ __global__ __launch_bounds__(256) void resize_dct_hash_cropped_small_kernel(cons
         sh.cube[f * 64 + g * 16 + r16] = finalize4(vh, vl, T.prec_v);  // centred bytes of out[oy = 4 g + r][x = r16], r = 0..3
     }
     __syncthreads();
-    dct_hash_block(sh, (const_f64_ptr)(uintptr_t)cos_table, d.src_clip, out_hashes, out_dontcare);
+    dct_hash_block<PLANES>(sh, (const_f64_ptr)(uintptr_t)cos_table, d.src_clip, out_hashes, out_dontcare);
 }
 
 hipError_t launch_resize_dct_cropped_small(const uint8_t *frames, size_t n_clips, uint32_t pitch, size_t frame_stride,
                                            size_t clip_stride, const uint8_t *buf_end, const CropClipDesc *desc,
                                            const CropTableEntry *tables, const double *cos_table, uint64_t *out_hashes,
-                                           uint32_t *out_dontcare, hipStream_t stream)
+                                           uint32_t *out_dontcare, hipStream_t stream, uint64_t *out_zero)
 {
     if (n_clips == 0) return hipSuccess;
-    hipLaunchKernelGGL(resize_dct_hash_cropped_small_kernel<false>, dim3((uint32_t)n_clips), dim3(256), 0, stream, frames, pitch, frame_stride,
-                       clip_stride, buf_end, desc, tables, cos_table, out_hashes, out_dontcare, (const uint32_t *)nullptr, 0u);
+    if (out_zero)
+        hipLaunchKernelGGL((resize_dct_hash_cropped_small_kernel<false, true>), dim3((uint32_t)n_clips), dim3(256), 0, stream, frames, pitch, frame_stride,
+                           clip_stride, buf_end, desc, tables, cos_table, out_hashes, out_dontcare, (const uint32_t *)nullptr, 0u, out_zero);
+    else
+        hipLaunchKernelGGL((resize_dct_hash_cropped_small_kernel<false, false>), dim3((uint32_t)n_clips), dim3(256), 0, stream, frames, pitch, frame_stride,
+                           clip_stride, buf_end, desc, tables, cos_table, out_hashes, out_dontcare, (const uint32_t *)nullptr, 0u, out_zero);
     return hipGetLastError();
 }
 
@@ -2099,8 +2168,8 @@ hipError_t launch_resize_dct_cropped_small_boxes(const uint8_t *frames, size_t n
                                                  uint32_t *out_dontcare, hipStream_t stream)
 {
     if (n_clips == 0) return hipSuccess;
-    hipLaunchKernelGGL(resize_dct_hash_cropped_small_kernel<true>, dim3((uint32_t)n_clips), dim3(256), 0, stream, frames, w, frame_stride,
-                       clip_stride, buf_end, (const CropClipDesc *)nullptr, tables, cos_table, out_hashes, out_dontcare, boxes, h);
+    hipLaunchKernelGGL((resize_dct_hash_cropped_small_kernel<true, false>), dim3((uint32_t)n_clips), dim3(256), 0, stream, frames, w, frame_stride,
+                       clip_stride, buf_end, (const CropClipDesc *)nullptr, tables, cos_table, out_hashes, out_dontcare, boxes, h, (uint64_t *)nullptr);
     return hipGetLastError();
 }
 
@@ -2497,16 +2566,18 @@ __device__ __forceinline__ MfmaResizeTables mixed_tables(const CropTableEntry &t
 
 // Small frames (at most 256 columns, 128 rows): resize_dct_hash_cropped_small_kernel's body - one workgroup per clip, a wave per four frames,
 // the DCT in the same workgroup; the hash goes to the clip's place in the CALL (d.out_index), whichever launch of the call this is.
+template <bool PLANES>
 __global__ __launch_bounds__(256) void resize_dct_hash_mixed_small_kernel(const uint8_t *__restrict__ buf, const uint8_t *buf_end,
                                                                           const MixedClipDesc *__restrict__ desc,
                                                                           const CropTableEntry *__restrict__ tables,
                                                                           const double *__restrict__ cos_table,
                                                                           uint64_t *__restrict__ out_hashes,
-                                                                          uint32_t *__restrict__ out_dontcare)
+                                                                          uint32_t *__restrict__ out_dontcare, uint64_t *__restrict__ out_zero)
 {
     __shared__ DctShared sh;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, r16 = lane & 15;
     if (tid < 32) sh.words[tid] = 0u;
+    zero_plane_begin<PLANES>(out_zero);
     const MixedClipDesc d = desc[blockIdx.x];
     const MfmaResizeTables T = mixed_tables(tables[d.h_table], tables[d.v_table]);
     const size_t pitch = d.pitch, frame_stride = (size_t)d.frame_stride;
@@ -2547,7 +2618,7 @@ __global__ __launch_bounds__(256) void resize_dct_hash_mixed_small_kernel(const 
             sh.cube[(4 * wave + q) * 64 + g * 16 + r16] = finalize4(vh, vl, T.prec_v);
         }
         __syncthreads();
-        dct_hash_block(sh, (const_f64_ptr)(uintptr_t)cos_table, d.out_index, out_hashes, out_dontcare);
+        dct_hash_block<PLANES>(sh, (const_f64_ptr)(uintptr_t)cos_table, d.out_index, out_hashes, out_dontcare);
         return;
     }
 #pragma unroll 1
@@ -2561,7 +2632,7 @@ __global__ __launch_bounds__(256) void resize_dct_hash_mixed_small_kernel(const 
         sh.cube[f * 64 + g * 16 + r16] = finalize4(vh, vl, T.prec_v);
     }
     __syncthreads();
-    dct_hash_block(sh, (const_f64_ptr)(uintptr_t)cos_table, d.out_index, out_hashes, out_dontcare);
+    dct_hash_block<PLANES>(sh, (const_f64_ptr)(uintptr_t)cos_table, d.out_index, out_hashes, out_dontcare);
 }
 
 // Everything else: resize_mfma_cropped_kernel<WIDE>'s body - one workgroup per frame; the 16 x 16 frame goes to slot blockIdx.x of `small`
@@ -2610,13 +2681,15 @@ __global__ __launch_bounds__(256) void resize_mfma_mixed_kernel(const uint8_t *_
 
 // dct_hash_kernel for the 16 x 16 frames of a mixed launch: cube blockIdx.x of `small` (tightly packed) -> the hash of clip
 // desc[blockIdx.x].out_index of the call.
+template <bool PLANES>
 __global__ __launch_bounds__(256) void dct_hash_indexed_kernel(const uint8_t *__restrict__ small, const MixedClipDesc *__restrict__ desc,
                                                                const double *__restrict__ cos_table, uint64_t *__restrict__ out_hashes,
-                                                               uint32_t *__restrict__ out_dontcare)
+                                                               uint32_t *__restrict__ out_dontcare, uint64_t *__restrict__ out_zero)
 {
     __shared__ DctShared sh;
     const uint32_t tid = threadIdx.x;
     if (tid < 32) sh.words[tid] = 0u;
+    zero_plane_begin<PLANES>(out_zero);
     {
         const uint32_t t = tid >> 4, g = (tid >> 2) & 3, xq = tid & 3;
         const uint8_t *src = small + (size_t)blockIdx.x * 4096 + (size_t)t * 256 + (4 * g) * 16 + 4 * xq;
@@ -2632,16 +2705,20 @@ __global__ __launch_bounds__(256) void dct_hash_indexed_kernel(const uint8_t *__
         }
     }
     __syncthreads();
-    dct_hash_block(sh, (const_f64_ptr)(uintptr_t)cos_table, desc[blockIdx.x].out_index, out_hashes, out_dontcare);
+    dct_hash_block<PLANES>(sh, (const_f64_ptr)(uintptr_t)cos_table, desc[blockIdx.x].out_index, out_hashes, out_dontcare);
 }
 
 hipError_t launch_mixed_small(const uint8_t *buf, const uint8_t *buf_end, const MixedClipDesc *desc, size_t n_clips, const CropTableEntry *tables,
-                              const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream)
+                              const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream, uint64_t *out_zero)
 {
     if (n_clips == 0) return hipSuccess;
     if (n_clips > kMaxClipsPerLaunch) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(resize_dct_hash_mixed_small_kernel, dim3((uint32_t)n_clips), dim3(256), 0, stream, buf, buf_end, desc, tables, cos_table, out_hashes,
-                       out_dontcare);
+    if (out_zero)
+        hipLaunchKernelGGL(resize_dct_hash_mixed_small_kernel<true>, dim3((uint32_t)n_clips), dim3(256), 0, stream, buf, buf_end, desc, tables, cos_table,
+                           out_hashes, out_dontcare, out_zero);
+    else
+        hipLaunchKernelGGL(resize_dct_hash_mixed_small_kernel<false>, dim3((uint32_t)n_clips), dim3(256), 0, stream, buf, buf_end, desc, tables, cos_table,
+                           out_hashes, out_dontcare, out_zero);
     return hipGetLastError();
 }
 
@@ -2656,11 +2733,12 @@ hipError_t launch_mixed_frames(const uint8_t *buf, const uint8_t *buf_end, const
 }
 
 hipError_t launch_dct_hash_indexed(const uint8_t *small, const MixedClipDesc *desc, size_t n_clips, const double *cos_table, uint64_t *out_hashes,
-                                   uint32_t *out_dontcare, hipStream_t stream)
+                                   uint32_t *out_dontcare, hipStream_t stream, uint64_t *out_zero)
 {
     if (n_clips == 0) return hipSuccess;
     if (n_clips > kMaxClipsPerLaunch) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(dct_hash_indexed_kernel, dim3((uint32_t)n_clips), dim3(256), 0, stream, small, desc, cos_table, out_hashes, out_dontcare);
+    if (out_zero) hipLaunchKernelGGL(dct_hash_indexed_kernel<true>, dim3((uint32_t)n_clips), dim3(256), 0, stream, small, desc, cos_table, out_hashes, out_dontcare, out_zero);
+    else hipLaunchKernelGGL(dct_hash_indexed_kernel<false>, dim3((uint32_t)n_clips), dim3(256), 0, stream, small, desc, cos_table, out_hashes, out_dontcare, out_zero);
     return hipGetLastError();
 }
 
@@ -2680,10 +2758,11 @@ static MfmaResizeTables make_tables(const MfmaResizeArgs &a)
     return T;
 }
 
-hipError_t launch_resize_dct_fused(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h, size_t frame_stride,
-                                   size_t clip_stride, const uint8_t *buf_end, const MfmaResizeArgs &a, const HashPlan &plan,
-                                   const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare,
-                                   hipStream_t stream)
+template <bool PLANES>
+static hipError_t launch_resize_dct_fused_as(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h, size_t frame_stride,
+                                             size_t clip_stride, const uint8_t *buf_end, const MfmaResizeArgs &a, const HashPlan &plan,
+                                             const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare,
+                                             hipStream_t stream, uint64_t *out_zero)
 {
     if (n_clips == 0) return hipSuccess;
     const bool per_clip = plan.route == HashRoute::kPerClipFused;
@@ -2691,33 +2770,33 @@ hipError_t launch_resize_dct_fused(const uint8_t *frames, size_t n_clips, uint32
     if (!per_clip && (n_clips > 0xFFFFFFFFull || a.n_kt > 4 || a.n_rg > 4 || !(w % 16 == 0 || (plan.last_clip_apart && n_clips >= 2 && clip_stride >= 16))))
         return hipErrorInvalidValue;
     // the one-workgroup-per-clip kernel and its careful loader: every clip of its route, or the last clip of a persistent launch
-    const auto per_clip_launch = [&](const uint8_t *f, size_t n, uint64_t *oh, uint32_t *od) {
+    const auto per_clip_launch = [&](const uint8_t *f, size_t n, uint64_t *oh, uint32_t *od, uint64_t *oz) {
         if (a.n_kt == 1 && a.n_rg == 1)
-            hipLaunchKernelGGL(resize_dct_hash_fused_kernel<true>, dim3((uint32_t)n), dim3(256), 0, stream, f, w, h, frame_stride, clip_stride, buf_end,
-                               make_tables(a), cos_table, oh, od);
+            hipLaunchKernelGGL((resize_dct_hash_fused_kernel<true, PLANES>), dim3((uint32_t)n), dim3(256), 0, stream, f, w, h, frame_stride, clip_stride, buf_end,
+                               make_tables(a), cos_table, oh, od, oz);
         else
-            hipLaunchKernelGGL(resize_dct_hash_fused_kernel<false>, dim3((uint32_t)n), dim3(256), 0, stream, f, w, h, frame_stride, clip_stride, buf_end,
-                               make_tables(a), cos_table, oh, od);
+            hipLaunchKernelGGL((resize_dct_hash_fused_kernel<false, PLANES>), dim3((uint32_t)n), dim3(256), 0, stream, f, w, h, frame_stride, clip_stride, buf_end,
+                               make_tables(a), cos_table, oh, od, oz);
     };
     const size_t n_all = n_clips;
     if (plan.last_clip_apart) n_clips -= 1;
     const int cus = cu_count();
 #define VDF_PERSISTENT(KERNEL, PER_CU)                                                                                                            \
     hipLaunchKernelGGL(KERNEL, dim3((uint32_t)std::min<size_t>(n_clips, (size_t)cus * (size_t)(PER_CU))), dim3(256), 0, stream, frames, w, h, \
-                       frame_stride, clip_stride, make_tables(a), cos_table, out_hashes, out_dontcare, (uint32_t)n_clips)
+                       frame_stride, clip_stride, make_tables(a), cos_table, out_hashes, out_dontcare, (uint32_t)n_clips, out_zero)
 #define VDF_TILED(NKT, NRG)                                                                                                                   \
     case NKT * 8 + NRG: {                                                                                                                     \
         int per_cu = 3;                                                                                                                       \
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resize_dct_hash_tiled_kernel<NKT, NRG, tiled_waves(NKT, NRG)>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 3; \
-        VDF_PERSISTENT((resize_dct_hash_tiled_kernel<NKT, NRG, tiled_waves(NKT, NRG)>), per_cu);                                              \
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, resize_dct_hash_tiled_kernel<NKT, NRG, tiled_waves(NKT, NRG), PLANES>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 3; \
+        VDF_PERSISTENT((resize_dct_hash_tiled_kernel<NKT, NRG, tiled_waves(NKT, NRG), PLANES>), per_cu);                                      \
         break;                                                                                                                                \
     }
     if (per_clip) {
-        per_clip_launch(frames, n_clips, out_hashes, out_dontcare);
+        per_clip_launch(frames, n_clips, out_hashes, out_dontcare, out_zero);
     } else if (plan.route == HashRoute::kPersistentOneTile) {
         if (a.n_kt != 1 || a.n_rg != 1 || (plan.full_tile && (w != 64 || h != 64))) return hipErrorInvalidValue;
-        if (plan.full_tile) VDF_PERSISTENT(resize_dct_hash_persistent_kernel<true>, a.persistent_wgs_per_cu);
-        else VDF_PERSISTENT(resize_dct_hash_persistent_kernel<false>, a.persistent_wgs_per_cu);
+        if (plan.full_tile) VDF_PERSISTENT((resize_dct_hash_persistent_kernel<true, PLANES>), a.persistent_wgs_per_cu);
+        else VDF_PERSISTENT((resize_dct_hash_persistent_kernel<false, PLANES>), a.persistent_wgs_per_cu);
     } else if (plan.route == HashRoute::kTiled && a.n_kt == plan.n_kt && (plan.tiled_nrg == 4 ? a.n_rg > 2 : a.n_rg == plan.tiled_nrg)) {
         switch (plan.n_kt * 8 + plan.tiled_nrg) {
             VDF_TILED(4, 4) VDF_TILED(3, 4) VDF_TILED(2, 4) VDF_TILED(1, 4) VDF_TILED(4, 2) VDF_TILED(4, 1) VDF_TILED(3, 2) VDF_TILED(3, 1)
@@ -2730,8 +2809,19 @@ hipError_t launch_resize_dct_fused(const uint8_t *frames, size_t n_clips, uint32
 #undef VDF_TILED
 #undef VDF_PERSISTENT
     if (plan.last_clip_apart)
-        per_clip_launch(frames + (n_all - 1) * clip_stride, 1, out_hashes + (n_all - 1) * 16, out_dontcare ? out_dontcare + (n_all - 1) : nullptr);
+        per_clip_launch(frames + (n_all - 1) * clip_stride, 1, out_hashes + (n_all - 1) * 16, out_dontcare ? out_dontcare + (n_all - 1) : nullptr,
+                        out_zero ? out_zero + (n_all - 1) * 16 : nullptr);
     return hipGetLastError();
+}
+
+hipError_t launch_resize_dct_fused(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h, size_t frame_stride,
+                                   size_t clip_stride, const uint8_t *buf_end, const MfmaResizeArgs &a, const HashPlan &plan,
+                                   const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare,
+                                   hipStream_t stream, uint64_t *out_zero)
+{
+    if (out_zero)
+        return launch_resize_dct_fused_as<true>(frames, n_clips, w, h, frame_stride, clip_stride, buf_end, a, plan, cos_table, out_hashes, out_dontcare, stream, out_zero);
+    return launch_resize_dct_fused_as<false>(frames, n_clips, w, h, frame_stride, clip_stride, buf_end, a, plan, cos_table, out_hashes, out_dontcare, stream, nullptr);
 }
 
 hipError_t launch_resize_mfma_frames(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h,
@@ -2742,6 +2832,35 @@ hipError_t launch_resize_mfma_frames(const uint8_t *frames, size_t n_clips, uint
     // a.av is in kMfmaLayoutVerticalWide order
     hipLaunchKernelGGL(resize_mfma_frame_wide_kernel, dim3((uint32_t)(n_clips * 16)), dim3(256), 0, stream, frames, w,
                        h, frame_stride, clip_stride, buf_end, make_tables(a), small);
+    return hipGetLastError();
+}
+
+// ---- hashes of the flipped clips ---------------------------------------------------------------------------------------
+// out[j][c] = (H[c] ^ M_v(j)) & ~Z[c]: one thread per 64-bit word, every variant of the word from one read.  variants: 3 bits per entry.
+__constant__ VariantMasks c_variant_masks = make_variant_masks();
+
+__global__ __launch_bounds__(256) void hash_variants_kernel(const uint64_t *__restrict__ hashes, const uint64_t *__restrict__ zero, size_t n_words,
+                                                            uint32_t variants, uint32_t n_variants, uint64_t *__restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_words) return;
+    const uint64_t h = hashes[i], keep = ~zero[i];
+    const uint32_t k = (uint32_t)(i & 15);
+    for (uint32_t j = 0; j < n_variants; j++) out[(size_t)j * n_words + i] = (h ^ c_variant_masks.m[(variants >> (3 * j)) & 7u][k]) & keep;
+}
+
+hipError_t launch_hash_variants(const uint64_t *hashes, const uint64_t *zero, size_t n, const uint32_t *variants, uint32_t n_variants, uint64_t *out,
+                                hipStream_t stream)
+{
+    if (n == 0 || n_variants == 0) return hipSuccess;
+    if (n > 0xFFFFFFFFull || n_variants > 8) return hipErrorInvalidValue;
+    uint32_t packed = 0;
+    for (uint32_t j = 0; j < n_variants; j++) {
+        if (variants[j] > 7) return hipErrorInvalidValue;
+        packed |= variants[j] << (3 * j);
+    }
+    const size_t n_words = n * 16;
+    hipLaunchKernelGGL(hash_variants_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, stream, hashes, zero, n_words, packed, n_variants, out);
     return hipGetLastError();
 }
 

@@ -88,8 +88,9 @@ static CopyPool *pool_of(vdf_ctx *ctx)
 constexpr size_t kBatchBytes = 256ull << 20;  // device batch buffer (x 2)
 
 int hash_host_locked(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h, size_t frame_stride,
-                     size_t clip_stride, int letterbox, uint64_t *out_hashes, uint32_t *out_crops, uint32_t *out_dontcare)
+                     size_t clip_stride, int letterbox, uint64_t *out_hashes, uint32_t *out_crops, uint32_t *out_dontcare, uint64_t *out_zero)
 {
+    if (letterbox && out_zero) return fail(ctx, VDF_E_INVAL, "no zero plane from the letterbox call");
     VDF_HIP(ctx, hipSetDevice(ctx->device));
     const size_t fbytes = (size_t)w * h, cbytes = fbytes * VDF_DCT_SIZE;
     const size_t batch = std::max<size_t>(1, std::min<size_t>(n_clips, kBatchBytes / cbytes));
@@ -102,13 +103,16 @@ int hash_host_locked(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32
     const bool direct_env = ctx->host_direct;
     const bool packed = frame_stride == fbytes && clip_stride == cbytes;
     DevBuf *d_frames[2] = {&ctx->frames, &ctx->frames2}, *d_hash[2] = {&ctx->out_hashes, &ctx->out_hashes2},
-           *d_dc[2] = {&ctx->out_dc, &ctx->out_dc2};
+           *d_dc[2] = {&ctx->out_dc, &ctx->out_dc2}, *d_zero[2] = {&ctx->out_zero, &ctx->out_zero2};
     const size_t n_batches = (n_clips + batch - 1) / batch;
+    // pinned results of a batch: hashes | dontcare | (planes call) zero planes, from an 8-byte boundary
+    const size_t zero_at = (batch * (VDF_HASH_WORDS * 8 + 4) + 7) & ~size_t(7);
     for (int i = 0; i < (n_batches > 1 ? 2 : 1); i++) {
         VDF_HIP(ctx, d_frames[i]->reserve(batch * cbytes));
         VDF_HIP(ctx, d_hash[i]->reserve(batch * VDF_HASH_WORDS * 8));
         VDF_HIP(ctx, d_dc[i]->reserve(batch * 4));
-        if (!ctx->pin_out[i].reserve(batch * (VDF_HASH_WORDS * 8 + 4))) return fail(ctx, VDF_E_OOM, "pinned result buffer");
+        if (out_zero) VDF_HIP(ctx, d_zero[i]->reserve(batch * VDF_HASH_WORDS * 8));
+        if (!ctx->pin_out[i].reserve(out_zero ? zero_at + batch * VDF_HASH_WORDS * 8 : batch * (VDF_HASH_WORDS * 8 + 4))) return fail(ctx, VDF_E_OOM, "pinned result buffer");
     }
     for (int i = 0; i < 2; i++)  // full-size chunks from the first call on: pinning memory is slow, do it once
         if (!ctx->pin[i].reserve(std::max(kChunkBytes, chunk * cbytes))) return fail(ctx, VDF_E_OOM, "pinned staging buffer");
@@ -124,6 +128,7 @@ int hash_host_locked(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32
         const uint8_t *src = ctx->pin_out[b & 1].as<uint8_t>();
         std::memcpy(out_hashes + c0 * VDF_HASH_WORDS, src, nb * VDF_HASH_WORDS * 8);
         if (out_dontcare) std::memcpy(out_dontcare + c0, src + batch * VDF_HASH_WORDS * 8, nb * 4);
+        if (out_zero) std::memcpy(out_zero + c0 * VDF_HASH_WORDS, src + zero_at, nb * VDF_HASH_WORDS * 8);
     };
     size_t chunk_counter = 0;
     for (size_t b = 0; b < n_batches; b++) {
@@ -186,11 +191,12 @@ int hash_host_locked(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32
                                               d_hash[slot]->as<uint64_t>(), dc, out_crops ? out_crops + 4 * c0 : nullptr, s);
         else
             rc = hash_device_locked(ctx, d_frames[slot]->as<uint8_t>(), nb, VDF_DCT_SIZE, w, h, fbytes, cbytes,
-                                    d_hash[slot]->as<uint64_t>(), dc, s);
+                                    d_hash[slot]->as<uint64_t>(), dc, s, out_zero ? d_zero[slot]->as<uint64_t>() : nullptr);
         if (rc) return rc;
         uint8_t *po = ctx->pin_out[slot].as<uint8_t>();
         VDF_HIP(ctx, hipMemcpyAsync(po, d_hash[slot]->p, nb * VDF_HASH_WORDS * 8, hipMemcpyDeviceToHost, s));
         if (dc) VDF_HIP(ctx, hipMemcpyAsync(po + batch * VDF_HASH_WORDS * 8, dc, nb * 4, hipMemcpyDeviceToHost, s));
+        if (out_zero) VDF_HIP(ctx, hipMemcpyAsync(po + zero_at, d_zero[slot]->p, nb * VDF_HASH_WORDS * 8, hipMemcpyDeviceToHost, s));
         VDF_HIP(ctx, hipEventRecord(ctx->ev_done[slot], s));
         if ((rc = end_turn())) return rc;  // (behind the kernels' launches: they start the moment the frames are in)
         // the next batch's DMA into the other device buffer must not overtake the kernels that still read it
@@ -214,8 +220,9 @@ int hash_host_locked(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32
 constexpr size_t kStagedTailSlack = 128, kStagedClipAlign = 64, kDirectClipBytes = 1u << 20;
 
 int hash_clips_host_locked(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
-                           uint64_t *out_hashes, uint32_t *out_dontcare, int letterbox, uint32_t *out_crops)
+                           uint64_t *out_hashes, uint32_t *out_dontcare, int letterbox, uint32_t *out_crops, uint64_t *out_zero)
 {
+    if (letterbox && out_zero) return fail(ctx, VDF_E_INVAL, "no zero plane from the letterbox call");
     if (n_clips && !clips) return fail(ctx, VDF_E_INVAL, "null pointer");
     const vdf::MixedCheck chk = vdf::check_mixed(reinterpret_cast<const vdf::MixedClip *>(clips), n_clips, frames_per_clip, buf_bytes);
     if (chk.error != vdf::MixedError::kNone) return mixed_check_failed(ctx, chk);
@@ -239,7 +246,9 @@ int hash_clips_host_locked(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, c
         } while (c < n_clips && b.bytes + staged_bytes(clips[c]) + kStagedTailSlack <= capacity);
         batches.push_back(b);
     }
-    DevBuf *d_frames[2] = {&ctx->frames, &ctx->frames2}, *d_hash[2] = {&ctx->out_hashes, &ctx->out_hashes2}, *d_dc[2] = {&ctx->out_dc, &ctx->out_dc2};
+    DevBuf *d_frames[2] = {&ctx->frames, &ctx->frames2}, *d_hash[2] = {&ctx->out_hashes, &ctx->out_hashes2}, *d_dc[2] = {&ctx->out_dc, &ctx->out_dc2},
+           *d_zero[2] = {&ctx->out_zero, &ctx->out_zero2};
+    const auto zero_at = [](size_t n) { return (n * (VDF_HASH_WORDS * 8 + 4) + 7) & ~size_t(7); };  // pinned results: hashes | dontcare | (planes call) zero planes
     CopyPool *pool = pool_of(ctx);
     hipStream_t s = ctx->stream;
     std::vector<vdf_clip> staged[2];
@@ -280,6 +289,7 @@ int hash_clips_host_locked(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, c
         const uint8_t *src = ctx->pin_out[b & 1].as<uint8_t>();
         std::memcpy(out_hashes + B.c0 * VDF_HASH_WORDS, src, B.n * VDF_HASH_WORDS * 8);
         if (out_dontcare) std::memcpy(out_dontcare + B.c0, src + B.n * VDF_HASH_WORDS * 8, B.n * 4);
+        if (out_zero) std::memcpy(out_zero + B.c0 * VDF_HASH_WORDS, src + zero_at(B.n), B.n * VDF_HASH_WORDS * 8);
     };
     int rc = fill(0);
     if (rc) return rc;
@@ -290,7 +300,8 @@ int hash_clips_host_locked(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, c
         VDF_HIP(ctx, d_frames[slot]->reserve(total));
         VDF_HIP(ctx, d_hash[slot]->reserve(B.n * VDF_HASH_WORDS * 8));
         VDF_HIP(ctx, d_dc[slot]->reserve(B.n * 4));
-        if (!ctx->pin_out[slot].reserve(B.n * (VDF_HASH_WORDS * 8 + 4))) return fail(ctx, VDF_E_OOM, "pinned result buffer");
+        if (out_zero) VDF_HIP(ctx, d_zero[slot]->reserve(B.n * VDF_HASH_WORDS * 8));
+        if (!ctx->pin_out[slot].reserve(out_zero ? zero_at(B.n) + B.n * VDF_HASH_WORDS * 8 : B.n * (VDF_HASH_WORDS * 8 + 4))) return fail(ctx, VDF_E_OOM, "pinned result buffer");
         uint8_t *dev = d_frames[slot]->as<uint8_t>();
         // a bulk transfer holds the device's link mutex until its frames are over (see hash_host_locked)
         std::unique_lock<std::mutex> turn(link_mutex(ctx->device), std::defer_lock);
@@ -318,11 +329,13 @@ int hash_clips_host_locked(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, c
         if (letterbox)
             rc = letterbox_clips_locked(ctx, dev, total, staged[slot].data(), B.n, VDF_DCT_SIZE, d_hash[slot]->as<uint64_t>(), dc, out_crops ? out_crops + 4 * B.c0 : nullptr, s);
         else
-            rc = hash_clips_locked(ctx, dev, total, staged[slot].data(), B.n, VDF_DCT_SIZE, d_hash[slot]->as<uint64_t>(), dc, s);
+            rc = hash_clips_locked(ctx, dev, total, staged[slot].data(), B.n, VDF_DCT_SIZE, d_hash[slot]->as<uint64_t>(), dc, s,
+                                   out_zero ? d_zero[slot]->as<uint64_t>() : nullptr);
         if (rc) return rc;
         uint8_t *po = ctx->pin_out[slot].as<uint8_t>();
         VDF_HIP(ctx, hipMemcpyAsync(po, d_hash[slot]->p, B.n * VDF_HASH_WORDS * 8, hipMemcpyDeviceToHost, s));
         if (dc) VDF_HIP(ctx, hipMemcpyAsync(po + B.n * VDF_HASH_WORDS * 8, dc, B.n * 4, hipMemcpyDeviceToHost, s));
+        if (out_zero) VDF_HIP(ctx, hipMemcpyAsync(po + zero_at(B.n), d_zero[slot]->p, B.n * VDF_HASH_WORDS * 8, hipMemcpyDeviceToHost, s));
         VDF_HIP(ctx, hipEventRecord(ctx->ev_done[slot], s));
     }
     // what has not been copied out yet: the last two batches (the loop fetches batch b - 1 only when it stages batch b + 1)

@@ -76,6 +76,21 @@ bool build_axis_table(uint32_t in_size, uint32_t out_size, HostAxisTable &t)
     return true;
 }
 
+bool axis_table_mirror_symmetric(uint32_t in_size)
+{
+    if (in_size == 16) return true;  // the identity
+    HostAxisTable h;
+    if (!build_axis_table(in_size, 16, h)) return false;
+    const auto coef = [&](uint32_t o, int64_t x) -> int16_t {
+        const int64_t k = x - h.start[o];
+        return k >= 0 && k < h.size[o] ? h.w[(size_t)o * h.window + (size_t)k] : (int16_t)0;
+    };
+    for (uint32_t o = 0; o < 16; o++)
+        for (int64_t x = 0; x < (int64_t)in_size; x++)
+            if (coef(o, x) != coef(15 - o, (int64_t)in_size - 1 - x)) return false;
+    return true;
+}
+
 bool build_mfma_axis_table(uint32_t in_size, int layout, MfmaAxisTable &t)
 {
     t = MfmaAxisTable();

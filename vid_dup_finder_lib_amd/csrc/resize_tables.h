@@ -14,6 +14,11 @@ struct HostAxisTable {
 
 bool build_axis_table(uint32_t in_size, uint32_t out_size, HostAxisTable &t);
 
+// M[o][x] == M[15 - o][in_size - 1 - x] for the dense 16 x in_size table of i16 coefficients (the values every kernel's table is made of):
+// the resize is integer arithmetic with a clip after each pass, so on such an axis the thumbnail of a mirrored frame is exactly the
+// mirrored thumbnail - what the zero plane and the hashes derived from it rest on.  The planes calls ask per axis size.
+bool axis_table_mirror_symmetric(uint32_t in_size);
+
 // The same coefficients laid out as v_mfma_i32_16x16x64_i8 operands.  Each i16 coefficient c is split
 // c = 256 * hi + lo with lo in [-128, 127]; pixels are centred (p - 128) so both factors are signed i8 and
 // bias = 2^(precision-1) + 128 * sum(c) restores the unsigned sum exactly.

@@ -154,6 +154,7 @@ struct vdf_ctx {
     DevBuf sort_scratch;  // keys / indices / rocPRIM temporary storage of the device-side sorts inside a search call
     DevBuf sort_scratch_pub;  // the same for vdf_sort_order_device: the caller may sort on one stream and search on another
     // hash scratch
+    DevBuf out_zero, out_zero2, up_zero, variant_hashes;  // zero planes of the host-frame calls' batches / of vdf_search_variants, and its derived references
     DevBuf small, frames, frames2, out_hashes, out_hashes2, out_dc, out_dc2, cos_table, crops, crop_desc, crop_tables, crop_desc2, crop_tables2, crop_work;
     PinBuf pin[2], pin_out[2];
     PinBuf pin_ctrl;   // search: the counters of a launch (pageable destinations make hipMemcpyAsync synchronous)
@@ -169,6 +170,7 @@ struct vdf_ctx {
     std::map<uint32_t, DeviceAxisTable *> axis_tables;
     std::map<uint64_t, DeviceMfmaTable *> mfma_tables;  // key = in_size * 4 + layout (resize_tables.h)
     std::map<uint64_t, BoxTableSet *> box_tables;       // key = w << 32 | h
+    std::map<uint32_t, bool> axis_symmetric;            // planes calls: resize_tables.h axis_table_mirror_symmetric, asked once per axis size
     bool no_device_path_order = false;  // VDF_NO_DEVICE_PATH_ORDER: vdf_search_cache_entries orders paths on the host (vdf_path_ranks), as before round 6
     bool lb_host_plan = false;     // VDF_LB_HOST_PLAN: small frames' boxes visit the host between detect and hash (as before round 6: A/B runs)
     bool no_lb_fused = false;      // VDF_NO_LB_FUSED: frames of at most 64 x 64 take detect kernels + cropped kernel instead of the fused kernel
@@ -270,12 +272,14 @@ int search_refs_device_locked(vdf_ctx *ctx, const uint64_t *d_cand_hashes, const
                               size_t n_cand, const uint64_t *d_ref_hashes, const uint32_t *d_ref_durations, size_t n_ref,
                               uint32_t tol_int, uint32_t ref_index_base, vdf_hit *hits, uint64_t capacity,
                               uint64_t *n_hits, hipStream_t s, vdf_ctx::HostHits *staging = nullptr);
+// d_zero (here and below; nullable): the clips' zero planes, 16 words each, beside the hashes - same route, the kernels' PLANES forms
 int hash_device_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w,
                        uint32_t h, size_t frame_stride, size_t clip_stride, uint64_t *d_out, uint32_t *d_dc,
-                       hipStream_t stream);
+                       hipStream_t stream, uint64_t *d_zero = nullptr);
 // host frames -> hashes on ONE device: pinned, double-buffered staging (copy of batch k + 1 under the kernels of batch k)
 int hash_host_locked(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h, size_t frame_stride,
-                     size_t clip_stride, int letterbox, uint64_t *out_hashes, uint32_t *out_crops, uint32_t *out_dontcare);
+                     size_t clip_stride, int letterbox, uint64_t *out_hashes, uint32_t *out_crops, uint32_t *out_dontcare,
+                     uint64_t *out_zero = nullptr);  // (not with letterbox)
 // The greedy search() loop over a database that is already resident on every device of the context
 // (d_hashes(dev) / d_dur(dev) give each device's replica): overflow protocol, merge, replay.
 int search_self_resident(vdf_ctx *ctx, size_t n, uint32_t tol_int, vdf_groups *out);
@@ -287,9 +291,10 @@ int letterbox_hash_device_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n
 // clips of different frame sizes in one buffer (include/vdf.h: vdf_hash_clips_u8[_device]): checks every clip, then the uniform launchers or
 // the mixed kernels (api.cpp); the host form repacks the clips into pinned staging batch by batch (hash_host.cpp)
 int hash_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
-                      uint64_t *d_out, uint32_t *d_dc, hipStream_t stream);
+                      uint64_t *d_out, uint32_t *d_dc, hipStream_t stream, uint64_t *d_zero = nullptr);
 int hash_clips_host_locked(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
-                           uint64_t *out_hashes, uint32_t *out_dontcare, int letterbox = 0, uint32_t *out_crops = nullptr);
+                           uint64_t *out_hashes, uint32_t *out_dontcare, int letterbox = 0, uint32_t *out_crops = nullptr,
+                           uint64_t *out_zero = nullptr);  // (not with letterbox)
 // the same with Cropdetect::Letterbox first (vdf_hash_clips_u8_letterbox[_device]): detect on per-clip descriptors, the boxes down, the mixed hash on them
 int letterbox_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips, uint32_t frames_per_clip,
                            uint64_t *d_out, uint32_t *d_dc, uint32_t *out_crops, hipStream_t stream);

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/vdf.h"
+#include "hash_variant.h"
 #include "resize_dispatch.h"
 
 namespace vdf {
@@ -101,7 +102,7 @@ struct MfmaResizeArgs {  // device pointers to the MFMA-layout tables (resize_ta
 hipError_t launch_resize_dct_fused(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h, size_t frame_stride,
                                    size_t clip_stride, const uint8_t *buf_end, const MfmaResizeArgs &a, const HashPlan &plan,
                                    const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare,
-                                   hipStream_t stream);
+                                   hipStream_t stream, uint64_t *out_zero = nullptr);
 // the whole-line kernel (a.av in kMfmaLayoutVerticalWide order)
 hipError_t launch_resize_mfma_frames(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h,
                                      size_t frame_stride, size_t clip_stride, const uint8_t *buf_end,
@@ -167,7 +168,7 @@ hipError_t launch_letterbox(const uint8_t *frames, size_t n_clips, uint32_t fram
 hipError_t launch_resize_dct_cropped_small(const uint8_t *frames, size_t n_clips, uint32_t pitch, size_t frame_stride,
                                            size_t clip_stride, const uint8_t *buf_end, const CropClipDesc *desc,
                                            const CropTableEntry *tables, const double *cos_table, uint64_t *out_hashes,
-                                           uint32_t *out_dontcare, hipStream_t stream);
+                                           uint32_t *out_dontcare, hipStream_t stream, uint64_t *out_zero = nullptr);
 // the same kernel fed from the device (round 6): boxes = the detect's output [n_clips][4] {left, right, top, bottom} in device memory, tables = the
 // (w, h) set of ALL box sizes - horizontal table of box width bw at [bw], vertical table of box height bh at [w + 1 + bh] (api.cpp: box_table_set)
 hipError_t launch_resize_dct_cropped_small_boxes(const uint8_t *frames, size_t n_clips, uint32_t w, uint32_t h, size_t frame_stride,
@@ -194,13 +195,13 @@ hipError_t launch_resize_mfma_cropped(const uint8_t *frames, size_t n_clips, uin
 // first; h_table / v_table index `tables`.  buf_end = buf + buf_bytes of the ONE buffer every clip's offset is relative to.  At most
 // kMaxClipsPerLaunch clips per launch.
 hipError_t launch_mixed_small(const uint8_t *buf, const uint8_t *buf_end, const MixedClipDesc *desc, size_t n_clips, const CropTableEntry *tables,
-                              const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream);
+                              const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream, uint64_t *out_zero = nullptr);
 // small: this launch's first 4 KB slot; wide: whole-line loads, vertical tables in kMfmaLayoutVerticalWide order
 hipError_t launch_mixed_frames(const uint8_t *buf, const uint8_t *buf_end, const MixedClipDesc *desc, size_t n_clips, const CropTableEntry *tables,
                                bool wide, uint8_t *small, hipStream_t stream);
 // slot i of small -> the hash of clip desc[i].out_index
 hipError_t launch_dct_hash_indexed(const uint8_t *small, const MixedClipDesc *desc, size_t n_clips, const double *cos_table, uint64_t *out_hashes,
-                                   uint32_t *out_dontcare, hipStream_t stream);
+                                   uint32_t *out_dontcare, hipStream_t stream, uint64_t *out_zero = nullptr);
 // ---- Search::sort on the device (sort_order.hip) ----------------------------------------------------------------
 // perm_out = the stable order by (duration, path rank); rank nullable (all paths equal).  scratch from sort_order_scratch_bytes.
 size_t sort_order_scratch_bytes(uint32_t n, bool with_rank);
@@ -221,6 +222,12 @@ hipError_t launch_sort_hits(vdf_hit *hits, size_t n, unsigned row_bits, void *sc
 hipError_t launch_gather_hashes(const uint64_t *hashes, const uint32_t *dur, const uint32_t *perm, uint32_t n, uint64_t *hashes_out,
                                 uint32_t *dur_out, hipStream_t stream);
 hipError_t launch_dct_hash(const uint8_t *small, size_t small_clip_stride, size_t small_frame_stride, size_t n_clips,
-                           const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream);
+                           const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream, uint64_t *out_zero = nullptr);
+// ---- the zero plane and the hashes of the flipped clips -------------------------------------------------------------------
+// out_zero (above; nullable): the launch runs its kernels' PLANES instantiations and writes 16 words per clip - bit i set iff coefficient i
+// of the clip is 0.0 - beside the hashes.  Null: the plain instantiations, as before.
+// out[j][c][16] = the hash of clip c flipped by variants[j] (0 ... 7; at most 8 entries, n <= 2^32 - 1)
+hipError_t launch_hash_variants(const uint64_t *hashes, const uint64_t *zero, size_t n, const uint32_t *variants, uint32_t n_variants, uint64_t *out,
+                                hipStream_t stream);
 
 }  // namespace vdf

@@ -194,6 +194,75 @@ class Engine:
         self._check(self.lib.vdf_hash_frames_u8_device(self.ctx, d_frames, n_clips, frames_per_clip, w, h, fs, cs,
                                                        d_out, d_dontcare or None, stream or None))
 
+    # --------------------------------------------- the zero plane and the flipped hashes (include/vdf.h)
+    def hash_frames_planes(self, frames: np.ndarray, want_dontcare: bool = False):
+        """hash_frames plus the zero planes (vdf_hash_frames_u8_planes): -> (hashes [n, 16] u64, zero [n, 16] u64 [, dontcare]); bit i of a
+        zero plane is set iff coefficient i of the clip is exactly 0.0.  The hashes are the plain call's."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.ndim != 4:
+            raise ValueError("frames must be [n_clips, n_frames, H, W]")
+        nc, nf, h, w = frames.shape
+        out = np.zeros((nc, HASH_WORDS), np.uint64)
+        zero = np.zeros((nc, HASH_WORDS), np.uint64)
+        dc = np.zeros(nc, np.uint32) if want_dontcare else None
+        self._check(self.lib.vdf_hash_frames_u8_planes(self.ctx, frames.ctypes.data, nc, nf, w, h, w * h, nf * w * h, out.ctypes.data,
+                                                       dc.ctypes.data if want_dontcare else None, zero.ctypes.data))
+        return (out, zero, dc) if want_dontcare else (out, zero)
+
+    def hash_frames_planes_device(self, d_frames: int, n_clips: int, frames_per_clip: int, w: int, h: int, d_out: int, d_zero: int,
+                                  d_dontcare: int = 0, frame_stride: Optional[int] = None, clip_stride: Optional[int] = None, stream: int = 0):
+        fs = w * h if frame_stride is None else frame_stride
+        cs = fs * frames_per_clip if clip_stride is None else clip_stride
+        self._check(self.lib.vdf_hash_frames_u8_planes_device(self.ctx, d_frames, n_clips, frames_per_clip, w, h, fs, cs, d_out, d_dontcare or None,
+                                                              d_zero or None, stream or None))
+
+    def hash_clips_planes(self, stacks: Sequence[np.ndarray], crops=None, want_dontcare: bool = False):
+        """hash_clips plus the zero planes (vdf_hash_clips_u8_planes): -> (hashes [n, 16] u64, zero [n, 16] u64 [, dontcare]).  With crops
+        (e.g. the boxes a letterbox call detected) the planes - and every variant derived from them - are those of the CROPPED clips."""
+        buf, clips, nf = self._pack_stacks(stacks)
+        n = len(clips)
+        if crops is not None:
+            clips["crop"] = np.asarray(crops, dtype=np.uint32).reshape(n, 4)
+        out = np.zeros((n, HASH_WORDS), np.uint64)
+        zero = np.zeros((n, HASH_WORDS), np.uint64)
+        dc = np.zeros(n, np.uint32) if want_dontcare else None
+        self._check(self.lib.vdf_hash_clips_u8_planes(self.ctx, buf.ctypes.data, buf.size, clips.ctypes.data, n, nf, out.ctypes.data,
+                                                      dc.ctypes.data if want_dontcare else None, zero.ctypes.data))
+        return (out, zero, dc) if want_dontcare else (out, zero)
+
+    def hash_clips_planes_device(self, d_buf: int, buf_bytes: int, clips: np.ndarray, d_out: int, d_zero: int, d_dontcare: int = 0,
+                                 frames_per_clip: int = 16, stream: int = 0):
+        c = np.ascontiguousarray(clips, dtype=CLIP_DTYPE)
+        self._check(self.lib.vdf_hash_clips_u8_planes_device(self.ctx, d_buf, int(buf_bytes), c.ctypes.data if c.size else None, c.size,
+                                                             int(frames_per_clip), d_out, d_dontcare or None, d_zero or None, stream or None))
+
+    def hash_variants_device(self, d_hashes: int, d_zero: int, n: int, variant: int, d_out: int, stream: int = 0):
+        """d_out[c] = the hash of clip c flipped by `variant` (bit 0 = mirror along W, 1 = flip along H, 2 = reverse the frames)."""
+        self._check(self.lib.vdf_hash_variants_device(self.ctx, d_hashes or None, d_zero or None, int(n), int(variant), d_out or None, stream or None))
+
+    def _variant_groups(self, call, variant_mask: int):
+        arr = (VdfGroups * 8)()
+        try:
+            self._check(call(arr))
+            return {v: _groups_to_lists(arr[v]) for v in range(1, 8) if variant_mask >> v & 1}
+        finally:
+            for v in range(8):
+                self.lib.vdf_groups_free(C.byref(arr[v]))
+
+    def search_variants_sorted(self, hashes, zero, durations, tol_int: int, variant_mask: int):
+        """vdf_search_variants on SoA input in Search::sort order: {v: [(r, [indices whose hash is within tol_int of the variant-v hash of r])]}
+        for every v of variant_mask (bits 1 ... 7); (r, r) and empty groups are dropped."""
+        h = np.ascontiguousarray(hashes, dtype=np.uint64).reshape(-1, HASH_WORDS)
+        z = np.ascontiguousarray(zero, dtype=np.uint64).reshape(-1, HASH_WORDS)
+        d = np.ascontiguousarray(durations, dtype=np.uint32)
+        assert h.shape == z.shape and h.shape[0] == d.shape[0]
+        return self._variant_groups(lambda arr: self.lib.vdf_search_variants(self.ctx, h.ctypes.data, z.ctypes.data, d.ctypes.data, len(d), int(tol_int),
+                                                                             int(variant_mask), arr), int(variant_mask))
+
+    def search_variants_device(self, d_hashes: int, d_zero: int, d_durations: int, n: int, tol_int: int, variant_mask: int, stream: int = 0):
+        return self._variant_groups(lambda arr: self.lib.vdf_search_variants_device(self.ctx, d_hashes or None, d_zero or None, d_durations or None, int(n),
+                                                                                    int(tol_int), int(variant_mask), arr, stream or None), int(variant_mask))
+
     @staticmethod
     def _pack_stacks(stacks: Sequence[np.ndarray]):
         """The stacks of a mixed call one after the other in one buffer, every clip on a 64-byte boundary: (buffer, CLIP_DTYPE records, frames)."""
@@ -469,6 +538,17 @@ def hamming_distance_words(a, b) -> int:
     b = np.ascontiguousarray(b, dtype=np.uint64).reshape(HASH_WORDS)
     return int(_capi.load().vdf_hamming_u1024(a.ctypes.data_as(C.POINTER(C.c_uint64)),
                                               b.ctypes.data_as(C.POINTER(C.c_uint64))))
+
+
+def hash_variant(hash_words, zero_words, variant: int) -> np.ndarray:
+    """vdf_hash_variant: the hash of the clip flipped by `variant` (0 ... 7) from its hash and zero plane, [16] u64."""
+    h = np.ascontiguousarray(hash_words, dtype=np.uint64).reshape(HASH_WORDS)
+    z = np.ascontiguousarray(zero_words, dtype=np.uint64).reshape(HASH_WORDS)
+    out = np.zeros(HASH_WORDS, np.uint64)
+    rc = _capi.load().vdf_hash_variant(h.ctypes.data, z.ctypes.data, int(variant), out.ctypes.data)
+    if rc:
+        raise VdfError(rc, "vdf_hash_variant: variant must be 0 ... 7")
+    return out
 
 
 def tolerance_int(tolerance: float) -> int:

@@ -12,6 +12,7 @@
 #pragma once
 #include <algorithm>
 #include <array>
+#include <map>
 #include <cstdint>
 #include <cstdlib>
 #include <memory>
@@ -143,12 +144,32 @@ struct Crop {
     }
 };
 
+// Which way a clip is flipped (not in the reference, which cannot see through a mirror: lib.rs:102-111): X = mirrored along the width,
+// Y = flipped along the height, T = its 16 frames reversed; any combination - the `variant` of vdf_hash_variant.
+enum Flip : uint32_t { FlipX = 1, FlipY = 2, FlipT = 4 };
+
 // ---- VideoHash (video_hash.rs:26-32) ----------------------------------------------------------------------
 class VideoHash {
 public:
+    using Words = std::array<uint64_t, VDF_HASH_WORDS>;
     VideoHash() : hash_{}, duration_(0) {}  // Default, video_hash.rs:34-42
     VideoHash(const std::array<uint64_t, VDF_HASH_WORDS> &h, std::string src_path, uint32_t duration)
         : hash_(h), src_path_(std::move(src_path)), duration_(duration) {}
+    // ... with the clip's zero plane (bit i set iff DCT coefficient i is exactly 0.0): what flipped() needs.  The hash cache's wire format
+    // has no room for it, so hashes loaded from a cache have none.  It takes no part in comparisons.
+    VideoHash(const Words &h, std::string src_path, uint32_t duration, const Words &zero)
+        : hash_(h), src_path_(std::move(src_path)), duration_(duration), zero_(zero) {}
+    const std::optional<Words> &zero() const { return zero_; }
+
+    // The VideoHash the same pipeline gives for the flipped clip (a combination of FlipX, FlipY, FlipT), from this hash and its zero plane
+    // alone (vdf_hash_variant).  No zero plane -> Error::VidProc.
+    VideoHash flipped(uint32_t flip) const
+    {
+        if (!zero_) throw Error::vid_proc("this VideoHash carries no zero plane (from_frame_stacks_planes; hashes loaded from a cache have none)");
+        Words out{};
+        if (vdf_hash_variant(hash_.data(), zero_->data(), flip, out.data()) != VDF_OK) throw std::invalid_argument("flip must be a combination of FlipX, FlipY, FlipT");
+        return VideoHash(out, src_path_, duration_, *zero_);
+    }
 
     // video_hash.rs:45-73.  frames: equal-size gray u8 frames (row-major, w x h); fewer than 16 (or none) ->
     // NotEnoughFrames; only the first 16 are used (dct_3d.rs:25).
@@ -201,6 +222,37 @@ public:
         return out;
     }
 
+    // from_frame_stacks with the zero planes (vdf_hash_clips_u8_planes): the hashes are the same words and can be flipped.  crops (optional, one
+    // l, r, t, b per clip - e.g. what from_frame_stacks_letterbox detected): hash, plane and every flip are those of the CROPPED clip.
+    static std::vector<VideoHash> from_frame_stacks_planes(const std::vector<FrameStack> &stacks, const std::vector<std::array<uint32_t, 4>> *crops = nullptr,
+                                                           Context *ctx_opt = nullptr)
+    {
+        Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+        if (crops && crops->size() != stacks.size()) throw std::invalid_argument("one crop box per clip");
+        std::vector<vdf_clip> clips(stacks.size());
+        size_t at = 0;
+        for (size_t i = 0; i < stacks.size(); i++) {
+            const std::array<uint32_t, 4> c = crops ? (*crops)[i] : std::array<uint32_t, 4>{0, 0, 0, 0};
+            clips[i] = vdf_clip{at, (uint64_t)stacks[i].w * stacks[i].h, stacks[i].w, stacks[i].h, c[0], c[1], c[2], c[3]};
+            at += ((size_t)VDF_DCT_SIZE * stacks[i].w * stacks[i].h + 63) & ~(size_t)63;
+        }
+        std::vector<uint8_t> packed(at);
+        for (size_t i = 0; i < stacks.size(); i++)
+            std::copy(stacks[i].frames, stacks[i].frames + (size_t)VDF_DCT_SIZE * stacks[i].w * stacks[i].h, packed.begin() + (size_t)clips[i].offset);
+        std::vector<uint64_t> words(stacks.size() * VDF_HASH_WORDS), zero(stacks.size() * VDF_HASH_WORDS);
+        const int rc = vdf_hash_clips_u8_planes(ctx.get(), packed.data(), packed.size(), clips.data(), clips.size(), VDF_DCT_SIZE, words.data(), nullptr, zero.data());
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+        std::vector<VideoHash> out;
+        for (size_t i = 0; i < stacks.size(); i++) {
+            Words h, z;
+            std::copy(words.begin() + i * VDF_HASH_WORDS, words.begin() + (i + 1) * VDF_HASH_WORDS, h.begin());
+            std::copy(zero.begin() + i * VDF_HASH_WORDS, zero.begin() + (i + 1) * VDF_HASH_WORDS, z.begin());
+            out.emplace_back(h, stacks[i].src_path, stacks[i].duration, z);
+        }
+        return out;
+    }
+
     // ... with Cropdetect::Letterbox first, the builder's default (vdf_hash_clips_u8_letterbox); crops_out (optional): l, r, t, b per clip
     static std::vector<VideoHash> from_frame_stacks_letterbox(const std::vector<FrameStack> &stacks, std::vector<std::array<uint32_t, 4>> *crops_out = nullptr,
                                                               Context *ctx_opt = nullptr)
@@ -237,8 +289,8 @@ public:
     double normalized_hamming_distance(const VideoHash &o) const { return hamming_distance(o) / 1000.0; }
     const std::array<uint64_t, VDF_HASH_WORDS> &words() const { return hash_; }
 
-    VideoHash with_duration(uint32_t d) const { return VideoHash(hash_, src_path_, d); }
-    VideoHash with_src_path(const std::string &p) const { return VideoHash(hash_, p, duration_); }
+    VideoHash with_duration(uint32_t d) const { VideoHash v(*this); v.duration_ = d; return v; }
+    VideoHash with_src_path(const std::string &p) const { VideoHash v(*this); v.src_path_ = p; return v; }
     static VideoHash empty_hash(const std::string &p) { return VideoHash({}, p, 0); }
     static VideoHash full_hash(const std::string &p)
     {
@@ -252,6 +304,7 @@ private:
     std::array<uint64_t, VDF_HASH_WORDS> hash_;
     std::string src_path_;
     uint32_t duration_;
+    std::optional<Words> zero_;
 };
 
 // ---- MatchGroup (matches/match_group.rs) ---------------------------------------------------------------------
@@ -386,6 +439,43 @@ inline std::vector<MatchGroup> search_with_references(const std::vector<VideoHas
         for (uint64_t k = gr.g.offsets[g]; k < gr.g.offsets[g + 1]; k++) paths.push_back(new_hashes[order[gr.g.members[k]]].src_path());
         out.push_back(MatchGroup::make_with_reference(ref_hashes[(size_t)gr.g.ref_index[g]].src_path(), std::move(paths)));
     }
+    return out;
+}
+
+// Mirrored / flipped / reversed duplicates (vdf_search_variants): for every flip of `flips` (each 1 ... 7) one list of groups - a group's
+// reference is the path of an entry r, its duplicates the entries within `tolerance` of the hash of r FLIPPED, inside r's +-5 % duration window
+// (search_one's); r itself is never among them, entries whose flip matches nothing have no group.  A pair usually shows from both sides.
+// Every hash needs its zero plane (from_frame_stacks_planes), else Error::VidProc.
+inline std::map<uint32_t, std::vector<MatchGroup>> search_flipped(const std::vector<VideoHash> &hashes, double tolerance, const std::vector<uint32_t> &flips = {FlipX},
+                                                                  Context &ctx = Context::default_context())
+{
+    std::map<uint32_t, std::vector<MatchGroup>> out;
+    uint32_t mask = 0;
+    for (uint32_t f : flips) {
+        if (f < 1 || f > 7) throw std::invalid_argument("flips are non-empty combinations of FlipX, FlipY, FlipT");
+        mask |= 1u << f;
+        out[f];
+    }
+    for (const auto &h : hashes)
+        if (!h.zero()) throw Error::vid_proc("search_flipped needs the zero plane of every hash (from_frame_stacks_planes)");
+    if (hashes.empty() || flips.empty()) return out;
+    const auto order = detail::sort_order(hashes, &ctx);
+    std::vector<uint64_t> words, zero(order.size() * VDF_HASH_WORDS);
+    std::vector<uint32_t> dur;
+    detail::to_soa(hashes, order, words, dur);
+    for (size_t k = 0; k < order.size(); k++) std::copy(hashes[order[k]].zero()->begin(), hashes[order[k]].zero()->end(), zero.begin() + k * VDF_HASH_WORDS);
+    vdf_groups gr[8] = {};
+    const int rc = vdf_search_variants(ctx.get(), words.data(), zero.data(), dur.data(), dur.size(), vdf_tolerance_int(tolerance), mask, gr);
+    if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+    for (auto &kv : out) {
+        const vdf_groups &g = gr[kv.first];
+        for (uint64_t i = 0; i < g.n_groups; i++) {
+            std::vector<std::string> paths;
+            for (uint64_t k = g.offsets[i]; k < g.offsets[i + 1]; k++) paths.push_back(hashes[order[g.members[k]]].src_path());
+            kv.second.push_back(MatchGroup::make_with_reference(hashes[order[(size_t)g.ref_index[i]]].src_path(), std::move(paths)));
+        }
+    }
+    for (auto &g : gr) vdf_groups_free(&g);
     return out;
 }
 
