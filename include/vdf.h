@@ -204,6 +204,29 @@ int vdf_hash_frames_u8_letterbox(vdf_ctx *ctx, const uint8_t *frames, size_t n_c
                                  uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride, uint64_t *out_hashes,
                                  uint32_t *out_crops, uint32_t *out_dontcare);
 
+/* ---- every 16-frame window of a clip: duplicates that are shifted in time ---------------------------
+ * A copy with the intro trimmed, a clip cut out of a longer video, a re-upload that starts a few seconds later: the
+ * hash of frames 0..15 does not see them.  These calls hash EVERY window of a clip - window k = frames
+ * [k * window_stride, k * window_stride + 16), n_win = (frames_per_clip - 16) / window_stride + 1 of them
+ * (vdf_hash_window_count) - and read, resize and spatially transform every frame ONCE: the 3-D DCT runs along y,
+ * x, then t, and the y and x passes of a frame are the same in every window that holds it.
+ * Word for word what vdf_hash_frames_u8_device gives on the same buffer with clip_stride = window_stride *
+ * frame_stride, don't-care counts included.  ALL frames_per_clip frames of a clip are used; frame f of clip c at
+ * frames + c*clip_stride + f*frame_stride, no byte outside [frames, end of the last clip's last frame) is read.
+ * out_hashes: n_clips x n_win x 16 words, window k of clip c at 16 (c n_win + k); out_dontcare (nullable) at c n_win + k.
+ * Errors, in this order: frames_per_clip < 16 -> VDF_E_NOT_ENOUGH_FRAMES; a zero dimension -> VDF_E_BAD_DIMS;
+ * frame_stride < w*h -> VDF_E_INVAL; window_stride == 0 -> VDF_E_INVAL; n_clips * n_win >= 2^32 -> VDF_E_INVAL;
+ * (n_clips == 0: VDF_OK, nothing is launched;) a null pointer -> VDF_E_INVAL; a multi-GPU context -> VDF_E_INVAL.
+ * The host form uploads the frames in one piece and calls the device form (no pipelining over the link).
+ * Not here: zero planes of window hashes (flips of windows), letterbox boxes and mixed frame sizes. */
+size_t vdf_hash_window_count(uint32_t frames_per_clip, uint32_t window_stride); /* 0 if frames_per_clip < 16 or window_stride == 0 */
+int vdf_hash_windows_u8(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w,
+                        uint32_t h, size_t frame_stride, size_t clip_stride, uint32_t window_stride, uint64_t *out_hashes,
+                        uint32_t *out_dontcare);
+int vdf_hash_windows_u8_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip,
+                               uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride, uint32_t window_stride,
+                               uint64_t *d_out_hashes, uint32_t *d_out_dontcare, void *stream);
+
 /* ---- clips of DIFFERENT frame sizes in one call ----------------------------------------------------
  * A library holds dozens of resolutions and its files arrive in any order.  All clips of a call live in ONE
  * buffer of buf_bytes bytes and name their place by offset: every address is checked against that buffer on

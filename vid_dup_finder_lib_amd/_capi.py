@@ -133,6 +133,11 @@ SIGNATURES = {
                                      C.c_size_t, C.c_void_p, C.c_void_p]),
     "vdf_hash_frames_u8_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                             C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vdf_hash_window_count": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "vdf_hash_windows_u8": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t,
+                                      C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vdf_hash_windows_u8_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                             C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vdf_cropdetect_letterbox_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                                   C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "vdf_hash_frames_u8_cropped_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -21,7 +21,7 @@ from ._capi import DEFAULT_SEARCH_TOLERANCE, HASH_BITS, HASH_WORDS, TOLERANCE_SC
 from .engine import Engine, hamming_distance_words, hash_variant, tolerance_int
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
-           "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "rust_path_key", "sort_order",
+           "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "hash_frame_windows", "locate", "rust_path_key", "sort_order",
            "DEFAULT_SEARCH_TOLERANCE", "TOLERANCE_SCALING_FACTOR"]
 
 
@@ -491,6 +491,42 @@ def hash_frame_stacks(frames: np.ndarray, src_paths: Sequence, durations: Sequen
             raise NotEnoughFrames() from e
         raise
     return [VideoHash(words[i], src_paths[i], durations[i]) for i in range(len(words))]
+
+
+def hash_frame_windows(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int], stride: int = 1,
+                       engine: Optional[Engine] = None) -> List[List[VideoHash]]:
+    """Every 16-frame window of every video (Engine.hash_windows): frames [n_videos, n_frames >= 16, H, W] u8 -> per video the VideoHash of
+    frames [k * stride, k * stride + 16) for k = 0 .. (n_frames - 16) // stride, each carrying the video's src_paths[i] and durations[i].
+    What finds a duplicate that is shifted in time (`locate`); the reference hashes one 16-frame stack per file (definitions.rs:31-34)."""
+    if len(src_paths) < len(frames) or len(durations) < len(frames):
+        raise ValueError("a path and a duration per video")
+    try:
+        words = (engine or default_engine()).hash_windows(frames, stride)
+    except VdfError as e:
+        if e.code == _capi.VDF_E_NOT_ENOUGH_FRAMES:
+            raise NotEnoughFrames() from e
+        raise
+    return [[VideoHash(words[i, k], src_paths[i], durations[i]) for k in range(words.shape[1])] for i in range(words.shape[0])]
+
+
+def locate(needles: Sequence[VideoHash], windows: List[List[VideoHash]], tolerance: float, stride: int = 1,
+           engine: Optional[Engine] = None) -> List[List[tuple]]:
+    """Where do the needles occur in the videos?  windows: hash_frame_windows' result at the same `stride`.  Per needle, ascending, the
+    (video index, first frame = k * stride, hamming distance) of every window within `tolerance` of it.  The existing reference search
+    with every duration set to 0, so that search_one's +-5 % duration window admits every entry: where in a video a clip sits says
+    nothing about how long the clip is."""
+    needles = list(needles)
+    flat = [(v, k) for v, ws in enumerate(windows) for k in range(len(ws))]
+    if not needles or not flat:
+        return [[] for _ in needles]
+    engine = engine or default_engine()
+    words = np.stack([windows[v][k].hash for v, k in flat])
+    rwords = np.stack([n.hash for n in needles])
+    res = engine.search_refs_sorted(words, np.zeros(len(flat), np.uint32), rwords, np.zeros(len(needles), np.uint32), tolerance_int(tolerance))
+    out: List[List[tuple]] = [[] for _ in needles]
+    for r, ms in res:
+        out[r] = sorted((flat[m][0], flat[m][1] * stride, hamming_distance_words(needles[r].hash, words[m])) for m in ms)
+    return out
 
 
 def gen_hashes(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int],

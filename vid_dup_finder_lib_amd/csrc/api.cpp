@@ -656,25 +656,67 @@ int dct_hash_of_small(vdf_ctx *ctx, const HashJob &j)
     return VDF_OK;
 }
 
-// scalar fixed-point resize (any coefficient range)
-int hash_scalar(vdf_ctx *ctx, const HashJob &j)
+// Fetch the MFMA tables a plan names; a table that does not fit is what the plan could not know: plan again (plan_of(fit)) with that fact - the
+// second plan ends in kScalar or kRefused.  *plan: the plan that stands; *mh, *mv: its tables (none for kDirect16, kScalar, kRefused).
+template <class PlanOf>
+int settle_plan(vdf_ctx *ctx, const HashJob &j, PlanOf plan_of, vdf::HashPlan *plan, DeviceMfmaTable **mh, DeviceMfmaTable **mv)
 {
-    const int need_h = (j.w != VDF_DCT_SIZE), need_v = (j.h != VDF_DCT_SIZE);
+    using vdf::HashRoute;
     int rc = VDF_OK;
-    DeviceAxisTable *th = need_h ? axis_table(ctx, j.w, j.stream, &rc) : nullptr;
-    if (rc) return rc;
-    DeviceAxisTable *tv = need_v ? axis_table(ctx, j.h, j.stream, &rc) : nullptr;
-    if (rc) return rc;
-    int32_t y_first = 0, tmp_rows = VDF_DCT_SIZE;
-    if (need_v) {
-        y_first = tv->host.start[0];
-        tmp_rows = tv->host.start[VDF_DCT_SIZE - 1] + tv->host.size[VDF_DCT_SIZE - 1] - y_first;
+    *plan = plan_of(vdf::TableFit::kAll);
+    *mh = *mv = nullptr;
+    while (plan->route != HashRoute::kDirect16 && plan->route != HashRoute::kScalar && plan->route != HashRoute::kRefused) {
+        *mh = mfma_table(ctx, j.w, plan->layout_h, j.stream, &rc);
+        if (rc) return rc;
+        if (!(*mh)->host.ok && plan->layout_h == vdf::kMfmaLayoutHorizontalBand) { *plan = plan_of(vdf::TableFit::kNoBand); continue; }
+        *mv = mfma_table(ctx, j.h, plan->layout_v, j.stream, &rc);
+        if (rc) return rc;
+        if ((*mh)->host.ok && (*mv)->host.ok) break;
+        *plan = plan_of(vdf::TableFit::kNoPlain);
     }
-    if ((size_t)tmp_rows * 16 > 64 * 1024) return fail(ctx, VDF_E_BAD_DIMS, "frame height above 4096 is not supported by the scalar resize kernel");
-    VDF_HIP(ctx, ctx->small.reserve(j.n_clips * 4096));
-    VDF_HIP(ctx, vdf::launch_resize_generic(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, dev_view(th), dev_view(tv), need_h, need_v,
-                                            y_first, tmp_rows, ctx->small.as<uint8_t>(), j.stream));
-    return dct_hash_of_small(ctx, j);
+    return VDF_OK;
+}
+
+// The routes that resize apart from the DCT (chunk stream, wave stream, K-split, whole-line, scalar): frame f of clip c of the job to
+// small + 4096 c + 256 f.  The plain call's second half (dct_hash_of_small follows) and the whole resize stage of the windows calls.
+int resize_into_small(vdf_ctx *ctx, const HashJob &j, const vdf::HashPlan &plan, const DeviceMfmaTable *mh, const DeviceMfmaTable *mv, uint8_t *small)
+{
+    using vdf::HashRoute;
+    switch (plan.route) {
+    case HashRoute::kChunkStream:
+    case HashRoute::kWaveStream:
+        VDF_HIP(ctx, vdf::launch_resize_mfma_frames_stream(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, resize_args(ctx, mh, mv), plan, small, j.stream));
+        return VDF_OK;
+    case HashRoute::kKsplit:
+        VDF_HIP(ctx, vdf::launch_resize_mfma_frames_ksplit(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, resize_args(ctx, mh, mv), plan, small, j.stream));
+        return VDF_OK;
+    case HashRoute::kWholeLine:
+        VDF_HIP(ctx, vdf::launch_resize_mfma_frames(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, j.buf_end(), resize_args(ctx, mh, mv), small, j.stream));
+        return VDF_OK;
+    case HashRoute::kScalar: {  // scalar fixed-point resize (any coefficient range)
+        const int need_h = (j.w != VDF_DCT_SIZE), need_v = (j.h != VDF_DCT_SIZE);
+        int rc = VDF_OK;
+        DeviceAxisTable *th = need_h ? axis_table(ctx, j.w, j.stream, &rc) : nullptr;
+        if (rc) return rc;
+        DeviceAxisTable *tv = need_v ? axis_table(ctx, j.h, j.stream, &rc) : nullptr;
+        if (rc) return rc;
+        int32_t y_first = 0, tmp_rows = VDF_DCT_SIZE;
+        if (need_v) {
+            y_first = tv->host.start[0];
+            tmp_rows = tv->host.start[VDF_DCT_SIZE - 1] + tv->host.size[VDF_DCT_SIZE - 1] - y_first;
+        }
+        if ((size_t)tmp_rows * 16 > 64 * 1024) return fail(ctx, VDF_E_BAD_DIMS, "frame height above 4096 is not supported by the scalar resize kernel");
+        VDF_HIP(ctx, vdf::launch_resize_generic(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, dev_view(th), dev_view(tv), need_h, need_v,
+                                                y_first, tmp_rows, small, j.stream));
+        return VDF_OK;
+    }
+    case HashRoute::kRefused: return fail(ctx, VDF_E_BAD_DIMS, "coefficients do not fit the i8 split");
+    case HashRoute::kDirect16:
+    case HashRoute::kPersistentOneTile:
+    case HashRoute::kTiled:
+    case HashRoute::kPerClipFused: break;
+    }
+    return fail(ctx, VDF_E_INVAL, "internal: a route that does not resize into the 16 x 16 buffer");
 }
 
 // Plan (resize_dispatch.h: plan_hash), fetch the tables the plan names, launch its route.
@@ -685,26 +727,11 @@ int hash_launch(vdf_ctx *ctx, const HashJob &j)
     int rc = ensure_cos_table(ctx, j.stream);
     if (rc) return rc;
     const vdf::HashKnobs knobs = hash_knobs(ctx);
-    vdf::HashPlan plan = vdf::plan_hash(j.call(), knobs);
+    vdf::HashPlan plan;
     DeviceMfmaTable *mh = nullptr, *mv = nullptr;
-    // a table that does not fit is what the plan could not know: plan again with that fact (the second one ends in kScalar or kRefused)
-    while (plan.route != HashRoute::kDirect16 && plan.route != HashRoute::kScalar && plan.route != HashRoute::kRefused) {
-        mh = mfma_table(ctx, j.w, plan.layout_h, j.stream, &rc);
-        if (rc) return rc;
-        if (!mh->host.ok && plan.layout_h == vdf::kMfmaLayoutHorizontalBand) { plan = vdf::plan_hash(j.call(), knobs, vdf::TableFit::kNoBand); continue; }
-        mv = mfma_table(ctx, j.h, plan.layout_v, j.stream, &rc);
-        if (rc) return rc;
-        if (mh->host.ok && mv->host.ok) break;
-        plan = vdf::plan_hash(j.call(), knobs, vdf::TableFit::kNoPlain);
-    }
-    uint8_t *small = nullptr;
-    if (plan.route == HashRoute::kChunkStream || plan.route == HashRoute::kWaveStream || plan.route == HashRoute::kKsplit || plan.route == HashRoute::kWholeLine) {
-        VDF_HIP(ctx, ctx->small.reserve(j.n_clips * 4096));
-        small = ctx->small.as<uint8_t>();
-    }
+    if ((rc = settle_plan(ctx, j, [&](vdf::TableFit fit) { return vdf::plan_hash(j.call(), knobs, fit); }, &plan, &mh, &mv))) return rc;
     switch (plan.route) {
     case HashRoute::kRefused: return fail(ctx, VDF_E_BAD_DIMS, "coefficients do not fit the i8 split");
-    case HashRoute::kScalar: return hash_scalar(ctx, j);
     case HashRoute::kDirect16:
         VDF_HIP(ctx, vdf::launch_dct_hash(j.d_frames, j.clip_stride, j.frame_stride, j.n_clips, ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream, j.d_zero));
         return VDF_OK;
@@ -714,17 +741,10 @@ int hash_launch(vdf_ctx *ctx, const HashJob &j)
         VDF_HIP(ctx, vdf::launch_resize_dct_fused(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, j.buf_end(), resize_args(ctx, mh, mv), plan,
                                                   ctx->cos_table.as<double>(), j.d_out, j.d_dc, j.stream, j.d_zero));
         return VDF_OK;
-    case HashRoute::kChunkStream:
-    case HashRoute::kWaveStream:
-        VDF_HIP(ctx, vdf::launch_resize_mfma_frames_stream(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, resize_args(ctx, mh, mv), plan, small, j.stream));
-        break;
-    case HashRoute::kKsplit:
-        VDF_HIP(ctx, vdf::launch_resize_mfma_frames_ksplit(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, resize_args(ctx, mh, mv), plan, small, j.stream));
-        break;
-    case HashRoute::kWholeLine:
-        VDF_HIP(ctx, vdf::launch_resize_mfma_frames(j.d_frames, j.n_clips, j.w, j.h, j.frame_stride, j.clip_stride, j.buf_end(), resize_args(ctx, mh, mv), small, j.stream));
-        break;
+    default: break;
     }
+    VDF_HIP(ctx, ctx->small.reserve(j.n_clips * 4096));
+    if ((rc = resize_into_small(ctx, j, plan, mh, mv, ctx->small.as<uint8_t>()))) return rc;
     return dct_hash_of_small(ctx, j);
 }
 
@@ -734,6 +754,75 @@ int hash_device_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, ui
 {
     const HashJob all{d_frames, n_clips, w, h, frame_stride, clip_stride, d_out, d_dc, stream, d_zero};
     return checked_launches(ctx, all, frames_per_clip, [&](size_t c0, size_t n) { return hash_launch(ctx, all.clips(c0, n)); });
+}
+
+// ---- every 16-frame window of a clip (include/vdf.h: vdf_hash_windows_u8[_device]) ----------------------------------------------
+// The resize stage of one run of 16-frame pseudo-clips (windows_plan.h): planned by plan_resize_only (resize_dispatch.h: the plain call's plan, with the
+// routes that fuse the DCT sent to the whole-line or the scalar kernel), the plain call's tables and launchers, pseudo-clip i to small + 4096 i.
+int windows_resize_run(vdf_ctx *ctx, const HashJob &j, uint8_t *small)
+{
+    const vdf::HashKnobs knobs = hash_knobs(ctx);
+    vdf::HashPlan plan;
+    DeviceMfmaTable *mh = nullptr, *mv = nullptr;
+    if (int rc = settle_plan(ctx, j, [&](vdf::TableFit fit) { return vdf::plan_resize_only(j.call(), knobs, fit); }, &plan, &mh, &mv)) return rc;
+    return resize_into_small(ctx, j, plan, mh, mv, small);
+}
+
+// the argument checks of the windows calls, in the order their codes are reported; *run: there is something to hash
+int windows_checks(vdf_ctx *ctx, const void *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h, size_t frame_stride,
+                   uint32_t window_stride, const void *out_hashes, bool *run)
+{
+    *run = false;
+    if (frames_per_clip < VDF_DCT_SIZE) return fail(ctx, VDF_E_NOT_ENOUGH_FRAMES, "fewer than 16 frames per clip");
+    if (w == 0 || h == 0) return fail(ctx, VDF_E_BAD_DIMS, "zero frame dimension");
+    if (frame_stride < (size_t)w * h) return fail(ctx, VDF_E_INVAL, "frame_stride smaller than a frame");
+    if (window_stride == 0) return fail(ctx, VDF_E_INVAL, "window_stride of zero");
+    const size_t n_win = vdf::window_count(frames_per_clip, window_stride);
+    // (frame counts within 64 of 2^32 are refused with the same code: the kernel's frame arithmetic is 32-bit)
+    if (frames_per_clip > 0xFFFFFFC0u || (n_clips && n_win > 0xFFFFFFFFull / n_clips)) return fail(ctx, VDF_E_INVAL, "2^32 windows or more in one call");
+    if (n_clips == 0) return VDF_OK;
+    if (!frames || !out_hashes) return fail(ctx, VDF_E_INVAL, "null pointer");
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "the windows calls take a single-device context");
+    *run = true;
+    return VDF_OK;
+}
+
+// windows_checks has passed
+int hash_windows_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h, size_t frame_stride,
+                        size_t clip_stride, uint32_t window_stride, uint64_t *d_out, uint32_t *d_dc, hipStream_t stream)
+{
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = ensure_cos_table(ctx, stream)) return rc;
+    const vdf::WindowsPlan plan = vdf::plan_windows(frames_per_clip, window_stride);
+    vdf::WindowsFrames wf{};
+    if (w == VDF_DCT_SIZE && h == VDF_DCT_SIZE) {  // the resize is a copy: the kernel reads the caller's frames
+        wf.base = wf.tail = d_frames;
+        wf.clip_stride = clip_stride;
+        wf.chunk_stride = 16 * frame_stride;
+        wf.frame_stride = frame_stride;
+        wf.main_frames = frames_per_clip;
+        wf.dwords = (((uintptr_t)d_frames | frame_stride | clip_stride) & 3u) == 0;
+    } else {
+        const vdf::WindowsResizePlan rp = vdf::plan_windows_resize(n_clips, frames_per_clip, frame_stride, clip_stride);
+        VDF_HIP(ctx, ctx->small.reserve(rp.small_bytes));
+        uint8_t *small = ctx->small.as<uint8_t>();
+        for (const vdf::WindowsResizeRun &r : vdf::windows_resize_runs(rp, n_clips, frames_per_clip, frame_stride, clip_stride))
+            for (size_t c0 = 0; c0 < r.n; c0 += kMaxClipsPerLaunch) {  // launches of at most kMaxClipsPerLaunch pseudo-clips
+                const HashJob j{d_frames + r.src_offset + c0 * r.step, std::min(kMaxClipsPerLaunch, r.n - c0), w, h, frame_stride, r.step, nullptr, nullptr, stream};
+                if (int rc = windows_resize_run(ctx, j, small + r.dst_offset + c0 * 4096)) return rc;
+            }
+        wf.base = small;
+        wf.tail = small + rp.tail_offset;
+        wf.clip_stride = rp.clip_step;
+        wf.chunk_stride = rp.chunk_step;
+        wf.frame_stride = 256;
+        wf.tail_clip_stride = 4096;
+        wf.main_frames = 16 * rp.n_chunks;
+        wf.tail_first = frames_per_clip - 16;
+        wf.dwords = true;
+    }
+    VDF_HIP(ctx, vdf::launch_dct_hash_windows(wf, n_clips, plan, ctx->cos_table.as<double>(), d_out, d_dc, stream));
+    return VDF_OK;
 }
 
 // The tables that the descriptors of one launch name, by (box size, axis): each is fetched, and gets its entry, where a box first asks for it.
@@ -1658,6 +1747,49 @@ int vdf_hash_frames_u8_letterbox(vdf_ctx *ctx, const uint8_t *frames, size_t n_c
 {
     return hash_host_entry(ctx, frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, 1, out_hashes, out_crops,
                            out_dontcare);
+}
+
+size_t vdf_hash_window_count(uint32_t frames_per_clip, uint32_t window_stride) { return vdf::window_count(frames_per_clip, window_stride); }
+
+int vdf_hash_windows_u8_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h,
+                               size_t frame_stride, size_t clip_stride, uint32_t window_stride, uint64_t *d_out_hashes,
+                               uint32_t *d_out_dontcare, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    bool run;
+    if (int rc = windows_checks(ctx, d_frames, n_clips, frames_per_clip, w, h, frame_stride, window_stride, d_out_hashes, &run)) return rc;
+    if (!run) return VDF_OK;
+    return hash_windows_locked(ctx, d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, window_stride, d_out_hashes, d_out_dontcare,
+                               stream ? (hipStream_t)stream : ctx->stream);
+}
+
+// Host arrays: the frames go up through the context's staging buffer in one piece, the device form runs on it, the results come down.
+int vdf_hash_windows_u8(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h,
+                        size_t frame_stride, size_t clip_stride, uint32_t window_stride, uint64_t *out_hashes, uint32_t *out_dontcare)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    bool run;
+    if (int rc = windows_checks(ctx, frames, n_clips, frames_per_clip, w, h, frame_stride, window_stride, out_hashes, &run)) return rc;
+    if (!run) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n_out = n_clips * vdf::window_count(frames_per_clip, window_stride);
+    size_t clips_span = 0, frames_span = 0, bytes = 0;  // first byte of clip 0 to the last byte of the last clip's last frame, in size_t
+    if (__builtin_mul_overflow(n_clips - 1, clip_stride, &clips_span) || __builtin_mul_overflow((size_t)(frames_per_clip - 1), frame_stride, &frames_span) ||
+        __builtin_add_overflow(clips_span, frames_span, &bytes) || __builtin_add_overflow(bytes, (size_t)w * h, &bytes))
+        return fail(ctx, VDF_E_INVAL, "the clips' extent does not fit size_t");
+    if (int rc = upload(ctx, ctx->frames, frames, bytes, ctx->stream)) return rc;
+    VDF_HIP(ctx, ctx->out_hashes.reserve(n_out * VDF_HASH_WORDS * sizeof(uint64_t)));
+    if (out_dontcare) VDF_HIP(ctx, ctx->out_dc.reserve(n_out * sizeof(uint32_t)));
+    uint32_t *d_dc = out_dontcare ? ctx->out_dc.as<uint32_t>() : nullptr;
+    if (int rc = hash_windows_locked(ctx, ctx->frames.as<uint8_t>(), n_clips, frames_per_clip, w, h, frame_stride, clip_stride, window_stride,
+                                     ctx->out_hashes.as<uint64_t>(), d_dc, ctx->stream))
+        return rc;
+    VDF_HIP(ctx, hipMemcpyAsync(out_hashes, ctx->out_hashes.p, n_out * VDF_HASH_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (out_dontcare) VDF_HIP(ctx, hipMemcpyAsync(out_dontcare, d_dc, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VDF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VDF_OK;
 }
 
 int vdf_cropdetect_letterbox_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip,

@@ -254,6 +254,22 @@ HashPlan plan_hash(const HashCall &c, const HashKnobs &k, TableFit fit)
     return p;
 }
 
+HashPlan plan_resize_only(const HashCall &c, const HashKnobs &k, TableFit fit)
+{
+    HashPlan p = plan_hash(c, k, fit);
+    if (p.route == HashRoute::kPersistentOneTile || p.route == HashRoute::kTiled || p.route == HashRoute::kPerClipFused || p.route == HashRoute::kDirect16) {
+        HashKnobs whole_line = k;
+        whole_line.resize_mode = 4;
+        p = plan_hash(c, whole_line, fit);
+        if (p.route == HashRoute::kDirect16) {  // (16 x 16 frames on 16-byte boundaries: the windows calls read them in place and never ask)
+            p.route = HashRoute::kWholeLine;
+            p.layout_v = kMfmaLayoutVerticalWide;
+        }
+        if (p.route == HashRoute::kRefused) p.route = HashRoute::kScalar;  // (refused by the mode forced here, not by the caller's)
+    }
+    return p;
+}
+
 CropPlan plan_cropped(const HashCall &c, const HashKnobs &k, const uint32_t *crops, const CropTableFit &fit)
 {
     CropPlan p;

@@ -107,6 +107,11 @@ struct HashPlan {
     bool last_clip_apart = false;  // the persistent kernels: the last clip goes through the per-clip kernel and its careful loader
 };
 HashPlan plan_hash(const HashCall &c, const HashKnobs &k, TableFit fit = TableFit::kAll);
+// The resize stage alone (the windows calls, DESIGN.md 4.9: the DCT is a kernel of its own there): plan_hash's route where that route writes
+// the 16 x 16 frames to memory - chunk stream, wave stream, K-split, whole-line, scalar - and, where plan_hash names a kernel with the DCT
+// fused in (or the 16 x 16 copy), the whole-line kernel; the scalar kernel where the whole-line tables do not fit the i8 split (kNoPlain).
+// Never a fused route, never kDirect16; kRefused only as plan_hash refuses (a forced mode of the caller's whose tables do not fit).
+HashPlan plan_resize_only(const HashCall &c, const HashKnobs &k, TableFit fit = TableFit::kAll);
 
 // resize_dct_hash_tiled_kernel<NKT, NRG, WAVES>: WAVES (the second __launch_bounds__ argument) by [NKT - 1][NRG = 1, 2, 4]; measured
 // (profiles/r05_short_frames.txt).  0: no such instantiation (one tile is the persistent kernel's).

@@ -7,6 +7,7 @@
 #include "../../include/vdf.h"
 #include "hash_variant.h"
 #include "resize_dispatch.h"
+#include "windows_plan.h"
 
 namespace vdf {
 
@@ -229,5 +230,17 @@ hipError_t launch_dct_hash(const uint8_t *small, size_t small_clip_stride, size_
 // out[j][c][16] = the hash of clip c flipped by variants[j] (0 ... 7; at most 8 entries, n <= 2^32 - 1)
 hipError_t launch_hash_variants(const uint64_t *hashes, const uint64_t *zero, size_t n, const uint32_t *variants, uint32_t n_variants, uint64_t *out,
                                 hipStream_t stream);
+// ---- every 16-frame window of a clip (windows_plan.h) -------------------------------------------------------------------------
+// Where the 16 x 16 frames of the clips are: frame f of clip c at base + c clip_stride + (f / 16) chunk_stride + (f % 16) frame_stride for
+// f < main_frames, else at tail + c tail_clip_stride + 256 (f - tail_first).  dwords: every frame starts on a 4-byte boundary.
+struct WindowsFrames {
+    const uint8_t *base, *tail;
+    size_t clip_stride, chunk_stride, frame_stride, tail_clip_stride;
+    uint32_t main_frames, tail_first;
+    bool dwords;
+};
+// out_hashes[16 (c n_win + k)] = the hash of frames [k stride, k stride + 16) of clip c; out_dontcare (nullable) at c n_win + k
+hipError_t launch_dct_hash_windows(const WindowsFrames &f, size_t n_clips, const WindowsPlan &plan, const double *cos_table, uint64_t *out_hashes,
+                                   uint32_t *out_dontcare, hipStream_t stream);
 
 }  // namespace vdf

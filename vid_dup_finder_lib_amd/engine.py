@@ -53,6 +53,15 @@ def _atoi(text: str) -> int:
     return int(m.group(1)) if m else 0
 
 
+def _window_stride(stride) -> int:
+    """The window stride as the C ABI's uint32_t takes it.  ctypes would wrap a value outside the type without a word (-1 -> 2^32 - 1,
+    2^32 + 1 -> 1) and the library would then write a different number of windows than the caller sized its output for."""
+    s = int(stride)
+    if s != stride or not 1 <= s < 2**32:
+        raise ValueError(f"window stride must be an integer in 1 .. 2^32 - 1, not {stride!r}")
+    return s
+
+
 class Engine:
     """One context: one GPU (`device`, default LOCAL_RANK or 0), or - `devices=[...]` - ONE context over several GPUs
     of the node (vdf_ctx_create_multi: the host-array calls fan out inside the library, the *_shards methods take
@@ -193,6 +202,31 @@ class Engine:
         cs = fs * frames_per_clip if clip_stride is None else clip_stride
         self._check(self.lib.vdf_hash_frames_u8_device(self.ctx, d_frames, n_clips, frames_per_clip, w, h, fs, cs,
                                                        d_out, d_dontcare or None, stream or None))
+
+    # --------------------------------------------- every 16-frame window of a clip (include/vdf.h)
+    def hash_windows(self, frames: np.ndarray, stride: int = 1, want_dontcare: bool = False):
+        """frames [n_clips, n_frames, H, W] u8 (host) -> hashes [n_clips, n_win, 16] u64: window k = frames [k * stride, k * stride + 16),
+        n_win = (n_frames - 16) // stride + 1; every frame is read, resized and spatially transformed once (vdf_hash_windows_u8)."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.ndim != 4:
+            raise ValueError("frames must be [n_clips, n_frames, H, W]")
+        nc, nf, h, w = frames.shape
+        stride = _window_stride(stride)
+        n_win = int(self.lib.vdf_hash_window_count(nf, stride))
+        out = np.zeros((nc, n_win, HASH_WORDS), np.uint64)
+        dc = np.zeros((nc, n_win), np.uint32) if want_dontcare else None
+        self._check(self.lib.vdf_hash_windows_u8(self.ctx, frames.ctypes.data, nc, nf, w, h, w * h, nf * w * h, stride, out.ctypes.data,
+                                                 dc.ctypes.data if want_dontcare else None))
+        return (out, dc) if want_dontcare else out
+
+    def hash_windows_device(self, d_frames: int, n_clips: int, frames_per_clip: int, w: int, h: int, stride: int, d_out: int,
+                            d_dontcare: int = 0, frame_stride: Optional[int] = None, clip_stride: Optional[int] = None, stream: int = 0):
+        """d_out: n_clips x n_win x 16 words (window_count(frames_per_clip, stride) windows per clip); all frames_per_clip frames are used."""
+        stride = _window_stride(stride)
+        fs = w * h if frame_stride is None else frame_stride
+        cs = fs * frames_per_clip if clip_stride is None else clip_stride
+        self._check(self.lib.vdf_hash_windows_u8_device(self.ctx, d_frames, n_clips, frames_per_clip, w, h, fs, cs, stride, d_out,
+                                                        d_dontcare or None, stream or None))
 
     # --------------------------------------------- the zero plane and the flipped hashes (include/vdf.h, DESIGN.md 4.8)
     def hash_frames_planes(self, frames: np.ndarray, want_dontcare: bool = False):

@@ -222,6 +222,41 @@ public:
         return out;
     }
 
+    // Every 16-frame window of every video (vdf_hash_windows_u8): frames = n_videos x frames_per_video tightly packed gray
+    // frames of w x h.  Per video the VideoHash of frames [k * stride, k * stride + 16), k = 0 .. (frames_per_video - 16) / stride, each with
+    // the video's path and duration: what finds a duplicate that is shifted in time.  Every frame is read and resized once.
+    static std::vector<std::vector<VideoHash>> hash_windows(const uint8_t *frames, size_t n_videos, uint32_t frames_per_video, uint32_t w, uint32_t h,
+                                                            uint32_t stride, const std::vector<std::string> &src_paths,
+                                                            const std::vector<uint32_t> &durations, Context *ctx_opt = nullptr)
+    {
+        if (frames_per_video < VDF_DCT_SIZE) throw Error::not_enough_frames();
+        if (src_paths.size() < n_videos || durations.size() < n_videos) throw std::invalid_argument("a path and a duration per video");
+        Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+        const size_t n_win = vdf_hash_window_count(frames_per_video, stride), fs = (size_t)w * h;
+        std::vector<uint64_t> words(n_videos * n_win * VDF_HASH_WORDS);
+        const int rc = vdf_hash_windows_u8(ctx.get(), frames, n_videos, frames_per_video, w, h, fs, fs * frames_per_video, stride, words.data(), nullptr);
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+        std::vector<std::vector<VideoHash>> out(n_videos);
+        for (size_t i = 0; i < n_videos; i++)
+            for (size_t k = 0; k < n_win; k++) {
+                std::array<uint64_t, VDF_HASH_WORDS> hw;
+                std::copy(words.begin() + (i * n_win + k) * VDF_HASH_WORDS, words.begin() + (i * n_win + k + 1) * VDF_HASH_WORDS, hw.begin());
+                out[i].emplace_back(hw, src_paths[i], durations[i]);
+            }
+        return out;
+    }
+    // The same on device memory: d_out = n_clips x vdf_hash_window_count(frames_per_clip, stride) x 16 words, d_dontcare nullable.
+    static void hash_windows_device(Context &ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h,
+                                    size_t frame_stride, size_t clip_stride, uint32_t stride, uint64_t *d_out, uint32_t *d_dontcare = nullptr,
+                                    void *stream = nullptr)
+    {
+        const int rc = vdf_hash_windows_u8_device(ctx.get(), d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, stride, d_out, d_dontcare, stream);
+        if (rc == VDF_E_NOT_ENOUGH_FRAMES) throw Error::not_enough_frames();
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+    }
+
     // from_frame_stacks with the zero planes (vdf_hash_clips_u8_planes): the hashes are the same words and can be flipped.  crops (optional, one
     // l, r, t, b per clip - e.g. what from_frame_stacks_letterbox detected): hash, plane and every flip are those of the CROPPED clip.
     static std::vector<VideoHash> from_frame_stacks_planes(const std::vector<FrameStack> &stacks, const std::vector<std::array<uint32_t, 4>> *crops = nullptr,
