@@ -227,6 +227,55 @@ int vdf_hash_windows_u8_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_c
                                uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride, uint32_t window_stride,
                                uint64_t *d_out_hashes, uint32_t *d_out_dontcare, void *stream);
 
+/* ---- align videos on their window hashes: the longest shared stretch of every pair of videos -------------
+ * Which videos share a stretch, at what offset, and for how long.  Two sets of videos, A and B, each the
+ * window hashes of its videos one after the other (what vdf_hash_windows_* writes): hashes[n_windows_total][16] and
+ * first[n_videos + 1], video v owning the windows first[v] ... first[v + 1].  Videos may differ in window count; a video of
+ * 0 windows is legal and pairs with nothing.  For videos a, b with Na, Nb windows:
+ *   - a CELL (ka, kb) matches iff neither window is skipped and vdf_hamming_u1024(A[a][ka], B[b][kb]) <= tol
+ *     (tol = min(tol_int, 1024), as the searches clamp it);
+ *   - a RUN is a maximal stretch of consecutive matching cells on one diagonal offset = kb - ka: (offset, start_a,
+ *     n_windows, dist_sum); only runs of n_windows >= min_run compete;
+ *   - the best run of the pair maximises score = n_windows * (tol + 1) - dist_sum: every matching cell adds at least 1, so a
+ *     maximal run beats its sub-runs, and a true copy at distance ~0 beats the same stretch seen one diagonal off at a
+ *     larger distance, even where that one is a window longer.  Ties: the smaller signed offset, then the smaller start_a;
+ *   - a pair without a competing run produces nothing: at most ONE record per pair, however dense the matches are.
+ * b_hashes == NULL is SELF mode: B = A (b_first, n_b, b_skip are ignored) and only the pairs a < b are evaluated; a video is
+ * never aligned with itself.  skip (nullable, one byte per window, non-zero = this window abstains) lets static stretches
+ * stay out: their windows are all alike and match everything static.
+ * out: HOST buffer of `capacity` records, filled in (a, b) order.  *n_out = the number of records found; if it exceeds
+ * capacity the first `capacity` entries of out are valid (the first in (a, b) order) and the caller calls again with a larger
+ * buffer - VDF_OK, like the hit buffers.
+ * Errors, in this order, all VDF_E_INVAL: a null required pointer (out may be NULL when capacity is 0); min_run == 0; a
+ * video of more than 2^20 windows (keeps the score below 2^31); a first array that is not non-decreasing (the device
+ * form reads the first arrays back to plan the launch and checks them too; that they fit the hash arrays is the caller's
+ * contract); more than 2^24 pairs of videos in one call (the mirrors split); a multi-GPU context.
+ * n_a == 0, n_b == 0 or self mode with one video: VDF_OK, *n_out = 0, nothing is launched.
+ * vdf_align_windows_device: the array pointers are DEVICE pointers (hashes 16-byte aligned), out is on the host; the call
+ * waits for its own work.  vdf_align_windows: host arrays; uploads them and calls the device form.
+ * vdf_align_windows_host: no context, no GPU - the definition above in plain C++ (every diagonal walked, XOR + popcount):
+ * the CPU-tested statement of the semantics, for tiny inputs and tests.
+ * Known limit: ONE stretch per pair - a video that holds two separate excerpts of another reports the better one.
+ * Not here: flipped or reversed stretches, multi-GPU contexts. */
+typedef struct vdf_alignment { /* 24 bytes */
+    uint32_t a;                /* video index in A */
+    uint32_t b;                /* video index in B (self mode: in A, a < b) */
+    int32_t offset;            /* kb - ka, in windows */
+    uint32_t start_a;          /* ka of the run's first window */
+    uint32_t n_windows;
+    uint32_t dist_sum;         /* sum of the run's distances */
+} vdf_alignment;
+int vdf_align_windows_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                           const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                           uint32_t tol_int, uint32_t min_run, vdf_alignment *out, size_t capacity, size_t *n_out);
+int vdf_align_windows(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                      const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                      uint32_t tol_int, uint32_t min_run, vdf_alignment *out, size_t capacity, size_t *n_out);
+int vdf_align_windows_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a,
+                             const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b,
+                             const uint8_t *d_b_skip, uint32_t tol_int, uint32_t min_run, vdf_alignment *out,
+                             size_t capacity, size_t *n_out, void *stream);
+
 /* ---- clips of DIFFERENT frame sizes in one call ----------------------------------------------------
  * A library holds dozens of resolutions and its files arrive in any order.  All clips of a call live in ONE
  * buffer of buf_bytes bytes and name their place by offset: every address is checked against that buffer on

@@ -1,0 +1,258 @@
+#!/usr/bin/env python3
+"""What aligning videos on the device buys: vdf_align_windows_device of this build beside the only way to get the same
+answer from the parent commit - its reference search of all A windows against all B windows with every duration 0, the hit list brought
+down, and the runs aggregated in numpy - on the same device-resident window hashes.
+
+    python tools/bench_align.py --parent-lib tools/_libvdf_parent.so [--out profiles/align_windows.txt]
+
+Shapes: 1000 videos x 49 windows against each other (self mode); 2 videos x 7185 windows (self mode: one pair, 225 bands); 64 x 64 videos x
+1000 windows.  Corpora: `plain` - random hashes with planted shifted copies (0 .. 40 flipped bits per window); `static` - the same with a
+stretch of 10 % of every video's windows replaced by ONE static hash, so that every pair of videos shares static cells; `static+skip`
+(align only) - the static windows flagged in the skip bytes.
+Legs, each in a fresh child process, taking turns ROUNDS times, each turn one warm-up and REPEATS timed calls per (shape, corpus); host
+clock around calls that end in a device synchronise:
+  align    vdf_align_windows_device, capacity = all pairs
+  parent   vdf_search_refs_device of the library built from the PARENT commit (--parent-lib; without it this build's own search stands in
+           and is labelled so) with a 2^24-entry hit buffer, then the aggregation; on an overflow the call is timed as far as it got and
+           the answer is reported as not available
+The records of both legs must be equal wherever the parent leg has an answer.  The one claim under test: the align call's time on the
+static corpus is that of the plain corpus within the run-to-run spread of the 12 calls.  cells/s is printed beside the VALU search
+backend's measured 7.5e11 pairs/s (README): the yardstick of this inner loop, not a gate."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REPEATS, ROUNDS = 6, 2
+TOL, MIN_RUN = 350, 2
+HIT_CAPACITY = 1 << 24
+VALU_PAIRS_PER_S = 7.5e11
+SHAPES = {"1000x49 self": (1000, 49, None), "2x7185 self": (2, 7185, None), "64x64x1000": (64, 1000, 64)}
+ALIGN_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("offset", "<i4"), ("start_a", "<u4"), ("n_windows", "<u4"), ("dist_sum", "<u4")])
+
+
+def random_hashes(rng, n):
+    w = rng.integers(0, 2**64, size=(n, 16), dtype=np.uint64)
+    w[:, 15] &= np.uint64((1 << 40) - 1)
+    return w
+
+
+def flip_bits(rng, rows):
+    """0 .. 40 flipped bits per row"""
+    out = rows.copy()
+    for r in out:
+        for pos in rng.choice(1000, size=int(rng.integers(0, 41)), replace=False):
+            r[pos >> 6] ^= np.uint64(1) << np.uint64(pos & 63)
+    return out
+
+
+def corpus(shape, static):
+    """-> a_hashes, a_first, b_hashes | None, b_first | None, a_skip, b_skip (the static windows)"""
+    n_a, n_win, n_b = SHAPES[shape]
+    rng = np.random.default_rng([11, n_a, n_win])
+    a, fa = random_hashes(rng, n_a * n_win), np.arange(n_a + 1, dtype=np.uint32) * n_win
+    b, fb = (None, None) if n_b is None else (random_hashes(rng, n_b * n_win), np.arange(n_b + 1, dtype=np.uint32) * n_win)
+    length = n_win // 2
+    if n_b is None:  # every tenth video holds a shifted copy of half of its predecessor
+        for v in range(1, n_a, 10 if n_a > 2 else 1):
+            s, t = int(rng.integers(0, n_win - length + 1)), int(rng.integers(0, n_win - length + 1))
+            a[v * n_win + s:v * n_win + s + length] = flip_bits(rng, a[(v - 1) * n_win + t:(v - 1) * n_win + t + length])
+    else:
+        for v in range(0, n_b, 4):
+            s, t = int(rng.integers(0, n_win - length + 1)), int(rng.integers(0, n_win - length + 1))
+            b[v * n_win + s:v * n_win + s + length] = flip_bits(rng, a[v * n_win + t:v * n_win + t + length])
+    ska, skb = np.zeros(len(a), np.uint8), None if b is None else np.zeros(len(b), np.uint8)
+    if static:
+        one = random_hashes(rng, 1)[0]
+        k = max(1, n_win // 10)
+        for h, sk, n in ((a, ska, n_a),) + (() if b is None else ((b, skb, n_b),)):
+            for v in range(n):
+                s = int(rng.integers(0, n_win - k + 1))
+                h[v * n_win + s:v * n_win + s + k] = one
+                sk[v * n_win + s:v * n_win + s + k] = 1
+    return a, fa, b, fb, ska, skb
+
+
+POP8 = np.array([bin(i).count("1") for i in range(256)], np.uint8)
+
+
+def aggregate(hits, a, fa, b, fb, self_mode):
+    """the runs of a (row = window of A, col = window of B) hit list, the best per pair of videos: the definition of include/vdf.h in numpy"""
+    ra, cb = hits[:, 0].astype(np.int64), hits[:, 1].astype(np.int64)
+    va, vb = np.searchsorted(fa, ra, side="right") - 1, np.searchsorted(fb, cb, side="right") - 1
+    if self_mode:
+        keep = va < vb
+        ra, cb, va, vb = ra[keep], cb[keep], va[keep], vb[keep]
+    ka, kb = ra - fa[va], cb - fb[vb]
+    dist = np.zeros(len(ra), np.int64)
+    for i in range(0, len(ra), 1 << 18):
+        dist[i:i + (1 << 18)] = POP8[(a[ra[i:i + (1 << 18)]] ^ b[cb[i:i + (1 << 18)]]).view(np.uint8)].sum(axis=1)
+    off = kb - ka
+    order = np.lexsort((ka, off, vb, va))
+    va, vb, off, ka, dist = va[order], vb[order], off[order], ka[order], dist[order]
+    if len(va) == 0:
+        return np.zeros(0, ALIGN_DTYPE)
+    new = np.ones(len(va), bool)
+    new[1:] = (va[1:] != va[:-1]) | (vb[1:] != vb[:-1]) | (off[1:] != off[:-1]) | (ka[1:] != ka[:-1] + 1)
+    first = np.flatnonzero(new)
+    n = np.diff(np.append(first, len(va)))
+    s = np.add.reduceat(dist, first)
+    ok = n >= MIN_RUN
+    first, n, s = first[ok], n[ok], s[ok]
+    score = n * (TOL + 1) - s
+    pick = np.lexsort((ka[first], off[first], -score, vb[first], va[first]))
+    first, n, s = first[pick], n[pick], s[pick]
+    lead = np.ones(len(first), bool)
+    lead[1:] = (va[first][1:] != va[first][:-1]) | (vb[first][1:] != vb[first][:-1])
+    first, n, s = first[lead], n[lead], s[lead]
+    out = np.zeros(len(first), ALIGN_DTYPE)
+    out["a"], out["b"], out["offset"], out["start_a"], out["n_windows"], out["dist_sum"] = va[first], vb[first], off[first], ka[first], n, s
+    return out
+
+
+def digest(rec):
+    w = np.ascontiguousarray(rec).view(np.uint32).astype(np.uint64).reshape(-1)
+    return int(np.bitwise_xor.reduce(w * np.arange(1, w.size + 1, dtype=np.uint64))) if w.size else 0
+
+
+def child(args):
+    import torch
+
+    lib = C.CDLL(args.lib)
+    lib.vdf_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    lib.vdf_last_error.restype = C.c_char_p
+    lib.vdf_last_error.argtypes = [C.c_void_p]
+    ctx = C.c_void_p()
+    assert lib.vdf_ctx_create(0, C.byref(ctx)) == 0, lib.vdf_last_error(None)
+    if args.leg == "align":
+        lib.vdf_align_windows_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                 C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    else:
+        lib.vdf_search_refs_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                               C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]
+    dev = lambda x, t: None if x is None else torch.from_numpy(np.ascontiguousarray(x).view(t)).cuda()
+    ptr = lambda t: None if t is None else t.data_ptr()
+    res = {}
+    for shape, (n_a, n_win, n_b) in SHAPES.items():
+        self_mode = n_b is None
+        pairs = n_a * (n_a - 1) // 2 if self_mode else n_a * n_b
+        for kind in ("plain", "static", "static+skip") if args.leg == "align" else ("plain", "static"):
+            a, fa, b, fb, ska, skb = corpus(shape, kind != "plain")
+            d_a, d_fa, d_b, d_fb = dev(a, np.int64), dev(fa, np.int32), dev(b, np.int64), dev(fb, np.int32)
+            d_ska, d_skb = (dev(ska, np.uint8), dev(skb, np.uint8)) if kind == "static+skip" else (None, None)
+            torch.cuda.synchronize()
+            key = f"{shape}/{kind}"
+            if args.leg == "align":
+                out = np.zeros(pairs, ALIGN_DTYPE)
+                n_out = C.c_size_t(0)
+
+                def run():
+                    rc = lib.vdf_align_windows_device(ctx, ptr(d_a), ptr(d_fa), n_a, ptr(d_ska), ptr(d_b), ptr(d_fb), 0 if self_mode else n_b, ptr(d_skb), TOL, MIN_RUN,
+                                                      out.ctypes.data, pairs, C.byref(n_out), None)
+                    assert rc == 0, (rc, lib.vdf_last_error(ctx))
+                times = []
+                for r in range(REPEATS + 1):
+                    t0 = time.perf_counter()
+                    run()
+                    if r:
+                        times.append(time.perf_counter() - t0)
+                res[key] = {"times": times, "records": int(n_out.value), "digest": digest(out[:n_out.value]), "overflow": False}
+            else:
+                bb, fbb, d_bb = (a, fa, d_a) if self_mode else (b, fb, d_b)
+                zeros_a, zeros_b = torch.zeros(len(a), dtype=torch.int32, device="cuda"), torch.zeros(len(bb), dtype=torch.int32, device="cuda")
+                hits = np.zeros((HIT_CAPACITY, 2), np.uint32)
+                n_hits = C.c_uint64(0)
+                torch.cuda.synchronize()
+                times, search_times, rec, overflow = [], [], None, False
+                for r in range(REPEATS + 1):
+                    t0 = time.perf_counter()
+                    rc = lib.vdf_search_refs_device(ctx, ptr(d_bb), zeros_b.data_ptr(), len(bb), ptr(d_a), zeros_a.data_ptr(), len(a), TOL, 0, hits.ctypes.data,
+                                                    HIT_CAPACITY, C.byref(n_hits), None)
+                    t1 = time.perf_counter()
+                    overflow = rc == -6 or n_hits.value > HIT_CAPACITY
+                    assert rc == 0 or overflow, (rc, lib.vdf_last_error(ctx))
+                    rec = None if overflow else aggregate(hits[:n_hits.value], a, fa.astype(np.int64), bb, fbb.astype(np.int64), self_mode)
+                    if r:
+                        times.append(time.perf_counter() - t0)
+                        search_times.append(t1 - t0)
+                res[key] = {"times": times, "search_times": search_times, "hits": int(n_hits.value), "overflow": bool(overflow),
+                            "records": None if rec is None else len(rec), "digest": None if rec is None else digest(rec)}
+            del d_a, d_b
+        torch.cuda.empty_cache()
+    print("RESULT " + json.dumps(res))
+
+
+def run_child(lib, leg):
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--lib", lib, "--leg", leg], capture_output=True, text=True, timeout=900)
+    line = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")]
+    if out.returncode != 0 or not line:
+        raise SystemExit(f"child {leg} failed ({out.returncode}):\n{out.stdout[-2000:]}\n{out.stderr[-4000:]}")
+    return json.loads(line[-1][7:])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_windows.txt"))
+    ap.add_argument("--child", action="store_true")
+    ap.add_argument("--lib", default=os.path.join(ROOT, "vid_dup_finder_lib_amd", "libvdf_hip.so"))
+    ap.add_argument("--leg", default="align")
+    args = ap.parse_args()
+    if args.child:
+        return child(args)
+    search_lib = os.path.abspath(args.parent_lib) if args.parent_lib else args.lib
+    got = {}
+    for _ in range(ROUNDS):
+        for leg, lib in (("align", args.lib), ("parent", search_lib)):
+            for key, v in run_child(lib, leg).items():
+                e = got.setdefault(key, {}).setdefault(leg, {"times": [], "search_times": []})
+                e["times"] += v["times"]
+                e["search_times"] += v.get("search_times", [])
+                e.update({k: v[k] for k in v if k not in ("times", "search_times")})
+    whose = "the PARENT commit's library" if args.parent_lib else "THIS build's search (no --parent-lib: not the parent commit)"
+    lines = [f"tools/bench_align.py: {ROUNDS} rounds x {REPEATS} timed calls per leg (one warm-up per round), fresh process per leg and round, legs in turn",
+             f"tolerance {TOL}, min_run {MIN_RUN}; parent leg: vdf_search_refs_device of {whose}, durations 0, {HIT_CAPACITY} hit slots, + numpy aggregation",
+             f"cells/s beside the VALU search backend's measured {VALU_PAIRS_PER_S:.2e} pairs/s (README): a yardstick, not a gate"]
+    ok = True
+    ms = lambda ts: f"min {min(ts) * 1e3:9.3f}  median {statistics.median(ts) * 1e3:9.3f}  max {max(ts) * 1e3:9.3f} ms ({len(ts)} calls)"
+    for shape, (n_a, n_win, n_b) in SHAPES.items():
+        pairs = n_a * (n_a - 1) // 2 if n_b is None else n_a * n_b
+        cells = pairs * n_win * n_win
+        lines.append(f"\n{shape}: {pairs} pairs of videos, {cells:.3e} cells")
+        for kind in ("plain", "static", "static+skip"):
+            e = got[f"{shape}/{kind}"]
+            al = e["align"]
+            med = statistics.median(al["times"])
+            lines.append(f"  {kind:12s} align   {ms(al['times'])}  {al['records']} records  {cells / med:.3e} cells/s = {cells / med / VALU_PAIRS_PER_S:.2f} of the VALU yardstick")
+            if "parent" in e:
+                pa = e["parent"]
+                lines.append(f"  {kind:12s} parent  {ms(pa['times'])}  of which search {statistics.median(pa['search_times']) * 1e3:.3f} ms median; {pa['hits']} hits, "
+                             f"hit buffer {'OVERFLOWED: no answer' if pa['overflow'] else 'held them'}")
+                if not pa["overflow"]:
+                    same = pa["digest"] == al["digest"] and pa["records"] == al["records"]
+                    ok &= same
+                    lines.append(f"  {kind:12s} records of both legs {'equal' if same else 'DIFFER'}; parent / align, medians = {statistics.median(pa['times']) / med:.2f}x")
+        p, s = got[f"{shape}/plain"]["align"]["times"], got[f"{shape}/static"]["align"]["times"]
+        spread = max(max(p) - min(p), max(s) - min(s))
+        diff = abs(statistics.median(s) - statistics.median(p))
+        held = diff <= spread
+        ok &= held
+        lines.append(f"  claim (align on the static corpus takes what it takes on the plain one, within the spread of the 12 calls): medians differ by {diff * 1e3:.3f} ms, "
+                     f"spread (max - min, the wider of the two) {spread * 1e3:.3f} ms: {'HOLDS' if held else 'MISSED'}")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

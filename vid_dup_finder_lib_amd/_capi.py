@@ -89,6 +89,12 @@ class VdfClip(C.Structure):
                 ("crop_left", C.c_uint32), ("crop_right", C.c_uint32), ("crop_top", C.c_uint32), ("crop_bottom", C.c_uint32)]
 
 
+class VdfAlignment(C.Structure):
+    """One record of vdf_align_windows[_device|_host]: 24 bytes (the numpy twin is engine.ALIGN_DTYPE)."""
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("offset", C.c_int32), ("start_a", C.c_uint32), ("n_windows", C.c_uint32),
+                ("dist_sum", C.c_uint32)]
+
+
 AGREE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64))
 OR_BITMAP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -138,6 +144,12 @@ SIGNATURES = {
                                       C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vdf_hash_windows_u8_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                              C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vdf_align_windows_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vdf_align_windows": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                    C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vdf_align_windows_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                           C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
     "vdf_cropdetect_letterbox_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                                   C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "vdf_hash_frames_u8_cropped_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,

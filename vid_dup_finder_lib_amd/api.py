@@ -12,13 +12,14 @@ from __future__ import annotations
 import enum
 import itertools
 import os
-from typing import Iterable, Iterator, List, Optional, Sequence
+import math
+from typing import Iterable, Iterator, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 
 from . import _capi
 from ._capi import DEFAULT_SEARCH_TOLERANCE, HASH_BITS, HASH_WORDS, TOLERANCE_SCALING_FACTOR, VdfError
-from .engine import Engine, hamming_distance_words, hash_variant, tolerance_int
+from .engine import ALIGN_DTYPE, Engine, align_windows_host, hamming_distance_words, hash_variant, tolerance_int
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
            "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "hash_frame_windows", "locate", "rust_path_key", "sort_order",
@@ -526,6 +527,111 @@ def locate(needles: Sequence[VideoHash], windows: List[List[VideoHash]], toleran
     out: List[List[tuple]] = [[] for _ in needles]
     for r, ms in res:
         out[r] = sorted((flat[m][0], flat[m][1] * stride, hamming_distance_words(needles[r].hash, words[m])) for m in ms)
+    return out
+
+
+class Alignment(NamedTuple):
+    """The longest stretch two videos share (align): video indices into windows_a / windows_b, the shift and the stretch in frames,
+    the mean hamming distance of its windows, and the two videos' paths."""
+    a: int
+    b: int
+    offset_frames: int     # first_frame_b - first_frame_a
+    first_frame_a: int
+    first_frame_b: int
+    n_frames: int          # (n_windows - 1) * stride + 16
+    n_windows: int
+    mean_distance: float
+    path_a: object = None
+    path_b: object = None
+
+
+ALIGN_MAX_PAIRS = 1 << 24       # pairs of videos one call of the C ABI takes (include/vdf.h); align splits above it
+ALIGN_FIRST_CAPACITY = 4096     # records the first try of a call makes room for; a call that finds more is repeated with room for all
+ALIGN_HOST_CELLS = 1 << 16      # with no engine given, inputs of at most this many cells are walked on the CPU (vdf_align_windows_host)
+ALIGN_STATIC_DONTCARE = 900     # a window of identical frames has no temporal content: its 900 coefficients of temporal frequency > 0 are 0
+
+
+def static_windows(dontcare, threshold: int = ALIGN_STATIC_DONTCARE) -> np.ndarray:
+    """Per-window skip flags for align from the don't-care counts of Engine.hash_windows(..., want_dontcare=True): a window with at least
+    `threshold` of its 1000 coefficients at zero is static - its hash is rounding noise and like every other static window's."""
+    return (np.asarray(dontcare) >= threshold).astype(np.uint8)
+
+
+def _align_csr(windows, static):
+    counts = [len(ws) for ws in windows]
+    first = np.zeros(len(windows) + 1, np.uint32)
+    first[1:] = np.cumsum(counts)
+    words = np.zeros((int(first[-1]), HASH_WORDS), np.uint64)
+    k = 0
+    for ws in windows:
+        for h in ws:
+            words[k] = h.hash
+            k += 1
+    skip = None
+    if static is not None:
+        if len(static) != len(windows) or any(len(f) != n for f, n in zip(static, counts)):
+            raise ValueError("one static flag per window of every video")
+        skip = np.concatenate([np.asarray(f, dtype=bool).astype(np.uint8).reshape(-1) for f in static] + [np.zeros(0, np.uint8)])
+    return words, first, skip, counts
+
+
+def _align_call(engine, a, b, tol_int, min_run):
+    """One call of the C ABI, repeated with a larger buffer if the first try's was too small.  a, b: (words, first, skip); b None: self."""
+    def once(capacity):
+        kw = dict(tol_int=tol_int, min_run=min_run, a_skip=a[2], capacity=capacity)
+        if b is not None:
+            kw.update(b_hashes=b[0], b_first=b[1], b_skip=b[2])
+        return align_windows_host(a[0], a[1], **kw) if engine is None else engine.align_windows(a[0], a[1], **kw)
+    rec, found = once(ALIGN_FIRST_CAPACITY)
+    if found > len(rec):
+        rec, found = once(found)
+    return rec
+
+
+def align(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoHash]]] = None, tolerance: float = DEFAULT_SEARCH_TOLERANCE,
+          min_run: int = 1, stride: int = 1, static_a=None, static_b=None, engine: Optional[Engine] = None) -> List[Alignment]:
+    """Which videos share a stretch, at what offset, and for how long?  windows_a / windows_b: hash_frame_windows' results at the same
+    `stride` (videos may differ in length); windows_b None: the videos of windows_a against each other, every pair once (a < b).
+    Per pair of videos at most ONE Alignment, ordered by (a, b): the run of consecutive windows within `tolerance` on one diagonal
+    (first_frame_b - first_frame_a constant) that maximises n_windows * (tol_int + 1) - sum of distances, of at least min_run windows
+    (include/vdf.h: vdf_align_windows; a video that holds two separate excerpts of another reports the better one).
+    static_a / static_b: per video, one flag per window (static_windows); flagged windows abstain - static stretches match each other
+    everywhere.  Calls of more than ALIGN_MAX_PAIRS pairs are split.  With no engine given, tiny inputs are walked on the CPU."""
+    self_mode = windows_b is None
+    s = int(stride)
+    if s != stride or s < 1:
+        raise ValueError("stride must be a positive integer")
+    tol_int = tolerance_int(tolerance)
+    wa, fa, ka, ca = _align_csr(windows_a, static_a)
+    wb, fb, kb, cb = (wa, fa, ka, ca) if self_mode else _align_csr(windows_b, static_b)
+    if engine is None:
+        cells = (sum(ca) ** 2 - sum(n * n for n in ca)) // 2 if self_mode else sum(ca) * sum(cb)
+        if cells > ALIGN_HOST_CELLS:
+            engine = default_engine()
+
+    def block(words, first, skip, lo, hi):
+        w0, w1 = int(first[lo]), int(first[hi])
+        return words[w0:w1], first[lo:hi + 1] - first[lo], None if skip is None else skip[w0:w1]
+
+    step = max(1, math.isqrt(ALIGN_MAX_PAIRS))
+    parts = []
+    for a0 in range(0, len(ca), step):
+        a1 = min(a0 + step, len(ca))
+        A = block(wa, fa, ka, a0, a1)
+        for b0 in range(a0 if self_mode else 0, len(cb), step):
+            b1 = min(b0 + step, len(cb))
+            rec = _align_call(engine, A, None if (self_mode and b0 == a0) else block(wb, fb, kb, b0, b1), tol_int, int(min_run)).copy()
+            rec["a"] += a0
+            rec["b"] += b0
+            parts.append(rec)
+    rec = np.concatenate(parts) if parts else np.zeros(0, ALIGN_DTYPE)
+    rec = rec[np.lexsort((rec["b"], rec["a"]))]
+    pa = [ws[0].src_path() if ws else None for ws in windows_a]
+    pb = pa if self_mode else [ws[0].src_path() if ws else None for ws in windows_b]
+    out = []
+    for r in rec:
+        a, b, off, st, n, ds = (int(r[k]) for k in ("a", "b", "offset", "start_a", "n_windows", "dist_sum"))
+        out.append(Alignment(a, b, off * s, st * s, (st + off) * s, (n - 1) * s + _capi.DCT_SIZE, n, ds / n, pa[a], pb[b]))
     return out
 
 

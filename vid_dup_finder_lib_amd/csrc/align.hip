@@ -1,0 +1,250 @@
+// Alignment of videos on their window hashes for gfx950 (MI355X), wave64: the longest shared stretch of every (video a, video b) pair
+// (include/vdf.h: vdf_align_windows[_device]).  The answer is a reduction along the diagonals of each pair's distance
+// matrix, so nothing here emits a hit list and the cost does not depend on how dense the matches are.
+//
+// align_bands_kernel: one wave per (pair, band of 64 diagonals d0 ... d0 + 63), four waves per workgroup.  The wave walks ka upward:
+//   - the row of A is wave-uniform: scalar loads, the SGPR operand of v_xor_b32, v_bcnt_u32_b32 accumulates - the inner loop of the
+//     VALU search backend (hamming.hip: hamming_tile_kernel), 64 VALU lane-ops per cell;
+//   - lane kb mod 64 keeps row kb of B in 32 VGPRs; the 64 rows a step needs slide by one per step, so one lane reloads one row
+//     (128 B, exec-masked) per step and every other lane keeps its row;
+//   - the run state of a diagonal (length, dist_sum) moves one lane up per step: two wave rotates (ds_bpermute_b32), the only cross-lane traffic.
+//     No LDS, no carry between waves: a diagonal never leaves its wave;
+//   - a run ends at a non-matching cell or at the matrix edge; the lane that sees the end folds it into its own best.
+// The lane-ownership rules are align_plan.h's (shared with the CPU replay in tests/cpp/align_plan_main.cpp).
+// align_reduce_kernel / align_scan_kernel / align_scatter_kernel: the bands of each pair -> one record, the pairs that have one -> a
+// dense list in (a, b) order (flag + scan: the pairs of a chunk are enumerated in that order).
+#include "align_plan.h"
+#include "vdf_internal.h"
+
+namespace vdf {
+
+typedef const __attribute__((address_space(4))) uint32_t *align_u32_ptr;  // forces s_load for uniform addresses
+
+// every lane takes the value of the lane below it, lane 0 that of lane 63 (align_plan.h: align_rotate_source).  The DPP form (one
+// v_mov_b32_dpp wave_ror:1 instead of a ds_bpermute_b32) assembles for gfx950 but has not been run on the part: it stays off until
+// tools/probe_wave_rotate.hip has confirmed it there.
+constexpr bool kAlignRotateDpp = false;
+__device__ __forceinline__ uint32_t align_rotate_up(uint32_t v, uint32_t lane)
+{
+    if (kAlignRotateDpp) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x13C, 0xF, 0xF, false);  // v_mov_b32_dpp wave_ror:1
+    return (uint32_t)__shfl((int)v, (int)align_rotate_source(lane), 64);
+}
+
+__device__ __forceinline__ void align_load_row(uint32_t (&rw)[32], const uint32_t *__restrict__ rows, uint32_t kb)
+{
+    const uint4 *rp = reinterpret_cast<const uint4 *>(rows + (size_t)kb * 32);
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        const uint4 v = rp[q];
+        rw[4 * q + 0] = v.x; rw[4 * q + 1] = v.y; rw[4 * q + 2] = v.z; rw[4 * q + 3] = v.w;
+    }
+}
+
+__global__ __launch_bounds__(256) void align_bands_kernel(
+    const uint32_t *__restrict__ a_hashes, const uint32_t *__restrict__ a_first, const uint8_t *__restrict__ a_skip,
+    const uint32_t *__restrict__ b_hashes, const uint32_t *__restrict__ b_first, const uint8_t *__restrict__ b_skip,
+    const AlignPair *__restrict__ pairs, const uint32_t *__restrict__ unit_offset, uint32_t n_pairs, uint32_t n_units, uint32_t tol,
+    uint32_t min_run, AlignBandRecord *__restrict__ band_records, uint32_t group_base)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t unit = (blockIdx.x + group_base) * kAlignWaves + wave;  // grids above 2^32 work-items are launched in cuts
+    if (unit >= n_units) return;
+
+    const uint32_t p = align_unit_pair((align_u32_ptr)(uintptr_t)unit_offset, n_pairs, unit);
+    const uint32_t band = unit - ((align_u32_ptr)(uintptr_t)unit_offset)[p];
+    const uint32_t va = ((align_u32_ptr)(uintptr_t)pairs)[2 * p], vb = ((align_u32_ptr)(uintptr_t)pairs)[2 * p + 1];
+    const uint32_t fa = ((align_u32_ptr)(uintptr_t)a_first)[va], Na = ((align_u32_ptr)(uintptr_t)a_first)[va + 1] - fa;
+    const uint32_t fb = ((align_u32_ptr)(uintptr_t)b_first)[vb], Nb = ((align_u32_ptr)(uintptr_t)b_first)[vb + 1] - fb;
+    const int32_t d0 = align_band_d0(Na, band);
+    const uint32_t ka0 = align_ka_begin(d0), ka1 = align_ka_end(Na, Nb, d0);
+
+    const uint32_t *b_rows = b_hashes + (size_t)fb * 32;
+    const uint8_t *b_sk = b_skip ? b_skip + fb : nullptr;
+    align_u32_ptr a_rows = (align_u32_ptr)(uintptr_t)a_hashes + (size_t)fa * 32;
+
+    // this lane's row of B; cells outside the matrix are misses and no address is formed for them
+    uint32_t rw[32];
+    int32_t kb = align_lane_row(lane, ka0, d0);
+    bool row_ok = kb >= 0 && kb < (int32_t)Nb;
+    uint32_t row_skip = 0;  // the row's skip byte: compared where the row is used, so that the load is not waited for where it is issued
+    if (row_ok) {
+        if (b_sk) row_skip = b_sk[kb];
+        align_load_row(rw, b_rows, (uint32_t)kb);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 32; q++) rw[q] = 0u;
+    }
+
+    uint32_t len = 0, sum = 0;                                              // the run of the diagonal this lane is on
+    uint32_t best_score = 0, best_start = 0, best_n = 0, best_sum = 0;     // score 0 = none: every run scores at least 1
+    int32_t best_off = 0;
+    for (uint32_t ka = ka0; ka < ka1; ++ka) {
+        align_u32_ptr ap = a_rows + (size_t)ka * 32;
+        uint32_t d = 0;
+#pragma unroll
+        for (int w = 0; w < 32; ++w) d += __builtin_popcount(rw[w] ^ ap[w]);  // ap[w]: SGPR
+        bool a_ok = true;  // wave-uniform: the skip byte of A's row comes with the aligned dword that holds it, by a scalar load like the row
+        if (a_skip) {
+            const uintptr_t at = (uintptr_t)a_skip + fa + ka;
+            a_ok = ((*(align_u32_ptr)(at & ~(uintptr_t)3) >> (8 * (uint32_t)(at & 3))) & 0xFFu) == 0u;
+        }
+        const bool match = row_ok && row_skip == 0 && a_ok && d <= tol;
+        if (match) { len += 1; sum += d; }
+        const bool edge = ka + 1 == Na || kb + 1 == (int32_t)Nb;              // the diagonal's last cell
+        const bool ends = len != 0 && (!match || edge);
+        if (__builtin_amdgcn_ballot_w64(ends) != 0ull) {
+            if (ends && len >= min_run) {
+                const uint32_t score = len * (tol + 1) - sum;
+                const uint32_t start = (match ? ka + 1 : ka) - len;
+                const int32_t off = kb - (int32_t)ka;
+                if (align_better(score, off, start, best_score, best_off, best_start)) {
+                    best_score = score; best_off = off; best_start = start; best_n = len; best_sum = sum;
+                }
+            }
+            if (ends) { len = 0; sum = 0; }
+        }
+        // the state follows its diagonal one lane up
+        len = align_rotate_up(len, lane);
+        sum = align_rotate_up(sum, lane);
+        // the lane whose diagonal d0 is done takes the row of diagonal d0 + 63 of the next step
+        if (ka + 1 < ka1 && lane == align_reload_lane(ka, d0)) {
+            kb += (int32_t)kAlignBand;  // = align_reload_row(ka, d0) >= 1, from the lane's own register: the address stays a vector address
+            row_ok = kb < (int32_t)Nb;
+            row_skip = 0;
+            if (row_ok) {
+                if (b_sk) row_skip = b_sk[kb];
+                align_load_row(rw, b_rows, (uint32_t)kb);
+            }
+        }
+    }
+
+    // the wave's best of its 64 lane-bests; every run has its own (score, offset, start)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t o_score = (uint32_t)__shfl_xor((int)best_score, o, 64), o_start = (uint32_t)__shfl_xor((int)best_start, o, 64);
+        const uint32_t o_n = (uint32_t)__shfl_xor((int)best_n, o, 64), o_sum = (uint32_t)__shfl_xor((int)best_sum, o, 64);
+        const int32_t o_off = __shfl_xor(best_off, o, 64);
+        if (align_better(o_score, o_off, o_start, best_score, best_off, best_start)) {
+            best_score = o_score; best_off = o_off; best_start = o_start; best_n = o_n; best_sum = o_sum;
+        }
+    }
+    if (lane == 0) band_records[unit] = AlignBandRecord{best_off, best_start, best_score ? best_n : 0u, best_sum};
+}
+
+__device__ __forceinline__ uint32_t align_block_rank(bool has, uint32_t *s_wave, uint32_t *block_total)
+{  // rank of a thread among the threads of its 256-thread workgroup with `has`, in thread order
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(has);
+    if (lane == 0) s_wave[wave] = (uint32_t)__builtin_popcountll(m);
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+    for (uint32_t k = 0; k < 4; k++) { if (k < wave) before += s_wave[k]; total += s_wave[k]; }
+    *block_total = total;
+    return before + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+}
+
+// one thread per pair of the chunk: the best of its bands -> pair_records (n_windows = 0: none); block_count[g] = pairs with a record
+__global__ __launch_bounds__(256) void align_reduce_kernel(const AlignPair *__restrict__ pairs, const uint32_t *__restrict__ unit_offset,
+                                                           uint32_t n_pairs, uint32_t tol, const AlignBandRecord *__restrict__ band_records,
+                                                           vdf_alignment *__restrict__ pair_records, uint32_t *__restrict__ block_count)
+{
+    __shared__ uint32_t s_wave[4];
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    bool has = false;
+    if (p < n_pairs) {
+        uint32_t best_score = 0, best_start = 0, best_n = 0, best_sum = 0;
+        int32_t best_off = 0;
+        const uint32_t u1 = unit_offset[p + 1];
+        for (uint32_t u = unit_offset[p]; u < u1; ++u) {
+            const AlignBandRecord r = band_records[u];
+            if (r.n_windows == 0) continue;
+            const uint32_t score = r.n_windows * (tol + 1) - r.dist_sum;
+            if (align_better(score, r.offset, r.start_a, best_score, best_off, best_start)) {
+                best_score = score; best_off = r.offset; best_start = r.start_a; best_n = r.n_windows; best_sum = r.dist_sum;
+            }
+        }
+        has = best_score != 0;
+        const AlignPair ab = pairs[p];
+        pair_records[p] = vdf_alignment{ab.a, ab.b, best_off, best_start, has ? best_n : 0u, best_sum};
+    }
+    uint32_t total;
+    (void)align_block_rank(has, s_wave, &total);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+
+// exclusive scan of block_count[0 .. n) into block_offset, the sum to *total; one workgroup of 1024 threads
+__global__ __launch_bounds__(1024) void align_scan_kernel(const uint32_t *__restrict__ block_count, uint32_t n, uint32_t *__restrict__ block_offset,
+                                                          uint32_t *__restrict__ total)
+{
+    __shared__ uint32_t s_part[1024];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t per = (n + 1023) / 1024;
+    const uint32_t b = min(tid * per, n), e = min(b + per, n);
+    uint32_t sum = 0;
+    for (uint32_t i = b; i < e; i++) sum += block_count[i];
+    s_part[tid] = sum;
+    __syncthreads();
+    for (uint32_t o = 1; o < 1024; o <<= 1) {  // Hillis-Steele inclusive scan
+        const uint32_t v = (tid >= o) ? s_part[tid - o] : 0u;
+        __syncthreads();
+        s_part[tid] += v;
+        __syncthreads();
+    }
+    uint32_t run = s_part[tid] - sum;
+    for (uint32_t i = b; i < e; i++) { block_offset[i] = run; run += block_count[i]; }
+    if (tid == 1023) *total = s_part[1023];
+}
+
+__global__ __launch_bounds__(256) void align_scatter_kernel(const vdf_alignment *__restrict__ pair_records, uint32_t n_pairs,
+                                                            const uint32_t *__restrict__ block_offset, vdf_alignment *__restrict__ out)
+{
+    __shared__ uint32_t s_wave[4];
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    vdf_alignment r{};
+    if (p < n_pairs) r = pair_records[p];
+    const bool has = r.n_windows != 0;
+    uint32_t total;
+    const uint32_t rank = align_block_rank(has, s_wave, &total);
+    if (has) out[(size_t)block_offset[blockIdx.x] + rank] = r;
+}
+
+size_t align_scratch_bytes(size_t n_pairs, size_t n_units)
+{
+    const size_t n_blocks = (n_pairs + 255) / 256;
+    return n_units * sizeof(AlignBandRecord) + 2 * n_pairs * sizeof(vdf_alignment) + (2 * n_blocks + 4) * sizeof(uint32_t) + 64;
+}
+
+hipError_t launch_align_chunk(const AlignLaunch &L, hipStream_t stream)
+{
+    if (L.n_pairs == 0 || L.n_units == 0) return hipErrorInvalidValue;
+    // scratch: band records | pair records | dense records | block counts | block offsets | total
+    char *s = static_cast<char *>(L.scratch);
+    AlignBandRecord *band_records = reinterpret_cast<AlignBandRecord *>(s);
+    s += (size_t)L.n_units * sizeof(AlignBandRecord);
+    vdf_alignment *pair_records = reinterpret_cast<vdf_alignment *>(s);
+    s += (size_t)L.n_pairs * sizeof(vdf_alignment);
+    vdf_alignment *dense = reinterpret_cast<vdf_alignment *>(s);
+    s += (size_t)L.n_pairs * sizeof(vdf_alignment);
+    const uint32_t n_blocks = (L.n_pairs + 255) / 256;
+    uint32_t *block_count = reinterpret_cast<uint32_t *>(s), *block_offset = block_count + n_blocks, *total = block_offset + n_blocks;
+
+    const size_t n_groups = ((size_t)L.n_units + kAlignWaves - 1) / kAlignWaves;
+    for (const AlignLaunchCut &cut : align_launch_cuts(n_groups)) {
+        hipLaunchKernelGGL(align_bands_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_first, L.a_skip, L.b_hashes, L.b_first,
+                           L.b_skip, L.pairs, L.unit_offset, L.n_pairs, L.n_units, L.tol, L.min_run, band_records, (uint32_t)cut.group_base);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(align_reduce_kernel, dim3(n_blocks), dim3(256), 0, stream, L.pairs, L.unit_offset, L.n_pairs, L.tol, band_records, pair_records,
+                       block_count);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(align_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, n_blocks, block_offset, total);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(align_scatter_kernel, dim3(n_blocks), dim3(256), 0, stream, pair_records, L.n_pairs, block_offset, dense);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    *L.dense_out = dense;
+    *L.total_out = total;
+    return hipSuccess;
+}
+
+}  // namespace vdf

@@ -1,0 +1,121 @@
+// Alignment of videos on their window hashes (vdf_align_windows[_device]): which (video a, video b) pairs a call evaluates,
+// how a pair's distance matrix is cut into bands of 64 diagonals, which ka range a band walks, how the workgroups of a launch map to
+// (pair, band) units - and the lane-ownership rules of the band kernel (align.hip), as __host__ __device__ inline functions so that the
+// kernel and the CPU replay (tests/cpp/align_plan_main.cpp) share one text.  No HIP calls: api.cpp and the test program include it.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#if defined(__HIPCC__)
+#define VDF_ALIGN_HD __host__ __device__ inline
+#else
+#define VDF_ALIGN_HD inline
+#endif
+
+namespace vdf {
+
+constexpr uint32_t kAlignBand = 64;                      // diagonals per band = lanes of a wave
+constexpr uint32_t kAlignWaves = 4;                      // (pair, band) units per workgroup: one per wave
+constexpr uint32_t kAlignMaxWindows = 1u << 20;          // per video: score = n (tol + 1) - dist_sum <= 2^20 * 1025 < 2^31
+constexpr uint64_t kAlignMaxPairs = 1ull << 24;          // per call
+constexpr size_t kAlignMaxGroupsPerLaunch = size_t(1) << 23;  // x 256 threads stays under HIP's 2^32 work-item grid limit
+// A call is evaluated in chunks of consecutive pairs: a chunk closes once it holds this many pairs or units (it always takes one pair,
+// and one pair has at most 2^15 bands), which bounds the scratch of a call: 16 B per unit, 24 B + 24 B per pair.
+constexpr size_t kAlignChunkPairs = size_t(1) << 20;
+constexpr size_t kAlignChunkUnits = size_t(1) << 22;
+
+// ---- one pair: Na x Nb cells (ka, kb), diagonal d = kb - ka in [-(Na - 1), Nb - 1] -----------------------------------------------------------
+VDF_ALIGN_HD uint32_t align_bands(uint32_t Na, uint32_t Nb) { return (Na == 0 || Nb == 0) ? 0u : (Na + Nb - 1 + kAlignBand - 1) / kAlignBand; }
+// band j owns the diagonals d0 ... d0 + 63
+VDF_ALIGN_HD int32_t align_band_d0(uint32_t Na, uint32_t band) { return -(int32_t)(Na - 1) + (int32_t)(band * kAlignBand); }
+// the steps ka a band needs: every cell of its diagonals lies in [ka_begin, ka_end), and at both ends some diagonal has a cell
+VDF_ALIGN_HD uint32_t align_ka_begin(int32_t d0) { const int32_t d_hi = d0 + (int32_t)kAlignBand - 1; return d_hi < 0 ? (uint32_t)(-d_hi) : 0u; }
+VDF_ALIGN_HD uint32_t align_ka_end(uint32_t Na, uint32_t Nb, int32_t d0) { const int64_t e = (int64_t)Nb - d0; return e < (int64_t)Na ? (uint32_t)e : Na; }
+
+// ---- lane ownership inside a band (one wave) --------------------------------------------------------------------------------------------------
+// Row kb of B lives in lane kb mod 64 for as long as the band needs it (kb may be negative or >= Nb: a cell outside the matrix, never loaded).
+VDF_ALIGN_HD uint32_t align_row_lane(int32_t kb) { return (uint32_t)kb & (kAlignBand - 1); }
+// the row a lane holds at step ka: the one of ka + d0 ... ka + d0 + 63 that is congruent to the lane
+VDF_ALIGN_HD int32_t align_lane_row(uint32_t lane, uint32_t ka, int32_t d0)
+{
+    const int32_t base = (int32_t)ka + d0;
+    return base + (int32_t)((lane - (uint32_t)base) & (kAlignBand - 1));
+}
+// after step ka the row ka + d0 (diagonal d0) is done; its lane takes row ka + d0 + 64 (diagonal d0 + 63 of step ka + 1) - if there is a step ka + 1
+VDF_ALIGN_HD uint32_t align_reload_lane(uint32_t ka, int32_t d0) { return align_row_lane((int32_t)ka + d0); }
+VDF_ALIGN_HD int32_t align_reload_row(uint32_t ka, int32_t d0) { return (int32_t)ka + d0 + (int32_t)kAlignBand; }
+// the run state (length, dist_sum) of diagonal d is read and written at step ka by the lane of its cell's row; between two steps every
+// lane takes the state of the lane below it (lane 0 that of lane 63): the state follows its diagonal
+VDF_ALIGN_HD uint32_t align_state_lane(int32_t d, uint32_t ka) { return align_row_lane((int32_t)ka + d); }
+VDF_ALIGN_HD uint32_t align_rotate_source(uint32_t lane) { return (lane - 1) & (kAlignBand - 1); }
+
+// ---- ranking: the better of two runs (score = n (tol + 1) - dist_sum; 0 = no run) -----------------------------------------------------------
+VDF_ALIGN_HD bool align_better(uint32_t score, int32_t offset, uint32_t start_a, uint32_t best_score, int32_t best_offset, uint32_t best_start_a)
+{
+    if (score != best_score) return score > best_score;
+    if (offset != best_offset) return offset < best_offset;
+    return start_a < best_start_a;
+}
+
+// ---- the pairs of a call and their units ------------------------------------------------------------------------------------------------------
+struct AlignPair { uint32_t a, b; };
+// what a band leaves in scratch: its best run (n_windows = 0: none)
+struct AlignBandRecord { int32_t offset; uint32_t start_a, n_windows, dist_sum; };
+
+inline uint64_t align_pair_count(uint64_t n_a, uint64_t n_b, bool self) { return self ? n_a * (n_a - (n_a ? 1 : 0)) / 2 : n_a * n_b; }
+
+// Walks the pairs of a call in (a, b) order - all a x b, or a < b in self mode - and cuts them into chunks.
+struct AlignChunk {
+    std::vector<AlignPair> pairs;      // pairs with at least one band (a video of 0 windows pairs with nothing)
+    std::vector<uint32_t> unit_offset; // [pairs + 1]: pair i owns the units unit_offset[i] ... unit_offset[i + 1], one per band
+    size_t n_units() const { return unit_offset.empty() ? 0 : unit_offset.back(); }
+    size_t n_groups() const { return (n_units() + kAlignWaves - 1) / kAlignWaves; }
+};
+struct AlignCursor { uint64_t a = 0, b = 0; bool started = false; };
+
+// Fills `c` with the next chunk; false once the pairs are used up (c is then empty).  first_b = first_a, n_b = n_a in self mode.
+inline bool align_next_chunk(const uint32_t *first_a, size_t n_a, const uint32_t *first_b, size_t n_b, bool self, AlignCursor &cur, AlignChunk &c,
+                             size_t max_pairs = kAlignChunkPairs, size_t max_units = kAlignChunkUnits)
+{
+    c.pairs.clear();
+    c.unit_offset.assign(1, 0u);
+    if (!cur.started) { cur.started = true; cur.a = 0; cur.b = self ? 1 : 0; }
+    size_t units = 0;
+    while (cur.a < n_a) {
+        if (cur.b >= n_b) { cur.a++; cur.b = self ? cur.a + 1 : 0; continue; }
+        const uint32_t Na = first_a[cur.a + 1] - first_a[cur.a], Nb = first_b[cur.b + 1] - first_b[cur.b];
+        const uint32_t bands = align_bands(Na, Nb);
+        if (bands) {
+            if (!c.pairs.empty() && (c.pairs.size() >= max_pairs || units + bands > max_units)) return true;
+            c.pairs.push_back({(uint32_t)cur.a, (uint32_t)cur.b});
+            units += bands;
+            c.unit_offset.push_back((uint32_t)units);
+        }
+        cur.b++;
+    }
+    return !c.pairs.empty();
+}
+
+// unit -> pair of the chunk: the largest i with unit_offset[i] <= unit (the kernel makes the same search)
+template <class Ptr> VDF_ALIGN_HD uint32_t align_unit_pair(Ptr unit_offset, uint32_t n_pairs, uint32_t unit)
+{
+    uint32_t lo = 0, hi = n_pairs;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (unit_offset[mid] <= unit) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// launches of a chunk: [group_base, group_base + n) for every cut of at most kAlignMaxGroupsPerLaunch workgroups
+struct AlignLaunchCut { size_t group_base, n; };
+inline std::vector<AlignLaunchCut> align_launch_cuts(size_t n_groups, size_t max_groups = kAlignMaxGroupsPerLaunch)
+{
+    std::vector<AlignLaunchCut> cuts;
+    for (size_t g = 0; g < n_groups; g += max_groups) cuts.push_back({g, std::min(max_groups, n_groups - g)});
+    return cuts;
+}
+
+}  // namespace vdf

@@ -39,7 +39,7 @@ vdf_ctx::~vdf_ctx()
                      &hits, &perm, &matched, &exp_cols, &exp_rows, &pop_cols, &pop_rows, &cand, &group_cmin, &group_offset, &group_blocks, &up_hashes,
                      &up_dur, &up_ref_hashes, &up_ref_dur, &small, &frames, &frames2, &out_hashes, &out_hashes2, &out_dc,
                      &out_dc2, &cos_table, &crops, &crop_desc, &crop_tables, &crop_desc2, &crop_tables2, &crop_work, &sort_scratch, &sort_scratch_pub, &hits2, &hit_bitmaps, &bitmap_gather,
-                     &out_zero, &out_zero2, &up_zero, &variant_hashes};
+                     &out_zero, &out_zero2, &up_zero, &variant_hashes, &align_plan, &align_scratch, &align_up};
     for (DevBuf *b : all) b->release();
     for (PinBuf &b : pin) b.release();
     for (PinBuf &b : pin_out) b.release();
@@ -1629,6 +1629,99 @@ int search_refs_resident(vdf_ctx *ctx, size_t n_cand, const std::vector<size_t> 
     return rcg;
 }
 
+// ---- alignment of videos on their window hashes (include/vdf.h: vdf_align_windows[_device|_host]) -------------------------------
+// the argument checks all three forms share, in the order their messages are reported; first arrays on the host (null: not checked here)
+int align_checks(vdf_ctx *ctx, const void *a_hashes, const uint32_t *a_first, size_t n_a, const void *b_hashes, const uint32_t *b_first, size_t n_b,
+                 const void *a_first_ptr, const void *b_first_ptr, uint32_t min_run, const void *out, size_t capacity, const size_t *n_out)
+{
+    const bool self = b_hashes == nullptr;
+    if (!n_out || (n_a && (!a_hashes || !a_first_ptr)) || (!self && n_b && !b_first_ptr) || (capacity && !out)) return fail(ctx, VDF_E_INVAL, "null pointer");
+    if (min_run == 0) return fail(ctx, VDF_E_INVAL, "min_run of zero");
+    const uint32_t *firsts[2] = {a_first, self ? nullptr : b_first};
+    const size_t counts[2] = {n_a, n_b};
+    for (int side = 0; side < 2; side++)
+        for (size_t v = 0; firsts[side] && v < counts[side]; v++)
+            if (firsts[side][v + 1] >= firsts[side][v] && firsts[side][v + 1] - firsts[side][v] > vdf::kAlignMaxWindows)
+                return fail(ctx, VDF_E_INVAL, std::string("video ") + std::to_string(v) + (side ? " of B" : " of A") + " has more than 2^20 windows");
+    for (int side = 0; side < 2; side++)
+        for (size_t v = 0; firsts[side] && v < counts[side]; v++)
+            if (firsts[side][v + 1] < firsts[side][v])
+                return fail(ctx, VDF_E_INVAL, std::string("the first array") + (side ? " of B" : " of A") + " decreases at video " + std::to_string(v));
+    if (n_a > 0xFFFFFFFFull || n_b > 0xFFFFFFFFull || vdf::align_pair_count(n_a, self ? n_a : n_b, self) > vdf::kAlignMaxPairs)
+        return fail(ctx, VDF_E_INVAL, "more than 2^24 pairs of videos in one call");
+    return VDF_OK;
+}
+
+// the literal definition: every diagonal of the pair walked, XOR + popcount; *best.n_windows = 0: no competing run
+void align_pair_host(const uint64_t *A, uint32_t Na, const uint8_t *skip_a, const uint64_t *B, uint32_t Nb, const uint8_t *skip_b, uint32_t tol,
+                     uint32_t min_run, vdf_alignment *best)
+{
+    uint32_t best_score = 0;
+    best->offset = 0; best->start_a = 0; best->n_windows = 0; best->dist_sum = 0;
+    for (int64_t d = -((int64_t)Na - 1); d <= (int64_t)Nb - 1; d++) {
+        const int64_t ka0 = std::max<int64_t>(0, -d), ka1 = std::min<int64_t>(Na, (int64_t)Nb - d);
+        uint32_t len = 0, sum = 0;
+        for (int64_t ka = ka0; ka <= ka1; ka++) {  // ka1: the cell behind the diagonal's last, a miss
+            bool match = false;
+            uint32_t dist = 0;
+            if (ka < ka1 && !(skip_a && skip_a[ka]) && !(skip_b && skip_b[ka + d])) {
+                const uint64_t *x = A + 16 * ka, *y = B + 16 * (ka + d);
+                for (int w = 0; w < VDF_HASH_WORDS; w++) dist += (uint32_t)__builtin_popcountll(x[w] ^ y[w]);
+                match = dist <= tol;
+            }
+            if (match) { len++; sum += dist; continue; }
+            if (len >= min_run) {
+                const uint32_t score = len * (tol + 1) - sum, start = (uint32_t)(ka - len);
+                if (vdf::align_better(score, (int32_t)d, start, best_score, best->offset, best->start_a)) {
+                    best_score = score; best->offset = (int32_t)d; best->start_a = start; best->n_windows = len; best->dist_sum = sum;
+                }
+            }
+            len = 0; sum = 0;
+        }
+    }
+}
+
+// align_checks has passed on h_first_a / h_first_b (host copies of the device arrays); every array pointer is a device pointer
+int align_locked(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, const uint32_t *h_first_a, size_t n_a, const uint8_t *d_a_skip,
+                 const uint64_t *d_b_hashes, const uint32_t *d_b_first, const uint32_t *h_first_b, size_t n_b, const uint8_t *d_b_skip, bool self,
+                 uint32_t tol_int, uint32_t min_run, vdf_alignment *out, size_t capacity, size_t *n_out, hipStream_t s)
+{
+    vdf::AlignCursor cur;
+    vdf::AlignChunk ch;
+    size_t found = 0;
+    while (vdf::align_next_chunk(h_first_a, n_a, h_first_b, n_b, self, cur, ch)) {
+        const size_t n_pairs = ch.pairs.size(), n_units = ch.n_units();
+        const size_t pair_bytes = n_pairs * sizeof(vdf::AlignPair), off_bytes = (n_pairs + 1) * sizeof(uint32_t);
+        VDF_HIP(ctx, ctx->align_plan.reserve(pair_bytes + off_bytes));
+        VDF_HIP(ctx, ctx->align_scratch.reserve(vdf::align_scratch_bytes(n_pairs, n_units)));
+        char *plan = ctx->align_plan.as<char>();
+        VDF_HIP(ctx, hipMemcpyAsync(plan, ch.pairs.data(), pair_bytes, hipMemcpyHostToDevice, s));
+        VDF_HIP(ctx, hipMemcpyAsync(plan + pair_bytes, ch.unit_offset.data(), off_bytes, hipMemcpyHostToDevice, s));
+        vdf_alignment *d_dense = nullptr;
+        uint32_t *d_total = nullptr;
+        vdf::AlignLaunch L{};
+        L.a_hashes = reinterpret_cast<const uint32_t *>(d_a_hashes); L.a_first = d_a_first; L.a_skip = d_a_skip;
+        L.b_hashes = reinterpret_cast<const uint32_t *>(d_b_hashes); L.b_first = d_b_first; L.b_skip = d_b_skip;
+        L.pairs = reinterpret_cast<const vdf::AlignPair *>(plan);
+        L.unit_offset = reinterpret_cast<const uint32_t *>(plan + pair_bytes);
+        L.n_pairs = (uint32_t)n_pairs; L.n_units = (uint32_t)n_units;
+        L.tol = std::min<uint32_t>(tol_int, 1024u); L.min_run = min_run;
+        L.scratch = ctx->align_scratch.p; L.dense_out = &d_dense; L.total_out = &d_total;
+        VDF_HIP(ctx, vdf::launch_align_chunk(L, s));
+        uint32_t total = 0;
+        VDF_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, s));
+        VDF_HIP(ctx, hipStreamSynchronize(s));  // also: the chunk's plan arrays are free to change
+        const size_t room = capacity > found ? capacity - found : 0, take = std::min<size_t>(total, room);
+        if (take) {
+            VDF_HIP(ctx, hipMemcpyAsync(out + found, d_dense, take * sizeof(vdf_alignment), hipMemcpyDeviceToHost, s));
+            VDF_HIP(ctx, hipStreamSynchronize(s));
+        }
+        found += total;
+    }
+    *n_out = found;
+    return VDF_OK;
+}
+
 }  // namespace vdf_impl
 
 using namespace vdf_impl;
@@ -1747,6 +1840,94 @@ int vdf_hash_frames_u8_letterbox(vdf_ctx *ctx, const uint8_t *frames, size_t n_c
 {
     return hash_host_entry(ctx, frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, 1, out_hashes, out_crops,
                            out_dontcare);
+}
+
+int vdf_align_windows_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                           const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, uint32_t tol_int, uint32_t min_run, vdf_alignment *out,
+                           size_t capacity, size_t *n_out)
+{
+    if (int rc = align_checks(nullptr, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, min_run, out, capacity, n_out)) return rc;
+    const bool self = b_hashes == nullptr;
+    if (self) { b_hashes = a_hashes; b_first = a_first; n_b = n_a; b_skip = a_skip; }
+    const uint32_t tol = std::min<uint32_t>(tol_int, 1024u);
+    size_t found = 0;
+    for (size_t a = 0; a < n_a; a++)
+        for (size_t b = self ? a + 1 : 0; b < n_b; b++) {
+            vdf_alignment r;
+            align_pair_host(a_hashes + 16 * (size_t)a_first[a], a_first[a + 1] - a_first[a], a_skip ? a_skip + a_first[a] : nullptr,
+                            b_hashes + 16 * (size_t)b_first[b], b_first[b + 1] - b_first[b], b_skip ? b_skip + b_first[b] : nullptr, tol, min_run, &r);
+            if (r.n_windows == 0) continue;
+            r.a = (uint32_t)a; r.b = (uint32_t)b;
+            if (found < capacity) out[found] = r;
+            found++;
+        }
+    *n_out = found;
+    return VDF_OK;
+}
+
+int vdf_align_windows_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a, const uint8_t *d_a_skip,
+                             const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip, uint32_t tol_int,
+                             uint32_t min_run, vdf_alignment *out, size_t capacity, size_t *n_out, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    // everything that can be said without the first arrays; then they come down, are checked, and plan the launch
+    if (int rc = align_checks(ctx, d_a_hashes, nullptr, n_a, d_b_hashes, nullptr, n_b, d_a_first, d_b_first, min_run, out, capacity, n_out)) return rc;
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_align_windows_device takes a single-device context");
+    const bool self = d_b_hashes == nullptr;
+    *n_out = 0;
+    if (n_a == 0 || (self ? n_a < 2 : n_b == 0)) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<uint32_t> fa(n_a + 1), fb(self ? 0 : n_b + 1);
+    VDF_HIP(ctx, hipMemcpyAsync(fa.data(), d_a_first, fa.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (!self) VDF_HIP(ctx, hipMemcpyAsync(fb.data(), d_b_first, fb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));
+    if (int rc = align_checks(ctx, d_a_hashes, fa.data(), n_a, d_b_hashes, self ? nullptr : fb.data(), n_b, d_a_first, d_b_first, min_run, out, capacity, n_out))
+        return rc;
+    if (self) return align_locked(ctx, d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, true, tol_int, min_run,
+                                  out, capacity, n_out, s);
+    return align_locked(ctx, d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, d_b_hashes, d_b_first, fb.data(), n_b, d_b_skip, false, tol_int, min_run, out,
+                        capacity, n_out, s);
+}
+
+// Host arrays: hashes, first and skip arrays go up through the context's staging buffers, the device form's core runs on them.
+int vdf_align_windows(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                      const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, uint32_t tol_int, uint32_t min_run, vdf_alignment *out, size_t capacity,
+                      size_t *n_out)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (int rc = align_checks(ctx, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, min_run, out, capacity, n_out)) return rc;
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_align_windows takes a single-device context");
+    const bool self = b_hashes == nullptr;
+    *n_out = 0;
+    if (n_a == 0 || (self ? n_a < 2 : n_b == 0)) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t wa = a_first[n_a] - a_first[0], wb = self ? 0 : b_first[n_b] - b_first[0];
+    // first arrays rebased to the uploaded windows; [first a | first b | skip a | skip b] in one buffer
+    std::vector<uint32_t> fa(n_a + 1), fb(self ? 0 : n_b + 1);
+    for (size_t v = 0; v <= n_a; v++) fa[v] = a_first[v] - a_first[0];
+    for (size_t v = 0; v < fb.size(); v++) fb[v] = b_first[v] - b_first[0];
+    const size_t fa_bytes = fa.size() * sizeof(uint32_t), fb_bytes = fb.size() * sizeof(uint32_t);
+    const size_t ska = a_skip ? wa : 0, skb = (!self && b_skip) ? wb : 0;
+    VDF_HIP(ctx, ctx->align_up.reserve(fa_bytes + fb_bytes + ska + skb + 16));
+    char *up = ctx->align_up.as<char>();
+    VDF_HIP(ctx, hipMemcpyAsync(up, fa.data(), fa_bytes, hipMemcpyHostToDevice, s));
+    if (fb_bytes) VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes, fb.data(), fb_bytes, hipMemcpyHostToDevice, s));
+    if (ska) VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes + fb_bytes, a_skip + a_first[0], ska, hipMemcpyHostToDevice, s));
+    if (skb) VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes + fb_bytes + ska, b_skip + b_first[0], skb, hipMemcpyHostToDevice, s));
+    if (int rc = upload(ctx, ctx->up_hashes, a_hashes + 16 * (size_t)a_first[0], wa * 16 * sizeof(uint64_t), s)) return rc;
+    if (!self)
+        if (int rc = upload(ctx, ctx->up_ref_hashes, b_hashes + 16 * (size_t)b_first[0], wb * 16 * sizeof(uint64_t), s)) return rc;
+    const uint32_t *d_fa = reinterpret_cast<const uint32_t *>(up), *d_fb = reinterpret_cast<const uint32_t *>(up + fa_bytes);
+    const uint8_t *d_ska = ska ? reinterpret_cast<const uint8_t *>(up + fa_bytes + fb_bytes) : nullptr;
+    const uint8_t *d_skb = skb ? reinterpret_cast<const uint8_t *>(up + fa_bytes + fb_bytes + ska) : nullptr;
+    if (self) return align_locked(ctx, ctx->up_hashes.as<uint64_t>(), d_fa, fa.data(), n_a, d_ska, ctx->up_hashes.as<uint64_t>(), d_fa, fa.data(), n_a, d_ska,
+                                  true, tol_int, min_run, out, capacity, n_out, s);
+    return align_locked(ctx, ctx->up_hashes.as<uint64_t>(), d_fa, fa.data(), n_a, d_ska, ctx->up_ref_hashes.as<uint64_t>(), d_fb, fb.data(), n_b, d_skb, false,
+                        tol_int, min_run, out, capacity, n_out, s);
 }
 
 size_t vdf_hash_window_count(uint32_t frames_per_clip, uint32_t window_stride) { return vdf::window_count(frames_per_clip, window_stride); }

@@ -8,6 +8,7 @@
 #include "hash_variant.h"
 #include "resize_dispatch.h"
 #include "windows_plan.h"
+#include "align_plan.h"
 
 namespace vdf {
 
@@ -242,5 +243,24 @@ struct WindowsFrames {
 // out_hashes[16 (c n_win + k)] = the hash of frames [k stride, k stride + 16) of clip c; out_dontcare (nullable) at c n_win + k
 hipError_t launch_dct_hash_windows(const WindowsFrames &f, size_t n_clips, const WindowsPlan &plan, const double *cos_table, uint64_t *out_hashes,
                                    uint32_t *out_dontcare, hipStream_t stream);
+// ---- alignment of videos on their window hashes (align_plan.h, align.hip) ---------------------------------------------------
+// One chunk of pairs (align_plan.h: align_next_chunk): band kernel, per-pair reduction, dense list in (a, b) order.  All pointers are device
+// pointers; scratch holds align_scratch_bytes(n_pairs, n_units).  *dense_out / *total_out: where in scratch the records and their number are
+// once the stream has run.
+struct AlignLaunch {
+    const uint32_t *a_hashes, *a_first;  // [windows][32] dwords, [videos + 1]
+    const uint8_t *a_skip;               // nullable, per window
+    const uint32_t *b_hashes, *b_first;
+    const uint8_t *b_skip;
+    const AlignPair *pairs;
+    const uint32_t *unit_offset;         // [n_pairs + 1]
+    uint32_t n_pairs, n_units;
+    uint32_t tol, min_run;
+    void *scratch;
+    vdf_alignment **dense_out;
+    uint32_t **total_out;
+};
+size_t align_scratch_bytes(size_t n_pairs, size_t n_units);
+hipError_t launch_align_chunk(const AlignLaunch &L, hipStream_t stream);
 
 }  // namespace vdf

@@ -62,6 +62,61 @@ def _window_stride(stride) -> int:
     return s
 
 
+# one record of the align calls (include/vdf.h: vdf_alignment, 24 bytes)
+ALIGN_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("offset", "<i4"), ("start_a", "<u4"), ("n_windows", "<u4"), ("dist_sum", "<u4")])
+
+
+def _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip):
+    """The host arrays of an align call as the C ABI takes them; b_hashes None = self mode.  Returns the arrays (to keep alive) and
+    (a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip) as ctypes arguments."""
+    def side(hashes, first, skip):
+        h = np.ascontiguousarray(hashes, dtype=np.uint64).reshape(-1, HASH_WORDS)
+        f = np.ascontiguousarray(first, dtype=np.uint32).reshape(-1)
+        if f.size == 0:
+            raise ValueError("a first array has n_videos + 1 entries")
+        if int(f.max()) > h.shape[0]:
+            raise ValueError("a first array points behind its hashes")
+        k = None
+        if skip is not None:
+            k = np.ascontiguousarray(skip, dtype=np.uint8).reshape(-1)
+            if k.size != h.shape[0]:
+                raise ValueError("one skip byte per window")
+        return h, f, k
+    ah, af, ak = side(a_hashes, a_first, a_skip)
+    keep = [ah, af, ak]
+    args = [ah.ctypes.data, af.ctypes.data, af.size - 1, ak.ctypes.data if ak is not None else None]
+    if b_hashes is None:
+        args += [None, None, 0, None]
+    else:
+        bh, bf, bk = side(b_hashes, b_first, b_skip)
+        keep += [bh, bf, bk]
+        # an empty B must not read as self mode (a NULL b_hashes): numpy gives an empty array a non-null address
+        args += [bh.ctypes.data or af.ctypes.data, bf.ctypes.data, bf.size - 1, bk.ctypes.data if bk is not None else None]
+    return keep, args
+
+
+def _align_uint32(name: str, v) -> int:
+    i = int(v)
+    if i != v or not 0 <= i < 2**32:
+        raise ValueError(f"{name} must be an integer in 0 .. 2^32 - 1, not {v!r}")
+    return i
+
+
+def align_windows_host(a_hashes, a_first, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1, a_skip=None, b_skip=None,
+                       capacity: int = 1024):
+    """vdf_align_windows_host: the definition of the align calls in plain C++ on the CPU (no context, no GPU) - for tiny inputs and tests.
+    -> (records [min(found, capacity)] of ALIGN_DTYPE in (a, b) order, found); found > capacity: call again with a larger capacity."""
+    lib = _capi.load()
+    keep, args = _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+    out = np.zeros(max(int(capacity), 0), ALIGN_DTYPE)
+    n = C.c_size_t(0)
+    rc = lib.vdf_align_windows_host(*args, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run), out.ctypes.data if out.size else None,
+                                    out.size, C.byref(n))
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_align_windows_host: bad argument")
+    return out[:min(n.value, out.size)], int(n.value)
+
+
 class Engine:
     """One context: one GPU (`device`, default LOCAL_RANK or 0), or - `devices=[...]` - ONE context over several GPUs
     of the node (vdf_ctx_create_multi: the host-array calls fan out inside the library, the *_shards methods take
@@ -227,6 +282,31 @@ class Engine:
         cs = fs * frames_per_clip if clip_stride is None else clip_stride
         self._check(self.lib.vdf_hash_windows_u8_device(self.ctx, d_frames, n_clips, frames_per_clip, w, h, fs, cs, stride, d_out,
                                                         d_dontcare or None, stream or None))
+
+    # --------------------------------------------- videos aligned on their window hashes (include/vdf.h)
+    def align_windows(self, a_hashes, a_first, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1, a_skip=None, b_skip=None,
+                      capacity: int = 1024):
+        """The longest shared stretch of every pair of videos (vdf_align_windows).  a_hashes [windows, 16] u64 = the window hashes of the
+        videos one after the other, a_first [videos + 1] u32; b_hashes None: self mode, the pairs a < b of A.  skip: one byte per window,
+        non-zero = the window abstains.  -> (records [min(found, capacity)] of ALIGN_DTYPE in (a, b) order, found); found > capacity: call
+        again with a larger capacity."""
+        keep, args = _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+        out = np.zeros(max(int(capacity), 0), ALIGN_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows(self.ctx, *args, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                               out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_device(self, d_a_hashes: int, d_a_first: int, n_a: int, d_b_hashes: int = 0, d_b_first: int = 0, n_b: int = 0,
+                             tol_int: int = 350, min_run: int = 1, d_a_skip: int = 0, d_b_skip: int = 0, capacity: int = 1024, stream: int = 0):
+        """The same on device arrays (d_b_hashes 0: self mode); the records come back to the host, the call waits for its own work."""
+        out = np.zeros(max(int(capacity), 0), ALIGN_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_device(self.ctx, d_a_hashes or None, d_a_first or None, int(n_a), d_a_skip or None, d_b_hashes or None,
+                                                      d_b_first or None, int(n_b), d_b_skip or None, _align_uint32("tol_int", tol_int),
+                                                      _align_uint32("min_run", min_run), out.ctypes.data if out.size else None, out.size, C.byref(n),
+                                                      stream or None))
+        return out[:min(n.value, out.size)], int(n.value)
 
     # --------------------------------------------- the zero plane and the flipped hashes (include/vdf.h, DESIGN.md 4.8)
     def hash_frames_planes(self, frames: np.ndarray, want_dontcare: bool = False):

@@ -257,6 +257,51 @@ public:
         if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
     }
 
+    // Which videos share a stretch, at what offset, for how long (vdf_align_windows): windows_a / windows_b = hash_windows'
+    // results (videos may differ in length); windows_b null: the videos of windows_a against each other, every pair a < b once.  At most one
+    // record per pair of videos, in (a, b) order: the best run of consecutive windows within tol_int on one diagonal (offset = kb - ka), of at
+    // least min_run windows.  skip_a / skip_b (optional): one byte per window in the order of the lists, non-zero = the window abstains
+    // (static stretches).  One call of the C ABI: at most 2^24 pairs of videos.  ctx_opt null and a tiny input: walked on the CPU
+    // (vdf_align_windows_host, the definition in plain C++).
+    static std::vector<vdf_alignment> align_windows(const std::vector<std::vector<VideoHash>> &windows_a, const std::vector<std::vector<VideoHash>> *windows_b,
+                                                    uint32_t tol_int, uint32_t min_run = 1, const std::vector<uint8_t> *skip_a = nullptr,
+                                                    const std::vector<uint8_t> *skip_b = nullptr, Context *ctx_opt = nullptr)
+    {
+        auto csr = [](const std::vector<std::vector<VideoHash>> &w, std::vector<uint64_t> &words, std::vector<uint32_t> &first) {
+            first.assign(1, 0u);
+            for (const auto &video : w) {
+                for (const VideoHash &h : video) words.insert(words.end(), h.words().begin(), h.words().end());
+                first.push_back((uint32_t)(words.size() / VDF_HASH_WORDS));
+            }
+            if (words.empty()) words.push_back(0);  // a non-null pointer for an empty side
+        };
+        std::vector<uint64_t> wa, wb;
+        std::vector<uint32_t> fa, fb;
+        csr(windows_a, wa, fa);
+        if (windows_b) csr(*windows_b, wb, fb);
+        if (skip_a && skip_a->size() != fa.back()) throw std::invalid_argument("one skip byte per window of A");
+        if (windows_b && skip_b && skip_b->size() != fb.back()) throw std::invalid_argument("one skip byte per window of B");
+        const uint8_t *ska = skip_a && !skip_a->empty() ? skip_a->data() : nullptr, *skb = windows_b && skip_b && !skip_b->empty() ? skip_b->data() : nullptr;
+        const size_t n_a = windows_a.size(), n_b = windows_b ? windows_b->size() : 0;
+        const uint64_t cells = (uint64_t)fa.back() * (windows_b ? fb.back() : fa.back());
+        std::vector<vdf_alignment> out(1024);
+        for (;;) {
+            size_t found = 0;
+            int rc;
+            if (!ctx_opt && cells <= (1u << 16))
+                rc = vdf_align_windows_host(wa.data(), fa.data(), n_a, ska, windows_b ? wb.data() : nullptr, fb.data(), n_b, skb, tol_int, min_run, out.data(), out.size(), &found);
+            else {
+                Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+                rc = vdf_align_windows(ctx.get(), wa.data(), fa.data(), n_a, ska, windows_b ? wb.data() : nullptr, fb.data(), n_b, skb, tol_int, min_run, out.data(),
+                                       out.size(), &found);
+                if (rc != VDF_OK && rc != VDF_E_INVAL) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            }
+            if (rc != VDF_OK) throw std::invalid_argument("align_windows: min_run of 0, a video of more than 2^20 windows, more than 2^24 pairs, or a multi-GPU context");
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
     // from_frame_stacks with the zero planes (vdf_hash_clips_u8_planes): the hashes are the same words and can be flipped.  crops (optional, one
     // l, r, t, b per clip - e.g. what from_frame_stacks_letterbox detected): hash, plane and every flip are those of the CROPPED clip.
     static std::vector<VideoHash> from_frame_stacks_planes(const std::vector<FrameStack> &stacks, const std::vector<std::array<uint32_t, 4>> *crops = nullptr,
