@@ -218,7 +218,12 @@ int vdf_hash_frames_u8_letterbox(vdf_ctx *ctx, const uint8_t *frames, size_t n_c
  * frame_stride < w*h -> VDF_E_INVAL; window_stride == 0 -> VDF_E_INVAL; n_clips * n_win >= 2^32 -> VDF_E_INVAL;
  * (n_clips == 0: VDF_OK, nothing is launched;) a null pointer -> VDF_E_INVAL; a multi-GPU context -> VDF_E_INVAL.
  * The host form uploads the frames in one piece and calls the device form (no pipelining over the link).
- * Not here: zero planes of window hashes (flips of windows), letterbox boxes and mixed frame sizes. */
+ * The _planes forms are these calls plus out_zero (required; n_clips x n_win x 16 words, window k of clip c at 16 (c n_win + k)): the ZERO PLANE
+ * of every window, as the planes calls below define it - bit i set iff coefficient i == 0.0, bits 1000 ... 1023 are 0, H & Z == 0.  Same
+ * checks in the same order (a null out_zero is among the null pointers), then an axis size whose resize table is not its own mirror image ->
+ * VDF_E_BAD_DIMS, and a multi-GPU context last -> VDF_E_INVAL.  Same resize runs and routes; out_hashes and out_dontcare are bit-identical to
+ * the plain calls'.  With the planes, vdf_window_variants_* and vdf_align_windows_variants* see flipped and reversed stretches.
+ * Not here: zero planes of window hashes from the two plain calls (the _planes forms write them), letterbox boxes and mixed frame sizes. */
 size_t vdf_hash_window_count(uint32_t frames_per_clip, uint32_t window_stride); /* 0 if frames_per_clip < 16 or window_stride == 0 */
 int vdf_hash_windows_u8(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w,
                         uint32_t h, size_t frame_stride, size_t clip_stride, uint32_t window_stride, uint64_t *out_hashes,
@@ -226,6 +231,12 @@ int vdf_hash_windows_u8(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uin
 int vdf_hash_windows_u8_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip,
                                uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride, uint32_t window_stride,
                                uint64_t *d_out_hashes, uint32_t *d_out_dontcare, void *stream);
+int vdf_hash_windows_u8_planes(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w,
+                               uint32_t h, size_t frame_stride, size_t clip_stride, uint32_t window_stride, uint64_t *out_hashes,
+                               uint32_t *out_dontcare, uint64_t *out_zero);
+int vdf_hash_windows_u8_planes_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip,
+                                      uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride, uint32_t window_stride,
+                                      uint64_t *d_out_hashes, uint32_t *d_out_dontcare, uint64_t *d_out_zero, void *stream);
 
 /* ---- align videos on their window hashes: the longest shared stretch of every pair of videos -------------
  * Which videos share a stretch, at what offset, and for how long.  Two sets of videos, A and B, each the
@@ -256,7 +267,7 @@ int vdf_hash_windows_u8_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_c
  * vdf_align_windows_host: no context, no GPU - the definition above in plain C++ (every diagonal walked, XOR + popcount):
  * the CPU-tested statement of the semantics, for tiny inputs and tests.
  * Known limit: ONE stretch per pair - a video that holds two separate excerpts of another reports the better one.
- * Not here: flipped or reversed stretches, multi-GPU contexts. */
+ * Flipped and reversed stretches: vdf_align_windows_variants* below.  Not here: multi-GPU contexts. */
 typedef struct vdf_alignment { /* 24 bytes */
     uint32_t a;                /* video index in A */
     uint32_t b;                /* video index in B (self mode: in A, a < b) */
@@ -275,6 +286,63 @@ int vdf_align_windows_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uin
                              const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b,
                              const uint8_t *d_b_skip, uint32_t tol_int, uint32_t min_run, vdf_alignment *out,
                              size_t capacity, size_t *n_out, void *stream);
+
+/* ---- mirrored, flipped and reversed STRETCHES: window hashes with their zero planes -----------------------
+ * A mirrored re-upload with its intro trimmed: the variant search sees only frames 0 ... 15 of a file, the align calls only unflipped
+ * stretches.  With the zero plane of every window (vdf_hash_windows_u8_planes*) the window hashes of the flipped video follow from the
+ * video's own, by the rule of the planes calls below (H_v = (H ^ M_v) & ~Z; variant bit 0 = mirror along W, bit 1 = flip along H, bit 2 =
+ * reverse the frames).
+ *
+ * vdf_window_variants_*: the variant of a SET of window hashes.  hashes / zero: [windows][16], first[n_videos + 1], video v owning the rows
+ * first[v] ... first[v + 1] (N of them; 0 is legal); rows outside [first[0], first[n_videos]) are neither read nor written.  Output row
+ * first[v] + j = (H[i] ^ M_variant) & ~Z[i] with i = first[v] + j without bit 2 and i = first[v] + N - 1 - j with it; the skip byte
+ * (skip nullable; out_skip is null iff skip is) is carried along the same way.  Without bit 2 the rows are the window hashes of the flipped
+ * video, word for word.  With bit 2 they are the window hashes of the REVERSED video: exactly so when (F - 16) % window_stride == 0 for its F
+ * frames, otherwise those of the reversed video with its first (F - 16) % window_stride frames dropped - still a reversed stretch, on the
+ * window grid of the original.
+ * Errors, in this order, all VDF_E_INVAL: variant outside 1 ... 7; (n_videos == 0: VDF_OK;) a null required pointer, or exactly one of skip /
+ * out_skip; an output that is one of the inputs; a first array that decreases; (device form) a multi-GPU context.  The device form reads the
+ * first array back to check it and size its launch; the rows are ordered on `stream`.  The host form takes no context. */
+int vdf_window_variants_host(const uint64_t *hashes, const uint64_t *zero, const uint32_t *first, size_t n_videos, const uint8_t *skip,
+                             uint32_t variant, uint64_t *out_hashes, uint8_t *out_skip);
+int vdf_window_variants_device(vdf_ctx *ctx, const uint64_t *d_hashes, const uint64_t *d_zero, const uint32_t *d_first, size_t n_videos,
+                               const uint8_t *d_skip, uint32_t variant, uint64_t *d_out_hashes, uint8_t *d_out_skip, void *stream);
+/* vdf_align_windows against the variants of B: for every variant v whose bit is set in variant_mask (bits 1 ... 7), in ascending order, the
+ * variant-v set of B is derived (vdf_window_variants_*) and A is aligned against it - the semantics of vdf_align_windows word for word (cell
+ * rule, run, score, ties, min_run, skip, the tol clamp, 2^20 windows per video, 2^24 pairs per call), with B's rows replaced by the derived
+ * rows.  So offset and start_a + offset index the DERIVED order of b: with bit 2 of v set, derived window j is original window
+ * kb = Nb - 1 - j, and the stretch runs backwards through b.
+ * A: hashes, first, skip.  B: hashes, ZERO (b_zero, required), first, skip.  b_hashes == NULL is SELF mode: B = A with a_zero as its zero
+ * plane (required then, ignored otherwise); only the pairs a < b are evaluated, so a video is never aligned with its own mirror, as
+ * vdf_search_variants drops (r, r).
+ * out: HOST buffer of `capacity` records ordered by (variant, a, b), at most one per (variant, pair).  *n_out = the number found over all
+ * variants; if it exceeds capacity the first `capacity` records in that order are valid - VDF_OK, as the align calls.
+ * Errors: those of vdf_align_windows in their order; then variant_mask with bit 0 or a bit above 7; then a missing zero plane; then a
+ * multi-GPU context - all VDF_E_INVAL.
+ * Where coefficients are exactly zero d(a, v(b)) and d(v(a), b) can differ: the zero plane of b clears bits of v(b) that a may have set.  So
+ * near the tolerance a stretch may be found with B flipped and not with the sides swapped (the asymmetry of vdf_search_variants). */
+typedef struct vdf_alignment_variant { /* 28 bytes */
+    uint32_t a;                /* the six fields of vdf_alignment; offset and start_a + offset count in the DERIVED order of b */
+    uint32_t b;
+    int32_t offset;
+    uint32_t start_a;
+    uint32_t n_windows;
+    uint32_t dist_sum;
+    uint32_t variant;          /* 1 ... 7 */
+} vdf_alignment_variant;
+int vdf_align_windows_variants_host(const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first, size_t n_a,
+                                    const uint8_t *a_skip, const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first,
+                                    size_t n_b, const uint8_t *b_skip, uint32_t tol_int, uint32_t min_run, uint32_t variant_mask,
+                                    vdf_alignment_variant *out, size_t capacity, size_t *n_out);
+int vdf_align_windows_variants(vdf_ctx *ctx, const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first, size_t n_a,
+                               const uint8_t *a_skip, const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first,
+                               size_t n_b, const uint8_t *b_skip, uint32_t tol_int, uint32_t min_run, uint32_t variant_mask,
+                               vdf_alignment_variant *out, size_t capacity, size_t *n_out);
+int vdf_align_windows_variants_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint64_t *d_a_zero, const uint32_t *d_a_first,
+                                      size_t n_a, const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint64_t *d_b_zero,
+                                      const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip, uint32_t tol_int,
+                                      uint32_t min_run, uint32_t variant_mask, vdf_alignment_variant *out, size_t capacity,
+                                      size_t *n_out, void *stream);
 
 /* ---- clips of DIFFERENT frame sizes in one call ----------------------------------------------------
  * A library holds dozens of resolutions and its files arrive in any order.  All clips of a call live in ONE

@@ -17,7 +17,14 @@ clock around calls that end in a device synchronise:
            the answer is reported as not available
 The records of both legs must be equal wherever the parent leg has an answer.  The one claim under test: the align call's time on the
 static corpus is that of the plain corpus within the run-to-run spread of the 12 calls.  cells/s is printed beside the VALU search
-backend's measured 7.5e11 pairs/s (README): the yardstick of this inner loop, not a gate."""
+backend's measured 7.5e11 pairs/s (README): the yardstick of this inner loop, not a gate.
+
+    python tools/bench_align.py --variants [--out profiles/align_variants.txt]
+
+What alignment against the variants costs, on the 1000 x 49 self shape, plain corpus, with random zero planes (5 % of the
+bits): vdf_align_windows_variants_device with 1 and with 3 variants beside ONE vdf_align_windows_device call and one
+vdf_window_variants_device call, all of this build, same protocol.  Expected: plain x variants + derive x variants.  Reported; nothing is
+gated."""
 import argparse
 import ctypes as C
 import json
@@ -189,8 +196,100 @@ def child(args):
     print("RESULT " + json.dumps(res))
 
 
-def run_child(lib, leg):
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--lib", lib, "--leg", leg], capture_output=True, text=True, timeout=900)
+VARIANTS_SHAPE = "1000x49 self"
+VARIANT_MASKS = {"variants-1": 1 << 1, "variants-3": (1 << 1) | (1 << 4) | (1 << 5)}
+ALIGN_VARIANT_DTYPE = np.dtype(ALIGN_DTYPE.descr + [("variant", "<u4")])
+
+
+def variants_child(args):
+    """one leg of --variants: align | derive | variants-1 | variants-3"""
+    import torch
+
+    lib = C.CDLL(args.lib)
+    lib.vdf_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    lib.vdf_last_error.restype = C.c_char_p
+    lib.vdf_last_error.argtypes = [C.c_void_p]
+    ctx = C.c_void_p()
+    assert lib.vdf_ctx_create(0, C.byref(ctx)) == 0, lib.vdf_last_error(None)
+    P = C.c_void_p
+    lib.vdf_align_windows_device.argtypes = [P, P, P, C.c_size_t, P, P, P, C.c_size_t, P, C.c_uint32, C.c_uint32, P, C.c_size_t, C.POINTER(C.c_size_t), P]
+    lib.vdf_window_variants_device.argtypes = [P, P, P, P, C.c_size_t, P, C.c_uint32, P, P, P]
+    lib.vdf_align_windows_variants_device.argtypes = [P, P, P, P, C.c_size_t, P, P, P, P, C.c_size_t, P, C.c_uint32, C.c_uint32, C.c_uint32, P, C.c_size_t,
+                                                      C.POINTER(C.c_size_t), P]
+    n_a, n_win, _ = SHAPES[VARIANTS_SHAPE]
+    pairs = n_a * (n_a - 1) // 2
+    a, fa, _, _, _, _ = corpus(VARIANTS_SHAPE, False)
+    rng = np.random.default_rng(12)
+    zero = np.zeros_like(a)
+    for pos in range(1000):
+        zero[rng.random(len(a)) < 0.05, pos >> 6] |= np.uint64(1) << np.uint64(pos & 63)
+    a &= ~zero
+    d_a, d_z, d_fa = (torch.from_numpy(x.view(t)).cuda() for x, t in ((a, np.int64), (zero, np.int64), (fa, np.int32)))
+    d_out = torch.zeros_like(d_a)
+    torch.cuda.synchronize()
+    n_out = C.c_size_t(0)
+    if args.leg == "align":
+        out = np.zeros(pairs, ALIGN_DTYPE)
+
+        def run():
+            return lib.vdf_align_windows_device(ctx, d_a.data_ptr(), d_fa.data_ptr(), n_a, None, None, None, 0, None, TOL, MIN_RUN, out.ctypes.data, pairs, C.byref(n_out), None)
+    elif args.leg == "derive":
+        out = np.zeros(0, ALIGN_DTYPE)
+
+        def run():
+            rc = lib.vdf_window_variants_device(ctx, d_a.data_ptr(), d_z.data_ptr(), d_fa.data_ptr(), n_a, None, 5, d_out.data_ptr(), None, None)
+            torch.cuda.synchronize()
+            return rc
+    else:
+        mask = VARIANT_MASKS[args.leg]
+        out = np.zeros(pairs * bin(mask).count("1"), ALIGN_VARIANT_DTYPE)
+
+        def run():
+            return lib.vdf_align_windows_variants_device(ctx, d_a.data_ptr(), d_z.data_ptr(), d_fa.data_ptr(), n_a, None, None, None, None, 0, None, TOL, MIN_RUN, mask,
+                                                         out.ctypes.data, len(out), C.byref(n_out), None)
+    times = []
+    for r in range(REPEATS + 1):
+        t0 = time.perf_counter()
+        rc = run()
+        if r:
+            times.append(time.perf_counter() - t0)
+        assert rc == 0, (rc, lib.vdf_last_error(ctx))
+    print("RESULT " + json.dumps({"times": times, "records": int(n_out.value)}))
+
+
+def variants_main(args):
+    legs = ["align", "derive"] + list(VARIANT_MASKS)
+    got = {leg: {"times": []} for leg in legs}
+    for _ in range(ROUNDS):
+        for leg in legs:
+            v = run_child(args.lib, leg, variants=True)
+            got[leg]["times"] += v["times"]
+            got[leg]["records"] = v["records"]
+    n_a, n_win, _ = SHAPES[VARIANTS_SHAPE]
+    pairs = n_a * (n_a - 1) // 2
+    med = {leg: statistics.median(got[leg]["times"]) for leg in legs}
+    ms = lambda ts: f"min {min(ts) * 1e3:9.3f}  median {statistics.median(ts) * 1e3:9.3f}  max {max(ts) * 1e3:9.3f} ms ({len(ts)} calls)"
+    lines = [f"tools/bench_align.py --variants: {ROUNDS} rounds x {REPEATS} timed calls per leg (one warm-up per round), fresh process per leg and round, legs in turn",
+             f"{VARIANTS_SHAPE}: {pairs} pairs of videos, {n_a * n_win} windows, zero planes with 5 % of the bits; tolerance {TOL}, min_run {MIN_RUN}; all legs of this build",
+             f"  align       {ms(got['align']['times'])}  {got['align']['records']} records   (one vdf_align_windows_device call)",
+             f"  derive      {ms(got['derive']['times'])}   (one vdf_window_variants_device call and the wait for it)"]
+    for leg, mask in VARIANT_MASKS.items():
+        k = bin(mask).count("1")
+        expected = k * (med["align"] + med["derive"])
+        lines.append(f"  {leg:11s} {ms(got[leg]['times'])}  {got[leg]['records']} records; expected {k} x (align + derive) = {expected * 1e3:.3f} ms: measured / expected = "
+                     f"{med[leg] / expected:.3f}x")
+    lines.append("nothing is gated")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    return 0
+
+
+def run_child(lib, leg, variants=False):
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--lib", lib, "--leg", leg] + (["--variants"] if variants else []),
+                         capture_output=True, text=True, timeout=900)
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")]
     if out.returncode != 0 or not line:
         raise SystemExit(f"child {leg} failed ({out.returncode}):\n{out.stdout[-2000:]}\n{out.stderr[-4000:]}")
@@ -200,13 +299,18 @@ def run_child(lib, leg):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_windows.txt"))
+    ap.add_argument("--variants", action="store_true")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--lib", default=os.path.join(ROOT, "vid_dup_finder_lib_amd", "libvdf_hip.so"))
     ap.add_argument("--leg", default="align")
     args = ap.parse_args()
     if args.child:
-        return child(args)
+        return variants_child(args) if args.variants else child(args)
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "align_variants.txt" if args.variants else "align_windows.txt")
+    if args.variants:
+        return variants_main(args)
     search_lib = os.path.abspath(args.parent_lib) if args.parent_lib else args.lib
     got = {}
     for _ in range(ROUNDS):

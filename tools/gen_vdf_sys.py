@@ -26,7 +26,9 @@ GROUPS = [
     ("every 16-frame window of a clip from one read of its frames: duplicates shifted in time, which one stack per file cannot see (definitions.rs:31-34)",
      r"vdf_hash_window"),
     ("the longest shared stretch of every pair of videos, on their window hashes: which videos share a stretch, at what offset, for how long",
-     r"vdf_align_windows"),
+     r"vdf_align_windows(_host|_device)?$"),
+    ("mirrored / flipped / reversed STRETCHES: the variant of a set of window hashes from their zero planes, and alignment against it",
+     r"vdf_window_variants|vdf_align_windows_variants"),
     ("mirrored / flipped / reversed duplicates, which the crate cannot see (lib.rs:102-111): the flipped clip's hash from the hash and the zero plane of the planes calls",
      r"vdf_hash_variant|vdf_search_variants"),
     ("search() / search_with_references() (video_dup_finder.rs:7-46 over search_algorithm.rs:63-185)", r"vdf_search_self$|vdf_search_refs$"),

@@ -19,7 +19,8 @@ import numpy as np
 
 from . import _capi
 from ._capi import DEFAULT_SEARCH_TOLERANCE, HASH_BITS, HASH_WORDS, TOLERANCE_SCALING_FACTOR, VdfError
-from .engine import ALIGN_DTYPE, Engine, align_windows_host, hamming_distance_words, hash_variant, tolerance_int
+from .engine import (ALIGN_DTYPE, ALIGN_VARIANT_DTYPE, Engine, align_windows_host, align_windows_variants_host, hamming_distance_words, hash_variant,
+                     tolerance_int)
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
            "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "hash_frame_windows", "locate", "rust_path_key", "sort_order",
@@ -495,12 +496,18 @@ def hash_frame_stacks(frames: np.ndarray, src_paths: Sequence, durations: Sequen
 
 
 def hash_frame_windows(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int], stride: int = 1,
-                       engine: Optional[Engine] = None) -> List[List[VideoHash]]:
+                       engine: Optional[Engine] = None, zero_plane: bool = False) -> List[List[VideoHash]]:
     """Every 16-frame window of every video (Engine.hash_windows): frames [n_videos, n_frames >= 16, H, W] u8 -> per video the VideoHash of
     frames [k * stride, k * stride + 16) for k = 0 .. (n_frames - 16) // stride, each carrying the video's src_paths[i] and durations[i].
-    What finds a duplicate that is shifted in time (`locate`); the reference hashes one 16-frame stack per file (definitions.rs:31-34)."""
+    What finds a duplicate that is shifted in time (`locate`); the reference hashes one 16-frame stack per file (definitions.rs:31-34).
+    zero_plane: every window's hash also carries its zero plane (VideoHash.zero; Engine.hash_windows_planes), which align_flipped needs;
+    the hash words are the same."""
     if len(src_paths) < len(frames) or len(durations) < len(frames):
         raise ValueError("a path and a duration per video")
+    if zero_plane:
+        eng = engine or default_engine()
+        words, zero = _with_planes(lambda: eng.hash_windows_planes(frames, stride))
+        return [[VideoHash(words[i, k], src_paths[i], durations[i], zero[i, k]) for k in range(words.shape[1])] for i in range(words.shape[0])]
     try:
         words = (engine or default_engine()).hash_windows(frames, stride)
     except VdfError as e:
@@ -632,6 +639,106 @@ def align(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoH
     for r in rec:
         a, b, off, st, n, ds = (int(r[k]) for k in ("a", "b", "offset", "start_a", "n_windows", "dist_sum"))
         out.append(Alignment(a, b, off * s, st * s, (st + off) * s, (n - 1) * s + _capi.DCT_SIZE, n, ds / n, pa[a], pb[b]))
+    return out
+
+
+class FlippedAlignment(NamedTuple):
+    """The longest stretch video a shares with the FLIPPED video b (align_flipped): Alignment's fields plus the flip.  first_frame_b and
+    n_frames describe the stretch in b's ORIGINAL frame numbering: frames [first_frame_b, first_frame_b + n_frames) of b, flipped, are
+    frames [first_frame_a, first_frame_a + n_frames) of a.  With Flip.T in the flip b's stretch plays BACKWARDS: frame first_frame_a + i
+    of a is frame first_frame_b + n_frames - 1 - i of b, and first_frame_b = (Nb - 1 - (start_a + offset + n_windows - 1)) * stride for
+    the record (start_a, offset, n_windows) of the C ABI and the Nb windows of b."""
+    a: int
+    b: int
+    offset_frames: int     # first_frame_b - first_frame_a
+    first_frame_a: int
+    first_frame_b: int
+    n_frames: int          # (n_windows - 1) * stride + 16
+    n_windows: int
+    mean_distance: float
+    path_a: object = None
+    path_b: object = None
+    flip: Flip = Flip.X
+
+
+def _align_zero(windows, what):
+    planes = [h.zero for ws in windows for h in ws]
+    if any(z is None for z in planes):
+        raise VidProc(f"align_flipped needs the zero plane of every hash of {what} (hash_frame_windows with zero_plane=True)")
+    return np.stack(planes) if planes else np.zeros((0, HASH_WORDS), np.uint64)
+
+
+def _align_flipped_call(engine, a, b, tol_int, min_run, mask):
+    """_align_call for the variants: a = (words, first, skip, zero or None), b likewise or None for self mode."""
+    def once(capacity):
+        kw = dict(tol_int=tol_int, min_run=min_run, variant_mask=mask, a_skip=a[2], capacity=capacity, a_zero=a[3])
+        if b is not None:
+            kw.update(b_hashes=b[0], b_first=b[1], b_skip=b[2], b_zero=b[3])
+        return align_windows_variants_host(a[0], a[1], **kw) if engine is None else engine.align_windows_variants(a[0], a[1], **kw)
+    rec, found = once(ALIGN_FIRST_CAPACITY)
+    if found > len(rec):
+        rec, found = once(found)
+    return rec
+
+
+def align_flipped(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoHash]]] = None, tolerance: float = DEFAULT_SEARCH_TOLERANCE,
+                  min_run: int = 1, stride: int = 1, flips: Sequence = (Flip.X,), static_a=None, static_b=None,
+                  engine: Optional[Engine] = None) -> dict:
+    """`align` against the mirrored / flipped / reversed videos of windows_b - the re-upload that is mirrored AND has its intro trimmed, which
+    neither search_flipped (frames 0 ... 15 of a file) nor align (unflipped stretches) sees: {flip: [FlippedAlignment]} for every flip of `flips`,
+    each list ordered by (a, b) with at most one entry per pair, by align's rules on the window hashes of the flipped b (derived from b's hashes
+    and zero planes; include/vdf.h: vdf_align_windows_variants).  windows_b None: the videos of windows_a against each other's flips, every
+    pair once (a < b), never a video against its own mirror.  The hashes of the flipped side (windows_b, or windows_a in self mode) need their
+    zero planes (hash_frame_windows with zero_plane=True), else VidProc.  With Flip.T the matched stretch of b plays backwards
+    (FlippedAlignment); it lies on b's window grid, i.e. reversed b is taken from its last window's last frame.  Near the tolerance a stretch
+    can show with b flipped and not with the sides swapped: b's zero plane clears bits of the flipped hash that a may have set."""
+    self_mode = windows_b is None
+    s = int(stride)
+    if s != stride or s < 1:
+        raise ValueError("stride must be a positive integer")
+    flips = [Flip(int(f)) for f in flips]
+    if any(not 1 <= int(f) <= 7 for f in flips):
+        raise ValueError("flips are non-empty combinations of Flip.X, Flip.Y, Flip.T")
+    tol_int = tolerance_int(tolerance)
+    wa, fa, ka, ca = _align_csr(windows_a, static_a)
+    wb, fb, kb, cb = (wa, fa, ka, ca) if self_mode else _align_csr(windows_b, static_b)
+    zb = _align_zero(windows_a if self_mode else windows_b, "windows_a" if self_mode else "windows_b")
+    if not flips:
+        return {}
+    mask = 0
+    for f in flips:
+        mask |= 1 << int(f)
+    if engine is None:
+        cells = (sum(ca) ** 2 - sum(n * n for n in ca)) // 2 if self_mode else sum(ca) * sum(cb)
+        if cells * len(flips) > ALIGN_HOST_CELLS:
+            engine = default_engine()
+
+    def block(words, first, skip, zero, lo, hi):
+        w0, w1 = int(first[lo]), int(first[hi])
+        return words[w0:w1], first[lo:hi + 1] - first[lo], None if skip is None else skip[w0:w1], None if zero is None else zero[w0:w1]
+
+    step = max(1, math.isqrt(ALIGN_MAX_PAIRS))
+    parts = []
+    for a0 in range(0, len(ca), step):
+        a1 = min(a0 + step, len(ca))
+        for b0 in range(a0 if self_mode else 0, len(cb), step):
+            b1 = min(b0 + step, len(cb))
+            same = self_mode and b0 == a0
+            A = block(wa, fa, ka, zb if same else None, a0, a1)
+            rec = _align_flipped_call(engine, A, None if same else block(wb, fb, kb, zb, b0, b1), tol_int, int(min_run), mask).copy()
+            rec["a"] += a0
+            rec["b"] += b0
+            parts.append(rec)
+    rec = np.concatenate(parts) if parts else np.zeros(0, ALIGN_VARIANT_DTYPE)
+    rec = rec[np.lexsort((rec["b"], rec["a"], rec["variant"]))]
+    pa = [ws[0].src_path() if ws else None for ws in windows_a]
+    pb = pa if self_mode else [ws[0].src_path() if ws else None for ws in windows_b]
+    out = {f: [] for f in flips}
+    for r in rec:
+        a, b, off, st, n, ds, v = (int(r[k]) for k in ("a", "b", "offset", "start_a", "n_windows", "dist_sum", "variant"))
+        j0 = st + off                                                  # the stretch's first window of b in the DERIVED order
+        kb0 = cb[b] - 1 - (j0 + n - 1) if v & int(Flip.T) else j0      # its first window in b's own order
+        out[Flip(v)].append(FlippedAlignment(a, b, (kb0 - st) * s, st * s, kb0 * s, (n - 1) * s + _capi.DCT_SIZE, n, ds / n, pa[a], pb[b], Flip(v)))
     return out
 
 

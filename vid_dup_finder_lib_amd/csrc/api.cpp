@@ -787,9 +787,9 @@ int windows_checks(vdf_ctx *ctx, const void *frames, size_t n_clips, uint32_t fr
     return VDF_OK;
 }
 
-// windows_checks has passed
+// windows_checks has passed.  d_zero (nullable): the windows' zero planes as well - the same resize runs and routes, the kernel's PLANES form
 int hash_windows_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h, size_t frame_stride,
-                        size_t clip_stride, uint32_t window_stride, uint64_t *d_out, uint32_t *d_dc, hipStream_t stream)
+                        size_t clip_stride, uint32_t window_stride, uint64_t *d_out, uint32_t *d_dc, hipStream_t stream, uint64_t *d_zero = nullptr)
 {
     VDF_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = ensure_cos_table(ctx, stream)) return rc;
@@ -821,7 +821,7 @@ int hash_windows_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, u
         wf.tail_first = frames_per_clip - 16;
         wf.dwords = true;
     }
-    VDF_HIP(ctx, vdf::launch_dct_hash_windows(wf, n_clips, plan, ctx->cos_table.as<double>(), d_out, d_dc, stream));
+    VDF_HIP(ctx, vdf::launch_dct_hash_windows(wf, n_clips, plan, ctx->cos_table.as<double>(), d_out, d_dc, stream, d_zero));
     return VDF_OK;
 }
 
@@ -1891,6 +1891,40 @@ int vdf_align_windows_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uin
                         capacity, n_out, s);
 }
 
+// Host arrays of an align call -> the context's staging buffers: the hashes of A (up_hashes) and, unless self, of B (up_ref_hashes), the first
+// arrays rebased to the uploaded windows and the skip arrays ([first a | first b | skip a | skip b] in align_up).
+struct AlignUploaded {
+    std::vector<uint32_t> fa, fb;  // the rebased first arrays, on the host
+    const uint32_t *d_fa, *d_fb;
+    const uint8_t *d_ska, *d_skb;
+};
+static int align_upload(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                        const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, bool self, hipStream_t s, AlignUploaded *u)
+{
+    const size_t wa = a_first[n_a] - a_first[0], wb = self ? 0 : b_first[n_b] - b_first[0];
+    std::vector<uint32_t> &fa = u->fa, &fb = u->fb;
+    fa.assign(n_a + 1, 0);
+    fb.assign(self ? 0 : n_b + 1, 0);
+    for (size_t v = 0; v <= n_a; v++) fa[v] = a_first[v] - a_first[0];
+    for (size_t v = 0; v < fb.size(); v++) fb[v] = b_first[v] - b_first[0];
+    const size_t fa_bytes = fa.size() * sizeof(uint32_t), fb_bytes = fb.size() * sizeof(uint32_t);
+    const size_t ska = a_skip ? wa : 0, skb = (!self && b_skip) ? wb : 0;
+    VDF_HIP(ctx, ctx->align_up.reserve(fa_bytes + fb_bytes + ska + skb + 16));
+    char *up = ctx->align_up.as<char>();
+    VDF_HIP(ctx, hipMemcpyAsync(up, fa.data(), fa_bytes, hipMemcpyHostToDevice, s));
+    if (fb_bytes) VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes, fb.data(), fb_bytes, hipMemcpyHostToDevice, s));
+    if (ska) VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes + fb_bytes, a_skip + a_first[0], ska, hipMemcpyHostToDevice, s));
+    if (skb) VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes + fb_bytes + ska, b_skip + b_first[0], skb, hipMemcpyHostToDevice, s));
+    if (int rc = upload(ctx, ctx->up_hashes, a_hashes + 16 * (size_t)a_first[0], wa * 16 * sizeof(uint64_t), s)) return rc;
+    if (!self)
+        if (int rc = upload(ctx, ctx->up_ref_hashes, b_hashes + 16 * (size_t)b_first[0], wb * 16 * sizeof(uint64_t), s)) return rc;
+    u->d_fa = reinterpret_cast<const uint32_t *>(up);
+    u->d_fb = reinterpret_cast<const uint32_t *>(up + fa_bytes);
+    u->d_ska = ska ? reinterpret_cast<const uint8_t *>(up + fa_bytes + fb_bytes) : nullptr;
+    u->d_skb = skb ? reinterpret_cast<const uint8_t *>(up + fa_bytes + fb_bytes + ska) : nullptr;
+    return VDF_OK;
+}
+
 // Host arrays: hashes, first and skip arrays go up through the context's staging buffers, the device form's core runs on them.
 int vdf_align_windows(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
                       const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, uint32_t tol_int, uint32_t min_run, vdf_alignment *out, size_t capacity,
@@ -1905,29 +1939,12 @@ int vdf_align_windows(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_
     if (n_a == 0 || (self ? n_a < 2 : n_b == 0)) return VDF_OK;
     VDF_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const size_t wa = a_first[n_a] - a_first[0], wb = self ? 0 : b_first[n_b] - b_first[0];
-    // first arrays rebased to the uploaded windows; [first a | first b | skip a | skip b] in one buffer
-    std::vector<uint32_t> fa(n_a + 1), fb(self ? 0 : n_b + 1);
-    for (size_t v = 0; v <= n_a; v++) fa[v] = a_first[v] - a_first[0];
-    for (size_t v = 0; v < fb.size(); v++) fb[v] = b_first[v] - b_first[0];
-    const size_t fa_bytes = fa.size() * sizeof(uint32_t), fb_bytes = fb.size() * sizeof(uint32_t);
-    const size_t ska = a_skip ? wa : 0, skb = (!self && b_skip) ? wb : 0;
-    VDF_HIP(ctx, ctx->align_up.reserve(fa_bytes + fb_bytes + ska + skb + 16));
-    char *up = ctx->align_up.as<char>();
-    VDF_HIP(ctx, hipMemcpyAsync(up, fa.data(), fa_bytes, hipMemcpyHostToDevice, s));
-    if (fb_bytes) VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes, fb.data(), fb_bytes, hipMemcpyHostToDevice, s));
-    if (ska) VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes + fb_bytes, a_skip + a_first[0], ska, hipMemcpyHostToDevice, s));
-    if (skb) VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes + fb_bytes + ska, b_skip + b_first[0], skb, hipMemcpyHostToDevice, s));
-    if (int rc = upload(ctx, ctx->up_hashes, a_hashes + 16 * (size_t)a_first[0], wa * 16 * sizeof(uint64_t), s)) return rc;
-    if (!self)
-        if (int rc = upload(ctx, ctx->up_ref_hashes, b_hashes + 16 * (size_t)b_first[0], wb * 16 * sizeof(uint64_t), s)) return rc;
-    const uint32_t *d_fa = reinterpret_cast<const uint32_t *>(up), *d_fb = reinterpret_cast<const uint32_t *>(up + fa_bytes);
-    const uint8_t *d_ska = ska ? reinterpret_cast<const uint8_t *>(up + fa_bytes + fb_bytes) : nullptr;
-    const uint8_t *d_skb = skb ? reinterpret_cast<const uint8_t *>(up + fa_bytes + fb_bytes + ska) : nullptr;
-    if (self) return align_locked(ctx, ctx->up_hashes.as<uint64_t>(), d_fa, fa.data(), n_a, d_ska, ctx->up_hashes.as<uint64_t>(), d_fa, fa.data(), n_a, d_ska,
-                                  true, tol_int, min_run, out, capacity, n_out, s);
-    return align_locked(ctx, ctx->up_hashes.as<uint64_t>(), d_fa, fa.data(), n_a, d_ska, ctx->up_ref_hashes.as<uint64_t>(), d_fb, fb.data(), n_b, d_skb, false,
-                        tol_int, min_run, out, capacity, n_out, s);
+    AlignUploaded u;
+    if (int rc = align_upload(ctx, a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, self, s, &u)) return rc;
+    if (self) return align_locked(ctx, ctx->up_hashes.as<uint64_t>(), u.d_fa, u.fa.data(), n_a, u.d_ska, ctx->up_hashes.as<uint64_t>(), u.d_fa, u.fa.data(), n_a,
+                                  u.d_ska, true, tol_int, min_run, out, capacity, n_out, s);
+    return align_locked(ctx, ctx->up_hashes.as<uint64_t>(), u.d_fa, u.fa.data(), n_a, u.d_ska, ctx->up_ref_hashes.as<uint64_t>(), u.d_fb, u.fb.data(), n_b, u.d_skb,
+                        false, tol_int, min_run, out, capacity, n_out, s);
 }
 
 size_t vdf_hash_window_count(uint32_t frames_per_clip, uint32_t window_stride) { return vdf::window_count(frames_per_clip, window_stride); }
@@ -2118,6 +2135,264 @@ int vdf_hash_clips_u8_planes(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes,
     if (int rc = planes_clips_checks(ctx, buf, buf_bytes, clips, n_clips, frames_per_clip, out_hashes, out_zero, &run)) return rc;
     if (!run) return VDF_OK;
     return hash_clips_host_locked(ctx, buf, buf_bytes, clips, n_clips, frames_per_clip, out_hashes, out_dontcare, 0, nullptr, out_zero);
+}
+
+// ---- zero planes of window hashes, the variant of a set of them, alignment against the variants (include/vdf.h) ---------------
+// windows_checks' checks in windows_checks' order with out_zero among the null pointers, then the plane's own, the context last
+static int windows_planes_checks(vdf_ctx *ctx, const void *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h, size_t frame_stride,
+                                 uint32_t window_stride, const void *out_hashes, const void *out_zero, bool *run)
+{
+    *run = false;
+    if (frames_per_clip < VDF_DCT_SIZE) return fail(ctx, VDF_E_NOT_ENOUGH_FRAMES, "fewer than 16 frames per clip");
+    if (w == 0 || h == 0) return fail(ctx, VDF_E_BAD_DIMS, "zero frame dimension");
+    if (frame_stride < (size_t)w * h) return fail(ctx, VDF_E_INVAL, "frame_stride smaller than a frame");
+    if (window_stride == 0) return fail(ctx, VDF_E_INVAL, "window_stride of zero");
+    const size_t n_win = vdf::window_count(frames_per_clip, window_stride);
+    if (frames_per_clip > 0xFFFFFFC0u || (n_clips && n_win > 0xFFFFFFFFull / n_clips)) return fail(ctx, VDF_E_INVAL, "2^32 windows or more in one call");
+    if (n_clips == 0) return VDF_OK;
+    if (!frames || !out_hashes || !out_zero) return fail(ctx, VDF_E_INVAL, "null pointer");
+    if (int rc = planes_axis_ok(ctx, w)) return rc;
+    if (int rc = planes_axis_ok(ctx, h)) return rc;
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "the windows calls take a single-device context");
+    *run = true;
+    return VDF_OK;
+}
+
+int vdf_hash_windows_u8_planes_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h,
+                                      size_t frame_stride, size_t clip_stride, uint32_t window_stride, uint64_t *d_out_hashes, uint32_t *d_out_dontcare,
+                                      uint64_t *d_out_zero, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    bool run;
+    if (int rc = windows_planes_checks(ctx, d_frames, n_clips, frames_per_clip, w, h, frame_stride, window_stride, d_out_hashes, d_out_zero, &run)) return rc;
+    if (!run) return VDF_OK;
+    return hash_windows_locked(ctx, d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, window_stride, d_out_hashes, d_out_dontcare,
+                               stream ? (hipStream_t)stream : ctx->stream, d_out_zero);
+}
+
+int vdf_hash_windows_u8_planes(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h, size_t frame_stride,
+                               size_t clip_stride, uint32_t window_stride, uint64_t *out_hashes, uint32_t *out_dontcare, uint64_t *out_zero)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    bool run;
+    if (int rc = windows_planes_checks(ctx, frames, n_clips, frames_per_clip, w, h, frame_stride, window_stride, out_hashes, out_zero, &run)) return rc;
+    if (!run) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n_out = n_clips * vdf::window_count(frames_per_clip, window_stride), hash_bytes = n_out * VDF_HASH_WORDS * sizeof(uint64_t);
+    size_t clips_span = 0, frames_span = 0, bytes = 0;  // as vdf_hash_windows_u8: first byte of clip 0 to the last byte of the last clip's last frame
+    if (__builtin_mul_overflow(n_clips - 1, clip_stride, &clips_span) || __builtin_mul_overflow((size_t)(frames_per_clip - 1), frame_stride, &frames_span) ||
+        __builtin_add_overflow(clips_span, frames_span, &bytes) || __builtin_add_overflow(bytes, (size_t)w * h, &bytes))
+        return fail(ctx, VDF_E_INVAL, "the clips' extent does not fit size_t");
+    if (int rc = upload(ctx, ctx->frames, frames, bytes, ctx->stream)) return rc;
+    VDF_HIP(ctx, ctx->out_hashes.reserve(hash_bytes));
+    VDF_HIP(ctx, ctx->out_zero.reserve(hash_bytes));
+    if (out_dontcare) VDF_HIP(ctx, ctx->out_dc.reserve(n_out * sizeof(uint32_t)));
+    uint32_t *d_dc = out_dontcare ? ctx->out_dc.as<uint32_t>() : nullptr;
+    if (int rc = hash_windows_locked(ctx, ctx->frames.as<uint8_t>(), n_clips, frames_per_clip, w, h, frame_stride, clip_stride, window_stride,
+                                     ctx->out_hashes.as<uint64_t>(), d_dc, ctx->stream, ctx->out_zero.as<uint64_t>()))
+        return rc;
+    VDF_HIP(ctx, hipMemcpyAsync(out_hashes, ctx->out_hashes.p, hash_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    VDF_HIP(ctx, hipMemcpyAsync(out_zero, ctx->out_zero.p, hash_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_dontcare) VDF_HIP(ctx, hipMemcpyAsync(out_dontcare, d_dc, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VDF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VDF_OK;
+}
+
+// the argument checks both window-variant forms share, in the order their messages are reported; first on the host (null: not checked here)
+static int window_variants_checks(vdf_ctx *ctx, const void *hashes, const void *zero, const void *first_ptr, const uint32_t *first, size_t n_videos,
+                                  const void *skip, uint32_t variant, const void *out_hashes, const void *out_skip)
+{
+    if (variant == 0 || variant >= vdf::kHashVariants) return fail(ctx, VDF_E_INVAL, "variant outside 1 ... 7");
+    if (n_videos == 0) return VDF_OK;
+    if (!hashes || !zero || !first_ptr || !out_hashes || (skip == nullptr) != (out_skip == nullptr)) return fail(ctx, VDF_E_INVAL, "null pointer");
+    if (out_hashes == hashes || out_hashes == zero || (skip && out_skip == skip)) return fail(ctx, VDF_E_INVAL, "the variants are not made in place");
+    if (n_videos >= 0xFFFFFFFFull) return fail(ctx, VDF_E_INVAL, "more than 2^32-2 videos");
+    for (size_t v = 0; first && v < n_videos; v++)
+        if (first[v + 1] < first[v]) return fail(ctx, VDF_E_INVAL, "the first array decreases at video " + std::to_string(v));
+    return VDF_OK;
+}
+
+// rows [first[0], first[n_videos]) of out from hashes / zero / skip: the kernel's rule (window_variant.h) in plain C++
+static void window_variants_rows_host(const uint64_t *hashes, const uint64_t *zero, const uint32_t *first, size_t n_videos, const uint8_t *skip,
+                                      uint32_t variant, uint64_t *out_hashes, uint8_t *out_skip)
+{
+    for (uint32_t row = first[0]; row < first[n_videos]; row++) {
+        const uint32_t src = vdf::window_variant_source(first, (uint32_t)n_videos, row, variant);
+        for (int k = 0; k < VDF_HASH_WORDS; k++)
+            out_hashes[(size_t)row * 16 + k] = (hashes[(size_t)src * 16 + k] ^ vdf::kVariantMasks.m[variant][k]) & ~zero[(size_t)src * 16 + k];
+        if (skip) out_skip[row] = skip[src];
+    }
+}
+
+int vdf_window_variants_host(const uint64_t *hashes, const uint64_t *zero, const uint32_t *first, size_t n_videos, const uint8_t *skip, uint32_t variant,
+                             uint64_t *out_hashes, uint8_t *out_skip)
+{
+    if (int rc = window_variants_checks(nullptr, hashes, zero, first, first, n_videos, skip, variant, out_hashes, out_skip)) return rc;
+    if (n_videos) window_variants_rows_host(hashes, zero, first, n_videos, skip, variant, out_hashes, out_skip);
+    return VDF_OK;
+}
+
+int vdf_window_variants_device(vdf_ctx *ctx, const uint64_t *d_hashes, const uint64_t *d_zero, const uint32_t *d_first, size_t n_videos,
+                               const uint8_t *d_skip, uint32_t variant, uint64_t *d_out_hashes, uint8_t *d_out_skip, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (int rc = window_variants_checks(ctx, d_hashes, d_zero, d_first, nullptr, n_videos, d_skip, variant, d_out_hashes, d_out_skip)) return rc;
+    if (n_videos == 0) return VDF_OK;
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_window_variants_device takes a single-device context");
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<uint32_t> first(n_videos + 1);
+    VDF_HIP(ctx, hipMemcpyAsync(first.data(), d_first, first.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));
+    if (int rc = window_variants_checks(ctx, d_hashes, d_zero, d_first, first.data(), n_videos, d_skip, variant, d_out_hashes, d_out_skip)) return rc;
+    VDF_HIP(ctx, vdf::launch_window_variants(d_hashes, d_zero, d_first, (uint32_t)n_videos, d_skip, variant, first[0], first[n_videos] - first[0], d_out_hashes,
+                                             d_out_skip, s));
+    return VDF_OK;
+}
+
+// behind align_checks: the mask, then the zero plane of the side that is flipped
+static int align_variants_checks(vdf_ctx *ctx, uint32_t variant_mask, size_t n_flipped, const void *zero)
+{
+    if ((variant_mask & ~0xFEu) != 0) return fail(ctx, VDF_E_INVAL, "variant_mask takes bits 1 ... 7");
+    if (n_flipped && !zero) return fail(ctx, VDF_E_INVAL, "the flipped side has no zero plane");
+    return VDF_OK;
+}
+
+static vdf_alignment_variant alignment_of_variant(const vdf_alignment &r, uint32_t variant)
+{
+    return vdf_alignment_variant{r.a, r.b, r.offset, r.start_a, r.n_windows, r.dist_sum, variant};
+}
+
+int vdf_align_windows_variants_host(const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                    const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                                    uint32_t tol_int, uint32_t min_run, uint32_t variant_mask, vdf_alignment_variant *out, size_t capacity, size_t *n_out)
+{
+    if (int rc = align_checks(nullptr, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, min_run, out, capacity, n_out)) return rc;
+    const bool self = b_hashes == nullptr;
+    if (self) { b_hashes = a_hashes; b_zero = a_zero; b_first = a_first; n_b = n_a; b_skip = a_skip; }
+    if (int rc = align_variants_checks(nullptr, variant_mask, n_b, b_zero)) return rc;
+    *n_out = 0;
+    if (n_a == 0 || (self ? n_a < 2 : n_b == 0)) return VDF_OK;
+    const uint32_t tol = std::min<uint32_t>(tol_int, 1024u);
+    std::vector<uint64_t> derived((size_t)b_first[n_b] * 16);  // one buffer, re-used by every variant; rows below b_first[0] stay unused
+    std::vector<uint8_t> derived_skip(b_skip ? b_first[n_b] : 0);
+    size_t found = 0;
+    for (uint32_t v = 1; v < vdf::kHashVariants; v++) {
+        if (!(variant_mask >> v & 1u)) continue;
+        window_variants_rows_host(b_hashes, b_zero, b_first, n_b, b_skip, v, derived.data(), b_skip ? derived_skip.data() : nullptr);
+        for (size_t a = 0; a < n_a; a++)
+            for (size_t b = self ? a + 1 : 0; b < n_b; b++) {
+                vdf_alignment r;
+                align_pair_host(a_hashes + 16 * (size_t)a_first[a], a_first[a + 1] - a_first[a], a_skip ? a_skip + a_first[a] : nullptr,
+                                derived.data() + 16 * (size_t)b_first[b], b_first[b + 1] - b_first[b], b_skip ? derived_skip.data() + b_first[b] : nullptr, tol,
+                                min_run, &r);
+                if (r.n_windows == 0) continue;
+                r.a = (uint32_t)a; r.b = (uint32_t)b;
+                if (found < capacity) out[found] = alignment_of_variant(r, v);
+                found++;
+            }
+    }
+    *n_out = found;
+    return VDF_OK;
+}
+
+// One align per requested variant, ascending: the variant set of B derived into the context's scratch (hashes, then skip bytes; all variants re-use
+// it), then the align core on (A, derived B).  align_checks and align_variants_checks have passed; every array pointer is a device pointer, the
+// first arrays are also on the host.  self: B's pointers are A's.
+static int align_variants_locked(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, const uint32_t *h_first_a, size_t n_a,
+                                 const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint64_t *d_b_zero, const uint32_t *d_b_first,
+                                 const uint32_t *h_first_b, size_t n_b, const uint8_t *d_b_skip, bool self, uint32_t tol_int, uint32_t min_run,
+                                 uint32_t variant_mask, vdf_alignment_variant *out, size_t capacity, size_t *n_out, hipStream_t s)
+{
+    const uint32_t row0 = h_first_b[0], row_end = h_first_b[n_b];
+    const size_t hash_bytes = (size_t)row_end * VDF_HASH_WORDS * sizeof(uint64_t);
+    VDF_HIP(ctx, ctx->variant_hashes.reserve(hash_bytes + (d_b_skip ? row_end : 0) + 16));
+    uint64_t *d_var = ctx->variant_hashes.as<uint64_t>();
+    uint8_t *d_var_skip = d_b_skip ? ctx->variant_hashes.as<uint8_t>() + hash_bytes : nullptr;
+    const size_t n_pairs = vdf::align_pair_count(n_a, n_b, self);
+    std::vector<vdf_alignment> records;
+    size_t found = 0;
+    for (uint32_t v = 1; v < vdf::kHashVariants; v++) {
+        if (!(variant_mask >> v & 1u)) continue;
+        VDF_HIP(ctx, vdf::launch_window_variants(d_b_hashes, d_b_zero, d_b_first, (uint32_t)n_b, d_b_skip, v, row0, row_end - row0, d_var, d_var_skip, s));
+        records.resize(std::min(capacity > found ? capacity - found : 0, n_pairs));
+        size_t n_v = 0;
+        if (int rc = align_locked(ctx, d_a_hashes, d_a_first, h_first_a, n_a, d_a_skip, d_var, d_b_first, h_first_b, n_b, d_var_skip, self, tol_int, min_run,
+                                  records.data(), records.size(), &n_v, s))
+            return rc;
+        for (size_t i = 0; i < std::min(n_v, records.size()); i++) out[found + i] = alignment_of_variant(records[i], v);
+        found += n_v;
+    }
+    VDF_HIP(ctx, hipStreamSynchronize(s));  // (a variant without a pair to align leaves only its derive kernel behind)
+    *n_out = found;
+    return VDF_OK;
+}
+
+int vdf_align_windows_variants_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint64_t *d_a_zero, const uint32_t *d_a_first, size_t n_a,
+                                      const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint64_t *d_b_zero, const uint32_t *d_b_first, size_t n_b,
+                                      const uint8_t *d_b_skip, uint32_t tol_int, uint32_t min_run, uint32_t variant_mask, vdf_alignment_variant *out,
+                                      size_t capacity, size_t *n_out, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const bool self = d_b_hashes == nullptr;
+    const auto late_checks = [&]() -> int {
+        if (int rc = align_variants_checks(ctx, variant_mask, self ? n_a : n_b, self ? d_a_zero : d_b_zero)) return rc;
+        if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_align_windows_variants_device takes a single-device context");
+        return VDF_OK;
+    };
+    // as vdf_align_windows_device: everything that can be said without the first arrays; then they come down, are checked, and plan the launch
+    if (int rc = align_checks(ctx, d_a_hashes, nullptr, n_a, d_b_hashes, nullptr, n_b, d_a_first, d_b_first, min_run, out, capacity, n_out)) return rc;
+    if (n_a == 0 || (self ? n_a < 2 : n_b == 0) || !ctx->subs.empty()) {  // nothing to read back, or no device to read it from
+        if (int rc = late_checks()) return rc;
+        *n_out = 0;
+        return VDF_OK;
+    }
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<uint32_t> fa(n_a + 1), fb(self ? 0 : n_b + 1);
+    VDF_HIP(ctx, hipMemcpyAsync(fa.data(), d_a_first, fa.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (!self) VDF_HIP(ctx, hipMemcpyAsync(fb.data(), d_b_first, fb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));
+    if (int rc = align_checks(ctx, d_a_hashes, fa.data(), n_a, d_b_hashes, self ? nullptr : fb.data(), n_b, d_a_first, d_b_first, min_run, out, capacity, n_out))
+        return rc;
+    if (int rc = late_checks()) return rc;
+    *n_out = 0;
+    if (self) return align_variants_locked(ctx, d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, d_a_hashes, d_a_zero, d_a_first, fa.data(), n_a, d_a_skip, true,
+                                           tol_int, min_run, variant_mask, out, capacity, n_out, s);
+    return align_variants_locked(ctx, d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, d_b_hashes, d_b_zero, d_b_first, fb.data(), n_b, d_b_skip, false, tol_int,
+                                 min_run, variant_mask, out, capacity, n_out, s);
+}
+
+// Host arrays: as vdf_align_windows, and the zero plane of the flipped side goes up beside its hashes.
+int vdf_align_windows_variants(vdf_ctx *ctx, const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                               const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, uint32_t tol_int,
+                               uint32_t min_run, uint32_t variant_mask, vdf_alignment_variant *out, size_t capacity, size_t *n_out)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (int rc = align_checks(ctx, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, min_run, out, capacity, n_out)) return rc;
+    const bool self = b_hashes == nullptr;
+    const uint64_t *zero = self ? a_zero : b_zero;
+    const uint32_t *zero_first = self ? a_first : b_first;
+    const size_t n_flipped = self ? n_a : n_b;
+    if (int rc = align_variants_checks(ctx, variant_mask, n_flipped, zero)) return rc;
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_align_windows_variants takes a single-device context");
+    *n_out = 0;
+    if (n_a == 0 || (self ? n_a < 2 : n_b == 0)) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    AlignUploaded u;
+    if (int rc = align_upload(ctx, a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, self, s, &u)) return rc;
+    if (int rc = upload(ctx, ctx->up_zero, zero + 16 * (size_t)zero_first[0], (size_t)(zero_first[n_flipped] - zero_first[0]) * 16 * sizeof(uint64_t), s)) return rc;
+    if (self) return align_variants_locked(ctx, ctx->up_hashes.as<uint64_t>(), u.d_fa, u.fa.data(), n_a, u.d_ska, ctx->up_hashes.as<uint64_t>(),
+                                           ctx->up_zero.as<uint64_t>(), u.d_fa, u.fa.data(), n_a, u.d_ska, true, tol_int, min_run, variant_mask, out, capacity,
+                                           n_out, s);
+    return align_variants_locked(ctx, ctx->up_hashes.as<uint64_t>(), u.d_fa, u.fa.data(), n_a, u.d_ska, ctx->up_ref_hashes.as<uint64_t>(),
+                                 ctx->up_zero.as<uint64_t>(), u.d_fb, u.fb.data(), n_b, u.d_skb, false, tol_int, min_run, variant_mask, out, capacity, n_out, s);
 }
 
 int vdf_hash_variant(const uint64_t *hash, const uint64_t *zero, uint32_t variant, uint64_t *out)

@@ -2752,6 +2752,7 @@ hipError_t launch_dct_hash_indexed(const uint8_t *small, const MixedClipDesc *de
 // and the don't-care counts are double-buffered by the parity of the pair, which leaves ONE barrier per pair: a buffer is cleared by the lanes
 // that read it out, and is OR-ed into again two pairs - at least one barrier - later.
 // LDS: b 21 760 + ring 27 136 + cube 4 096 + words 512 + counts 32 = 53 536 bytes, three workgroups per CU (160 KB).
+// The PLANES form (the windows' zero planes) adds a second set of 512 bytes of ballot words: 54 048 bytes.
 struct WindowsShared {
     double b[16 * 10 * kPadY];         // first-pass output [t][ky][x] of the chunk in hand
     double c[32 * kStrideT];           // the ring: S of frame f at slot (f - run start) & 31, [slot][10 kx + ky]
@@ -2769,13 +2770,27 @@ struct WindowsSource {
     uint32_t main_frames, tail_first;
 };
 
+// The zero planes of the pair of windows in hand: [parity][window of the pair][32] ballot words, OR-assembled, read out and
+// cleared exactly as WindowsShared::words are.  LDS of the PLANES form only - the plain form never reaches this function and allocates nothing
+// for it - and a buffer of its own: `cube` is written by the next chunk's load with no barrier behind the store phase, so nothing may overlay it.
+__device__ __forceinline__ uint32_t *windows_zero_words()
+{
+    __shared__ uint32_t zw[2 * 2 * 32];
+    return zw;
+}
+
 // DWORDS: every frame starts on a dword boundary (always true of `small`; of 16 x 16 input when its base and strides are multiples of 4)
-template <bool DWORDS>
+// PLANES: also every window's zero plane - bit i set iff coefficient i == 0.0, either sign - to out_zero + 16 (clip n_win + k).  A compile-time
+// switch: the plain form has none of it, never reads out_zero, and is still named and called with its nine arguments.
+template <bool DWORDS, bool PLANES = false>
 __global__ __launch_bounds__(256) void dct_hash_windows_kernel(WindowsSource src, uint32_t stride, uint32_t n_win, uint32_t per_seg, uint32_t n_seg,
                                                                uint64_t first_group, const double *__restrict__ cos_table,
-                                                               uint64_t *__restrict__ out_hashes, uint32_t *__restrict__ out_dontcare)
+                                                               uint64_t *__restrict__ out_hashes, uint32_t *__restrict__ out_dontcare,
+                                                               uint64_t *__restrict__ out_zero = nullptr)
 {
     __shared__ WindowsShared sh;
+    uint32_t *zw = nullptr;
+    if constexpr (PLANES) zw = windows_zero_words();
     const const_f64_ptr cosv = (const_f64_ptr)(uintptr_t)cos_table;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint64_t group = first_group + blockIdx.x;  // the launcher's grid holds no group past n_clips * n_seg
@@ -2791,6 +2806,9 @@ __global__ __launch_bounds__(256) void dct_hash_windows_kernel(WindowsSource src
     for (int i = 0; i < 2; i++) { cm.t8[i][0] = cosv[264 + 2 * i]; cm.t8[i][1] = cosv[265 + 2 * i]; }
     cm.t4[0] = cosv[268]; cm.t4[1] = cosv[269]; cm.h = cosv[270];
     if (tid < 128) (&sh.words[0][0][0])[tid] = 0u;  // (the first OR is behind the barriers of the first chunk)
+    if constexpr (PLANES) {
+        if (tid >= 128) zw[tid - 128] = 0u;
+    }
 
     uint32_t k = k_begin, parity = 0;
     // run: the segment's first frame, slot 0 of the ring.  A segment's windows are at most 16 frames apart (strides above 16 get a segment per
@@ -2883,6 +2901,22 @@ __global__ __launch_bounds__(256) void dct_hash_windows_kernel(WindowsSource src
                     atomicOr(&words[wi + 1], (hi << sh_l) | (sh_l ? lo >> (32u - sh_l) : 0u));
                     if (sh_l && wi + 2 < 32) atomicOr(&words[wi + 2], hi >> (32u - sh_l));
                 }
+                if constexpr (PLANES) {  // a pass of its own behind the hash words', as in dct_hash_block: `piece` is dead, its registers serve again
+                    unsigned long long zpiece = 0;
+#pragma unroll
+                    for (int kt = 0; kt < 10; kt++) {
+                        const unsigned long long zeros = __builtin_amdgcn_ballot_w64(live && o[kt] == 0.0);  // +0.0 and -0.0
+                        if (lane == (uint32_t)kt) zpiece = zeros;
+                    }
+                    uint32_t *zwords = zw + (parity * 2 + half) * 32;
+                    if (lane < 10) {
+                        const uint32_t off = 100u * lane + 64u * wv, wi = off >> 5, sh_l = off & 31u;
+                        const uint32_t zlo = (uint32_t)zpiece, zhi = (uint32_t)(zpiece >> 32);
+                        atomicOr(&zwords[wi], zlo << sh_l);
+                        atomicOr(&zwords[wi + 1], (zhi << sh_l) | (sh_l ? zlo >> (32u - sh_l) : 0u));
+                        if (sh_l && wi + 2 < 32) atomicOr(&zwords[wi + 2], zhi >> (32u - sh_l));
+                    }
+                }
                 if (lane == 0) sh.dc[parity][half][wv] = dc;
             }
             __syncthreads();
@@ -2898,6 +2932,16 @@ __global__ __launch_bounds__(256) void dct_hash_windows_kernel(WindowsSource src
                     if (out_dontcare && i == 0) out_dontcare[slot] = sh.dc[parity][half][0] + sh.dc[parity][half][1];
                 }
             }
+            if constexpr (PLANES) {
+                if ((tid & 127u) >= 16 && (tid & 127u) < 32) {  // lanes 16 ... 31 of the same wave: the plane, read out and cleared in the same way
+                    const uint32_t i = (tid & 127u) - 16;
+                    uint32_t *zwords = zw + (parity * 2 + half) * 32;
+                    const unsigned long long z = (unsigned long long)zwords[2 * i] | ((unsigned long long)zwords[2 * i + 1] << 32);
+                    zwords[2 * i] = 0u;
+                    zwords[2 * i + 1] = 0u;
+                    if (kk < k_ready) out_zero[((size_t)clip * n_win + kk) * 16 + i] = z;
+                }
+            }
             parity ^= 1u;
         }
         k = k_ready;
@@ -2905,14 +2949,20 @@ __global__ __launch_bounds__(256) void dct_hash_windows_kernel(WindowsSource src
 }
 
 hipError_t launch_dct_hash_windows(const WindowsFrames &f, size_t n_clips, const WindowsPlan &plan, const double *cos_table, uint64_t *out_hashes,
-                                   uint32_t *out_dontcare, hipStream_t stream)
+                                   uint32_t *out_dontcare, hipStream_t stream, uint64_t *out_zero)
 {
     if (n_clips == 0 || plan.n_win == 0) return hipSuccess;
     const WindowsSource src{f.base, f.tail, f.clip_stride, f.chunk_stride, f.frame_stride, f.tail_clip_stride, f.main_frames, f.tail_first};
     const uint64_t groups = (uint64_t)n_clips * plan.n_seg;
     for (uint64_t g0 = 0; g0 < groups; g0 += kMaxWindowGroupsPerLaunch) {
         const uint32_t grid = (uint32_t)std::min<uint64_t>(kMaxWindowGroupsPerLaunch, groups - g0);
-        if (f.dwords)
+        if (out_zero && f.dwords)
+            hipLaunchKernelGGL((dct_hash_windows_kernel<true, true>), dim3(grid), dim3(256), 0, stream, src, plan.stride, plan.n_win, plan.per_seg, plan.n_seg, g0,
+                               cos_table, out_hashes, out_dontcare, out_zero);
+        else if (out_zero)
+            hipLaunchKernelGGL((dct_hash_windows_kernel<false, true>), dim3(grid), dim3(256), 0, stream, src, plan.stride, plan.n_win, plan.per_seg, plan.n_seg, g0,
+                               cos_table, out_hashes, out_dontcare, out_zero);
+        else if (f.dwords)
             hipLaunchKernelGGL(dct_hash_windows_kernel<true>, dim3(grid), dim3(256), 0, stream, src, plan.stride, plan.n_win, plan.per_seg, plan.n_seg, g0,
                                cos_table, out_hashes, out_dontcare);
         else
@@ -3041,6 +3091,33 @@ hipError_t launch_hash_variants(const uint64_t *hashes, const uint64_t *zero, si
     }
     const size_t n_words = n * 16;
     hipLaunchKernelGGL(hash_variants_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, stream, hashes, zero, n_words, packed, n_variants, out);
+    return hipGetLastError();
+}
+
+// ---- the variant of a set of window hashes ----------------------------------------------------------------------------------
+// out[row] = (H[src] ^ M_v) & ~Z[src], src = window_variant_source(row): one thread per 64-bit word of rows [row0, row0 + n_rows), the masks of
+// hash_variants_kernel; the thread of a row's word 0 carries the row's skip byte along.
+__global__ __launch_bounds__(256) void window_variants_kernel(const uint64_t *__restrict__ hashes, const uint64_t *__restrict__ zero,
+                                                              const uint32_t *__restrict__ first, uint32_t n_videos, const uint8_t *__restrict__ skip,
+                                                              uint32_t variant, uint32_t row0, size_t n_words, uint64_t *__restrict__ out,
+                                                              uint8_t *__restrict__ out_skip)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_words) return;
+    const uint32_t row = row0 + (uint32_t)(i >> 4), k = (uint32_t)(i & 15);
+    const uint32_t src = window_variant_source(first, n_videos, row, variant);
+    out[(size_t)row * 16 + k] = (hashes[(size_t)src * 16 + k] ^ c_variant_masks.m[variant & 7u][k]) & ~zero[(size_t)src * 16 + k];
+    if (skip && k == 0) out_skip[row] = skip[src];
+}
+
+hipError_t launch_window_variants(const uint64_t *hashes, const uint64_t *zero, const uint32_t *first, uint32_t n_videos, const uint8_t *skip,
+                                  uint32_t variant, uint32_t row0, uint32_t n_rows, uint64_t *out, uint8_t *out_skip, hipStream_t stream)
+{
+    if (n_rows == 0 || n_videos == 0) return hipSuccess;
+    if (variant > 7 || (skip && !out_skip)) return hipErrorInvalidValue;
+    const size_t n_words = (size_t)n_rows * 16;  // < 2^36: at most 2^28 workgroups
+    hipLaunchKernelGGL(window_variants_kernel, dim3((uint32_t)((n_words + 255) / 256)), dim3(256), 0, stream, hashes, zero, first, n_videos, skip, variant, row0,
+                       n_words, out, out_skip);
     return hipGetLastError();
 }
 

@@ -6,6 +6,7 @@
 
 #include "../../include/vdf.h"
 #include "hash_variant.h"
+#include "window_variant.h"
 #include "resize_dispatch.h"
 #include "windows_plan.h"
 #include "align_plan.h"
@@ -241,8 +242,13 @@ struct WindowsFrames {
     bool dwords;
 };
 // out_hashes[16 (c n_win + k)] = the hash of frames [k stride, k stride + 16) of clip c; out_dontcare (nullable) at c n_win + k
+// out_zero (nullable): the kernel's PLANES form, the windows' zero planes at out_zero + 16 (c n_win + k); null: the plain form, as before
 hipError_t launch_dct_hash_windows(const WindowsFrames &f, size_t n_clips, const WindowsPlan &plan, const double *cos_table, uint64_t *out_hashes,
-                                   uint32_t *out_dontcare, hipStream_t stream);
+                                   uint32_t *out_dontcare, hipStream_t stream, uint64_t *out_zero = nullptr);
+// ---- the variant of a set of window hashes (window_variant.h) ------------------------------------------------------------------
+// rows [row0, row0 + n_rows) = [first[0], first[n_videos]) of out (and of out_skip, if skip is given) from hashes / zero / skip; variant 0 ... 7
+hipError_t launch_window_variants(const uint64_t *hashes, const uint64_t *zero, const uint32_t *first, uint32_t n_videos, const uint8_t *skip,
+                                  uint32_t variant, uint32_t row0, uint32_t n_rows, uint64_t *out, uint8_t *out_skip, hipStream_t stream);
 // ---- alignment of videos on their window hashes (align_plan.h, align.hip) ---------------------------------------------------
 // One chunk of pairs (align_plan.h: align_next_chunk): band kernel, per-pair reduction, dense list in (a, b) order.  All pointers are device
 // pointers; scratch holds align_scratch_bytes(n_pairs, n_units).  *dense_out / *total_out: where in scratch the records and their number are

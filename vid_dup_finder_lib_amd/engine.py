@@ -117,6 +117,76 @@ def align_windows_host(a_hashes, a_first, b_hashes=None, b_first=None, tol_int: 
     return out[:min(n.value, out.size)], int(n.value)
 
 
+# one record of the align-variants calls (include/vdf.h: vdf_alignment_variant, 28 bytes)
+ALIGN_VARIANT_DTYPE = np.dtype(ALIGN_DTYPE.descr + [("variant", "<u4")])
+
+
+def _zero_arg(zero, hashes_arg_rows: int):
+    """A zero plane beside its hashes, as the C ABI takes it (None stays NULL: the library says what is missing)."""
+    if zero is None:
+        return None
+    z = np.ascontiguousarray(zero, dtype=np.uint64).reshape(-1, HASH_WORDS)
+    if z.shape[0] != hashes_arg_rows:
+        raise ValueError("one zero plane per window hash")
+    return z
+
+
+def _align_variants_host_args(a_hashes, a_zero, a_first, b_hashes, b_zero, b_first, a_skip, b_skip):
+    """_align_host_args with the zero planes in their places: (a_hashes, a_zero, a_first, n_a, a_skip, b_hashes, b_zero, b_first, n_b, b_skip)."""
+    keep, args = _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+    az = _zero_arg(a_zero, keep[0].shape[0])
+    bz = None if b_hashes is None else _zero_arg(b_zero, keep[3].shape[0])
+    keep += [az, bz]
+    # an empty plane must not read as a missing one: numpy gives an empty array a non-null address, ctypes turns 0 into NULL
+    ptr = lambda z: None if z is None else (z.ctypes.data or keep[1].ctypes.data)
+    return keep, [args[0], ptr(az), args[1], args[2], args[3], args[4], ptr(bz), args[5], args[6], args[7]]
+
+
+def _variant_mask(variant_mask) -> int:
+    return _align_uint32("variant_mask", variant_mask)
+
+
+def align_windows_variants_host(a_hashes, a_first, a_zero=None, b_hashes=None, b_first=None, b_zero=None, tol_int: int = 350, min_run: int = 1,
+                                variant_mask: int = 2, a_skip=None, b_skip=None, capacity: int = 1024):
+    """vdf_align_windows_variants_host: align_windows_host against the variants of B named by variant_mask (bits 1 ... 7), in plain C++ on the
+    CPU.  b_hashes None: self mode, B = A with a_zero.  -> (records [min(found, capacity)] of ALIGN_VARIANT_DTYPE in (variant, a, b) order, found)."""
+    lib = _capi.load()
+    keep, args = _align_variants_host_args(a_hashes, a_zero, a_first, b_hashes, b_zero, b_first, a_skip, b_skip)
+    out = np.zeros(max(int(capacity), 0), ALIGN_VARIANT_DTYPE)
+    n = C.c_size_t(0)
+    rc = lib.vdf_align_windows_variants_host(*args, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run), _variant_mask(variant_mask),
+                                             out.ctypes.data if out.size else None, out.size, C.byref(n))
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_align_windows_variants_host: bad argument")
+    return out[:min(n.value, out.size)], int(n.value)
+
+
+def window_variants_host(hashes, zero, first, variant: int, skip=None):
+    """vdf_window_variants_host: the variant of a set of window hashes (hashes / zero [windows, 16] u64, first [videos + 1]) on the CPU ->
+    hashes [windows, 16] (and the skip bytes carried along, if skip is given).  Rows outside [first[0], first[-1]) come back zero."""
+    lib = _capi.load()
+    h = np.ascontiguousarray(hashes, dtype=np.uint64).reshape(-1, HASH_WORDS)
+    z = np.ascontiguousarray(zero, dtype=np.uint64).reshape(-1, HASH_WORDS)
+    f = np.ascontiguousarray(first, dtype=np.uint32).reshape(-1)
+    if f.size == 0 or z.shape != h.shape or int(f.max()) > h.shape[0]:
+        raise ValueError("hashes and zero [windows, 16], first [videos + 1] within them")
+    k = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8).reshape(-1)
+    if k is not None and k.size != h.shape[0]:
+        raise ValueError("one skip byte per window")
+    rows = h.shape[0]
+    if rows == 0:  # videos without windows: numpy gives an empty array a null address, which the library takes for a missing argument
+        h, z, k = np.zeros((1, HASH_WORDS), np.uint64), np.zeros((1, HASH_WORDS), np.uint64), None if k is None else np.zeros(1, np.uint8)
+    out = np.zeros_like(h)
+    out_k = None if k is None else np.zeros_like(k)
+    rc = lib.vdf_window_variants_host(h.ctypes.data, z.ctypes.data, f.ctypes.data, f.size - 1, None if k is None else k.ctypes.data,
+                                      _align_uint32("variant", variant), out.ctypes.data, None if k is None else out_k.ctypes.data)
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_window_variants_host: bad argument")
+    out = out[:rows]
+    out_k = None if k is None else out_k[:rows]
+    return out if k is None else (out, out_k)
+
+
 class Engine:
     """One context: one GPU (`device`, default LOCAL_RANK or 0), or - `devices=[...]` - ONE context over several GPUs
     of the node (vdf_ctx_create_multi: the host-array calls fan out inside the library, the *_shards methods take
@@ -282,6 +352,65 @@ class Engine:
         cs = fs * frames_per_clip if clip_stride is None else clip_stride
         self._check(self.lib.vdf_hash_windows_u8_device(self.ctx, d_frames, n_clips, frames_per_clip, w, h, fs, cs, stride, d_out,
                                                         d_dontcare or None, stream or None))
+
+    def hash_windows_planes(self, frames: np.ndarray, stride: int = 1, want_dontcare: bool = False):
+        """hash_windows plus the zero plane of every window (vdf_hash_windows_u8_planes): -> (hashes [n_clips, n_win, 16] u64, zero
+        [n_clips, n_win, 16] u64 [, dontcare]); bit i of a plane is set iff coefficient i of the window is exactly 0.0.  The hashes are
+        hash_windows'."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.ndim != 4:
+            raise ValueError("frames must be [n_clips, n_frames, H, W]")
+        nc, nf, h, w = frames.shape
+        stride = _window_stride(stride)
+        n_win = int(self.lib.vdf_hash_window_count(nf, stride))
+        out = np.zeros((nc, n_win, HASH_WORDS), np.uint64)
+        zero = np.zeros((nc, n_win, HASH_WORDS), np.uint64)
+        dc = np.zeros((nc, n_win), np.uint32) if want_dontcare else None
+        self._check(self.lib.vdf_hash_windows_u8_planes(self.ctx, frames.ctypes.data, nc, nf, w, h, w * h, nf * w * h, stride, out.ctypes.data,
+                                                        dc.ctypes.data if want_dontcare else None, zero.ctypes.data))
+        return (out, zero, dc) if want_dontcare else (out, zero)
+
+    def hash_windows_planes_device(self, d_frames: int, n_clips: int, frames_per_clip: int, w: int, h: int, stride: int, d_out: int, d_zero: int,
+                                   d_dontcare: int = 0, frame_stride: Optional[int] = None, clip_stride: Optional[int] = None, stream: int = 0):
+        """d_out and d_zero: n_clips x n_win x 16 words each."""
+        stride = _window_stride(stride)
+        fs = w * h if frame_stride is None else frame_stride
+        cs = fs * frames_per_clip if clip_stride is None else clip_stride
+        self._check(self.lib.vdf_hash_windows_u8_planes_device(self.ctx, d_frames, n_clips, frames_per_clip, w, h, fs, cs, stride, d_out,
+                                                               d_dontcare or None, d_zero or None, stream or None))
+
+    # --------------------------------------------- flipped and reversed stretches (include/vdf.h, DESIGN.md 4.11)
+    def window_variants(self, d_hashes: int, d_zero: int, d_first: int, n_videos: int, variant: int, d_out: int, d_skip: int = 0, d_out_skip: int = 0,
+                        stream: int = 0):
+        """vdf_window_variants_device: d_out (and d_out_skip) = the variant set of the window hashes at d_hashes / d_zero / d_first - with
+        bit 2 of the variant every video's rows in reversed order.  Device pointers; ordered on stream."""
+        self._check(self.lib.vdf_window_variants_device(self.ctx, d_hashes or None, d_zero or None, d_first or None, int(n_videos), d_skip or None,
+                                                        _align_uint32("variant", variant), d_out or None, d_out_skip or None, stream or None))
+
+    def align_windows_variants(self, a_hashes, a_first, a_zero=None, b_hashes=None, b_first=None, b_zero=None, tol_int: int = 350, min_run: int = 1,
+                               variant_mask: int = 2, a_skip=None, b_skip=None, capacity: int = 1024):
+        """align_windows against the variants of B named by variant_mask (vdf_align_windows_variants; bits 1 ... 7): b_zero is B's zero planes;
+        b_hashes None: self mode, B = A with a_zero.  offset and start_a + offset count in the DERIVED order of b (reversed with bit 2).
+        -> (records [min(found, capacity)] of ALIGN_VARIANT_DTYPE in (variant, a, b) order, found)."""
+        keep, args = _align_variants_host_args(a_hashes, a_zero, a_first, b_hashes, b_zero, b_first, a_skip, b_skip)
+        out = np.zeros(max(int(capacity), 0), ALIGN_VARIANT_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_variants(self.ctx, *args, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                                        _variant_mask(variant_mask), out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_variants_device(self, d_a_hashes: int, d_a_first: int, n_a: int, d_a_zero: int = 0, d_b_hashes: int = 0, d_b_first: int = 0,
+                                      n_b: int = 0, d_b_zero: int = 0, tol_int: int = 350, min_run: int = 1, variant_mask: int = 2, d_a_skip: int = 0,
+                                      d_b_skip: int = 0, capacity: int = 1024, stream: int = 0):
+        """The same on device arrays (d_b_hashes 0: self mode); the records come back to the host, the call waits for its own work."""
+        out = np.zeros(max(int(capacity), 0), ALIGN_VARIANT_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_variants_device(self.ctx, d_a_hashes or None, d_a_zero or None, d_a_first or None, int(n_a), d_a_skip or None,
+                                                               d_b_hashes or None, d_b_zero or None, d_b_first or None, int(n_b), d_b_skip or None,
+                                                               _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                                               _variant_mask(variant_mask), out.ctypes.data if out.size else None, out.size, C.byref(n),
+                                                               stream or None))
+        return out[:min(n.value, out.size)], int(n.value)
 
     # --------------------------------------------- videos aligned on their window hashes (include/vdf.h, DESIGN.md 4.10)
     def align_windows(self, a_hashes, a_first, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1, a_skip=None, b_skip=None,

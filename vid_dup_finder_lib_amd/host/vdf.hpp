@@ -302,6 +302,110 @@ public:
         }
     }
 
+    // hash_windows with the zero plane of every window (vdf_hash_windows_u8_planes): the same words, and every VideoHash
+    // carries zero() - what align_windows_variants needs of the flipped side.
+    static std::vector<std::vector<VideoHash>> hash_windows_planes(const uint8_t *frames, size_t n_videos, uint32_t frames_per_video, uint32_t w, uint32_t h,
+                                                                   uint32_t stride, const std::vector<std::string> &src_paths,
+                                                                   const std::vector<uint32_t> &durations, Context *ctx_opt = nullptr)
+    {
+        if (frames_per_video < VDF_DCT_SIZE) throw Error::not_enough_frames();
+        if (src_paths.size() < n_videos || durations.size() < n_videos) throw std::invalid_argument("a path and a duration per video");
+        Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+        const size_t n_win = vdf_hash_window_count(frames_per_video, stride), fs = (size_t)w * h;
+        std::vector<uint64_t> words(n_videos * n_win * VDF_HASH_WORDS), zero(words.size());
+        const int rc = vdf_hash_windows_u8_planes(ctx.get(), frames, n_videos, frames_per_video, w, h, fs, fs * frames_per_video, stride, words.data(), nullptr,
+                                                  zero.data());
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+        std::vector<std::vector<VideoHash>> out(n_videos);
+        for (size_t i = 0; i < n_videos; i++)
+            for (size_t k = 0; k < n_win; k++) {
+                std::array<uint64_t, VDF_HASH_WORDS> hw, zw;
+                std::copy(words.begin() + (i * n_win + k) * VDF_HASH_WORDS, words.begin() + (i * n_win + k + 1) * VDF_HASH_WORDS, hw.begin());
+                std::copy(zero.begin() + (i * n_win + k) * VDF_HASH_WORDS, zero.begin() + (i * n_win + k + 1) * VDF_HASH_WORDS, zw.begin());
+                out[i].emplace_back(hw, src_paths[i], durations[i], zw);
+            }
+        return out;
+    }
+    static void hash_windows_planes_device(Context &ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h,
+                                           size_t frame_stride, size_t clip_stride, uint32_t stride, uint64_t *d_out, uint64_t *d_zero,
+                                           uint32_t *d_dontcare = nullptr, void *stream = nullptr)
+    {
+        const int rc = vdf_hash_windows_u8_planes_device(ctx.get(), d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, stride, d_out, d_dontcare,
+                                                         d_zero, stream);
+        if (rc == VDF_E_NOT_ENOUGH_FRAMES) throw Error::not_enough_frames();
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+    }
+    // The variant of a set of resident window hashes (vdf_window_variants_device): d_out (and d_out_skip, iff d_skip) = the set flipped by
+    // `flip`, every video's rows in reversed order with FlipT.
+    static void window_variants(Context &ctx, const uint64_t *d_hashes, const uint64_t *d_zero, const uint32_t *d_first, size_t n_videos, uint32_t flip,
+                                uint64_t *d_out, const uint8_t *d_skip = nullptr, uint8_t *d_out_skip = nullptr, void *stream = nullptr)
+    {
+        const int rc = vdf_window_variants_device(ctx.get(), d_hashes, d_zero, d_first, n_videos, d_skip, flip, d_out, d_out_skip, stream);
+        if (rc == VDF_E_INVAL) throw std::invalid_argument(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+    }
+
+    // align_windows against the flipped videos of B (vdf_align_windows_variants): for every flip of `flips` (each 1 ... 7) the
+    // records of align_windows on the window hashes of the flipped b, in (variant, a, b) order.  The hashes of the flipped side (windows_b, or
+    // windows_a when windows_b is null) need their zero planes (hash_windows_planes), else Error::VidProc.  offset and start_a + offset count in
+    // the DERIVED order of b: with FlipT derived window j is b's window Nb - 1 - j, and the stretch runs backwards through b.
+    static std::vector<vdf_alignment_variant> align_windows_variants(const std::vector<std::vector<VideoHash>> &windows_a,
+                                                                     const std::vector<std::vector<VideoHash>> *windows_b, uint32_t tol_int,
+                                                                     const std::vector<uint32_t> &flips, uint32_t min_run = 1,
+                                                                     const std::vector<uint8_t> *skip_a = nullptr, const std::vector<uint8_t> *skip_b = nullptr,
+                                                                     Context *ctx_opt = nullptr)
+    {
+        auto csr = [](const std::vector<std::vector<VideoHash>> &w, std::vector<uint64_t> &words, std::vector<uint64_t> *zero, std::vector<uint32_t> &first) {
+            first.assign(1, 0u);
+            for (const auto &video : w) {
+                for (const VideoHash &h : video) {
+                    words.insert(words.end(), h.words().begin(), h.words().end());
+                    if (zero) {
+                        if (!h.zero()) throw Error::vid_proc("align_windows_variants needs the zero plane of every hash of the flipped side (hash_windows_planes)");
+                        zero->insert(zero->end(), h.zero()->begin(), h.zero()->end());
+                    }
+                }
+                first.push_back((uint32_t)(words.size() / VDF_HASH_WORDS));
+            }
+            if (words.empty()) words.push_back(0);  // a non-null pointer for an empty side
+            if (zero && zero->empty()) zero->push_back(0);
+        };
+        uint32_t mask = 0;
+        for (uint32_t f : flips) {
+            if (f < 1 || f > 7) throw std::invalid_argument("flips are non-empty combinations of FlipX, FlipY, FlipT");
+            mask |= 1u << f;
+        }
+        std::vector<uint64_t> wa, wb, za, zb;
+        std::vector<uint32_t> fa, fb;
+        csr(windows_a, wa, windows_b ? nullptr : &za, fa);
+        if (windows_b) csr(*windows_b, wb, &zb, fb);
+        if (skip_a && skip_a->size() != fa.back()) throw std::invalid_argument("one skip byte per window of A");
+        if (windows_b && skip_b && skip_b->size() != fb.back()) throw std::invalid_argument("one skip byte per window of B");
+        const uint8_t *ska = skip_a && !skip_a->empty() ? skip_a->data() : nullptr, *skb = windows_b && skip_b && !skip_b->empty() ? skip_b->data() : nullptr;
+        const size_t n_a = windows_a.size(), n_b = windows_b ? windows_b->size() : 0;
+        const uint64_t cells = (uint64_t)fa.back() * (windows_b ? fb.back() : fa.back()) * flips.size();
+        std::vector<vdf_alignment_variant> out(1024);
+        for (;;) {
+            size_t found = 0;
+            int rc;
+            if (!ctx_opt && cells <= (1u << 16))
+                rc = vdf_align_windows_variants_host(wa.data(), windows_b ? nullptr : za.data(), fa.data(), n_a, ska, windows_b ? wb.data() : nullptr,
+                                                     windows_b ? zb.data() : nullptr, fb.data(), n_b, skb, tol_int, min_run, mask, out.data(), out.size(), &found);
+            else {
+                Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+                rc = vdf_align_windows_variants(ctx.get(), wa.data(), windows_b ? nullptr : za.data(), fa.data(), n_a, ska, windows_b ? wb.data() : nullptr,
+                                                windows_b ? zb.data() : nullptr, fb.data(), n_b, skb, tol_int, min_run, mask, out.data(), out.size(), &found);
+                if (rc != VDF_OK && rc != VDF_E_INVAL) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            }
+            if (rc != VDF_OK)
+                throw std::invalid_argument("align_windows_variants: min_run of 0, a video of more than 2^20 windows, more than 2^24 pairs, or a multi-GPU context");
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
     // from_frame_stacks with the zero planes (vdf_hash_clips_u8_planes): the hashes are the same words and can be flipped.  crops (optional, one
     // l, r, t, b per clip - e.g. what from_frame_stacks_letterbox detected): hash, plane and every flip are those of the CROPPED clip.
     static std::vector<VideoHash> from_frame_stacks_planes(const std::vector<FrameStack> &stacks, const std::vector<std::array<uint32_t, 4>> *crops = nullptr,
