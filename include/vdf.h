@@ -266,7 +266,8 @@ int vdf_hash_windows_u8_planes_device(vdf_ctx *ctx, const uint8_t *d_frames, siz
  * waits for its own work.  vdf_align_windows: host arrays; uploads them and calls the device form.
  * vdf_align_windows_host: no context, no GPU - the definition above in plain C++ (every diagonal walked, XOR + popcount):
  * the CPU-tested statement of the semantics, for tiny inputs and tests.
- * Known limit: ONE stretch per pair - a video that holds two separate excerpts of another reports the better one.
+ * ONE stretch per pair here - a video that holds two separate excerpts of another reports the better one; every shared stretch of a
+ * pair: vdf_align_windows_stretches* below.
  * Flipped and reversed stretches: vdf_align_windows_variants* below.  Not here: multi-GPU contexts. */
 typedef struct vdf_alignment { /* 24 bytes */
     uint32_t a;                /* video index in A */
@@ -286,6 +287,53 @@ int vdf_align_windows_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uin
                              const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b,
                              const uint8_t *d_b_skip, uint32_t tol_int, uint32_t min_run, vdf_alignment *out,
                              size_t capacity, size_t *n_out, void *stream);
+
+/* ---- EVERY shared stretch of a pair, not only the best one -------------------------------------------------
+ * An ad break cut out of a re-upload leaves two stretches at two offsets; a compilation that uses a source twice, or a loop, repeats one.
+ * The definition is vdf_align_windows' word for word - cell rule, run, score, ties, min_run, skip bytes, the tol clamp, self mode, 2^20
+ * windows per video, 2^24 pairs per call - and then, for one pair (a, b) of Na x Nb windows:
+ *   - RANK 0 is the record vdf_align_windows reports;
+ *   - after a stretch (offset, start_a, n) is reported, with start_b = start_a + offset, its RECTANGLE
+ *       [max(0, start_a - guard), min(Na, start_a + n + guard)) x [max(0, start_b - guard), min(Nb, start_b + n + guard))
+ *     (bounds in 64-bit arithmetic: nothing wraps) becomes misses for all later ranks.  A cell is masked only if ka lies in the A range AND
+ *     kb in the B range of the SAME rectangle: the same rows of A matched against another part of B stay visible, so a source used twice in
+ *     a compilation gives two records;
+ *   - a masked cell ends a run exactly as a non-matching cell does: a diagonal that crosses a rectangle yields separate runs before and
+ *     after it, each of which competes only if it has min_run windows of its own;
+ *   - RANK r is the best run of the matrix masked by the rectangles of ranks 0 ... r - 1;
+ *   - a pair stops at the first rank without a competing run, or after max_stretches ranks.
+ * max_stretches: 1 ... 8.  guard: 0 ... 2^20 windows; it widens the rectangles so that the neighbouring diagonals of slowly changing content
+ * - windows one frame apart share 15 of their 16 frames - are not reported as stretches of their own.
+ * out: HOST buffer of `capacity` records ordered by (a, b, rank).  *n_out = the number found; if it exceeds capacity the first `capacity`
+ * records in that order are valid - VDF_OK, as the align calls.  With max_stretches == 1 the records are vdf_align_windows' field for
+ * field, with rank 0.
+ * Errors: those of vdf_align_windows in their order; then max_stretches outside 1 ... 8; then guard above 2^20; then a multi-GPU context -
+ * all VDF_E_INVAL.
+ * vdf_align_windows_stretches_host: no context, no GPU - the definition above in plain C++, the CPU-tested statement of the semantics.
+ * vdf_align_windows_stretches: host arrays, uploaded as vdf_align_windows uploads them.  vdf_align_windows_stretches_device: DEVICE
+ * pointers, out on the host; the call waits for its own work.
+ * Not offered: more than one stretch per pair against the flipped variants (vdf_align_windows_variants* stays one per pair). */
+typedef struct vdf_alignment_stretch { /* 28 bytes */
+    uint32_t a;                /* the six fields of vdf_alignment */
+    uint32_t b;
+    int32_t offset;
+    uint32_t start_a;
+    uint32_t n_windows;
+    uint32_t dist_sum;
+    uint32_t rank;             /* 0 ... max_stretches - 1: 0 is the pair's best stretch */
+} vdf_alignment_stretch;
+int vdf_align_windows_stretches_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                     const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                                     uint32_t tol_int, uint32_t min_run, uint32_t max_stretches, uint32_t guard,
+                                     vdf_alignment_stretch *out, size_t capacity, size_t *n_out);
+int vdf_align_windows_stretches(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                                uint32_t tol_int, uint32_t min_run, uint32_t max_stretches, uint32_t guard,
+                                vdf_alignment_stretch *out, size_t capacity, size_t *n_out);
+int vdf_align_windows_stretches_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a,
+                                       const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b,
+                                       const uint8_t *d_b_skip, uint32_t tol_int, uint32_t min_run, uint32_t max_stretches,
+                                       uint32_t guard, vdf_alignment_stretch *out, size_t capacity, size_t *n_out, void *stream);
 
 /* ---- mirrored, flipped and reversed STRETCHES: window hashes with their zero planes -----------------------
  * A mirrored re-upload with its intro trimmed: the variant search sees only frames 0 ... 15 of a file, the align calls only unflipped

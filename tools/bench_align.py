@@ -24,7 +24,17 @@ backend's measured 7.5e11 pairs/s (README): the yardstick of this inner loop, no
 What alignment against the variants costs, on the 1000 x 49 self shape, plain corpus, with random zero planes (5 % of the
 bits): vdf_align_windows_variants_device with 1 and with 3 variants beside ONE vdf_align_windows_device call and one
 vdf_window_variants_device call, all of this build, same protocol.  Expected: plain x variants + derive x variants.  Reported; nothing is
-gated."""
+gated.
+
+    python tools/bench_align.py --stretches --parent-lib tools/_libvdf_parent.so [--out profiles/align_stretches.txt]
+
+What reporting every stretch of a pair costs, on the 1000 x 49 self shape, device-resident input, max_stretches 4, guard 2.
+Leg (a): the shape's random hashes WITHOUT planted copies - no pair has a record, so no second round is launched and the call runs the plain
+kernel once, as vdf_align_windows_device does: vdf_align_windows_stretches_device of this build beside vdf_align_windows_device of the parent
+commit's library (without --parent-lib this build's stands in and is labelled so).  GATE: the new call's median is at most the parent's
+median times the parent's own max / min over its 12 calls.  Leg (b): the same hashes with 0.99 % of the pairs (90 groups of 11 videos) sharing
+two planted stretches of 12 windows on two different diagonals: the time, the rounds and the surviving pairs per round, beside leg (a) - no
+gate."""
 import argparse
 import ctypes as C
 import json
@@ -287,8 +297,122 @@ def variants_main(args):
     return 0
 
 
-def run_child(lib, leg, variants=False):
-    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--lib", lib, "--leg", leg] + (["--variants"] if variants else []),
+STRETCH_DTYPE = np.dtype(ALIGN_DTYPE.descr + [("rank", "<u4")])
+STRETCH_MAX, STRETCH_GUARD, STRETCH_GROUP, STRETCH_LEN = 4, 2, 11, 12
+
+
+def stretches_corpus(planted):
+    """the 1000 x 49 self shape: random hashes; planted: in every group of 11 consecutive videos (90 groups) all videos hold the same two
+    stretches of 12 windows, video i of a group at windows i and 35 - i - so the pair (i, j) shares them on the diagonals j - i and i - j"""
+    n_a, n_win, _ = SHAPES[VARIANTS_SHAPE]
+    rng = np.random.default_rng([13, n_a, n_win])
+    a, fa = random_hashes(rng, n_a * n_win), np.arange(n_a + 1, dtype=np.uint32) * n_win
+    pairs = 0
+    if planted:
+        for g in range(n_a // STRETCH_GROUP):
+            one, two = random_hashes(rng, STRETCH_LEN), random_hashes(rng, STRETCH_LEN)
+            for i in range(STRETCH_GROUP):
+                v = (g * STRETCH_GROUP + i) * n_win
+                a[v + i:v + i + STRETCH_LEN] = flip_bits(rng, one)
+                a[v + 35 - i:v + 35 - i + STRETCH_LEN] = flip_bits(rng, two)
+            pairs += STRETCH_GROUP * (STRETCH_GROUP - 1) // 2
+    return a, fa, pairs
+
+
+def stretches_child(args):
+    """one leg of --stretches: parent-align (vdf_align_windows_device of args.lib) | stretches-a | stretches-b"""
+    import torch
+
+    lib = C.CDLL(args.lib)
+    lib.vdf_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    lib.vdf_last_error.restype = C.c_char_p
+    lib.vdf_last_error.argtypes = [C.c_void_p]
+    ctx = C.c_void_p()
+    assert lib.vdf_ctx_create(0, C.byref(ctx)) == 0, lib.vdf_last_error(None)
+    P = C.c_void_p
+    n_a, n_win, _ = SHAPES[VARIANTS_SHAPE]
+    pairs = n_a * (n_a - 1) // 2
+    a, fa, _ = stretches_corpus(args.leg == "stretches-b")
+    d_a, d_fa = torch.from_numpy(a.view(np.int64)).cuda(), torch.from_numpy(fa.view(np.int32)).cuda()
+    torch.cuda.synchronize()
+    n_out = C.c_size_t(0)
+    if args.leg == "parent-align":
+        lib.vdf_align_windows_device.argtypes = [P, P, P, C.c_size_t, P, P, P, C.c_size_t, P, C.c_uint32, C.c_uint32, P, C.c_size_t, C.POINTER(C.c_size_t), P]
+        out = np.zeros(pairs, ALIGN_DTYPE)
+
+        def run():
+            return lib.vdf_align_windows_device(ctx, d_a.data_ptr(), d_fa.data_ptr(), n_a, None, None, None, 0, None, TOL, MIN_RUN, out.ctypes.data, len(out), C.byref(n_out), None)
+    else:
+        lib.vdf_align_windows_stretches_device.argtypes = [P, P, P, C.c_size_t, P, P, P, C.c_size_t, P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P, C.c_size_t,
+                                                           C.POINTER(C.c_size_t), P]
+        out = np.zeros(pairs, STRETCH_DTYPE)  # room for one record per pair: the planted legs find far fewer
+
+        def run():
+            return lib.vdf_align_windows_stretches_device(ctx, d_a.data_ptr(), d_fa.data_ptr(), n_a, None, None, None, 0, None, TOL, MIN_RUN, STRETCH_MAX, STRETCH_GUARD,
+                                                          out.ctypes.data, len(out), C.byref(n_out), None)
+    times = []
+    for r in range(REPEATS + 1):
+        t0 = time.perf_counter()
+        rc = run()
+        if r:
+            times.append(time.perf_counter() - t0)
+        assert rc == 0, (rc, lib.vdf_last_error(ctx))
+    res = {"times": times, "records": int(n_out.value)}
+    if args.leg != "parent-align":
+        rec = out[:n_out.value]
+        res["per_rank"] = [int((rec["rank"] == r).sum()) for r in range(STRETCH_MAX)]
+    print("RESULT " + json.dumps(res))
+
+
+def stretches_main(args):
+    parent_lib = os.path.abspath(args.parent_lib) if args.parent_lib else args.lib
+    legs = [("parent-align", parent_lib), ("stretches-a", args.lib), ("stretches-b", args.lib)]
+    got = {leg: {"times": []} for leg, _ in legs}
+    for _ in range(ROUNDS):
+        for leg, lib in legs:
+            v = run_child(lib, leg, mode="--stretches")
+            got[leg]["times"] += v["times"]
+            got[leg].update({k: v[k] for k in v if k != "times"})
+    n_a, n_win, _ = SHAPES[VARIANTS_SHAPE]
+    pairs = n_a * (n_a - 1) // 2
+    _, _, planted = stretches_corpus(True)
+    med = {leg: statistics.median(got[leg]["times"]) for leg, _ in legs}
+    ms = lambda ts: f"min {min(ts) * 1e3:9.3f}  median {statistics.median(ts) * 1e3:9.3f}  max {max(ts) * 1e3:9.3f} ms ({len(ts)} calls)"
+    pt = got["parent-align"]["times"]
+    spread = max(pt) / min(pt)
+    bound = med["parent-align"] * spread
+    held = med["stretches-a"] <= bound
+    whose = "the PARENT commit's library" if args.parent_lib else "THIS build's library (no --parent-lib: not the parent commit)"
+
+    def rounds(per_rank):
+        """round 0 always runs; round r runs on the pairs that had a record of rank r - 1, while r < max_stretches"""
+        out = [f"round 0: {pairs} pairs"]
+        for r in range(1, STRETCH_MAX):
+            if per_rank[r - 1] == 0:
+                break
+            out.append(f"round {r}: {per_rank[r - 1]} surviving pairs")
+        return len(out), ", ".join(out)
+    ra, rb = rounds(got["stretches-a"]["per_rank"]), rounds(got["stretches-b"]["per_rank"])
+    lines = [f"tools/bench_align.py --stretches: {ROUNDS} rounds x {REPEATS} timed calls per leg (one warm-up per round), fresh process per leg and round, legs in turn",
+             f"{VARIANTS_SHAPE}: {pairs} pairs of videos, {n_a * n_win} windows, device-resident; tolerance {TOL}, min_run {MIN_RUN}, max_stretches {STRETCH_MAX}, guard {STRETCH_GUARD}",
+             "leg (a): random hashes without planted copies - no pair has a record",
+             f"  parent align   {ms(pt)}  {got['parent-align']['records']} records   (vdf_align_windows_device of {whose})",
+             f"  stretches (a)  {ms(got['stretches-a']['times'])}  {got['stretches-a']['records']} records; {ra[0]} round(s): {ra[1]}",
+             f"  GATE: median {med['stretches-a'] * 1e3:.3f} ms <= parent median {med['parent-align'] * 1e3:.3f} ms x parent max / min {spread:.3f} = {bound * 1e3:.3f} ms: "
+             f"{'HOLDS' if held else 'MISSED'}   (stretches / parent, medians = {med['stretches-a'] / med['parent-align']:.3f}x)",
+             f"leg (b): {planted} pairs ({100.0 * planted / pairs:.2f} %) share two planted stretches of {STRETCH_LEN} windows on two diagonals",
+             f"  stretches (b)  {ms(got['stretches-b']['times'])}  {got['stretches-b']['records']} records, per rank {got['stretches-b']['per_rank']}; {rb[0]} round(s): {rb[1]}",
+             f"  (b) - (a), medians = {(med['stretches-b'] - med['stretches-a']) * 1e3:.3f} ms for {rb[0] - 1} more round(s); no gate"]
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    return 0 if held else 1
+
+
+def run_child(lib, leg, variants=False, mode=None):
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--lib", lib, "--leg", leg] + (["--variants"] if variants else []) + ([mode] if mode else []),
                          capture_output=True, text=True, timeout=900)
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")]
     if out.returncode != 0 or not line:
@@ -300,15 +424,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--variants", action="store_true")
+    ap.add_argument("--stretches", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--lib", default=os.path.join(ROOT, "vid_dup_finder_lib_amd", "libvdf_hip.so"))
     ap.add_argument("--leg", default="align")
     args = ap.parse_args()
     if args.child:
-        return variants_child(args) if args.variants else child(args)
+        return stretches_child(args) if args.stretches else variants_child(args) if args.variants else child(args)
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "align_variants.txt" if args.variants else "align_windows.txt")
+        args.out = os.path.join(ROOT, "profiles", "align_stretches.txt" if args.stretches else "align_variants.txt" if args.variants else "align_windows.txt")
+    if args.stretches:
+        return stretches_main(args)
     if args.variants:
         return variants_main(args)
     search_lib = os.path.abspath(args.parent_lib) if args.parent_lib else args.lib

@@ -27,6 +27,8 @@ GROUPS = [
      r"vdf_hash_window"),
     ("the longest shared stretch of every pair of videos, on their window hashes: which videos share a stretch, at what offset, for how long",
      r"vdf_align_windows(_host|_device)?$"),
+    ("EVERY shared stretch of a pair, ranked: an ad break cut out, a source used twice - the best run, then the best outside its rectangle, ...",
+     r"vdf_align_windows_stretches"),
     ("mirrored / flipped / reversed STRETCHES: the variant of a set of window hashes from their zero planes, and alignment against it",
      r"vdf_window_variants|vdf_align_windows_variants"),
     ("mirrored / flipped / reversed duplicates, which the crate cannot see (lib.rs:102-111): the flipped clip's hash from the hash and the zero plane of the planes calls",

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import DEFAULT_SEARCH_TOLERANCE, HASH_BITS, HASH_WORDS, TOLERANCE_SCALING_FACTOR, VdfError
-from .engine import (ALIGN_DTYPE, ALIGN_VARIANT_DTYPE, Engine, align_windows_host, align_windows_variants_host, hamming_distance_words, hash_variant,
+from .engine import (ALIGN_DTYPE, ALIGN_STRETCH_DTYPE, ALIGN_VARIANT_DTYPE, Engine, align_windows_host, align_windows_stretches_host, align_windows_variants_host, hamming_distance_words, hash_variant,
                      tolerance_int)
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
@@ -601,7 +601,7 @@ def align(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoH
     `stride` (videos may differ in length); windows_b None: the videos of windows_a against each other, every pair once (a < b).
     Per pair of videos at most ONE Alignment, ordered by (a, b): the run of consecutive windows within `tolerance` on one diagonal
     (first_frame_b - first_frame_a constant) that maximises n_windows * (tol_int + 1) - sum of distances, of at least min_run windows
-    (include/vdf.h: vdf_align_windows; a video that holds two separate excerpts of another reports the better one).
+    (include/vdf.h: vdf_align_windows; a video that holds two separate excerpts of another reports the better one - align_all reports both).
     static_a / static_b: per video, one flag per window (static_windows); flagged windows abstain - static stretches match each other
     everywhere.  Calls of more than ALIGN_MAX_PAIRS pairs are split.  With no engine given, tiny inputs are walked on the CPU."""
     self_mode = windows_b is None
@@ -639,6 +639,87 @@ def align(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoH
     for r in rec:
         a, b, off, st, n, ds = (int(r[k]) for k in ("a", "b", "offset", "start_a", "n_windows", "dist_sum"))
         out.append(Alignment(a, b, off * s, st * s, (st + off) * s, (n - 1) * s + _capi.DCT_SIZE, n, ds / n, pa[a], pb[b]))
+    return out
+
+
+class AlignmentStretch(NamedTuple):
+    """One of the stretches two videos share (align_all): Alignment's fields plus the rank - 0 is the pair's best stretch, the one `align`
+    reports; rank r is the best outside the rectangles of the ranks before it."""
+    a: int
+    b: int
+    offset_frames: int     # first_frame_b - first_frame_a
+    first_frame_a: int
+    first_frame_b: int
+    n_frames: int          # (n_windows - 1) * stride + 16
+    n_windows: int
+    mean_distance: float
+    path_a: object = None
+    path_b: object = None
+    rank: int = 0
+
+
+def _align_all_call(engine, a, b, tol_int, min_run, max_stretches, guard):
+    """_align_call for the stretches calls."""
+    def once(capacity):
+        kw = dict(tol_int=tol_int, min_run=min_run, max_stretches=max_stretches, guard=guard, a_skip=a[2], capacity=capacity)
+        if b is not None:
+            kw.update(b_hashes=b[0], b_first=b[1], b_skip=b[2])
+        return align_windows_stretches_host(a[0], a[1], **kw) if engine is None else engine.align_windows_stretches(a[0], a[1], **kw)
+    rec, found = once(ALIGN_FIRST_CAPACITY)
+    if found > len(rec):
+        rec, found = once(found)
+    return rec
+
+
+def align_all(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoHash]]] = None, tolerance: float = DEFAULT_SEARCH_TOLERANCE,
+              min_run: int = 1, stride: int = 1, max_stretches: int = 4, guard: Optional[int] = None, static_a=None, static_b=None,
+              engine: Optional[Engine] = None) -> List[AlignmentStretch]:
+    """EVERY stretch two videos share, not only the best one: a re-upload with an ad break cut out shares two stretches at two offsets with
+    its source, a compilation that uses a source twice repeats one.  Arguments as `align`; per pair of videos up to max_stretches (1 ... 8)
+    AlignmentStretch, ordered by (a, b, rank).  Rank 0 is the Alignment `align` reports; after every reported stretch its rectangle - its
+    windows of a x its windows of b, each widened by `guard` windows - counts as non-matching, and the next rank is the best run of what is
+    left (include/vdf.h: vdf_align_windows_stretches).  The same windows of a matched against ANOTHER part of b stay visible.
+    guard None: ceil(15 / stride) windows - windows less than 16 frames apart share frames, so in slowly changing content the diagonals
+    beside a stretch match too, and what the bare rectangle leaves of them at its ends would be reported as short stretches of their own.
+    Calls of more than ALIGN_MAX_PAIRS pairs are split.  With no engine given, tiny inputs are walked on the CPU."""
+    self_mode = windows_b is None
+    s = int(stride)
+    if s != stride or s < 1:
+        raise ValueError("stride must be a positive integer")
+    if guard is None:
+        guard = -(-(_capi.DCT_SIZE - 1) // s)
+    tol_int = tolerance_int(tolerance)
+    wa, fa, ka, ca = _align_csr(windows_a, static_a)
+    wb, fb, kb, cb = (wa, fa, ka, ca) if self_mode else _align_csr(windows_b, static_b)
+    if engine is None:
+        cells = (sum(ca) ** 2 - sum(n * n for n in ca)) // 2 if self_mode else sum(ca) * sum(cb)
+        if cells > ALIGN_HOST_CELLS:
+            engine = default_engine()
+
+    def block(words, first, skip, lo, hi):
+        w0, w1 = int(first[lo]), int(first[hi])
+        return words[w0:w1], first[lo:hi + 1] - first[lo], None if skip is None else skip[w0:w1]
+
+    step = max(1, math.isqrt(ALIGN_MAX_PAIRS))
+    parts = []
+    for a0 in range(0, len(ca), step):
+        a1 = min(a0 + step, len(ca))
+        A = block(wa, fa, ka, a0, a1)
+        for b0 in range(a0 if self_mode else 0, len(cb), step):
+            b1 = min(b0 + step, len(cb))
+            rec = _align_all_call(engine, A, None if (self_mode and b0 == a0) else block(wb, fb, kb, b0, b1), tol_int, int(min_run), int(max_stretches),
+                                  int(guard)).copy()
+            rec["a"] += a0
+            rec["b"] += b0
+            parts.append(rec)
+    rec = np.concatenate(parts) if parts else np.zeros(0, ALIGN_STRETCH_DTYPE)
+    rec = rec[np.lexsort((rec["rank"], rec["b"], rec["a"]))]
+    pa = [ws[0].src_path() if ws else None for ws in windows_a]
+    pb = pa if self_mode else [ws[0].src_path() if ws else None for ws in windows_b]
+    out = []
+    for r in rec:
+        a, b, off, st, n, ds, rank = (int(r[k]) for k in ("a", "b", "offset", "start_a", "n_windows", "dist_sum", "rank"))
+        out.append(AlignmentStretch(a, b, off * s, st * s, (st + off) * s, (n - 1) * s + _capi.DCT_SIZE, n, ds / n, pa[a], pb[b], rank))
     return out
 
 

@@ -2,7 +2,8 @@
 // (include/vdf.h: vdf_align_windows[_device]).  The answer is a reduction along the diagonals of each pair's distance
 // matrix, so nothing here emits a hit list and the cost does not depend on how dense the matches are.
 //
-// align_bands_kernel: one wave per (pair, band of 64 diagonals d0 ... d0 + 63), four waves per workgroup.  The wave walks ka upward:
+// align_bands_kernel (and align_bands_masked_kernel, the same walk with the cells of a pair's rectangles as misses: DESIGN.md 4.12): one wave
+// per (pair, band of 64 diagonals d0 ... d0 + 63), four waves per workgroup.  The wave walks ka upward:
 //   - the row of A is wave-uniform: scalar loads, the SGPR operand of v_xor_b32, v_bcnt_u32_b32 accumulates - the inner loop of the
 //     VALU search backend (hamming.hip: hamming_tile_kernel), 64 VALU lane-ops per cell;
 //   - lane kb mod 64 keeps row kb of B in 32 VGPRs; the 64 rows a step needs slide by one per step, so one lane reloads one row
@@ -132,6 +133,114 @@ __global__ __launch_bounds__(256) void align_bands_kernel(
     if (lane == 0) band_records[unit] = AlignBandRecord{best_off, best_start, best_score ? best_n : 0u, best_sum};
 }
 
+// The plain kernel's walk with the cells of the pair's rectangles as misses: the rounds r >= 1 of vdf_align_windows_stretches* (DESIGN.md 4.12).
+// A kernel of its own, so that the plain kernel's text and code stay what they were.  The unit's pair has n_rects = r rectangles at
+// rects[pair * n_rects] (align_plan.h: AlignRect).  They are wave-uniform: scalar loads into SGPRs before the walk (the slots behind n_rects
+// are empty rectangles), the ka test of a step is scalar, and the kb test - two compares per rectangle and lane - runs only in steps whose ka
+// lies in a rectangle's rows of A.  The branch holds nothing else: the rotates and the reload run in every step as in the plain kernel.
+__global__ __launch_bounds__(256) void align_bands_masked_kernel(
+    const uint32_t *__restrict__ a_hashes, const uint32_t *__restrict__ a_first, const uint8_t *__restrict__ a_skip,
+    const uint32_t *__restrict__ b_hashes, const uint32_t *__restrict__ b_first, const uint8_t *__restrict__ b_skip,
+    const AlignPair *__restrict__ pairs, const uint32_t *__restrict__ unit_offset, uint32_t n_pairs, uint32_t n_units, uint32_t tol,
+    uint32_t min_run, AlignBandRecord *__restrict__ band_records, uint32_t group_base, const AlignRect *__restrict__ rects, uint32_t n_rects)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t unit = (blockIdx.x + group_base) * kAlignWaves + wave;  // grids above 2^32 work-items are launched in cuts
+    if (unit >= n_units) return;
+
+    const uint32_t p = align_unit_pair((align_u32_ptr)(uintptr_t)unit_offset, n_pairs, unit);
+    const uint32_t band = unit - ((align_u32_ptr)(uintptr_t)unit_offset)[p];
+    const uint32_t va = ((align_u32_ptr)(uintptr_t)pairs)[2 * p], vb = ((align_u32_ptr)(uintptr_t)pairs)[2 * p + 1];
+    const uint32_t fa = ((align_u32_ptr)(uintptr_t)a_first)[va], Na = ((align_u32_ptr)(uintptr_t)a_first)[va + 1] - fa;
+    const uint32_t fb = ((align_u32_ptr)(uintptr_t)b_first)[vb], Nb = ((align_u32_ptr)(uintptr_t)b_first)[vb + 1] - fb;
+    const int32_t d0 = align_band_d0(Na, band);
+    const uint32_t ka0 = align_ka_begin(d0), ka1 = align_ka_end(Na, Nb, d0);
+    AlignRect rc[kAlignMaxStretches - 1];
+    align_u32_ptr rp = (align_u32_ptr)(uintptr_t)rects + (size_t)p * n_rects * 4;
+#pragma unroll
+    for (uint32_t i = 0; i < kAlignMaxStretches - 1; i++) {
+        if (i < n_rects) rc[i] = AlignRect{rp[4 * i], rp[4 * i + 1], rp[4 * i + 2], rp[4 * i + 3]};
+        else rc[i] = AlignRect{0u, 0u, 0u, 0u};
+    }
+
+    const uint32_t *b_rows = b_hashes + (size_t)fb * 32;
+    const uint8_t *b_sk = b_skip ? b_skip + fb : nullptr;
+    align_u32_ptr a_rows = (align_u32_ptr)(uintptr_t)a_hashes + (size_t)fa * 32;
+
+    // this lane's row of B; cells outside the matrix are misses and no address is formed for them
+    uint32_t rw[32];
+    int32_t kb = align_lane_row(lane, ka0, d0);
+    bool row_ok = kb >= 0 && kb < (int32_t)Nb;
+    uint32_t row_skip = 0;  // the row's skip byte: compared where the row is used, so that the load is not waited for where it is issued
+    if (row_ok) {
+        if (b_sk) row_skip = b_sk[kb];
+        align_load_row(rw, b_rows, (uint32_t)kb);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 32; q++) rw[q] = 0u;
+    }
+
+    uint32_t len = 0, sum = 0;                                              // the run of the diagonal this lane is on
+    uint32_t best_score = 0, best_start = 0, best_n = 0, best_sum = 0;     // score 0 = none: every run scores at least 1
+    int32_t best_off = 0;
+    for (uint32_t ka = ka0; ka < ka1; ++ka) {
+        align_u32_ptr ap = a_rows + (size_t)ka * 32;
+        uint32_t d = 0;
+#pragma unroll
+        for (int w = 0; w < 32; ++w) d += __builtin_popcount(rw[w] ^ ap[w]);  // ap[w]: SGPR
+        bool a_ok = true;  // wave-uniform: the skip byte of A's row comes with the aligned dword that holds it, by a scalar load like the row
+        if (a_skip) {
+            const uintptr_t at = (uintptr_t)a_skip + fa + ka;
+            a_ok = ((*(align_u32_ptr)(at & ~(uintptr_t)3) >> (8 * (uint32_t)(at & 3))) & 0xFFu) == 0u;
+        }
+        bool match = row_ok && row_skip == 0 && a_ok && d <= tol;
+        bool in_a = false;  // wave-uniform
+#pragma unroll
+        for (uint32_t i = 0; i < kAlignMaxStretches - 1; i++) in_a = in_a || align_rect_has_a(rc[i], ka);
+        if (in_a) match = match && !align_cell_masked(rc, kAlignMaxStretches - 1, ka, (uint32_t)kb);
+        if (match) { len += 1; sum += d; }
+        const bool edge = ka + 1 == Na || kb + 1 == (int32_t)Nb;              // the diagonal's last cell
+        const bool ends = len != 0 && (!match || edge);
+        if (__builtin_amdgcn_ballot_w64(ends) != 0ull) {
+            if (ends && len >= min_run) {
+                const uint32_t score = len * (tol + 1) - sum;
+                const uint32_t start = (match ? ka + 1 : ka) - len;
+                const int32_t off = kb - (int32_t)ka;
+                if (align_better(score, off, start, best_score, best_off, best_start)) {
+                    best_score = score; best_off = off; best_start = start; best_n = len; best_sum = sum;
+                }
+            }
+            if (ends) { len = 0; sum = 0; }
+        }
+        // the state follows its diagonal one lane up
+        len = align_rotate_up(len, lane);
+        sum = align_rotate_up(sum, lane);
+        // the lane whose diagonal d0 is done takes the row of diagonal d0 + 63 of the next step
+        if (ka + 1 < ka1 && lane == align_reload_lane(ka, d0)) {
+            kb += (int32_t)kAlignBand;  // = align_reload_row(ka, d0) >= 1, from the lane's own register: the address stays a vector address
+            row_ok = kb < (int32_t)Nb;
+            row_skip = 0;
+            if (row_ok) {
+                if (b_sk) row_skip = b_sk[kb];
+                align_load_row(rw, b_rows, (uint32_t)kb);
+            }
+        }
+    }
+
+    // the wave's best of its 64 lane-bests; every run has its own (score, offset, start)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t o_score = (uint32_t)__shfl_xor((int)best_score, o, 64), o_start = (uint32_t)__shfl_xor((int)best_start, o, 64);
+        const uint32_t o_n = (uint32_t)__shfl_xor((int)best_n, o, 64), o_sum = (uint32_t)__shfl_xor((int)best_sum, o, 64);
+        const int32_t o_off = __shfl_xor(best_off, o, 64);
+        if (align_better(o_score, o_off, o_start, best_score, best_off, best_start)) {
+            best_score = o_score; best_off = o_off; best_start = o_start; best_n = o_n; best_sum = o_sum;
+        }
+    }
+    if (lane == 0) band_records[unit] = AlignBandRecord{best_off, best_start, best_score ? best_n : 0u, best_sum};
+}
+
 __device__ __forceinline__ uint32_t align_block_rank(bool has, uint32_t *s_wave, uint32_t *block_total)
 {  // rank of a thread among the threads of its 256-thread workgroup with `has`, in thread order
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -217,7 +326,7 @@ size_t align_scratch_bytes(size_t n_pairs, size_t n_units)
 
 hipError_t launch_align_chunk(const AlignLaunch &L, hipStream_t stream)
 {
-    if (L.n_pairs == 0 || L.n_units == 0) return hipErrorInvalidValue;
+    if (L.n_pairs == 0 || L.n_units == 0 || L.n_rects >= kAlignMaxStretches || (L.n_rects && !L.rects)) return hipErrorInvalidValue;
     // scratch: band records | pair records | dense records | block counts | block offsets | total
     char *s = static_cast<char *>(L.scratch);
     AlignBandRecord *band_records = reinterpret_cast<AlignBandRecord *>(s);
@@ -231,8 +340,13 @@ hipError_t launch_align_chunk(const AlignLaunch &L, hipStream_t stream)
 
     const size_t n_groups = ((size_t)L.n_units + kAlignWaves - 1) / kAlignWaves;
     for (const AlignLaunchCut &cut : align_launch_cuts(n_groups)) {
-        hipLaunchKernelGGL(align_bands_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_first, L.a_skip, L.b_hashes, L.b_first,
-                           L.b_skip, L.pairs, L.unit_offset, L.n_pairs, L.n_units, L.tol, L.min_run, band_records, (uint32_t)cut.group_base);
+        if (L.n_rects)
+            hipLaunchKernelGGL(align_bands_masked_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_first, L.a_skip, L.b_hashes,
+                               L.b_first, L.b_skip, L.pairs, L.unit_offset, L.n_pairs, L.n_units, L.tol, L.min_run, band_records,
+                               (uint32_t)cut.group_base, L.rects, L.n_rects);
+        else
+            hipLaunchKernelGGL(align_bands_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_first, L.a_skip, L.b_hashes, L.b_first,
+                               L.b_skip, L.pairs, L.unit_offset, L.n_pairs, L.n_units, L.tol, L.min_run, band_records, (uint32_t)cut.group_base);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(align_reduce_kernel, dim3(n_blocks), dim3(256), 0, stream, L.pairs, L.unit_offset, L.n_pairs, L.tol, band_records, pair_records,

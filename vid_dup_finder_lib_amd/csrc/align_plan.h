@@ -118,4 +118,78 @@ inline std::vector<AlignLaunchCut> align_launch_cuts(size_t n_groups, size_t max
     return cuts;
 }
 
+// ---- more than one stretch per pair (vdf_align_windows_stretches*) --------------------------------------------------------------
+// Rank r of a pair is the best run of its matrix with the rectangles of ranks 0 ... r - 1 masked: a masked cell is a miss.  A chunk is walked
+// in rounds: round 0 is the plain launch on the chunk's pairs, round r >= 1 the masked kernel on the SURVIVORS - the pairs that had a record in
+// round r - 1 - each with exactly r rectangles.
+constexpr uint32_t kAlignMaxStretches = 8;       // ranks per pair: at most 7 rectangles in a masked round
+constexpr uint32_t kAlignMaxGuard = 1u << 20;    // = kAlignMaxWindows: a wider guard masks no more
+
+struct AlignRect { uint32_t a_lo, a_hi, b_lo, b_hi; };  // [a_lo, a_hi) x [b_lo, b_hi); a_lo == a_hi: empty
+
+// the rectangle a reported stretch masks: its rows of A and of B (start_b = start_a + offset), each widened by guard and clipped to the matrix.
+// 64-bit arithmetic: nothing wraps for any start, n and guard of 32 bits.
+VDF_ALIGN_HD AlignRect align_rect_of(int32_t offset, uint32_t start_a, uint32_t n, uint32_t guard, uint32_t Na, uint32_t Nb)
+{
+    const int64_t sa = (int64_t)start_a, sb = sa + offset, g = (int64_t)guard, len = (int64_t)n, na = (int64_t)Na, nb = (int64_t)Nb;
+    const auto clip = [](int64_t v, int64_t hi) { return (uint32_t)(v < 0 ? 0 : v > hi ? hi : v); };  // a stretch outside the matrix: an empty range
+    return AlignRect{clip(sa - g, na), clip(sa + len + g, na), clip(sb - g, nb), clip(sb + len + g, nb)};
+}
+VDF_ALIGN_HD bool align_rect_has_a(const AlignRect &r, uint32_t ka) { return ka >= r.a_lo && ka < r.a_hi; }
+VDF_ALIGN_HD bool align_rect_has_b(const AlignRect &r, uint32_t kb) { return kb >= r.b_lo && kb < r.b_hi; }
+// a cell is masked iff ONE rectangle holds both its row of A and its row of B (kb of a cell outside the matrix, cast from a negative
+// int32_t, is above every b_hi)
+template <class Ptr> VDF_ALIGN_HD bool align_cell_masked(Ptr rects, uint32_t n_rects, uint32_t ka, uint32_t kb)
+{
+    bool masked = false;
+    for (uint32_t i = 0; i < n_rects; i++) masked = masked || (align_rect_has_a(rects[i], ka) && align_rect_has_b(rects[i], kb));
+    return masked;
+}
+
+// One round of a chunk: its pairs in (a, b) order, their units, and rects[pair * n_rects + i], the rectangles of ranks 0 ... n_rects - 1.
+struct AlignRound {
+    std::vector<AlignPair> pairs;
+    std::vector<uint32_t> unit_offset;  // [pairs + 1]
+    std::vector<AlignRect> rects;       // [pairs][n_rects]
+    uint32_t n_rects = 0;               // = the round's number
+    size_t n_units() const { return unit_offset.empty() ? 0 : unit_offset.back(); }
+};
+// round 0 of a chunk: all of its pairs, no rectangle.  The chunk's arrays are TAKEN, not copied (a chunk holds up to 2^20 pairs, and a call
+// whose pairs have no record must cost what the plain call costs); align_next_chunk refills the chunk from scratch.
+inline void align_round_zero(AlignChunk &c, AlignRound &r0)
+{
+    r0.pairs.swap(c.pairs);
+    r0.unit_offset.swap(c.unit_offset);
+    c.pairs.clear();
+    c.unit_offset.assign(1, 0u);
+    r0.rects.clear();
+    r0.n_rects = 0;
+}
+// Round prev.n_rects + 1 from round prev and its records (one per pair of prev that had a competing run, in (a, b) order; Rec has a, b, offset,
+// start_a, n_windows): the pairs with a record survive, in (a, b) order, each with its rectangles so far and the one of its new record, and
+// the same align_bands units as before.  So a round is a subset of its predecessor and of its chunk: it stays inside the chunk's pair and unit
+// limits, and the scratch of the chunk's round 0 holds every later round (align_scratch_bytes grows with both counts).  False: a record
+// names a pair that prev does not hold in that order - not a result of prev.
+template <class Rec>
+inline bool align_next_round(const AlignRound &prev, const Rec *recs, size_t n_recs, const uint32_t *first_a, const uint32_t *first_b, uint32_t guard,
+                             AlignRound &next)
+{
+    next.pairs.clear();
+    next.unit_offset.assign(1, 0u);
+    next.rects.clear();
+    next.n_rects = prev.n_rects + 1;
+    size_t p = 0;
+    for (size_t i = 0; i < n_recs; i++) {
+        while (p < prev.pairs.size() && (prev.pairs[p].a != recs[i].a || prev.pairs[p].b != recs[i].b)) p++;
+        if (p == prev.pairs.size()) return false;
+        const uint32_t Na = first_a[recs[i].a + 1] - first_a[recs[i].a], Nb = first_b[recs[i].b + 1] - first_b[recs[i].b];
+        next.pairs.push_back(prev.pairs[p]);
+        next.unit_offset.push_back(next.unit_offset.back() + (prev.unit_offset[p + 1] - prev.unit_offset[p]));
+        for (uint32_t k = 0; k < prev.n_rects; k++) next.rects.push_back(prev.rects[p * prev.n_rects + k]);
+        next.rects.push_back(align_rect_of(recs[i].offset, recs[i].start_a, recs[i].n_windows, guard, Na, Nb));
+        p++;
+    }
+    return next.pairs.size() <= prev.pairs.size() && next.n_units() <= prev.n_units();
+}
+
 }  // namespace vdf

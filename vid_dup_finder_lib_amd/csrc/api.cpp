@@ -1653,8 +1653,9 @@ int align_checks(vdf_ctx *ctx, const void *a_hashes, const uint32_t *a_first, si
 }
 
 // the literal definition: every diagonal of the pair walked, XOR + popcount; *best.n_windows = 0: no competing run
+// rects (nullable): the cells of these n_rects rectangles are misses (vdf_align_windows_stretches*: the ranks before this one)
 void align_pair_host(const uint64_t *A, uint32_t Na, const uint8_t *skip_a, const uint64_t *B, uint32_t Nb, const uint8_t *skip_b, uint32_t tol,
-                     uint32_t min_run, vdf_alignment *best)
+                     uint32_t min_run, vdf_alignment *best, const vdf::AlignRect *rects = nullptr, uint32_t n_rects = 0)
 {
     uint32_t best_score = 0;
     best->offset = 0; best->start_a = 0; best->n_windows = 0; best->dist_sum = 0;
@@ -1664,7 +1665,7 @@ void align_pair_host(const uint64_t *A, uint32_t Na, const uint8_t *skip_a, cons
         for (int64_t ka = ka0; ka <= ka1; ka++) {  // ka1: the cell behind the diagonal's last, a miss
             bool match = false;
             uint32_t dist = 0;
-            if (ka < ka1 && !(skip_a && skip_a[ka]) && !(skip_b && skip_b[ka + d])) {
+            if (ka < ka1 && !(skip_a && skip_a[ka]) && !(skip_b && skip_b[ka + d]) && !vdf::align_cell_masked(rects, n_rects, (uint32_t)ka, (uint32_t)(ka + d))) {
                 const uint64_t *x = A + 16 * ka, *y = B + 16 * (ka + d);
                 for (int w = 0; w < VDF_HASH_WORDS; w++) dist += (uint32_t)__builtin_popcountll(x[w] ^ y[w]);
                 match = dist <= tol;
@@ -1717,6 +1718,112 @@ int align_locked(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_f
             VDF_HIP(ctx, hipStreamSynchronize(s));
         }
         found += total;
+    }
+    *n_out = found;
+    return VDF_OK;
+}
+
+// ---- more than one stretch per pair (include/vdf.h: vdf_align_windows_stretches[_device|_host]) ----------------------------------
+// behind align_checks: max_stretches, then guard
+int align_stretches_checks(vdf_ctx *ctx, uint32_t max_stretches, uint32_t guard)
+{
+    if (max_stretches < 1 || max_stretches > vdf::kAlignMaxStretches) return fail(ctx, VDF_E_INVAL, "max_stretches outside 1 ... 8");
+    if (guard > vdf::kAlignMaxGuard) return fail(ctx, VDF_E_INVAL, "guard above 2^20 windows");
+    return VDF_OK;
+}
+
+vdf_alignment_stretch stretch_of(const vdf_alignment &r, uint32_t rank)
+{
+    return vdf_alignment_stretch{r.a, r.b, r.offset, r.start_a, r.n_windows, r.dist_sum, rank};
+}
+
+// the rounds' record lists of one chunk (each in (a, b) order, the pairs of round r a subset of those of round r - 1) -> (a, b, rank) order
+template <class Emit> void align_merge_rounds(const std::vector<std::vector<vdf_alignment>> &rounds, Emit emit)
+{
+    if (rounds.empty()) return;
+    std::vector<size_t> at(rounds.size(), 0);
+    for (const vdf_alignment &r0 : rounds[0]) {
+        emit(stretch_of(r0, 0));
+        for (size_t r = 1; r < rounds.size(); r++) {
+            if (at[r] == rounds[r].size() || rounds[r][at[r]].a != r0.a || rounds[r][at[r]].b != r0.b) break;
+            emit(stretch_of(rounds[r][at[r]++], (uint32_t)r));
+        }
+    }
+}
+
+struct AlignSides {  // device pointers, and the first arrays on the host as well
+    const uint64_t *d_a_hashes; const uint32_t *d_a_first, *h_first_a; size_t n_a; const uint8_t *d_a_skip;
+    const uint64_t *d_b_hashes; const uint32_t *d_b_first, *h_first_b; size_t n_b; const uint8_t *d_b_skip;
+    bool self;
+};
+
+// one round of a chunk: plan up, the band kernel (masked from round 1 on) and the reductions, the dense records down into recs
+static int align_run_round(vdf_ctx *ctx, const AlignSides &in, const vdf::AlignRound &round, uint32_t tol, uint32_t min_run, std::vector<vdf_alignment> &recs,
+                           hipStream_t s)
+{
+    const size_t n_pairs = round.pairs.size(), n_units = round.n_units();
+    const size_t pair_bytes = n_pairs * sizeof(vdf::AlignPair), off_bytes = (n_pairs + 1) * sizeof(uint32_t);
+    const size_t rect_at = (pair_bytes + off_bytes + 15) & ~(size_t)15, rect_bytes = round.rects.size() * sizeof(vdf::AlignRect);
+    VDF_HIP(ctx, ctx->align_plan.reserve(rect_at + rect_bytes));
+    VDF_HIP(ctx, ctx->align_scratch.reserve(vdf::align_scratch_bytes(n_pairs, n_units)));
+    char *plan = ctx->align_plan.as<char>();
+    VDF_HIP(ctx, hipMemcpyAsync(plan, round.pairs.data(), pair_bytes, hipMemcpyHostToDevice, s));
+    VDF_HIP(ctx, hipMemcpyAsync(plan + pair_bytes, round.unit_offset.data(), off_bytes, hipMemcpyHostToDevice, s));
+    if (rect_bytes) VDF_HIP(ctx, hipMemcpyAsync(plan + rect_at, round.rects.data(), rect_bytes, hipMemcpyHostToDevice, s));
+    vdf_alignment *d_dense = nullptr;
+    uint32_t *d_total = nullptr;
+    vdf::AlignLaunch L{};
+    L.a_hashes = reinterpret_cast<const uint32_t *>(in.d_a_hashes); L.a_first = in.d_a_first; L.a_skip = in.d_a_skip;
+    L.b_hashes = reinterpret_cast<const uint32_t *>(in.d_b_hashes); L.b_first = in.d_b_first; L.b_skip = in.d_b_skip;
+    L.pairs = reinterpret_cast<const vdf::AlignPair *>(plan);
+    L.unit_offset = reinterpret_cast<const uint32_t *>(plan + pair_bytes);
+    L.n_pairs = (uint32_t)n_pairs; L.n_units = (uint32_t)n_units;
+    L.tol = tol; L.min_run = min_run;
+    L.scratch = ctx->align_scratch.p; L.dense_out = &d_dense; L.total_out = &d_total;
+    L.rects = round.n_rects ? reinterpret_cast<const vdf::AlignRect *>(plan + rect_at) : nullptr;
+    L.n_rects = round.n_rects;
+    VDF_HIP(ctx, vdf::launch_align_chunk(L, s));
+    uint32_t total = 0;
+    VDF_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));  // also: the round's plan arrays are free to change
+    if (total > n_pairs) return fail(ctx, VDF_E_HIP, "align: more records than pairs");
+    recs.resize(total);
+    if (total) {
+        VDF_HIP(ctx, hipMemcpyAsync(recs.data(), d_dense, total * sizeof(vdf_alignment), hipMemcpyDeviceToHost, s));
+        VDF_HIP(ctx, hipStreamSynchronize(s));
+    }
+    return VDF_OK;
+}
+
+// align_checks and align_stretches_checks have passed.  Per chunk: round 0 is the plain launch of align_locked; round r runs the masked kernel
+// on the pairs that had a record in round r - 1 (align_plan.h: align_next_round), until a round has no survivors or max_stretches rounds have
+// run; the rounds are merged into (a, b, rank) order.  Chunks arrive in (a, b) order and each is finished before the next, so the first
+// `capacity` records of the call are the ones written.
+int align_stretches_locked(vdf_ctx *ctx, const AlignSides &in, uint32_t tol_int, uint32_t min_run, uint32_t max_stretches, uint32_t guard,
+                           vdf_alignment_stretch *out, size_t capacity, size_t *n_out, hipStream_t s)
+{
+    vdf::AlignCursor cur;
+    vdf::AlignChunk ch;
+    vdf::AlignRound round, next;
+    std::vector<std::vector<vdf_alignment>> rounds;
+    const uint32_t tol = std::min<uint32_t>(tol_int, 1024u);
+    size_t found = 0;
+    while (vdf::align_next_chunk(in.h_first_a, in.n_a, in.h_first_b, in.n_b, in.self, cur, ch)) {
+        vdf::align_round_zero(ch, round);
+        rounds.clear();
+        for (uint32_t r = 0; r < max_stretches; r++) {
+            rounds.emplace_back();
+            if (int rc = align_run_round(ctx, in, round, tol, min_run, rounds.back(), s)) return rc;
+            if (rounds.back().empty()) { rounds.pop_back(); break; }
+            if (r + 1 == max_stretches) break;
+            if (!vdf::align_next_round(round, rounds.back().data(), rounds.back().size(), in.h_first_a, in.h_first_b, guard, next))
+                return fail(ctx, VDF_E_HIP, "align: a round's records do not belong to its pairs");
+            std::swap(round, next);
+        }
+        align_merge_rounds(rounds, [&](const vdf_alignment_stretch &r) {
+            if (found < capacity) out[found] = r;
+            found++;
+        });
     }
     *n_out = found;
     return VDF_OK;
@@ -1945,6 +2052,90 @@ int vdf_align_windows(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_
                                   u.d_ska, true, tol_int, min_run, out, capacity, n_out, s);
     return align_locked(ctx, ctx->up_hashes.as<uint64_t>(), u.d_fa, u.fa.data(), n_a, u.d_ska, ctx->up_ref_hashes.as<uint64_t>(), u.d_fb, u.fb.data(), n_b, u.d_skb,
                         false, tol_int, min_run, out, capacity, n_out, s);
+}
+
+int vdf_align_windows_stretches_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                                     const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, uint32_t tol_int, uint32_t min_run, uint32_t max_stretches,
+                                     uint32_t guard, vdf_alignment_stretch *out, size_t capacity, size_t *n_out)
+{
+    if (int rc = align_checks(nullptr, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, min_run, out, capacity, n_out)) return rc;
+    if (int rc = align_stretches_checks(nullptr, max_stretches, guard)) return rc;
+    const bool self = b_hashes == nullptr;
+    if (self) { b_hashes = a_hashes; b_first = a_first; n_b = n_a; b_skip = a_skip; }
+    const uint32_t tol = std::min<uint32_t>(tol_int, 1024u);
+    size_t found = 0;
+    for (size_t a = 0; a < n_a; a++)
+        for (size_t b = self ? a + 1 : 0; b < n_b; b++) {
+            const uint32_t Na = a_first[a + 1] - a_first[a], Nb = b_first[b + 1] - b_first[b];
+            vdf::AlignRect rects[vdf::kAlignMaxStretches];
+            for (uint32_t rank = 0; rank < max_stretches; rank++) {
+                vdf_alignment r;
+                align_pair_host(a_hashes + 16 * (size_t)a_first[a], Na, a_skip ? a_skip + a_first[a] : nullptr, b_hashes + 16 * (size_t)b_first[b], Nb,
+                                b_skip ? b_skip + b_first[b] : nullptr, tol, min_run, &r, rects, rank);
+                if (r.n_windows == 0) break;
+                r.a = (uint32_t)a; r.b = (uint32_t)b;
+                if (found < capacity) out[found] = stretch_of(r, rank);
+                found++;
+                rects[rank] = vdf::align_rect_of(r.offset, r.start_a, r.n_windows, guard, Na, Nb);
+            }
+        }
+    *n_out = found;
+    return VDF_OK;
+}
+
+int vdf_align_windows_stretches_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a, const uint8_t *d_a_skip,
+                                       const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip, uint32_t tol_int,
+                                       uint32_t min_run, uint32_t max_stretches, uint32_t guard, vdf_alignment_stretch *out, size_t capacity,
+                                       size_t *n_out, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const bool self = d_b_hashes == nullptr;
+    // as vdf_align_windows_device: everything that can be said without the first arrays; then they come down, are checked, and plan the launch
+    if (int rc = align_checks(ctx, d_a_hashes, nullptr, n_a, d_b_hashes, nullptr, n_b, d_a_first, d_b_first, min_run, out, capacity, n_out)) return rc;
+    auto later_checks = [&]() -> int {
+        if (int rc = align_stretches_checks(ctx, max_stretches, guard)) return rc;
+        if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_align_windows_stretches_device takes a single-device context");
+        return VDF_OK;
+    };
+    *n_out = 0;
+    if (n_a == 0 || (self ? n_a < 2 : n_b == 0)) return later_checks();
+    if (!ctx->subs.empty()) return later_checks();  // the first arrays of a multi-GPU context's caller are not read: the call is refused either way
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<uint32_t> fa(n_a + 1), fb(self ? 0 : n_b + 1);
+    VDF_HIP(ctx, hipMemcpyAsync(fa.data(), d_a_first, fa.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (!self) VDF_HIP(ctx, hipMemcpyAsync(fb.data(), d_b_first, fb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));
+    if (int rc = align_checks(ctx, d_a_hashes, fa.data(), n_a, d_b_hashes, self ? nullptr : fb.data(), n_b, d_a_first, d_b_first, min_run, out, capacity, n_out))
+        return rc;
+    if (int rc = later_checks()) return rc;
+    const AlignSides in = self ? AlignSides{d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, true}
+                               : AlignSides{d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, d_b_hashes, d_b_first, fb.data(), n_b, d_b_skip, false};
+    return align_stretches_locked(ctx, in, tol_int, min_run, max_stretches, guard, out, capacity, n_out, s);
+}
+
+// Host arrays: uploaded as vdf_align_windows uploads them, then the device form's core.
+int vdf_align_windows_stretches(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                                const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, uint32_t tol_int, uint32_t min_run, uint32_t max_stretches,
+                                uint32_t guard, vdf_alignment_stretch *out, size_t capacity, size_t *n_out)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (int rc = align_checks(ctx, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, min_run, out, capacity, n_out)) return rc;
+    if (int rc = align_stretches_checks(ctx, max_stretches, guard)) return rc;
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_align_windows_stretches takes a single-device context");
+    const bool self = b_hashes == nullptr;
+    *n_out = 0;
+    if (n_a == 0 || (self ? n_a < 2 : n_b == 0)) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    AlignUploaded u;
+    if (int rc = align_upload(ctx, a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, self, s, &u)) return rc;
+    const uint64_t *d_a = ctx->up_hashes.as<uint64_t>();
+    const AlignSides in = self ? AlignSides{d_a, u.d_fa, u.fa.data(), n_a, u.d_ska, d_a, u.d_fa, u.fa.data(), n_a, u.d_ska, true}
+                               : AlignSides{d_a, u.d_fa, u.fa.data(), n_a, u.d_ska, ctx->up_ref_hashes.as<uint64_t>(), u.d_fb, u.fb.data(), n_b, u.d_skb, false};
+    return align_stretches_locked(ctx, in, tol_int, min_run, max_stretches, guard, out, capacity, n_out, s);
 }
 
 size_t vdf_hash_window_count(uint32_t frames_per_clip, uint32_t window_stride) { return vdf::window_count(frames_per_clip, window_stride); }

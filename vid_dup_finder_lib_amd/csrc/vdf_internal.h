@@ -265,6 +265,8 @@ struct AlignLaunch {
     void *scratch;
     vdf_alignment **dense_out;
     uint32_t **total_out;
+    const AlignRect *rects;              // n_rects != 0: the masked kernel, rects[pair * n_rects + i]; 0: the plain kernel
+    uint32_t n_rects;                    // 0 ... kAlignMaxStretches - 1
 };
 size_t align_scratch_bytes(size_t n_pairs, size_t n_units);
 hipError_t launch_align_chunk(const AlignLaunch &L, hipStream_t stream);

@@ -161,6 +161,27 @@ def align_windows_variants_host(a_hashes, a_first, a_zero=None, b_hashes=None, b
     return out[:min(n.value, out.size)], int(n.value)
 
 
+# one record of the align-stretches calls (include/vdf.h: vdf_alignment_stretch, 28 bytes)
+ALIGN_STRETCH_DTYPE = np.dtype(ALIGN_DTYPE.descr + [("rank", "<u4")])
+
+
+def align_windows_stretches_host(a_hashes, a_first, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1, max_stretches: int = 4,
+                                 guard: int = 0, a_skip=None, b_skip=None, capacity: int = 1024):
+    """vdf_align_windows_stretches_host: every shared stretch of every pair - align_windows_host's record as rank 0, then the best run of the
+    matrix with the rectangles of the earlier ranks (widened by guard) masked, up to max_stretches per pair - in plain C++ on the CPU.
+    -> (records [min(found, capacity)] of ALIGN_STRETCH_DTYPE in (a, b, rank) order, found)."""
+    lib = _capi.load()
+    keep, args = _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+    out = np.zeros(max(int(capacity), 0), ALIGN_STRETCH_DTYPE)
+    n = C.c_size_t(0)
+    rc = lib.vdf_align_windows_stretches_host(*args, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                              _align_uint32("max_stretches", max_stretches), _align_uint32("guard", guard),
+                                              out.ctypes.data if out.size else None, out.size, C.byref(n))
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_align_windows_stretches_host: bad argument")
+    return out[:min(n.value, out.size)], int(n.value)
+
+
 def window_variants_host(hashes, zero, first, variant: int, skip=None):
     """vdf_window_variants_host: the variant of a set of window hashes (hashes / zero [windows, 16] u64, first [videos + 1]) on the CPU ->
     hashes [windows, 16] (and the skip bytes carried along, if skip is given).  Rows outside [first[0], first[-1]) come back zero."""
@@ -435,6 +456,34 @@ class Engine:
                                                       d_b_first or None, int(n_b), d_b_skip or None, _align_uint32("tol_int", tol_int),
                                                       _align_uint32("min_run", min_run), out.ctypes.data if out.size else None, out.size, C.byref(n),
                                                       stream or None))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    # --------------------------------------------- every shared stretch of a pair (include/vdf.h)
+    def align_windows_stretches(self, a_hashes, a_first, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1, max_stretches: int = 4,
+                                guard: int = 0, a_skip=None, b_skip=None, capacity: int = 1024):
+        """Every shared stretch of every pair of videos (vdf_align_windows_stretches): align_windows' record as rank 0, then per rank the best
+        run of the pair's matrix with the rectangles of the earlier ranks - their rows of A x their rows of B, widened by guard windows -
+        masked; at most max_stretches (1 ... 8) per pair.  -> (records [min(found, capacity)] of ALIGN_STRETCH_DTYPE in (a, b, rank) order,
+        found); found > capacity: call again with a larger capacity."""
+        keep, args = _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+        out = np.zeros(max(int(capacity), 0), ALIGN_STRETCH_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_stretches(self.ctx, *args, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                                         _align_uint32("max_stretches", max_stretches), _align_uint32("guard", guard),
+                                                         out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_stretches_device(self, d_a_hashes: int, d_a_first: int, n_a: int, d_b_hashes: int = 0, d_b_first: int = 0, n_b: int = 0,
+                                       tol_int: int = 350, min_run: int = 1, max_stretches: int = 4, guard: int = 0, d_a_skip: int = 0,
+                                       d_b_skip: int = 0, capacity: int = 1024, stream: int = 0):
+        """The same on device arrays (d_b_hashes 0: self mode); the records come back to the host, the call waits for its own work."""
+        out = np.zeros(max(int(capacity), 0), ALIGN_STRETCH_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_stretches_device(self.ctx, d_a_hashes or None, d_a_first or None, int(n_a), d_a_skip or None,
+                                                                d_b_hashes or None, d_b_first or None, int(n_b), d_b_skip or None,
+                                                                _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                                                _align_uint32("max_stretches", max_stretches), _align_uint32("guard", guard),
+                                                                out.ctypes.data if out.size else None, out.size, C.byref(n), stream or None))
         return out[:min(n.value, out.size)], int(n.value)
 
     # --------------------------------------------- the zero plane and the flipped hashes (include/vdf.h, DESIGN.md 4.8)

@@ -302,6 +302,53 @@ public:
         }
     }
 
+    // EVERY stretch two videos share (vdf_align_windows_stretches): align_windows' arguments, plus max_stretches (1 ... 8) records
+    // per pair and the guard in windows.  Records in (a, b, rank) order: rank 0 is align_windows' record, rank r the best run of the pair's
+    // matrix with the rectangles of the ranks before it - their windows of a x their windows of b, each widened by guard - masked.  ctx_opt
+    // null and a tiny input: walked on the CPU (vdf_align_windows_stretches_host).
+    static std::vector<vdf_alignment_stretch> align_windows_stretches(const std::vector<std::vector<VideoHash>> &windows_a,
+                                                                      const std::vector<std::vector<VideoHash>> *windows_b, uint32_t tol_int, uint32_t min_run = 1,
+                                                                      uint32_t max_stretches = 4, uint32_t guard = 15, const std::vector<uint8_t> *skip_a = nullptr,
+                                                                      const std::vector<uint8_t> *skip_b = nullptr, Context *ctx_opt = nullptr)
+    {
+        auto csr = [](const std::vector<std::vector<VideoHash>> &w, std::vector<uint64_t> &words, std::vector<uint32_t> &first) {
+            first.assign(1, 0u);
+            for (const auto &video : w) {
+                for (const VideoHash &h : video) words.insert(words.end(), h.words().begin(), h.words().end());
+                first.push_back((uint32_t)(words.size() / VDF_HASH_WORDS));
+            }
+            if (words.empty()) words.push_back(0);  // a non-null pointer for an empty side
+        };
+        std::vector<uint64_t> wa, wb;
+        std::vector<uint32_t> fa, fb;
+        csr(windows_a, wa, fa);
+        if (windows_b) csr(*windows_b, wb, fb);
+        if (skip_a && skip_a->size() != fa.back()) throw std::invalid_argument("one skip byte per window of A");
+        if (windows_b && skip_b && skip_b->size() != fb.back()) throw std::invalid_argument("one skip byte per window of B");
+        const uint8_t *ska = skip_a && !skip_a->empty() ? skip_a->data() : nullptr, *skb = windows_b && skip_b && !skip_b->empty() ? skip_b->data() : nullptr;
+        const size_t n_a = windows_a.size(), n_b = windows_b ? windows_b->size() : 0;
+        const uint64_t cells = (uint64_t)fa.back() * (windows_b ? fb.back() : fa.back());
+        std::vector<vdf_alignment_stretch> out(1024);
+        for (;;) {
+            size_t found = 0;
+            int rc;
+            if (!ctx_opt && cells <= (1u << 16))
+                rc = vdf_align_windows_stretches_host(wa.data(), fa.data(), n_a, ska, windows_b ? wb.data() : nullptr, fb.data(), n_b, skb, tol_int, min_run, max_stretches,
+                                                      guard, out.data(), out.size(), &found);
+            else {
+                Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+                rc = vdf_align_windows_stretches(ctx.get(), wa.data(), fa.data(), n_a, ska, windows_b ? wb.data() : nullptr, fb.data(), n_b, skb, tol_int, min_run,
+                                                 max_stretches, guard, out.data(), out.size(), &found);
+                if (rc != VDF_OK && rc != VDF_E_INVAL) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            }
+            if (rc != VDF_OK)
+                throw std::invalid_argument("align_windows_stretches: min_run of 0, a video of more than 2^20 windows, more than 2^24 pairs, max_stretches outside 1 ... 8, "
+                                            "a guard above 2^20, or a multi-GPU context");
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
     // hash_windows with the zero plane of every window (vdf_hash_windows_u8_planes): the same words, and every VideoHash
     // carries zero() - what align_windows_variants needs of the flipped side.
     static std::vector<std::vector<VideoHash>> hash_windows_planes(const uint8_t *frames, size_t n_videos, uint32_t frames_per_video, uint32_t w, uint32_t h,
