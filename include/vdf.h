@@ -335,6 +335,77 @@ int vdf_align_windows_stretches_device(vdf_ctx *ctx, const uint64_t *d_a_hashes,
                                        const uint8_t *d_b_skip, uint32_t tol_int, uint32_t min_run, uint32_t max_stretches,
                                        uint32_t guard, vdf_alignment_stretch *out, size_t capacity, size_t *n_out, void *stream);
 
+/* ---- a library is not walked pair by pair: seed the candidate pairs, align only those ------------------------
+ * The align calls above walk every cell of every pair of videos, also where no pair shares anything.  An exact filter: a run that competes
+ * has at least min_run consecutive matching cells on one diagonal, and any min_run consecutive values of ka contain a multiple of min_run.
+ * So a pair (a, b) can have a record only if some cell (ka, kb) matches with ka % min_run == 0.
+ * Inputs: those of vdf_align_windows - hashes, first arrays, nullable skip bytes, tol = min(tol_int, 1024), min_run >= 1, self mode when
+ * b_hashes == NULL.
+ *   - a SEED is window ka of video a with ka % min_run == 0; ka counts from the video's own first window, not from the array's;
+ *   - pair (a, b) is a CANDIDATE iff some seed of a and some window kb of b form a matching cell under the align rule: neither window is
+ *     skipped and the distance over all 16 words is <= tol.  In self mode the pair must also have a < b.
+ * The candidates are a set, exact and deterministic.  It holds every pair for which vdf_align_windows has a record; it may hold pairs that
+ * have none (an isolated matching cell).  With min_run == 1 every window is a seed.
+ * vdf_align_seed_pairs*: out is a HOST buffer of `capacity` pairs, filled in (a, b) order, under the capacity protocol of the align calls
+ * (*n_out = the number found; the first `capacity` are valid).  Errors: those of vdf_align_windows, in their order - the limit of 2^24 pairs
+ * of videos included (it sizes the bitmap the pairs are marked in) and a multi-GPU context last.
+ * vdf_align_windows_pairs*: vdf_align_windows restricted to a caller-given HOST list of n_pairs pairs (also in the device form): the records
+ * are those the all-pairs call reports for the listed pairs, field for field, in (a, b) order.  The list must be strictly increasing in
+ * (a, b), with a < n_a and b < n_b, and a < b in self mode (b < n_a there).  Errors, in this order, all VDF_E_INVAL: a null list with
+ * n_pairs > 0; those of vdf_align_windows up to the first arrays; n_a or n_b above 2^32 - 1 (a video index does not fit 32 bits: n_a x n_b
+ * may be anything below that); more than 2^24 LISTED pairs; a list that is not strictly increasing; a pair that names a video that does not exist; a pair with a >= b in self mode;
+ * a multi-GPU context.  (The device form reads the first arrays back and checks them after the list, as vdf_align_windows_device does
+ * after its own checks.)
+ * vdf_align_windows_stretches_pairs*: the same restriction for vdf_align_windows_stretches; max_stretches and guard are checked behind the
+ * align checks, as there, and before the list.
+ * Each in the usual three forms: _host (plain C++, no context: the CPU-tested statement of the semantics), host arrays through a context,
+ * _device (DEVICE arrays and a stream; the call waits for its own work).
+ * A skip byte is read with the aligned 32-bit word that holds it (the seed kernel reads a seed's byte by a scalar load, as the band kernels of
+ * vdf_align_windows read a row's): for a skip array that does not begin or end on a 4-byte boundary up to 3 bytes beside it are read - inside
+ * the same word, so inside the same page and, with any device allocator, the same allocation - and their values are ignored.
+ * Not offered: the variants (vdf_align_windows_variants*) on a pair list. */
+typedef struct vdf_video_pair { /* 8 bytes */
+    uint32_t a;                /* video index in A */
+    uint32_t b;                /* video index in B (self mode: in A, a < b) */
+} vdf_video_pair;
+int vdf_align_seed_pairs_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                              const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                              uint32_t tol_int, uint32_t min_run, vdf_video_pair *out, size_t capacity, size_t *n_out);
+int vdf_align_seed_pairs(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                         const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                         uint32_t tol_int, uint32_t min_run, vdf_video_pair *out, size_t capacity, size_t *n_out);
+int vdf_align_seed_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a,
+                                const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b,
+                                const uint8_t *d_b_skip, uint32_t tol_int, uint32_t min_run, vdf_video_pair *out,
+                                size_t capacity, size_t *n_out, void *stream);
+int vdf_align_windows_pairs_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                 const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                                 const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int, uint32_t min_run,
+                                 vdf_alignment *out, size_t capacity, size_t *n_out);
+int vdf_align_windows_pairs(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                            const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                            const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int, uint32_t min_run,
+                            vdf_alignment *out, size_t capacity, size_t *n_out);
+int vdf_align_windows_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a,
+                                   const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b,
+                                   const uint8_t *d_b_skip, const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int,
+                                   uint32_t min_run, vdf_alignment *out, size_t capacity, size_t *n_out, void *stream);
+int vdf_align_windows_stretches_pairs_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                           const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                                           const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int, uint32_t min_run,
+                                           uint32_t max_stretches, uint32_t guard, vdf_alignment_stretch *out, size_t capacity,
+                                           size_t *n_out);
+int vdf_align_windows_stretches_pairs(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a,
+                                      const uint8_t *a_skip, const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b,
+                                      const uint8_t *b_skip, const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int,
+                                      uint32_t min_run, uint32_t max_stretches, uint32_t guard, vdf_alignment_stretch *out,
+                                      size_t capacity, size_t *n_out);
+int vdf_align_windows_stretches_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a,
+                                             const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint32_t *d_b_first,
+                                             size_t n_b, const uint8_t *d_b_skip, const vdf_video_pair *pairs, size_t n_pairs,
+                                             uint32_t tol_int, uint32_t min_run, uint32_t max_stretches, uint32_t guard,
+                                             vdf_alignment_stretch *out, size_t capacity, size_t *n_out, void *stream);
+
 /* ---- mirrored, flipped and reversed STRETCHES: window hashes with their zero planes -----------------------
  * A mirrored re-upload with its intro trimmed: the variant search sees only frames 0 ... 15 of a file, the align calls only unflipped
  * stretches.  With the zero plane of every window (vdf_hash_windows_u8_planes*) the window hashes of the flipped video follow from the

@@ -34,7 +34,18 @@ kernel once, as vdf_align_windows_device does: vdf_align_windows_stretches_devic
 commit's library (without --parent-lib this build's stands in and is labelled so).  GATE: the new call's median is at most the parent's
 median times the parent's own max / min over its 12 calls.  Leg (b): the same hashes with 0.99 % of the pairs (90 groups of 11 videos) sharing
 two planted stretches of 12 windows on two different diagonals: the time, the rounds and the surviving pairs per round, beside leg (a) - no
-gate."""
+gate.
+
+    python tools/bench_align.py --seeded --parent-lib tools/_libvdf_parent.so [--out profiles/align_seeded.txt]
+
+What seeding the candidate pairs buys, same protocol.  The seeded path on device arrays is vdf_align_seed_pairs_device and
+then, if there is a candidate, vdf_align_windows_pairs_device on the candidates.  Leg (a): the no-copies corpus of --stretches (1000 x 49 self,
+device-resident; no candidate), min_run 2 and 4, beside vdf_align_windows_device of the parent commit's library.  GATE: the seeded median is
+below the parent's median divided by the parent's own max / min over its 12 calls - faster by more than the parent's noise - at both min_run.
+Leg (b): the planted corpus of --stretches (0.99 % of the pairs share stretches), min_run 2: the seeded path beside this build's all-pairs
+call; the records must be equal.  Leg (c): 8000 videos x 49 windows, self mode, host lists through api.align (three blocks of videos):
+seed=True beside seed=False, equal lists.  Leg (d): leg (a) at min_run 1, where every window is a seed and the filter saves no distance
+work.  Only leg (a) is gated."""
 import argparse
 import ctypes as C
 import json
@@ -411,6 +422,136 @@ def stretches_main(args):
     return 0 if held else 1
 
 
+SEEDED_API_VIDEOS = 8000
+
+
+def seeded_child(args):
+    """one leg of --seeded: parent-a (vdf_align_windows_device of args.lib at min_run 1, 2, 4) | seeded-a | b | api-plain | api-seeded"""
+    import torch
+
+    n_a, n_win, _ = SHAPES[VARIANTS_SHAPE]
+    if args.leg.startswith("api-"):
+        sys.path.insert(0, ROOT)
+        import vid_dup_finder_lib_amd as vdf
+
+        rng = np.random.default_rng([14, SEEDED_API_VIDEOS, n_win])
+        words = random_hashes(rng, SEEDED_API_VIDEOS * n_win)
+        for v in range(1, SEEDED_API_VIDEOS, 100):  # every hundredth video holds 24 windows of its predecessor, shifted
+            words[v * n_win + 5:v * n_win + 29] = flip_bits(rng, words[(v - 1) * n_win + 11:(v - 1) * n_win + 35])
+        wins = [[vdf.VideoHash(words[v * n_win + k], f"/v/{v}.mp4", 1) for k in range(n_win)] for v in range(SEEDED_API_VIDEOS)]
+        eng = vdf.Engine(0)
+        times, got = [], None
+        for r in range(REPEATS + 1):
+            t0 = time.perf_counter()
+            got = vdf.align(wins, min_run=MIN_RUN, engine=eng, seed=args.leg == "api-seeded")
+            if r:
+                times.append(time.perf_counter() - t0)
+        rec = np.array([(g.a, g.b, g.offset_frames, g.first_frame_a, g.n_windows, round(g.mean_distance * g.n_windows)) for g in got], ALIGN_DTYPE)
+        eng.close()
+        print("RESULT " + json.dumps({"api": {"times": times, "records": len(got), "digest": digest(rec)}}))
+        return
+    lib = C.CDLL(args.lib)
+    lib.vdf_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    lib.vdf_last_error.restype = C.c_char_p
+    lib.vdf_last_error.argtypes = [C.c_void_p]
+    ctx = C.c_void_p()
+    assert lib.vdf_ctx_create(0, C.byref(ctx)) == 0, lib.vdf_last_error(None)
+    P = C.c_void_p
+    sides = [P, P, P, C.c_size_t, P, P, P, C.c_size_t, P]
+    lib.vdf_align_windows_device.argtypes = sides + [C.c_uint32, C.c_uint32, P, C.c_size_t, C.POINTER(C.c_size_t), P]
+    if args.leg != "parent-a":
+        lib.vdf_align_seed_pairs_device.argtypes = sides + [C.c_uint32, C.c_uint32, P, C.c_size_t, C.POINTER(C.c_size_t), P]
+        lib.vdf_align_windows_pairs_device.argtypes = sides + [P, C.c_size_t, C.c_uint32, C.c_uint32, P, C.c_size_t, C.POINTER(C.c_size_t), P]
+    pairs = n_a * (n_a - 1) // 2
+    a, fa, _ = stretches_corpus(args.leg == "b")
+    d_a, d_fa = torch.from_numpy(a.view(np.int64)).cuda(), torch.from_numpy(fa.view(np.int32)).cuda()
+    torch.cuda.synchronize()
+    out, cand = np.zeros(pairs, ALIGN_DTYPE), np.zeros(pairs, np.dtype([("a", "<u4"), ("b", "<u4")]))
+    n_out, n_cand = C.c_size_t(0), C.c_size_t(0)
+    dev = (ctx, d_a.data_ptr(), d_fa.data_ptr(), n_a, None, None, None, 0, None)
+
+    def all_pairs(min_run):
+        return lib.vdf_align_windows_device(*dev, TOL, min_run, out.ctypes.data, len(out), C.byref(n_out), None)
+
+    def seeded(min_run):
+        rc = lib.vdf_align_seed_pairs_device(*dev, TOL, min_run, cand.ctypes.data, len(cand), C.byref(n_cand), None)
+        n_out.value = 0
+        if rc == 0 and n_cand.value:
+            rc = lib.vdf_align_windows_pairs_device(*dev, cand.ctypes.data, n_cand.value, TOL, min_run, out.ctypes.data, len(out), C.byref(n_out), None)
+        return rc
+    runs = {"parent-a": [("align", m, all_pairs) for m in (1, 2, 4)], "seeded-a": [("seeded", m, seeded) for m in (1, 2, 4)],
+            "b": [("align", MIN_RUN, all_pairs), ("seeded", MIN_RUN, seeded)]}[args.leg]
+    res = {}
+    for name, min_run, run in runs:
+        times = []
+        for r in range(REPEATS + 1):
+            t0 = time.perf_counter()
+            rc = run(min_run)
+            if r:
+                times.append(time.perf_counter() - t0)
+            assert rc == 0, (rc, lib.vdf_last_error(ctx))
+        res[f"{name}-m{min_run}"] = {"times": times, "records": int(n_out.value), "digest": digest(out[:n_out.value]),
+                                     "candidates": int(n_cand.value) if name == "seeded" else None}
+    print("RESULT " + json.dumps(res))
+
+
+def seeded_main(args):
+    parent_lib = os.path.abspath(args.parent_lib) if args.parent_lib else args.lib
+    legs = [("parent-a", parent_lib), ("seeded-a", args.lib), ("b", args.lib), ("api-plain", args.lib), ("api-seeded", args.lib)]
+    got = {}
+    for _ in range(ROUNDS):
+        for leg, lib in legs:
+            for key, v in run_child(lib, leg, mode="--seeded").items():
+                e = got.setdefault(f"{leg}/{key}", {"times": []})
+                e["times"] += v["times"]
+                e.update({k: v[k] for k in v if k != "times"})
+    n_a, n_win, _ = SHAPES[VARIANTS_SHAPE]
+    pairs = n_a * (n_a - 1) // 2
+    _, _, planted = stretches_corpus(True)
+    med = lambda key: statistics.median(got[key]["times"])
+    ms = lambda ts: f"min {min(ts) * 1e3:9.3f}  median {statistics.median(ts) * 1e3:9.3f}  max {max(ts) * 1e3:9.3f} ms ({len(ts)} calls)"
+    whose = "the PARENT commit's library" if args.parent_lib else "THIS build's library (no --parent-lib: not the parent commit)"
+    lines = [f"tools/bench_align.py --seeded: {ROUNDS} rounds x {REPEATS} timed calls per leg (one warm-up per round), fresh process per leg and round, legs in turn",
+             f"{VARIANTS_SHAPE}: {pairs} pairs of videos, {n_a * n_win} windows, device-resident; tolerance {TOL}",
+             "seeded = vdf_align_seed_pairs_device, then vdf_align_windows_pairs_device on the candidates if there is one",
+             f"leg (a): random hashes without planted copies - no pair is a candidate; all-pairs = vdf_align_windows_device of {whose}"]
+    held = True
+    for m in (2, 4):
+        pt, st = got[f"parent-a/align-m{m}"]["times"], got[f"seeded-a/seeded-m{m}"]
+        spread = max(pt) / min(pt)
+        bound = statistics.median(pt) / spread
+        ok = statistics.median(st["times"]) < bound
+        held &= ok
+        lines += [f"  min_run {m}  all-pairs  {ms(pt)}  {got[f'parent-a/align-m{m}']['records']} records",
+                  f"  min_run {m}  seeded     {ms(st['times'])}  {st['candidates']} candidates, {st['records']} records",
+                  f"  GATE min_run {m}: seeded median {statistics.median(st['times']) * 1e3:.3f} ms < parent median {statistics.median(pt) * 1e3:.3f} ms / parent max / min "
+                  f"{spread:.3f} = {bound * 1e3:.3f} ms: {'HOLDS' if ok else 'MISSED'}   (all-pairs / seeded, medians = {statistics.median(pt) / statistics.median(st['times']):.2f}x)"]
+    al, se = got[f"b/align-m{MIN_RUN}"], got[f"b/seeded-m{MIN_RUN}"]
+    same = al["digest"] == se["digest"] and al["records"] == se["records"]
+    lines += [f"leg (b): {planted} pairs ({100.0 * planted / pairs:.2f} %) share planted stretches; min_run {MIN_RUN}; both legs of this build",
+              f"  all-pairs  {ms(al['times'])}  {al['records']} records",
+              f"  seeded     {ms(se['times'])}  {se['candidates']} candidates, {se['records']} records: records of both legs {'equal' if same else 'DIFFER'}; "
+              f"all-pairs / seeded, medians = {med(f'b/align-m{MIN_RUN}') / med(f'b/seeded-m{MIN_RUN}'):.2f}x"]
+    ap_, as_ = got["api-plain/api"], got["api-seeded/api"]
+    same_c = ap_["digest"] == as_["digest"] and ap_["records"] == as_["records"]
+    lines += [f"leg (c): {SEEDED_API_VIDEOS} videos x {n_win} windows, self mode, host lists through api.align (three blocks of videos), min_run {MIN_RUN}; host clock around the call",
+              f"  seed=False {ms(ap_['times'])}  {ap_['records']} alignments",
+              f"  seed=True  {ms(as_['times'])}  {as_['records']} alignments: lists {'equal' if same_c else 'DIFFER'}; seed=False / seed=True, medians = "
+              f"{med('api-plain/api') / med('api-seeded/api'):.2f}x   (both legs build the same arrays from the lists and upload them)"]
+    p1, s1 = got["parent-a/align-m1"], got["seeded-a/seeded-m1"]
+    lines += ["leg (d): leg (a) at min_run 1 - every window is a seed: the seed pass computes every distance the all-pairs call computes, and saves only the walk",
+              f"  all-pairs  {ms(p1['times'])}  {p1['records']} records",
+              f"  seeded     {ms(s1['times'])}  {s1['candidates']} candidates, {s1['records']} records; all-pairs / seeded, medians = {med('parent-a/align-m1') / med('seeded-a/seeded-m1'):.2f}x",
+              "only leg (a) is gated"]
+    ok = held and same and same_c
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    return 0 if ok else 1
+
+
 def run_child(lib, leg, variants=False, mode=None):
     out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--lib", lib, "--leg", leg] + (["--variants"] if variants else []) + ([mode] if mode else []),
                          capture_output=True, text=True, timeout=900)
@@ -425,15 +566,19 @@ def main():
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--variants", action="store_true")
     ap.add_argument("--stretches", action="store_true")
+    ap.add_argument("--seeded", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--lib", default=os.path.join(ROOT, "vid_dup_finder_lib_amd", "libvdf_hip.so"))
     ap.add_argument("--leg", default="align")
     args = ap.parse_args()
     if args.child:
-        return stretches_child(args) if args.stretches else variants_child(args) if args.variants else child(args)
+        return seeded_child(args) if args.seeded else stretches_child(args) if args.stretches else variants_child(args) if args.variants else child(args)
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "align_stretches.txt" if args.stretches else "align_variants.txt" if args.variants else "align_windows.txt")
+        args.out = os.path.join(ROOT, "profiles", "align_seeded.txt" if args.seeded else "align_stretches.txt" if args.stretches else "align_variants.txt" if args.variants
+                                else "align_windows.txt")
+    if args.seeded:
+        return seeded_main(args)
     if args.stretches:
         return stretches_main(args)
     if args.variants:

@@ -27,6 +27,8 @@ GROUPS = [
      r"vdf_hash_window"),
     ("the longest shared stretch of every pair of videos, on their window hashes: which videos share a stretch, at what offset, for how long",
      r"vdf_align_windows(_host|_device)?$"),
+    ("a library is not walked pair by pair: the candidate pairs of the align calls from every min_run-th window, and the align calls on a list of pairs",
+     r"vdf_align_seed_pairs|vdf_align_windows_(stretches_)?pairs"),
     ("EVERY shared stretch of a pair, ranked: an ad break cut out, a source used twice - the best run, then the best outside its rectangle, ...",
      r"vdf_align_windows_stretches"),
     ("mirrored / flipped / reversed STRETCHES: the variant of a set of window hashes from their zero planes, and alignment against it",

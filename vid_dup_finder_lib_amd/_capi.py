@@ -105,6 +105,11 @@ class VdfAlignmentStretch(C.Structure):
     _fields_ = VdfAlignment._fields_ + [("rank", C.c_uint32)]
 
 
+class VdfVideoPair(C.Structure):
+    """One pair of vdf_align_seed_pairs* and of the lists of the *_pairs calls: 8 bytes (the numpy twin is engine.VIDEO_PAIR_DTYPE)."""
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32)]
+
+
 AGREE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64))
 OR_BITMAP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -121,6 +126,7 @@ _u64p = C.POINTER(C.c_uint64)
 _u32p = C.POINTER(C.c_uint32)
 _u8p = C.POINTER(C.c_uint8)
 _ctx = C.c_void_p
+_ALIGN_SIDES = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
 
 # name -> (restype, argtypes).  Keep in step with include/vdf.h; tests/test_capi_symbols.py checks both ways.
 SIGNATURES = {
@@ -183,6 +189,21 @@ SIGNATURES = {
     "vdf_align_windows_stretches_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                      C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                                      C.POINTER(C.c_size_t), C.c_void_p]),
+    # the three sides-of-a-call blocks: (a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip); the *_pairs forms then take (pairs, n_pairs)
+    "vdf_align_seed_pairs_host": (C.c_int, _ALIGN_SIDES + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vdf_align_seed_pairs": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vdf_align_seed_pairs_device": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "vdf_align_windows_pairs_host": (C.c_int, _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vdf_align_windows_pairs": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                                   C.POINTER(C.c_size_t)]),
+    "vdf_align_windows_pairs_device": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                                          C.POINTER(C.c_size_t), C.c_void_p]),
+    "vdf_align_windows_stretches_pairs_host": (C.c_int, _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                                         C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vdf_align_windows_stretches_pairs": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                             C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vdf_align_windows_stretches_pairs_device": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                                    C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
     "vdf_cropdetect_letterbox_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                                   C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "vdf_hash_frames_u8_cropped_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,

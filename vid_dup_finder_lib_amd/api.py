@@ -20,7 +20,8 @@ import numpy as np
 from . import _capi
 from ._capi import DEFAULT_SEARCH_TOLERANCE, HASH_BITS, HASH_WORDS, TOLERANCE_SCALING_FACTOR, VdfError
 from .engine import (ALIGN_DTYPE, ALIGN_STRETCH_DTYPE, ALIGN_VARIANT_DTYPE, Engine, align_windows_host, align_windows_stretches_host, align_windows_variants_host, hamming_distance_words, hash_variant,
-                     tolerance_int)
+                     tolerance_int, video_pairs, align_seed_pairs_host, align_windows_pairs_host, align_windows_stretches_pairs_host,
+                     pair_list_problem)
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
            "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "hash_frame_windows", "locate", "rust_path_key", "sort_order",
@@ -582,12 +583,15 @@ def _align_csr(windows, static):
     return words, first, skip, counts
 
 
-def _align_call(engine, a, b, tol_int, min_run):
-    """One call of the C ABI, repeated with a larger buffer if the first try's was too small.  a, b: (words, first, skip); b None: self."""
+def _align_call(engine, a, b, tol_int, min_run, plist=None):
+    """One call of the C ABI, repeated with a larger buffer if the first try's was too small.  a, b: (words, first, skip); b None: self.
+    plist: only these pairs of the call's videos (the *_pairs form); None: all of them."""
     def once(capacity):
         kw = dict(tol_int=tol_int, min_run=min_run, a_skip=a[2], capacity=capacity)
         if b is not None:
             kw.update(b_hashes=b[0], b_first=b[1], b_skip=b[2])
+        if plist is not None:
+            return align_windows_pairs_host(a[0], a[1], plist, **kw) if engine is None else engine.align_windows_pairs(a[0], a[1], plist, **kw)
         return align_windows_host(a[0], a[1], **kw) if engine is None else engine.align_windows(a[0], a[1], **kw)
     rec, found = once(ALIGN_FIRST_CAPACITY)
     if found > len(rec):
@@ -595,15 +599,94 @@ def _align_call(engine, a, b, tol_int, min_run):
     return rec
 
 
+def _seed_call(engine, a, b, tol_int, min_run):
+    """_align_call for the seed calls: the candidate pairs of one call, VIDEO_PAIR_DTYPE in (a, b) order."""
+    def once(capacity):
+        kw = dict(tol_int=tol_int, min_run=min_run, a_skip=a[2], capacity=capacity)
+        if b is not None:
+            kw.update(b_hashes=b[0], b_first=b[1], b_skip=b[2])
+        return align_seed_pairs_host(a[0], a[1], **kw) if engine is None else engine.align_seed_pairs(a[0], a[1], **kw)
+    p, found = once(ALIGN_FIRST_CAPACITY)
+    if found > len(p):
+        p, found = once(found)
+    return p
+
+
+def _align_pair_list(pairs, n_a, n_b, self_mode):
+    """The `pairs` keyword of align / align_all as VIDEO_PAIR_DTYPE, checked as the library checks the list of a *_pairs call."""
+    if pairs is None:
+        return None
+    p = video_pairs(pairs if isinstance(pairs, np.ndarray) else np.asarray(list(pairs), dtype=np.int64))
+    problem = pair_list_problem(p, n_a, n_b, self_mode)
+    if problem:
+        raise ValueError(problem)
+    return p
+
+
+def _block_pairs(engine, A, B, a0, a1, b0, b1, tol_int, min_run, pair_list, seed):
+    """The pairs of one block of videos [a0, a1) x [b0, b1) that are aligned, counted inside the block: those of the caller's list, the seeded
+    candidates (vdf_align_seed_pairs), or the candidates that are on the list.  None: every pair of the block."""
+    plist = None
+    if pair_list is not None:
+        sel = (pair_list["a"] >= a0) & (pair_list["a"] < a1) & (pair_list["b"] >= b0) & (pair_list["b"] < b1)
+        plist = pair_list[sel].copy()
+        plist["a"] -= a0
+        plist["b"] -= b0
+        if not len(plist):
+            return plist
+    if seed:
+        cand = _seed_call(engine, A, B, tol_int, min_run)
+        if plist is None:
+            return cand
+        key = lambda p: (p["a"].astype(np.uint64) << np.uint64(32)) | p["b"].astype(np.uint64)
+        plist = plist[np.isin(key(plist), key(cand))]
+    return plist
+
+
+def candidate_pairs(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoHash]]] = None, tolerance: float = DEFAULT_SEARCH_TOLERANCE,
+                    min_run: int = 1, static_a=None, static_b=None, engine: Optional[Engine] = None) -> List[tuple]:
+    """Which pairs of videos can share a stretch at all?  Arguments as `align`; -> [(a, b)] in (a, b) order: the pairs with a window ka of a,
+    ka a multiple of min_run, and a window of b within `tolerance` of each other, neither static (include/vdf.h: vdf_align_seed_pairs).  A run of
+    min_run windows holds such a window, so every pair `align` reports is among them - and a library of unrelated videos costs 1 / min_run of
+    the distances of `align` at several times its rate instead of a walk of every pair."""
+    self_mode = windows_b is None
+    tol_int = tolerance_int(tolerance)
+    wa, fa, ka, ca = _align_csr(windows_a, static_a)
+    wb, fb, kb, cb = (wa, fa, ka, ca) if self_mode else _align_csr(windows_b, static_b)
+    if engine is None:
+        cells = (sum(ca) ** 2 - sum(n * n for n in ca)) // 2 if self_mode else sum(ca) * sum(cb)
+        if cells > ALIGN_HOST_CELLS:
+            engine = default_engine()
+
+    def block(words, first, skip, lo, hi):
+        w0, w1 = int(first[lo]), int(first[hi])
+        return words[w0:w1], first[lo:hi + 1] - first[lo], None if skip is None else skip[w0:w1]
+
+    step = max(1, math.isqrt(ALIGN_MAX_PAIRS))
+    out = []
+    for a0 in range(0, len(ca), step):
+        a1 = min(a0 + step, len(ca))
+        A = block(wa, fa, ka, a0, a1)
+        for b0 in range(a0 if self_mode else 0, len(cb), step):
+            b1 = min(b0 + step, len(cb))
+            p = _seed_call(engine, A, None if (self_mode and b0 == a0) else block(wb, fb, kb, b0, b1), tol_int, int(min_run))
+            out += [(int(a) + a0, int(b) + b0) for a, b in zip(p["a"], p["b"])]
+    return sorted(out)
+
+
 def align(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoHash]]] = None, tolerance: float = DEFAULT_SEARCH_TOLERANCE,
-          min_run: int = 1, stride: int = 1, static_a=None, static_b=None, engine: Optional[Engine] = None) -> List[Alignment]:
+          min_run: int = 1, stride: int = 1, static_a=None, static_b=None, engine: Optional[Engine] = None, pairs=None,
+          seed: bool = False) -> List[Alignment]:
     """Which videos share a stretch, at what offset, and for how long?  windows_a / windows_b: hash_frame_windows' results at the same
     `stride` (videos may differ in length); windows_b None: the videos of windows_a against each other, every pair once (a < b).
     Per pair of videos at most ONE Alignment, ordered by (a, b): the run of consecutive windows within `tolerance` on one diagonal
     (first_frame_b - first_frame_a constant) that maximises n_windows * (tol_int + 1) - sum of distances, of at least min_run windows
     (include/vdf.h: vdf_align_windows; a video that holds two separate excerpts of another reports the better one - align_all reports both).
     static_a / static_b: per video, one flag per window (static_windows); flagged windows abstain - static stretches match each other
-    everywhere.  Calls of more than ALIGN_MAX_PAIRS pairs are split.  With no engine given, tiny inputs are walked on the CPU."""
+    everywhere.  Calls of more than ALIGN_MAX_PAIRS pairs are split.  With no engine given, tiny inputs are walked on the CPU.
+    pairs: only these (a, b) are aligned - strictly increasing in (a, b), a < b when windows_b is None (vdf_align_windows_pairs).
+    seed=True: every block of videos is seeded first (candidate_pairs) and only its candidates are aligned; the result is the same list, and
+    a library in which few videos share anything is not walked pair by pair.  With both, the candidates on the list."""
     self_mode = windows_b is None
     s = int(stride)
     if s != stride or s < 1:
@@ -611,6 +694,7 @@ def align(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoH
     tol_int = tolerance_int(tolerance)
     wa, fa, ka, ca = _align_csr(windows_a, static_a)
     wb, fb, kb, cb = (wa, fa, ka, ca) if self_mode else _align_csr(windows_b, static_b)
+    pair_list = _align_pair_list(pairs, len(ca), len(cb), self_mode)
     if engine is None:
         cells = (sum(ca) ** 2 - sum(n * n for n in ca)) // 2 if self_mode else sum(ca) * sum(cb)
         if cells > ALIGN_HOST_CELLS:
@@ -627,7 +711,11 @@ def align(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoH
         A = block(wa, fa, ka, a0, a1)
         for b0 in range(a0 if self_mode else 0, len(cb), step):
             b1 = min(b0 + step, len(cb))
-            rec = _align_call(engine, A, None if (self_mode and b0 == a0) else block(wb, fb, kb, b0, b1), tol_int, int(min_run)).copy()
+            B = None if (self_mode and b0 == a0) else block(wb, fb, kb, b0, b1)
+            plist = _block_pairs(engine, A, B, a0, a1, b0, b1, tol_int, int(min_run), pair_list, seed)
+            if plist is not None and not len(plist):
+                continue
+            rec = _align_call(engine, A, B, tol_int, int(min_run), plist).copy()
             rec["a"] += a0
             rec["b"] += b0
             parts.append(rec)
@@ -658,12 +746,16 @@ class AlignmentStretch(NamedTuple):
     rank: int = 0
 
 
-def _align_all_call(engine, a, b, tol_int, min_run, max_stretches, guard):
+def _align_all_call(engine, a, b, tol_int, min_run, max_stretches, guard, plist=None):
     """_align_call for the stretches calls."""
     def once(capacity):
         kw = dict(tol_int=tol_int, min_run=min_run, max_stretches=max_stretches, guard=guard, a_skip=a[2], capacity=capacity)
         if b is not None:
             kw.update(b_hashes=b[0], b_first=b[1], b_skip=b[2])
+        if plist is not None:
+            if engine is None:
+                return align_windows_stretches_pairs_host(a[0], a[1], plist, **kw)
+            return engine.align_windows_stretches_pairs(a[0], a[1], plist, **kw)
         return align_windows_stretches_host(a[0], a[1], **kw) if engine is None else engine.align_windows_stretches(a[0], a[1], **kw)
     rec, found = once(ALIGN_FIRST_CAPACITY)
     if found > len(rec):
@@ -673,7 +765,7 @@ def _align_all_call(engine, a, b, tol_int, min_run, max_stretches, guard):
 
 def align_all(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoHash]]] = None, tolerance: float = DEFAULT_SEARCH_TOLERANCE,
               min_run: int = 1, stride: int = 1, max_stretches: int = 4, guard: Optional[int] = None, static_a=None, static_b=None,
-              engine: Optional[Engine] = None) -> List[AlignmentStretch]:
+              engine: Optional[Engine] = None, pairs=None, seed: bool = False) -> List[AlignmentStretch]:
     """EVERY stretch two videos share, not only the best one: a re-upload with an ad break cut out shares two stretches at two offsets with
     its source, a compilation that uses a source twice repeats one.  Arguments as `align`; per pair of videos up to max_stretches (1 ... 8)
     AlignmentStretch, ordered by (a, b, rank).  Rank 0 is the Alignment `align` reports; after every reported stretch its rectangle - its
@@ -681,7 +773,8 @@ def align_all(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[Vi
     left (include/vdf.h: vdf_align_windows_stretches).  The same windows of a matched against ANOTHER part of b stay visible.
     guard None: ceil(15 / stride) windows - windows less than 16 frames apart share frames, so in slowly changing content the diagonals
     beside a stretch match too, and what the bare rectangle leaves of them at its ends would be reported as short stretches of their own.
-    Calls of more than ALIGN_MAX_PAIRS pairs are split.  With no engine given, tiny inputs are walked on the CPU."""
+    Calls of more than ALIGN_MAX_PAIRS pairs are split.  With no engine given, tiny inputs are walked on the CPU.
+    pairs / seed: as in `align` - only the listed pairs, only the seeded candidates (the same list as without), or the candidates on the list."""
     self_mode = windows_b is None
     s = int(stride)
     if s != stride or s < 1:
@@ -691,6 +784,7 @@ def align_all(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[Vi
     tol_int = tolerance_int(tolerance)
     wa, fa, ka, ca = _align_csr(windows_a, static_a)
     wb, fb, kb, cb = (wa, fa, ka, ca) if self_mode else _align_csr(windows_b, static_b)
+    pair_list = _align_pair_list(pairs, len(ca), len(cb), self_mode)
     if engine is None:
         cells = (sum(ca) ** 2 - sum(n * n for n in ca)) // 2 if self_mode else sum(ca) * sum(cb)
         if cells > ALIGN_HOST_CELLS:
@@ -707,8 +801,11 @@ def align_all(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[Vi
         A = block(wa, fa, ka, a0, a1)
         for b0 in range(a0 if self_mode else 0, len(cb), step):
             b1 = min(b0 + step, len(cb))
-            rec = _align_all_call(engine, A, None if (self_mode and b0 == a0) else block(wb, fb, kb, b0, b1), tol_int, int(min_run), int(max_stretches),
-                                  int(guard)).copy()
+            B = None if (self_mode and b0 == a0) else block(wb, fb, kb, b0, b1)
+            plist = _block_pairs(engine, A, B, a0, a1, b0, b1, tol_int, int(min_run), pair_list, seed)
+            if plist is not None and not len(plist):
+                continue
+            rec = _align_all_call(engine, A, B, tol_int, int(min_run), int(max_stretches), int(guard), plist).copy()
             rec["a"] += a0
             rec["b"] += b0
             parts.append(rec)

@@ -14,6 +14,8 @@
 // The lane-ownership rules are align_plan.h's (shared with the CPU replay in tests/cpp/align_plan_main.cpp).
 // align_reduce_kernel / align_scan_kernel / align_scatter_kernel: the bands of each pair -> one record, the pairs that have one -> a
 // dense list in (a, b) order (flag + scan: the pairs of a chunk are enumerated in that order).
+// align_seed_kernel / align_seed_count_kernel / align_seed_scatter_kernel, at the end of the file: which pairs of videos can have a record at
+// all (vdf_align_seed_pairs*), so that the band kernels run on those pairs only.
 #include "align_plan.h"
 #include "vdf_internal.h"
 
@@ -359,6 +361,189 @@ hipError_t launch_align_chunk(const AlignLaunch &L, hipStream_t stream)
     *L.dense_out = dense;
     *L.total_out = total;
     return hipSuccess;
+}
+
+// ---- seeding: the pairs of videos that have a matching (seed, row) cell (include/vdf.h: vdf_align_seed_pairs*) -------------------
+// align_seed_kernel: one workgroup per unit (chunk of seeds, tile of rows of B; align_plan.h: AlignSeedPlan), modelled on the VALU search
+// backend (hamming.hip: hamming_tile_kernel).  The tile's rows sit in VGPRs, R per lane, each with its video index and its skip byte; the
+// chunk's seeds stream through SGPRs (scalar loads: the seed's row of A, its video, its skip byte).  After CHKW dwords a seed that every row of
+// the wave is already more than tol away from is left: partial distances only grow, so the exit is exact.  A hit - behind a wave-uniform ballot
+// - sets bit seed_video * n_b + row_video of the bitmap: the word is read first and the atomic is issued only if the bit is still clear, so
+// dense matches cost reads that hit in L2, no atomics and no list.  Rows at or behind n_rows are never addressed: their lanes hold zero rows
+// with the skip byte set, which cannot hit.
+typedef const __attribute__((address_space(4))) unsigned long long *align_u64_ptr;
+
+template <int R, int CHKW>
+__global__ __launch_bounds__(256) void align_seed_kernel(
+    const uint32_t *__restrict__ a_hashes, const uint8_t *__restrict__ a_skip, const uint32_t *__restrict__ seed_window,
+    const uint32_t *__restrict__ seed_video, uint32_t n_seeds, uint32_t chunk_seeds, const uint32_t *__restrict__ b_hashes,
+    const uint8_t *__restrict__ b_skip, const uint32_t *__restrict__ row_video, uint32_t row_base, uint32_t n_rows,
+    const unsigned long long *__restrict__ unit_offset, const uint32_t *__restrict__ tile_first, uint32_t n_chunks, uint32_t tol, int self_mode,
+    uint32_t n_b, uint32_t *__restrict__ bitmap, unsigned long long unit_base)
+{
+    constexpr uint32_t TILE_ROWS = 256 * R;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned long long unit = unit_base + blockIdx.x;  // grids above 2^32 work-items are launched in cuts
+    const uint32_t chunk = align_seed_unit_chunk((align_u64_ptr)(uintptr_t)unit_offset, n_chunks, unit);
+    const uint32_t tile = ((align_u32_ptr)(uintptr_t)tile_first)[chunk] + (uint32_t)(unit - ((align_u64_ptr)(uintptr_t)unit_offset)[chunk]);
+    const uint64_t wave_row0 = (uint64_t)tile * TILE_ROWS + wave * (64 * R);
+    if (wave_row0 >= n_rows) return;  // wave-uniform: a wave of padding rows only (no barrier below)
+    const uint32_t s0 = chunk * chunk_seeds, s1 = min(s0 + chunk_seeds, n_seeds);
+
+    // rows -> VGPRs
+    uint32_t rw[R][32];
+    uint32_t rvid[R], rskip[R];
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+        const uint64_t r = wave_row0 + k * 64 + lane;
+        if (r < n_rows) {
+            const size_t w = (size_t)row_base + (size_t)r;
+            align_load_row(rw[k], b_hashes, (uint32_t)w);  // row_base + r <= first_b[n_b]: 32 bits
+            rvid[k] = row_video[r];
+            rskip[k] = b_skip ? b_skip[w] : 0u;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 32; q++) rw[k][q] = 0u;
+            rvid[k] = 0u;
+            rskip[k] = 1u;
+        }
+    }
+
+    align_u32_ptr a_rows = (align_u32_ptr)(uintptr_t)a_hashes;
+    for (uint32_t s = s0; s < s1; ++s) {
+        const uint32_t sw = ((align_u32_ptr)(uintptr_t)seed_window)[s];
+        align_u32_ptr ap = a_rows + (size_t)sw * 32;
+        uint32_t d[R];
+#pragma unroll
+        for (int k = 0; k < R; k++) d[k] = 0u;
+#pragma unroll
+        for (int w = 0; w < (CHKW < 32 ? CHKW : 32); ++w) {
+            const uint32_t aw = ap[w];  // SGPR
+#pragma unroll
+            for (int k = 0; k < R; k++) d[k] += __builtin_popcount(rw[k][w] ^ aw);
+        }
+        uint32_t m = d[0];
+#pragma unroll
+        for (int k = 1; k < R; k++) m = min(m, d[k]);
+        if (CHKW < 32) {
+            if (__builtin_amdgcn_ballot_w64(m <= tol) == 0ull) continue;  // partial distances only grow
+#pragma unroll
+            for (int w = CHKW; w < 32; ++w) {
+                const uint32_t aw = ap[w];
+#pragma unroll
+                for (int k = 0; k < R; k++) d[k] += __builtin_popcount(rw[k][w] ^ aw);
+            }
+            m = d[0];
+#pragma unroll
+            for (int k = 1; k < R; k++) m = min(m, d[k]);
+        }
+        if (__builtin_amdgcn_ballot_w64(m <= tol) != 0ull) {
+            // rare path: the seed's skip byte (with the aligned dword that holds it, by a scalar load like the row), the triangle, the bitmap
+            bool a_ok = true;
+            if (a_skip) {
+                const uintptr_t at = (uintptr_t)a_skip + sw;
+                a_ok = ((*(align_u32_ptr)(at & ~(uintptr_t)3) >> (8 * (uint32_t)(at & 3))) & 0xFFu) == 0u;
+            }
+            if (a_ok) {
+                const uint32_t sv = ((align_u32_ptr)(uintptr_t)seed_video)[s];
+#pragma unroll
+                for (int k = 0; k < R; k++) {
+                    if (d[k] <= tol && rskip[k] == 0u && (!self_mode || sv < rvid[k])) {
+                        const uint64_t bit = (uint64_t)sv * n_b + rvid[k];
+                        uint32_t *word = bitmap + (size_t)(bit >> 5);
+                        const uint32_t mask = 1u << (uint32_t)(bit & 31);
+                        if ((__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & mask) == 0u) atomicOr(word, mask);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// the sum of v over the threads in front of this one in its 256-thread workgroup, and the workgroup's sum
+__device__ __forceinline__ uint32_t align_block_prefix(uint32_t v, uint32_t *s_wave, uint32_t *block_total)
+{
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)inc, o, 64);
+        if (lane >= (uint32_t)o) inc += up;
+    }
+    if (lane == 63) s_wave[wave] = inc;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+    for (uint32_t k = 0; k < 4; k++) { if (k < wave) before += s_wave[k]; total += s_wave[k]; }
+    *block_total = total;
+    return before + inc - v;
+}
+
+// align_seed_compact: bitmap -> the dense list of its set bits in bit order = (a, b) order.  Count (one thread per word, block_count[g] = bits
+// of workgroup g's 256 words), the scan of the align reductions (align_scan_kernel, launched as it is), scatter.
+__global__ __launch_bounds__(256) void align_seed_count_kernel(const uint32_t *__restrict__ bitmap, uint32_t n_words, uint32_t *__restrict__ block_count)
+{
+    __shared__ uint32_t s_wave[4];
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t n = i < n_words ? (uint32_t)__builtin_popcount(bitmap[i]) : 0u;
+    uint32_t total;
+    (void)align_block_prefix(n, s_wave, &total);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+
+// the first `limit` pairs of the list are written (the caller's capacity: the list of a dense bitmap is 2^24 x 8 bytes)
+__global__ __launch_bounds__(256) void align_seed_scatter_kernel(const uint32_t *__restrict__ bitmap, uint32_t n_words, uint32_t n_b,
+                                                                 const uint32_t *__restrict__ block_offset, vdf_video_pair *__restrict__ out,
+                                                                 uint32_t limit)
+{
+    __shared__ uint32_t s_wave[4];
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    uint32_t bits = i < n_words ? bitmap[i] : 0u;
+    uint32_t total;
+    uint32_t at = block_offset[blockIdx.x] + align_block_prefix((uint32_t)__builtin_popcount(bits), s_wave, &total);
+    while (bits != 0u && at < limit) {
+        const uint64_t bit = (uint64_t)i * 32 + (uint32_t)__builtin_ctz(bits);
+        bits &= bits - 1;
+        out[at++] = vdf_video_pair{(uint32_t)(bit / n_b), (uint32_t)(bit % n_b)};
+    }
+}
+
+size_t align_seed_scratch_bytes(size_t n_words) { return (2 * ((n_words + 255) / 256) + 4) * sizeof(uint32_t) + 64; }
+
+hipError_t launch_align_seed(const AlignSeedLaunch &L, hipStream_t stream)
+{
+    if (L.n_units == 0 || L.n_words == 0 || L.n_words > (1u << 21)) return hipErrorInvalidValue;  // 2^24 pairs a < b: 5793^2 bits, just above 2^25
+    for (const AlignLaunchCut &cut : align_launch_cuts((size_t)L.n_units)) {
+#define VDF_SEED_LAUNCH(CW)                                                                                                                         \
+    hipLaunchKernelGGL((align_seed_kernel<(int)kSeedRowsPerLane, CW>), dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_skip,            \
+                       L.seed_window, L.seed_video, L.n_seeds, kSeedChunk, L.b_hashes, L.b_skip, L.row_video, L.row_base, L.n_rows, L.unit_offset, \
+                       L.tile_first, L.n_chunks, L.tol, L.self_mode, L.n_b, L.bitmap, (unsigned long long)cut.group_base)
+        switch (align_seed_check_words(L.tol)) {
+        case 14: VDF_SEED_LAUNCH(14); break;
+        case 22: VDF_SEED_LAUNCH(22); break;
+        case 26: VDF_SEED_LAUNCH(26); break;
+        default: VDF_SEED_LAUNCH(32); break;
+        }
+#undef VDF_SEED_LAUNCH
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    // scratch: block counts | block offsets | total
+    const uint32_t n_blocks = (L.n_words + 255) / 256;
+    uint32_t *block_count = static_cast<uint32_t *>(L.scratch), *block_offset = block_count + n_blocks, *total = block_offset + n_blocks;
+    hipLaunchKernelGGL(align_seed_count_kernel, dim3(n_blocks), dim3(256), 0, stream, L.bitmap, L.n_words, block_count);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(align_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, n_blocks, block_offset, total);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    *L.total_out = total;
+    return hipSuccess;
+}
+
+hipError_t launch_align_seed_scatter(const AlignSeedLaunch &L, vdf_video_pair *out, uint32_t limit, hipStream_t stream)
+{
+    const uint32_t n_blocks = (L.n_words + 255) / 256;
+    const uint32_t *block_offset = static_cast<const uint32_t *>(L.scratch) + n_blocks;
+    hipLaunchKernelGGL(align_seed_scatter_kernel, dim3(n_blocks), dim3(256), 0, stream, L.bitmap, L.n_words, L.n_b, block_offset, out, limit);
+    return hipGetLastError();
 }
 
 }  // namespace vdf

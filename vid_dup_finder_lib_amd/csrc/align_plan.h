@@ -192,4 +192,112 @@ inline bool align_next_round(const AlignRound &prev, const Rec *recs, size_t n_r
     return next.pairs.size() <= prev.pairs.size() && next.n_units() <= prev.n_units();
 }
 
+// ---- a caller-given list of pairs instead of all of them (vdf_align_windows_pairs*, vdf_align_windows_stretches_pairs*) --------
+// What a pair list must be: strictly increasing in (a, b), a < n_a, b < n_b, and a < b in self mode.  0: fine; 1: not strictly increasing at
+// *at (unsorted or a duplicate); 2: pair *at names a video that does not exist; 3: pair *at has a >= b in self mode.
+template <class P> inline int align_pair_list_check(const P *list, size_t n_list, size_t n_a, size_t n_b, bool self, size_t *at)
+{
+    for (size_t i = 0; i < n_list; i++) {
+        *at = i;
+        if (i && (list[i].a < list[i - 1].a || (list[i].a == list[i - 1].a && list[i].b <= list[i - 1].b))) return 1;
+        if (list[i].a >= n_a || list[i].b >= (self ? n_a : n_b)) return 2;
+        if (self && list[i].a >= list[i].b) return 3;
+    }
+    return 0;
+}
+
+// align_next_chunk fed from a checked pair list: the same limits per chunk, pairs with a video of 0 windows skipped.  cur: the next list entry.
+template <class P>
+inline bool align_next_chunk_pairs(const uint32_t *first_a, const uint32_t *first_b, const P *list, size_t n_list, size_t &cur, AlignChunk &c,
+                                   size_t max_pairs = kAlignChunkPairs, size_t max_units = kAlignChunkUnits)
+{
+    c.pairs.clear();
+    c.unit_offset.assign(1, 0u);
+    size_t units = 0;
+    for (; cur < n_list; cur++) {
+        const uint32_t a = list[cur].a, b = list[cur].b;
+        const uint32_t bands = align_bands(first_a[a + 1] - first_a[a], first_b[b + 1] - first_b[b]);
+        if (!bands) continue;
+        if (!c.pairs.empty() && (c.pairs.size() >= max_pairs || units + bands > max_units)) return true;
+        c.pairs.push_back({a, b});
+        units += bands;
+        c.unit_offset.push_back((uint32_t)units);
+    }
+    return !c.pairs.empty();
+}
+
+// ---- seeding: which pairs of videos can have a record at all (vdf_align_seed_pairs*) ---------------------------------------------
+// A competing run has min_run consecutive matching cells on one diagonal, and any min_run consecutive ka hold a multiple of min_run: a pair
+// with a record has a matching cell whose ka - counted inside video a - is a multiple of min_run.  Those windows of A are the SEEDS; the seed
+// kernel (align.hip) compares every seed with every row of B and marks the pairs of videos that have a matching cell.
+// Rows of B are cut into tiles (a workgroup keeps a tile in VGPRs), seeds into chunks (a workgroup streams one through SGPRs); a UNIT is
+// (chunk, tile).  In self mode only the cells with seed video < row video count: both video arrays ascend, so the tiles that hold such a
+// cell for chunk c are a suffix of the tiles, tile_first[c] ... n_tiles - 1 - the triangle.
+constexpr uint32_t kSeedRowsPerLane = 2;                       // the VALU search backend's default instantiation (hamming.hip)
+constexpr uint32_t kSeedTileRows = 256 * kSeedRowsPerLane;
+constexpr uint32_t kSeedChunk = 256;                           // seeds per unit
+// The exact early exit: after this many of a hash's 32 dwords, unrelated hashes (partial distance 16 w +- sqrt(8 w)) are, 4 sigma down, still
+// more than tol apart, and nearly every (seed, wave) stops there.  32: no test.  The kernel is instantiated for 14, 22, 26 and 32.
+inline uint32_t align_seed_check_words(uint32_t tol)
+{
+    for (uint32_t w : {14u, 22u, 26u}) {
+        uint32_t r = 0;  // floor(sqrt(32 w))
+        while ((r + 1) * (r + 1) <= 32 * w) r++;
+        if (16 * w >= tol + 1 + 2 * (r + 1)) return w;
+    }
+    return 32;
+}
+
+struct AlignSeedPlan {
+    std::vector<uint32_t> seed_window;  // [seeds]: the seed's row of A (an index into a_hashes, as first_a counts)
+    std::vector<uint32_t> seed_video;   // [seeds]: ascending
+    std::vector<uint32_t> row_video;    // [rows]: the video of row r of B; row r is window row_base + r of b_hashes.  Ascending
+    std::vector<uint32_t> tile_first;   // [chunks]: the first tile chunk c is compared with
+    std::vector<uint64_t> unit_offset;  // [chunks + 1]: chunk c owns the units unit_offset[c] ..., unit u is tile tile_first[c] + u - unit_offset[c]
+    uint32_t row_base = 0, n_rows = 0, n_tiles = 0;
+    size_t n_seeds() const { return seed_window.size(); }
+    size_t n_chunks() const { return tile_first.size(); }
+    uint64_t n_units() const { return unit_offset.empty() ? 0 : unit_offset.back(); }
+};
+
+// first_b = first_a, n_b = n_a in self mode
+inline void align_seed_plan(const uint32_t *first_a, size_t n_a, const uint32_t *first_b, size_t n_b, bool self, uint32_t min_run, AlignSeedPlan &p,
+                            uint32_t tile_rows = kSeedTileRows, uint32_t chunk = kSeedChunk)
+{
+    p.seed_window.clear(); p.seed_video.clear(); p.row_video.clear(); p.tile_first.clear(); p.unit_offset.assign(1, 0ull);
+    p.row_base = n_b ? first_b[0] : 0;
+    p.n_rows = n_b ? first_b[n_b] - first_b[0] : 0;
+    p.n_tiles = (uint32_t)(((uint64_t)p.n_rows + tile_rows - 1) / tile_rows);
+    for (size_t a = 0; a < n_a; a++)
+        for (uint64_t w = first_a[a]; w < first_a[a + 1]; w += min_run) {  // ka = w - first_a[a] = 0, min_run, 2 min_run, ...
+            p.seed_window.push_back((uint32_t)w);
+            p.seed_video.push_back((uint32_t)a);
+        }
+    p.row_video.resize(p.n_rows);
+    for (size_t b = 0; b < n_b; b++)
+        for (uint32_t w = first_b[b]; w < first_b[b + 1]; w++) p.row_video[w - p.row_base] = (uint32_t)b;
+    if (p.n_rows == 0) return;
+    const size_t n_chunks = (p.n_seeds() + chunk - 1) / chunk;
+    uint32_t t = 0;
+    for (size_t c = 0; c < n_chunks; c++) {
+        if (self) {  // the first tile whose largest row video is above the chunk's smallest seed video; it ascends with c
+            const uint32_t v_min = p.seed_video[c * chunk];
+            while (t < p.n_tiles && p.row_video[std::min<uint64_t>((uint64_t)(t + 1) * tile_rows, p.n_rows) - 1] <= v_min) t++;
+        }
+        p.tile_first.push_back(t);
+        p.unit_offset.push_back(p.unit_offset.back() + (p.n_tiles - t));
+    }
+}
+
+// unit -> chunk: the largest c with unit_offset[c] <= unit, among the chunks that own a unit (the kernel makes the same search)
+template <class Ptr> VDF_ALIGN_HD uint32_t align_seed_unit_chunk(Ptr unit_offset, uint32_t n_chunks, uint64_t unit)
+{
+    uint32_t lo = 0, hi = n_chunks;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (unit_offset[mid] <= unit) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 }  // namespace vdf

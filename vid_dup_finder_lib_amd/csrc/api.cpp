@@ -39,7 +39,7 @@ vdf_ctx::~vdf_ctx()
                      &hits, &perm, &matched, &exp_cols, &exp_rows, &pop_cols, &pop_rows, &cand, &group_cmin, &group_offset, &group_blocks, &up_hashes,
                      &up_dur, &up_ref_hashes, &up_ref_dur, &small, &frames, &frames2, &out_hashes, &out_hashes2, &out_dc,
                      &out_dc2, &cos_table, &crops, &crop_desc, &crop_tables, &crop_desc2, &crop_tables2, &crop_work, &sort_scratch, &sort_scratch_pub, &hits2, &hit_bitmaps, &bitmap_gather,
-                     &out_zero, &out_zero2, &up_zero, &variant_hashes, &align_plan, &align_scratch, &align_up};
+                     &out_zero, &out_zero2, &up_zero, &variant_hashes, &align_plan, &align_scratch, &align_up, &seed_bitmap, &seed_plan, &seed_out};
     for (DevBuf *b : all) b->release();
     for (PinBuf &b : pin) b.release();
     for (PinBuf &b : pin_out) b.release();
@@ -1632,7 +1632,8 @@ int search_refs_resident(vdf_ctx *ctx, size_t n_cand, const std::vector<size_t> 
 // ---- alignment of videos on their window hashes (include/vdf.h: vdf_align_windows[_device|_host]) -------------------------------
 // the argument checks all three forms share, in the order their messages are reported; first arrays on the host (null: not checked here)
 int align_checks(vdf_ctx *ctx, const void *a_hashes, const uint32_t *a_first, size_t n_a, const void *b_hashes, const uint32_t *b_first, size_t n_b,
-                 const void *a_first_ptr, const void *b_first_ptr, uint32_t min_run, const void *out, size_t capacity, const size_t *n_out)
+                 const void *a_first_ptr, const void *b_first_ptr, uint32_t min_run, const void *out, size_t capacity, const size_t *n_out,
+                 const size_t *n_listed = nullptr)  // the *_pairs forms: the limit is on the LISTED pairs, not on n_a x n_b
 {
     const bool self = b_hashes == nullptr;
     if (!n_out || (n_a && (!a_hashes || !a_first_ptr)) || (!self && n_b && !b_first_ptr) || (capacity && !out)) return fail(ctx, VDF_E_INVAL, "null pointer");
@@ -1647,6 +1648,11 @@ int align_checks(vdf_ctx *ctx, const void *a_hashes, const uint32_t *a_first, si
         for (size_t v = 0; firsts[side] && v < counts[side]; v++)
             if (firsts[side][v + 1] < firsts[side][v])
                 return fail(ctx, VDF_E_INVAL, std::string("the first array") + (side ? " of B" : " of A") + " decreases at video " + std::to_string(v));
+    if (n_listed) {
+        if (n_a > 0xFFFFFFFFull || n_b > 0xFFFFFFFFull) return fail(ctx, VDF_E_INVAL, "more than 2^32 - 1 videos on one side: a video index does not fit 32 bits");
+        if (*n_listed > vdf::kAlignMaxPairs) return fail(ctx, VDF_E_INVAL, "more than 2^24 listed pairs in one call");
+        return VDF_OK;
+    }
     if (n_a > 0xFFFFFFFFull || n_b > 0xFFFFFFFFull || vdf::align_pair_count(n_a, self ? n_a : n_b, self) > vdf::kAlignMaxPairs)
         return fail(ctx, VDF_E_INVAL, "more than 2^24 pairs of videos in one call");
     return VDF_OK;
@@ -1685,12 +1691,13 @@ void align_pair_host(const uint64_t *A, uint32_t Na, const uint8_t *skip_a, cons
 // align_checks has passed on h_first_a / h_first_b (host copies of the device arrays); every array pointer is a device pointer
 int align_locked(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, const uint32_t *h_first_a, size_t n_a, const uint8_t *d_a_skip,
                  const uint64_t *d_b_hashes, const uint32_t *d_b_first, const uint32_t *h_first_b, size_t n_b, const uint8_t *d_b_skip, bool self,
-                 uint32_t tol_int, uint32_t min_run, vdf_alignment *out, size_t capacity, size_t *n_out, hipStream_t s)
+                 uint32_t tol_int, uint32_t min_run, vdf_alignment *out, size_t capacity, size_t *n_out, hipStream_t s,
+                 const vdf_video_pair *list = nullptr, size_t n_list = 0)  // list: only these pairs (checked: align_pair_list_check), not all of them
 {
     vdf::AlignCursor cur;
     vdf::AlignChunk ch;
-    size_t found = 0;
-    while (vdf::align_next_chunk(h_first_a, n_a, h_first_b, n_b, self, cur, ch)) {
+    size_t found = 0, list_at = 0;
+    while (list ? vdf::align_next_chunk_pairs(h_first_a, h_first_b, list, n_list, list_at, ch) : vdf::align_next_chunk(h_first_a, n_a, h_first_b, n_b, self, cur, ch)) {
         const size_t n_pairs = ch.pairs.size(), n_units = ch.n_units();
         const size_t pair_bytes = n_pairs * sizeof(vdf::AlignPair), off_bytes = (n_pairs + 1) * sizeof(uint32_t);
         VDF_HIP(ctx, ctx->align_plan.reserve(pair_bytes + off_bytes));
@@ -1800,15 +1807,17 @@ static int align_run_round(vdf_ctx *ctx, const AlignSides &in, const vdf::AlignR
 // run; the rounds are merged into (a, b, rank) order.  Chunks arrive in (a, b) order and each is finished before the next, so the first
 // `capacity` records of the call are the ones written.
 int align_stretches_locked(vdf_ctx *ctx, const AlignSides &in, uint32_t tol_int, uint32_t min_run, uint32_t max_stretches, uint32_t guard,
-                           vdf_alignment_stretch *out, size_t capacity, size_t *n_out, hipStream_t s)
+                           vdf_alignment_stretch *out, size_t capacity, size_t *n_out, hipStream_t s, const vdf_video_pair *list = nullptr,
+                           size_t n_list = 0)  // list: only these pairs (checked: align_pair_list_check), not all of them
 {
     vdf::AlignCursor cur;
     vdf::AlignChunk ch;
     vdf::AlignRound round, next;
     std::vector<std::vector<vdf_alignment>> rounds;
     const uint32_t tol = std::min<uint32_t>(tol_int, 1024u);
-    size_t found = 0;
-    while (vdf::align_next_chunk(in.h_first_a, in.n_a, in.h_first_b, in.n_b, in.self, cur, ch)) {
+    size_t found = 0, list_at = 0;
+    while (list ? vdf::align_next_chunk_pairs(in.h_first_a, in.h_first_b, list, n_list, list_at, ch)
+                : vdf::align_next_chunk(in.h_first_a, in.n_a, in.h_first_b, in.n_b, in.self, cur, ch)) {
         vdf::align_round_zero(ch, round);
         rounds.clear();
         for (uint32_t r = 0; r < max_stretches; r++) {
@@ -1826,6 +1835,86 @@ int align_stretches_locked(vdf_ctx *ctx, const AlignSides &in, uint32_t tol_int,
         });
     }
     *n_out = found;
+    return VDF_OK;
+}
+
+// ---- seeded candidate pairs, and the align calls on a list of pairs (include/vdf.h: vdf_align_seed_pairs*, vdf_align_windows_pairs*)
+// behind align_checks: what the list of a *_pairs call must be
+int align_list_checks(vdf_ctx *ctx, const vdf_video_pair *list, size_t n_list, size_t n_a, size_t n_b, bool self)
+{
+    size_t at = 0;
+    switch (vdf::align_pair_list_check(list, n_list, n_a, n_b, self, &at)) {
+    case 1: return fail(ctx, VDF_E_INVAL, "the pair list is not strictly increasing in (a, b) at entry " + std::to_string(at));
+    case 2: return fail(ctx, VDF_E_INVAL, "pair " + std::to_string(at) + " of the list names a video that does not exist");
+    case 3: return fail(ctx, VDF_E_INVAL, "pair " + std::to_string(at) + " of the list has a >= b in self mode");
+    default: return VDF_OK;
+    }
+}
+
+// the literal definition of the candidate set: every seed of a against every window of b, XOR + popcount
+bool seed_pair_host(const uint64_t *A, uint32_t Na, const uint8_t *skip_a, const uint64_t *B, uint32_t Nb, const uint8_t *skip_b, uint32_t tol, uint32_t min_run)
+{
+    for (uint64_t ka = 0; ka < Na; ka += min_run) {
+        if (skip_a && skip_a[ka]) continue;
+        for (uint32_t kb = 0; kb < Nb; kb++) {
+            if (skip_b && skip_b[kb]) continue;
+            uint32_t dist = 0;
+            for (int w = 0; w < VDF_HASH_WORDS; w++) dist += (uint32_t)__builtin_popcountll(A[16 * ka + w] ^ B[16 * (size_t)kb + w]);
+            if (dist <= tol) return true;
+        }
+    }
+    return false;
+}
+
+// align_checks has passed on the host copies of the first arrays; every array pointer of `in` is a device pointer.  The bitmap is cleared on
+// the call's stream, the seed kernel marks it, count + scan give the total; the host reads it, then the first min(total, capacity) pairs.
+int align_seed_locked(vdf_ctx *ctx, const AlignSides &in, uint32_t tol_int, uint32_t min_run, vdf_video_pair *out, size_t capacity, size_t *n_out, hipStream_t s)
+{
+    *n_out = 0;
+    vdf::AlignSeedPlan plan;
+    vdf::align_seed_plan(in.h_first_a, in.n_a, in.h_first_b, in.n_b, in.self, min_run, plan);
+    if (plan.n_units() == 0) return VDF_OK;  // no seed, no row of B, or (self mode) no seed below a row
+    const uint64_t n_bits = (uint64_t)in.n_a * in.n_b;  // <= 2^25 + 2^13: align_checks
+    const uint32_t n_words = (uint32_t)((n_bits + 31) / 32);
+    const size_t n_seeds = plan.n_seeds(), n_chunks = plan.n_chunks();
+    const size_t at_video = n_seeds * 4, at_row = at_video + n_seeds * 4, at_tile = at_row + (size_t)plan.n_rows * 4;
+    const size_t at_unit = (at_tile + n_chunks * 4 + 7) & ~(size_t)7, plan_bytes = at_unit + (n_chunks + 1) * 8;
+    VDF_HIP(ctx, ctx->seed_bitmap.reserve((size_t)n_words * 4));
+    VDF_HIP(ctx, ctx->seed_plan.reserve(plan_bytes));
+    VDF_HIP(ctx, ctx->align_scratch.reserve(vdf::align_seed_scratch_bytes(n_words)));
+    char *dp = ctx->seed_plan.as<char>();
+    VDF_HIP(ctx, hipMemsetAsync(ctx->seed_bitmap.p, 0, (size_t)n_words * 4, s));
+    VDF_HIP(ctx, hipMemcpyAsync(dp, plan.seed_window.data(), n_seeds * 4, hipMemcpyHostToDevice, s));
+    VDF_HIP(ctx, hipMemcpyAsync(dp + at_video, plan.seed_video.data(), n_seeds * 4, hipMemcpyHostToDevice, s));
+    VDF_HIP(ctx, hipMemcpyAsync(dp + at_row, plan.row_video.data(), (size_t)plan.n_rows * 4, hipMemcpyHostToDevice, s));
+    VDF_HIP(ctx, hipMemcpyAsync(dp + at_tile, plan.tile_first.data(), n_chunks * 4, hipMemcpyHostToDevice, s));
+    VDF_HIP(ctx, hipMemcpyAsync(dp + at_unit, plan.unit_offset.data(), (n_chunks + 1) * 8, hipMemcpyHostToDevice, s));
+    uint32_t *d_total = nullptr;
+    vdf::AlignSeedLaunch L{};
+    L.a_hashes = reinterpret_cast<const uint32_t *>(in.d_a_hashes); L.a_skip = in.d_a_skip;
+    L.seed_window = reinterpret_cast<const uint32_t *>(dp); L.seed_video = reinterpret_cast<const uint32_t *>(dp + at_video);
+    L.n_seeds = (uint32_t)n_seeds;
+    L.b_hashes = reinterpret_cast<const uint32_t *>(in.d_b_hashes); L.b_skip = in.d_b_skip;
+    L.row_video = reinterpret_cast<const uint32_t *>(dp + at_row); L.row_base = plan.row_base; L.n_rows = plan.n_rows;
+    L.unit_offset = reinterpret_cast<const unsigned long long *>(dp + at_unit);
+    L.tile_first = reinterpret_cast<const uint32_t *>(dp + at_tile);
+    L.n_chunks = (uint32_t)n_chunks; L.n_units = plan.n_units();
+    L.tol = std::min<uint32_t>(tol_int, 1024u); L.self_mode = in.self ? 1 : 0; L.n_b = (uint32_t)in.n_b;
+    L.bitmap = ctx->seed_bitmap.as<uint32_t>(); L.n_words = n_words;
+    L.scratch = ctx->align_scratch.p; L.total_out = &d_total;
+    VDF_HIP(ctx, vdf::launch_align_seed(L, s));
+    uint32_t total = 0;
+    VDF_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));  // also: the plan arrays are free to go
+    if ((uint64_t)total > n_bits) return fail(ctx, VDF_E_HIP, "align seed: more pairs than bits");
+    const size_t take = std::min<size_t>(total, capacity);
+    if (take) {
+        VDF_HIP(ctx, ctx->seed_out.reserve(take * sizeof(vdf_video_pair)));
+        VDF_HIP(ctx, vdf::launch_align_seed_scatter(L, ctx->seed_out.as<vdf_video_pair>(), (uint32_t)take, s));
+        VDF_HIP(ctx, hipMemcpyAsync(out, ctx->seed_out.p, take * sizeof(vdf_video_pair), hipMemcpyDeviceToHost, s));
+        VDF_HIP(ctx, hipStreamSynchronize(s));
+    }
+    *n_out = total;
     return VDF_OK;
 }
 
@@ -2136,6 +2225,248 @@ int vdf_align_windows_stretches(vdf_ctx *ctx, const uint64_t *a_hashes, const ui
     const AlignSides in = self ? AlignSides{d_a, u.d_fa, u.fa.data(), n_a, u.d_ska, d_a, u.d_fa, u.fa.data(), n_a, u.d_ska, true}
                                : AlignSides{d_a, u.d_fa, u.fa.data(), n_a, u.d_ska, ctx->up_ref_hashes.as<uint64_t>(), u.d_fb, u.fb.data(), n_b, u.d_skb, false};
     return align_stretches_locked(ctx, in, tol_int, min_run, max_stretches, guard, out, capacity, n_out, s);
+}
+
+// ---- seeded candidate pairs, and the align calls on a list of pairs ---------------------------------------------------------------
+int vdf_align_seed_pairs_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                              const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, uint32_t tol_int, uint32_t min_run, vdf_video_pair *out,
+                              size_t capacity, size_t *n_out)
+{
+    if (int rc = align_checks(nullptr, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, min_run, out, capacity, n_out)) return rc;
+    const bool self = b_hashes == nullptr;
+    if (self) { b_hashes = a_hashes; b_first = a_first; n_b = n_a; b_skip = a_skip; }
+    const uint32_t tol = std::min<uint32_t>(tol_int, 1024u);
+    size_t found = 0;
+    for (size_t a = 0; a < n_a; a++)
+        for (size_t b = self ? a + 1 : 0; b < n_b; b++) {
+            if (!seed_pair_host(a_hashes + 16 * (size_t)a_first[a], a_first[a + 1] - a_first[a], a_skip ? a_skip + a_first[a] : nullptr,
+                                b_hashes + 16 * (size_t)b_first[b], b_first[b + 1] - b_first[b], b_skip ? b_skip + b_first[b] : nullptr, tol, min_run))
+                continue;
+            if (found < capacity) out[found] = vdf_video_pair{(uint32_t)a, (uint32_t)b};
+            found++;
+        }
+    *n_out = found;
+    return VDF_OK;
+}
+
+// The first arrays of a device form come down to plan the launch (as vdf_align_windows_device reads them)
+static int align_first_down(vdf_ctx *ctx, const uint32_t *d_a_first, size_t n_a, const uint32_t *d_b_first, size_t n_b, bool self, hipStream_t s,
+                            std::vector<uint32_t> &fa, std::vector<uint32_t> &fb)
+{
+    fa.assign(n_a + 1, 0);
+    fb.assign(self ? 0 : n_b + 1, 0);
+    VDF_HIP(ctx, hipMemcpyAsync(fa.data(), d_a_first, fa.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (!self) VDF_HIP(ctx, hipMemcpyAsync(fb.data(), d_b_first, fb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));
+    return VDF_OK;
+}
+
+int vdf_align_seed_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a, const uint8_t *d_a_skip,
+                                const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip, uint32_t tol_int,
+                                uint32_t min_run, vdf_video_pair *out, size_t capacity, size_t *n_out, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    // as vdf_align_windows_device: everything that can be said without the first arrays; then they come down, are checked, and plan the launch
+    if (int rc = align_checks(ctx, d_a_hashes, nullptr, n_a, d_b_hashes, nullptr, n_b, d_a_first, d_b_first, min_run, out, capacity, n_out)) return rc;
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_align_seed_pairs_device takes a single-device context");
+    const bool self = d_b_hashes == nullptr;
+    *n_out = 0;
+    if (n_a == 0 || (self ? n_a < 2 : n_b == 0)) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<uint32_t> fa, fb;
+    if (int rc = align_first_down(ctx, d_a_first, n_a, d_b_first, n_b, self, s, fa, fb)) return rc;
+    if (int rc = align_checks(ctx, d_a_hashes, fa.data(), n_a, d_b_hashes, self ? nullptr : fb.data(), n_b, d_a_first, d_b_first, min_run, out, capacity, n_out))
+        return rc;
+    const AlignSides in = self ? AlignSides{d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, true}
+                               : AlignSides{d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, d_b_hashes, d_b_first, fb.data(), n_b, d_b_skip, false};
+    return align_seed_locked(ctx, in, tol_int, min_run, out, capacity, n_out, s);
+}
+
+// the sides of a host-array call once align_upload has staged them
+static AlignSides align_sides_uploaded(vdf_ctx *ctx, const AlignUploaded &u, size_t n_a, size_t n_b, bool self)
+{
+    const uint64_t *d_a = ctx->up_hashes.as<uint64_t>();
+    return self ? AlignSides{d_a, u.d_fa, u.fa.data(), n_a, u.d_ska, d_a, u.d_fa, u.fa.data(), n_a, u.d_ska, true}
+                : AlignSides{d_a, u.d_fa, u.fa.data(), n_a, u.d_ska, ctx->up_ref_hashes.as<uint64_t>(), u.d_fb, u.fb.data(), n_b, u.d_skb, false};
+}
+
+int vdf_align_seed_pairs(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                         const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, uint32_t tol_int, uint32_t min_run, vdf_video_pair *out,
+                         size_t capacity, size_t *n_out)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (int rc = align_checks(ctx, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, min_run, out, capacity, n_out)) return rc;
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_align_seed_pairs takes a single-device context");
+    const bool self = b_hashes == nullptr;
+    *n_out = 0;
+    if (n_a == 0 || (self ? n_a < 2 : n_b == 0)) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    AlignUploaded u;
+    if (int rc = align_upload(ctx, a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, self, s, &u)) return rc;
+    return align_seed_locked(ctx, align_sides_uploaded(ctx, u, n_a, n_b, self), tol_int, min_run, out, capacity, n_out, s);
+}
+
+// The checks of the *_pairs forms, in the order include/vdf.h gives them.  stretches: max_stretches and guard are checked too, behind the
+// align checks.  first arrays on the host, or null (a device form before they have come down).
+static int align_pairs_checks(vdf_ctx *ctx, const char *name, const void *a_hashes, const uint32_t *a_first, size_t n_a, const void *b_hashes,
+                              const uint32_t *b_first, size_t n_b, const void *a_first_ptr, const void *b_first_ptr, const vdf_video_pair *pairs,
+                              size_t n_pairs, uint32_t min_run, bool stretches, uint32_t max_stretches, uint32_t guard, const void *out, size_t capacity,
+                              const size_t *n_out, bool device_ctx)
+{
+    if (n_pairs && !pairs) return fail(ctx, VDF_E_INVAL, "null pair list");
+    if (int rc = align_checks(ctx, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first_ptr, b_first_ptr, min_run, out, capacity, n_out, &n_pairs)) return rc;
+    if (stretches)
+        if (int rc = align_stretches_checks(ctx, max_stretches, guard)) return rc;
+    if (int rc = align_list_checks(ctx, pairs, n_pairs, n_a, n_b, b_hashes == nullptr)) return rc;
+    if (device_ctx && !ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, std::string(name) + " takes a single-device context");
+    return VDF_OK;
+}
+
+// The plain and the stretches form share their bodies: `stretches` says which of out / out_st is written (the plain form: max_stretches 1).
+static int align_pairs_host_impl(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                                 const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int,
+                                 uint32_t min_run, bool stretches, uint32_t max_stretches, uint32_t guard, vdf_alignment *out, vdf_alignment_stretch *out_st,
+                                 size_t capacity, size_t *n_out)
+{
+    const void *o = stretches ? (const void *)out_st : (const void *)out;
+    if (int rc = align_pairs_checks(nullptr, "", a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, pairs, n_pairs, min_run, stretches,
+                                    max_stretches, guard, o, capacity, n_out, false))
+        return rc;
+    const bool self = b_hashes == nullptr;
+    if (self) { b_hashes = a_hashes; b_first = a_first; n_b = n_a; b_skip = a_skip; }
+    const uint32_t tol = std::min<uint32_t>(tol_int, 1024u);
+    size_t found = 0;
+    for (size_t i = 0; i < n_pairs; i++) {
+        const uint32_t a = pairs[i].a, b = pairs[i].b;
+        const uint32_t Na = a_first[a + 1] - a_first[a], Nb = b_first[b + 1] - b_first[b];
+        vdf::AlignRect rects[vdf::kAlignMaxStretches];
+        for (uint32_t rank = 0; rank < max_stretches; rank++) {
+            vdf_alignment r;
+            align_pair_host(a_hashes + 16 * (size_t)a_first[a], Na, a_skip ? a_skip + a_first[a] : nullptr, b_hashes + 16 * (size_t)b_first[b], Nb,
+                            b_skip ? b_skip + b_first[b] : nullptr, tol, min_run, &r, rects, rank);
+            if (r.n_windows == 0) break;
+            r.a = a; r.b = b;
+            if (found < capacity) {
+                if (stretches) out_st[found] = stretch_of(r, rank);
+                else out[found] = r;
+            }
+            found++;
+            rects[rank] = vdf::align_rect_of(r.offset, r.start_a, r.n_windows, guard, Na, Nb);
+        }
+    }
+    *n_out = found;
+    return VDF_OK;
+}
+
+static int align_pairs_run(vdf_ctx *ctx, const AlignSides &in, const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int, uint32_t min_run, bool stretches,
+                           uint32_t max_stretches, uint32_t guard, vdf_alignment *out, vdf_alignment_stretch *out_st, size_t capacity, size_t *n_out, hipStream_t s)
+{
+    if (stretches) return align_stretches_locked(ctx, in, tol_int, min_run, max_stretches, guard, out_st, capacity, n_out, s, pairs, n_pairs);
+    return align_locked(ctx, in.d_a_hashes, in.d_a_first, in.h_first_a, in.n_a, in.d_a_skip, in.d_b_hashes, in.d_b_first, in.h_first_b, in.n_b, in.d_b_skip,
+                        in.self, tol_int, min_run, out, capacity, n_out, s, pairs, n_pairs);
+}
+
+static int align_pairs_device_impl(vdf_ctx *ctx, const char *name, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a, const uint8_t *d_a_skip,
+                                   const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip, const vdf_video_pair *pairs,
+                                   size_t n_pairs, uint32_t tol_int, uint32_t min_run, bool stretches, uint32_t max_stretches, uint32_t guard,
+                                   vdf_alignment *out, vdf_alignment_stretch *out_st, size_t capacity, size_t *n_out, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const void *o = stretches ? (const void *)out_st : (const void *)out;
+    const bool self = d_b_hashes == nullptr;
+    // everything that can be said without the first arrays - the multi-GPU refusal last; then they come down and are checked
+    if (int rc = align_pairs_checks(ctx, name, d_a_hashes, nullptr, n_a, d_b_hashes, nullptr, n_b, d_a_first, d_b_first, pairs, n_pairs, min_run, stretches,
+                                    max_stretches, guard, o, capacity, n_out, true))
+        return rc;
+    *n_out = 0;
+    if (n_pairs == 0) return VDF_OK;  // (a checked list with an entry: both sides have a video)
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<uint32_t> fa, fb;
+    if (int rc = align_first_down(ctx, d_a_first, n_a, d_b_first, n_b, self, s, fa, fb)) return rc;
+    if (int rc = align_checks(ctx, d_a_hashes, fa.data(), n_a, d_b_hashes, self ? nullptr : fb.data(), n_b, d_a_first, d_b_first, min_run, o, capacity, n_out, &n_pairs))
+        return rc;
+    const AlignSides in = self ? AlignSides{d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, true}
+                               : AlignSides{d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, d_b_hashes, d_b_first, fb.data(), n_b, d_b_skip, false};
+    return align_pairs_run(ctx, in, pairs, n_pairs, tol_int, min_run, stretches, max_stretches, guard, out, out_st, capacity, n_out, s);
+}
+
+static int align_pairs_ctx_impl(vdf_ctx *ctx, const char *name, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, const vdf_video_pair *pairs, size_t n_pairs,
+                                uint32_t tol_int, uint32_t min_run, bool stretches, uint32_t max_stretches, uint32_t guard, vdf_alignment *out,
+                                vdf_alignment_stretch *out_st, size_t capacity, size_t *n_out)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const void *o = stretches ? (const void *)out_st : (const void *)out;
+    if (int rc = align_pairs_checks(ctx, name, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, pairs, n_pairs, min_run, stretches, max_stretches,
+                                    guard, o, capacity, n_out, true))
+        return rc;
+    const bool self = b_hashes == nullptr;
+    *n_out = 0;
+    if (n_pairs == 0) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    AlignUploaded u;
+    if (int rc = align_upload(ctx, a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, self, s, &u)) return rc;
+    return align_pairs_run(ctx, align_sides_uploaded(ctx, u, n_a, n_b, self), pairs, n_pairs, tol_int, min_run, stretches, max_stretches, guard, out, out_st,
+                           capacity, n_out, s);
+}
+
+int vdf_align_windows_pairs_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                                 const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int,
+                                 uint32_t min_run, vdf_alignment *out, size_t capacity, size_t *n_out)
+{
+    return align_pairs_host_impl(a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, pairs, n_pairs, tol_int, min_run, false, 1,
+                                                       0, out, nullptr, capacity, n_out);
+}
+
+int vdf_align_windows_stretches_pairs_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                                           const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, const vdf_video_pair *pairs, size_t n_pairs,
+                                           uint32_t tol_int, uint32_t min_run, uint32_t max_stretches, uint32_t guard, vdf_alignment_stretch *out,
+                                           size_t capacity, size_t *n_out)
+{
+    return align_pairs_host_impl(a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, pairs, n_pairs, tol_int, min_run, true, max_stretches, guard,
+                                 nullptr, out, capacity, n_out);
+}
+
+int vdf_align_windows_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a, const uint8_t *d_a_skip,
+                                   const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip, const vdf_video_pair *pairs,
+                                   size_t n_pairs, uint32_t tol_int, uint32_t min_run, vdf_alignment *out, size_t capacity, size_t *n_out, void *stream)
+{
+    return align_pairs_device_impl(ctx, "vdf_align_windows_pairs_device", d_a_hashes, d_a_first, n_a, d_a_skip, d_b_hashes, d_b_first, n_b, d_b_skip, pairs,
+                                   n_pairs, tol_int, min_run, false, 1, 0, out, nullptr, capacity, n_out, stream);
+}
+
+int vdf_align_windows_stretches_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a, const uint8_t *d_a_skip,
+                                             const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip,
+                                             const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int, uint32_t min_run, uint32_t max_stretches,
+                                             uint32_t guard, vdf_alignment_stretch *out, size_t capacity, size_t *n_out, void *stream)
+{
+    return align_pairs_device_impl(ctx, "vdf_align_windows_stretches_pairs_device", d_a_hashes, d_a_first, n_a, d_a_skip, d_b_hashes, d_b_first, n_b, d_b_skip,
+                                   pairs, n_pairs, tol_int, min_run, true, max_stretches, guard, nullptr, out, capacity, n_out, stream);
+}
+
+int vdf_align_windows_pairs(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                            const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int,
+                            uint32_t min_run, vdf_alignment *out, size_t capacity, size_t *n_out)
+{
+    return align_pairs_ctx_impl(ctx, "vdf_align_windows_pairs", a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, pairs, n_pairs, tol_int, min_run,
+                                false, 1, 0, out, nullptr, capacity, n_out);
+}
+
+int vdf_align_windows_stretches_pairs(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                      const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, const vdf_video_pair *pairs,
+                                      size_t n_pairs, uint32_t tol_int, uint32_t min_run, uint32_t max_stretches, uint32_t guard, vdf_alignment_stretch *out,
+                                      size_t capacity, size_t *n_out)
+{
+    return align_pairs_ctx_impl(ctx, "vdf_align_windows_stretches_pairs", a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, pairs, n_pairs, tol_int,
+                                min_run, true, max_stretches, guard, nullptr, out, capacity, n_out);
 }
 
 size_t vdf_hash_window_count(uint32_t frames_per_clip, uint32_t window_stride) { return vdf::window_count(frames_per_clip, window_stride); }

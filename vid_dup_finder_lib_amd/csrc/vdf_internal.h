@@ -270,5 +270,33 @@ struct AlignLaunch {
 };
 size_t align_scratch_bytes(size_t n_pairs, size_t n_units);
 hipError_t launch_align_chunk(const AlignLaunch &L, hipStream_t stream);
+// The seed pass of a call (align_plan.h: AlignSeedPlan): every unit's seeds against its rows of B into `bitmap` (n_a x n_b
+// bits, cleared by the caller on the stream), then the count and scan of its set bits.  *total_out: where in scratch the number of pairs is
+// once the stream has run; launch_align_seed_scatter then writes the first `limit` of them, in (a, b) order.  All pointers are device pointers;
+// scratch holds align_seed_scratch_bytes(n_words).
+struct AlignSeedLaunch {
+    const uint32_t *a_hashes;
+    const uint8_t *a_skip;               // nullable, per window
+    const uint32_t *seed_window, *seed_video;
+    uint32_t n_seeds;
+    const uint32_t *b_hashes;
+    const uint8_t *b_skip;
+    const uint32_t *row_video;           // [n_rows]
+    uint32_t row_base, n_rows;
+    const unsigned long long *unit_offset;  // [n_chunks + 1]
+    const uint32_t *tile_first;          // [n_chunks]
+    uint32_t n_chunks;
+    uint64_t n_units;
+    uint32_t tol;
+    int self_mode;
+    uint32_t n_b;
+    uint32_t *bitmap;
+    uint32_t n_words;
+    void *scratch;
+    uint32_t **total_out;
+};
+size_t align_seed_scratch_bytes(size_t n_words);
+hipError_t launch_align_seed(const AlignSeedLaunch &L, hipStream_t stream);
+hipError_t launch_align_seed_scatter(const AlignSeedLaunch &L, vdf_video_pair *out, uint32_t limit, hipStream_t stream);
 
 }  // namespace vdf

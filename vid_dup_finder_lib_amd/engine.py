@@ -182,6 +182,97 @@ def align_windows_stretches_host(a_hashes, a_first, b_hashes=None, b_first=None,
     return out[:min(n.value, out.size)], int(n.value)
 
 
+# one pair of videos (include/vdf.h: vdf_video_pair, 8 bytes): what the seed calls return and the *_pairs calls take
+VIDEO_PAIR_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4")])
+
+
+def video_pairs(pairs) -> np.ndarray:
+    """A list of (a, b) - VIDEO_PAIR_DTYPE records, or anything numpy reads as [n, 2] integers - as the C ABI takes it."""
+    p = np.asarray(pairs)
+    if p.dtype == VIDEO_PAIR_DTYPE:
+        return np.ascontiguousarray(p).reshape(-1)
+    if p.size == 0:
+        return np.zeros(0, VIDEO_PAIR_DTYPE)
+    if p.dtype.kind not in "iu" or p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError("pairs: [n, 2] integers or VIDEO_PAIR_DTYPE records")
+    if int(p.min()) < 0 or int(p.max()) >= 2**32:
+        raise ValueError("pairs: video indices are 0 .. 2^32 - 1")
+    out = np.zeros(len(p), VIDEO_PAIR_DTYPE)
+    out["a"], out["b"] = p[:, 0], p[:, 1]
+    return out
+
+
+def pair_list_problem(pairs: np.ndarray, n_a: int, n_b: int, self_mode: bool):
+    """What the *_pairs calls refuse in a list, in the library's order and words (include/vdf.h) - the first entry that breaks a rule, and of
+    its rules the first; None: the list is fine.  The host forms have no context to keep the library's message in, and api.align checks the
+    caller's whole list before it cuts it into blocks: both name the problem through this."""
+    a, b = pairs["a"].astype(np.int64), pairs["b"].astype(np.int64)
+    code = np.zeros(len(pairs), np.uint8)
+    code[self_mode & (a >= b)] = 3
+    code[(a >= n_a) | (b >= (n_a if self_mode else n_b))] = 2
+    code[1:][(a[1:] < a[:-1]) | ((a[1:] == a[:-1]) & (b[1:] <= b[:-1]))] = 1
+    bad = np.flatnonzero(code)
+    if not bad.size:
+        return None
+    i = int(bad[0])
+    return {1: f"the pair list is not strictly increasing in (a, b) at entry {i}", 2: f"pair {i} of the list names a video that does not exist",
+            3: f"pair {i} of the list has a >= b in self mode"}[int(code[i])]
+
+
+def _pairs_host_error(name: str, rc: int, pairs: np.ndarray, args, self_mode: bool):
+    # the host forms have no context to keep a message in: the list's problem, if it has one, is named here
+    return VdfError(rc, f"{name}: {pair_list_problem(pairs, args[2], args[6], self_mode) or 'bad argument'}")
+
+
+def align_seed_pairs_host(a_hashes, a_first, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1, a_skip=None, b_skip=None,
+                          capacity: int = 1024):
+    """vdf_align_seed_pairs_host: the candidate pairs of the align calls - the pairs (a, b) with a matching cell (ka, kb), ka % min_run == 0 -
+    in plain C++ on the CPU.  Every pair align_windows_host has a record for is among them.
+    -> (pairs [min(found, capacity)] of VIDEO_PAIR_DTYPE in (a, b) order, found)."""
+    lib = _capi.load()
+    keep, args = _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+    out = np.zeros(max(int(capacity), 0), VIDEO_PAIR_DTYPE)
+    n = C.c_size_t(0)
+    rc = lib.vdf_align_seed_pairs_host(*args, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run), out.ctypes.data if out.size else None,
+                                       out.size, C.byref(n))
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_align_seed_pairs_host: bad argument")
+    return out[:min(n.value, out.size)], int(n.value)
+
+
+def align_windows_pairs_host(a_hashes, a_first, pairs, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1, a_skip=None, b_skip=None,
+                             capacity: int = 1024):
+    """vdf_align_windows_pairs_host: align_windows_host on the listed pairs only (strictly increasing in (a, b); a < b in self mode).
+    -> (records [min(found, capacity)] of ALIGN_DTYPE in (a, b) order, found)."""
+    lib = _capi.load()
+    keep, args = _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+    p = video_pairs(pairs)
+    out = np.zeros(max(int(capacity), 0), ALIGN_DTYPE)
+    n = C.c_size_t(0)
+    rc = lib.vdf_align_windows_pairs_host(*args, p.ctypes.data if p.size else None, p.size, _align_uint32("tol_int", tol_int),
+                                          _align_uint32("min_run", min_run), out.ctypes.data if out.size else None, out.size, C.byref(n))
+    if rc != _capi.VDF_OK:
+        raise _pairs_host_error("vdf_align_windows_pairs_host", rc, p, args, b_hashes is None)
+    return out[:min(n.value, out.size)], int(n.value)
+
+
+def align_windows_stretches_pairs_host(a_hashes, a_first, pairs, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1,
+                                       max_stretches: int = 4, guard: int = 0, a_skip=None, b_skip=None, capacity: int = 1024):
+    """vdf_align_windows_stretches_pairs_host: align_windows_stretches_host on the listed pairs only.
+    -> (records [min(found, capacity)] of ALIGN_STRETCH_DTYPE in (a, b, rank) order, found)."""
+    lib = _capi.load()
+    keep, args = _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+    p = video_pairs(pairs)
+    out = np.zeros(max(int(capacity), 0), ALIGN_STRETCH_DTYPE)
+    n = C.c_size_t(0)
+    rc = lib.vdf_align_windows_stretches_pairs_host(*args, p.ctypes.data if p.size else None, p.size, _align_uint32("tol_int", tol_int),
+                                                    _align_uint32("min_run", min_run), _align_uint32("max_stretches", max_stretches),
+                                                    _align_uint32("guard", guard), out.ctypes.data if out.size else None, out.size, C.byref(n))
+    if rc != _capi.VDF_OK:
+        raise _pairs_host_error("vdf_align_windows_stretches_pairs_host", rc, p, args, b_hashes is None)
+    return out[:min(n.value, out.size)], int(n.value)
+
+
 def window_variants_host(hashes, zero, first, variant: int, skip=None):
     """vdf_window_variants_host: the variant of a set of window hashes (hashes / zero [windows, 16] u64, first [videos + 1]) on the CPU ->
     hashes [windows, 16] (and the skip bytes carried along, if skip is given).  Rows outside [first[0], first[-1]) come back zero."""
@@ -484,6 +575,82 @@ class Engine:
                                                                 _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
                                                                 _align_uint32("max_stretches", max_stretches), _align_uint32("guard", guard),
                                                                 out.ctypes.data if out.size else None, out.size, C.byref(n), stream or None))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    # --------------------------------------------- seeded candidate pairs, the align calls on a list of pairs (include/vdf.h)
+    def align_seed_pairs(self, a_hashes, a_first, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1, a_skip=None, b_skip=None,
+                         capacity: int = 1024):
+        """The candidate pairs of the align calls (vdf_align_seed_pairs): the pairs (a, b) with a matching cell (ka, kb), ka % min_run == 0 -
+        every pair align_windows has a record for, and perhaps a few more.  -> (pairs [min(found, capacity)] of VIDEO_PAIR_DTYPE in (a, b)
+        order, found); found > capacity: call again with a larger capacity."""
+        keep, args = _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+        out = np.zeros(max(int(capacity), 0), VIDEO_PAIR_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_seed_pairs(self.ctx, *args, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                                  out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_seed_pairs_device(self, d_a_hashes: int, d_a_first: int, n_a: int, d_b_hashes: int = 0, d_b_first: int = 0, n_b: int = 0,
+                                tol_int: int = 350, min_run: int = 1, d_a_skip: int = 0, d_b_skip: int = 0, capacity: int = 1024, stream: int = 0):
+        """The same on device arrays (d_b_hashes 0: self mode); the pairs come back to the host, the call waits for its own work."""
+        out = np.zeros(max(int(capacity), 0), VIDEO_PAIR_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_seed_pairs_device(self.ctx, d_a_hashes or None, d_a_first or None, int(n_a), d_a_skip or None, d_b_hashes or None,
+                                                         d_b_first or None, int(n_b), d_b_skip or None, _align_uint32("tol_int", tol_int),
+                                                         _align_uint32("min_run", min_run), out.ctypes.data if out.size else None, out.size, C.byref(n),
+                                                         stream or None))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_pairs(self, a_hashes, a_first, pairs, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1, a_skip=None, b_skip=None,
+                            capacity: int = 1024):
+        """align_windows on the listed pairs only (vdf_align_windows_pairs): pairs = VIDEO_PAIR_DTYPE records or [n, 2] integers, strictly
+        increasing in (a, b), a < b in self mode.  The records are align_windows' for those pairs, field for field."""
+        keep, args = _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+        p = video_pairs(pairs)
+        out = np.zeros(max(int(capacity), 0), ALIGN_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_pairs(self.ctx, *args, p.ctypes.data if p.size else None, p.size, _align_uint32("tol_int", tol_int),
+                                                     _align_uint32("min_run", min_run), out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_pairs_device(self, d_a_hashes: int, d_a_first: int, n_a: int, pairs, d_b_hashes: int = 0, d_b_first: int = 0, n_b: int = 0,
+                                   tol_int: int = 350, min_run: int = 1, d_a_skip: int = 0, d_b_skip: int = 0, capacity: int = 1024, stream: int = 0):
+        """The same on device arrays (the pair list stays a host array)."""
+        p = video_pairs(pairs)
+        out = np.zeros(max(int(capacity), 0), ALIGN_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_pairs_device(self.ctx, d_a_hashes or None, d_a_first or None, int(n_a), d_a_skip or None, d_b_hashes or None,
+                                                            d_b_first or None, int(n_b), d_b_skip or None, p.ctypes.data if p.size else None, p.size,
+                                                            _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                                            out.ctypes.data if out.size else None, out.size, C.byref(n), stream or None))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_stretches_pairs(self, a_hashes, a_first, pairs, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1,
+                                      max_stretches: int = 4, guard: int = 0, a_skip=None, b_skip=None, capacity: int = 1024):
+        """align_windows_stretches on the listed pairs only (vdf_align_windows_stretches_pairs)."""
+        keep, args = _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+        p = video_pairs(pairs)
+        out = np.zeros(max(int(capacity), 0), ALIGN_STRETCH_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_stretches_pairs(self.ctx, *args, p.ctypes.data if p.size else None, p.size, _align_uint32("tol_int", tol_int),
+                                                               _align_uint32("min_run", min_run), _align_uint32("max_stretches", max_stretches),
+                                                               _align_uint32("guard", guard), out.ctypes.data if out.size else None, out.size,
+                                                               C.byref(n)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_stretches_pairs_device(self, d_a_hashes: int, d_a_first: int, n_a: int, pairs, d_b_hashes: int = 0, d_b_first: int = 0,
+                                             n_b: int = 0, tol_int: int = 350, min_run: int = 1, max_stretches: int = 4, guard: int = 0,
+                                             d_a_skip: int = 0, d_b_skip: int = 0, capacity: int = 1024, stream: int = 0):
+        """The same on device arrays (the pair list stays a host array)."""
+        p = video_pairs(pairs)
+        out = np.zeros(max(int(capacity), 0), ALIGN_STRETCH_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_stretches_pairs_device(self.ctx, d_a_hashes or None, d_a_first or None, int(n_a), d_a_skip or None,
+                                                                      d_b_hashes or None, d_b_first or None, int(n_b), d_b_skip or None,
+                                                                      p.ctypes.data if p.size else None, p.size, _align_uint32("tol_int", tol_int),
+                                                                      _align_uint32("min_run", min_run), _align_uint32("max_stretches", max_stretches),
+                                                                      _align_uint32("guard", guard), out.ctypes.data if out.size else None, out.size,
+                                                                      C.byref(n), stream or None))
         return out[:min(n.value, out.size)], int(n.value)
 
     # --------------------------------------------- the zero plane and the flipped hashes (include/vdf.h, DESIGN.md 4.8)

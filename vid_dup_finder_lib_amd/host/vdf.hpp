@@ -349,6 +349,126 @@ public:
         }
     }
 
+    // ---- a library is not walked pair by pair: seed the candidate pairs, align only those ----
+    // The two sides of an align call as the C ABI takes them, from hash_windows' lists.
+    struct AlignSides {
+        std::vector<uint64_t> wa, wb;
+        std::vector<uint32_t> fa, fb;
+        const uint8_t *ska = nullptr, *skb = nullptr;
+        size_t n_a = 0, n_b = 0;
+        bool self = true;
+        uint64_t cells = 0;
+        const uint64_t *b_words() const { return self ? nullptr : wb.data(); }
+        AlignSides(const std::vector<std::vector<VideoHash>> &windows_a, const std::vector<std::vector<VideoHash>> *windows_b, const std::vector<uint8_t> *skip_a,
+                   const std::vector<uint8_t> *skip_b)
+        {
+            auto csr = [](const std::vector<std::vector<VideoHash>> &w, std::vector<uint64_t> &words, std::vector<uint32_t> &first) {
+                first.assign(1, 0u);
+                for (const auto &video : w) {
+                    for (const VideoHash &h : video) words.insert(words.end(), h.words().begin(), h.words().end());
+                    first.push_back((uint32_t)(words.size() / VDF_HASH_WORDS));
+                }
+                if (words.empty()) words.push_back(0);  // a non-null pointer for an empty side
+            };
+            self = windows_b == nullptr;
+            csr(windows_a, wa, fa);
+            if (windows_b) csr(*windows_b, wb, fb);
+            if (skip_a && skip_a->size() != fa.back()) throw std::invalid_argument("one skip byte per window of A");
+            if (windows_b && skip_b && skip_b->size() != fb.back()) throw std::invalid_argument("one skip byte per window of B");
+            ska = skip_a && !skip_a->empty() ? skip_a->data() : nullptr;
+            skb = windows_b && skip_b && !skip_b->empty() ? skip_b->data() : nullptr;
+            n_a = windows_a.size();
+            n_b = windows_b ? windows_b->size() : 0;
+            cells = (uint64_t)fa.back() * (windows_b ? fb.back() : fa.back());
+        }
+    };
+
+    // Which pairs of videos can share a stretch at all (vdf_align_seed_pairs): align_windows' arguments; the pairs (a, b), in (a, b) order, with a
+    // window ka of a, ka a multiple of min_run, and a window of b within tol_int of each other, neither skipped.  Every pair align_windows has a
+    // record for is among them.  ctx_opt null and a tiny input: walked on the CPU (vdf_align_seed_pairs_host).
+    static std::vector<vdf_video_pair> align_seed_pairs(const std::vector<std::vector<VideoHash>> &windows_a, const std::vector<std::vector<VideoHash>> *windows_b,
+                                                        uint32_t tol_int, uint32_t min_run = 1, const std::vector<uint8_t> *skip_a = nullptr,
+                                                        const std::vector<uint8_t> *skip_b = nullptr, Context *ctx_opt = nullptr)
+    {
+        const AlignSides s(windows_a, windows_b, skip_a, skip_b);
+        std::vector<vdf_video_pair> out(1024);
+        for (;;) {
+            size_t found = 0;
+            int rc;
+            if (!ctx_opt && s.cells <= (1u << 16))
+                rc = vdf_align_seed_pairs_host(s.wa.data(), s.fa.data(), s.n_a, s.ska, s.b_words(), s.fb.data(), s.n_b, s.skb, tol_int, min_run, out.data(), out.size(), &found);
+            else {
+                Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+                rc = vdf_align_seed_pairs(ctx.get(), s.wa.data(), s.fa.data(), s.n_a, s.ska, s.b_words(), s.fb.data(), s.n_b, s.skb, tol_int, min_run, out.data(), out.size(),
+                                          &found);
+                if (rc != VDF_OK && rc != VDF_E_INVAL) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            }
+            if (rc != VDF_OK) throw std::invalid_argument("align_seed_pairs: min_run of 0, a video of more than 2^20 windows, more than 2^24 pairs, or a multi-GPU context");
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
+    // align_windows on the listed pairs only (vdf_align_windows_pairs): pairs strictly increasing in (a, b), a < b when windows_b is null.  The
+    // records are align_windows' for those pairs, field for field - with align_seed_pairs' list, all of them.
+    static std::vector<vdf_alignment> align_windows_pairs(const std::vector<std::vector<VideoHash>> &windows_a, const std::vector<std::vector<VideoHash>> *windows_b,
+                                                          const std::vector<vdf_video_pair> &pairs, uint32_t tol_int, uint32_t min_run = 1,
+                                                          const std::vector<uint8_t> *skip_a = nullptr, const std::vector<uint8_t> *skip_b = nullptr,
+                                                          Context *ctx_opt = nullptr)
+    {
+        const AlignSides s(windows_a, windows_b, skip_a, skip_b);
+        std::vector<vdf_alignment> out(1024);
+        for (;;) {
+            size_t found = 0;
+            int rc;
+            if (!ctx_opt && s.cells <= (1u << 16))
+                rc = vdf_align_windows_pairs_host(s.wa.data(), s.fa.data(), s.n_a, s.ska, s.b_words(), s.fb.data(), s.n_b, s.skb, pairs.empty() ? nullptr : pairs.data(),
+                                                  pairs.size(), tol_int, min_run, out.data(), out.size(), &found);
+            else {
+                Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+                rc = vdf_align_windows_pairs(ctx.get(), s.wa.data(), s.fa.data(), s.n_a, s.ska, s.b_words(), s.fb.data(), s.n_b, s.skb, pairs.empty() ? nullptr : pairs.data(),
+                                             pairs.size(), tol_int, min_run, out.data(), out.size(), &found);
+                if (rc != VDF_OK && rc != VDF_E_INVAL) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            }
+            if (rc != VDF_OK)
+                throw std::invalid_argument("align_windows_pairs: min_run of 0, a video of more than 2^20 windows, more than 2^24 listed pairs, a list that is not strictly "
+                                            "increasing, names a video that does not exist or has a >= b in self mode, or a multi-GPU context");
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
+    // align_windows_stretches on the listed pairs only (vdf_align_windows_stretches_pairs).
+    static std::vector<vdf_alignment_stretch> align_windows_stretches_pairs(const std::vector<std::vector<VideoHash>> &windows_a,
+                                                                            const std::vector<std::vector<VideoHash>> *windows_b,
+                                                                            const std::vector<vdf_video_pair> &pairs, uint32_t tol_int, uint32_t min_run = 1,
+                                                                            uint32_t max_stretches = 4, uint32_t guard = 15, const std::vector<uint8_t> *skip_a = nullptr,
+                                                                            const std::vector<uint8_t> *skip_b = nullptr, Context *ctx_opt = nullptr)
+    {
+        const AlignSides s(windows_a, windows_b, skip_a, skip_b);
+        std::vector<vdf_alignment_stretch> out(1024);
+        for (;;) {
+            size_t found = 0;
+            int rc;
+            if (!ctx_opt && s.cells <= (1u << 16))
+                rc = vdf_align_windows_stretches_pairs_host(s.wa.data(), s.fa.data(), s.n_a, s.ska, s.b_words(), s.fb.data(), s.n_b, s.skb,
+                                                            pairs.empty() ? nullptr : pairs.data(), pairs.size(), tol_int, min_run, max_stretches, guard, out.data(),
+                                                            out.size(), &found);
+            else {
+                Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+                rc = vdf_align_windows_stretches_pairs(ctx.get(), s.wa.data(), s.fa.data(), s.n_a, s.ska, s.b_words(), s.fb.data(), s.n_b, s.skb,
+                                                       pairs.empty() ? nullptr : pairs.data(), pairs.size(), tol_int, min_run, max_stretches, guard, out.data(), out.size(),
+                                                       &found);
+                if (rc != VDF_OK && rc != VDF_E_INVAL) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            }
+            if (rc != VDF_OK)
+                throw std::invalid_argument("align_windows_stretches_pairs: min_run of 0, a video of more than 2^20 windows, more than 2^24 listed pairs, max_stretches "
+                                            "outside 1 ... 8, a guard above 2^20, a bad pair list, or a multi-GPU context");
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
     // hash_windows with the zero plane of every window (vdf_hash_windows_u8_planes): the same words, and every VideoHash
     // carries zero() - what align_windows_variants needs of the flipped side.
     static std::vector<std::vector<VideoHash>> hash_windows_planes(const uint8_t *frames, size_t n_videos, uint32_t frames_per_video, uint32_t w, uint32_t h,
