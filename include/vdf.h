@@ -363,7 +363,7 @@ int vdf_align_windows_stretches_device(vdf_ctx *ctx, const uint64_t *d_a_hashes,
  * A skip byte is read with the aligned 32-bit word that holds it (the seed kernel reads a seed's byte by a scalar load, as the band kernels of
  * vdf_align_windows read a row's): for a skip array that does not begin or end on a 4-byte boundary up to 3 bytes beside it are read - inside
  * the same word, so inside the same page and, with any device allocator, the same allocation - and their values are ignored.
- * Not offered: the variants (vdf_align_windows_variants*) on a pair list. */
+ * The variants on a list and seeded: vdf_align_windows_variants_pairs* and vdf_align_seed_pairs_variants* below. */
 typedef struct vdf_video_pair { /* 8 bytes */
     uint32_t a;                /* video index in A */
     uint32_t b;                /* video index in B (self mode: in A, a < b) */
@@ -462,6 +462,79 @@ int vdf_align_windows_variants_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, 
                                       const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip, uint32_t tol_int,
                                       uint32_t min_run, uint32_t variant_mask, vdf_alignment_variant *out, size_t capacity,
                                       size_t *n_out, void *stream);
+
+/* ---- the flipped alignment, seeded: the candidates under every requested variant from one pass over the seeds ----
+ * For variant v in 1 ... 7: the variant-v set of B is vdf_window_variants_*'s output, and pair (a, b) is a CANDIDATE UNDER v iff it is a
+ * candidate of vdf_align_seed_pairs* on (A, variant-v set of B): seeds are the windows ka % min_run == 0 counted inside video a; neither row
+ * skipped; distance over all 16 words <= min(tol_int, 1024); a < b in self mode.  Self mode is B = A with a_zero as its plane, as
+ * vdf_align_windows_variants defines it.  A candidate needs only some seed and some row of b, and bit 2 of v only reorders b's rows and
+ * carries their skip bytes along: the candidate set under v does not depend on the reversal, only on M_v and Z.  It holds every pair with a
+ * record of vdf_align_windows_variants* under v.
+ * vdf_align_seed_pairs_variants*: the arguments of vdf_align_windows_variants* up to variant_mask; out is a HOST buffer of `capacity`
+ * triples ordered by (variant, a, b); *n_out = the total over the requested variants, the first `capacity` entries are valid if it exceeds
+ * capacity - VDF_OK.  Errors: those of vdf_align_seed_pairs* in their order; then variant_mask with bit 0 or a bit above 7; then a missing
+ * zero plane; then a multi-GPU context - all VDF_E_INVAL.  The context forms make one pass over the seeds for all requested variants (the
+ * seven masks split the 1000 bits into eight classes of 125 on which every M_v is constant, so eight partial sums give every distance).
+ * vdf_align_windows_variants_pairs*: vdf_align_windows_variants* restricted to a HOST list (also in the device form) of n_triples
+ * (variant, a, b) triples; the list names the variants, there is no mask.  Per variant present in the list, ascending, the set is derived and
+ * the align core runs on that variant's sublist.  The records are vdf_alignment_variant, equal field for field to the all-pairs variants
+ * call's for the listed triples, in (variant, a, b) order, under the same capacity protocol.  Errors, in this order, all VDF_E_INVAL: a null
+ * list with n_triples > 0; those of vdf_align_windows up to the first arrays; n_a or n_b above 2^32 - 1; more than 2^24 listed triples; a
+ * list that is not strictly increasing in (variant, a, b); a variant outside 1 ... 7; a triple that names a video that does not exist; a
+ * triple with a >= b in self mode (the list failures name the entry's index); a missing zero plane; a multi-GPU context.
+ * Each in the three forms: _host (plain C++, no context: vdf_window_variants_host, then the plain host forms - the reference), host arrays
+ * through a context, _device (DEVICE arrays and a stream; the call waits for its own work).  A _device form on a multi-GPU context has no
+ * device to read the first arrays back from: it makes every check that needs no first array, in the order above, and then refuses the
+ * context - a decreasing first array or a video above 2^20 windows is not reported there (as vdf_align_windows_variants_device).
+ * Not offered: more than one stretch per pair under a variant; multi-GPU contexts. */
+typedef struct vdf_video_pair_variant { /* 12 bytes */
+    uint32_t a;                /* video index in A */
+    uint32_t b;                /* video index in B (self mode: in A, a < b) */
+    uint32_t variant;          /* 1 ... 7 */
+} vdf_video_pair_variant;
+int vdf_align_seed_pairs_variants_host(const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first, size_t n_a,
+                                       const uint8_t *a_skip, const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first,
+                                       size_t n_b, const uint8_t *b_skip, uint32_t tol_int, uint32_t min_run, uint32_t variant_mask,
+                                       vdf_video_pair_variant *out, size_t capacity, size_t *n_out);
+int vdf_align_seed_pairs_variants(vdf_ctx *ctx, const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first, size_t n_a,
+                                  const uint8_t *a_skip, const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first,
+                                  size_t n_b, const uint8_t *b_skip, uint32_t tol_int, uint32_t min_run, uint32_t variant_mask,
+                                  vdf_video_pair_variant *out, size_t capacity, size_t *n_out);
+int vdf_align_seed_pairs_variants_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint64_t *d_a_zero, const uint32_t *d_a_first,
+                                         size_t n_a, const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint64_t *d_b_zero,
+                                         const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip, uint32_t tol_int,
+                                         uint32_t min_run, uint32_t variant_mask, vdf_video_pair_variant *out, size_t capacity,
+                                         size_t *n_out, void *stream);
+int vdf_align_windows_variants_pairs_host(const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first, size_t n_a,
+                                          const uint8_t *a_skip, const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first,
+                                          size_t n_b, const uint8_t *b_skip, const vdf_video_pair_variant *triples, size_t n_triples,
+                                          uint32_t tol_int, uint32_t min_run, vdf_alignment_variant *out, size_t capacity, size_t *n_out);
+int vdf_align_windows_variants_pairs(vdf_ctx *ctx, const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first, size_t n_a,
+                                     const uint8_t *a_skip, const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first,
+                                     size_t n_b, const uint8_t *b_skip, const vdf_video_pair_variant *triples, size_t n_triples,
+                                     uint32_t tol_int, uint32_t min_run, vdf_alignment_variant *out, size_t capacity, size_t *n_out);
+int vdf_align_windows_variants_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint64_t *d_a_zero, const uint32_t *d_a_first,
+                                            size_t n_a, const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint64_t *d_b_zero,
+                                            const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip,
+                                            const vdf_video_pair_variant *triples, size_t n_triples, uint32_t tol_int, uint32_t min_run,
+                                            vdf_alignment_variant *out, size_t capacity, size_t *n_out, void *stream);
+
+/* The class-major rows the seed pass against the variants reads (csrc/window_class_layout.h states the permutation): made
+ * callable so that the layout kernel can be held against its host twin word for word, and for callers who want to see what a window looks like
+ * to that pass.  hashes / first / skip as vdf_window_variants_*.
+ *   zero == NULL: the SEEDS of the set - window first[v] + k min_run of every video v, in order - 36 dwords each: [0, 33) the hash's bits
+ *     class-major, 33 the popcount of all 1024 bits, 34 the skip byte as 0 / 1, 35 the video index.
+ *   zero != NULL: the ROWS first[0] ... first[n_videos] - 1, 72 dwords each: [0, 33) H & ~Z class-major, 33 / 34 the counts of live (non-Z)
+ *     bits of classes 1 ... 4 / 5 ... 7, one byte each from the low byte up, 35 the skip byte as 0 / 1, [36, 69) ~Z class-major, 69 ... 71 zero.
+ * out holds capacity_rows rows of that size; *n_rows = the number the layout has.  Errors, in this order, all VDF_E_INVAL: a null required pointer;
+ * min_run == 0; more than 2^32 - 1 videos; (device form) a multi-GPU context; a first array that decreases; fewer rows of room than the layout has
+ * (*n_rows is set).  _host: plain C++, no context.  _device: DEVICE pointers, out included (16-byte aligned); the first array is read back; the
+ * call waits for its own work. */
+int vdf_window_class_layout_host(const uint64_t *hashes, const uint64_t *zero, const uint32_t *first, size_t n_videos, const uint8_t *skip,
+                                 uint32_t min_run, uint32_t *out, size_t capacity_rows, size_t *n_rows);
+int vdf_window_class_layout_device(vdf_ctx *ctx, const uint64_t *d_hashes, const uint64_t *d_zero, const uint32_t *d_first, size_t n_videos,
+                                   const uint8_t *d_skip, uint32_t min_run, uint32_t *d_out, size_t capacity_rows, size_t *n_rows,
+                                   void *stream);
 
 /* ---- clips of DIFFERENT frame sizes in one call ----------------------------------------------------
  * A library holds dozens of resolutions and its files arrive in any order.  All clips of a call live in ONE

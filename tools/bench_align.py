@@ -45,7 +45,15 @@ below the parent's median divided by the parent's own max / min over its 12 call
 Leg (b): the planted corpus of --stretches (0.99 % of the pairs share stretches), min_run 2: the seeded path beside this build's all-pairs
 call; the records must be equal.  Leg (c): 8000 videos x 49 windows, self mode, host lists through api.align (three blocks of videos):
 seed=True beside seed=False, equal lists.  Leg (d): leg (a) at min_run 1, where every window is a seed and the filter saves no distance
-work.  Only leg (a) is gated."""
+work.  Only leg (a) is gated.
+
+    python tools/bench_align.py --seeded-variants --parent-lib tools/_libvdf_parent.so [--out profiles/align_seeded_variants.txt]
+
+The candidates of the flipped alignment from ONE pass over the seeds (vdf_align_seed_pairs_variants_device) beside what the
+parent commit's library offers for the same question - per requested variant vdf_window_variants_device, then vdf_align_seed_pairs_device on the
+derived set - for 1, 3 and 7 variants, min_run 2 and 4, on the 1000 x 49 corpus with zero planes, without and with related pairs; the candidate
+lists must be equal.  GATE: at 7 variants the one-pass median is below the composition's median divided by the composition's own max / min over
+its 12 calls.  End to end: the parent's vdf_align_windows_variants_device beside seed + vdf_align_windows_variants_pairs_device, records equal."""
 import argparse
 import ctypes as C
 import json
@@ -552,6 +560,195 @@ def seeded_main(args):
     return 0 if ok else 1
 
 
+SV_MASKS = {"1 variant": 0b00000010, "3 variants": 0b00110010, "7 variants": 0b11111110}
+PAIR_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4")])
+TRIPLE_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("variant", "<u4")])
+
+
+def seeded_variants_corpus(related):
+    """the 1000 x 49 self shape with zero planes of 5 % of the bits; related: every fifth video (index % 5 == 4) is a SOURCE and is left as it
+    is; every other video a holds, at windows 9 k ... 9 k + 8 (k < 5), what the variant-v set of the k-th source behind it shows at derived
+    rows 5 ... 13, v = (1, 4, 5)[source % 3], with 0 ... 40 bits changed.  All holders of a source use one variant and no source is a holder,
+    so nothing chains: 3960 of the 499 500 pairs (0.79 %) share a stretch, each under one of the variants 1, 4, 5."""
+    n_a, n_win, _ = SHAPES[VARIANTS_SHAPE]
+    rng = np.random.default_rng([15, n_a, n_win])
+    a, fa = random_hashes(rng, n_a * n_win), np.arange(n_a + 1, dtype=np.uint32) * n_win
+    zero = np.zeros_like(a)
+    for pos in range(1000):
+        zero[rng.random(len(a)) < 0.05, pos >> 6] |= np.uint64(1) << np.uint64(pos & 63)
+    a &= ~zero
+    planted = 0
+    if related:
+        masks = {}
+        for v in (1, 4, 5):
+            m = np.zeros(16, np.uint64)
+            for i in range(1000):
+                kt, kx, ky = i // 100, (i // 10) % 10, i % 10
+                if ((v & 1) * kx + (v >> 1 & 1) * ky + (v >> 2 & 1) * kt) & 1:
+                    m[i >> 6] |= np.uint64(1) << np.uint64(i & 63)
+            masks[v] = m
+        for va in range(n_a):
+            if va % 5 == 4:
+                continue
+            for k in range(5):
+                vb = va // 5 * 5 + 4 + 5 * k
+                if vb >= n_a:
+                    continue
+                v = (1, 4, 5)[vb % 3]
+                src = np.arange(5, 14)
+                if v & 4:
+                    src = n_win - 1 - src
+                rows = vb * n_win + src
+                a[va * n_win + 9 * k:va * n_win + 9 * k + 9] = flip_bits(rng, (a[rows] ^ masks[v]) & ~zero[rows])
+                planted += 1
+    seeded_variants_corpus.planted = planted
+    return a, zero, fa
+
+
+def seeded_variants_child(args):
+    """one leg of --seeded-variants: parent-comp (per variant vdf_window_variants_device + vdf_align_seed_pairs_device of args.lib on the derived
+    set) | new (vdf_align_seed_pairs_variants_device) | parent-e2e (vdf_align_windows_variants_device of args.lib) | new-e2e (seed + list call)"""
+    import torch
+
+    lib = C.CDLL(args.lib)
+    lib.vdf_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
+    lib.vdf_last_error.restype = C.c_char_p
+    lib.vdf_last_error.argtypes = [C.c_void_p]
+    ctx = C.c_void_p()
+    assert lib.vdf_ctx_create(0, C.byref(ctx)) == 0, lib.vdf_last_error(None)
+    P, S = C.c_void_p, C.c_size_t
+    sides, vsides = [P, P, P, S, P, P, P, S, P], [P, P, P, P, S, P, P, P, P, S, P]
+    lib.vdf_window_variants_device.argtypes = [P, P, P, P, S, P, C.c_uint32, P, P, P]
+    lib.vdf_align_seed_pairs_device.argtypes = sides + [C.c_uint32, C.c_uint32, P, S, C.POINTER(S), P]
+    lib.vdf_align_windows_variants_device.argtypes = vsides + [C.c_uint32, C.c_uint32, C.c_uint32, P, S, C.POINTER(S), P]
+    if args.leg.startswith("new"):
+        lib.vdf_align_seed_pairs_variants_device.argtypes = vsides + [C.c_uint32, C.c_uint32, C.c_uint32, P, S, C.POINTER(S), P]
+        lib.vdf_align_windows_variants_pairs_device.argtypes = vsides + [P, S, C.c_uint32, C.c_uint32, P, S, C.POINTER(S), P]
+    n_a, n_win, _ = SHAPES[VARIANTS_SHAPE]
+    res = {}
+    for corpus_name in ("unrelated", "related"):
+        a, zero, fa = seeded_variants_corpus(corpus_name == "related")
+        d_a, d_z, d_fa = (torch.from_numpy(x.view(t)).cuda() for x, t in ((a, np.int64), (zero, np.int64), (fa, np.int32)))
+        d_var = torch.zeros_like(d_a)
+        torch.cuda.synchronize()
+        vdev = (ctx, d_a.data_ptr(), d_z.data_ptr(), d_fa.data_ptr(), n_a, None, None, None, None, 0, None)
+        cap = 1 << 22
+        pair_buf, triple_buf, rec_buf = np.zeros(cap, PAIR_DTYPE), np.zeros(cap, TRIPLE_DTYPE), np.zeros(cap, ALIGN_VARIANT_DTYPE)
+        n_out, n_cand = S(0), S(0)
+        state = {}
+
+        def composition(min_run, mask):  # what the parent offers: per variant the derived set, then the plain seed call on (A, derived A) - the whole square
+            found = []
+            for v in range(1, 8):
+                if not mask >> v & 1:
+                    continue
+                rc = lib.vdf_window_variants_device(ctx, d_a.data_ptr(), d_z.data_ptr(), d_fa.data_ptr(), n_a, None, v, d_var.data_ptr(), None, None)
+                if rc:
+                    return rc
+                rc = lib.vdf_align_seed_pairs_device(ctx, d_a.data_ptr(), d_fa.data_ptr(), n_a, None, d_var.data_ptr(), d_fa.data_ptr(), n_a, None, TOL, min_run,
+                                                     pair_buf.ctypes.data, cap, C.byref(n_cand), None)
+                if rc:
+                    return rc
+                p = pair_buf[:n_cand.value]
+                p = p[p["a"] < p["b"]]  # the self-mode rule
+                t = np.zeros(len(p), TRIPLE_DTYPE)
+                t["a"], t["b"], t["variant"] = p["a"], p["b"], v
+                found.append(t)
+            state["triples"] = np.concatenate(found) if found else np.zeros(0, TRIPLE_DTYPE)
+            return 0
+
+        def one_pass(min_run, mask):
+            rc = lib.vdf_align_seed_pairs_variants_device(*vdev, TOL, min_run, mask, triple_buf.ctypes.data, cap, C.byref(n_cand), None)
+            state["triples"] = triple_buf[:n_cand.value]
+            return rc
+
+        def e2e_parent(min_run, mask):
+            rc = lib.vdf_align_windows_variants_device(*vdev, TOL, min_run, mask, rec_buf.ctypes.data, cap, C.byref(n_out), None)
+            state["records"] = rec_buf[:n_out.value]
+            return rc
+
+        def e2e_new(min_run, mask):
+            rc = one_pass(min_run, mask)
+            n_out.value = 0
+            if rc == 0 and n_cand.value:
+                rc = lib.vdf_align_windows_variants_pairs_device(*vdev, triple_buf.ctypes.data, n_cand.value, TOL, min_run, rec_buf.ctypes.data, cap, C.byref(n_out), None)
+            state["records"] = rec_buf[:n_out.value]
+            return rc
+        if args.leg in ("parent-comp", "new"):
+            run = composition if args.leg == "parent-comp" else one_pass
+            runs = [(f"{name}/m{m}", m, mask, run) for m in ((2, 4) if corpus_name == "unrelated" else (2,)) for name, mask in SV_MASKS.items()]
+        else:
+            if corpus_name == "unrelated":
+                continue
+            runs = [("e2e/m2", 2, SV_MASKS["7 variants"], e2e_parent if args.leg == "parent-e2e" else e2e_new)]
+        for key, min_run, mask, run in runs:
+            times = []
+            for r in range(REPEATS + 1):
+                t0 = time.perf_counter()
+                rc = run(min_run, mask)
+                if r:
+                    times.append(time.perf_counter() - t0)
+                assert rc == 0, (rc, lib.vdf_last_error(ctx))
+            out = state["records" if key.startswith("e2e") else "triples"]
+            res[f"{corpus_name}/{key}"] = {"times": times, "n": int(len(out)), "digest": digest(out)}
+    print("RESULT " + json.dumps(res))
+
+
+def seeded_variants_main(args):
+    parent_lib = os.path.abspath(args.parent_lib) if args.parent_lib else args.lib
+    legs = [("parent-comp", parent_lib), ("new", args.lib), ("parent-e2e", parent_lib), ("new-e2e", args.lib)]
+    got = {}
+    for _ in range(ROUNDS):
+        for leg, lib in legs:
+            for key, v in run_child(lib, leg, mode="--seeded-variants").items():
+                e = got.setdefault(f"{leg}:{key}", {"times": []})
+                e["times"] += v["times"]
+                e.update({k: v[k] for k in v if k != "times"})
+    n_a, n_win, _ = SHAPES[VARIANTS_SHAPE]
+    pairs = n_a * (n_a - 1) // 2
+    seeded_variants_corpus(True)
+    n_planted = seeded_variants_corpus.planted
+    med = lambda e: statistics.median(e["times"])
+    ms = lambda ts: f"min {min(ts) * 1e3:9.3f}  median {statistics.median(ts) * 1e3:9.3f}  max {max(ts) * 1e3:9.3f} ms ({len(ts)} calls)"
+    whose = "the PARENT commit's library" if args.parent_lib else "THIS build's library (no --parent-lib: not the parent commit)"
+    lines = [f"tools/bench_align.py --seeded-variants: {ROUNDS} rounds x {REPEATS} timed calls per leg (one warm-up per round), fresh process per leg and round, legs in turn",
+             f"{VARIANTS_SHAPE}: {pairs} pairs of videos, {n_a * n_win} windows, zero planes with 5 % of the bits, device-resident; tolerance {TOL}; host clock around calls that wait",
+             f"composition = per requested variant vdf_window_variants_device, then vdf_align_seed_pairs_device on (A, the derived A) of {whose}: the parent has no self",
+             "mode against a derived set, so it compares the whole square of videos and the pairs a < b are kept on the host; one pass = vdf_align_seed_pairs_variants_device"]
+    ok = True
+    for corpus_name, runs in (("unrelated", (2, 4)), ("related", (2,))):
+        lines.append(f"corpus '{corpus_name}':" + ("  no pair shares anything" if corpus_name == "unrelated" else f"  {n_planted} pairs ({100.0 * n_planted / pairs:.2f} %) share a stretch planted under variant 1, 4 or 5"))
+        for m in runs:
+            for name in SV_MASKS:
+                pc, nw = got[f"parent-comp:{corpus_name}/{name}/m{m}"], got[f"new:{corpus_name}/{name}/m{m}"]
+                same = pc["digest"] == nw["digest"] and pc["n"] == nw["n"]
+                ok &= same
+                spread = max(pc["times"]) / min(pc["times"])
+                lines += [f"  min_run {m}  {name:10s}  composition  {ms(pc['times'])}  {pc['n']} candidates",
+                          f"  min_run {m}  {name:10s}  one pass     {ms(nw['times'])}  {nw['n']} candidates: lists {'equal' if same else 'DIFFER'}; composition / one pass, medians = "
+                          f"{med(pc) / med(nw):.2f}x  (composition's own max / min {spread:.3f})"]
+                if name == "7 variants":
+                    bound = med(pc) / spread
+                    held = med(nw) < bound
+                    ok &= held
+                    lines.append(f"  GATE min_run {m}, 7 variants, '{corpus_name}': one-pass median {med(nw) * 1e3:.3f} ms < composition median {med(pc) * 1e3:.3f} ms / its max / min "
+                                 f"{spread:.3f} = {bound * 1e3:.3f} ms: {'HOLDS' if held else 'MISSED'}")
+    pe, ne = got["parent-e2e:related/e2e/m2"], got["new-e2e:related/e2e/m2"]
+    same = pe["digest"] == ne["digest"] and pe["n"] == ne["n"]
+    ok &= same
+    lines += ["end to end, corpus 'related', 7 variants, min_run 2:",
+              f"  vdf_align_windows_variants_device of {whose}  {ms(pe['times'])}  {pe['n']} records",
+              f"  seed + vdf_align_windows_variants_pairs_device       {ms(ne['times'])}  {ne['n']} records: records {'equal' if same else 'DIFFER'}; all-pairs / seeded, medians = "
+              f"{med(pe) / med(ne):.2f}x",
+              "the 1- and 3-variant ratios and the end-to-end leg are reported, not gated; kernel times apart from call times: not measured"]
+    text = "\n".join(lines) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text)
+    return 0 if ok else 1
+
+
 def run_child(lib, leg, variants=False, mode=None):
     out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--lib", lib, "--leg", leg] + (["--variants"] if variants else []) + ([mode] if mode else []),
                          capture_output=True, text=True, timeout=900)
@@ -567,16 +764,21 @@ def main():
     ap.add_argument("--variants", action="store_true")
     ap.add_argument("--stretches", action="store_true")
     ap.add_argument("--seeded", action="store_true")
+    ap.add_argument("--seeded-variants", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--lib", default=os.path.join(ROOT, "vid_dup_finder_lib_amd", "libvdf_hip.so"))
     ap.add_argument("--leg", default="align")
     args = ap.parse_args()
+    if args.child and args.seeded_variants:
+        return seeded_variants_child(args)
     if args.child:
         return seeded_child(args) if args.seeded else stretches_child(args) if args.stretches else variants_child(args) if args.variants else child(args)
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "align_seeded.txt" if args.seeded else "align_stretches.txt" if args.stretches else "align_variants.txt" if args.variants
+        args.out = os.path.join(ROOT, "profiles", "align_seeded_variants.txt" if args.seeded_variants else "align_seeded.txt" if args.seeded else "align_stretches.txt" if args.stretches else "align_variants.txt" if args.variants
                                 else "align_windows.txt")
+    if args.seeded_variants:
+        return seeded_variants_main(args)
     if args.seeded:
         return seeded_main(args)
     if args.stretches:

@@ -32,7 +32,7 @@ GROUPS = [
     ("EVERY shared stretch of a pair, ranked: an ad break cut out, a source used twice - the best run, then the best outside its rectangle, ...",
      r"vdf_align_windows_stretches"),
     ("mirrored / flipped / reversed STRETCHES: the variant of a set of window hashes from their zero planes, and alignment against it",
-     r"vdf_window_variants|vdf_align_windows_variants"),
+     r"vdf_window_variants|vdf_window_class_layout|vdf_align_windows_variants"),
     ("mirrored / flipped / reversed duplicates, which the crate cannot see (lib.rs:102-111): the flipped clip's hash from the hash and the zero plane of the planes calls",
      r"vdf_hash_variant|vdf_search_variants"),
     ("search() / search_with_references() (video_dup_finder.rs:7-46 over search_algorithm.rs:63-185)", r"vdf_search_self$|vdf_search_refs$"),

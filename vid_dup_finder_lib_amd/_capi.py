@@ -110,6 +110,12 @@ class VdfVideoPair(C.Structure):
     _fields_ = [("a", C.c_uint32), ("b", C.c_uint32)]
 
 
+class VdfVideoPairVariant(C.Structure):
+    """One triple of vdf_align_seed_pairs_variants* and of the lists of vdf_align_windows_variants_pairs*: 12 bytes (the numpy twin is
+    engine.VIDEO_PAIR_VARIANT_DTYPE)."""
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("variant", C.c_uint32)]
+
+
 AGREE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_uint64))
 OR_BITMAP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -127,6 +133,7 @@ _u32p = C.POINTER(C.c_uint32)
 _u8p = C.POINTER(C.c_uint8)
 _ctx = C.c_void_p
 _ALIGN_SIDES = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+_ALIGN_VARIANT_SIDES = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
 
 # name -> (restype, argtypes).  Keep in step with include/vdf.h; tests/test_capi_symbols.py checks both ways.
 SIGNATURES = {
@@ -176,6 +183,22 @@ SIGNATURES = {
     "vdf_align_windows_variants_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                                     C.POINTER(C.c_size_t), C.c_void_p]),
+    # (a_hashes, a_zero, a_first, n_a, a_skip, b_hashes, b_zero, b_first, n_b, b_skip), then (tol_int, min_run, variant_mask) or (triples, n_triples, tol_int, min_run)
+    "vdf_align_seed_pairs_variants_host": (C.c_int, _ALIGN_VARIANT_SIDES + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vdf_align_seed_pairs_variants": (C.c_int, [_ctx] + _ALIGN_VARIANT_SIDES + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                                                 C.POINTER(C.c_size_t)]),
+    "vdf_align_seed_pairs_variants_device": (C.c_int, [_ctx] + _ALIGN_VARIANT_SIDES + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                                                        C.POINTER(C.c_size_t), C.c_void_p]),
+    "vdf_align_windows_variants_pairs_host": (C.c_int, _ALIGN_VARIANT_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                                                C.POINTER(C.c_size_t)]),
+    "vdf_align_windows_variants_pairs": (C.c_int, [_ctx] + _ALIGN_VARIANT_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                                                    C.POINTER(C.c_size_t)]),
+    "vdf_align_windows_variants_pairs_device": (C.c_int, [_ctx] + _ALIGN_VARIANT_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                                                           C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "vdf_window_class_layout_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                               C.POINTER(C.c_size_t)]),
+    "vdf_window_class_layout_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                 C.POINTER(C.c_size_t), C.c_void_p]),
     "vdf_align_windows_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                          C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vdf_align_windows": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,

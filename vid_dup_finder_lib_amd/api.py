@@ -21,7 +21,7 @@ from . import _capi
 from ._capi import DEFAULT_SEARCH_TOLERANCE, HASH_BITS, HASH_WORDS, TOLERANCE_SCALING_FACTOR, VdfError
 from .engine import (ALIGN_DTYPE, ALIGN_STRETCH_DTYPE, ALIGN_VARIANT_DTYPE, Engine, align_windows_host, align_windows_stretches_host, align_windows_variants_host, hamming_distance_words, hash_variant,
                      tolerance_int, video_pairs, align_seed_pairs_host, align_windows_pairs_host, align_windows_stretches_pairs_host,
-                     pair_list_problem)
+                     pair_list_problem, VIDEO_PAIR_VARIANT_DTYPE, align_seed_pairs_variants_host, align_windows_variants_pairs_host)
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
            "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "hash_frame_windows", "locate", "rust_path_key", "sort_order",
@@ -859,21 +859,77 @@ def _align_flipped_call(engine, a, b, tol_int, min_run, mask):
     return rec
 
 
-def align_flipped(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoHash]]] = None, tolerance: float = DEFAULT_SEARCH_TOLERANCE,
-                  min_run: int = 1, stride: int = 1, flips: Sequence = (Flip.X,), static_a=None, static_b=None,
-                  engine: Optional[Engine] = None) -> dict:
-    """`align` against the mirrored / flipped / reversed videos of windows_b - the re-upload that is mirrored AND has its intro trimmed, which
-    neither search_flipped (frames 0 ... 15 of a file) nor align (unflipped stretches) sees: {flip: [FlippedAlignment]} for every flip of `flips`,
-    each list ordered by (a, b) with at most one entry per pair, by align's rules on the window hashes of the flipped b (derived from b's hashes
-    and zero planes; include/vdf.h: vdf_align_windows_variants).  windows_b None: the videos of windows_a against each other's flips, every
-    pair once (a < b), never a video against its own mirror.  The hashes of the flipped side (windows_b, or windows_a in self mode) need their
-    zero planes (hash_frame_windows with zero_plane=True), else VidProc.  With Flip.T the matched stretch of b plays backwards
-    (FlippedAlignment); it lies on b's window grid, i.e. reversed b is taken from its last window's last frame.  Near the tolerance a stretch
-    can show with b flipped and not with the sides swapped: b's zero plane clears bits of the flipped hash that a may have set."""
+def _seed_flipped_call(engine, a, b, tol_int, min_run, mask):
+    """_seed_call for the variants: the candidate triples of one call, VIDEO_PAIR_VARIANT_DTYPE in (variant, a, b) order."""
+    def once(capacity):
+        kw = dict(tol_int=tol_int, min_run=min_run, variant_mask=mask, a_skip=a[2], capacity=capacity, a_zero=a[3])
+        if b is not None:
+            kw.update(b_hashes=b[0], b_first=b[1], b_skip=b[2], b_zero=b[3])
+        return align_seed_pairs_variants_host(a[0], a[1], **kw) if engine is None else engine.align_seed_pairs_variants(a[0], a[1], **kw)
+    t, found = once(ALIGN_FIRST_CAPACITY)
+    if found > len(t):
+        t, found = once(found)
+    return t
+
+
+def _align_flipped_pairs_call(engine, a, b, tol_int, min_run, triples):
+    """_align_flipped_call on a list of (variant, a, b) triples."""
+    def once(capacity):
+        kw = dict(tol_int=tol_int, min_run=min_run, a_skip=a[2], capacity=capacity, a_zero=a[3])
+        if b is not None:
+            kw.update(b_hashes=b[0], b_first=b[1], b_skip=b[2], b_zero=b[3])
+        if engine is None:
+            return align_windows_variants_pairs_host(a[0], a[1], triples, **kw)
+        return engine.align_windows_variants_pairs(a[0], a[1], triples, **kw)
+    rec, found = once(ALIGN_FIRST_CAPACITY)
+    if found > len(rec):
+        rec, found = once(found)
+    return rec
+
+
+def _flipped_triples(pairs, flips, n_a, n_b, self_mode):
+    """The `pairs` keyword of align_flipped - {flip: [(a, b)]} or one list for all flips - as VIDEO_PAIR_VARIANT_DTYPE in (variant, a, b)
+    order, every flip's list checked as the library checks the list of a *_pairs call.  None stays None."""
+    if pairs is None:
+        return None
+    parts = []
+    for f in sorted(set(flips), key=int):
+        one = pairs.get(f, pairs.get(int(f), [])) if isinstance(pairs, dict) else pairs
+        p = _align_pair_list(one, n_a, n_b, self_mode)
+        t = np.zeros(len(p), VIDEO_PAIR_VARIANT_DTYPE)
+        t["a"], t["b"], t["variant"] = p["a"], p["b"], int(f)
+        parts.append(t)
+    return np.concatenate(parts) if parts else np.zeros(0, VIDEO_PAIR_VARIANT_DTYPE)
+
+
+def _block_triples(engine, A, B, a0, a1, b0, b1, tol_int, min_run, mask, triple_list, seed):
+    """_block_pairs for the variants: the (variant, a, b) of one block of videos that are aligned, counted inside the block - those of the
+    caller's list, the seeded candidates (vdf_align_seed_pairs_variants), or the candidates that are on the list."""
+    tlist = None
+    if triple_list is not None:
+        sel = (triple_list["a"] >= a0) & (triple_list["a"] < a1) & (triple_list["b"] >= b0) & (triple_list["b"] < b1)
+        tlist = triple_list[sel].copy()
+        tlist["a"] -= a0
+        tlist["b"] -= b0
+        if not len(tlist):
+            return tlist
+    if seed:
+        cand = _seed_flipped_call(engine, A, B, tol_int, min_run, mask)
+        if tlist is None:
+            return cand
+        key = lambda t: (t["variant"].astype(np.uint64) << np.uint64(60)) | (t["a"].astype(np.uint64) << np.uint64(30)) | t["b"].astype(np.uint64)
+        tlist = tlist[np.isin(key(tlist), key(cand))]  # (a block holds at most isqrt(2^24) videos per side: 30 bits hold an index)
+    return tlist
+
+
+def candidate_pairs_flipped(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoHash]]] = None,
+                            tolerance: float = DEFAULT_SEARCH_TOLERANCE, min_run: int = 1, flips: Sequence = (Flip.X,), static_a=None, static_b=None,
+                            engine: Optional[Engine] = None) -> dict:
+    """Which pairs of videos can share a flipped stretch at all?  Arguments as `align_flipped`; -> {flip: [(a, b)]}, each list in (a, b) order:
+    the pairs with a window ka of a, ka a multiple of min_run, and a window of the flipped b within `tolerance` of each other, neither static
+    (include/vdf.h: vdf_align_seed_pairs_variants).  Every pair align_flipped reports under a flip is among that flip's candidates.  On an
+    engine all flips come from one pass over the seeds."""
     self_mode = windows_b is None
-    s = int(stride)
-    if s != stride or s < 1:
-        raise ValueError("stride must be a positive integer")
     flips = [Flip(int(f)) for f in flips]
     if any(not 1 <= int(f) <= 7 for f in flips):
         raise ValueError("flips are non-empty combinations of Flip.X, Flip.Y, Flip.T")
@@ -896,6 +952,61 @@ def align_flipped(windows_a: List[List[VideoHash]], windows_b: Optional[List[Lis
         return words[w0:w1], first[lo:hi + 1] - first[lo], None if skip is None else skip[w0:w1], None if zero is None else zero[w0:w1]
 
     step = max(1, math.isqrt(ALIGN_MAX_PAIRS))
+    out = {f: [] for f in flips}
+    for a0 in range(0, len(ca), step):
+        a1 = min(a0 + step, len(ca))
+        for b0 in range(a0 if self_mode else 0, len(cb), step):
+            b1 = min(b0 + step, len(cb))
+            same = self_mode and b0 == a0
+            A = block(wa, fa, ka, zb if same else None, a0, a1)
+            t = _seed_flipped_call(engine, A, None if same else block(wb, fb, kb, zb, b0, b1), tol_int, int(min_run), mask)
+            for v, a, b in zip(t["variant"], t["a"], t["b"]):
+                out[Flip(int(v))].append((int(a) + a0, int(b) + b0))
+    return {f: sorted(p) for f, p in out.items()}
+
+
+def align_flipped(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoHash]]] = None, tolerance: float = DEFAULT_SEARCH_TOLERANCE,
+                  min_run: int = 1, stride: int = 1, flips: Sequence = (Flip.X,), static_a=None, static_b=None,
+                  engine: Optional[Engine] = None, pairs=None, seed: bool = False) -> dict:
+    """`align` against the mirrored / flipped / reversed videos of windows_b - the re-upload that is mirrored AND has its intro trimmed, which
+    neither search_flipped (frames 0 ... 15 of a file) nor align (unflipped stretches) sees: {flip: [FlippedAlignment]} for every flip of `flips`,
+    each list ordered by (a, b) with at most one entry per pair, by align's rules on the window hashes of the flipped b (derived from b's hashes
+    and zero planes; include/vdf.h: vdf_align_windows_variants).  windows_b None: the videos of windows_a against each other's flips, every
+    pair once (a < b), never a video against its own mirror.  The hashes of the flipped side (windows_b, or windows_a in self mode) need their
+    zero planes (hash_frame_windows with zero_plane=True), else VidProc.  With Flip.T the matched stretch of b plays backwards
+    (FlippedAlignment); it lies on b's window grid, i.e. reversed b is taken from its last window's last frame.  Near the tolerance a stretch
+    can show with b flipped and not with the sides swapped: b's zero plane clears bits of the flipped hash that a may have set.
+    pairs: only these are aligned - {flip: [(a, b)]}, or one list of (a, b) for every flip; each list strictly increasing in (a, b), a < b when
+    windows_b is None (vdf_align_windows_variants_pairs).  seed=True: every block of videos is seeded first (candidate_pairs_flipped: all flips
+    from one pass over the seeds) and only its candidates are aligned; the result is the same dict.  With both, the candidates
+    on the list."""
+    self_mode = windows_b is None
+    s = int(stride)
+    if s != stride or s < 1:
+        raise ValueError("stride must be a positive integer")
+    flips = [Flip(int(f)) for f in flips]
+    if any(not 1 <= int(f) <= 7 for f in flips):
+        raise ValueError("flips are non-empty combinations of Flip.X, Flip.Y, Flip.T")
+    tol_int = tolerance_int(tolerance)
+    wa, fa, ka, ca = _align_csr(windows_a, static_a)
+    wb, fb, kb, cb = (wa, fa, ka, ca) if self_mode else _align_csr(windows_b, static_b)
+    zb = _align_zero(windows_a if self_mode else windows_b, "windows_a" if self_mode else "windows_b")
+    triple_list = _flipped_triples(pairs, flips, len(ca), len(cb), self_mode)
+    if not flips:
+        return {}
+    mask = 0
+    for f in flips:
+        mask |= 1 << int(f)
+    if engine is None:
+        cells = (sum(ca) ** 2 - sum(n * n for n in ca)) // 2 if self_mode else sum(ca) * sum(cb)
+        if cells * len(flips) > ALIGN_HOST_CELLS:
+            engine = default_engine()
+
+    def block(words, first, skip, zero, lo, hi):
+        w0, w1 = int(first[lo]), int(first[hi])
+        return words[w0:w1], first[lo:hi + 1] - first[lo], None if skip is None else skip[w0:w1], None if zero is None else zero[w0:w1]
+
+    step = max(1, math.isqrt(ALIGN_MAX_PAIRS))
     parts = []
     for a0 in range(0, len(ca), step):
         a1 = min(a0 + step, len(ca))
@@ -903,6 +1014,15 @@ def align_flipped(windows_a: List[List[VideoHash]], windows_b: Optional[List[Lis
             b1 = min(b0 + step, len(cb))
             same = self_mode and b0 == a0
             A = block(wa, fa, ka, zb if same else None, a0, a1)
+            if triple_list is not None or seed:
+                B = None if same else block(wb, fb, kb, zb, b0, b1)
+                tlist = _block_triples(engine, A, B, a0, a1, b0, b1, tol_int, int(min_run), mask, triple_list, seed)
+                if len(tlist):
+                    rec = _align_flipped_pairs_call(engine, A, B, tol_int, int(min_run), tlist).copy()
+                    rec["a"] += a0
+                    rec["b"] += b0
+                    parts.append(rec)
+                continue
             rec = _align_flipped_call(engine, A, None if same else block(wb, fb, kb, zb, b0, b1), tol_int, int(min_run), mask).copy()
             rec["a"] += a0
             rec["b"] += b0

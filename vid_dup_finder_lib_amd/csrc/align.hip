@@ -16,8 +16,12 @@
 // dense list in (a, b) order (flag + scan: the pairs of a chunk are enumerated in that order).
 // align_seed_kernel / align_seed_count_kernel / align_seed_scatter_kernel, at the end of the file: which pairs of videos can have a record at
 // all (vdf_align_seed_pairs*), so that the band kernels run on those pairs only.
+// align_class_layout_kernel / align_seed_variants_kernel / align_seed_variants_scatter_kernel, behind them: the same question against the
+// mirrored, flipped and reversed variants of B, every requested variant from one pass over the seeds (vdf_align_seed_pairs_variants*;
+// DESIGN.md 4.14; window_class_layout.h).
 #include "align_plan.h"
 #include "vdf_internal.h"
+#include "window_class_layout.h"
 
 namespace vdf {
 
@@ -543,6 +547,203 @@ hipError_t launch_align_seed_scatter(const AlignSeedLaunch &L, vdf_video_pair *o
     const uint32_t n_blocks = (L.n_words + 255) / 256;
     const uint32_t *block_offset = static_cast<const uint32_t *>(L.scratch) + n_blocks;
     hipLaunchKernelGGL(align_seed_scatter_kernel, dim3(n_blocks), dim3(256), 0, stream, L.bitmap, L.n_words, L.n_b, block_offset, out, limit);
+    return hipGetLastError();
+}
+
+// ---- seeding against the variants: every requested variant from one pass over the seeds (include/vdf.h: vdf_align_seed_pairs_variants*;
+// DESIGN.md 4.14) --------------------------------------------------------------------------------------------------------------------------
+// align_class_layout_kernel: the seeds of A, or the rows of B with their zero planes, into the class-major rows of window_class_layout.h.
+// One thread per output dword, plain vector loads and stores; where a bit comes from is read from the header's table (4.2 KB, L1 / L2
+// resident), and the live counts are popcounts of ~Z under the class masks.  zero == null: seeds (row r = window seed_window[r] of `hashes`, 36 dwords);
+// otherwise rows of B (row r = window row_base + r, 72 dwords).
+__device__ const ClassTables kClassTablesDevice = make_class_tables();  // window_class_layout.h: the permutation and the class masks as tables
+
+__global__ __launch_bounds__(256) void align_class_layout_kernel(const uint32_t *__restrict__ hashes, const uint32_t *__restrict__ zero,
+                                                                 const uint8_t *__restrict__ skip, const uint32_t *__restrict__ seed_window,
+                                                                 const uint32_t *__restrict__ seed_video, uint32_t row_base, uint32_t n,
+                                                                 uint32_t *__restrict__ out, unsigned long long block_base)
+{
+    const uint32_t stride = zero ? kClassRowStride : kClassSeedStride;
+    const uint64_t i = (block_base + blockIdx.x) * 256 + threadIdx.x;
+    if (i >= (uint64_t)n * stride) return;
+    const uint32_t r = (uint32_t)(i / stride), q = (uint32_t)(i % stride);
+    if (zero) {
+        const size_t w = (size_t)row_base + r;
+        out[i] = window_class_row_dword(hashes + w * 32, zero + w * 32, skip ? skip[w] : 0u, q, &kClassTablesDevice);
+    } else {
+        const size_t w = seed_window[r];
+        out[i] = window_class_seed_dword(hashes + w * 32, skip ? skip[w] : 0u, seed_video[r], q, &kClassTablesDevice);
+    }
+}
+
+// align_seed_variants_kernel: align_seed_kernel's units and streams (one workgroup per (chunk of seeds, tile of 256 rows of B); the rows in
+// VGPRs, one per lane: Hz, nZ, the seven live counts, video, skip byte; the seeds through SGPRs by scalar loads) on the class-major rows.  Per
+// dword t = a & nZ, u = t ^ Hz, popcount(t) into one subtrahend and popcount(u) into the accumulator of the dword's class; from the eight
+// sums the distance to EVERY variant of the row follows (window_class_layout.h).  Behind the 33 dwords a lower bound of min_v d_v over the
+// REQUESTED variants - popcount(A) - sub + acc_0 + per class acc_c, live_c - acc_c or the smaller of the two, as the requested variants keep
+// it, flip it or differ on it - is compared with tol under a wave-uniform ballot (exact: no requested d_v lies below it; with one variant
+// requested it is that d_v); only behind it are the distances to the requested variants formed, and a hit under variant v sets bit
+// (slot(v) n_a + seed_video) n_b + row_video, read first, atomicOr only if clear.  Rows at or behind n_rows are never addressed: their
+// lanes hold zero rows with the skip byte set.
+__global__ __launch_bounds__(256) void align_seed_variants_kernel(
+    const uint32_t *__restrict__ seeds, uint32_t n_seeds, uint32_t chunk_seeds, const uint32_t *__restrict__ rows,
+    const uint32_t *__restrict__ row_video, uint32_t n_rows, const unsigned long long *__restrict__ unit_offset,
+    const uint32_t *__restrict__ tile_first, uint32_t n_chunks, uint32_t tol, int self_mode, uint32_t variant_mask, uint32_t n_a, uint32_t n_b,
+    uint32_t *__restrict__ bitmap, unsigned long long unit_base)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned long long unit = unit_base + blockIdx.x;
+    const uint32_t chunk = align_seed_unit_chunk((align_u64_ptr)(uintptr_t)unit_offset, n_chunks, unit);
+    const uint32_t tile = ((align_u32_ptr)(uintptr_t)tile_first)[chunk] + (uint32_t)(unit - ((align_u64_ptr)(uintptr_t)unit_offset)[chunk]);
+    const uint64_t wave_row0 = (uint64_t)tile * kSeedVariantsTileRows + wave * 64;
+    if (wave_row0 >= n_rows) return;  // wave-uniform: a wave of padding rows only (no barrier below)
+    const uint32_t s0 = chunk * chunk_seeds, s1 = min(s0 + chunk_seeds, n_seeds);
+
+    // this lane's row -> VGPRs
+    uint32_t hz[kClassDwords], nz[kClassDwords], live[8], rvid = 0u, rskip = 1u;
+    const uint64_t r = wave_row0 + lane;
+    if (r < n_rows) {
+        const uint4 *rp = reinterpret_cast<const uint4 *>(rows + (size_t)r * kClassRowStride);
+        uint32_t lo[36], hi[36];
+#pragma unroll
+        for (int k = 0; k < 9; k++) {
+            const uint4 x = rp[k], y = rp[9 + k];
+            lo[4 * k] = x.x; lo[4 * k + 1] = x.y; lo[4 * k + 2] = x.z; lo[4 * k + 3] = x.w;
+            hi[4 * k] = y.x; hi[4 * k + 1] = y.y; hi[4 * k + 2] = y.z; hi[4 * k + 3] = y.w;
+        }
+#pragma unroll
+        for (int q = 0; q < (int)kClassDwords; q++) { hz[q] = lo[q]; nz[q] = hi[q]; }
+#pragma unroll
+        for (int c = 1; c < 8; c++) live[c] = lo[33 + ((c - 1) >> 2)] >> (8 * ((c - 1) & 3)) & 0xFFu;
+        rskip = lo[35];
+        rvid = row_video[r];
+    } else {
+#pragma unroll
+        for (int q = 0; q < (int)kClassDwords; q++) { hz[q] = 0u; nz[q] = 0u; }
+#pragma unroll
+        for (int c = 1; c < 8; c++) live[c] = 0u;
+    }
+    live[0] = 0u;
+
+    // which classes some requested variant flips, and which some requested variant keeps (bit c; wave-uniform)
+    uint32_t flip_any = 0u, keep_any = 0u;
+#pragma unroll
+    for (uint32_t v = 1; v < 8; v++) {
+        if (!(variant_mask >> v & 1u)) continue;
+#pragma unroll
+        for (uint32_t c = 1; c < 8; c++) {
+            if (window_class_flipped(v, c)) flip_any |= 1u << c;
+            else keep_any |= 1u << c;
+        }
+    }
+
+    align_u32_ptr seed_rows = (align_u32_ptr)(uintptr_t)seeds;
+    for (uint32_t s = s0; s < s1; ++s) {
+        align_u32_ptr ap = seed_rows + (size_t)s * kClassSeedStride;
+        uint32_t sub = 0u, acc[8];
+#pragma unroll
+        for (int c = 0; c < 8; c++) acc[c] = 0u;
+#pragma unroll
+        for (int q = 0; q < (int)kClassDwords; q++) {
+            const uint32_t t = ap[q] & nz[q];  // ap[q]: SGPR
+            sub += __builtin_popcount(t);
+            acc[window_class_of_dword(q)] += __builtin_popcount(t ^ hz[q]);
+        }
+        const uint32_t base = ap[33] - sub + acc[0];  // the never-flipped part: popcount(A & Z) + the distance inside group 0
+        // a lower bound of min over the REQUESTED variants of d_v: a class that every requested variant flips counts flipped, one that none flips
+        // counts as it is, one on which they differ counts the smaller of the two (flip_any / keep_any: wave-uniform).  With one variant requested
+        // the bound is that variant's distance itself; with several, a row close to a mix of them that no single variant reaches still passes
+        // the ballot and is turned away by the exact distances below.
+        uint32_t bound = base;
+#pragma unroll
+        for (int c = 1; c < 8; c++) {
+            const uint32_t kept = acc[c], flipped = live[c] - acc[c];
+            bound += (flip_any >> c & 1u) ? ((keep_any >> c & 1u) ? min(kept, flipped) : flipped) : kept;
+        }
+        if (__builtin_amdgcn_ballot_w64(bound <= tol) == 0ull) continue;
+        // rare path: the seed's skip byte and video, the triangle, the distances to the requested variants, the bitmap
+        if (ap[34] != 0u) continue;  // (uniform)
+        const uint32_t sv = ap[35];
+        if (rskip == 0u && (!self_mode || sv < rvid)) {
+#pragma unroll
+            for (uint32_t v = 1; v < 8; v++) {
+                if (!(variant_mask >> v & 1u)) continue;  // (uniform)
+                uint32_t d = base;
+#pragma unroll
+                for (uint32_t c = 1; c < 8; c++) d += window_class_flipped(v, c) ? live[c] - acc[c] : acc[c];
+                if (d <= tol) {
+                    const uint32_t slot = (uint32_t)__builtin_popcount(variant_mask & ((1u << v) - 1u));
+                    const uint64_t bit = ((uint64_t)slot * n_a + sv) * n_b + rvid;
+                    uint32_t *word = bitmap + (size_t)(bit >> 5);
+                    const uint32_t mask = 1u << (uint32_t)(bit & 31);
+                    if ((__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & mask) == 0u) atomicOr(word, mask);
+                }
+            }
+        }
+    }
+}
+
+// bit order of the concatenated bitmap = (slot, a, b) order = (variant, a, b) order; slots: 4 bits per slot, the slot's variant
+__global__ __launch_bounds__(256) void align_seed_variants_scatter_kernel(const uint32_t *__restrict__ bitmap, uint32_t n_words, uint32_t n_a,
+                                                                          uint32_t n_b, uint32_t slots,
+                                                                          const uint32_t *__restrict__ block_offset,
+                                                                          vdf_video_pair_variant *__restrict__ out, uint32_t limit)
+{
+    __shared__ uint32_t s_wave[4];
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    uint32_t bits = i < n_words ? bitmap[i] : 0u;
+    uint32_t total;
+    uint32_t at = block_offset[blockIdx.x] + align_block_prefix((uint32_t)__builtin_popcount(bits), s_wave, &total);
+    while (bits != 0u && at < limit) {
+        const uint64_t bit = (uint64_t)i * 32 + (uint32_t)__builtin_ctz(bits);
+        bits &= bits - 1;
+        const uint64_t sa = bit / n_b;
+        out[at++] = vdf_video_pair_variant{(uint32_t)(sa % n_a), (uint32_t)(bit % n_b), slots >> (4 * (uint32_t)(sa / n_a)) & 15u};
+    }
+}
+
+hipError_t launch_align_class_layout(const uint32_t *hashes, const uint32_t *zero, const uint8_t *skip, const uint32_t *seed_window,
+                                     const uint32_t *seed_video, uint32_t row_base, uint32_t n, uint32_t *out, hipStream_t stream)
+{
+    const size_t n_blocks = ((size_t)n * (zero ? kClassRowStride : kClassSeedStride) + 255) / 256;
+    for (const AlignLaunchCut &cut : align_launch_cuts(n_blocks)) {
+        hipLaunchKernelGGL(align_class_layout_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, hashes, zero, skip, seed_window, seed_video, row_base, n,
+                           out, (unsigned long long)cut.group_base);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_align_seed_variants(const AlignSeedVariantsLaunch &L, hipStream_t stream)
+{
+    const uint32_t n_slots = (uint32_t)__builtin_popcount(L.variant_mask);
+    if (L.n_units == 0 || n_slots == 0 || (L.variant_mask & ~0xFEu) || L.n_words == 0 || L.n_words > 7 * (1u << 21)) return hipErrorInvalidValue;
+    for (const AlignLaunchCut &cut : align_launch_cuts((size_t)L.n_units)) {
+        hipLaunchKernelGGL(align_seed_variants_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.seeds, L.n_seeds, kSeedChunk, L.rows, L.row_video,
+                           L.n_rows, L.unit_offset, L.tile_first, L.n_chunks, L.tol, L.self_mode, L.variant_mask, L.n_a, L.n_b, L.bitmap,
+                           (unsigned long long)cut.group_base);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    const uint32_t n_blocks = (L.n_words + 255) / 256;
+    uint32_t *block_count = static_cast<uint32_t *>(L.scratch), *block_offset = block_count + n_blocks, *total = block_offset + n_blocks;
+    hipLaunchKernelGGL(align_seed_count_kernel, dim3(n_blocks), dim3(256), 0, stream, L.bitmap, L.n_words, block_count);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(align_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, n_blocks, block_offset, total);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    *L.total_out = total;
+    return hipSuccess;
+}
+
+hipError_t launch_align_seed_variants_scatter(const AlignSeedVariantsLaunch &L, vdf_video_pair_variant *out, uint32_t limit, hipStream_t stream)
+{
+    const uint32_t n_blocks = (L.n_words + 255) / 256;
+    const uint32_t *block_offset = static_cast<const uint32_t *>(L.scratch) + n_blocks;
+    uint32_t slots = 0, slot = 0;
+    for (uint32_t v = 1; v < 8; v++)
+        if (L.variant_mask >> v & 1u) slots |= v << (4 * slot++);
+    hipLaunchKernelGGL(align_seed_variants_scatter_kernel, dim3(n_blocks), dim3(256), 0, stream, L.bitmap, L.n_words, L.n_a, L.n_b, slots, block_offset, out,
+                       limit);
     return hipGetLastError();
 }
 

@@ -206,6 +206,23 @@ template <class P> inline int align_pair_list_check(const P *list, size_t n_list
     return 0;
 }
 
+// The list of vdf_align_windows_variants_pairs* (DESIGN.md 4.14): strictly increasing in (variant, a, b), every variant in 1 ... 7, the pair
+// rules above.  0: fine; 1: not strictly increasing at *at; 2: video; 3: a >= b in self mode; 4: entry *at has a variant outside 1 ... 7.
+template <class T> inline int align_triple_list_check(const T *list, size_t n_list, size_t n_a, size_t n_b, bool self, size_t *at)
+{
+    for (size_t i = 0; i < n_list; i++) {
+        *at = i;
+        if (i) {
+            const T &p = list[i - 1], &q = list[i];
+            if (q.variant < p.variant || (q.variant == p.variant && (q.a < p.a || (q.a == p.a && q.b <= p.b)))) return 1;
+        }
+        if (list[i].variant < 1 || list[i].variant > 7) return 4;
+        if (list[i].a >= n_a || list[i].b >= (self ? n_a : n_b)) return 2;
+        if (self && list[i].a >= list[i].b) return 3;
+    }
+    return 0;
+}
+
 // align_next_chunk fed from a checked pair list: the same limits per chunk, pairs with a video of 0 windows skipped.  cur: the next list entry.
 template <class P>
 inline bool align_next_chunk_pairs(const uint32_t *first_a, const uint32_t *first_b, const P *list, size_t n_list, size_t &cur, AlignChunk &c,
@@ -236,6 +253,7 @@ inline bool align_next_chunk_pairs(const uint32_t *first_a, const uint32_t *firs
 constexpr uint32_t kSeedRowsPerLane = 2;                       // the VALU search backend's default instantiation (hamming.hip)
 constexpr uint32_t kSeedTileRows = 256 * kSeedRowsPerLane;
 constexpr uint32_t kSeedChunk = 256;                           // seeds per unit
+constexpr uint32_t kSeedVariantsTileRows = 256;                // the seed pass against the variants keeps ONE class-major row per lane
 // The exact early exit: after this many of a hash's 32 dwords, unrelated hashes (partial distance 16 w +- sqrt(8 w)) are, 4 sigma down, still
 // more than tol apart, and nearly every (seed, wave) stops there.  32: no test.  The kernel is instantiated for 14, 22, 26 and 32.
 inline uint32_t align_seed_check_words(uint32_t tol)

@@ -13,6 +13,7 @@
 
 #include "host_sort.h"
 #include "vdf_ctx.h"
+#include "window_class_layout.h"
 
 namespace {
 thread_local std::string g_create_error;
@@ -39,7 +40,7 @@ vdf_ctx::~vdf_ctx()
                      &hits, &perm, &matched, &exp_cols, &exp_rows, &pop_cols, &pop_rows, &cand, &group_cmin, &group_offset, &group_blocks, &up_hashes,
                      &up_dur, &up_ref_hashes, &up_ref_dur, &small, &frames, &frames2, &out_hashes, &out_hashes2, &out_dc,
                      &out_dc2, &cos_table, &crops, &crop_desc, &crop_tables, &crop_desc2, &crop_tables2, &crop_work, &sort_scratch, &sort_scratch_pub, &hits2, &hit_bitmaps, &bitmap_gather,
-                     &out_zero, &out_zero2, &up_zero, &variant_hashes, &align_plan, &align_scratch, &align_up, &seed_bitmap, &seed_plan, &seed_out};
+                     &out_zero, &out_zero2, &up_zero, &variant_hashes, &align_plan, &align_scratch, &align_up, &seed_bitmap, &seed_plan, &seed_out, &seed_classes};
     for (DevBuf *b : all) b->release();
     for (PinBuf &b : pin) b.release();
     for (PinBuf &b : pin_out) b.release();
@@ -1633,7 +1634,8 @@ int search_refs_resident(vdf_ctx *ctx, size_t n_cand, const std::vector<size_t> 
 // the argument checks all three forms share, in the order their messages are reported; first arrays on the host (null: not checked here)
 int align_checks(vdf_ctx *ctx, const void *a_hashes, const uint32_t *a_first, size_t n_a, const void *b_hashes, const uint32_t *b_first, size_t n_b,
                  const void *a_first_ptr, const void *b_first_ptr, uint32_t min_run, const void *out, size_t capacity, const size_t *n_out,
-                 const size_t *n_listed = nullptr)  // the *_pairs forms: the limit is on the LISTED pairs, not on n_a x n_b
+                 const size_t *n_listed = nullptr,  // the *_pairs forms: the limit is on the LISTED pairs, not on n_a x n_b
+                 const char *listed_what = "pairs")  // ... or "triples" (vdf_align_windows_variants_pairs*)
 {
     const bool self = b_hashes == nullptr;
     if (!n_out || (n_a && (!a_hashes || !a_first_ptr)) || (!self && n_b && !b_first_ptr) || (capacity && !out)) return fail(ctx, VDF_E_INVAL, "null pointer");
@@ -1650,7 +1652,7 @@ int align_checks(vdf_ctx *ctx, const void *a_hashes, const uint32_t *a_first, si
                 return fail(ctx, VDF_E_INVAL, std::string("the first array") + (side ? " of B" : " of A") + " decreases at video " + std::to_string(v));
     if (n_listed) {
         if (n_a > 0xFFFFFFFFull || n_b > 0xFFFFFFFFull) return fail(ctx, VDF_E_INVAL, "more than 2^32 - 1 videos on one side: a video index does not fit 32 bits");
-        if (*n_listed > vdf::kAlignMaxPairs) return fail(ctx, VDF_E_INVAL, "more than 2^24 listed pairs in one call");
+        if (*n_listed > vdf::kAlignMaxPairs) return fail(ctx, VDF_E_INVAL, std::string("more than 2^24 listed ") + listed_what + " in one call");
         return VDF_OK;
     }
     if (n_a > 0xFFFFFFFFull || n_b > 0xFFFFFFFFull || vdf::align_pair_count(n_a, self ? n_a : n_b, self) > vdf::kAlignMaxPairs)
@@ -2915,6 +2917,400 @@ int vdf_align_windows_variants(vdf_ctx *ctx, const uint64_t *a_hashes, const uin
                                            n_out, s);
     return align_variants_locked(ctx, ctx->up_hashes.as<uint64_t>(), u.d_fa, u.fa.data(), n_a, u.d_ska, ctx->up_ref_hashes.as<uint64_t>(),
                                  ctx->up_zero.as<uint64_t>(), u.d_fb, u.fb.data(), n_b, u.d_skb, false, tol_int, min_run, variant_mask, out, capacity, n_out, s);
+}
+
+// ---- the flipped alignment, seeded and on a list of (variant, a, b) triples (include/vdf.h) -------------------------------------
+// The checks of both calls in the order include/vdf.h gives them.  first arrays on the host, or null (a device form before they have come
+// down).  late: the checks behind the first arrays too - the mask, the zero plane of the flipped side, the multi-GPU refusal.
+static int align_flipped_seed_checks(vdf_ctx *ctx, const char *name, bool listed, const void *a_hashes, const uint32_t *a_first, size_t n_a,
+                                     const void *b_hashes, const uint32_t *b_first, size_t n_b, const void *a_first_ptr, const void *b_first_ptr,
+                                     const void *a_zero, const void *b_zero, const vdf_video_pair_variant *triples, size_t n_triples,
+                                     uint32_t variant_mask, uint32_t min_run, const void *out, size_t capacity, const size_t *n_out, bool late,
+                                     bool device_ctx)
+{
+    const bool self = b_hashes == nullptr;
+    if (listed) {
+        if (n_triples && !triples) return fail(ctx, VDF_E_INVAL, "null triple list");
+        if (int rc = align_checks(ctx, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first_ptr, b_first_ptr, min_run, out, capacity, n_out, &n_triples, "triples")) return rc;
+        size_t at = 0;
+        switch (vdf::align_triple_list_check(triples, n_triples, n_a, n_b, self, &at)) {
+        case 1: return fail(ctx, VDF_E_INVAL, "the triple list is not strictly increasing in (variant, a, b) at entry " + std::to_string(at));
+        case 4: return fail(ctx, VDF_E_INVAL, "triple " + std::to_string(at) + " of the list has a variant outside 1 ... 7");
+        case 2: return fail(ctx, VDF_E_INVAL, "triple " + std::to_string(at) + " of the list names a video that does not exist");
+        case 3: return fail(ctx, VDF_E_INVAL, "triple " + std::to_string(at) + " of the list has a >= b in self mode");
+        default: break;
+        }
+    } else if (int rc = align_checks(ctx, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first_ptr, b_first_ptr, min_run, out, capacity, n_out)) {
+        return rc;
+    }
+    if (!late) return VDF_OK;
+    if (int rc = align_variants_checks(ctx, listed ? 0u : variant_mask, self ? n_a : n_b, self ? a_zero : b_zero)) return rc;
+    if (device_ctx && !ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, std::string(name) + " takes a single-device context");
+    return VDF_OK;
+}
+
+static bool align_flipped_seed_trivial(bool listed, size_t n_a, size_t n_b, bool self, size_t n_triples)
+{
+    return listed ? n_triples == 0 : (n_a == 0 || (self ? n_a < 2 : n_b == 0));
+}
+
+// The host forms state the definitions directly: the variant set by the rule of vdf_window_variants_host, then the plain definitions
+// (seed_pair_host, align_pair_host) on (A, derived B); in self mode the pairs a < b of A against the derived A.
+static int align_flipped_seed_host_impl(bool listed, const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first, size_t n_a,
+                                        const uint8_t *a_skip, const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first, size_t n_b,
+                                        const uint8_t *b_skip, const vdf_video_pair_variant *triples, size_t n_triples, uint32_t tol_int, uint32_t min_run,
+                                        uint32_t variant_mask, vdf_video_pair_variant *out_pairs, vdf_alignment_variant *out_records, size_t capacity,
+                                        size_t *n_out)
+{
+    const void *o = listed ? (const void *)out_records : (const void *)out_pairs;
+    if (int rc = align_flipped_seed_checks(nullptr, "", listed, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, a_zero, b_zero, triples,
+                                           n_triples, variant_mask, min_run, o, capacity, n_out, true, false))
+        return rc;
+    const bool self = b_hashes == nullptr;
+    *n_out = 0;
+    if (align_flipped_seed_trivial(listed, n_a, n_b, self, n_triples)) return VDF_OK;
+    if (self) { b_hashes = a_hashes; b_zero = a_zero; b_first = a_first; n_b = n_a; b_skip = a_skip; }
+    const uint32_t tol = std::min<uint32_t>(tol_int, 1024u);
+    std::vector<uint64_t> derived((size_t)b_first[n_b] * 16);
+    std::vector<uint8_t> derived_skip(b_skip ? b_first[n_b] : 0);
+    const auto side_a = [&](size_t a, const uint64_t **h, uint32_t *n, const uint8_t **sk) {
+        *h = a_hashes + 16 * (size_t)a_first[a]; *n = a_first[a + 1] - a_first[a]; *sk = a_skip ? a_skip + a_first[a] : nullptr;
+    };
+    const auto side_b = [&](size_t b, const uint64_t **h, uint32_t *n, const uint8_t **sk) {
+        *h = derived.data() + 16 * (size_t)b_first[b]; *n = b_first[b + 1] - b_first[b]; *sk = b_skip ? derived_skip.data() + b_first[b] : nullptr;
+    };
+    size_t found = 0, at = 0;
+    for (uint32_t v = 1; v < vdf::kHashVariants; v++) {
+        size_t end = at;
+        if (listed) {
+            while (end < n_triples && triples[end].variant == v) end++;
+            if (end == at) continue;
+        } else if (!(variant_mask >> v & 1u)) {
+            continue;
+        }
+        window_variants_rows_host(b_hashes, b_zero, b_first, n_b, b_skip, v, derived.data(), b_skip ? derived_skip.data() : nullptr);
+        const uint64_t *ha, *hb;
+        const uint8_t *ska, *skb;
+        uint32_t Na, Nb;
+        if (listed) {
+            for (; at < end; at++) {
+                side_a(triples[at].a, &ha, &Na, &ska);
+                side_b(triples[at].b, &hb, &Nb, &skb);
+                vdf_alignment r;
+                align_pair_host(ha, Na, ska, hb, Nb, skb, tol, min_run, &r);
+                if (r.n_windows == 0) continue;
+                r.a = triples[at].a; r.b = triples[at].b;
+                if (found < capacity) out_records[found] = alignment_of_variant(r, v);
+                found++;
+            }
+            continue;
+        }
+        for (size_t a = 0; a < n_a; a++)
+            for (size_t b = self ? a + 1 : 0; b < n_b; b++) {
+                side_a(a, &ha, &Na, &ska);
+                side_b(b, &hb, &Nb, &skb);
+                if (!seed_pair_host(ha, Na, ska, hb, Nb, skb, tol, min_run)) continue;
+                if (found < capacity) out_pairs[found] = vdf_video_pair_variant{(uint32_t)a, (uint32_t)b, v};
+                found++;
+            }
+    }
+    *n_out = found;
+    return VDF_OK;
+}
+
+// The seed pass against the variants.  The checks have passed on the host copies of the first arrays; every array pointer of `in` and d_b_zero
+// (the zero plane that goes with in.d_b_hashes) is a device pointer.  Seeds and rows go into their class-major form, the bitmap's requested
+// slots are cleared on the call's stream, ONE seed kernel marks every requested variant, count + scan give the total; the host reads it, then
+// the first min(total, capacity) triples.
+static int align_seed_variants_locked(vdf_ctx *ctx, const AlignSides &in, const uint64_t *d_b_zero, uint32_t tol_int, uint32_t min_run,
+                                      uint32_t variant_mask, vdf_video_pair_variant *out, size_t capacity, size_t *n_out, hipStream_t s)
+{
+    *n_out = 0;
+    const uint32_t n_slots = (uint32_t)__builtin_popcount(variant_mask);
+    vdf::AlignSeedPlan plan;
+    vdf::align_seed_plan(in.h_first_a, in.n_a, in.h_first_b, in.n_b, in.self, min_run, plan, vdf::kSeedVariantsTileRows);
+    if (n_slots == 0 || plan.n_units() == 0) return VDF_OK;
+    const uint64_t n_bits = (uint64_t)n_slots * in.n_a * in.n_b;  // <= 7 (2^25 + 2^13): align_checks
+    const uint32_t n_words = (uint32_t)((n_bits + 31) / 32);
+    const size_t n_seeds = plan.n_seeds(), n_chunks = plan.n_chunks();
+    const size_t at_video = n_seeds * 4, at_row = at_video + n_seeds * 4, at_tile = at_row + (size_t)plan.n_rows * 4;
+    const size_t at_unit = (at_tile + n_chunks * 4 + 7) & ~(size_t)7, plan_bytes = at_unit + (n_chunks + 1) * 8;
+    const size_t seed_bytes = n_seeds * vdf::kClassSeedStride * 4, row_bytes = (size_t)plan.n_rows * vdf::kClassRowStride * 4;  // multiples of 16
+    VDF_HIP(ctx, ctx->seed_bitmap.reserve((size_t)n_words * 4));
+    VDF_HIP(ctx, ctx->seed_plan.reserve(plan_bytes));
+    VDF_HIP(ctx, ctx->seed_classes.reserve(seed_bytes + row_bytes));
+    VDF_HIP(ctx, ctx->align_scratch.reserve(vdf::align_seed_scratch_bytes(n_words)));
+    char *dp = ctx->seed_plan.as<char>();
+    uint32_t *d_seeds = ctx->seed_classes.as<uint32_t>(), *d_rows = d_seeds + n_seeds * vdf::kClassSeedStride;
+    VDF_HIP(ctx, hipMemsetAsync(ctx->seed_bitmap.p, 0, (size_t)n_words * 4, s));
+    VDF_HIP(ctx, hipMemcpyAsync(dp, plan.seed_window.data(), n_seeds * 4, hipMemcpyHostToDevice, s));
+    VDF_HIP(ctx, hipMemcpyAsync(dp + at_video, plan.seed_video.data(), n_seeds * 4, hipMemcpyHostToDevice, s));
+    VDF_HIP(ctx, hipMemcpyAsync(dp + at_row, plan.row_video.data(), (size_t)plan.n_rows * 4, hipMemcpyHostToDevice, s));
+    VDF_HIP(ctx, hipMemcpyAsync(dp + at_tile, plan.tile_first.data(), n_chunks * 4, hipMemcpyHostToDevice, s));
+    VDF_HIP(ctx, hipMemcpyAsync(dp + at_unit, plan.unit_offset.data(), (n_chunks + 1) * 8, hipMemcpyHostToDevice, s));
+    VDF_HIP(ctx, vdf::launch_align_class_layout(reinterpret_cast<const uint32_t *>(in.d_a_hashes), nullptr, in.d_a_skip, reinterpret_cast<const uint32_t *>(dp),
+                                                reinterpret_cast<const uint32_t *>(dp + at_video), 0, (uint32_t)n_seeds, d_seeds, s));
+    VDF_HIP(ctx, vdf::launch_align_class_layout(reinterpret_cast<const uint32_t *>(in.d_b_hashes), reinterpret_cast<const uint32_t *>(d_b_zero), in.d_b_skip,
+                                                nullptr, nullptr, plan.row_base, plan.n_rows, d_rows, s));
+    uint32_t *d_total = nullptr;
+    vdf::AlignSeedVariantsLaunch L{};
+    L.seeds = d_seeds; L.n_seeds = (uint32_t)n_seeds;
+    L.rows = d_rows; L.row_video = reinterpret_cast<const uint32_t *>(dp + at_row); L.n_rows = plan.n_rows;
+    L.unit_offset = reinterpret_cast<const unsigned long long *>(dp + at_unit);
+    L.tile_first = reinterpret_cast<const uint32_t *>(dp + at_tile);
+    L.n_chunks = (uint32_t)n_chunks; L.n_units = plan.n_units();
+    L.tol = std::min<uint32_t>(tol_int, 1024u); L.self_mode = in.self ? 1 : 0; L.variant_mask = variant_mask;
+    L.n_a = (uint32_t)in.n_a; L.n_b = (uint32_t)in.n_b;
+    L.bitmap = ctx->seed_bitmap.as<uint32_t>(); L.n_words = n_words;
+    L.scratch = ctx->align_scratch.p; L.total_out = &d_total;
+    VDF_HIP(ctx, vdf::launch_align_seed_variants(L, s));
+    uint32_t total = 0;
+    VDF_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));  // also: the plan arrays are free to go
+    if ((uint64_t)total > n_bits) return fail(ctx, VDF_E_HIP, "align seed: more triples than bits");
+    const size_t take = std::min<size_t>(total, capacity);
+    if (take) {
+        VDF_HIP(ctx, ctx->seed_out.reserve(take * sizeof(vdf_video_pair_variant)));
+        VDF_HIP(ctx, vdf::launch_align_seed_variants_scatter(L, ctx->seed_out.as<vdf_video_pair_variant>(), (uint32_t)take, s));
+        VDF_HIP(ctx, hipMemcpyAsync(out, ctx->seed_out.p, take * sizeof(vdf_video_pair_variant), hipMemcpyDeviceToHost, s));
+        VDF_HIP(ctx, hipStreamSynchronize(s));
+    }
+    *n_out = total;
+    return VDF_OK;
+}
+
+// align_variants_locked on a checked list: per variant present, ascending, the set is derived and the align core runs on that variant's
+// contiguous sublist.
+static int align_variants_pairs_locked(vdf_ctx *ctx, const AlignSides &in, const uint64_t *d_b_zero, const vdf_video_pair_variant *triples, size_t n_triples,
+                                       uint32_t tol_int, uint32_t min_run, vdf_alignment_variant *out, size_t capacity, size_t *n_out, hipStream_t s)
+{
+    const uint32_t row0 = in.h_first_b[0], row_end = in.h_first_b[in.n_b];
+    const size_t hash_bytes = (size_t)row_end * VDF_HASH_WORDS * sizeof(uint64_t);
+    VDF_HIP(ctx, ctx->variant_hashes.reserve(hash_bytes + (in.d_b_skip ? row_end : 0) + 16));
+    uint64_t *d_var = ctx->variant_hashes.as<uint64_t>();
+    uint8_t *d_var_skip = in.d_b_skip ? ctx->variant_hashes.as<uint8_t>() + hash_bytes : nullptr;
+    std::vector<vdf_video_pair> sub;
+    std::vector<vdf_alignment> records;
+    size_t found = 0;
+    for (size_t at = 0; at < n_triples;) {
+        const uint32_t v = triples[at].variant;
+        sub.clear();
+        for (; at < n_triples && triples[at].variant == v; at++) sub.push_back(vdf_video_pair{triples[at].a, triples[at].b});
+        VDF_HIP(ctx, vdf::launch_window_variants(in.d_b_hashes, d_b_zero, in.d_b_first, (uint32_t)in.n_b, in.d_b_skip, v, row0, row_end - row0, d_var, d_var_skip, s));
+        records.resize(std::min(capacity > found ? capacity - found : 0, sub.size()));
+        size_t n_v = 0;
+        if (int rc = align_locked(ctx, in.d_a_hashes, in.d_a_first, in.h_first_a, in.n_a, in.d_a_skip, d_var, in.d_b_first, in.h_first_b, in.n_b, d_var_skip,
+                                  in.self, tol_int, min_run, records.data(), records.size(), &n_v, s, sub.data(), sub.size()))
+            return rc;
+        for (size_t i = 0; i < std::min(n_v, records.size()); i++) out[found + i] = alignment_of_variant(records[i], v);
+        found += n_v;
+    }
+    VDF_HIP(ctx, hipStreamSynchronize(s));
+    *n_out = found;
+    return VDF_OK;
+}
+
+static int align_flipped_seed_run(vdf_ctx *ctx, bool listed, const AlignSides &in, const uint64_t *d_b_zero, const vdf_video_pair_variant *triples,
+                                  size_t n_triples, uint32_t tol_int, uint32_t min_run, uint32_t variant_mask, vdf_video_pair_variant *out_pairs,
+                                  vdf_alignment_variant *out_records, size_t capacity, size_t *n_out, hipStream_t s)
+{
+    if (listed) return align_variants_pairs_locked(ctx, in, d_b_zero, triples, n_triples, tol_int, min_run, out_records, capacity, n_out, s);
+    return align_seed_variants_locked(ctx, in, d_b_zero, tol_int, min_run, variant_mask, out_pairs, capacity, n_out, s);
+}
+
+static int align_flipped_seed_device_impl(vdf_ctx *ctx, const char *name, bool listed, const uint64_t *d_a_hashes, const uint64_t *d_a_zero,
+                                          const uint32_t *d_a_first, size_t n_a, const uint8_t *d_a_skip, const uint64_t *d_b_hashes,
+                                          const uint64_t *d_b_zero, const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip,
+                                          const vdf_video_pair_variant *triples, size_t n_triples, uint32_t tol_int, uint32_t min_run, uint32_t variant_mask,
+                                          vdf_video_pair_variant *out_pairs, vdf_alignment_variant *out_records, size_t capacity, size_t *n_out, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const void *o = listed ? (const void *)out_records : (const void *)out_pairs;
+    const bool self = d_b_hashes == nullptr;
+    const auto checks = [&](const uint32_t *fa, const uint32_t *fb, bool late) {
+        return align_flipped_seed_checks(ctx, name, listed, d_a_hashes, fa, n_a, d_b_hashes, fb, n_b, d_a_first, d_b_first, d_a_zero, d_b_zero, triples, n_triples,
+                                         variant_mask, min_run, o, capacity, n_out, late, true);
+    };
+    // everything that can be said without the first arrays (the list form: all of it, the multi-GPU refusal last); then they come down and are checked
+    if (int rc = checks(nullptr, nullptr, listed)) return rc;
+    if (align_flipped_seed_trivial(listed, n_a, n_b, self, n_triples) || !ctx->subs.empty()) {  // nothing to read back, or no device to read it from
+        if (int rc = checks(nullptr, nullptr, true)) return rc;
+        *n_out = 0;
+        return VDF_OK;
+    }
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<uint32_t> fa, fb;
+    if (int rc = align_first_down(ctx, d_a_first, n_a, d_b_first, n_b, self, s, fa, fb)) return rc;
+    if (int rc = checks(fa.data(), self ? nullptr : fb.data(), true)) return rc;
+    *n_out = 0;
+    const AlignSides in = self ? AlignSides{d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, true}
+                               : AlignSides{d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, d_b_hashes, d_b_first, fb.data(), n_b, d_b_skip, false};
+    return align_flipped_seed_run(ctx, listed, in, self ? d_a_zero : d_b_zero, triples, n_triples, tol_int, min_run, variant_mask, out_pairs, out_records,
+                                  capacity, n_out, s);
+}
+
+// Host arrays: as vdf_align_windows_variants - the zero plane of the flipped side goes up beside its hashes.
+static int align_flipped_seed_ctx_impl(vdf_ctx *ctx, const char *name, bool listed, const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first,
+                                       size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first, size_t n_b,
+                                       const uint8_t *b_skip, const vdf_video_pair_variant *triples, size_t n_triples, uint32_t tol_int, uint32_t min_run,
+                                       uint32_t variant_mask, vdf_video_pair_variant *out_pairs, vdf_alignment_variant *out_records, size_t capacity,
+                                       size_t *n_out)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const void *o = listed ? (const void *)out_records : (const void *)out_pairs;
+    if (int rc = align_flipped_seed_checks(ctx, name, listed, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, a_zero, b_zero, triples, n_triples,
+                                           variant_mask, min_run, o, capacity, n_out, true, true))
+        return rc;
+    const bool self = b_hashes == nullptr;
+    *n_out = 0;
+    if (align_flipped_seed_trivial(listed, n_a, n_b, self, n_triples)) return VDF_OK;
+    const uint64_t *zero = self ? a_zero : b_zero;
+    const uint32_t *zero_first = self ? a_first : b_first;
+    const size_t n_flipped = self ? n_a : n_b;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    AlignUploaded u;
+    if (int rc = align_upload(ctx, a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, self, s, &u)) return rc;
+    if (int rc = upload(ctx, ctx->up_zero, zero + 16 * (size_t)zero_first[0], (size_t)(zero_first[n_flipped] - zero_first[0]) * 16 * sizeof(uint64_t), s)) return rc;
+    return align_flipped_seed_run(ctx, listed, align_sides_uploaded(ctx, u, n_a, n_b, self), ctx->up_zero.as<uint64_t>(), triples, n_triples, tol_int, min_run,
+                                  variant_mask, out_pairs, out_records, capacity, n_out, s);
+}
+
+int vdf_align_seed_pairs_variants_host(const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                       const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                                       uint32_t tol_int, uint32_t min_run, uint32_t variant_mask, vdf_video_pair_variant *out, size_t capacity, size_t *n_out)
+{
+    return align_flipped_seed_host_impl(false, a_hashes, a_zero, a_first, n_a, a_skip, b_hashes, b_zero, b_first, n_b, b_skip, nullptr, 0, tol_int, min_run,
+                                        variant_mask, out, nullptr, capacity, n_out);
+}
+
+int vdf_align_seed_pairs_variants(vdf_ctx *ctx, const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                  const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, uint32_t tol_int,
+                                  uint32_t min_run, uint32_t variant_mask, vdf_video_pair_variant *out, size_t capacity, size_t *n_out)
+{
+    return align_flipped_seed_ctx_impl(ctx, "vdf_align_seed_pairs_variants", false, a_hashes, a_zero, a_first, n_a, a_skip, b_hashes, b_zero, b_first, n_b, b_skip,
+                                       nullptr, 0, tol_int, min_run, variant_mask, out, nullptr, capacity, n_out);
+}
+
+int vdf_align_seed_pairs_variants_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint64_t *d_a_zero, const uint32_t *d_a_first, size_t n_a,
+                                         const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint64_t *d_b_zero, const uint32_t *d_b_first, size_t n_b,
+                                         const uint8_t *d_b_skip, uint32_t tol_int, uint32_t min_run, uint32_t variant_mask, vdf_video_pair_variant *out,
+                                         size_t capacity, size_t *n_out, void *stream)
+{
+    return align_flipped_seed_device_impl(ctx, "vdf_align_seed_pairs_variants_device", false, d_a_hashes, d_a_zero, d_a_first, n_a, d_a_skip, d_b_hashes, d_b_zero,
+                                          d_b_first, n_b, d_b_skip, nullptr, 0, tol_int, min_run, variant_mask, out, nullptr, capacity, n_out, stream);
+}
+
+int vdf_align_windows_variants_pairs_host(const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                          const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                                          const vdf_video_pair_variant *triples, size_t n_triples, uint32_t tol_int, uint32_t min_run,
+                                          vdf_alignment_variant *out, size_t capacity, size_t *n_out)
+{
+    return align_flipped_seed_host_impl(true, a_hashes, a_zero, a_first, n_a, a_skip, b_hashes, b_zero, b_first, n_b, b_skip, triples, n_triples, tol_int, min_run,
+                                        0, nullptr, out, capacity, n_out);
+}
+
+int vdf_align_windows_variants_pairs(vdf_ctx *ctx, const uint64_t *a_hashes, const uint64_t *a_zero, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                     const uint64_t *b_hashes, const uint64_t *b_zero, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                                     const vdf_video_pair_variant *triples, size_t n_triples, uint32_t tol_int, uint32_t min_run, vdf_alignment_variant *out,
+                                     size_t capacity, size_t *n_out)
+{
+    return align_flipped_seed_ctx_impl(ctx, "vdf_align_windows_variants_pairs", true, a_hashes, a_zero, a_first, n_a, a_skip, b_hashes, b_zero, b_first, n_b, b_skip,
+                                       triples, n_triples, tol_int, min_run, 0, nullptr, out, capacity, n_out);
+}
+
+int vdf_align_windows_variants_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint64_t *d_a_zero, const uint32_t *d_a_first, size_t n_a,
+                                            const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint64_t *d_b_zero, const uint32_t *d_b_first, size_t n_b,
+                                            const uint8_t *d_b_skip, const vdf_video_pair_variant *triples, size_t n_triples, uint32_t tol_int, uint32_t min_run,
+                                            vdf_alignment_variant *out, size_t capacity, size_t *n_out, void *stream)
+{
+    return align_flipped_seed_device_impl(ctx, "vdf_align_windows_variants_pairs_device", true, d_a_hashes, d_a_zero, d_a_first, n_a, d_a_skip, d_b_hashes, d_b_zero,
+                                          d_b_first, n_b, d_b_skip, triples, n_triples, tol_int, min_run, 0, nullptr, out, capacity, n_out, stream);
+}
+
+// ---- the class-major rows themselves (include/vdf.h: vdf_window_class_layout_*): what the seed pass against the variants reads,
+// made reachable so that the layout kernel can be compared with its host twin word for word
+static int class_layout_checks(vdf_ctx *ctx, const void *hashes, const void *first_ptr, const uint32_t *first, size_t n_videos, uint32_t min_run, const void *out,
+                               const size_t *n_rows)
+{
+    if (!n_rows || (n_videos && (!hashes || !first_ptr))) return fail(ctx, VDF_E_INVAL, "null pointer");
+    if (min_run == 0) return fail(ctx, VDF_E_INVAL, "min_run of zero");
+    if (n_videos > 0xFFFFFFFFull) return fail(ctx, VDF_E_INVAL, "more than 2^32 - 1 videos");
+    for (size_t v = 0; first && v < n_videos; v++)
+        if (first[v + 1] < first[v]) return fail(ctx, VDF_E_INVAL, "the first array decreases at video " + std::to_string(v));
+    return VDF_OK;
+}
+
+// the seeds of a set (zero == null: window first[v] + k min_run of every video v) or its rows [first[0], first[n_videos])
+static void class_layout_plan(const uint32_t *first, size_t n_videos, bool seeds, uint32_t min_run, std::vector<uint32_t> &window, std::vector<uint32_t> &video)
+{
+    window.clear(); video.clear();
+    for (size_t v = 0; seeds && v < n_videos; v++)
+        for (uint64_t w = first[v]; w < first[v + 1]; w += min_run) { window.push_back((uint32_t)w); video.push_back((uint32_t)v); }
+}
+
+int vdf_window_class_layout_host(const uint64_t *hashes, const uint64_t *zero, const uint32_t *first, size_t n_videos, const uint8_t *skip, uint32_t min_run,
+                                 uint32_t *out, size_t capacity_rows, size_t *n_rows)
+{
+    if (int rc = class_layout_checks(nullptr, hashes, first, first, n_videos, min_run, out, n_rows)) return rc;
+    *n_rows = 0;
+    if (n_videos == 0) return VDF_OK;
+    const uint32_t *h32 = reinterpret_cast<const uint32_t *>(hashes), *z32 = reinterpret_cast<const uint32_t *>(zero);
+    std::vector<uint32_t> window, video;
+    class_layout_plan(first, n_videos, zero == nullptr, min_run, window, video);
+    const size_t n = zero ? first[n_videos] - first[0] : window.size();
+    *n_rows = n;
+    if (n > capacity_rows || (n && !out)) return VDF_E_INVAL;
+    for (size_t r = 0; r < n; r++) {
+        if (zero) {
+            const size_t w = (size_t)first[0] + r;
+            for (uint32_t q = 0; q < vdf::kClassRowStride; q++)
+                out[r * vdf::kClassRowStride + q] = vdf::window_class_row_dword(h32 + w * 32, z32 + w * 32, skip ? skip[w] : 0u, q);
+        } else {
+            const size_t w = window[r];
+            for (uint32_t q = 0; q < vdf::kClassSeedStride; q++)
+                out[r * vdf::kClassSeedStride + q] = vdf::window_class_seed_dword(h32 + w * 32, skip ? skip[w] : 0u, video[r], q);
+        }
+    }
+    return VDF_OK;
+}
+
+int vdf_window_class_layout_device(vdf_ctx *ctx, const uint64_t *d_hashes, const uint64_t *d_zero, const uint32_t *d_first, size_t n_videos, const uint8_t *d_skip,
+                                   uint32_t min_run, uint32_t *d_out, size_t capacity_rows, size_t *n_rows, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (int rc = class_layout_checks(ctx, d_hashes, d_first, nullptr, n_videos, min_run, d_out, n_rows)) return rc;
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "vdf_window_class_layout_device takes a single-device context");
+    *n_rows = 0;
+    if (n_videos == 0) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<uint32_t> first(n_videos + 1);
+    VDF_HIP(ctx, hipMemcpyAsync(first.data(), d_first, first.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));
+    if (int rc = class_layout_checks(ctx, d_hashes, d_first, first.data(), n_videos, min_run, d_out, n_rows)) return rc;
+    std::vector<uint32_t> window, video;
+    class_layout_plan(first.data(), n_videos, d_zero == nullptr, min_run, window, video);
+    const size_t n = d_zero ? first[n_videos] - first[0] : window.size();
+    *n_rows = n;
+    if (n > 0xFFFFFFFFull || n > capacity_rows || (n && !d_out)) return fail(ctx, VDF_E_INVAL, "the output holds fewer rows than the layout has");
+    if (n == 0) return VDF_OK;
+    const uint32_t *d_window = nullptr, *d_video = nullptr;
+    if (!d_zero) {
+        VDF_HIP(ctx, ctx->seed_plan.reserve(2 * n * 4));
+        char *dp = ctx->seed_plan.as<char>();
+        VDF_HIP(ctx, hipMemcpyAsync(dp, window.data(), n * 4, hipMemcpyHostToDevice, s));
+        VDF_HIP(ctx, hipMemcpyAsync(dp + n * 4, video.data(), n * 4, hipMemcpyHostToDevice, s));
+        d_window = reinterpret_cast<const uint32_t *>(dp); d_video = reinterpret_cast<const uint32_t *>(dp + n * 4);
+    }
+    VDF_HIP(ctx, vdf::launch_align_class_layout(reinterpret_cast<const uint32_t *>(d_hashes), reinterpret_cast<const uint32_t *>(d_zero), d_skip, d_window, d_video,
+                                                first[0], (uint32_t)n, d_out, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));  // the plan arrays are free to go; the rows are there
+    return VDF_OK;
 }
 
 int vdf_hash_variant(const uint64_t *hash, const uint64_t *zero, uint32_t variant, uint64_t *out)

@@ -155,6 +155,7 @@ struct vdf_ctx {
     DevBuf sort_scratch_pub;  // the same for vdf_sort_order_device: the caller may sort on one stream and search on another
     // hash scratch
     DevBuf align_plan, align_scratch, align_up;  // vdf_align_windows: a chunk's pairs + unit offsets, its band / pair records, the host form's first + skip arrays
+    DevBuf seed_classes;                         // vdf_align_seed_pairs_variants: the class-major seeds of A, then the class-major rows of B (window_class_layout.h)
     DevBuf seed_bitmap, seed_plan, seed_out;     // vdf_align_seed_pairs: the n_a x n_b bits of a call (reserved once, cleared by every call), its seeds / row videos / units, its dense pairs
     DevBuf out_zero, out_zero2, up_zero, variant_hashes;  // zero planes of the host-frame calls' batches / of vdf_search_variants, and its derived references
     DevBuf small, frames, frames2, out_hashes, out_hashes2, out_dc, out_dc2, cos_table, crops, crop_desc, crop_tables, crop_desc2, crop_tables2, crop_work;

@@ -298,5 +298,33 @@ struct AlignSeedLaunch {
 size_t align_seed_scratch_bytes(size_t n_words);
 hipError_t launch_align_seed(const AlignSeedLaunch &L, hipStream_t stream);
 hipError_t launch_align_seed_scatter(const AlignSeedLaunch &L, vdf_video_pair *out, uint32_t limit, hipStream_t stream);
+// The seed pass against the variants.  launch_align_class_layout: n seeds of A (zero == null; row r = window seed_window[r]) or
+// n rows of B from window row_base on, into the class-major rows of window_class_layout.h (36 / 72 dwords each).  launch_align_seed_variants:
+// every unit's seeds against its tile of 256 rows into `bitmap` - popcount(variant_mask) slots of n_a x n_b bits, the requested variants in
+// ascending order, cleared by the caller on the stream - then the count and scan of its set bits; the scatter writes the first `limit`
+// triples in (variant, a, b) order.  scratch holds align_seed_scratch_bytes(n_words).
+struct AlignSeedVariantsLaunch {
+    const uint32_t *seeds;               // [n_seeds][36]
+    uint32_t n_seeds;
+    const uint32_t *rows;                // [n_rows][72], 16-byte aligned
+    const uint32_t *row_video;           // [n_rows]
+    uint32_t n_rows;
+    const unsigned long long *unit_offset;  // [n_chunks + 1]; the plan is align_seed_plan's at tile_rows = kSeedVariantsTileRows
+    const uint32_t *tile_first;          // [n_chunks]
+    uint32_t n_chunks;
+    uint64_t n_units;
+    uint32_t tol;
+    int self_mode;
+    uint32_t variant_mask;               // bits 1 ... 7
+    uint32_t n_a, n_b;
+    uint32_t *bitmap;
+    uint32_t n_words;
+    void *scratch;
+    uint32_t **total_out;
+};
+hipError_t launch_align_class_layout(const uint32_t *hashes, const uint32_t *zero, const uint8_t *skip, const uint32_t *seed_window,
+                                     const uint32_t *seed_video, uint32_t row_base, uint32_t n, uint32_t *out, hipStream_t stream);
+hipError_t launch_align_seed_variants(const AlignSeedVariantsLaunch &L, hipStream_t stream);
+hipError_t launch_align_seed_variants_scatter(const AlignSeedVariantsLaunch &L, vdf_video_pair_variant *out, uint32_t limit, hipStream_t stream);
 
 }  // namespace vdf

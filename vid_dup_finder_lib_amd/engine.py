@@ -273,6 +273,97 @@ def align_windows_stretches_pairs_host(a_hashes, a_first, pairs, b_hashes=None, 
     return out[:min(n.value, out.size)], int(n.value)
 
 
+# one (variant, a, b) triple (include/vdf.h: vdf_video_pair_variant, 12 bytes): what the seeded variants call returns and the variants-pairs calls take
+VIDEO_PAIR_VARIANT_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("variant", "<u4")])
+
+
+def video_pair_variants(triples) -> np.ndarray:
+    """A list of (variant, a, b) - VIDEO_PAIR_VARIANT_DTYPE records, or anything numpy reads as [n, 3] integers in that order - as the C ABI
+    takes it."""
+    t = np.asarray(triples)
+    if t.dtype == VIDEO_PAIR_VARIANT_DTYPE:
+        return np.ascontiguousarray(t).reshape(-1)
+    if t.size == 0:
+        return np.zeros(0, VIDEO_PAIR_VARIANT_DTYPE)
+    if t.dtype.kind not in "iu" or t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("triples: [n, 3] integers (variant, a, b) or VIDEO_PAIR_VARIANT_DTYPE records")
+    if int(t.min()) < 0 or int(t.max()) >= 2**32:
+        raise ValueError("triples: variants and video indices are 0 .. 2^32 - 1")
+    out = np.zeros(len(t), VIDEO_PAIR_VARIANT_DTYPE)
+    out["variant"], out["a"], out["b"] = t[:, 0], t[:, 1], t[:, 2]
+    return out
+
+
+def triple_list_problem(triples: np.ndarray, n_a: int, n_b: int, self_mode: bool):
+    """What vdf_align_windows_variants_pairs* refuses in a list, in the library's order and words - the first entry that breaks a rule, and of
+    its rules the first; None: the list is fine (pair_list_problem's twin for triples)."""
+    v, a, b = (triples[k].astype(np.int64) for k in ("variant", "a", "b"))
+    code = np.zeros(len(triples), np.uint8)
+    code[self_mode & (a >= b)] = 3
+    code[(a >= n_a) | (b >= (n_a if self_mode else n_b))] = 2
+    code[(v < 1) | (v > 7)] = 4
+    key = (v[1:] < v[:-1]) | ((v[1:] == v[:-1]) & ((a[1:] < a[:-1]) | ((a[1:] == a[:-1]) & (b[1:] <= b[:-1]))))
+    code[1:][key] = 1
+    bad = np.flatnonzero(code)
+    if not bad.size:
+        return None
+    i = int(bad[0])
+    return {1: f"the triple list is not strictly increasing in (variant, a, b) at entry {i}", 4: f"triple {i} of the list has a variant outside 1 ... 7",
+            2: f"triple {i} of the list names a video that does not exist", 3: f"triple {i} of the list has a >= b in self mode"}[int(code[i])]
+
+
+def align_seed_pairs_variants_host(a_hashes, a_first, a_zero=None, b_hashes=None, b_first=None, b_zero=None, tol_int: int = 350, min_run: int = 1,
+                                   variant_mask: int = 2, a_skip=None, b_skip=None, capacity: int = 1024):
+    """vdf_align_seed_pairs_variants_host: per variant of variant_mask (bits 1 ... 7) the candidate pairs of align_seed_pairs_host on (A, the
+    variant set of B), in plain C++ on the CPU.  -> (triples [min(found, capacity)] of VIDEO_PAIR_VARIANT_DTYPE in (variant, a, b) order, found)."""
+    lib = _capi.load()
+    keep, args = _align_variants_host_args(a_hashes, a_zero, a_first, b_hashes, b_zero, b_first, a_skip, b_skip)  # keep: holds the arrays alive over the call
+    out = np.zeros(max(int(capacity), 0), VIDEO_PAIR_VARIANT_DTYPE)
+    n = C.c_size_t(0)
+    rc = lib.vdf_align_seed_pairs_variants_host(*args, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run), _variant_mask(variant_mask),
+                                                out.ctypes.data if out.size else None, out.size, C.byref(n))
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_align_seed_pairs_variants_host: bad argument")
+    return out[:min(n.value, out.size)], int(n.value)
+
+
+def align_windows_variants_pairs_host(a_hashes, a_first, triples, a_zero=None, b_hashes=None, b_first=None, b_zero=None, tol_int: int = 350,
+                                      min_run: int = 1, a_skip=None, b_skip=None, capacity: int = 1024):
+    """vdf_align_windows_variants_pairs_host: align_windows_variants_host on the listed (variant, a, b) triples only (strictly increasing).
+    -> (records [min(found, capacity)] of ALIGN_VARIANT_DTYPE in (variant, a, b) order, found)."""
+    lib = _capi.load()
+    keep, args = _align_variants_host_args(a_hashes, a_zero, a_first, b_hashes, b_zero, b_first, a_skip, b_skip)  # keep: holds the arrays alive over the call
+    t = video_pair_variants(triples)
+    out = np.zeros(max(int(capacity), 0), ALIGN_VARIANT_DTYPE)
+    n = C.c_size_t(0)
+    rc = lib.vdf_align_windows_variants_pairs_host(*args, t.ctypes.data if t.size else None, t.size, _align_uint32("tol_int", tol_int),
+                                                   _align_uint32("min_run", min_run), out.ctypes.data if out.size else None, out.size, C.byref(n))
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, f"vdf_align_windows_variants_pairs_host: {triple_list_problem(t, args[3], args[8], b_hashes is None) or 'bad argument'}")
+    return out[:min(n.value, out.size)], int(n.value)
+
+
+CLASS_SEED_DWORDS, CLASS_ROW_DWORDS = 36, 72   # a seed / a row of B in the class-major layout (include/vdf.h: vdf_window_class_layout_*)
+
+
+def window_class_layout_host(hashes, first, zero=None, skip=None, min_run: int = 1) -> np.ndarray:
+    """vdf_window_class_layout_host: the class-major rows the seeded flipped alignment reads, on the CPU.  zero None: the seeds of the set at
+    min_run, [n_seeds, 36] u32; otherwise its rows with their planes, [n_rows, 72] u32."""
+    lib = _capi.load()
+    h = np.ascontiguousarray(hashes, dtype=np.uint64).reshape(-1, HASH_WORDS)
+    f = np.ascontiguousarray(first, dtype=np.uint32)
+    z = _zero_arg(zero, h.shape[0])
+    sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8)
+    width = CLASS_SEED_DWORDS if z is None else CLASS_ROW_DWORDS
+    out = np.zeros((max(len(h), 1), width), np.uint32)
+    n = C.c_size_t(0)
+    rc = lib.vdf_window_class_layout_host(h.ctypes.data or f.ctypes.data, None if z is None else (z.ctypes.data or f.ctypes.data), f.ctypes.data, len(f) - 1,
+                                          None if sk is None else sk.ctypes.data, _align_uint32("min_run", min_run), out.ctypes.data, len(out), C.byref(n))
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_window_class_layout_host: bad argument")
+    return out[:n.value]
+
+
 def window_variants_host(hashes, zero, first, variant: int, skip=None):
     """vdf_window_variants_host: the variant of a set of window hashes (hashes / zero [windows, 16] u64, first [videos + 1]) on the CPU ->
     hashes [windows, 16] (and the skip bytes carried along, if skip is given).  Rows outside [first[0], first[-1]) come back zero."""
@@ -575,6 +666,67 @@ class Engine:
                                                                 _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
                                                                 _align_uint32("max_stretches", max_stretches), _align_uint32("guard", guard),
                                                                 out.ctypes.data if out.size else None, out.size, C.byref(n), stream or None))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def window_class_layout_device(self, d_hashes: int, d_first: int, n_videos: int, d_out: int, capacity_rows: int, d_zero: int = 0, d_skip: int = 0,
+                                   min_run: int = 1, stream: int = 0) -> int:
+        """vdf_window_class_layout_device: the class-major seeds (d_zero 0; 36 dwords each) or rows (72 dwords each) of a set into the device
+        buffer d_out - what align_class_layout_kernel writes for the seeded flipped alignment.  -> the number of rows written."""
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_window_class_layout_device(self.ctx, d_hashes or None, d_zero or None, d_first or None, int(n_videos), d_skip or None,
+                                                            _align_uint32("min_run", min_run), d_out or None, int(capacity_rows), C.byref(n), stream or None))
+        return int(n.value)
+
+    # --------------------------------------------- the flipped alignment seeded and on a list of triples (include/vdf.h, DESIGN.md 4.14)
+    def align_seed_pairs_variants(self, a_hashes, a_first, a_zero=None, b_hashes=None, b_first=None, b_zero=None, tol_int: int = 350, min_run: int = 1,
+                                  variant_mask: int = 2, a_skip=None, b_skip=None, capacity: int = 1024):
+        """The candidate pairs of align_windows_variants under every variant of variant_mask, from ONE pass over the seeds
+        (vdf_align_seed_pairs_variants).  -> (triples [min(found, capacity)] of VIDEO_PAIR_VARIANT_DTYPE in (variant, a, b) order, found)."""
+        keep, args = _align_variants_host_args(a_hashes, a_zero, a_first, b_hashes, b_zero, b_first, a_skip, b_skip)  # keep: holds the arrays alive
+        out = np.zeros(max(int(capacity), 0), VIDEO_PAIR_VARIANT_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_seed_pairs_variants(self.ctx, *args, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                                           _variant_mask(variant_mask), out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_seed_pairs_variants_device(self, d_a_hashes: int, d_a_first: int, n_a: int, d_a_zero: int = 0, d_b_hashes: int = 0, d_b_first: int = 0,
+                                         n_b: int = 0, d_b_zero: int = 0, tol_int: int = 350, min_run: int = 1, variant_mask: int = 2, d_a_skip: int = 0,
+                                         d_b_skip: int = 0, capacity: int = 1024, stream: int = 0):
+        """The same on device arrays (d_b_hashes 0: self mode); the triples come back to the host, the call waits for its own work."""
+        out = np.zeros(max(int(capacity), 0), VIDEO_PAIR_VARIANT_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_seed_pairs_variants_device(self.ctx, d_a_hashes or None, d_a_zero or None, d_a_first or None, int(n_a),
+                                                                  d_a_skip or None, d_b_hashes or None, d_b_zero or None, d_b_first or None, int(n_b),
+                                                                  d_b_skip or None, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                                                  _variant_mask(variant_mask), out.ctypes.data if out.size else None, out.size,
+                                                                  C.byref(n), stream or None))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_variants_pairs(self, a_hashes, a_first, triples, a_zero=None, b_hashes=None, b_first=None, b_zero=None, tol_int: int = 350,
+                                     min_run: int = 1, a_skip=None, b_skip=None, capacity: int = 1024):
+        """align_windows_variants on the listed (variant, a, b) triples only (vdf_align_windows_variants_pairs): VIDEO_PAIR_VARIANT_DTYPE records
+        or [n, 3] integers, strictly increasing.  The records are align_windows_variants' for those triples, field for field."""
+        keep, args = _align_variants_host_args(a_hashes, a_zero, a_first, b_hashes, b_zero, b_first, a_skip, b_skip)  # keep: holds the arrays alive
+        t = video_pair_variants(triples)
+        out = np.zeros(max(int(capacity), 0), ALIGN_VARIANT_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_variants_pairs(self.ctx, *args, t.ctypes.data if t.size else None, t.size, _align_uint32("tol_int", tol_int),
+                                                              _align_uint32("min_run", min_run), out.ctypes.data if out.size else None, out.size,
+                                                              C.byref(n)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_variants_pairs_device(self, d_a_hashes: int, d_a_first: int, n_a: int, triples, d_a_zero: int = 0, d_b_hashes: int = 0,
+                                            d_b_first: int = 0, n_b: int = 0, d_b_zero: int = 0, tol_int: int = 350, min_run: int = 1, d_a_skip: int = 0,
+                                            d_b_skip: int = 0, capacity: int = 1024, stream: int = 0):
+        """The same on device arrays (the triple list stays a host array)."""
+        t = video_pair_variants(triples)
+        out = np.zeros(max(int(capacity), 0), ALIGN_VARIANT_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_variants_pairs_device(self.ctx, d_a_hashes or None, d_a_zero or None, d_a_first or None, int(n_a),
+                                                                     d_a_skip or None, d_b_hashes or None, d_b_zero or None, d_b_first or None, int(n_b),
+                                                                     d_b_skip or None, t.ctypes.data if t.size else None, t.size,
+                                                                     _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                                                     out.ctypes.data if out.size else None, out.size, C.byref(n), stream or None))
         return out[:min(n.value, out.size)], int(n.value)
 
     # --------------------------------------------- seeded candidate pairs, the align calls on a list of pairs (include/vdf.h, DESIGN.md 4.13)

@@ -573,6 +573,115 @@ public:
         }
     }
 
+    // The arrays of the two calls below, as align_windows_variants builds its own: hashes, zero planes of the flipped side, first arrays, skip bytes.
+    struct AlignVariantSides {
+        std::vector<uint64_t> wa, wb, za, zb;
+        std::vector<uint32_t> fa, fb;
+        const uint8_t *ska = nullptr, *skb = nullptr;
+        size_t n_a = 0, n_b = 0;
+        bool two_sets = false;
+        uint64_t cells = 0;
+        AlignVariantSides(const char *what, const std::vector<std::vector<VideoHash>> &windows_a, const std::vector<std::vector<VideoHash>> *windows_b,
+                          const std::vector<uint8_t> *skip_a, const std::vector<uint8_t> *skip_b)
+        {
+            auto csr = [what](const std::vector<std::vector<VideoHash>> &w, std::vector<uint64_t> &words, std::vector<uint64_t> *zero, std::vector<uint32_t> &first) {
+                first.assign(1, 0u);
+                for (const auto &video : w) {
+                    for (const VideoHash &h : video) {
+                        words.insert(words.end(), h.words().begin(), h.words().end());
+                        if (zero) {
+                            if (!h.zero()) throw Error::vid_proc(std::string(what) + " needs the zero plane of every hash of the flipped side (hash_windows_planes)");
+                            zero->insert(zero->end(), h.zero()->begin(), h.zero()->end());
+                        }
+                    }
+                    first.push_back((uint32_t)(words.size() / VDF_HASH_WORDS));
+                }
+                if (words.empty()) words.push_back(0);  // a non-null pointer for an empty side
+                if (zero && zero->empty()) zero->push_back(0);
+            };
+            two_sets = windows_b != nullptr;
+            csr(windows_a, wa, two_sets ? nullptr : &za, fa);
+            if (two_sets) csr(*windows_b, wb, &zb, fb);
+            if (skip_a && skip_a->size() != fa.back()) throw std::invalid_argument("one skip byte per window of A");
+            if (two_sets && skip_b && skip_b->size() != fb.back()) throw std::invalid_argument("one skip byte per window of B");
+            ska = skip_a && !skip_a->empty() ? skip_a->data() : nullptr;
+            skb = two_sets && skip_b && !skip_b->empty() ? skip_b->data() : nullptr;
+            n_a = windows_a.size();
+            n_b = two_sets ? windows_b->size() : 0;
+            cells = (uint64_t)fa.back() * (two_sets ? fb.back() : fa.back());
+        }
+        const uint64_t *a_zero() const { return two_sets ? nullptr : za.data(); }
+        const uint64_t *b_words() const { return two_sets ? wb.data() : nullptr; }
+        const uint64_t *b_zero() const { return two_sets ? zb.data() : nullptr; }
+    };
+
+    // Which pairs of videos can share a FLIPPED stretch at all (vdf_align_seed_pairs_variants): align_windows_variants' arguments;
+    // the (variant, a, b) triples, in that order, that are candidates of align_seed_pairs on (A, the flipped B) - every triple
+    // align_windows_variants has a record for is among them, and on a context all flips come from one pass over the seeds.
+    static std::vector<vdf_video_pair_variant> align_seed_pairs_variants(const std::vector<std::vector<VideoHash>> &windows_a,
+                                                                         const std::vector<std::vector<VideoHash>> *windows_b, uint32_t tol_int,
+                                                                         const std::vector<uint32_t> &flips, uint32_t min_run = 1,
+                                                                         const std::vector<uint8_t> *skip_a = nullptr, const std::vector<uint8_t> *skip_b = nullptr,
+                                                                         Context *ctx_opt = nullptr)
+    {
+        uint32_t mask = 0;
+        for (uint32_t f : flips) {
+            if (f < 1 || f > 7) throw std::invalid_argument("flips are non-empty combinations of FlipX, FlipY, FlipT");
+            mask |= 1u << f;
+        }
+        const AlignVariantSides s("align_seed_pairs_variants", windows_a, windows_b, skip_a, skip_b);
+        std::vector<vdf_video_pair_variant> out(1024);
+        for (;;) {
+            size_t found = 0;
+            int rc;
+            if (!ctx_opt && s.cells * flips.size() <= (1u << 16))
+                rc = vdf_align_seed_pairs_variants_host(s.wa.data(), s.a_zero(), s.fa.data(), s.n_a, s.ska, s.b_words(), s.b_zero(), s.fb.data(), s.n_b, s.skb, tol_int,
+                                                        min_run, mask, out.data(), out.size(), &found);
+            else {
+                Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+                rc = vdf_align_seed_pairs_variants(ctx.get(), s.wa.data(), s.a_zero(), s.fa.data(), s.n_a, s.ska, s.b_words(), s.b_zero(), s.fb.data(), s.n_b, s.skb,
+                                                   tol_int, min_run, mask, out.data(), out.size(), &found);
+                if (rc != VDF_OK && rc != VDF_E_INVAL) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            }
+            if (rc != VDF_OK)
+                throw std::invalid_argument("align_seed_pairs_variants: min_run of 0, a video of more than 2^20 windows, more than 2^24 pairs, or a multi-GPU context");
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
+    // align_windows_variants on the listed (variant, a, b) triples only (vdf_align_windows_variants_pairs): strictly increasing in (variant, a, b),
+    // every variant 1 ... 7, a < b when windows_b is null.  The records are align_windows_variants' for those triples, field for field - with
+    // align_seed_pairs_variants' list, all of them.
+    static std::vector<vdf_alignment_variant> align_windows_variants_pairs(const std::vector<std::vector<VideoHash>> &windows_a,
+                                                                           const std::vector<std::vector<VideoHash>> *windows_b,
+                                                                           const std::vector<vdf_video_pair_variant> &triples, uint32_t tol_int,
+                                                                           uint32_t min_run = 1, const std::vector<uint8_t> *skip_a = nullptr,
+                                                                           const std::vector<uint8_t> *skip_b = nullptr, Context *ctx_opt = nullptr)
+    {
+        const AlignVariantSides s("align_windows_variants_pairs", windows_a, windows_b, skip_a, skip_b);
+        const vdf_video_pair_variant *list = triples.empty() ? nullptr : triples.data();
+        std::vector<vdf_alignment_variant> out(1024);
+        for (;;) {
+            size_t found = 0;
+            int rc;
+            if (!ctx_opt && s.cells * 7 <= (1u << 16))
+                rc = vdf_align_windows_variants_pairs_host(s.wa.data(), s.a_zero(), s.fa.data(), s.n_a, s.ska, s.b_words(), s.b_zero(), s.fb.data(), s.n_b, s.skb, list,
+                                                           triples.size(), tol_int, min_run, out.data(), out.size(), &found);
+            else {
+                Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+                rc = vdf_align_windows_variants_pairs(ctx.get(), s.wa.data(), s.a_zero(), s.fa.data(), s.n_a, s.ska, s.b_words(), s.b_zero(), s.fb.data(), s.n_b, s.skb,
+                                                      list, triples.size(), tol_int, min_run, out.data(), out.size(), &found);
+                if (rc != VDF_OK && rc != VDF_E_INVAL) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            }
+            if (rc != VDF_OK)
+                throw std::invalid_argument("align_windows_variants_pairs: a list that is not strictly increasing in (variant, a, b) or names a variant or a video that "
+                                            "does not exist, min_run of 0, a video of more than 2^20 windows, more than 2^24 triples, or a multi-GPU context");
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);
+        }
+    }
+
     // from_frame_stacks with the zero planes (vdf_hash_clips_u8_planes): the hashes are the same words and can be flipped.  crops (optional, one
     // l, r, t, b per clip - e.g. what from_frame_stacks_letterbox detected): hash, plane and every flip are those of the CROPPED clip.
     static std::vector<VideoHash> from_frame_stacks_planes(const std::vector<FrameStack> &stacks, const std::vector<std::array<uint32_t, 4>> *crops = nullptr,
