@@ -223,7 +223,8 @@ int vdf_hash_frames_u8_letterbox(vdf_ctx *ctx, const uint8_t *frames, size_t n_c
  * checks in the same order (a null out_zero is among the null pointers), then an axis size whose resize table is not its own mirror image ->
  * VDF_E_BAD_DIMS, and a multi-GPU context last -> VDF_E_INVAL.  Same resize runs and routes; out_hashes and out_dontcare are bit-identical to
  * the plain calls'.  With the planes, vdf_window_variants_* and vdf_align_windows_variants* see flipped and reversed stretches.
- * Not here: zero planes of window hashes from the two plain calls (the _planes forms write them), letterbox boxes and mixed frame sizes. */
+ * Not here: zero planes of window hashes from the two plain calls (the _planes forms write them).  Videos of different frame sizes and
+ * lengths, with crop boxes if they have any, in one call: vdf_hash_windows_clips_u8* below. */
 size_t vdf_hash_window_count(uint32_t frames_per_clip, uint32_t window_stride); /* 0 if frames_per_clip < 16 or window_stride == 0 */
 int vdf_hash_windows_u8(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w,
                         uint32_t h, size_t frame_stride, size_t clip_stride, uint32_t window_stride, uint64_t *out_hashes,
@@ -580,6 +581,38 @@ int vdf_hash_clips_u8_letterbox_device(vdf_ctx *ctx, const uint8_t *d_buf, size_
                                        uint32_t *out_crops, void *stream);
 int vdf_hash_clips_u8_letterbox(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips,
                                 uint32_t frames_per_clip, uint64_t *out_hashes, uint32_t *out_crops, uint32_t *out_dontcare);
+
+/* ---- every 16-frame window of videos of DIFFERENT frame sizes and lengths in one call ----------------
+ * The producer of what the align calls read.  n_videos videos in ONE buffer, each with its own vdf_clip descriptor (size,
+ * frame stride, optional crop box, read in place) and its own frame count n_frames[i] (HOST array).  Window k of video i is frames
+ * [k * window_stride, k * window_stride + 16) of that video inside its box; with first[] = the prefix sums of
+ * vdf_hash_window_count(n_frames[i], window_stride) (vdf_hash_windows_clips_first) its hash goes to out_hashes + 16 (first[i] + k), its
+ * don't-care count to out_dontcare[first[i] + k] (nullable) and, in the _planes forms, its zero plane to out_zero + 16 (first[i] + k)
+ * (required there) - whatever order the kernels take the videos in.  The words are the words vdf_hash_windows_u8* gives for each video alone
+ * (on a contiguous cropped copy, if it has a box).
+ * vdf_hash_windows_clips_first: host only, no context; first has n_videos + 1 entries, the caller sizes its buffers by first[n_videos].
+ * A null pointer, window_stride == 0 or 2^32 windows or more -> VDF_E_INVAL; an n_frames below 16 -> VDF_E_NOT_ENOUGH_FRAMES.
+ * Errors of the hash calls, checked over all videos on the host before anything is queued (a rejected call launches nothing), in this order,
+ * each message naming the first offending video: n_frames < 16 -> VDF_E_NOT_ENOUGH_FRAMES; a zero dimension -> VDF_E_BAD_DIMS;
+ * frame_stride < w*h -> VDF_E_INVAL; a box that leaves no pixels -> VDF_E_INVAL; offset + (n_frames - 1)*frame_stride + w*h > buf_bytes ->
+ * VDF_E_INVAL; window_stride == 0 -> VDF_E_INVAL; an n_frames within 64 of 2^32 -> VDF_E_INVAL; 2^32 windows or more in the call ->
+ * VDF_E_INVAL; (n_videos == 0: VDF_OK, nothing is launched;) a null pointer -> VDF_E_INVAL (a null clips or n_frames array with n_videos > 0 is
+ * reported before everything else: there is nothing to check the videos by); a box size whose coefficients do not fit the i8 split ->
+ * VDF_E_BAD_DIMS; _planes forms: an axis size whose resize table is not its own mirror image -> VDF_E_BAD_DIMS; a multi-GPU context ->
+ * VDF_E_INVAL, last.
+ * Videos that all share (w, h, frame_stride, n_frames), have no box and sit at offsets one positive step apart take exactly the route of
+ * vdf_hash_windows_u8[_planes]_device with clip_stride = that step.  The host forms upload the buffer in one piece.  The device forms are
+ * ordered on `stream`; clips and n_frames are HOST arrays, and the call returns once the descriptors have left the host. */
+int vdf_hash_windows_clips_first(const uint32_t *n_frames, size_t n_videos, uint32_t window_stride, uint32_t *first);
+int vdf_hash_windows_clips_u8(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames,
+                              size_t n_videos, uint32_t window_stride, uint64_t *out_hashes, uint32_t *out_dontcare);
+int vdf_hash_windows_clips_u8_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames,
+                                     size_t n_videos, uint32_t window_stride, uint64_t *d_out_hashes, uint32_t *d_out_dontcare, void *stream);
+int vdf_hash_windows_clips_u8_planes(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames,
+                                     size_t n_videos, uint32_t window_stride, uint64_t *out_hashes, uint32_t *out_dontcare, uint64_t *out_zero);
+int vdf_hash_windows_clips_u8_planes_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips,
+                                            const uint32_t *n_frames, size_t n_videos, uint32_t window_stride, uint64_t *d_out_hashes,
+                                            uint32_t *d_out_dontcare, uint64_t *d_out_zero, void *stream);
 
 /* ---- mirrored, flipped and reversed duplicates from ONE hash pass -------------------------------------
  * The reference cannot see through a horizontal mirror or a flip (vid_dup_finder_lib/src/lib.rs:102-111).  Here the hash of the

@@ -171,6 +171,15 @@ SIGNATURES = {
                                              C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vdf_hash_windows_u8_planes_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                                     C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (ctx, buf, buf_bytes, clips, n_frames, n_videos, window_stride, out_hashes, out_dontcare [, out_zero] [, stream])
+    "vdf_hash_windows_clips_first": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
+    "vdf_hash_windows_clips_u8": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vdf_hash_windows_clips_u8_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]),
+    "vdf_hash_windows_clips_u8_planes": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]),
+    "vdf_hash_windows_clips_u8_planes_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "vdf_window_variants_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vdf_window_variants_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),

@@ -496,15 +496,50 @@ def hash_frame_stacks(frames: np.ndarray, src_paths: Sequence, durations: Sequen
     return [VideoHash(words[i], src_paths[i], durations[i]) for i in range(len(words))]
 
 
+def _hash_frame_windows_mixed(stacks, src_paths, durations, stride, engine, zero_plane, crops, letterbox) -> List[List[VideoHash]]:
+    """hash_frame_windows on a list of stacks: one Engine.hash_windows_clips[_planes] call, cut into per-video lists at first[]."""
+    if crops is not None and letterbox:
+        raise ValueError("crops and letterbox=True are two sources of the same boxes")
+    eng = engine or default_engine()
+    stacks = list(stacks)
+
+    def call():
+        boxes = None
+        if crops is not None:
+            if len(crops) != len(stacks):
+                raise ValueError("a Crop per video")
+            boxes = np.stack([c.as_abi() if isinstance(c, Crop) else np.asarray(c, np.uint32).reshape(4) for c in crops]).reshape(-1, 4) if len(stacks) else None
+        elif letterbox and stacks:  # the boxes of frames 0 and 8 of every video, by the mixed letterbox call (which hashes frames 0 .. 15 beside them)
+            boxes = eng.hash_clips_letterbox(stacks)[1]
+        if zero_plane:
+            words, zero, first = eng.hash_windows_clips_planes(stacks, stride, crops=boxes)
+        else:
+            (words, first), zero = eng.hash_windows_clips(stacks, stride, crops=boxes), None
+        return words, zero, first
+
+    words, zero, first = _with_planes(call)
+    return [[VideoHash(words[r], src_paths[i], durations[i], None if zero is None else zero[r]) for r in range(int(first[i]), int(first[i + 1]))]
+            for i in range(len(stacks))]
+
+
 def hash_frame_windows(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int], stride: int = 1,
-                       engine: Optional[Engine] = None, zero_plane: bool = False) -> List[List[VideoHash]]:
+                       engine: Optional[Engine] = None, zero_plane: bool = False, crops: Optional[Sequence] = None,
+                       letterbox: bool = False) -> List[List[VideoHash]]:
     """Every 16-frame window of every video (Engine.hash_windows): frames [n_videos, n_frames >= 16, H, W] u8 -> per video the VideoHash of
     frames [k * stride, k * stride + 16) for k = 0 .. (n_frames - 16) // stride, each carrying the video's src_paths[i] and durations[i].
     What finds a duplicate that is shifted in time (`locate`); the reference hashes one 16-frame stack per file (definitions.rs:31-34).
     zero_plane: every window's hash also carries its zero plane (VideoHash.zero; Engine.hash_windows_planes), which align_flipped needs;
-    the hash words are the same."""
+    the hash words are the same.
+    frames may also be a LIST of [F_i >= 16, H_i, W_i] stacks of different frame sizes AND lengths, as a library's files are: they are hashed
+    by one call (Engine.hash_windows_clips[_planes]) and the per-video lists differ in length.  List input only: crops = a Crop (or four
+    edge offsets l, r, t, b) per video, read in place; letterbox=True detects every video's box on its frames 0 and 8 (Engine.hash_clips_letterbox,
+    as gen_hashes does) and hashes the windows inside it."""
     if len(src_paths) < len(frames) or len(durations) < len(frames):
         raise ValueError("a path and a duration per video")
+    if isinstance(frames, (list, tuple)):
+        return _hash_frame_windows_mixed(frames, src_paths, durations, stride, engine, zero_plane, crops, letterbox)
+    if crops is not None or letterbox:
+        raise ValueError("crops and letterbox take a list of stacks")
     if zero_plane:
         eng = engine or default_engine()
         words, zero = _with_planes(lambda: eng.hash_windows_planes(frames, stride))

@@ -2724,6 +2724,206 @@ int vdf_hash_windows_u8_planes(vdf_ctx *ctx, const uint8_t *frames, size_t n_cli
     return VDF_OK;
 }
 
+// ---- window hashes of videos of different sizes and lengths in one call (include/vdf.h: vdf_hash_windows_clips_u8*) -----------
+int vdf_hash_windows_clips_first(const uint32_t *n_frames, size_t n_videos, uint32_t window_stride, uint32_t *first)
+{
+    if (!first || (n_videos && !n_frames) || window_stride == 0 || n_videos >= 0xFFFFFFFFull) return VDF_E_INVAL;
+    for (size_t i = 0; i < n_videos; i++)
+        if (n_frames[i] < VDF_DCT_SIZE) return VDF_E_NOT_ENOUGH_FRAMES;
+    return vdf::windows_first(n_frames, n_videos, window_stride, first) ? VDF_OK : VDF_E_INVAL;
+}
+
+// does the table of one box axis fit the i8 split?  A single-device context fetches it (it is about to be used); a multi-GPU context - refused
+// last, after this check - asks the host-side builder and touches no device.
+static int windows_clips_table_fits(vdf_ctx *ctx, uint32_t size, int layout, hipStream_t stream, bool *fits)
+{
+    if (!ctx->subs.empty()) {
+        vdf::MfmaAxisTable t;
+        *fits = vdf::build_mfma_axis_table(size, layout, t) && t.ok;
+        return VDF_OK;
+    }
+    int rc = VDF_OK;
+    const DeviceMfmaTable *t = mfma_table(ctx, size, layout, stream, &rc);
+    if (rc) return rc;
+    *fits = t->host.ok;
+    return VDF_OK;
+}
+
+// The argument checks of the mixed windows calls over ALL videos, in the order their codes are reported; *run: there is something to hash.
+static int windows_clips_checks(vdf_ctx *ctx, const void *buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames, size_t n_videos,
+                                uint32_t window_stride, const void *out_hashes, const void *out_zero, bool planes, hipStream_t stream, bool *run)
+{
+    *run = false;
+    if (n_videos && (!clips || !n_frames)) return fail(ctx, VDF_E_INVAL, "null pointer");  // (nothing to check the videos by)
+    if (n_videos >= 0xFFFFFFFFull) return fail(ctx, VDF_E_INVAL, "more than 2^32 - 2 videos in one call");
+    const vdf::MixedClip *mc = reinterpret_cast<const vdf::MixedClip *>(clips);
+    const vdf::WindowsMixedCheck chk = vdf::check_windows_mixed(mc, n_frames, n_videos, window_stride, buf_bytes);
+    const std::string at = " (video " + std::to_string(chk.video) + ")";
+    switch (chk.error) {
+    case vdf::WindowsMixedError::kNotEnoughFrames: return fail(ctx, VDF_E_NOT_ENOUGH_FRAMES, "fewer than 16 frames" + at);
+    case vdf::WindowsMixedError::kZeroDim: return fail(ctx, VDF_E_BAD_DIMS, "zero frame dimension" + at);
+    case vdf::WindowsMixedError::kStrideBelowFrame: return fail(ctx, VDF_E_INVAL, "frame_stride smaller than a frame" + at);
+    case vdf::WindowsMixedError::kEmptyBox: return fail(ctx, VDF_E_INVAL, "crop box leaves no pixels" + at);
+    case vdf::WindowsMixedError::kOutOfBuffer: return fail(ctx, VDF_E_INVAL, "video reaches past the end of the buffer" + at);
+    case vdf::WindowsMixedError::kZeroWindowStride: return fail(ctx, VDF_E_INVAL, "window_stride of zero");
+    case vdf::WindowsMixedError::kFrameCount: return fail(ctx, VDF_E_INVAL, "frame count within 64 of 2^32" + at);
+    case vdf::WindowsMixedError::kTooManyWindows: return fail(ctx, VDF_E_INVAL, "2^32 windows or more in one call" + at);
+    case vdf::WindowsMixedError::kNone: break;
+    }
+    if (n_videos == 0) return VDF_OK;
+    if (!buf || !out_hashes || (planes && !out_zero)) return fail(ctx, VDF_E_INVAL, "null pointer");
+    for (size_t i = 0; i < n_videos; i++) {  // the BOX is what is resized (check_windows_mixed: it leaves pixels)
+        const uint32_t bw = clips[i].w - clips[i].crop_left - clips[i].crop_right, bh = clips[i].h - clips[i].crop_top - clips[i].crop_bottom;
+        const int layout_v = vdf::windows_mixed_part_of(clips[i].w) == vdf::MixedPart::kWideLines ? vdf::kMfmaLayoutVerticalWide : vdf::kMfmaLayoutVertical;
+        bool fits_h = false, fits_v = false;
+        if (int rc = windows_clips_table_fits(ctx, bw, vdf::kMfmaLayoutHorizontal, stream, &fits_h)) return rc;
+        if (int rc = windows_clips_table_fits(ctx, bh, layout_v, stream, &fits_v)) return rc;
+        if (!fits_h || !fits_v) return fail(ctx, VDF_E_BAD_DIMS, "box size whose coefficients do not fit the i8 split (video " + std::to_string(i) + ")");
+    }
+    if (planes)
+        for (size_t i = 0; i < n_videos; i++) {
+            if (int rc = planes_axis_ok(ctx, clips[i].w - clips[i].crop_left - clips[i].crop_right)) return rc;
+            if (int rc = planes_axis_ok(ctx, clips[i].h - clips[i].crop_top - clips[i].crop_bottom)) return rc;
+        }
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "the windows calls take a single-device context");
+    *run = true;
+    return VDF_OK;
+}
+
+// windows_clips_checks has passed.  Uniform input: the uniform call.  Otherwise descriptors, table entries, the videos' records and the segment
+// table go up in ONE copy through the pinned staging, the mixed whole-line kernels write every pseudo-clip's 16 x 16 frames to `small`, and
+// dct_hash_windows_mixed_kernel hashes the windows from there to the rows first[i] + k.
+static int hash_windows_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames, size_t n_videos,
+                                     uint32_t window_stride, uint64_t *d_out, uint32_t *d_dc, hipStream_t stream, uint64_t *d_zero)
+{
+    const vdf::MixedClip *mc = reinterpret_cast<const vdf::MixedClip *>(clips);
+    const vdf::WindowsMixedPlan plan = vdf::plan_windows_mixed(mc, n_frames, n_videos, window_stride);
+    if (plan.kind == vdf::WindowsMixedPlan::kUniform)
+        return hash_windows_locked(ctx, d_buf + plan.offset0, n_videos, n_frames[0], mc[0].w, mc[0].h, (size_t)mc[0].frame_stride, (size_t)plan.clip_stride,
+                                   window_stride, d_out, d_dc, stream, d_zero);
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_cos_table(ctx, stream);
+    if (rc) return rc;
+    const auto pad64 = [](size_t b) { return (b + 63) & ~size_t(63); };
+    const size_t n_desc = plan.descs.size(), max_entries = 2 * ((size_t)plan.max_w + plan.max_h + 2);
+    const size_t off_tab = pad64(n_desc * sizeof(vdf::MixedClipDesc)), off_vid = off_tab + pad64(max_entries * sizeof(vdf::CropTableEntry)),
+                 off_seg = off_vid + pad64(n_videos * sizeof(vdf::WindowsVideoRecord)), blob = off_seg + pad64((n_videos + 1) * sizeof(uint32_t));
+    if (!ctx->pin_desc.reserve(blob)) return fail(ctx, VDF_E_OOM, "host staging for the video descriptors");
+    char *stage = ctx->pin_desc.as<char>();
+    vdf::MixedClipDesc *dsc = reinterpret_cast<vdf::MixedClipDesc *>(stage);
+    vdf::CropTableEntry *ent = reinterpret_cast<vdf::CropTableEntry *>(stage + off_tab);
+    // two sets, as hash_mixed_launch: the wide-line part reads its vertical tables in another k order
+    LaunchTables plain(plan.max_w, plan.max_h, vdf::kMfmaLayoutHorizontal, vdf::kMfmaLayoutVertical), wide(plan.max_w, plan.max_h, vdf::kMfmaLayoutHorizontal, vdf::kMfmaLayoutVerticalWide);
+    for (const vdf::MixedLaunch &l : plan.launches) {
+        LaunchTables &tabs = l.part == vdf::MixedPart::kWideLines ? wide : plain;
+        for (size_t i = l.first; i < l.first + l.count; i++) {
+            vdf::MixedClipDesc d = plan.descs[i];
+            const int32_t ih = tabs.entry(ctx, d.bw, false, stream, &rc), iv = ih < 0 ? -1 : tabs.entry(ctx, d.bh, true, stream, &rc);
+            if (iv < 0) return rc ? rc : fail(ctx, VDF_E_BAD_DIMS, "box size whose coefficients do not fit the i8 split (video " + std::to_string(d.out_index) + ")");
+            d.h_table = (uint32_t)ih; d.v_table = (uint32_t)iv;
+            dsc[i] = d;
+        }
+    }
+    const size_t n_plain = plain.used.size(), n_entries = n_plain + wide.used.size();
+    if (n_entries > max_entries) return fail(ctx, VDF_E_INVAL, "table index of a mixed windows call outgrew its staging");  // (cannot happen: one entry per size and axis)
+    for (size_t i = 0; i < n_plain; i++) ent[i] = plain.crop_entry(i);
+    for (size_t i = n_plain; i < n_entries; i++) ent[i] = wide.crop_entry(i - n_plain);
+    for (const vdf::MixedLaunch &l : plan.launches)
+        for (size_t i = l.first; i < l.first + l.count; i++) {
+            if (l.part == vdf::MixedPart::kWideLines) { dsc[i].h_table += (uint32_t)n_plain; dsc[i].v_table += (uint32_t)n_plain; }
+            if (dsc[i].h_table >= n_entries || dsc[i].v_table >= n_entries) return fail(ctx, VDF_E_INVAL, "descriptor names a table that is not there");
+        }
+    std::memcpy(stage + off_vid, plan.videos.data(), n_videos * sizeof(vdf::WindowsVideoRecord));
+    std::memcpy(stage + off_seg, plan.seg_first.data(), (n_videos + 1) * sizeof(uint32_t));
+    VDF_HIP(ctx, ctx->small.reserve(std::max<size_t>(plan.small_bytes, 4096)));
+    if ((rc = upload(ctx, ctx->crop_desc2, stage, blob, stream))) return rc;
+    VDF_HIP(ctx, hipEventRecord(ctx->ev_mid, stream));
+    const char *d_blob = ctx->crop_desc2.as<char>();
+    const vdf::MixedClipDesc *d_desc = reinterpret_cast<const vdf::MixedClipDesc *>(d_blob);
+    const vdf::CropTableEntry *d_tab = reinterpret_cast<const vdf::CropTableEntry *>(d_blob + off_tab);
+    uint8_t *small = ctx->small.as<uint8_t>();
+    hipError_t e = hipSuccess;
+    for (const vdf::MixedLaunch &l : plan.launches) {
+        if (e != hipSuccess) break;
+        e = vdf::launch_mixed_frames(d_buf, d_buf + buf_bytes, d_desc + l.first, l.count, d_tab, l.part == vdf::MixedPart::kWideLines, small + l.first * 4096, stream);
+    }
+    if (e == hipSuccess)
+        e = vdf::launch_dct_hash_windows_mixed(small, reinterpret_cast<const vdf::WindowsVideoRecord *>(d_blob + off_vid), reinterpret_cast<const uint32_t *>(d_blob + off_seg),
+                                               (uint32_t)n_videos, plan.seg_first[n_videos], window_stride, plan.per_seg, ctx->cos_table.as<double>(), d_out, d_dc,
+                                               stream, d_zero);
+    // the staging is read by the copy: it must have run before the next call on this context rewrites it (the kernels stay queued)
+    const hipError_t ew = hipEventSynchronize(ctx->ev_mid);
+    if (e != hipSuccess) return fail_hip(ctx, e, "mixed windows launch");
+    VDF_HIP(ctx, ew);
+    return VDF_OK;
+}
+
+static int hash_windows_clips_device_impl(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames, size_t n_videos,
+                                          uint32_t window_stride, uint64_t *d_out_hashes, uint32_t *d_out_dontcare, uint64_t *d_out_zero, bool planes,
+                                          void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    bool run;
+    if (int rc = windows_clips_checks(ctx, d_buf, buf_bytes, clips, n_frames, n_videos, window_stride, d_out_hashes, d_out_zero, planes, s, &run)) return rc;
+    if (!run) return VDF_OK;
+    return hash_windows_clips_locked(ctx, d_buf, buf_bytes, clips, n_frames, n_videos, window_stride, d_out_hashes, d_out_dontcare, s, planes ? d_out_zero : nullptr);
+}
+
+// Host arrays: the buffer goes up through the context's staging buffer in one piece, the device form runs on it, the results come down.
+static int hash_windows_clips_host_impl(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames, size_t n_videos,
+                                        uint32_t window_stride, uint64_t *out_hashes, uint32_t *out_dontcare, uint64_t *out_zero, bool planes)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    bool run;
+    if (int rc = windows_clips_checks(ctx, buf, buf_bytes, clips, n_frames, n_videos, window_stride, out_hashes, out_zero, planes, ctx->stream, &run)) return rc;
+    if (!run) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    size_t n_out = 0;
+    for (size_t i = 0; i < n_videos; i++) n_out += vdf::window_count(n_frames[i], window_stride);
+    const size_t hash_bytes = n_out * VDF_HASH_WORDS * sizeof(uint64_t);
+    if (int rc = upload(ctx, ctx->frames, buf, buf_bytes, ctx->stream)) return rc;
+    VDF_HIP(ctx, ctx->out_hashes.reserve(hash_bytes));
+    if (planes) VDF_HIP(ctx, ctx->out_zero.reserve(hash_bytes));
+    if (out_dontcare) VDF_HIP(ctx, ctx->out_dc.reserve(n_out * sizeof(uint32_t)));
+    uint32_t *d_dc = out_dontcare ? ctx->out_dc.as<uint32_t>() : nullptr;
+    if (int rc = hash_windows_clips_locked(ctx, ctx->frames.as<uint8_t>(), buf_bytes, clips, n_frames, n_videos, window_stride, ctx->out_hashes.as<uint64_t>(), d_dc,
+                                           ctx->stream, planes ? ctx->out_zero.as<uint64_t>() : nullptr))
+        return rc;
+    VDF_HIP(ctx, hipMemcpyAsync(out_hashes, ctx->out_hashes.p, hash_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (planes) VDF_HIP(ctx, hipMemcpyAsync(out_zero, ctx->out_zero.p, hash_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_dontcare) VDF_HIP(ctx, hipMemcpyAsync(out_dontcare, d_dc, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VDF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VDF_OK;
+}
+
+int vdf_hash_windows_clips_u8_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames, size_t n_videos,
+                                     uint32_t window_stride, uint64_t *d_out_hashes, uint32_t *d_out_dontcare, void *stream)
+{
+    return hash_windows_clips_device_impl(ctx, d_buf, buf_bytes, clips, n_frames, n_videos, window_stride, d_out_hashes, d_out_dontcare, nullptr, false, stream);
+}
+
+int vdf_hash_windows_clips_u8(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames, size_t n_videos,
+                              uint32_t window_stride, uint64_t *out_hashes, uint32_t *out_dontcare)
+{
+    return hash_windows_clips_host_impl(ctx, buf, buf_bytes, clips, n_frames, n_videos, window_stride, out_hashes, out_dontcare, nullptr, false);
+}
+
+int vdf_hash_windows_clips_u8_planes_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames,
+                                            size_t n_videos, uint32_t window_stride, uint64_t *d_out_hashes, uint32_t *d_out_dontcare, uint64_t *d_out_zero,
+                                            void *stream)
+{
+    return hash_windows_clips_device_impl(ctx, d_buf, buf_bytes, clips, n_frames, n_videos, window_stride, d_out_hashes, d_out_dontcare, d_out_zero, true, stream);
+}
+
+int vdf_hash_windows_clips_u8_planes(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames, size_t n_videos,
+                                     uint32_t window_stride, uint64_t *out_hashes, uint32_t *out_dontcare, uint64_t *out_zero)
+{
+    return hash_windows_clips_host_impl(ctx, buf, buf_bytes, clips, n_frames, n_videos, window_stride, out_hashes, out_dontcare, out_zero, true);
+}
+
 // the argument checks both window-variant forms share, in the order their messages are reported; first on the host (null: not checked here)
 static int window_variants_checks(vdf_ctx *ctx, const void *hashes, const void *zero, const void *first_ptr, const uint32_t *first, size_t n_videos,
                                   const void *skip, uint32_t variant, const void *out_hashes, const void *out_skip)

@@ -9,6 +9,7 @@
 #include "window_variant.h"
 #include "resize_dispatch.h"
 #include "windows_plan.h"
+#include "windows_mixed_plan.h"
 #include "align_plan.h"
 
 namespace vdf {
@@ -245,6 +246,12 @@ struct WindowsFrames {
 // out_zero (nullable): the kernel's PLANES form, the windows' zero planes at out_zero + 16 (c n_win + k); null: the plain form, as before
 hipError_t launch_dct_hash_windows(const WindowsFrames &f, size_t n_clips, const WindowsPlan &plan, const double *cos_table, uint64_t *out_hashes,
                                    uint32_t *out_dontcare, hipStream_t stream, uint64_t *out_zero = nullptr);
+// ---- window hashes of videos of different sizes and lengths (windows_mixed_plan.h) ---------------------------------------------
+// small: the 16 x 16 frames of every pseudo-clip of the plan, slot s at small + 4096 s; videos / seg_first: DEVICE copies of the plan's records and
+// of its segment table (n_videos + 1 entries); n_groups = seg_first[n_videos].  Window k of video i to row first[i] + k of the outputs.
+hipError_t launch_dct_hash_windows_mixed(const uint8_t *small, const WindowsVideoRecord *videos, const uint32_t *seg_first, uint32_t n_videos,
+                                         uint32_t n_groups, uint32_t stride, uint32_t per_seg, const double *cos_table, uint64_t *out_hashes,
+                                         uint32_t *out_dontcare, hipStream_t stream, uint64_t *out_zero = nullptr);
 // ---- the variant of a set of window hashes (window_variant.h) ------------------------------------------------------------------
 // rows [row0, row0 + n_rows) = [first[0], first[n_videos]) of out (and of out_skip, if skip is given) from hashes / zero / skip; variant 0 ... 7
 hipError_t launch_window_variants(const uint64_t *hashes, const uint64_t *zero, const uint32_t *first, uint32_t n_videos, const uint8_t *skip,

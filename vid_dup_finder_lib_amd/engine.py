@@ -66,6 +66,21 @@ def _window_stride(stride) -> int:
 ALIGN_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("offset", "<i4"), ("start_a", "<u4"), ("n_windows", "<u4"), ("dist_sum", "<u4")])
 
 
+def hash_windows_first(n_frames, stride: int = 1) -> np.ndarray:
+    """vdf_hash_windows_clips_first (host only, no context): first [n_videos + 1] u32 = the prefix sums of the videos' window counts - where
+    Engine.hash_windows_clips puts video i's windows (rows first[i] ... first[i + 1]) and what the align calls read beside the hashes.
+    VdfError: a video of fewer than 16 frames (VDF_E_NOT_ENOUGH_FRAMES), 2^32 windows or more (VDF_E_INVAL)."""
+    nf = np.asarray(n_frames).reshape(-1)
+    if nf.size and (np.any(nf != nf.astype(np.int64)) or int(nf.min()) < 0 or int(nf.max()) >= 2**32):
+        raise ValueError("frame counts must be integers in 0 .. 2^32 - 1")
+    nf = np.ascontiguousarray(nf, dtype=np.uint32)
+    first = np.zeros(nf.size + 1, np.uint32)
+    rc = _capi.load().vdf_hash_windows_clips_first(nf.ctypes.data if nf.size else None, nf.size, _window_stride(stride), first.ctypes.data)
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_hash_windows_clips_first: " + ("a video of fewer than 16 frames" if rc == _capi.VDF_E_NOT_ENOUGH_FRAMES else "2^32 windows or more"))
+    return first
+
+
 def _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip):
     """The host arrays of an align call as the C ABI takes them; b_hashes None = self mode.  Returns the arrays (to keep alive) and
     (a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip) as ctypes arguments."""
@@ -581,6 +596,84 @@ class Engine:
         cs = fs * frames_per_clip if clip_stride is None else clip_stride
         self._check(self.lib.vdf_hash_windows_u8_planes_device(self.ctx, d_frames, n_clips, frames_per_clip, w, h, fs, cs, stride, d_out,
                                                                d_dontcare or None, d_zero or None, stream or None))
+
+    # --------------------------------------------- windows of videos of different sizes and lengths (include/vdf.h)
+    @staticmethod
+    def _pack_videos(stacks: Sequence[np.ndarray], crops=None):
+        """ALL frames of every video one after the other in one buffer, every video on a 64-byte boundary: (buffer, CLIP_DTYPE records,
+        frame counts [n] u32)."""
+        stacks = [np.ascontiguousarray(s, dtype=np.uint8) for s in stacks]
+        n = len(stacks)
+        if any(s.ndim != 3 for s in stacks):
+            raise ValueError("every video must be [n_frames, H, W]")
+        clips = np.zeros(n, CLIP_DTYPE)
+        n_frames = np.array([s.shape[0] for s in stacks], np.uint32)
+        at = 0
+        for i, s in enumerate(stacks):
+            clips[i]["offset"], clips[i]["frame_stride"], clips[i]["w"], clips[i]["h"] = at, s.shape[1] * s.shape[2], s.shape[2], s.shape[1]
+            at += (s.size + 63) & ~63
+        buf = np.zeros(max(at, 1), np.uint8)
+        for i, s in enumerate(stacks):
+            buf[int(clips[i]["offset"]):int(clips[i]["offset"]) + s.size] = s.reshape(-1)
+        if crops is not None:
+            clips["crop"] = np.asarray(crops, dtype=np.uint32).reshape(n, 4)
+        return buf, clips, n_frames
+
+    def _hash_windows_clips(self, stacks, stride, crops, want_dontcare, planes):
+        stride = _window_stride(stride)
+        buf, clips, n_frames = self._pack_videos(stacks, crops)
+        n = len(clips)
+        # a video of fewer than 16 frames has no window: the library names it (first would not); the buffers are sized without it
+        first = hash_windows_first(np.maximum(n_frames, 16), stride)
+        rows = int(first[-1])
+        out = np.zeros((rows, HASH_WORDS), np.uint64)
+        zero = np.zeros((rows, HASH_WORDS), np.uint64) if planes else None
+        dc = np.zeros(rows, np.uint32) if want_dontcare else None
+        args = (self.ctx, buf.ctypes.data, buf.size, clips.ctypes.data if n else None, n_frames.ctypes.data if n else None, n, stride, out.ctypes.data,
+                dc.ctypes.data if want_dontcare else None)
+        if planes:
+            self._check(self.lib.vdf_hash_windows_clips_u8_planes(*args, zero.ctypes.data))
+        else:
+            self._check(self.lib.vdf_hash_windows_clips_u8(*args))
+        return out, zero, dc, first
+
+    def hash_windows_clips(self, stacks: Sequence[np.ndarray], stride: int = 1, crops=None, want_dontcare: bool = False):
+        """Every 16-frame window of videos of DIFFERENT frame sizes and lengths in one call (vdf_hash_windows_clips_u8): stacks = a list of
+        [F_i >= 16, H_i, W_i] u8 arrays; crops (optional) = [n, 4] u32 left, right, top, bottom per video, read in place.
+        -> (words [n_total, 16] u64, first [n + 1] u32 [, dontcare [n_total] u32]): video i's windows are rows first[i] ... first[i + 1], the
+        layout align_windows* reads.  The words are hash_windows' for each video alone."""
+        out, _, dc, first = self._hash_windows_clips(stacks, stride, crops, want_dontcare, False)
+        return (out, first, dc) if want_dontcare else (out, first)
+
+    def hash_windows_clips_planes(self, stacks: Sequence[np.ndarray], stride: int = 1, crops=None, want_dontcare: bool = False):
+        """hash_windows_clips plus every window's zero plane (vdf_hash_windows_clips_u8_planes): -> (words [n_total, 16], zero [n_total, 16],
+        first [n + 1] [, dontcare]).  Words and don't-care counts are the plain form's."""
+        out, zero, dc, first = self._hash_windows_clips(stacks, stride, crops, want_dontcare, True)
+        return (out, zero, first, dc) if want_dontcare else (out, zero, first)
+
+    def hash_windows_clips_device(self, d_buf: int, buf_bytes: int, clips: np.ndarray, n_frames, stride: int, d_out: int, d_dontcare: int = 0,
+                                  stream: int = 0):
+        """vdf_hash_windows_clips_u8_device: clips = HOST array of CLIP_DTYPE records (offsets relative to d_buf), n_frames = HOST frame counts;
+        every address is checked against buf_bytes before anything is queued.  d_out: hash_windows_first(n_frames, stride)[-1] x 16 words;
+        ordered on `stream`."""
+        c = np.ascontiguousarray(clips, dtype=CLIP_DTYPE).reshape(-1)
+        nf = np.ascontiguousarray(n_frames, dtype=np.uint32).reshape(-1)
+        if nf.size != c.size:
+            raise ValueError("one frame count per video")
+        self._check(self.lib.vdf_hash_windows_clips_u8_device(self.ctx, d_buf or None, int(buf_bytes), c.ctypes.data if c.size else None,
+                                                              nf.ctypes.data if nf.size else None, c.size, _window_stride(stride), d_out or None,
+                                                              d_dontcare or None, stream or None))
+
+    def hash_windows_clips_planes_device(self, d_buf: int, buf_bytes: int, clips: np.ndarray, n_frames, stride: int, d_out: int, d_zero: int,
+                                         d_dontcare: int = 0, stream: int = 0):
+        """vdf_hash_windows_clips_u8_planes_device: d_out and d_zero hold hash_windows_first(n_frames, stride)[-1] x 16 words each."""
+        c = np.ascontiguousarray(clips, dtype=CLIP_DTYPE).reshape(-1)
+        nf = np.ascontiguousarray(n_frames, dtype=np.uint32).reshape(-1)
+        if nf.size != c.size:
+            raise ValueError("one frame count per video")
+        self._check(self.lib.vdf_hash_windows_clips_u8_planes_device(self.ctx, d_buf or None, int(buf_bytes), c.ctypes.data if c.size else None,
+                                                                     nf.ctypes.data if nf.size else None, c.size, _window_stride(stride), d_out or None,
+                                                                     d_dontcare or None, d_zero or None, stream or None))
 
     # --------------------------------------------- flipped and reversed stretches (include/vdf.h, DESIGN.md 4.11)
     def window_variants(self, d_hashes: int, d_zero: int, d_first: int, n_videos: int, variant: int, d_out: int, d_skip: int = 0, d_out_skip: int = 0,

@@ -257,6 +257,59 @@ public:
         if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
     }
 
+    // Every window of videos of DIFFERENT frame sizes and lengths in one call (vdf_hash_windows_clips_u8): video i = n_frames
+    // tightly packed gray frames of w x h, with an optional crop box {left, right, top, bottom} read in place.  Per video the VideoHash of
+    // frames [k * stride, k * stride + 16); the lists differ in length.  The words are hash_windows' for each video alone.
+    struct Video {
+        const uint8_t *frames;  // n_frames x w x h bytes
+        uint32_t n_frames, w, h;
+        std::string src_path;
+        uint32_t duration;
+        std::array<uint32_t, 4> crop{{0, 0, 0, 0}};
+    };
+    static std::vector<std::vector<VideoHash>> hash_windows_clips(const std::vector<Video> &videos, uint32_t stride, Context *ctx_opt = nullptr)
+    {
+        Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+        const size_t n = videos.size();
+        std::vector<vdf_clip> clips(n);
+        std::vector<uint32_t> n_frames(n), first(n + 1);
+        size_t at = 0;
+        for (size_t i = 0; i < n; i++) {
+            const Video &v = videos[i];
+            if (v.n_frames < VDF_DCT_SIZE) throw Error::not_enough_frames();
+            clips[i] = vdf_clip{at, (uint64_t)v.w * v.h, v.w, v.h, v.crop[0], v.crop[1], v.crop[2], v.crop[3]};
+            n_frames[i] = v.n_frames;
+            at += ((size_t)v.n_frames * v.w * v.h + 63) & ~(size_t)63;
+        }
+        if (vdf_hash_windows_clips_first(n_frames.data(), n, stride, first.data()) != VDF_OK)
+            throw std::invalid_argument("a window stride of zero, or 2^32 windows or more in one call");
+        std::vector<uint8_t> packed(at);
+        for (size_t i = 0; i < n; i++)
+            std::copy(videos[i].frames, videos[i].frames + (size_t)videos[i].n_frames * videos[i].w * videos[i].h, packed.begin() + (size_t)clips[i].offset);
+        std::vector<uint64_t> words((size_t)first[n] * VDF_HASH_WORDS);
+        const int rc = vdf_hash_windows_clips_u8(ctx.get(), packed.data(), packed.size(), clips.data(), n_frames.data(), n, stride, words.data(), nullptr);
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+        std::vector<std::vector<VideoHash>> out(n);
+        for (size_t i = 0; i < n; i++)
+            for (size_t r = first[i]; r < first[i + 1]; r++) {
+                std::array<uint64_t, VDF_HASH_WORDS> hw;
+                std::copy(words.begin() + r * VDF_HASH_WORDS, words.begin() + (r + 1) * VDF_HASH_WORDS, hw.begin());
+                out[i].emplace_back(hw, videos[i].src_path, videos[i].duration);
+            }
+        return out;
+    }
+    // The same on device memory: clips and n_frames are HOST arrays (offsets relative to d_buf); d_out = first[n_videos] x 16 words with first
+    // from vdf_hash_windows_clips_first, d_dontcare nullable; window k of video i at row first[i] + k.  Ordered on stream.
+    static void hash_windows_clips_device(Context &ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames, size_t n_videos,
+                                          uint32_t stride, uint64_t *d_out, uint32_t *d_dontcare = nullptr, void *stream = nullptr)
+    {
+        const int rc = vdf_hash_windows_clips_u8_device(ctx.get(), d_buf, buf_bytes, clips, n_frames, n_videos, stride, d_out, d_dontcare, stream);
+        if (rc == VDF_E_NOT_ENOUGH_FRAMES) throw Error::not_enough_frames();
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+    }
+
     // Which videos share a stretch, at what offset, for how long (vdf_align_windows): windows_a / windows_b = hash_windows'
     // results (videos may differ in length); windows_b null: the videos of windows_a against each other, every pair a < b once.  At most one
     // record per pair of videos, in (a, b) order: the best run of consecutive windows within tol_int on one diagonal (offset = kb - ka), of at
