@@ -406,8 +406,9 @@ __global__ __launch_bounds__(256) void expand_fp4_kernel(const uint32_t *__restr
 //      the other, alternating between the wave's two row tiles; while block b accumulates into one accumulator set the
 //      finished block b - 1 sits in the other and its test (8 v_max3 + a compare) issues in the shadow of block b's MFMAs.
 //      Each B fragment is read from LDS twice (once per row tile: 1 ds_read_b128 per MFMA, half of what the LDS array
-//      sustains).  The test only sets a bit in a scalar mask; flagged blocks (they may contain a pair within the
-//      tolerance: ~0.3 % on unrelated hashes) are evaluated over all 1024 bits at the end of the stage - operands from
+//      sustains) - in the two-set stream; the streams of K = 9 .. 13 run the two row tiles in lock-step on ONE read of a
+//      fragment, with four accumulator sets (see kLock in the kernel).  The test only sets a bit in a scalar mask;
+//      flagged blocks (they may contain a pair within the tolerance: ~0.3 % on unrelated hashes) are evaluated over all 1024 bits at the end of the stage - operands from
 //      the LDS image and the target registers - where window / consumption bitmap / append are applied as in the VALU
 //      kernel's slow path.  LDS reads run P fragments ahead in ONE stream across block boundaries; sched_barrier(0)
 //      between slots makes the source order the schedule.
@@ -425,6 +426,21 @@ __device__ __forceinline__ void static_for(F &&f)
         static_for<I + 1, N>(f);
     }
 }
+
+// Lock-step streams (below) keep the 32 row terms of a row tile in ONE register: lane l holds the term of the row this
+// function names, and accumulator register r is that register under v_mov_b32_dpp row_newbcast:r (lane r of each 16-lane row,
+// broadcast to its row).  The assert ties the map to the C layout above: lane r of either 16-lane row of lane group g holds
+// the row of accumulator register r of that group.
+constexpr uint32_t rowterm_row_of_lane(uint32_t l) { return (l & 3u) + 8u * ((l & 15u) >> 2) + 4u * (l >> 5); }
+constexpr bool rowterm_map_matches_c_layout()
+{
+    for (uint32_t g = 0; g < 2; g++)
+        for (uint32_t half = 0; half < 2; half++)
+            for (uint32_t r = 0; r < 16; r++)
+                if (rowterm_row_of_lane(32u * g + 16u * half + r) != (r & 3u) + 8u * (r >> 2) + 4u * g) return false;
+    return true;
+}
+static_assert(rowterm_map_matches_c_layout(), "row-term lanes do not match the MFMA C layout");
 
 // Second pass of the second-generation MFMA search.  A block of the stream that cannot be ruled out after K k-steps
 // (~0.3 % on unrelated hashes) names its suspects: per lane (= candidate column) the 16-bit mask of accumulator registers
@@ -546,6 +562,19 @@ __global__ __launch_bounds__(64 * WAVES, 2) void hamming_mfma2_kernel(
     // vector depends on (row tile, lane group) only: 256 B per wave - straight into the accumulator set of the NEXT block, in the four
     // slots behind the test that last read it.
     constexpr bool kRowcLds = K > 13;
+    // Which K runs which stream:
+    //   K = 9 .. 13 (CHK 8, 10, 11, 12), both tile heights: LOCK-STEP.  The wave's two row tiles run side by side - a sub-tile is one PAIR of 2 K
+    //     MFMAs, (rt 0, s), (rt 1, s) for s = 0 .. K - 1, both on the one fragment (sub, s) - so a fragment is read from LDS once, not twice:
+    //     one ds_read_b128 per two MFMAs.  That takes four accumulator sets (the pair in flight and the pair under test: 64 registers), which
+    //     fit because the row terms shrink from two 16-register vectors to one register per row tile (rowterm_row_of_lane; the sets are
+    //     re-loaded from it with 32 v_mov_b32_dpp under the next pair's MFMAs and every MFMA takes its set as C) and because a fragment that
+    //     feeds two MFMAs needs two reads in flight, three buffers, for the latency that four in flight covered.  As compiled for gfx950
+    //     (512-row / 256-row form): K = 9: 217 / 211 VGPRs, 11: 240 / 231, 12: 247 / 241, 13: 255 / 251; no scratch, no spills.
+    //   K = 7 (CHK 6): a pair has 14 slots, too few for two tests and 32 moves at this density; it keeps the two-set stream.
+    //   K = 14 .. 16: 112 - 128 registers of targets leave no room for four sets; they keep the two-set stream with the row terms in LDS.
+    constexpr bool kLock = K >= 9 && K <= 13;
+    constexpr int PL = 2, NBL = PL + 1;                   // lock-step: LDS fragments in flight / fragment buffers
+    constexpr int kLoadAt = 10;                           // lock-step: the tested sets are re-loaded under slots kLoadAt .. kLoadAt + 7 of a pair
     constexpr uint32_t kSub = WAVES >= 8 ? 4 : 2;         // 32-candidate sub-tiles per LDS stage
     constexpr uint32_t kColStep = 32 * kSub;
     constexpr int NBLK = 2 * (int)kSub;                   // blocks per stage and wave: (sub-tile, row tile)
@@ -558,6 +587,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void hamming_mfma2_kernel(
     static_assert(kDmaEvery >= 2, "stage too short for its DMA pieces");
     constexpr int kTestAt = 2;                            // the previous block's test issues under MFMAs kTestAt .. kTestAt + 3 of a block
     static_assert(K >= kTestAt + 4, "block too short to hide the previous block's test");
+    static_assert(!kLock || (kLoadAt >= kTestAt + 8 && 2 * K >= kLoadAt + 8), "pair too short for two tests and the re-load of two sets");
     const uint32_t bid = blockIdx.x + block_base;
     __shared__ __attribute__((aligned(16))) uint4 s_b0[kColStep * 32];
     __shared__ __attribute__((aligned(16))) uint4 s_b1[kColStep * 32];
@@ -598,6 +628,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void hamming_mfma2_kernel(
     v4i a[2][K];
     const float4 *s_rc = nullptr;  // kRowcLds: [wave][row tile][lane group][4 x float4]
     v16f rowc[2];
+    float rowv[2] = {0.f, 0.f};  // kLock: the row terms, one register per row tile (lane l: row rowterm_row_of_lane(l))
     uint32_t live[2];  // bit r: the row of accumulator register r has a non-empty window in this launch (suspects of other rows are noise)
 #pragma unroll
     for (int rt = 0; rt < 2; rt++) {
@@ -611,12 +642,19 @@ __global__ __launch_bounds__(64 * WAVES, 2) void hamming_mfma2_kernel(
             const uint4 v = rp[s];
             a[rt][s] = (v4i){(int)v.x, (int)v.y, (int)v.z, (int)v.w};
         }
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const uint32_t pr = row0 + 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * g;
+        if constexpr (kLock) {  // one row per lane; lanes 32 g .. 32 g + 15 hold the rows of registers 0 .. 15 of lane group g
+            const uint32_t pr = row0 + 32 * rt + rowterm_row_of_lane(lane);
             const uint32_t sr = (pr < n_rows && row_perm) ? row_perm[pr] : pr;
-            rowc[rt][r] = -0.5f * row_popk[sr];
-            if (row_hi[pr] > row_lo[pr]) live[rt] |= 1u << r;  // the window arrays are padded to whole tiles
+            rowv[rt] = -0.5f * row_popk[sr];
+            live[rt] = (uint32_t)(__builtin_amdgcn_ballot_w64(row_hi[pr] > row_lo[pr]) >> (32 * g)) & 0xFFFFu;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const uint32_t pr = row0 + 32 * rt + (r & 3) + 8 * (r >> 2) + 4 * g;
+                const uint32_t sr = (pr < n_rows && row_perm) ? row_perm[pr] : pr;
+                rowc[rt][r] = -0.5f * row_popk[sr];
+                if (row_hi[pr] > row_lo[pr]) live[rt] |= 1u << r;  // the window arrays are padded to whole tiles
+            }
         }
     }
     if constexpr (kRowcLds) {  // the vectors go to LDS (one lane of each lane group writes; read back by this wave only, behind the barrier
@@ -670,6 +708,16 @@ __global__ __launch_bounds__(64 * WAVES, 2) void hamming_mfma2_kernel(
 
     v16f acc[2] = {v16f{}, v16f{}};
     if constexpr (kRowcLds) acc[0] = rowc[0];  // the stream's first block starts from its row term (the later ones fetch theirs from LDS)
+    // kLock: four sets; pair p of a stage accumulates into sets 2 (p & 1) + rt while the two sets of the pair before are tested and re-loaded
+    // with their row terms.  `old` is the register itself: nothing to materialise, the slot carries the v_mov_b32_dpp alone.
+    v16f acc4[4] = {v16f{}, v16f{}, v16f{}, v16f{}};
+    auto load_rowterm = [&](v16f &c, float v, auto rc) __attribute__((always_inline)) {
+        constexpr int r = decltype(rc)::value;
+        c[r] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(c[r]), __float_as_int(v), 0x150 + r, 0xF, 0xF, false));  // row_newbcast:r
+    };
+    if constexpr (kLock) {
+        static_for<0, 16>([&](auto rc) __attribute__((always_inline)) { load_rowterm(acc4[0], rowv[0], rc); load_rowterm(acc4[1], rowv[1], rc); });
+    }
     uint32_t n_early = 0;  // blocks that stopped after K steps
     float thr[kSub], thr_next[kSub];
 
@@ -716,6 +764,21 @@ __global__ __launch_bounds__(64 * WAVES, 2) void hamming_mfma2_kernel(
             }
         }
         q_next += need;
+    };
+
+    // The end of a stage, both streams: count the blocks that stopped early, wait for the next stage's image, take its thresholds.
+    auto end_stage = [&](uint32_t cb, uint32_t flags) __attribute__((always_inline)) {
+        // blocks of sub-tiles at or beyond the end of the chunk hold nothing
+        uint32_t valid = 0;
+#pragma unroll
+        for (uint32_t sub = 0; sub < kSub; sub++)
+            if (cb + 32u * sub < c_end) valid |= 3u << (2 * sub);
+        flags &= valid;
+        n_early += (uint32_t)__builtin_popcount(valid & ~flags);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // explicit: the fence's vmcnt wait is the compiler's to drop (it did, in a resize kernel: DESIGN 4.3)
+        __syncthreads();  // the DMA and the threshold load have landed (every wave waited for its own) and every wave is done with `cur`
+#pragma unroll
+        for (uint32_t sub = 0; sub < kSub; sub++) thr[sub] = 0.5f * (thr_next[sub] - tol_f);
     };
 
     // One stage: NBLK blocks of K MFMAs over the candidates in `cur`; DMA of the next stage into `nxt`.
@@ -783,17 +846,77 @@ __global__ __launch_bounds__(64 * WAVES, 2) void hamming_mfma2_kernel(
                 emit(c, thr[kSub - 1], live[(NBLK - 1) & 1], row0 + 32u * (uint32_t)((NBLK - 1) & 1), cb + 32u * (kSub - 1));
             }
         }
-        // blocks of sub-tiles at or beyond the end of the chunk hold nothing
-        uint32_t valid = 0;
+        end_stage(cb, flags);
+    };
+
+    // The lock-step form of a stage (kLock): kSub pairs of 2 K MFMAs.  Slot j of pair p is step j >> 1 of row tile j & 1 into set 2 (p & 1) +
+    // (j & 1); the even slots read the fragment PL ahead (one stream across pair boundaries).  The two sets of pair p - 1 are tested under
+    // slots kTestAt .. kTestAt + 3 (row tile 0) and kTestAt + 4 .. kTestAt + 7 (row tile 1) and re-loaded with their row terms under slots
+    // kLoadAt .. kLoadAt + 7, four moves a slot.  Pair 0 re-loads the sets of the last pair of the stage before, tested at that stage's end.
+    auto run_stage_lock = [&](uint32_t cb, const uint4 *cur, uint4 *nxt) __attribute__((always_inline)) {
+        const uint32_t cb_next = cb + kColStep < c_end ? cb + kColStep : cb;
+        const __amdgpu_buffer_rsrc_t rs_next = stage_rsrc(cb_next);
+        load_thr(cb_next, thr_next);  // lands long before the barrier that ends this stage
+        uint32_t flags = 0;
+        uint4 fq[NBL];
+        constexpr int NF = (int)kSub * K;  // fragments per stage
+        auto frag = [&](int f) __attribute__((always_inline)) {  // fragment f of the stage: sub-tile f / K, step f % K
+            const uint32_t sub = (uint32_t)(f / K), s = (uint32_t)(f % K);
+            return cur[((32u * sub + c31) << 5) | ((s + 16u * g) ^ c31)];
+        };
 #pragma unroll
-        for (uint32_t sub = 0; sub < kSub; sub++)
-            if (cb + 32u * sub < c_end) valid |= 3u << (2 * sub);
-        flags &= valid;
-        n_early += (uint32_t)__builtin_popcount(valid & ~flags);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // explicit: the fence's vmcnt wait is the compiler's to drop (it did, in a resize kernel: DESIGN 4.3)
-        __syncthreads();  // the DMA and the threshold load have landed (every wave waited for its own) and every wave is done with `cur`
-#pragma unroll
-        for (uint32_t sub = 0; sub < kSub; sub++) thr[sub] = 0.5f * (thr_next[sub] - tol_f);
+        for (int f = 0; f < PL; f++) fq[f] = frag(f);
+        __builtin_amdgcn_sched_barrier(0);
+        float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 0.f, m5 = 0.f;
+        static_for<0, NM>([&](auto ic) __attribute__((always_inline)) {
+            constexpr int i = decltype(ic)::value;
+            constexpr int p = i / (2 * K), j = i % (2 * K), s = j >> 1, rt = j & 1, f = p * K + s;
+            constexpr int mine = 2 * (p & 1) + rt, other = 2 * ((p & 1) ^ 1);  // this MFMA's set; row tile 0's set of the other pair
+            const uint4 bv = fq[f % NBL];
+            const v8i b = {(int)bv.x, (int)bv.y, (int)bv.z, (int)bv.w, 0, 0, 0, 0};
+            const v8i ar = {a[rt][s].x, a[rt][s].y, a[rt][s].z, a[rt][s].w, 0, 0, 0, 0};
+            acc4[mine] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ar, b, acc4[mine], 4, 4, 0, 0, 0, 0);  // the set holds the row term at s == 0
+            if constexpr (rt == 0 && f + PL < NF) fq[(f + PL) % NBL] = frag(f + PL);
+            if constexpr ((i % kDmaEvery) == 1 && (i / kDmaEvery) < kDmaPerWave) load_piece(rs_next, nxt, i / kDmaEvery);
+            if constexpr (p >= 1 && j >= kTestAt && j < kTestAt + 8) {  // same max tree as the two-set stream, one set after the other
+                constexpr int trt = (j - kTestAt) >> 2, q = (j - kTestAt) & 3;
+                const v16f &c = acc4[other + trt];
+                if constexpr (q == 0) {
+                    m0 = fmaxf(fmaxf(c[0], c[1]), c[2]); m1 = fmaxf(fmaxf(c[3], c[4]), c[5]); m2 = fmaxf(fmaxf(c[6], c[7]), c[8]);
+                } else if constexpr (q == 1) {
+                    m3 = fmaxf(fmaxf(c[9], c[10]), c[11]); m4 = fmaxf(fmaxf(c[12], c[13]), c[14]);
+                } else if constexpr (q == 2) {
+                    m5 = fmaxf(fmaxf(m0, m1), m2); m3 = fmaxf(fmaxf(m3, m4), c[15]);
+                } else {
+                    if (__builtin_amdgcn_ballot_w64(fmaxf(m5, m3) >= thr[p - 1]) != 0ull) {
+                        flags |= 1u << (2 * (p - 1) + trt);
+                        emit(c, thr[p - 1], live[trt], row0 + 32u * (uint32_t)trt, cb + 32u * (uint32_t)(p - 1));
+                    }
+                }
+            }
+            if constexpr (j >= kLoadAt && j < kLoadAt + 8) {
+                constexpr int lrt = (j - kLoadAt) >> 2, q = (j - kLoadAt) & 3;
+                static_for<4 * q, 4 * q + 4>([&](auto rc) __attribute__((always_inline)) { load_rowterm(acc4[other + lrt], rowv[lrt], rc); });
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        // the two sets of the stage's last pair finish together and have nothing of their own stage to hide behind
+        static_for<0, 2>([&](auto rtc) __attribute__((always_inline)) {
+            constexpr int rt = decltype(rtc)::value;
+            const v16f &c = acc4[2 * (((int)kSub - 1) & 1) + rt];
+            m0 = fmaxf(fmaxf(c[0], c[1]), c[2]); m1 = fmaxf(fmaxf(c[3], c[4]), c[5]); m2 = fmaxf(fmaxf(c[6], c[7]), c[8]);
+            m3 = fmaxf(fmaxf(c[9], c[10]), c[11]); m4 = fmaxf(fmaxf(c[12], c[13]), c[14]);
+            const float pm = fmaxf(fmaxf(fmaxf(m0, m1), m2), fmaxf(fmaxf(m3, m4), c[15]));
+            if (__builtin_amdgcn_ballot_w64(pm >= thr[kSub - 1]) != 0ull) {
+                flags |= 1u << (2 * ((int)kSub - 1) + rt);
+                emit(c, thr[kSub - 1], live[rt], row0 + 32u * (uint32_t)rt, cb + 32u * (kSub - 1));
+            }
+        });
+        end_stage(cb, flags);
+    };
+    auto stage =[&](uint32_t cb, const uint4 *cur, uint4 *nxt) __attribute__((always_inline)) {
+        if constexpr (kLock) run_stage_lock(cb, cur, nxt);
+        else run_stage(cb, cur, nxt);
     };
 
 #pragma unroll
@@ -808,9 +931,9 @@ __global__ __launch_bounds__(64 * WAVES, 2) void hamming_mfma2_kernel(
 #pragma unroll
     for (uint32_t sub = 0; sub < kSub; sub++) thr[sub] = 0.5f * (thr_next[sub] - tol_f);
     for (uint32_t cb = cb0; cb < c_end; cb += 2 * kColStep) {
-        run_stage(cb, s_b0, s_b1);
+        stage(cb, s_b0, s_b1);
         if (cb + kColStep >= c_end) break;
-        run_stage(cb + kColStep, s_b1, s_b0);
+        stage(cb + kColStep, s_b1, s_b0);
     }
     if (tid == 0) atomicAdd(&counters[1], (unsigned long long)(c_end - c_begin) * kTileRows);
     if (CHK < 15 && lane == 0 && n_early) atomicAdd(&counters[3], (unsigned long long)n_early * (32u * 32u));
