@@ -239,6 +239,33 @@ int vdf_hash_windows_u8_planes_device(vdf_ctx *ctx, const uint8_t *d_frames, siz
                                       uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride, uint32_t window_stride,
                                       uint64_t *d_out_hashes, uint32_t *d_out_dontcare, uint64_t *d_out_zero, void *stream);
 
+/* ---- retimed window hashes: a copy at another frame rate or speed ----------------------------------------------
+ * The window calls above assume that two files hold the same frames, one for one.  A copy re-encoded from 30 to 25 fps keeps
+ * 5 of every 6 frames, a 1.5x re-upload 2 of 3: its window k holds the frames of NO window of the original.  These calls hash
+ * windows of the original that do hold them.  A rate is rate_num / rate_den with
+ * 1 <= rate_den <= rate_num <= 2 rate_den and rate_num <= 65535, and
+ *   tap(i) = floor(i * rate_num / rate_den), i = 0 ... 15;      span = tap(15) + 1 (16 ... 31);
+ *   retimed window k = the hash of the 16 frames k * window_stride + tap(i) - exactly what vdf_hash_frames_u8 gives on those
+ *   16 frames gathered into a stack, don't-care count included;
+ *   n_win = (frames_per_clip - span) / window_stride + 1 (vdf_hash_window_count_retimed; 0 if frames_per_clip < span, if
+ *   window_stride == 0 or if the rate is outside the range).
+ * If B[j] = A[c + floor(j num / den)], the retimed window c + num m of A at num / den equals the plain window den m of B.
+ * Always retime the side with MORE frames per second; rates below 1 would repeat frames and are not offered.
+ * Arguments, layout of the outputs and the resize stage as vdf_hash_windows_u8[_device]; every frame is read, resized and
+ * spatially transformed once.  Errors: that call's, in its order (frames_per_clip < 16 -> VDF_E_NOT_ENOUGH_FRAMES first), then
+ * a rate outside the range or rate_den == 0 -> VDF_E_INVAL, then frames_per_clip < span -> VDF_E_NOT_ENOUGH_FRAMES.
+ * At rate_num == rate_den, and at every rate whose taps are 0 ... 15 (25/24, say), the call IS the plain call: its route, its words.
+ * The host form uploads in one piece and calls the device form's work.  A multi-GPU context -> VDF_E_INVAL.
+ * Not here: zero planes of retimed windows, the mixed-library form, the batching queue. */
+size_t vdf_hash_window_count_retimed(uint32_t frames_per_clip, uint32_t window_stride, uint32_t rate_num, uint32_t rate_den);
+int vdf_hash_windows_u8_retimed(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w,
+                                uint32_t h, size_t frame_stride, size_t clip_stride, uint32_t window_stride, uint32_t rate_num,
+                                uint32_t rate_den, uint64_t *out_hashes, uint32_t *out_dontcare);
+int vdf_hash_windows_u8_retimed_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip,
+                                       uint32_t w, uint32_t h, size_t frame_stride, size_t clip_stride, uint32_t window_stride,
+                                       uint32_t rate_num, uint32_t rate_den, uint64_t *d_out_hashes, uint32_t *d_out_dontcare,
+                                       void *stream);
+
 /* ---- align videos on their window hashes: the longest shared stretch of every pair of videos -------------
  * Which videos share a stretch, at what offset, and for how long.  Two sets of videos, A and B, each the
  * window hashes of its videos one after the other (what vdf_hash_windows_* writes): hashes[n_windows_total][16] and

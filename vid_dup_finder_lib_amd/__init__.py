@@ -5,11 +5,11 @@ The compute path is hand-written HIP for gfx950 in csrc/, reached through the C 
 include/vdf.h (libvdf_hip.so).  There is no CPU fallback.
 """
 from ._capi import (DEFAULT_SEARCH_TOLERANCE, HASH_BITS, HASH_WORDS, TOLERANCE_SCALING_FACTOR, VdfError)
-from .api import (Alignment, AlignmentStretch, FlippedAlignment, align, align_all, align_flipped, candidate_pairs, candidate_pairs_flipped, static_windows, Crop, Cropdetect, Flip, search_flipped, cropdetect_letterbox, Error, MatchGroup, gen_hashes, NotEnoughFrames, NotVideo, TooFewEntries, VideoHash, VidProc, default_engine,
+from .api import (Alignment, AlignmentStretch, FlippedAlignment, RetimedAlignment, align, align_all, align_flipped, align_retimed, candidate_pairs, candidate_pairs_flipped, static_windows, Crop, Cropdetect, Flip, search_flipped, cropdetect_letterbox, Error, MatchGroup, gen_hashes, NotEnoughFrames, NotVideo, TooFewEntries, VideoHash, VidProc, default_engine,
                   hash_frame_stacks, hash_frame_windows, locate, rust_path_key, search, search_with_references, sort_order)
 from .engine import (ALIGN_DTYPE, ALIGN_STRETCH_DTYPE, ALIGN_VARIANT_DTYPE, Engine, align_windows_host, align_windows_stretches_host, align_windows_variants_host,
                      window_variants_host, VIDEO_PAIR_DTYPE, align_seed_pairs_host, align_windows_pairs_host, align_windows_stretches_pairs_host,
-                     VIDEO_PAIR_VARIANT_DTYPE, align_seed_pairs_variants_host, align_windows_variants_pairs_host, window_class_layout_host, hash_windows_first)
+                     VIDEO_PAIR_VARIANT_DTYPE, align_seed_pairs_variants_host, align_windows_variants_pairs_host, window_class_layout_host, hash_windows_first, hash_window_count_retimed)
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
            "search_with_references", "search_flipped", "Flip", "hash_frame_stacks", "hash_frame_windows", "locate", "align", "Alignment", "static_windows", "Engine", "default_engine", "VdfError", "rust_path_key",
@@ -18,4 +18,4 @@ __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHas
            "align_all", "AlignmentStretch", "ALIGN_STRETCH_DTYPE", "align_windows_stretches_host",
            "candidate_pairs", "VIDEO_PAIR_DTYPE", "align_seed_pairs_host", "align_windows_pairs_host", "align_windows_stretches_pairs_host",
            "candidate_pairs_flipped", "VIDEO_PAIR_VARIANT_DTYPE", "align_seed_pairs_variants_host", "align_windows_variants_pairs_host", "window_class_layout_host",
-           "hash_windows_first"]
+           "hash_windows_first", "hash_window_count_retimed", "align_retimed", "RetimedAlignment"]

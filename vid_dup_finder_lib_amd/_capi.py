@@ -163,6 +163,7 @@ SIGNATURES = {
     "vdf_hash_frames_u8_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                             C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vdf_hash_window_count": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "vdf_hash_window_count_retimed": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "vdf_hash_windows_u8": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t,
                                       C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vdf_hash_windows_u8_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -171,6 +172,11 @@ SIGNATURES = {
                                              C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vdf_hash_windows_u8_planes_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                                     C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # vdf_hash_windows_u8[_device]'s arguments with rate_num, rate_den behind window_stride
+    "vdf_hash_windows_u8_retimed": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t,
+                                              C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vdf_hash_windows_u8_retimed_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                     C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     # (ctx, buf, buf_bytes, clips, n_frames, n_videos, window_stride, out_hashes, out_dontcare [, out_zero] [, stream])
     "vdf_hash_windows_clips_first": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "vdf_hash_windows_clips_u8": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),

@@ -522,9 +522,24 @@ def _hash_frame_windows_mixed(stacks, src_paths, durations, stride, engine, zero
             for i in range(len(stacks))]
 
 
+def _hash_frame_windows_retimed(frames, src_paths, durations, stride, engine, rate):
+    """hash_frame_windows at a rate: one Engine.hash_windows_retimed call for a 4-D array, one uniform call per video for a list of stacks."""
+    eng = engine or default_engine()
+    try:
+        if isinstance(frames, (list, tuple)):
+            words = [eng.hash_windows_retimed(np.asarray(st)[None], rate, stride)[0] for st in frames]
+        else:
+            words = eng.hash_windows_retimed(frames, rate, stride)
+    except VdfError as e:
+        if e.code == _capi.VDF_E_NOT_ENOUGH_FRAMES:
+            raise NotEnoughFrames() from e
+        raise
+    return [[VideoHash(w[k], src_paths[i], durations[i]) for k in range(len(w))] for i, w in enumerate(words)]
+
+
 def hash_frame_windows(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int], stride: int = 1,
                        engine: Optional[Engine] = None, zero_plane: bool = False, crops: Optional[Sequence] = None,
-                       letterbox: bool = False) -> List[List[VideoHash]]:
+                       letterbox: bool = False, rate=None) -> List[List[VideoHash]]:
     """Every 16-frame window of every video (Engine.hash_windows): frames [n_videos, n_frames >= 16, H, W] u8 -> per video the VideoHash of
     frames [k * stride, k * stride + 16) for k = 0 .. (n_frames - 16) // stride, each carrying the video's src_paths[i] and durations[i].
     What finds a duplicate that is shifted in time (`locate`); the reference hashes one 16-frame stack per file (definitions.rs:31-34).
@@ -533,9 +548,17 @@ def hash_frame_windows(frames: np.ndarray, src_paths: Sequence, durations: Seque
     frames may also be a LIST of [F_i >= 16, H_i, W_i] stacks of different frame sizes AND lengths, as a library's files are: they are hashed
     by one call (Engine.hash_windows_clips[_planes]) and the per-video lists differ in length.  List input only: crops = a Crop (or four
     edge offsets l, r, t, b) per video, read in place; letterbox=True detects every video's box on its frames 0 and 8 (Engine.hash_clips_letterbox,
-    as gen_hashes does) and hashes the windows inside it."""
+    as gen_hashes does) and hashes the windows inside it.
+    rate=(num, den), 1 <= den <= num <= 2 den: RETIMED windows (Engine.hash_windows_retimed) - window k = the 16 frames k * stride +
+    (i * num) // den, which is what a copy of the video at den / num of its frame rate (or sped up num / den) holds in its plain windows;
+    align_retimed aligns the two.  Give it for the side with more frames per second.  No zero planes, crops or letterbox with a rate; a list
+    of stacks is hashed by one call per video."""
     if len(src_paths) < len(frames) or len(durations) < len(frames):
         raise ValueError("a path and a duration per video")
+    if rate is not None:
+        if zero_plane or crops is not None or letterbox:
+            raise ValueError("retimed windows have no zero planes, crops or letterbox")
+        return _hash_frame_windows_retimed(frames, src_paths, durations, stride, engine, rate)
     if isinstance(frames, (list, tuple)):
         return _hash_frame_windows_mixed(frames, src_paths, durations, stride, engine, zero_plane, crops, letterbox)
     if crops is not None or letterbox:
@@ -763,6 +786,70 @@ def align(windows_a: List[List[VideoHash]], windows_b: Optional[List[List[VideoH
         a, b, off, st, n, ds = (int(r[k]) for k in ("a", "b", "offset", "start_a", "n_windows", "dist_sum"))
         out.append(Alignment(a, b, off * s, st * s, (st + off) * s, (n - 1) * s + _capi.DCT_SIZE, n, ds / n, pa[a], pb[b]))
     return out
+
+
+class RetimedAlignment(NamedTuple):
+    """The longest stretch a video shares with a copy at num / den of its frames (align_retimed): video indices, the rate in lowest terms,
+    where the stretch starts in each video and how many of each video's frames it covers, the number of (sub-sampled) windows that matched,
+    their mean hamming distance, and the two videos' paths."""
+    a: int
+    b: int
+    num: int
+    den: int
+    first_frame_a: int
+    first_frame_b: int
+    n_frames_a: int        # (n_windows - 1) * num + span
+    n_frames_b: int        # (n_windows - 1) * den + 16
+    n_windows: int
+    mean_distance: float
+    path_a: object = None
+    path_b: object = None
+
+
+ALIGN_RETIMED_MAX_NUM = 32  # align_retimed makes `num` align calls
+
+
+def align_retimed(windows_a: List[List[VideoHash]], windows_b: List[List[VideoHash]], rate, tolerance: float = DEFAULT_SEARCH_TOLERANCE,
+                  min_run: int = 1, static_a=None, static_b=None, engine: Optional[Engine] = None, seed: bool = False) -> List[RetimedAlignment]:
+    """Which videos of A share a stretch with a video of B that runs at den / num of A's frames - a re-encode from 30 to 25 fps (rate 6/5), a
+    1.5 x re-upload (3/2), every other frame (2/1)?  windows_a: hash_frame_windows(..., rate=rate) at stride 1; windows_b: plain windows at
+    stride 1.  If B[j] = A[c + (j * num) // den], retimed window c + num * m of A equals plain window den * m of B: the matching cells of the
+    pair lie on a line of slope num / den, which `align` does not follow.  So for every phase p = 0 .. num - 1 the windows p, p + num, ... of A
+    are aligned (`align`, diagonals) with the windows 0, den, 2 den, ... of B, static flags sub-sampled alike, and per pair of videos the
+    record that maximises n_windows * (tol_int + 1) - sum of distances is kept (ties: the smaller first_frame_a, then first_frame_b).
+    A true stretch holds a window of B at a multiple of den, so B's phase 0 is enough: the stretch is found with its ends rounded inward by
+    less than den frames of B, and Na * Nb / den cells are walked.  min_run counts sub-sampled windows.  The rate is reduced by its gcd;
+    num > 32 is refused (the call makes num sub-calls).  No self mode.  -> one RetimedAlignment per pair at most, ordered by (a, b)."""
+    try:
+        num, den = (int(x) for x in rate)
+        if (num, den) != tuple(rate):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"rate must be a pair of integers (num, den), not {rate!r}") from None
+    if not 1 <= den <= num <= 2 * den:
+        raise ValueError("rate must have 1 <= den <= num <= 2 den")
+    g = math.gcd(num, den)
+    num, den = num // g, den // g
+    if num > ALIGN_RETIMED_MAX_NUM:
+        raise ValueError(f"align_retimed makes num sub-calls: num = {num} is above {ALIGN_RETIMED_MAX_NUM}")
+    span = (15 * num) // den + 1
+    tol_int = tolerance_int(tolerance)
+    sub_b = [ws[0::den] for ws in windows_b]
+    st_b = None if static_b is None else [np.asarray(f).reshape(-1)[0::den] for f in static_b]
+    best = {}
+    for p in range(num):
+        sub_a = [ws[p::num] for ws in windows_a]
+        st_a = None if static_a is None else [np.asarray(f).reshape(-1)[p::num] for f in static_a]
+        for al in align(sub_a, sub_b, tolerance, min_run=min_run, stride=1, static_a=st_a, static_b=st_b, engine=engine, seed=seed):
+            n, i0 = al.n_windows, al.first_frame_a
+            dist_sum = int(round(al.mean_distance * n))
+            rec = (-(n * (tol_int + 1) - dist_sum), p + num * i0, den * al.first_frame_b, n, dist_sum)
+            if (al.a, al.b) not in best or rec < best[(al.a, al.b)]:
+                best[(al.a, al.b)] = rec
+    pa = [ws[0].src_path() if ws else None for ws in windows_a]
+    pb = [ws[0].src_path() if ws else None for ws in windows_b]
+    return [RetimedAlignment(a, b, num, den, fa, fb, (n - 1) * num + span, (n - 1) * den + _capi.DCT_SIZE, n, ds / n, pa[a], pb[b])
+            for (a, b), (_, fa, fb, n, ds) in sorted(best.items())]
 
 
 class AlignmentStretch(NamedTuple):

@@ -789,8 +789,10 @@ int windows_checks(vdf_ctx *ctx, const void *frames, size_t n_clips, uint32_t fr
 }
 
 // windows_checks has passed.  d_zero (nullable): the windows' zero planes as well - the same resize runs and routes, the kernel's PLANES form
+// retimed (nullable; d_zero is null then): the retimed windows of that plan (windows_retimed_plan.h) - the same resize stage, the retimed kernel
 int hash_windows_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h, size_t frame_stride,
-                        size_t clip_stride, uint32_t window_stride, uint64_t *d_out, uint32_t *d_dc, hipStream_t stream, uint64_t *d_zero = nullptr)
+                        size_t clip_stride, uint32_t window_stride, uint64_t *d_out, uint32_t *d_dc, hipStream_t stream, uint64_t *d_zero = nullptr,
+                        const vdf::WindowsRetimedPlan *retimed = nullptr)
 {
     VDF_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = ensure_cos_table(ctx, stream)) return rc;
@@ -822,7 +824,16 @@ int hash_windows_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, u
         wf.tail_first = frames_per_clip - 16;
         wf.dwords = true;
     }
-    VDF_HIP(ctx, vdf::launch_dct_hash_windows(wf, n_clips, plan, ctx->cos_table.as<double>(), d_out, d_dc, stream, d_zero));
+    if (retimed) VDF_HIP(ctx, vdf::launch_dct_hash_windows_retimed(wf, n_clips, *retimed, ctx->cos_table.as<double>(), d_out, d_dc, stream));
+    else VDF_HIP(ctx, vdf::launch_dct_hash_windows(wf, n_clips, plan, ctx->cos_table.as<double>(), d_out, d_dc, stream, d_zero));
+    return VDF_OK;
+}
+
+// the rate checks of the retimed windows calls, behind windows_checks' (whose window count is the plain one: an upper bound of the retimed one)
+int windows_retimed_checks(vdf_ctx *ctx, uint32_t frames_per_clip, uint32_t rate_num, uint32_t rate_den)
+{
+    if (!vdf::retimed_rate_ok(rate_num, rate_den)) return fail(ctx, VDF_E_INVAL, "rate outside 1 <= den <= num <= 2 den, num <= 65535");
+    if (frames_per_clip < vdf::retimed_span(rate_num, rate_den)) return fail(ctx, VDF_E_NOT_ENOUGH_FRAMES, "fewer frames per clip than a retimed window spans");
     return VDF_OK;
 }
 
@@ -2507,6 +2518,61 @@ int vdf_hash_windows_u8(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uin
     uint32_t *d_dc = out_dontcare ? ctx->out_dc.as<uint32_t>() : nullptr;
     if (int rc = hash_windows_locked(ctx, ctx->frames.as<uint8_t>(), n_clips, frames_per_clip, w, h, frame_stride, clip_stride, window_stride,
                                      ctx->out_hashes.as<uint64_t>(), d_dc, ctx->stream))
+        return rc;
+    VDF_HIP(ctx, hipMemcpyAsync(out_hashes, ctx->out_hashes.p, n_out * VDF_HASH_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (out_dontcare) VDF_HIP(ctx, hipMemcpyAsync(out_dontcare, d_dc, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VDF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VDF_OK;
+}
+
+// ---- retimed window hashes (include/vdf.h: vdf_hash_windows_u8_retimed[_device]) ----------------------------------------------
+size_t vdf_hash_window_count_retimed(uint32_t frames_per_clip, uint32_t window_stride, uint32_t rate_num, uint32_t rate_den)
+{
+    return vdf::retimed_window_count(frames_per_clip, window_stride, rate_num, rate_den);
+}
+
+int vdf_hash_windows_u8_retimed_device(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h,
+                                       size_t frame_stride, size_t clip_stride, uint32_t window_stride, uint32_t rate_num, uint32_t rate_den,
+                                       uint64_t *d_out_hashes, uint32_t *d_out_dontcare, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    bool run;
+    if (int rc = windows_checks(ctx, d_frames, n_clips, frames_per_clip, w, h, frame_stride, window_stride, d_out_hashes, &run)) return rc;
+    if (int rc = windows_retimed_checks(ctx, frames_per_clip, rate_num, rate_den)) return rc;
+    if (!run) return VDF_OK;
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    if (vdf::retimed_is_plain(rate_num, rate_den))  // the taps are 0 ... 15: the plain call, its route and its words
+        return hash_windows_locked(ctx, d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, window_stride, d_out_hashes, d_out_dontcare, s);
+    const vdf::WindowsRetimedPlan rp = vdf::plan_windows_retimed(frames_per_clip, window_stride, rate_num, rate_den);
+    return hash_windows_locked(ctx, d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, window_stride, d_out_hashes, d_out_dontcare, s, nullptr,
+                               &rp);
+}
+
+// Host arrays: as vdf_hash_windows_u8 - one upload through the context's staging buffer, the device form's work on it, the results come down.
+int vdf_hash_windows_u8_retimed(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h,
+                                size_t frame_stride, size_t clip_stride, uint32_t window_stride, uint32_t rate_num, uint32_t rate_den,
+                                uint64_t *out_hashes, uint32_t *out_dontcare)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    bool run;
+    if (int rc = windows_checks(ctx, frames, n_clips, frames_per_clip, w, h, frame_stride, window_stride, out_hashes, &run)) return rc;
+    if (int rc = windows_retimed_checks(ctx, frames_per_clip, rate_num, rate_den)) return rc;
+    if (!run) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n_out = n_clips * vdf::retimed_window_count(frames_per_clip, window_stride, rate_num, rate_den);
+    size_t clips_span = 0, frames_span = 0, bytes = 0;  // as vdf_hash_windows_u8: first byte of clip 0 to the last byte of the last clip's last frame
+    if (__builtin_mul_overflow(n_clips - 1, clip_stride, &clips_span) || __builtin_mul_overflow((size_t)(frames_per_clip - 1), frame_stride, &frames_span) ||
+        __builtin_add_overflow(clips_span, frames_span, &bytes) || __builtin_add_overflow(bytes, (size_t)w * h, &bytes))
+        return fail(ctx, VDF_E_INVAL, "the clips' extent does not fit size_t");
+    if (int rc = upload(ctx, ctx->frames, frames, bytes, ctx->stream)) return rc;
+    VDF_HIP(ctx, ctx->out_hashes.reserve(n_out * VDF_HASH_WORDS * sizeof(uint64_t)));
+    if (out_dontcare) VDF_HIP(ctx, ctx->out_dc.reserve(n_out * sizeof(uint32_t)));
+    uint32_t *d_dc = out_dontcare ? ctx->out_dc.as<uint32_t>() : nullptr;
+    const vdf::WindowsRetimedPlan rp = vdf::plan_windows_retimed(frames_per_clip, window_stride, rate_num, rate_den);
+    if (int rc = hash_windows_locked(ctx, ctx->frames.as<uint8_t>(), n_clips, frames_per_clip, w, h, frame_stride, clip_stride, window_stride,
+                                     ctx->out_hashes.as<uint64_t>(), d_dc, ctx->stream, nullptr, vdf::retimed_is_plain(rate_num, rate_den) ? nullptr : &rp))
         return rc;
     VDF_HIP(ctx, hipMemcpyAsync(out_hashes, ctx->out_hashes.p, n_out * VDF_HASH_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     if (out_dontcare) VDF_HIP(ctx, hipMemcpyAsync(out_dontcare, d_dc, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));

@@ -3153,6 +3153,179 @@ hipError_t launch_dct_hash_windows_mixed(const uint8_t *small, const WindowsVide
     return hipGetLastError();
 }
 
+// ---- retimed window hashes: windows sampled at num / den of the clip's own frame rate (vdf_hash_windows_u8_retimed[_device]) ----
+// dct_hash_windows_kernel's body - the chunk walk, pass y, pass x, dct16_pruned, contraction off, the same constants and kPadY / kStrideT layouts,
+// the paired ballot pack, the double-buffered words, the same barriers - with ONE change to what is computed: pass t of window k reads the frames
+// k stride + tap(i), tap(i) = floor(i num / den) (windows_retimed_plan.h), not k stride + i.  A window then spans up to 31 frames, and with chunks
+// of 16 frames its first frame has to survive up to two more chunk loads (have < s + span + 16 <= s + 47 when the window is whole): the ring
+// holds 64 frames of S, slot (f - run) & 63, chunks still at slot 0 / 16 / 32 / 48.  A chunk load writes slots [have - run, have - run + 16) & 63;
+// the windows still to come start at frames >= s > have - 48, so it overwrites only frames below every one of them, and the barrier behind the
+// last pair of pass t stands between those reads and that write.  The taps are kernel arguments - 16 bytes in two qwords - so tap(t) of the
+// unrolled pass t is scalar shifts, and the ring address is one add and one mask more than the plain kernel's.
+// LDS: b 21 760 + ring 54 272 + cube 4 096 + words 512 + counts 32 = 80 672 bytes, two workgroups per CU (160 KB).
+struct WindowsRetimedShared {
+    double b[16 * 10 * kPadY];         // first-pass output [t][ky][x] of the chunk in hand
+    double c[64 * kStrideT];           // the ring: S of frame f at slot (f - run) & 63, [slot][10 kx + ky]
+    __attribute__((aligned(16))) uint32_t cube[16 * 64];  // the chunk's centred bytes in DctShared::cube's layout
+    uint32_t words[2][2][32];          // [parity][window of the pair] ballot words
+    uint32_t dc[2][2][2];              // [parity][window of the pair][wave of the window]
+};
+
+// DWORDS: every frame starts on a dword boundary, as in dct_hash_windows_kernel.  taps_lo / taps_hi: tap(i) in byte i & 7 (i < 8: taps_lo).
+template <bool DWORDS>
+__global__ __launch_bounds__(256) void dct_hash_windows_retimed_kernel(WindowsSource src, uint32_t stride, uint32_t span, uint64_t taps_lo, uint64_t taps_hi,
+                                                                       uint32_t n_win, uint32_t per_seg, uint32_t n_seg, uint64_t first_group,
+                                                                       const double *__restrict__ cos_table, uint64_t *__restrict__ out_hashes,
+                                                                       uint32_t *__restrict__ out_dontcare)
+{
+    __shared__ WindowsRetimedShared sh;
+    const const_f64_ptr cosv = (const_f64_ptr)(uintptr_t)cos_table;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint64_t group = first_group + blockIdx.x;  // the launcher's grid holds no group past n_clips * n_seg
+    const size_t clip = (size_t)(group / n_seg);
+    const uint32_t seg = (uint32_t)(group - (uint64_t)clip * n_seg);
+    const uint32_t k_begin = seg * per_seg;                                                       // (n_seg * per_seg < n_win + per_seg <= 2^32)
+    const uint32_t k_end = (uint32_t)min((unsigned long long)k_begin + per_seg, (unsigned long long)n_win);
+    const uint32_t f_end = (k_end - 1) * stride + span;  // one past the last frame this workgroup reads: at most F
+    DctTw cm;
+#pragma unroll
+    for (int i = 0; i < 4; i++) { cm.t16[i][0] = cosv[256 + 2 * i]; cm.t16[i][1] = cosv[257 + 2 * i]; }
+#pragma unroll
+    for (int i = 0; i < 2; i++) { cm.t8[i][0] = cosv[264 + 2 * i]; cm.t8[i][1] = cosv[265 + 2 * i]; }
+    cm.t4[0] = cosv[268]; cm.t4[1] = cosv[269]; cm.h = cosv[270];
+    if (tid < 128) (&sh.words[0][0][0])[tid] = 0u;  // (the first OR is behind the barriers of the first chunk)
+
+    uint32_t k = k_begin, parity = 0;
+    const uint32_t run = k_begin * stride;  // the segment's first frame, slot 0 of the ring: its frames are one contiguous walk
+    uint32_t have = run;  // frames [max(run, have - 64), have) are resident; everything below is workgroup-uniform
+    while (k < k_end) {
+        const uint32_t s = k * stride;
+        while (have < s + span) {
+            // ---- the next chunk of 16 frames: frames at or past f_end are not read (their lanes repeat the last frame and store nothing)
+            {
+                const uint32_t t = tid >> 4, g = (tid >> 2) & 3, xq = tid & 3;
+                const uint32_t f = min(have + t, f_end - 1);
+                const uint8_t *p = f < src.main_frames
+                                       ? src.base + clip * src.clip_stride + (size_t)(f >> 4) * src.chunk_stride + (size_t)(f & 15u) * src.frame_stride
+                                       : src.tail + clip * src.tail_clip_stride + (size_t)(f - src.tail_first) * 256;
+                p += (4 * g) * 16 + 4 * xq;
+                uint32_t row[4];
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    uint32_t v;
+                    if constexpr (DWORDS) v = *reinterpret_cast<const uint32_t *>(p + r * 16);
+                    else v = (uint32_t)p[r * 16] | ((uint32_t)p[r * 16 + 1] << 8) | ((uint32_t)p[r * 16 + 2] << 16) | ((uint32_t)p[r * 16 + 3] << 24);
+                    row[r] = v ^ 0x80808080u;
+                }
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    uint32_t w = 0;
+#pragma unroll
+                    for (int r = 0; r < 4; r++) w |= ((row[r] >> (8 * c)) & 255u) << (8 * r);
+                    sh.cube[t * 64 + g * 16 + 4 * xq + c] = w;  // (last read: pass y of the previous chunk, two barriers ago)
+                }
+            }
+            __syncthreads();
+            {  // pass y: thread (t, x) owns one 16-pixel column
+                const uint32_t t = tid >> 4, x = tid & 15;
+                double v[16], o[10];
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    const int32_t w = (int32_t)sh.cube[t * 64 + g * 16 + x];
+#pragma unroll
+                    for (int r = 0; r < 4; r++) v[4 * g + r] = (double)((w << (24 - 8 * r)) >> 24);
+                }
+                dct16_pruned(v, o, cm);
+#pragma unroll
+                for (int ky = 0; ky < 10; ky++) sh.b[(t * 10 + ky) * kPadY + x] = o[ky];  // (last read: pass x of the previous chunk, one barrier ago)
+            }
+            __syncthreads();
+            if (tid < 160) {  // pass x: thread (t, ky) -> the frame's slot of the ring (last read: pass t of a window that starts 48 frames or more later)
+                double v[16], ox[10];
+#pragma unroll
+                for (int x = 0; x < 16; x++) v[x] = sh.b[tid * kPadY + x];
+                dct16_pruned(v, ox, cm);
+                const uint32_t t = tid / 10, ky = tid - 10 * t;
+                if (have + t < f_end) {
+                    const uint32_t slot = (have + t - run) & 63u;  // chunks begin at slot 0, 16, 32 or 48: dct_hash_block's bank pattern
+#pragma unroll
+                    for (int kx = 0; kx < 10; kx++) sh.c[slot * kStrideT + 10 * kx + ky] = ox[kx];
+                }
+            }
+            __syncthreads();
+            have += 16;
+        }
+        // ---- pass t + sign + pack for every window that is whole now, two at a time
+        const uint32_t k_ready = min(k_end, (have - span) / stride + 1);  // windows with s + span <= have (have >= s + span >= span)
+        for (uint32_t kp = k; kp < k_ready; kp += 2) {
+            const uint32_t half = wave >> 1, wv = wave & 1u, kk = kp + half;
+            if (kk < k_ready) {  // wave-uniform
+                const uint32_t rem = 64u * wv + lane;  // 10 kx + ky; lanes with rem >= 100 idle
+                const bool live = rem < 100;
+                const uint32_t at = live ? rem : 0, s0 = kk * stride - run;
+                double v[16], o[10];
+#pragma unroll
+                for (int t = 0; t < 16; t++) {
+                    const uint32_t tap = (uint32_t)((t < 8 ? taps_lo : taps_hi) >> (8 * (t & 7))) & 255u;  // wave-uniform: scalar
+                    v[t] = sh.c[((s0 + tap) & 63u) * kStrideT + at];
+                }
+                dct16_pruned(v, o, cm);
+                unsigned long long piece = 0;
+                uint32_t dc = 0;
+#pragma unroll
+                for (int kt = 0; kt < 10; kt++) {
+                    const unsigned long long bits = __builtin_amdgcn_ballot_w64(live && o[kt] > 0.0);  // 0.0 and NaN -> 0
+                    const unsigned long long tiny = __builtin_amdgcn_ballot_w64(live && fabs(o[kt]) < 1e-6);
+                    dc += (uint32_t)__builtin_popcountll(tiny);
+                    if (lane == (uint32_t)kt) piece = bits;
+                }
+                uint32_t *words = sh.words[parity][half];
+                if (lane < 10) {
+                    const uint32_t off = 100u * lane + 64u * wv, wi = off >> 5, sh_l = off & 31u;
+                    const uint32_t lo = (uint32_t)piece, hi = (uint32_t)(piece >> 32);
+                    atomicOr(&words[wi], lo << sh_l);
+                    atomicOr(&words[wi + 1], (hi << sh_l) | (sh_l ? lo >> (32u - sh_l) : 0u));
+                    if (sh_l && wi + 2 < 32) atomicOr(&words[wi + 2], hi >> (32u - sh_l));
+                }
+                if (lane == 0) sh.dc[parity][half][wv] = dc;
+            }
+            __syncthreads();
+            if ((tid & 127u) < 16) {  // the first 16 lanes of each window's first wave: store the words and clear them for the pair after the next
+                const uint32_t i = tid & 127u;
+                uint32_t *words = sh.words[parity][half];
+                const unsigned long long w = (unsigned long long)words[2 * i] | ((unsigned long long)words[2 * i + 1] << 32);
+                words[2 * i] = 0u;
+                words[2 * i + 1] = 0u;
+                if (kk < k_ready) {
+                    const size_t slot = clip * n_win + kk;
+                    out_hashes[slot * 16 + i] = w;
+                    if (out_dontcare && i == 0) out_dontcare[slot] = sh.dc[parity][half][0] + sh.dc[parity][half][1];
+                }
+            }
+            parity ^= 1u;
+        }
+        k = k_ready;
+    }
+}
+
+hipError_t launch_dct_hash_windows_retimed(const WindowsFrames &f, size_t n_clips, const WindowsRetimedPlan &plan, const double *cos_table,
+                                           uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream)
+{
+    if (n_clips == 0 || plan.n_win == 0) return hipSuccess;
+    const WindowsSource src{f.base, f.tail, f.clip_stride, f.chunk_stride, f.frame_stride, f.tail_clip_stride, f.main_frames, f.tail_first};
+    const uint64_t groups = retimed_groups(n_clips, plan);
+    for (uint64_t g0 = 0; g0 < groups; g0 += kMaxWindowGroupsPerLaunch) {
+        const uint32_t grid = retimed_grid(groups, g0);
+        if (f.dwords)
+            hipLaunchKernelGGL(dct_hash_windows_retimed_kernel<true>, dim3(grid), dim3(256), 0, stream, src, plan.stride, plan.span, plan.taps_lo, plan.taps_hi,
+                               plan.n_win, plan.per_seg, plan.n_seg, g0, cos_table, out_hashes, out_dontcare);
+        else
+            hipLaunchKernelGGL(dct_hash_windows_retimed_kernel<false>, dim3(grid), dim3(256), 0, stream, src, plan.stride, plan.span, plan.taps_lo, plan.taps_hi,
+                               plan.n_win, plan.per_seg, plan.n_seg, g0, cos_table, out_hashes, out_dontcare);
+    }
+    return hipGetLastError();
+}
+
 static MfmaResizeTables make_tables(const MfmaResizeArgs &a)
 {
     MfmaResizeTables T;

@@ -62,6 +62,26 @@ def _window_stride(stride) -> int:
     return s
 
 
+def _window_rate(rate):
+    """A rate (num, den) as the C ABI's two uint32_t take it.  Whether it is a rate the calls offer (1 <= den <= num <= 2 den, num <= 65535)
+    is the library's to say (VDF_E_INVAL); only what ctypes would wrap without a word is refused here."""
+    try:
+        num, den = rate
+        n, d = int(num), int(den)
+    except (TypeError, ValueError):
+        raise ValueError(f"rate must be a pair of integers (num, den), not {rate!r}") from None
+    if n != num or d != den or not (0 <= n < 2**32 and 0 <= d < 2**32):
+        raise ValueError(f"rate must be a pair of integers (num, den) in 0 .. 2^32 - 1, not {rate!r}")
+    return n, d
+
+
+def hash_window_count_retimed(n_frames: int, stride: int, rate) -> int:
+    """Retimed windows of a clip of n_frames frames (vdf_hash_window_count_retimed; host-only): 0 if the clip is shorter than a window's span
+    or the rate is not one the calls take."""
+    num, den = _window_rate(rate)
+    return int(_capi.load().vdf_hash_window_count_retimed(int(n_frames), _window_stride(stride), num, den))
+
+
 # one record of the align calls (include/vdf.h: vdf_alignment, 24 bytes)
 ALIGN_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("offset", "<i4"), ("start_a", "<u4"), ("n_windows", "<u4"), ("dist_sum", "<u4")])
 
@@ -570,6 +590,34 @@ class Engine:
         cs = fs * frames_per_clip if clip_stride is None else clip_stride
         self._check(self.lib.vdf_hash_windows_u8_device(self.ctx, d_frames, n_clips, frames_per_clip, w, h, fs, cs, stride, d_out,
                                                         d_dontcare or None, stream or None))
+
+    # --------------------------------------------- retimed windows: a copy at another frame rate or speed (include/vdf.h)
+    def hash_windows_retimed(self, frames: np.ndarray, rate, stride: int = 1, want_dontcare: bool = False):
+        """hash_windows at rate = (num, den), 1 <= den <= num <= 2 den: window k = the 16 frames k * stride + (i * num) // den, i = 0 .. 15,
+        n_win = (n_frames - span) // stride + 1 with span = (15 * num) // den + 1 (vdf_hash_windows_u8_retimed).  If B[j] = A[c + (j * num) // den],
+        window c + num * m of A at this rate is the plain window den * m of B.  Retime the side with more frames per second."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.ndim != 4:
+            raise ValueError("frames must be [n_clips, n_frames, H, W]")
+        nc, nf, h, w = frames.shape
+        stride = _window_stride(stride)
+        num, den = _window_rate(rate)
+        n_win = int(self.lib.vdf_hash_window_count_retimed(nf, stride, num, den))
+        out = np.zeros((nc, n_win, HASH_WORDS), np.uint64)
+        dc = np.zeros((nc, n_win), np.uint32) if want_dontcare else None
+        self._check(self.lib.vdf_hash_windows_u8_retimed(self.ctx, frames.ctypes.data, nc, nf, w, h, w * h, nf * w * h, stride, num, den,
+                                                         out.ctypes.data, dc.ctypes.data if want_dontcare else None))
+        return (out, dc) if want_dontcare else out
+
+    def hash_windows_retimed_device(self, d_frames: int, n_clips: int, frames_per_clip: int, w: int, h: int, stride: int, rate, d_out: int,
+                                    d_dontcare: int = 0, frame_stride: Optional[int] = None, clip_stride: Optional[int] = None, stream: int = 0):
+        """d_out: n_clips x n_win x 16 words (vdf_hash_window_count_retimed windows per clip); all frames_per_clip frames are used."""
+        stride = _window_stride(stride)
+        num, den = _window_rate(rate)
+        fs = w * h if frame_stride is None else frame_stride
+        cs = fs * frames_per_clip if clip_stride is None else clip_stride
+        self._check(self.lib.vdf_hash_windows_u8_retimed_device(self.ctx, d_frames, n_clips, frames_per_clip, w, h, fs, cs, stride, num, den, d_out,
+                                                                d_dontcare or None, stream or None))
 
     def hash_windows_planes(self, frames: np.ndarray, stride: int = 1, want_dontcare: bool = False):
         """hash_windows plus the zero plane of every window (vdf_hash_windows_u8_planes): -> (hashes [n_clips, n_win, 16] u64, zero

@@ -257,6 +257,44 @@ public:
         if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
     }
 
+    // Retimed windows (vdf_hash_windows_u8_retimed): hash_windows at rate_num / rate_den, 1 <= den <= num <= 2 den - window k =
+    // the 16 frames k * stride + floor(i * num / den), which is what a copy at den / num of the frame rate (or sped up num / den) holds in its
+    // plain windows.  Retime the side with more frames per second.
+    static std::vector<std::vector<VideoHash>> hash_windows_retimed(const uint8_t *frames, size_t n_videos, uint32_t frames_per_video, uint32_t w, uint32_t h,
+                                                                    uint32_t stride, uint32_t rate_num, uint32_t rate_den,
+                                                                    const std::vector<std::string> &src_paths, const std::vector<uint32_t> &durations,
+                                                                    Context *ctx_opt = nullptr)
+    {
+        if (src_paths.size() < n_videos || durations.size() < n_videos) throw std::invalid_argument("a path and a duration per video");
+        Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+        const size_t n_win = vdf_hash_window_count_retimed(frames_per_video, stride, rate_num, rate_den), fs = (size_t)w * h;
+        std::vector<uint64_t> words(n_videos * n_win * VDF_HASH_WORDS);
+        const int rc = vdf_hash_windows_u8_retimed(ctx.get(), frames, n_videos, frames_per_video, w, h, fs, fs * frames_per_video, stride, rate_num, rate_den,
+                                                   words.data(), nullptr);
+        if (rc == VDF_E_NOT_ENOUGH_FRAMES) throw Error::not_enough_frames();
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+        std::vector<std::vector<VideoHash>> out(n_videos);
+        for (size_t i = 0; i < n_videos; i++)
+            for (size_t k = 0; k < n_win; k++) {
+                std::array<uint64_t, VDF_HASH_WORDS> hw;
+                std::copy(words.begin() + (i * n_win + k) * VDF_HASH_WORDS, words.begin() + (i * n_win + k + 1) * VDF_HASH_WORDS, hw.begin());
+                out[i].emplace_back(hw, src_paths[i], durations[i]);
+            }
+        return out;
+    }
+    // The same on device memory: d_out = n_clips x vdf_hash_window_count_retimed(frames_per_clip, stride, rate_num, rate_den) x 16 words.
+    static void hash_windows_retimed_device(Context &ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h,
+                                            size_t frame_stride, size_t clip_stride, uint32_t stride, uint32_t rate_num, uint32_t rate_den, uint64_t *d_out,
+                                            uint32_t *d_dontcare = nullptr, void *stream = nullptr)
+    {
+        const int rc = vdf_hash_windows_u8_retimed_device(ctx.get(), d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, stride, rate_num,
+                                                          rate_den, d_out, d_dontcare, stream);
+        if (rc == VDF_E_NOT_ENOUGH_FRAMES) throw Error::not_enough_frames();
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+    }
+
     // Every window of videos of DIFFERENT frame sizes and lengths in one call (vdf_hash_windows_clips_u8): video i = n_frames
     // tightly packed gray frames of w x h, with an optional crop box {left, right, top, bottom} read in place.  Per video the VideoHash of
     // frames [k * stride, k * stride + 16); the lists differ in length.  The words are hash_windows' for each video alone.
