@@ -434,6 +434,69 @@ int vdf_align_windows_stretches_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_h
                                              uint32_t tol_int, uint32_t min_run, uint32_t max_stretches, uint32_t guard,
                                              vdf_alignment_stretch *out, size_t capacity, size_t *n_out, void *stream);
 
+/* ---- align RETIMED windows: a copy at another frame rate or speed, every phase in one call ---------------------
+ * Which of these videos is a 30 -> 25 fps or 1.5 x copy of which, and where.  A holds RETIMED windows at stride 1 (what
+ * vdf_hash_windows_u8_retimed* writes at rate_num / rate_den), B plain windows at stride 1; arrays as vdf_align_windows takes them: hashes,
+ * first[n + 1], nullable skip bytes.  The rate is rate_num / rate_den with 1 <= rate_den <= rate_num <= 2 rate_den; the call reduces it by its
+ * gcd to num / den, and num <= VDF_ALIGN_RETIMED_MAX_NUM after that (above it the sub-matrices below degenerate).  If B[j] = A[c + (j num) / den],
+ * retimed window c + num m of A equals plain window den m of B: the matching cells lie on a line of slope num / den, which
+ * vdf_align_windows does not follow.  So for a pair (a, b) of Na x Nb windows and every PHASE p = 0 ... num - 1:
+ *   - the SUB-MATRIX of phase p has the cells (i, j) = (row p + num i of a, row den j of b) for i < ceil((Na - p) / num) - none if p >= Na -
+ *     and j < ceil(Nb / den);
+ *   - a cell matches iff both skip bytes - read at those same rows - are 0 and the distance is <= tol = min(tol_int, 1024);
+ *   - runs, min_run, score and ties INSIDE a phase are vdf_align_windows' rule on the sub-matrix, word for word: a run is a maximal stretch
+ *     of matching cells on one diagonal offset = j - i, min_run counts sub-sampled windows, score = n (tol + 1) - dist_sum, ties go to the
+ *     smaller offset, then the smaller i0: the PHASE-BEST;
+ *   - ACROSS the phases the pair keeps the phase-best with the largest score; on a tie the smaller first_a = p + num i0, then the smaller
+ *     first_b = den (i0 + offset).  Two levels, each with its own tie rule: one comparator over all runs of all phases gives other records.
+ * At most ONE record per pair, in (a, b) order, under the capacity protocol of vdf_align_windows (*n_out is always the number found, the
+ * first `capacity` records are valid).  There is NO self mode: A and B are different hash sets even for one library (b_hashes == NULL with
+ * n_b > 0 is a null pointer); a library against itself is the _pairs form with the list a != b.  At rate 1 / 1 the records are
+ * vdf_align_windows' with first_a = start_a, first_b = start_a + offset.
+ * Errors, all VDF_E_INVAL: those of vdf_align_windows in their order (2^20 windows per video and 2^24 pairs per call included); then a rate
+ * outside 1 <= den <= num <= 2 den; then a reduced num above VDF_ALIGN_RETIMED_MAX_NUM; then a multi-GPU context.  The _pairs forms: a
+ * caller-given HOST list as vdf_align_windows_pairs* takes it (strictly increasing in (a, b), a < n_a, b < n_b), checked as there, the rate
+ * behind the align checks and before the list.  Each in the usual three forms: _host (plain C++, no context, no GPU: the CPU-tested
+ * statement of the semantics), host arrays through a context (uploaded as vdf_align_windows uploads them), _device (DEVICE arrays, out
+ * on the host; the call waits for its own work).  Skip bytes are read as the other align calls read them (the aligned 32-bit word).
+ * Not offered: window starts of B that are not multiples of den; several stretches per pair or flips; rates above 2. */
+#define VDF_ALIGN_RETIMED_MAX_NUM 32
+typedef struct vdf_alignment_retimed { /* 24 bytes */
+    uint32_t a;                /* video index in A */
+    uint32_t b;                /* video index in B */
+    uint32_t first_a;          /* the run's first (retimed) window of a: p + num i0 */
+    uint32_t first_b;          /* the run's first window of b: den (i0 + offset); the run's m-th cell is (first_a + num m, first_b + den m) */
+    uint32_t n_windows;        /* sub-sampled windows in the run */
+    uint32_t dist_sum;         /* sum of the run's distances */
+} vdf_alignment_retimed;
+int vdf_align_windows_retimed_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                   const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                                   uint32_t tol_int, uint32_t min_run, uint32_t rate_num, uint32_t rate_den,
+                                   vdf_alignment_retimed *out, size_t capacity, size_t *n_out);
+int vdf_align_windows_retimed(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                              const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                              uint32_t tol_int, uint32_t min_run, uint32_t rate_num, uint32_t rate_den,
+                              vdf_alignment_retimed *out, size_t capacity, size_t *n_out);
+int vdf_align_windows_retimed_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a,
+                                     const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b,
+                                     const uint8_t *d_b_skip, uint32_t tol_int, uint32_t min_run, uint32_t rate_num,
+                                     uint32_t rate_den, vdf_alignment_retimed *out, size_t capacity, size_t *n_out, void *stream);
+int vdf_align_windows_retimed_pairs_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                         const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                                         const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int, uint32_t min_run,
+                                         uint32_t rate_num, uint32_t rate_den, vdf_alignment_retimed *out, size_t capacity,
+                                         size_t *n_out);
+int vdf_align_windows_retimed_pairs(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                    const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip,
+                                    const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int, uint32_t min_run,
+                                    uint32_t rate_num, uint32_t rate_den, vdf_alignment_retimed *out, size_t capacity,
+                                    size_t *n_out);
+int vdf_align_windows_retimed_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a,
+                                           const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b,
+                                           const uint8_t *d_b_skip, const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int,
+                                           uint32_t min_run, uint32_t rate_num, uint32_t rate_den, vdf_alignment_retimed *out,
+                                           size_t capacity, size_t *n_out, void *stream);
+
 /* ---- mirrored, flipped and reversed STRETCHES: window hashes with their zero planes -----------------------
  * A mirrored re-upload with its intro trimmed: the variant search sees only frames 0 ... 15 of a file, the align calls only unflipped
  * stretches.  With the zero plane of every window (vdf_hash_windows_u8_planes*) the window hashes of the flipped video follow from the

@@ -10,6 +10,8 @@ import ctypes as C
 import os
 import sys
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libvdf_hip.so")
 
@@ -103,6 +105,16 @@ class VdfAlignmentVariant(C.Structure):
 class VdfAlignmentStretch(C.Structure):
     """One record of vdf_align_windows_stretches[_device|_host]: 28 bytes (the numpy twin is engine.ALIGN_STRETCH_DTYPE)."""
     _fields_ = VdfAlignment._fields_ + [("rank", C.c_uint32)]
+
+
+class VdfAlignmentRetimed(C.Structure):
+    """One record of vdf_align_windows_retimed*: 24 bytes (the numpy twin is ALIGN_RETIMED_DTYPE)."""
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("first_a", C.c_uint32), ("first_b", C.c_uint32), ("n_windows", C.c_uint32),
+                ("dist_sum", C.c_uint32)]
+
+
+ALIGN_RETIMED_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("first_a", "<u4"), ("first_b", "<u4"), ("n_windows", "<u4"), ("dist_sum", "<u4")])
+ALIGN_RETIMED_MAX_NUM = 32  # VDF_ALIGN_RETIMED_MAX_NUM
 
 
 class VdfVideoPair(C.Structure):
@@ -242,6 +254,18 @@ SIGNATURES = {
                                                                              C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vdf_align_windows_stretches_pairs_device": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                                                     C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    # the align calls' arguments with (rate_num, rate_den) behind min_run; out: vdf_alignment_retimed
+    "vdf_align_windows_retimed_host": (C.c_int, _ALIGN_SIDES + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vdf_align_windows_retimed": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                                     C.POINTER(C.c_size_t)]),
+    "vdf_align_windows_retimed_device": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                                            C.POINTER(C.c_size_t), C.c_void_p]),
+    "vdf_align_windows_retimed_pairs_host": (C.c_int, _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                                       C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vdf_align_windows_retimed_pairs": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                           C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "vdf_align_windows_retimed_pairs_device": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                                                  C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
     "vdf_cropdetect_letterbox_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                                   C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     "vdf_hash_frames_u8_cropped_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -21,6 +21,7 @@ from . import _capi
 from ._capi import DEFAULT_SEARCH_TOLERANCE, HASH_BITS, HASH_WORDS, TOLERANCE_SCALING_FACTOR, VdfError
 from .engine import (ALIGN_DTYPE, ALIGN_STRETCH_DTYPE, ALIGN_VARIANT_DTYPE, Engine, align_windows_host, align_windows_stretches_host, align_windows_variants_host, hamming_distance_words, hash_variant,
                      tolerance_int, video_pairs, align_seed_pairs_host, align_windows_pairs_host, align_windows_stretches_pairs_host,
+                     ALIGN_RETIMED_DTYPE, VIDEO_PAIR_DTYPE, align_windows_retimed_host, align_windows_retimed_pairs_host,
                      pair_list_problem, VIDEO_PAIR_VARIANT_DTYPE, align_seed_pairs_variants_host, align_windows_variants_pairs_host)
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
@@ -806,11 +807,83 @@ class RetimedAlignment(NamedTuple):
     path_b: object = None
 
 
-ALIGN_RETIMED_MAX_NUM = 32  # align_retimed makes `num` align calls
+ALIGN_RETIMED_MAX_NUM = 32  # align_retimed makes `num` align calls; = VDF_ALIGN_RETIMED_MAX_NUM (include/vdf.h), the native call's limit
+assert ALIGN_RETIMED_MAX_NUM == _capi.ALIGN_RETIMED_MAX_NUM
+
+
+def _retimed_call(engine, a, b, tol_int, min_run, rate, plist=None):
+    """_align_call for the retimed calls: one call of the C ABI (vdf_align_windows_retimed[_pairs][_host]), ALIGN_RETIMED_DTYPE in (a, b) order."""
+    def once(capacity):
+        kw = dict(tol_int=tol_int, min_run=min_run, a_skip=a[2], b_skip=b[2], capacity=capacity)
+        if plist is not None:
+            return (align_windows_retimed_pairs_host(a[0], a[1], plist, b[0], b[1], rate, **kw) if engine is None
+                    else engine.align_windows_retimed_pairs(a[0], a[1], plist, b[0], b[1], rate, **kw))
+        return align_windows_retimed_host(a[0], a[1], b[0], b[1], rate, **kw) if engine is None else engine.align_windows_retimed(a[0], a[1], b[0], b[1], rate, **kw)
+    rec, found = once(ALIGN_FIRST_CAPACITY)
+    if found > len(rec):
+        rec, found = once(found)
+    return rec
+
+
+def _align_retimed_native(windows_a, windows_b, num, den, tolerance, min_run, static_a, static_b, engine, seed, pairs):
+    """align_retimed(native=True): the CSR of both sides once, one call of vdf_align_windows_retimed* per block of at most ALIGN_MAX_PAIRS pairs.
+    -> ALIGN_RETIMED_DTYPE records in (a, b) order."""
+    tol_int = tolerance_int(tolerance)
+    wa, fa, ka, ca = _align_csr(windows_a, static_a)
+    wb, fb, kb, cb = _align_csr(windows_b, static_b)
+    pair_list = _align_pair_list(pairs, len(ca), len(cb), False)
+    if engine is None and sum(ca) * sum(cb) // den > ALIGN_HOST_CELLS:  # the cells a call walks: Na x Nb / den per pair
+        engine = default_engine()
+
+    def block(words, first, skip, lo, hi):
+        w0, w1 = int(first[lo]), int(first[hi])
+        return words[w0:w1], first[lo:hi + 1] - first[lo], None if skip is None else skip[w0:w1]
+
+    def sub(side, p, step):
+        """the windows p, p + step, ... of every video of a block - what ws[p::step] is to the lists - cut out of its arrays"""
+        words, first, skip = side
+        counts = np.diff(first.astype(np.int64))
+        video = np.repeat(np.arange(len(counts)), counts)
+        keep = (np.arange(len(words)) - first[:-1].astype(np.int64)[video]) % step == p
+        sub_first = np.zeros(len(first), np.uint32)
+        sub_first[1:] = np.cumsum(np.bincount(video[keep], minlength=len(counts)))
+        return words[keep], sub_first, None if skip is None else skip[keep]
+
+    key = lambda p: (p["a"].astype(np.uint64) << np.uint64(32)) | p["b"].astype(np.uint64)
+
+    def seeded(A, B, plist):
+        """the candidates of the block: the union over the phases of candidate_pairs' call (vdf_align_seed_pairs) on the sub-sampled sets - exact per
+        phase, so no pair with a record is lost - and of those the pairs on the caller's list"""
+        B0 = sub(B, 0, den)
+        keys = np.unique(np.concatenate([key(_seed_call(engine, sub(A, p, num), B0, tol_int, int(min_run))) for p in range(num)]))
+        cand = np.zeros(len(keys), VIDEO_PAIR_DTYPE)
+        cand["a"], cand["b"] = keys >> np.uint64(32), keys & np.uint64(0xFFFFFFFF)
+        return cand if plist is None else plist[np.isin(key(plist), keys)]
+
+    step = max(1, math.isqrt(ALIGN_MAX_PAIRS))
+    parts = []
+    for a0 in range(0, len(ca), step):
+        a1 = min(a0 + step, len(ca))
+        A = block(wa, fa, ka, a0, a1)
+        for b0 in range(0, len(cb), step):
+            b1 = min(b0 + step, len(cb))
+            B = block(wb, fb, kb, b0, b1)
+            plist = _block_pairs(engine, A, None, a0, a1, b0, b1, tol_int, int(min_run), pair_list, False)
+            if seed and (plist is None or len(plist)):
+                plist = seeded(A, B, plist)
+            if plist is not None and not len(plist):
+                continue
+            rec = _retimed_call(engine, A, B, tol_int, int(min_run), (num, den), plist).copy()
+            rec["a"] += a0
+            rec["b"] += b0
+            parts.append(rec)
+    rec = np.concatenate(parts) if parts else np.zeros(0, ALIGN_RETIMED_DTYPE)
+    return rec[np.lexsort((rec["b"], rec["a"]))]
 
 
 def align_retimed(windows_a: List[List[VideoHash]], windows_b: List[List[VideoHash]], rate, tolerance: float = DEFAULT_SEARCH_TOLERANCE,
-                  min_run: int = 1, static_a=None, static_b=None, engine: Optional[Engine] = None, seed: bool = False) -> List[RetimedAlignment]:
+                  min_run: int = 1, static_a=None, static_b=None, engine: Optional[Engine] = None, seed: bool = False, native: bool = False,
+                  pairs=None) -> List[RetimedAlignment]:
     """Which videos of A share a stretch with a video of B that runs at den / num of A's frames - a re-encode from 30 to 25 fps (rate 6/5), a
     1.5 x re-upload (3/2), every other frame (2/1)?  windows_a: hash_frame_windows(..., rate=rate) at stride 1; windows_b: plain windows at
     stride 1.  If B[j] = A[c + (j * num) // den], retimed window c + num * m of A equals plain window den * m of B: the matching cells of the
@@ -819,7 +892,11 @@ def align_retimed(windows_a: List[List[VideoHash]], windows_b: List[List[VideoHa
     record that maximises n_windows * (tol_int + 1) - sum of distances is kept (ties: the smaller first_frame_a, then first_frame_b).
     A true stretch holds a window of B at a multiple of den, so B's phase 0 is enough: the stretch is found with its ends rounded inward by
     less than den frames of B, and Na * Nb / den cells are walked.  min_run counts sub-sampled windows.  The rate is reduced by its gcd;
-    num > 32 is refused (the call makes num sub-calls).  No self mode.  -> one RetimedAlignment per pair at most, ordered by (a, b)."""
+    num > 32 is refused (the call makes num sub-calls).  No self mode.  -> one RetimedAlignment per pair at most, ordered by (a, b).
+    native=True: the same list from ONE call of the C ABI per block of at most ALIGN_MAX_PAIRS pairs (vdf_align_windows_retimed*):
+    the CSR is built once and every phase of every pair is a unit of one launch.  With seed=True the candidates of the sub-sampled sets
+    (candidate_pairs) are united over the phases and one call on that list is made.  With no engine given, tiny inputs are walked on the CPU.
+    pairs: only these (a, b) are aligned - strictly increasing in (a, b), as `align` takes them."""
     try:
         num, den = (int(x) for x in rate)
         if (num, den) != tuple(rate):
@@ -833,6 +910,15 @@ def align_retimed(windows_a: List[List[VideoHash]], windows_b: List[List[VideoHa
     if num > ALIGN_RETIMED_MAX_NUM:
         raise ValueError(f"align_retimed makes num sub-calls: num = {num} is above {ALIGN_RETIMED_MAX_NUM}")
     span = (15 * num) // den + 1
+    pa = [ws[0].src_path() if ws else None for ws in windows_a]
+    pb = [ws[0].src_path() if ws else None for ws in windows_b]
+    if native:
+        rec = _align_retimed_native(windows_a, windows_b, num, den, tolerance, min_run, static_a, static_b, engine, seed, pairs)
+        out = []
+        for r in rec:
+            a, b, fa, fb, n, ds = (int(r[k]) for k in ("a", "b", "first_a", "first_b", "n_windows", "dist_sum"))
+            out.append(RetimedAlignment(a, b, num, den, fa, fb, (n - 1) * num + span, (n - 1) * den + _capi.DCT_SIZE, n, ds / n, pa[a], pb[b]))
+        return out
     tol_int = tolerance_int(tolerance)
     sub_b = [ws[0::den] for ws in windows_b]
     st_b = None if static_b is None else [np.asarray(f).reshape(-1)[0::den] for f in static_b]
@@ -840,14 +926,12 @@ def align_retimed(windows_a: List[List[VideoHash]], windows_b: List[List[VideoHa
     for p in range(num):
         sub_a = [ws[p::num] for ws in windows_a]
         st_a = None if static_a is None else [np.asarray(f).reshape(-1)[p::num] for f in static_a]
-        for al in align(sub_a, sub_b, tolerance, min_run=min_run, stride=1, static_a=st_a, static_b=st_b, engine=engine, seed=seed):
+        for al in align(sub_a, sub_b, tolerance, min_run=min_run, stride=1, static_a=st_a, static_b=st_b, engine=engine, seed=seed, pairs=pairs):
             n, i0 = al.n_windows, al.first_frame_a
             dist_sum = int(round(al.mean_distance * n))
             rec = (-(n * (tol_int + 1) - dist_sum), p + num * i0, den * al.first_frame_b, n, dist_sum)
             if (al.a, al.b) not in best or rec < best[(al.a, al.b)]:
                 best[(al.a, al.b)] = rec
-    pa = [ws[0].src_path() if ws else None for ws in windows_a]
-    pb = [ws[0].src_path() if ws else None for ws in windows_b]
     return [RetimedAlignment(a, b, num, den, fa, fb, (n - 1) * num + span, (n - 1) * den + _capi.DCT_SIZE, n, ds / n, pa[a], pb[b])
             for (a, b), (_, fa, fb, n, ds) in sorted(best.items())]
 

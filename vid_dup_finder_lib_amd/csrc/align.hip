@@ -19,7 +19,10 @@
 // align_class_layout_kernel / align_seed_variants_kernel / align_seed_variants_scatter_kernel, behind them: the same question against the
 // mirrored, flipped and reversed variants of B, every requested variant from one pass over the seeds (vdf_align_seed_pairs_variants*;
 // DESIGN.md 4.14; window_class_layout.h).
+// align_bands_retimed_kernel / align_reduce_retimed_kernel, behind launch_align_chunk: the band walk on the strided rows of a phase's sub-matrix
+// and the two-level reduction bands -> phase-best -> pair record (vdf_align_windows_retimed*; align_retimed_plan.h).
 #include "align_plan.h"
+#include "align_retimed_plan.h"
 #include "vdf_internal.h"
 #include "window_class_layout.h"
 
@@ -363,6 +366,170 @@ hipError_t launch_align_chunk(const AlignLaunch &L, hipStream_t stream)
     hipLaunchKernelGGL(align_scatter_kernel, dim3(n_blocks), dim3(256), 0, stream, pair_records, L.n_pairs, block_offset, dense);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     *L.dense_out = dense;
+    *L.total_out = total;
+    return hipSuccess;
+}
+
+// ---- retimed windows: every phase's sub-matrix of every pair in one launch (include/vdf.h: vdf_align_windows_retimed*) -----------
+// align_bands_retimed_kernel: the plain kernel's walk on the sub-matrix of one phase p of one pair (align_retimed_plan.h) - a kernel of its own,
+// so that the plain kernel's text and code stay what they were.  A unit is (pair, phase, band): one wave serves one band of 64 diagonals of
+// the Na_p x Nb_0 cells (i, j) = (row p + num i of a, row den j of b).  ka, kb, d0, the lanes, the rotation and the reload are the plain
+// kernel's in sub-matrix coordinates; only the addresses differ: the row of A at step ka is fa + p + num ka (wave-uniform: scalar loads),
+// lane kb mod 64 holds row fb + den kb, and the skip bytes are read at those same rows - A's with the aligned dword that holds it, which the
+// stride lands on any of its four bytes.  The band record holds (offset = j - i, i0, n, sum) of the sub-matrix; the phases meet in the reduction.
+__global__ __launch_bounds__(256) void align_bands_retimed_kernel(
+    const uint32_t *__restrict__ a_hashes, const uint32_t *__restrict__ a_first, const uint8_t *__restrict__ a_skip,
+    const uint32_t *__restrict__ b_hashes, const uint32_t *__restrict__ b_first, const uint8_t *__restrict__ b_skip,
+    const AlignPair *__restrict__ pairs, const uint32_t *__restrict__ unit_offset, uint32_t n_pairs, uint32_t n_units, uint32_t tol,
+    uint32_t min_run, AlignBandRecord *__restrict__ band_records, uint32_t group_base, uint32_t num, uint32_t den)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t unit = (blockIdx.x + group_base) * kAlignWaves + wave;  // grids above 2^32 work-items are launched in cuts
+    if (unit >= n_units) return;
+
+    const uint32_t p = align_unit_pair((align_u32_ptr)(uintptr_t)unit_offset, n_pairs, unit);
+    const uint32_t va = ((align_u32_ptr)(uintptr_t)pairs)[2 * p], vb = ((align_u32_ptr)(uintptr_t)pairs)[2 * p + 1];
+    const uint32_t fa = ((align_u32_ptr)(uintptr_t)a_first)[va], Na_all = ((align_u32_ptr)(uintptr_t)a_first)[va + 1] - fa;
+    const uint32_t fb = ((align_u32_ptr)(uintptr_t)b_first)[vb], Nb_all = ((align_u32_ptr)(uintptr_t)b_first)[vb + 1] - fb;
+    uint32_t phase, band;
+    align_retimed_unit(align_retimed_split(Na_all, Nb_all, num, den), unit - ((align_u32_ptr)(uintptr_t)unit_offset)[p], &phase, &band);
+    const uint32_t Na = align_retimed_na(Na_all, num, phase), Nb = align_retimed_nb(Nb_all, den);  // the sub-matrix
+    const int32_t d0 = align_band_d0(Na, band);
+    const uint32_t ka0 = align_ka_begin(d0), ka1 = align_ka_end(Na, Nb, d0);
+
+    const uint32_t *b_rows = b_hashes + (size_t)fb * 32;
+    const uint8_t *b_sk = b_skip ? b_skip + fb : nullptr;
+    align_u32_ptr a_rows = (align_u32_ptr)(uintptr_t)a_hashes + (size_t)fa * 32;
+
+    // this lane's row of B; cells outside the sub-matrix are misses and no address is formed for them
+    uint32_t rw[32];
+    int32_t kb = align_lane_row(lane, ka0, d0);
+    bool row_ok = kb >= 0 && kb < (int32_t)Nb;
+    uint32_t row_skip = 0;  // the row's skip byte: compared where the row is used, so that the load is not waited for where it is issued
+    if (row_ok) {
+        const uint32_t rb = align_retimed_row_b(den, (uint32_t)kb);  // < Nb_all
+        if (b_sk) row_skip = b_sk[rb];
+        align_load_row(rw, b_rows, rb);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 32; q++) rw[q] = 0u;
+    }
+
+    uint32_t len = 0, sum = 0;                                              // the run of the diagonal this lane is on
+    uint32_t best_score = 0, best_start = 0, best_n = 0, best_sum = 0;     // score 0 = none: every run scores at least 1
+    int32_t best_off = 0;
+    for (uint32_t ka = ka0; ka < ka1; ++ka) {
+        const uint32_t ra = align_retimed_row_a(phase, num, ka);  // < Na_all, wave-uniform
+        align_u32_ptr ap = a_rows + (size_t)ra * 32;
+        uint32_t d = 0;
+#pragma unroll
+        for (int w = 0; w < 32; ++w) d += __builtin_popcount(rw[w] ^ ap[w]);  // ap[w]: SGPR
+        bool a_ok = true;  // wave-uniform: the skip byte of A's row comes with the aligned dword that holds it, by a scalar load like the row
+        if (a_skip) {
+            const uintptr_t at = (uintptr_t)a_skip + fa + ra;
+            a_ok = ((*(align_u32_ptr)(at & ~(uintptr_t)3) >> (8 * (uint32_t)(at & 3))) & 0xFFu) == 0u;
+        }
+        const bool match = row_ok && row_skip == 0 && a_ok && d <= tol;
+        if (match) { len += 1; sum += d; }
+        const bool edge = ka + 1 == Na || kb + 1 == (int32_t)Nb;              // the diagonal's last cell
+        const bool ends = len != 0 && (!match || edge);
+        if (__builtin_amdgcn_ballot_w64(ends) != 0ull) {
+            if (ends && len >= min_run) {
+                const uint32_t score = len * (tol + 1) - sum;
+                const uint32_t start = (match ? ka + 1 : ka) - len;
+                const int32_t off = kb - (int32_t)ka;
+                if (align_better(score, off, start, best_score, best_off, best_start)) {
+                    best_score = score; best_off = off; best_start = start; best_n = len; best_sum = sum;
+                }
+            }
+            if (ends) { len = 0; sum = 0; }
+        }
+        // the state follows its diagonal one lane up
+        len = align_rotate_up(len, lane);
+        sum = align_rotate_up(sum, lane);
+        // the lane whose diagonal d0 is done takes the row of diagonal d0 + 63 of the next step
+        if (ka + 1 < ka1 && lane == align_reload_lane(ka, d0)) {
+            kb += (int32_t)kAlignBand;  // = align_reload_row(ka, d0) >= 1, from the lane's own register: the address stays a vector address
+            row_ok = kb < (int32_t)Nb;
+            row_skip = 0;
+            if (row_ok) {
+                const uint32_t rb = align_retimed_row_b(den, (uint32_t)kb);
+                if (b_sk) row_skip = b_sk[rb];
+                align_load_row(rw, b_rows, rb);
+            }
+        }
+    }
+
+    // the wave's best of its 64 lane-bests; every run has its own (score, offset, start)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t o_score = (uint32_t)__shfl_xor((int)best_score, o, 64), o_start = (uint32_t)__shfl_xor((int)best_start, o, 64);
+        const uint32_t o_n = (uint32_t)__shfl_xor((int)best_n, o, 64), o_sum = (uint32_t)__shfl_xor((int)best_sum, o, 64);
+        const int32_t o_off = __shfl_xor(best_off, o, 64);
+        if (align_better(o_score, o_off, o_start, best_score, best_off, best_start)) {
+            best_score = o_score; best_off = o_off; best_start = o_start; best_n = o_n; best_sum = o_sum;
+        }
+    }
+    if (lane == 0) band_records[unit] = AlignBandRecord{best_off, best_start, best_score ? best_n : 0u, best_sum};
+}
+
+// one thread per pair of the chunk: its bands -> the best of every phase (align_better) -> the best of the phase-bests (align_retimed_plan.h:
+// align_retimed_reduce, the text the plain C++ definition runs) -> pair_records (n_windows = 0: none); block_count[g] = pairs with a record
+__global__ __launch_bounds__(256) void align_reduce_retimed_kernel(const AlignPair *__restrict__ pairs, const uint32_t *__restrict__ unit_offset,
+                                                                   uint32_t n_pairs, const uint32_t *__restrict__ a_first,
+                                                                   const uint32_t *__restrict__ b_first, uint32_t num, uint32_t den, uint32_t tol,
+                                                                   const AlignBandRecord *__restrict__ band_records,
+                                                                   vdf_alignment_retimed *__restrict__ pair_records, uint32_t *__restrict__ block_count)
+{
+    __shared__ uint32_t s_wave[4];
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    bool has = false;
+    if (p < n_pairs) {
+        const AlignPair ab = pairs[p];
+        const AlignRetimedSplit sp = align_retimed_split(a_first[ab.a + 1] - a_first[ab.a], b_first[ab.b + 1] - b_first[ab.b], num, den);
+        const AlignRetimedBest best = align_retimed_reduce(band_records + unit_offset[p], sp, den, tol);
+        has = best.score != 0;
+        pair_records[p] = vdf_alignment_retimed{ab.a, ab.b, best.first_a, best.first_b, has ? best.n_windows : 0u, best.dist_sum};
+    }
+    uint32_t total;
+    (void)align_block_rank(has, s_wave, &total);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+
+// vdf_alignment_retimed is vdf_alignment with (first_a, first_b) where (offset, start_a) are: the scan and the scatter run on it as they are
+static_assert(sizeof(vdf_alignment_retimed) == sizeof(vdf_alignment) && offsetof(vdf_alignment_retimed, n_windows) == offsetof(vdf_alignment, n_windows),
+              "align_scatter_kernel reads n_windows of either record");
+
+hipError_t launch_align_retimed_chunk(const AlignLaunch &L, uint32_t num, uint32_t den, vdf_alignment_retimed **dense_out, hipStream_t stream)
+{
+    if (L.n_pairs == 0 || L.n_units == 0 || L.n_rects || num == 0 || den == 0 || num > kAlignRetimedMaxNum) return hipErrorInvalidValue;
+    // scratch: band records | pair records | dense records | block counts | block offsets | total (align_scratch_bytes)
+    char *s = static_cast<char *>(L.scratch);
+    AlignBandRecord *band_records = reinterpret_cast<AlignBandRecord *>(s);
+    s += (size_t)L.n_units * sizeof(AlignBandRecord);
+    vdf_alignment_retimed *pair_records = reinterpret_cast<vdf_alignment_retimed *>(s);
+    s += (size_t)L.n_pairs * sizeof(vdf_alignment_retimed);
+    vdf_alignment_retimed *dense = reinterpret_cast<vdf_alignment_retimed *>(s);
+    s += (size_t)L.n_pairs * sizeof(vdf_alignment_retimed);
+    const uint32_t n_blocks = (L.n_pairs + 255) / 256;
+    uint32_t *block_count = reinterpret_cast<uint32_t *>(s), *block_offset = block_count + n_blocks, *total = block_offset + n_blocks;
+
+    const size_t n_groups = ((size_t)L.n_units + kAlignWaves - 1) / kAlignWaves;
+    for (const AlignLaunchCut &cut : align_launch_cuts(n_groups)) {
+        hipLaunchKernelGGL(align_bands_retimed_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_first, L.a_skip, L.b_hashes, L.b_first,
+                           L.b_skip, L.pairs, L.unit_offset, L.n_pairs, L.n_units, L.tol, L.min_run, band_records, (uint32_t)cut.group_base, num, den);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(align_reduce_retimed_kernel, dim3(n_blocks), dim3(256), 0, stream, L.pairs, L.unit_offset, L.n_pairs, L.a_first, L.b_first, num, den,
+                       L.tol, band_records, pair_records, block_count);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(align_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, n_blocks, block_offset, total);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(align_scatter_kernel, dim3(n_blocks), dim3(256), 0, stream, reinterpret_cast<const vdf_alignment *>(pair_records), L.n_pairs,
+                       block_offset, reinterpret_cast<vdf_alignment *>(dense));
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    *dense_out = dense;
     *L.total_out = total;
     return hipSuccess;
 }

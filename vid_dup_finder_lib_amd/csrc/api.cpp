@@ -1931,6 +1931,103 @@ int align_seed_locked(vdf_ctx *ctx, const AlignSides &in, uint32_t tol_int, uint
     return VDF_OK;
 }
 
+// ---- retimed windows aligned in one call (include/vdf.h: vdf_align_windows_retimed*; align_retimed_plan.h) -----------------------
+// behind align_checks: the rate, reduced by its gcd into *num / *den
+int align_retimed_checks(vdf_ctx *ctx, uint32_t rate_num, uint32_t rate_den, uint32_t *num, uint32_t *den)
+{
+    switch (vdf::align_retimed_rate(rate_num, rate_den, num, den)) {
+    case 1: return fail(ctx, VDF_E_INVAL, "the rate must have 1 <= den <= num <= 2 den");
+    case 2: return fail(ctx, VDF_E_INVAL, "the rate's num is above 32 in lowest terms (VDF_ALIGN_RETIMED_MAX_NUM)");
+    default: return VDF_OK;
+    }
+}
+
+// the literal definition for one pair: every phase's sub-matrix walked diagonal by diagonal on the strided rows, XOR + popcount; every
+// diagonal leaves its best run as a band record would, and the header's reduction - the one the kernel's records go through - picks the
+// phase-bests and the pair's record.  best->n_windows = 0: no competing run
+void align_retimed_pair_host(const uint64_t *A, uint32_t Na, const uint8_t *skip_a, const uint64_t *B, uint32_t Nb, const uint8_t *skip_b, uint32_t num,
+                             uint32_t den, uint32_t tol, uint32_t min_run, vdf_alignment_retimed *best)
+{
+    const uint32_t nb0 = vdf::align_retimed_nb(Nb, den);
+    vdf::AlignRetimedBest pair{0u, 0u, 0u, 0u, 0u};
+    for (uint32_t p = 0; p < num; p++) {
+        const uint32_t na = vdf::align_retimed_na(Na, num, p);
+        if (na == 0 || nb0 == 0) continue;
+        vdf_alignment ph{};  // the phase-best: align_pair_host's walk with the rows behind (i, j)
+        uint32_t ph_score = 0;
+        for (int64_t d = -((int64_t)na - 1); d <= (int64_t)nb0 - 1; d++) {
+            const int64_t i0 = std::max<int64_t>(0, -d), i1 = std::min<int64_t>(na, (int64_t)nb0 - d);
+            uint32_t len = 0, sum = 0;
+            for (int64_t i = i0; i <= i1; i++) {  // i1: the cell behind the diagonal's last, a miss
+                bool match = false;
+                uint32_t dist = 0;
+                if (i < i1) {
+                    const size_t ra = vdf::align_retimed_row_a(p, num, (uint32_t)i), rb = vdf::align_retimed_row_b(den, (uint32_t)(i + d));
+                    if (!(skip_a && skip_a[ra]) && !(skip_b && skip_b[rb])) {
+                        const uint64_t *x = A + 16 * ra, *y = B + 16 * rb;
+                        for (int w = 0; w < VDF_HASH_WORDS; w++) dist += (uint32_t)__builtin_popcountll(x[w] ^ y[w]);
+                        match = dist <= tol;
+                    }
+                }
+                if (match) { len++; sum += dist; continue; }
+                if (len >= min_run) {
+                    const uint32_t score = len * (tol + 1) - sum, start = (uint32_t)(i - len);
+                    if (vdf::align_better(score, (int32_t)d, start, ph_score, ph.offset, ph.start_a)) {
+                        ph_score = score; ph.offset = (int32_t)d; ph.start_a = start; ph.n_windows = len; ph.dist_sum = sum;
+                    }
+                }
+                len = 0; sum = 0;
+            }
+        }
+        if (ph_score == 0) continue;
+        const uint32_t first_a = vdf::align_retimed_row_a(p, num, ph.start_a), first_b = vdf::align_retimed_row_b(den, (uint32_t)((int32_t)ph.start_a + ph.offset));
+        if (vdf::align_retimed_better(ph_score, first_a, first_b, pair)) pair = vdf::AlignRetimedBest{ph_score, first_a, first_b, ph.n_windows, ph.dist_sum};
+    }
+    best->first_a = pair.first_a; best->first_b = pair.first_b; best->n_windows = pair.score ? pair.n_windows : 0u; best->dist_sum = pair.dist_sum;
+}
+
+// align_locked for the retimed call: the chunks hold (pair, phase, band) units; num / den in lowest terms.  `in` is never self.
+int align_retimed_locked(vdf_ctx *ctx, const AlignSides &in, uint32_t tol_int, uint32_t min_run, uint32_t num, uint32_t den, vdf_alignment_retimed *out,
+                         size_t capacity, size_t *n_out, hipStream_t s, const vdf_video_pair *list = nullptr, size_t n_list = 0)
+{
+    vdf::AlignCursor cur;
+    vdf::AlignChunk ch;
+    size_t found = 0, list_at = 0;
+    while (list ? vdf::align_retimed_next_chunk_pairs(in.h_first_a, in.h_first_b, list, n_list, num, den, list_at, ch)
+                : vdf::align_retimed_next_chunk(in.h_first_a, in.n_a, in.h_first_b, in.n_b, num, den, cur, ch)) {
+        const size_t n_pairs = ch.pairs.size(), n_units = ch.n_units();
+        const size_t pair_bytes = n_pairs * sizeof(vdf::AlignPair), off_bytes = (n_pairs + 1) * sizeof(uint32_t);
+        VDF_HIP(ctx, ctx->align_plan.reserve(pair_bytes + off_bytes));
+        VDF_HIP(ctx, ctx->align_scratch.reserve(vdf::align_scratch_bytes(n_pairs, n_units)));
+        char *plan = ctx->align_plan.as<char>();
+        VDF_HIP(ctx, hipMemcpyAsync(plan, ch.pairs.data(), pair_bytes, hipMemcpyHostToDevice, s));
+        VDF_HIP(ctx, hipMemcpyAsync(plan + pair_bytes, ch.unit_offset.data(), off_bytes, hipMemcpyHostToDevice, s));
+        vdf_alignment_retimed *d_dense = nullptr;
+        uint32_t *d_total = nullptr;
+        vdf::AlignLaunch L{};
+        L.a_hashes = reinterpret_cast<const uint32_t *>(in.d_a_hashes); L.a_first = in.d_a_first; L.a_skip = in.d_a_skip;
+        L.b_hashes = reinterpret_cast<const uint32_t *>(in.d_b_hashes); L.b_first = in.d_b_first; L.b_skip = in.d_b_skip;
+        L.pairs = reinterpret_cast<const vdf::AlignPair *>(plan);
+        L.unit_offset = reinterpret_cast<const uint32_t *>(plan + pair_bytes);
+        L.n_pairs = (uint32_t)n_pairs; L.n_units = (uint32_t)n_units;
+        L.tol = std::min<uint32_t>(tol_int, 1024u); L.min_run = min_run;
+        L.scratch = ctx->align_scratch.p; L.total_out = &d_total;
+        VDF_HIP(ctx, vdf::launch_align_retimed_chunk(L, num, den, &d_dense, s));
+        uint32_t total = 0;
+        VDF_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, s));
+        VDF_HIP(ctx, hipStreamSynchronize(s));  // also: the chunk's plan arrays are free to change
+        if (total > n_pairs) return fail(ctx, VDF_E_HIP, "align retimed: more records than pairs");
+        const size_t room = capacity > found ? capacity - found : 0, take = std::min<size_t>(total, room);
+        if (take) {
+            VDF_HIP(ctx, hipMemcpyAsync(out + found, d_dense, take * sizeof(vdf_alignment_retimed), hipMemcpyDeviceToHost, s));
+            VDF_HIP(ctx, hipStreamSynchronize(s));
+        }
+        found += total;
+    }
+    *n_out = found;
+    return VDF_OK;
+}
+
 }  // namespace vdf_impl
 
 using namespace vdf_impl;
@@ -2480,6 +2577,156 @@ int vdf_align_windows_stretches_pairs(vdf_ctx *ctx, const uint64_t *a_hashes, co
 {
     return align_pairs_ctx_impl(ctx, "vdf_align_windows_stretches_pairs", a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, pairs, n_pairs, tol_int,
                                 min_run, true, max_stretches, guard, nullptr, out, capacity, n_out);
+}
+
+// ---- retimed windows aligned in one call ------------------------------------------------------------------------------------------
+// The checks of the six forms, in the order include/vdf.h gives them; `listed`: a *_pairs form.  first arrays on the host, or null (a device
+// form before they have come down).  *num / *den: the rate in lowest terms.
+static int align_retimed_all_checks(vdf_ctx *ctx, const char *name, const void *a_hashes, const uint32_t *a_first, size_t n_a, const void *b_hashes,
+                                    const uint32_t *b_first, size_t n_b, const void *a_first_ptr, const void *b_first_ptr, const vdf_video_pair *pairs,
+                                    size_t n_pairs, bool listed, uint32_t min_run, uint32_t rate_num, uint32_t rate_den, uint32_t *num, uint32_t *den,
+                                    const void *out, size_t capacity, const size_t *n_out, bool device_ctx)
+{
+    if (listed && n_pairs && !pairs) return fail(ctx, VDF_E_INVAL, "null pair list");
+    // no self mode: a missing B is a null pointer like any other (an empty B may come without hashes)
+    if (!b_hashes && n_b) return fail(ctx, VDF_E_INVAL, "null pointer");
+    static const uint64_t no_hashes = 0;
+    if (int rc = align_checks(ctx, a_hashes, a_first, n_a, b_hashes ? b_hashes : &no_hashes, b_first, n_b, a_first_ptr, b_first_ptr, min_run, out, capacity,
+                              n_out, listed ? &n_pairs : nullptr))
+        return rc;
+    if (int rc = align_retimed_checks(ctx, rate_num, rate_den, num, den)) return rc;
+    if (listed)
+        if (int rc = align_list_checks(ctx, pairs, n_pairs, n_a, n_b, false)) return rc;
+    if (device_ctx && !ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, std::string(name) + " takes a single-device context");
+    return VDF_OK;
+}
+
+static int align_retimed_host_impl(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                                   const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, const vdf_video_pair *pairs, size_t n_pairs, bool listed,
+                                   uint32_t tol_int, uint32_t min_run, uint32_t rate_num, uint32_t rate_den, vdf_alignment_retimed *out, size_t capacity,
+                                   size_t *n_out)
+{
+    uint32_t num = 1, den = 1;
+    if (int rc = align_retimed_all_checks(nullptr, "", a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, pairs, n_pairs, listed, min_run,
+                                          rate_num, rate_den, &num, &den, out, capacity, n_out, false))
+        return rc;
+    const uint32_t tol = std::min<uint32_t>(tol_int, 1024u);
+    size_t found = 0;
+    const auto pair = [&](uint32_t a, uint32_t b) {
+        vdf_alignment_retimed r;
+        align_retimed_pair_host(a_hashes + 16 * (size_t)a_first[a], a_first[a + 1] - a_first[a], a_skip ? a_skip + a_first[a] : nullptr,
+                                b_hashes + 16 * (size_t)b_first[b], b_first[b + 1] - b_first[b], b_skip ? b_skip + b_first[b] : nullptr, num, den, tol, min_run,
+                                &r);
+        if (r.n_windows == 0) return;
+        r.a = a; r.b = b;
+        if (found < capacity) out[found] = r;
+        found++;
+    };
+    if (listed)
+        for (size_t i = 0; i < n_pairs; i++) pair(pairs[i].a, pairs[i].b);
+    else
+        for (size_t a = 0; a < n_a; a++)
+            for (size_t b = 0; b < n_b; b++) pair((uint32_t)a, (uint32_t)b);
+    *n_out = found;
+    return VDF_OK;
+}
+
+static int align_retimed_device_impl(vdf_ctx *ctx, const char *name, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a, const uint8_t *d_a_skip,
+                                     const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip, const vdf_video_pair *pairs,
+                                     size_t n_pairs, bool listed, uint32_t tol_int, uint32_t min_run, uint32_t rate_num, uint32_t rate_den,
+                                     vdf_alignment_retimed *out, size_t capacity, size_t *n_out, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    uint32_t num = 1, den = 1;
+    // everything that can be said without the first arrays - the multi-GPU refusal last; then they come down and are checked
+    if (int rc = align_retimed_all_checks(ctx, name, d_a_hashes, nullptr, n_a, d_b_hashes, nullptr, n_b, d_a_first, d_b_first, pairs, n_pairs, listed, min_run,
+                                          rate_num, rate_den, &num, &den, out, capacity, n_out, true))
+        return rc;
+    *n_out = 0;
+    if (listed ? n_pairs == 0 : (n_a == 0 || n_b == 0)) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<uint32_t> fa, fb;
+    if (int rc = align_first_down(ctx, d_a_first, n_a, d_b_first, n_b, false, s, fa, fb)) return rc;
+    if (int rc = align_checks(ctx, d_a_hashes, fa.data(), n_a, d_b_hashes, fb.data(), n_b, d_a_first, d_b_first, min_run, out, capacity, n_out,
+                              listed ? &n_pairs : nullptr))
+        return rc;
+    const AlignSides in{d_a_hashes, d_a_first, fa.data(), n_a, d_a_skip, d_b_hashes, d_b_first, fb.data(), n_b, d_b_skip, false};
+    return align_retimed_locked(ctx, in, tol_int, min_run, num, den, out, capacity, n_out, s, listed ? pairs : nullptr, n_pairs);
+}
+
+static int align_retimed_ctx_impl(vdf_ctx *ctx, const char *name, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                  const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, const vdf_video_pair *pairs, size_t n_pairs,
+                                  bool listed, uint32_t tol_int, uint32_t min_run, uint32_t rate_num, uint32_t rate_den, vdf_alignment_retimed *out,
+                                  size_t capacity, size_t *n_out)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    uint32_t num = 1, den = 1;
+    if (int rc = align_retimed_all_checks(ctx, name, a_hashes, a_first, n_a, b_hashes, b_first, n_b, a_first, b_first, pairs, n_pairs, listed, min_run, rate_num,
+                                          rate_den, &num, &den, out, capacity, n_out, true))
+        return rc;
+    *n_out = 0;
+    if (listed ? n_pairs == 0 : (n_a == 0 || n_b == 0)) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    AlignUploaded u;
+    if (int rc = align_upload(ctx, a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, false, s, &u)) return rc;
+    return align_retimed_locked(ctx, align_sides_uploaded(ctx, u, n_a, n_b, false), tol_int, min_run, num, den, out, capacity, n_out, s,
+                                listed ? pairs : nullptr, n_pairs);
+}
+
+int vdf_align_windows_retimed_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                                   const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, uint32_t tol_int, uint32_t min_run, uint32_t rate_num,
+                                   uint32_t rate_den, vdf_alignment_retimed *out, size_t capacity, size_t *n_out)
+{
+    return align_retimed_host_impl(a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, nullptr, 0, false, tol_int, min_run, rate_num, rate_den, out,
+                                   capacity, n_out);
+}
+
+int vdf_align_windows_retimed(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                              const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, uint32_t tol_int, uint32_t min_run, uint32_t rate_num,
+                              uint32_t rate_den, vdf_alignment_retimed *out, size_t capacity, size_t *n_out)
+{
+    return align_retimed_ctx_impl(ctx, "vdf_align_windows_retimed", a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, nullptr, 0, false, tol_int,
+                                  min_run, rate_num, rate_den, out, capacity, n_out);
+}
+
+int vdf_align_windows_retimed_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a, const uint8_t *d_a_skip,
+                                     const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip, uint32_t tol_int,
+                                     uint32_t min_run, uint32_t rate_num, uint32_t rate_den, vdf_alignment_retimed *out, size_t capacity, size_t *n_out,
+                                     void *stream)
+{
+    return align_retimed_device_impl(ctx, "vdf_align_windows_retimed_device", d_a_hashes, d_a_first, n_a, d_a_skip, d_b_hashes, d_b_first, n_b, d_b_skip, nullptr,
+                                     0, false, tol_int, min_run, rate_num, rate_den, out, capacity, n_out, stream);
+}
+
+int vdf_align_windows_retimed_pairs_host(const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip, const uint64_t *b_hashes,
+                                         const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, const vdf_video_pair *pairs, size_t n_pairs,
+                                         uint32_t tol_int, uint32_t min_run, uint32_t rate_num, uint32_t rate_den, vdf_alignment_retimed *out,
+                                         size_t capacity, size_t *n_out)
+{
+    return align_retimed_host_impl(a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, pairs, n_pairs, true, tol_int, min_run, rate_num, rate_den,
+                                   out, capacity, n_out);
+}
+
+int vdf_align_windows_retimed_pairs(vdf_ctx *ctx, const uint64_t *a_hashes, const uint32_t *a_first, size_t n_a, const uint8_t *a_skip,
+                                    const uint64_t *b_hashes, const uint32_t *b_first, size_t n_b, const uint8_t *b_skip, const vdf_video_pair *pairs,
+                                    size_t n_pairs, uint32_t tol_int, uint32_t min_run, uint32_t rate_num, uint32_t rate_den, vdf_alignment_retimed *out,
+                                    size_t capacity, size_t *n_out)
+{
+    return align_retimed_ctx_impl(ctx, "vdf_align_windows_retimed_pairs", a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip, pairs, n_pairs, true,
+                                  tol_int, min_run, rate_num, rate_den, out, capacity, n_out);
+}
+
+int vdf_align_windows_retimed_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a, const uint8_t *d_a_skip,
+                                           const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b, const uint8_t *d_b_skip,
+                                           const vdf_video_pair *pairs, size_t n_pairs, uint32_t tol_int, uint32_t min_run, uint32_t rate_num,
+                                           uint32_t rate_den, vdf_alignment_retimed *out, size_t capacity, size_t *n_out, void *stream)
+{
+    return align_retimed_device_impl(ctx, "vdf_align_windows_retimed_pairs_device", d_a_hashes, d_a_first, n_a, d_a_skip, d_b_hashes, d_b_first, n_b, d_b_skip,
+                                     pairs, n_pairs, true, tol_int, min_run, rate_num, rate_den, out, capacity, n_out, stream);
 }
 
 size_t vdf_hash_window_count(uint32_t frames_per_clip, uint32_t window_stride) { return vdf::window_count(frames_per_clip, window_stride); }

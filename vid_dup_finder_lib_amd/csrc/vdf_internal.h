@@ -12,6 +12,7 @@
 #include "windows_mixed_plan.h"
 #include "windows_retimed_plan.h"
 #include "align_plan.h"
+#include "align_retimed_plan.h"
 
 namespace vdf {
 
@@ -282,6 +283,9 @@ struct AlignLaunch {
 };
 size_t align_scratch_bytes(size_t n_pairs, size_t n_units);
 hipError_t launch_align_chunk(const AlignLaunch &L, hipStream_t stream);
+// One chunk of a retimed call (align_retimed_plan.h: align_retimed_next_chunk): L as above with the chunk's (pair, phase, band)
+// units, no rectangles, and L.dense_out unused; num / den in lowest terms.  The same scratch; *dense_out: the records, in (a, b) order.
+hipError_t launch_align_retimed_chunk(const AlignLaunch &L, uint32_t num, uint32_t den, vdf_alignment_retimed **dense_out, hipStream_t stream);
 // The seed pass of a call (align_plan.h: AlignSeedPlan): every unit's seeds against its rows of B into `bitmap` (n_a x n_b
 // bits, cleared by the caller on the stream), then the count and scan of its set bits.  *total_out: where in scratch the number of pairs is
 // once the stream has run; launch_align_seed_scatter then writes the first `limit` of them, in (a, b) order.  All pointers are device pointers;

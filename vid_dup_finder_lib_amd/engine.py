@@ -308,6 +308,58 @@ def align_windows_stretches_pairs_host(a_hashes, a_first, pairs, b_hashes=None, 
     return out[:min(n.value, out.size)], int(n.value)
 
 
+# one record of the retimed align calls (include/vdf.h: vdf_alignment_retimed, 24 bytes)
+ALIGN_RETIMED_DTYPE = _capi.ALIGN_RETIMED_DTYPE
+
+
+def _align_rate(rate):
+    """(rate_num, rate_den) of a retimed align call as two uint32; the library says which rates it takes."""
+    try:
+        num, den = rate
+    except (TypeError, ValueError):
+        raise ValueError(f"rate must be a pair of integers (num, den), not {rate!r}") from None
+    return _align_uint32("rate num", num), _align_uint32("rate den", den)
+
+
+def _align_retimed_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip):
+    if b_hashes is None or b_first is None:
+        raise ValueError("the retimed align calls have no self mode: give b_hashes and b_first")
+    return _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+
+
+def align_windows_retimed_host(a_hashes, a_first, b_hashes, b_first, rate, tol_int: int = 350, min_run: int = 1, a_skip=None, b_skip=None,
+                               capacity: int = 1024):
+    """vdf_align_windows_retimed_host: the definition of the retimed align calls in plain C++ on the CPU (no context, no GPU).  a_hashes: RETIMED
+    windows at stride 1 (hash_windows(..., rate=rate)), b_hashes: plain windows at stride 1; rate = (num, den), 1 <= den <= num <= 2 den, at most
+    ALIGN_RETIMED_MAX_NUM in lowest terms.  -> (records [min(found, capacity)] of ALIGN_RETIMED_DTYPE in (a, b) order, found)."""
+    lib = _capi.load()
+    keep, args = _align_retimed_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+    out = np.zeros(max(int(capacity), 0), ALIGN_RETIMED_DTYPE)
+    n = C.c_size_t(0)
+    rc = lib.vdf_align_windows_retimed_host(*args, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run), *_align_rate(rate),
+                                            out.ctypes.data if out.size else None, out.size, C.byref(n))
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_align_windows_retimed_host: bad argument")
+    return out[:min(n.value, out.size)], int(n.value)
+
+
+def align_windows_retimed_pairs_host(a_hashes, a_first, pairs, b_hashes, b_first, rate, tol_int: int = 350, min_run: int = 1, a_skip=None, b_skip=None,
+                                     capacity: int = 1024):
+    """vdf_align_windows_retimed_pairs_host: align_windows_retimed_host on the listed pairs only (strictly increasing in (a, b)).
+    -> (records [min(found, capacity)] of ALIGN_RETIMED_DTYPE in (a, b) order, found)."""
+    lib = _capi.load()
+    keep, args = _align_retimed_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+    p = video_pairs(pairs)
+    out = np.zeros(max(int(capacity), 0), ALIGN_RETIMED_DTYPE)
+    n = C.c_size_t(0)
+    rc = lib.vdf_align_windows_retimed_pairs_host(*args, p.ctypes.data if p.size else None, p.size, _align_uint32("tol_int", tol_int),
+                                                  _align_uint32("min_run", min_run), *_align_rate(rate), out.ctypes.data if out.size else None, out.size,
+                                                  C.byref(n))
+    if rc != _capi.VDF_OK:
+        raise _pairs_host_error("vdf_align_windows_retimed_pairs_host", rc, p, args, False)
+    return out[:min(n.value, out.size)], int(n.value)
+
+
 # one (variant, a, b) triple (include/vdf.h: vdf_video_pair_variant, 12 bytes): what the seeded variants call returns and the variants-pairs calls take
 VIDEO_PAIR_VARIANT_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("variant", "<u4")])
 
@@ -944,6 +996,58 @@ class Engine:
                                                                       _align_uint32("min_run", min_run), _align_uint32("max_stretches", max_stretches),
                                                                       _align_uint32("guard", guard), out.ctypes.data if out.size else None, out.size,
                                                                       C.byref(n), stream or None))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    # --------------------------------------------- retimed windows aligned in one call (include/vdf.h)
+    def align_windows_retimed(self, a_hashes, a_first, b_hashes, b_first, rate, tol_int: int = 350, min_run: int = 1, a_skip=None, b_skip=None,
+                              capacity: int = 1024):
+        """Which video of A is a copy of which video of B at num / den of its frames, and where (vdf_align_windows_retimed): a_hashes = RETIMED
+        windows at stride 1 (hash_windows(..., rate=rate)), b_hashes = plain windows at stride 1, rate = (num, den).  Every phase of the rate in
+        one call: per pair the best run over the sub-sampled windows p + num i of a against den j of b.  No self mode.
+        -> (records [min(found, capacity)] of ALIGN_RETIMED_DTYPE in (a, b) order, found); found > capacity: call again with a larger capacity."""
+        keep, args = _align_retimed_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+        out = np.zeros(max(int(capacity), 0), ALIGN_RETIMED_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_retimed(self.ctx, *args, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                                       *_align_rate(rate), out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_retimed_device(self, d_a_hashes: int, d_a_first: int, n_a: int, d_b_hashes: int, d_b_first: int, n_b: int, rate,
+                                     tol_int: int = 350, min_run: int = 1, d_a_skip: int = 0, d_b_skip: int = 0, capacity: int = 1024, stream: int = 0):
+        """The same on device arrays; the records come back to the host, the call waits for its own work."""
+        out = np.zeros(max(int(capacity), 0), ALIGN_RETIMED_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_retimed_device(self.ctx, d_a_hashes or None, d_a_first or None, int(n_a), d_a_skip or None,
+                                                              d_b_hashes or None, d_b_first or None, int(n_b), d_b_skip or None,
+                                                              _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run), *_align_rate(rate),
+                                                              out.ctypes.data if out.size else None, out.size, C.byref(n), stream or None))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_retimed_pairs(self, a_hashes, a_first, pairs, b_hashes, b_first, rate, tol_int: int = 350, min_run: int = 1, a_skip=None,
+                                    b_skip=None, capacity: int = 1024):
+        """align_windows_retimed on the listed pairs only (vdf_align_windows_retimed_pairs): pairs = VIDEO_PAIR_DTYPE records or [n, 2] integers,
+        strictly increasing in (a, b).  The records are align_windows_retimed's for those pairs, field for field."""
+        keep, args = _align_retimed_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip)
+        p = video_pairs(pairs)
+        out = np.zeros(max(int(capacity), 0), ALIGN_RETIMED_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_retimed_pairs(self.ctx, *args, p.ctypes.data if p.size else None, p.size, _align_uint32("tol_int", tol_int),
+                                                             _align_uint32("min_run", min_run), *_align_rate(rate),
+                                                             out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_retimed_pairs_device(self, d_a_hashes: int, d_a_first: int, n_a: int, pairs, d_b_hashes: int, d_b_first: int, n_b: int, rate,
+                                           tol_int: int = 350, min_run: int = 1, d_a_skip: int = 0, d_b_skip: int = 0, capacity: int = 1024,
+                                           stream: int = 0):
+        """The same on device arrays (the pair list stays a host array)."""
+        p = video_pairs(pairs)
+        out = np.zeros(max(int(capacity), 0), ALIGN_RETIMED_DTYPE)
+        n = C.c_size_t(0)
+        self._check(self.lib.vdf_align_windows_retimed_pairs_device(self.ctx, d_a_hashes or None, d_a_first or None, int(n_a), d_a_skip or None,
+                                                                    d_b_hashes or None, d_b_first or None, int(n_b), d_b_skip or None,
+                                                                    p.ctypes.data if p.size else None, p.size, _align_uint32("tol_int", tol_int),
+                                                                    _align_uint32("min_run", min_run), *_align_rate(rate),
+                                                                    out.ctypes.data if out.size else None, out.size, C.byref(n), stream or None))
         return out[:min(n.value, out.size)], int(n.value)
 
     # --------------------------------------------- the zero plane and the flipped hashes (include/vdf.h, DESIGN.md 4.8)

@@ -560,6 +560,90 @@ public:
         }
     }
 
+    // ---- a copy at another frame rate or speed: retimed windows of A against plain windows of B, every phase in one call ----
+    // Which video of A is a copy of which video of B at rate_num / rate_den of its frames, and where (vdf_align_windows_retimed): windows_a =
+    // hash_windows_retimed' lists at stride 1, windows_b = hash_windows' at stride 1; 1 <= den <= num <= 2 den, num <= VDF_ALIGN_RETIMED_MAX_NUM in
+    // lowest terms.  At most one record per pair, in (a, b) order: the run's first windows first_a, first_b - its m-th cell is
+    // (first_a + num m, first_b + den m) - its sub-sampled windows and the sum of their distances.  There is no self mode.  ctx_opt null and
+    // a tiny input: walked on the CPU (vdf_align_windows_retimed_host, the definition in plain C++).
+    static std::vector<vdf_alignment_retimed> align_windows_retimed(const std::vector<std::vector<VideoHash>> &windows_a,
+                                                                    const std::vector<std::vector<VideoHash>> &windows_b, uint32_t rate_num, uint32_t rate_den,
+                                                                    uint32_t tol_int, uint32_t min_run = 1, const std::vector<uint8_t> *skip_a = nullptr,
+                                                                    const std::vector<uint8_t> *skip_b = nullptr, Context *ctx_opt = nullptr)
+    {
+        const AlignSides s(windows_a, &windows_b, skip_a, skip_b);
+        std::vector<vdf_alignment_retimed> out(1024);
+        for (;;) {
+            size_t found = 0;
+            int rc;
+            if (!ctx_opt && s.cells <= (1u << 16))
+                rc = vdf_align_windows_retimed_host(s.wa.data(), s.fa.data(), s.n_a, s.ska, s.wb.data(), s.fb.data(), s.n_b, s.skb, tol_int, min_run, rate_num, rate_den,
+                                                    out.data(), out.size(), &found);
+            else {
+                Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+                rc = vdf_align_windows_retimed(ctx.get(), s.wa.data(), s.fa.data(), s.n_a, s.ska, s.wb.data(), s.fb.data(), s.n_b, s.skb, tol_int, min_run, rate_num,
+                                               rate_den, out.data(), out.size(), &found);
+                if (rc != VDF_OK && rc != VDF_E_INVAL) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            }
+            if (rc != VDF_OK)
+                throw std::invalid_argument("align_windows_retimed: min_run of 0, a video of more than 2^20 windows, more than 2^24 pairs, a rate outside "
+                                            "1 <= den <= num <= 2 den or with num above 32 in lowest terms, or a multi-GPU context");
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
+    // align_windows_retimed on the listed pairs only (vdf_align_windows_retimed_pairs): pairs strictly increasing in (a, b).  The records are
+    // align_windows_retimed's for those pairs, field for field.  A library against itself: the list of the pairs a != b.
+    static std::vector<vdf_alignment_retimed> align_windows_retimed_pairs(const std::vector<std::vector<VideoHash>> &windows_a,
+                                                                          const std::vector<std::vector<VideoHash>> &windows_b,
+                                                                          const std::vector<vdf_video_pair> &pairs, uint32_t rate_num, uint32_t rate_den,
+                                                                          uint32_t tol_int, uint32_t min_run = 1, const std::vector<uint8_t> *skip_a = nullptr,
+                                                                          const std::vector<uint8_t> *skip_b = nullptr, Context *ctx_opt = nullptr)
+    {
+        const AlignSides s(windows_a, &windows_b, skip_a, skip_b);
+        std::vector<vdf_alignment_retimed> out(1024);
+        for (;;) {
+            size_t found = 0;
+            int rc;
+            if (!ctx_opt && s.cells <= (1u << 16))
+                rc = vdf_align_windows_retimed_pairs_host(s.wa.data(), s.fa.data(), s.n_a, s.ska, s.wb.data(), s.fb.data(), s.n_b, s.skb,
+                                                          pairs.empty() ? nullptr : pairs.data(), pairs.size(), tol_int, min_run, rate_num, rate_den, out.data(),
+                                                          out.size(), &found);
+            else {
+                Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+                rc = vdf_align_windows_retimed_pairs(ctx.get(), s.wa.data(), s.fa.data(), s.n_a, s.ska, s.wb.data(), s.fb.data(), s.n_b, s.skb,
+                                                     pairs.empty() ? nullptr : pairs.data(), pairs.size(), tol_int, min_run, rate_num, rate_den, out.data(), out.size(),
+                                                     &found);
+                if (rc != VDF_OK && rc != VDF_E_INVAL) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            }
+            if (rc != VDF_OK)
+                throw std::invalid_argument("align_windows_retimed_pairs: min_run of 0, a video of more than 2^20 windows, more than 2^24 listed pairs, a rate outside "
+                                            "1 <= den <= num <= 2 den or with num above 32 in lowest terms, a bad pair list, or a multi-GPU context");
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
+    // The same on device memory (vdf_align_windows_retimed_device): d_* are device arrays as the C ABI takes them, the records come back to the host
+    // and the call waits for its own work.
+    static std::vector<vdf_alignment_retimed> align_windows_retimed_device(Context &ctx, const uint64_t *d_a_hashes, const uint32_t *d_a_first, size_t n_a,
+                                                                           const uint8_t *d_a_skip, const uint64_t *d_b_hashes, const uint32_t *d_b_first, size_t n_b,
+                                                                           const uint8_t *d_b_skip, uint32_t rate_num, uint32_t rate_den, uint32_t tol_int,
+                                                                           uint32_t min_run = 1, void *stream = nullptr)
+    {
+        std::vector<vdf_alignment_retimed> out(1024);
+        for (;;) {
+            size_t found = 0;
+            const int rc = vdf_align_windows_retimed_device(ctx.get(), d_a_hashes, d_a_first, n_a, d_a_skip, d_b_hashes, d_b_first, n_b, d_b_skip, tol_int, min_run,
+                                                            rate_num, rate_den, out.data(), out.size(), &found, stream);
+            if (rc == VDF_E_INVAL) throw std::invalid_argument(vdf_last_error(ctx.get()));
+            if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
     // hash_windows with the zero plane of every window (vdf_hash_windows_u8_planes): the same words, and every VideoHash
     // carries zero() - what align_windows_variants needs of the flipped side.
     static std::vector<std::vector<VideoHash>> hash_windows_planes(const uint8_t *frames, size_t n_videos, uint32_t frames_per_video, uint32_t w, uint32_t h,
