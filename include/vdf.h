@@ -256,7 +256,8 @@ int vdf_hash_windows_u8_planes_device(vdf_ctx *ctx, const uint8_t *d_frames, siz
  * a rate outside the range or rate_den == 0 -> VDF_E_INVAL, then frames_per_clip < span -> VDF_E_NOT_ENOUGH_FRAMES.
  * At rate_num == rate_den, and at every rate whose taps are 0 ... 15 (25/24, say), the call IS the plain call: its route, its words.
  * The host form uploads in one piece and calls the device form's work.  A multi-GPU context -> VDF_E_INVAL.
- * Not here: zero planes of retimed windows, the mixed-library form, the batching queue. */
+ * Not here: zero planes of retimed windows, the batching queue.  A library of videos of different sizes and lengths in one call:
+ * vdf_hash_windows_clips_u8_retimed[_device] below. */
 size_t vdf_hash_window_count_retimed(uint32_t frames_per_clip, uint32_t window_stride, uint32_t rate_num, uint32_t rate_den);
 int vdf_hash_windows_u8_retimed(vdf_ctx *ctx, const uint8_t *frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w,
                                 uint32_t h, size_t frame_stride, size_t clip_stride, uint32_t window_stride, uint32_t rate_num,
@@ -703,6 +704,37 @@ int vdf_hash_windows_clips_u8_planes(vdf_ctx *ctx, const uint8_t *buf, size_t bu
 int vdf_hash_windows_clips_u8_planes_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips,
                                             const uint32_t *n_frames, size_t n_videos, uint32_t window_stride, uint64_t *d_out_hashes,
                                             uint32_t *d_out_dontcare, uint64_t *d_out_zero, void *stream);
+
+/* ---- the RETIMED windows of videos of different frame sizes and lengths in one call ----------------
+ * vdf_hash_windows_clips_u8[_device] with the windows of vdf_hash_windows_u8_retimed[_device]: the producer of the A side of
+ * vdf_align_windows_retimed* for a whole library.  The video arguments are those of vdf_hash_windows_clips_u8*: n_videos videos in ONE buffer,
+ * each with its own vdf_clip (offset, frame stride, size, optional crop box, read in place) and its own frame count n_frames[i]; clips and
+ * n_frames are HOST arrays.  The rate arguments are those of vdf_hash_windows_u8_retimed*: 1 <= rate_den <= rate_num <= 2 rate_den,
+ * rate_num <= 65535, tap(t) = floor(t * rate_num / rate_den), span = tap(15) + 1.  Retimed window k of video i is the hash of its frames
+ * k * window_stride + tap(t), t = 0 ... 15, inside its box.  With first[] = the prefix sums of
+ * vdf_hash_window_count_retimed(n_frames[i], window_stride, rate_num, rate_den) (vdf_hash_windows_clips_first_retimed) its hash goes to
+ * out_hashes + 16 (first[i] + k) and its don't-care count to out_dontcare[first[i] + k] (nullable).  Words and counts are exactly those of
+ * vdf_hash_windows_u8_retimed on that video alone (on a contiguous cropped copy, if it has a box).
+ * Errors, checked over all videos on the host before anything is queued (a rejected call launches nothing), each message naming the first
+ * offending video where one is meant: first those of vdf_hash_windows_clips_u8*, in that call's order (an n_frames below 16 ->
+ * VDF_E_NOT_ENOUGH_FRAMES first ... a multi-GPU context -> VDF_E_INVAL); then a rate outside the range or rate_den == 0 -> VDF_E_INVAL; then an
+ * n_frames[i] < span -> VDF_E_NOT_ENOUGH_FRAMES (a library call returns no 0-window video).  n_videos == 0: VDF_OK, nothing is launched.
+ * vdf_hash_windows_clips_first_retimed: host only, no context; first has n_videos + 1 entries.  A null pointer, window_stride == 0 or 2^32
+ * windows or more -> VDF_E_INVAL; an n_frames below 16 -> VDF_E_NOT_ENOUGH_FRAMES; then the two rate rules above.
+ * Routes: a rate whose taps are 0 ... 15 (rate_num == rate_den, 25/24) IS vdf_hash_windows_clips_u8[_device]: its route, its words.  Videos
+ * that all share (w, h, frame_stride, n_frames), have no box and sit at offsets one positive step apart take exactly the route of
+ * vdf_hash_windows_u8_retimed_device with clip_stride = that step.  Everything else is resized once, frame by frame, and hashed by one kernel
+ * whose workgroups find their video in a segment table.  The host form uploads the buffer in one piece.  The device form is ordered on `stream`
+ * and returns once the descriptors have left the host.
+ * Not here: zero planes of retimed windows, the batching queue, multi-GPU contexts. */
+int vdf_hash_windows_clips_first_retimed(const uint32_t *n_frames, size_t n_videos, uint32_t window_stride, uint32_t rate_num, uint32_t rate_den,
+                                         uint32_t *first);
+int vdf_hash_windows_clips_u8_retimed(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames,
+                                      size_t n_videos, uint32_t window_stride, uint32_t rate_num, uint32_t rate_den, uint64_t *out_hashes,
+                                      uint32_t *out_dontcare);
+int vdf_hash_windows_clips_u8_retimed_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips,
+                                             const uint32_t *n_frames, size_t n_videos, uint32_t window_stride, uint32_t rate_num,
+                                             uint32_t rate_den, uint64_t *d_out_hashes, uint32_t *d_out_dontcare, void *stream);
 
 /* ---- mirrored, flipped and reversed duplicates from ONE hash pass -------------------------------------
  * The reference cannot see through a horizontal mirror or a flip (vid_dup_finder_lib/src/lib.rs:102-111).  Here the hash of the

@@ -9,7 +9,7 @@ from .api import (Alignment, AlignmentStretch, FlippedAlignment, RetimedAlignmen
                   hash_frame_stacks, hash_frame_windows, locate, rust_path_key, search, search_with_references, sort_order)
 from .engine import (ALIGN_DTYPE, ALIGN_STRETCH_DTYPE, ALIGN_VARIANT_DTYPE, Engine, align_windows_host, align_windows_stretches_host, align_windows_variants_host,
                      window_variants_host, VIDEO_PAIR_DTYPE, align_seed_pairs_host, align_windows_pairs_host, align_windows_stretches_pairs_host,
-                     VIDEO_PAIR_VARIANT_DTYPE, align_seed_pairs_variants_host, align_windows_variants_pairs_host, window_class_layout_host, hash_windows_first, hash_window_count_retimed,
+                     VIDEO_PAIR_VARIANT_DTYPE, align_seed_pairs_variants_host, align_windows_variants_pairs_host, window_class_layout_host, hash_windows_first, hash_windows_first_retimed, hash_window_count_retimed,
                      ALIGN_RETIMED_DTYPE, align_windows_retimed_host, align_windows_retimed_pairs_host)
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
@@ -19,5 +19,5 @@ __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHas
            "align_all", "AlignmentStretch", "ALIGN_STRETCH_DTYPE", "align_windows_stretches_host",
            "candidate_pairs", "VIDEO_PAIR_DTYPE", "align_seed_pairs_host", "align_windows_pairs_host", "align_windows_stretches_pairs_host",
            "candidate_pairs_flipped", "VIDEO_PAIR_VARIANT_DTYPE", "align_seed_pairs_variants_host", "align_windows_variants_pairs_host", "window_class_layout_host",
-           "hash_windows_first", "hash_window_count_retimed", "align_retimed", "RetimedAlignment",
+           "hash_windows_first", "hash_windows_first_retimed", "hash_window_count_retimed", "align_retimed", "RetimedAlignment",
            "ALIGN_RETIMED_DTYPE", "align_windows_retimed_host", "align_windows_retimed_pairs_host"]

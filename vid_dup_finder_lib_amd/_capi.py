@@ -198,6 +198,12 @@ SIGNATURES = {
                                                    C.c_void_p]),
     "vdf_hash_windows_clips_u8_planes_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the mixed windows calls' arguments with rate_num, rate_den behind window_stride
+    "vdf_hash_windows_clips_first_retimed": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "vdf_hash_windows_clips_u8_retimed": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                    C.c_void_p, C.c_void_p]),
+    "vdf_hash_windows_clips_u8_retimed_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vdf_window_variants_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vdf_window_variants_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),

@@ -538,9 +538,31 @@ def _hash_frame_windows_retimed(frames, src_paths, durations, stride, engine, ra
     return [[VideoHash(w[k], src_paths[i], durations[i]) for k in range(len(w))] for i, w in enumerate(words)]
 
 
+def _hash_frame_windows_retimed_library(stacks, src_paths, durations, stride, engine, rate, crops, letterbox) -> List[List[VideoHash]]:
+    """hash_frame_windows(list, rate=, one_call=True): ONE Engine.hash_windows_clips_retimed call for the library, cut into per-video lists at
+    first[].  The boxes as _hash_frame_windows_mixed finds them."""
+    if crops is not None and letterbox:
+        raise ValueError("crops and letterbox=True are two sources of the same boxes")
+    eng = engine or default_engine()
+    stacks = list(stacks)
+
+    def call():
+        boxes = None
+        if crops is not None:
+            if len(crops) != len(stacks):
+                raise ValueError("a Crop per video")
+            boxes = np.stack([c.as_abi() if isinstance(c, Crop) else np.asarray(c, np.uint32).reshape(4) for c in crops]).reshape(-1, 4) if len(stacks) else None
+        elif letterbox and stacks:  # the boxes of frames 0 and 8 of every video, by the mixed letterbox call
+            boxes = eng.hash_clips_letterbox(stacks)[1]
+        return eng.hash_windows_clips_retimed(stacks, rate, stride, crops=boxes)
+
+    words, first = _with_planes(call)
+    return [[VideoHash(words[r], src_paths[i], durations[i]) for r in range(int(first[i]), int(first[i + 1]))] for i in range(len(stacks))]
+
+
 def hash_frame_windows(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int], stride: int = 1,
                        engine: Optional[Engine] = None, zero_plane: bool = False, crops: Optional[Sequence] = None,
-                       letterbox: bool = False, rate=None) -> List[List[VideoHash]]:
+                       letterbox: bool = False, rate=None, one_call: bool = False) -> List[List[VideoHash]]:
     """Every 16-frame window of every video (Engine.hash_windows): frames [n_videos, n_frames >= 16, H, W] u8 -> per video the VideoHash of
     frames [k * stride, k * stride + 16) for k = 0 .. (n_frames - 16) // stride, each carrying the video's src_paths[i] and durations[i].
     What finds a duplicate that is shifted in time (`locate`); the reference hashes one 16-frame stack per file (definitions.rs:31-34).
@@ -552,13 +574,21 @@ def hash_frame_windows(frames: np.ndarray, src_paths: Sequence, durations: Seque
     as gen_hashes does) and hashes the windows inside it.
     rate=(num, den), 1 <= den <= num <= 2 den: RETIMED windows (Engine.hash_windows_retimed) - window k = the 16 frames k * stride +
     (i * num) // den, which is what a copy of the video at den / num of its frame rate (or sped up num / den) holds in its plain windows;
-    align_retimed aligns the two.  Give it for the side with more frames per second.  No zero planes, crops or letterbox with a rate; a list
-    of stacks is hashed by one call per video."""
+    align_retimed aligns the two.  Give it for the side with more frames per second.  No zero planes with a rate; a list of stacks is hashed by
+    one call per video, without crops or letterbox.
+    one_call=True (a list of stacks and a rate only): the whole library's retimed windows by ONE call (Engine.hash_windows_clips_retimed), the
+    same words; crops and letterbox=True are then taken as the plain list form takes them."""
     if len(src_paths) < len(frames) or len(durations) < len(frames):
         raise ValueError("a path and a duration per video")
+    if one_call and (rate is None or not isinstance(frames, (list, tuple))):
+        raise ValueError("one_call=True takes a list of stacks and a rate")
     if rate is not None:
-        if zero_plane or crops is not None or letterbox:
-            raise ValueError("retimed windows have no zero planes, crops or letterbox")
+        if zero_plane:
+            raise ValueError("retimed windows have no zero planes")
+        if one_call:
+            return _hash_frame_windows_retimed_library(frames, src_paths, durations, stride, engine, rate, crops, letterbox)
+        if crops is not None or letterbox:
+            raise ValueError("retimed windows take crops or letterbox only for a list of stacks with one_call=True")
         return _hash_frame_windows_retimed(frames, src_paths, durations, stride, engine, rate)
     if isinstance(frames, (list, tuple)):
         return _hash_frame_windows_mixed(frames, src_paths, durations, stride, engine, zero_plane, crops, letterbox)

@@ -3103,17 +3103,15 @@ static int windows_clips_checks(vdf_ctx *ctx, const void *buf, size_t buf_bytes,
     return VDF_OK;
 }
 
-// windows_clips_checks has passed.  Uniform input: the uniform call.  Otherwise descriptors, table entries, the videos' records and the segment
-// table go up in ONE copy through the pinned staging, the mixed whole-line kernels write every pseudo-clip's 16 x 16 frames to `small`, and
-// dct_hash_windows_mixed_kernel hashes the windows from there to the rows first[i] + k.
-static int hash_windows_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames, size_t n_videos,
-                                     uint32_t window_stride, uint64_t *d_out, uint32_t *d_dc, hipStream_t stream, uint64_t *d_zero)
+// What the mixed windows calls do in front of their windows kernel (plan: a WindowsMixedPlan or WindowsMixedRetimedPlan of kind kMixed): descriptors,
+// table entries, the videos' records and the segment table go up in ONE copy through the pinned staging, and the mixed whole-line kernels write every
+// pseudo-clip's 16 x 16 frames to `small`.  *d_videos / *d_seg_first: the device copies the windows kernel reads; *launched: the launches' error so far -
+// the caller launches its kernel if that is hipSuccess and ends with windows_clips_staged_end either way.  (A template: C++ linkage inside the C block.)
+extern "C++" {
+template <class Plan>
+static int windows_clips_stage(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const Plan &plan, size_t n_videos, hipStream_t stream,
+                               const vdf::WindowsVideoRecord **d_videos, const uint32_t **d_seg_first, hipError_t *launched)
 {
-    const vdf::MixedClip *mc = reinterpret_cast<const vdf::MixedClip *>(clips);
-    const vdf::WindowsMixedPlan plan = vdf::plan_windows_mixed(mc, n_frames, n_videos, window_stride);
-    if (plan.kind == vdf::WindowsMixedPlan::kUniform)
-        return hash_windows_locked(ctx, d_buf + plan.offset0, n_videos, n_frames[0], mc[0].w, mc[0].h, (size_t)mc[0].frame_stride, (size_t)plan.clip_stride,
-                                   window_stride, d_out, d_dc, stream, d_zero);
     VDF_HIP(ctx, hipSetDevice(ctx->device));
     int rc = ensure_cos_table(ctx, stream);
     if (rc) return rc;
@@ -3160,15 +3158,41 @@ static int hash_windows_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t 
         if (e != hipSuccess) break;
         e = vdf::launch_mixed_frames(d_buf, d_buf + buf_bytes, d_desc + l.first, l.count, d_tab, l.part == vdf::MixedPart::kWideLines, small + l.first * 4096, stream);
     }
-    if (e == hipSuccess)
-        e = vdf::launch_dct_hash_windows_mixed(small, reinterpret_cast<const vdf::WindowsVideoRecord *>(d_blob + off_vid), reinterpret_cast<const uint32_t *>(d_blob + off_seg),
-                                               (uint32_t)n_videos, plan.seg_first[n_videos], window_stride, plan.per_seg, ctx->cos_table.as<double>(), d_out, d_dc,
-                                               stream, d_zero);
-    // the staging is read by the copy: it must have run before the next call on this context rewrites it (the kernels stay queued)
+    *d_videos = reinterpret_cast<const vdf::WindowsVideoRecord *>(d_blob + off_vid);
+    *d_seg_first = reinterpret_cast<const uint32_t *>(d_blob + off_seg);
+    *launched = e;
+    return VDF_OK;
+}
+}  // extern "C++"
+
+// the staging is read by the copy: it must have run before the next call on this context rewrites it (the kernels stay queued)
+static int windows_clips_staged_end(vdf_ctx *ctx, hipError_t e, const char *what)
+{
     const hipError_t ew = hipEventSynchronize(ctx->ev_mid);
-    if (e != hipSuccess) return fail_hip(ctx, e, "mixed windows launch");
+    if (e != hipSuccess) return fail_hip(ctx, e, what);
     VDF_HIP(ctx, ew);
     return VDF_OK;
+}
+
+// windows_clips_checks has passed.  Uniform input: the uniform call.  Otherwise descriptors, table entries, the videos' records and the segment
+// table go up in ONE copy through the pinned staging, the mixed whole-line kernels write every pseudo-clip's 16 x 16 frames to `small`, and
+// dct_hash_windows_mixed_kernel hashes the windows from there to the rows first[i] + k.
+static int hash_windows_clips_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames, size_t n_videos,
+                                     uint32_t window_stride, uint64_t *d_out, uint32_t *d_dc, hipStream_t stream, uint64_t *d_zero)
+{
+    const vdf::MixedClip *mc = reinterpret_cast<const vdf::MixedClip *>(clips);
+    const vdf::WindowsMixedPlan plan = vdf::plan_windows_mixed(mc, n_frames, n_videos, window_stride);
+    if (plan.kind == vdf::WindowsMixedPlan::kUniform)
+        return hash_windows_locked(ctx, d_buf + plan.offset0, n_videos, n_frames[0], mc[0].w, mc[0].h, (size_t)mc[0].frame_stride, (size_t)plan.clip_stride,
+                                   window_stride, d_out, d_dc, stream, d_zero);
+    const vdf::WindowsVideoRecord *d_videos = nullptr;
+    const uint32_t *d_seg_first = nullptr;
+    hipError_t e = hipSuccess;
+    if (int rc = windows_clips_stage(ctx, d_buf, buf_bytes, plan, n_videos, stream, &d_videos, &d_seg_first, &e)) return rc;
+    if (e == hipSuccess)
+        e = vdf::launch_dct_hash_windows_mixed(ctx->small.as<uint8_t>(), d_videos, d_seg_first, (uint32_t)n_videos, plan.seg_first[n_videos], window_stride, plan.per_seg,
+                                               ctx->cos_table.as<double>(), d_out, d_dc, stream, d_zero);
+    return windows_clips_staged_end(ctx, e, "mixed windows launch");
 }
 
 static int hash_windows_clips_device_impl(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames, size_t n_videos,
@@ -3235,6 +3259,99 @@ int vdf_hash_windows_clips_u8_planes(vdf_ctx *ctx, const uint8_t *buf, size_t bu
                                      uint32_t window_stride, uint64_t *out_hashes, uint32_t *out_dontcare, uint64_t *out_zero)
 {
     return hash_windows_clips_host_impl(ctx, buf, buf_bytes, clips, n_frames, n_videos, window_stride, out_hashes, out_dontcare, out_zero, true);
+}
+
+// ---- retimed window hashes of a whole library in one call (include/vdf.h: vdf_hash_windows_clips_u8_retimed*) --------------------
+int vdf_hash_windows_clips_first_retimed(const uint32_t *n_frames, size_t n_videos, uint32_t window_stride, uint32_t rate_num, uint32_t rate_den,
+                                         uint32_t *first)
+{
+    if (!first || (n_videos && !n_frames) || window_stride == 0 || n_videos >= 0xFFFFFFFFull) return VDF_E_INVAL;
+    for (size_t i = 0; i < n_videos; i++)
+        if (n_frames[i] < VDF_DCT_SIZE) return VDF_E_NOT_ENOUGH_FRAMES;
+    switch (vdf::check_windows_mixed_retimed(n_frames, n_videos, rate_num, rate_den).error) {
+    case vdf::WindowsMixedRetimedError::kBadRate: return VDF_E_INVAL;
+    case vdf::WindowsMixedRetimedError::kShorterThanSpan: return VDF_E_NOT_ENOUGH_FRAMES;
+    case vdf::WindowsMixedRetimedError::kNone: break;
+    }
+    return vdf::windows_first_retimed(n_frames, n_videos, window_stride, rate_num, rate_den, first) ? VDF_OK : VDF_E_INVAL;
+}
+
+// the rate checks of the library call, behind windows_clips_checks' (whose window counts are the plain ones: upper bounds of the retimed ones)
+static int windows_clips_retimed_checks(vdf_ctx *ctx, const uint32_t *n_frames, size_t n_videos, uint32_t rate_num, uint32_t rate_den)
+{
+    const vdf::WindowsMixedRetimedCheck chk = vdf::check_windows_mixed_retimed(n_frames, n_videos, rate_num, rate_den);
+    switch (chk.error) {
+    case vdf::WindowsMixedRetimedError::kBadRate: return fail(ctx, VDF_E_INVAL, "rate outside 1 <= den <= num <= 2 den, num <= 65535");
+    case vdf::WindowsMixedRetimedError::kShorterThanSpan:
+        return fail(ctx, VDF_E_NOT_ENOUGH_FRAMES, "fewer frames than a retimed window spans (video " + std::to_string(chk.video) + ")");
+    case vdf::WindowsMixedRetimedError::kNone: break;
+    }
+    return VDF_OK;
+}
+
+// windows_clips_checks and windows_clips_retimed_checks have passed.  Plain taps: the plain mixed call.  Uniform input: the uniform retimed call.
+// Otherwise hash_windows_clips_locked's steps - the one blob through the pinned staging, the mixed whole-line kernels into `small`, the event wait
+// on the staging - with dct_hash_windows_mixed_retimed_kernel hashing the retimed windows from there to the rows first[i] + k.
+static int hash_windows_clips_retimed_locked(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames,
+                                             size_t n_videos, uint32_t window_stride, uint32_t rate_num, uint32_t rate_den, uint64_t *d_out, uint32_t *d_dc,
+                                             hipStream_t stream)
+{
+    const vdf::MixedClip *mc = reinterpret_cast<const vdf::MixedClip *>(clips);
+    const vdf::WindowsMixedRetimedPlan plan = vdf::plan_windows_mixed_retimed(mc, n_frames, n_videos, window_stride, rate_num, rate_den);
+    if (plan.kind == vdf::WindowsMixedRetimedPlan::kPlain)
+        return hash_windows_clips_locked(ctx, d_buf, buf_bytes, clips, n_frames, n_videos, window_stride, d_out, d_dc, stream, nullptr);
+    if (plan.kind == vdf::WindowsMixedRetimedPlan::kUniform)
+        return hash_windows_locked(ctx, d_buf + plan.offset0, n_videos, n_frames[0], mc[0].w, mc[0].h, (size_t)mc[0].frame_stride, (size_t)plan.clip_stride,
+                                   window_stride, d_out, d_dc, stream, nullptr, &plan.rate);
+    const vdf::WindowsVideoRecord *d_videos = nullptr;
+    const uint32_t *d_seg_first = nullptr;
+    hipError_t e = hipSuccess;
+    if (int rc = windows_clips_stage(ctx, d_buf, buf_bytes, plan, n_videos, stream, &d_videos, &d_seg_first, &e)) return rc;
+    if (e == hipSuccess)
+        e = vdf::launch_dct_hash_windows_mixed_retimed(ctx->small.as<uint8_t>(), d_videos, d_seg_first, (uint32_t)n_videos, plan.seg_first[n_videos], plan.rate,
+                                                       ctx->cos_table.as<double>(), d_out, d_dc, stream);
+    return windows_clips_staged_end(ctx, e, "mixed retimed windows launch");
+}
+
+int vdf_hash_windows_clips_u8_retimed_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames,
+                                             size_t n_videos, uint32_t window_stride, uint32_t rate_num, uint32_t rate_den, uint64_t *d_out_hashes,
+                                             uint32_t *d_out_dontcare, void *stream)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const hipStream_t s = stream ? (hipStream_t)stream : ctx->stream;
+    bool run;
+    if (int rc = windows_clips_checks(ctx, d_buf, buf_bytes, clips, n_frames, n_videos, window_stride, d_out_hashes, nullptr, false, s, &run)) return rc;
+    if (int rc = windows_clips_retimed_checks(ctx, n_frames, n_videos, rate_num, rate_den)) return rc;
+    if (!run) return VDF_OK;
+    return hash_windows_clips_retimed_locked(ctx, d_buf, buf_bytes, clips, n_frames, n_videos, window_stride, rate_num, rate_den, d_out_hashes, d_out_dontcare, s);
+}
+
+// Host arrays: as hash_windows_clips_host_impl - the buffer goes up in one piece, the device form's work runs on it, the results come down.
+int vdf_hash_windows_clips_u8_retimed(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames, size_t n_videos,
+                                      uint32_t window_stride, uint32_t rate_num, uint32_t rate_den, uint64_t *out_hashes, uint32_t *out_dontcare)
+{
+    if (!ctx) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    bool run;
+    if (int rc = windows_clips_checks(ctx, buf, buf_bytes, clips, n_frames, n_videos, window_stride, out_hashes, nullptr, false, ctx->stream, &run)) return rc;
+    if (int rc = windows_clips_retimed_checks(ctx, n_frames, n_videos, rate_num, rate_den)) return rc;
+    if (!run) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    size_t n_out = 0;
+    for (size_t i = 0; i < n_videos; i++) n_out += vdf::retimed_window_count(n_frames[i], window_stride, rate_num, rate_den);
+    const size_t hash_bytes = n_out * VDF_HASH_WORDS * sizeof(uint64_t);
+    if (int rc = upload(ctx, ctx->frames, buf, buf_bytes, ctx->stream)) return rc;
+    VDF_HIP(ctx, ctx->out_hashes.reserve(hash_bytes));
+    if (out_dontcare) VDF_HIP(ctx, ctx->out_dc.reserve(n_out * sizeof(uint32_t)));
+    uint32_t *d_dc = out_dontcare ? ctx->out_dc.as<uint32_t>() : nullptr;
+    if (int rc = hash_windows_clips_retimed_locked(ctx, ctx->frames.as<uint8_t>(), buf_bytes, clips, n_frames, n_videos, window_stride, rate_num, rate_den,
+                                                   ctx->out_hashes.as<uint64_t>(), d_dc, ctx->stream))
+        return rc;
+    VDF_HIP(ctx, hipMemcpyAsync(out_hashes, ctx->out_hashes.p, hash_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_dontcare) VDF_HIP(ctx, hipMemcpyAsync(out_dontcare, d_dc, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VDF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VDF_OK;
 }
 
 // the argument checks both window-variant forms share, in the order their messages are reported; first on the host (null: not checked here)

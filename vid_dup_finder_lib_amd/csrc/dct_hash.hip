@@ -3326,6 +3326,154 @@ hipError_t launch_dct_hash_windows_retimed(const WindowsFrames &f, size_t n_clip
     return hipGetLastError();
 }
 
+// ---- retimed window hashes of videos of different sizes and lengths in one launch (vdf_hash_windows_clips_u8_retimed[_device]) ----
+// dct_hash_windows_retimed_kernel<true>'s body - WindowsRetimedShared, the chunk walk with `span`, the ring of 64 frames at slot (f - run) & 63,
+// pass y / x / t with the taps as two qword arguments, the paired ballot pack, the double-buffered words, the same barriers - with the three
+// things dct_hash_windows_mixed_kernel takes from the video's record instead of kernel arguments: where a frame is in `small`, the video's n_win
+// (here the retimed count, and with it f_end = (k_end - 1) stride + span, never past the video's last frame), and the output row first + k.
+// A workgroup is one (video, segment): binary search of its group index in seg_first, one record read, both workgroup-uniform.  Frames always
+// come from `small`, so every frame starts on a dword boundary: there is no byte form.  LDS as the retimed kernel's: 80 672 bytes.
+__global__ __launch_bounds__(256) void dct_hash_windows_mixed_retimed_kernel(const uint8_t *__restrict__ small, const WindowsVideoRecord *__restrict__ videos,
+                                                                             const uint32_t *__restrict__ seg_first, uint32_t n_videos, uint32_t stride,
+                                                                             uint32_t span, uint64_t taps_lo, uint64_t taps_hi, uint32_t per_seg,
+                                                                             uint32_t first_group, const double *__restrict__ cos_table,
+                                                                             uint64_t *__restrict__ out_hashes, uint32_t *__restrict__ out_dontcare)
+{
+    __shared__ WindowsRetimedShared sh;
+    const const_f64_ptr cosv = (const_f64_ptr)(uintptr_t)cos_table;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t group = first_group + blockIdx.x;  // the launcher's grid holds no group past seg_first[n_videos] (below 2^32: windows_mixed_plan.h)
+    const WindowsVideoRecord vid = videos[windows_video_of(seg_first, n_videos, group)];
+    const uint32_t seg = group - vid.seg_first, n_win = vid.n_win;
+    const uint32_t k_begin = seg * per_seg;                                                       // (n_seg * per_seg < n_win + per_seg <= 2^32)
+    const uint32_t k_end = (uint32_t)min((unsigned long long)k_begin + per_seg, (unsigned long long)n_win);
+    const uint32_t f_end = (k_end - 1) * stride + span;  // one past the last frame this workgroup reads: at most F
+    DctTw cm;
+#pragma unroll
+    for (int i = 0; i < 4; i++) { cm.t16[i][0] = cosv[256 + 2 * i]; cm.t16[i][1] = cosv[257 + 2 * i]; }
+#pragma unroll
+    for (int i = 0; i < 2; i++) { cm.t8[i][0] = cosv[264 + 2 * i]; cm.t8[i][1] = cosv[265 + 2 * i]; }
+    cm.t4[0] = cosv[268]; cm.t4[1] = cosv[269]; cm.h = cosv[270];
+    if (tid < 128) (&sh.words[0][0][0])[tid] = 0u;  // (the first OR is behind the barriers of the first chunk)
+
+    uint32_t k = k_begin, parity = 0;
+    const uint32_t run = k_begin * stride;  // the segment's first frame, slot 0 of the ring: its frames are one contiguous walk
+    uint32_t have = run;  // frames [max(run, have - 64), have) are resident; everything below is workgroup-uniform
+    while (k < k_end) {
+        const uint32_t s = k * stride;
+        while (have < s + span) {
+            // ---- the next chunk of 16 frames: frames at or past f_end are not read (their lanes repeat the last frame and store nothing)
+            {
+                const uint32_t t = tid >> 4, g = (tid >> 2) & 3, xq = tid & 3;
+                const uint32_t f = min(have + t, f_end - 1);
+                const uint8_t *p = small + windows_mixed_frame_offset(vid, f) + (4 * g) * 16 + 4 * xq;
+                uint32_t row[4];
+#pragma unroll
+                for (int r = 0; r < 4; r++) row[r] = *reinterpret_cast<const uint32_t *>(p + r * 16) ^ 0x80808080u;
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    uint32_t w = 0;
+#pragma unroll
+                    for (int r = 0; r < 4; r++) w |= ((row[r] >> (8 * c)) & 255u) << (8 * r);
+                    sh.cube[t * 64 + g * 16 + 4 * xq + c] = w;  // (last read: pass y of the previous chunk, two barriers ago)
+                }
+            }
+            __syncthreads();
+            {  // pass y: thread (t, x) owns one 16-pixel column
+                const uint32_t t = tid >> 4, x = tid & 15;
+                double v[16], o[10];
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    const int32_t w = (int32_t)sh.cube[t * 64 + g * 16 + x];
+#pragma unroll
+                    for (int r = 0; r < 4; r++) v[4 * g + r] = (double)((w << (24 - 8 * r)) >> 24);
+                }
+                dct16_pruned(v, o, cm);
+#pragma unroll
+                for (int ky = 0; ky < 10; ky++) sh.b[(t * 10 + ky) * kPadY + x] = o[ky];  // (last read: pass x of the previous chunk, one barrier ago)
+            }
+            __syncthreads();
+            if (tid < 160) {  // pass x: thread (t, ky) -> the frame's slot of the ring (last read: pass t of a window that starts 48 frames or more later)
+                double v[16], ox[10];
+#pragma unroll
+                for (int x = 0; x < 16; x++) v[x] = sh.b[tid * kPadY + x];
+                dct16_pruned(v, ox, cm);
+                const uint32_t t = tid / 10, ky = tid - 10 * t;
+                if (have + t < f_end) {
+                    const uint32_t slot = (have + t - run) & 63u;  // chunks begin at slot 0, 16, 32 or 48: dct_hash_block's bank pattern
+#pragma unroll
+                    for (int kx = 0; kx < 10; kx++) sh.c[slot * kStrideT + 10 * kx + ky] = ox[kx];
+                }
+            }
+            __syncthreads();
+            have += 16;
+        }
+        // ---- pass t + sign + pack for every window that is whole now, two at a time
+        const uint32_t k_ready = min(k_end, (have - span) / stride + 1);  // windows with s + span <= have (have >= s + span >= span)
+        for (uint32_t kp = k; kp < k_ready; kp += 2) {
+            const uint32_t half = wave >> 1, wv = wave & 1u, kk = kp + half;
+            if (kk < k_ready) {  // wave-uniform
+                const uint32_t rem = 64u * wv + lane;  // 10 kx + ky; lanes with rem >= 100 idle
+                const bool live = rem < 100;
+                const uint32_t at = live ? rem : 0, s0 = kk * stride - run;
+                double v[16], o[10];
+#pragma unroll
+                for (int t = 0; t < 16; t++) {
+                    const uint32_t tap = (uint32_t)((t < 8 ? taps_lo : taps_hi) >> (8 * (t & 7))) & 255u;  // wave-uniform: scalar
+                    v[t] = sh.c[((s0 + tap) & 63u) * kStrideT + at];
+                }
+                dct16_pruned(v, o, cm);
+                unsigned long long piece = 0;
+                uint32_t dc = 0;
+#pragma unroll
+                for (int kt = 0; kt < 10; kt++) {
+                    const unsigned long long bits = __builtin_amdgcn_ballot_w64(live && o[kt] > 0.0);  // 0.0 and NaN -> 0
+                    const unsigned long long tiny = __builtin_amdgcn_ballot_w64(live && fabs(o[kt]) < 1e-6);
+                    dc += (uint32_t)__builtin_popcountll(tiny);
+                    if (lane == (uint32_t)kt) piece = bits;
+                }
+                uint32_t *words = sh.words[parity][half];
+                if (lane < 10) {
+                    const uint32_t off = 100u * lane + 64u * wv, wi = off >> 5, sh_l = off & 31u;
+                    const uint32_t lo = (uint32_t)piece, hi = (uint32_t)(piece >> 32);
+                    atomicOr(&words[wi], lo << sh_l);
+                    atomicOr(&words[wi + 1], (hi << sh_l) | (sh_l ? lo >> (32u - sh_l) : 0u));
+                    if (sh_l && wi + 2 < 32) atomicOr(&words[wi + 2], hi >> (32u - sh_l));
+                }
+                if (lane == 0) sh.dc[parity][half][wv] = dc;
+            }
+            __syncthreads();
+            if ((tid & 127u) < 16) {  // the first 16 lanes of each window's first wave: store the words and clear them for the pair after the next
+                const uint32_t i = tid & 127u;
+                uint32_t *words = sh.words[parity][half];
+                const unsigned long long w = (unsigned long long)words[2 * i] | ((unsigned long long)words[2 * i + 1] << 32);
+                words[2 * i] = 0u;
+                words[2 * i + 1] = 0u;
+                if (kk < k_ready) {
+                    const size_t slot = (size_t)vid.first + kk;  // the row the align calls read: first[i] + k
+                    out_hashes[slot * 16 + i] = w;
+                    if (out_dontcare && i == 0) out_dontcare[slot] = sh.dc[parity][half][0] + sh.dc[parity][half][1];
+                }
+            }
+            parity ^= 1u;
+        }
+        k = k_ready;
+    }
+}
+
+hipError_t launch_dct_hash_windows_mixed_retimed(const uint8_t *small, const WindowsVideoRecord *videos, const uint32_t *seg_first, uint32_t n_videos,
+                                                 uint32_t n_groups, const WindowsRetimedPlan &rate, const double *cos_table, uint64_t *out_hashes,
+                                                 uint32_t *out_dontcare, hipStream_t stream)
+{
+    if (n_videos == 0 || n_groups == 0) return hipSuccess;
+    for (uint64_t g0 = 0; g0 < n_groups; g0 += kMaxWindowGroupsPerLaunch) {
+        const uint32_t grid = retimed_grid(n_groups, g0);
+        hipLaunchKernelGGL(dct_hash_windows_mixed_retimed_kernel, dim3(grid), dim3(256), 0, stream, small, videos, seg_first, n_videos, rate.stride, rate.span,
+                           rate.taps_lo, rate.taps_hi, rate.per_seg, (uint32_t)g0, cos_table, out_hashes, out_dontcare);
+    }
+    return hipGetLastError();
+}
+
 static MfmaResizeTables make_tables(const MfmaResizeArgs &a)
 {
     MfmaResizeTables T;

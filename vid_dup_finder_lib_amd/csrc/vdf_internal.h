@@ -11,6 +11,7 @@
 #include "windows_plan.h"
 #include "windows_mixed_plan.h"
 #include "windows_retimed_plan.h"
+#include "windows_mixed_retimed_plan.h"
 #include "align_plan.h"
 #include "align_retimed_plan.h"
 
@@ -258,6 +259,12 @@ hipError_t launch_dct_hash_windows_mixed(const uint8_t *small, const WindowsVide
 // out_hashes[16 (c n_win + k)] = the hash of the 16 frames k stride + tap(i) of clip c; out_dontcare (nullable) at c n_win + k
 hipError_t launch_dct_hash_windows_retimed(const WindowsFrames &f, size_t n_clips, const WindowsRetimedPlan &plan, const double *cos_table,
                                            uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream);
+// ---- retimed window hashes of videos of different sizes and lengths (windows_mixed_retimed_plan.h) -----------------------------
+// small, videos, seg_first, n_groups as launch_dct_hash_windows_mixed (n_win, first and seg_first of the records: the retimed ones); rate: stride,
+// span, taps and per_seg of the call.  Grids are cut at kMaxWindowGroupsPerLaunch.
+hipError_t launch_dct_hash_windows_mixed_retimed(const uint8_t *small, const WindowsVideoRecord *videos, const uint32_t *seg_first, uint32_t n_videos,
+                                                 uint32_t n_groups, const WindowsRetimedPlan &rate, const double *cos_table, uint64_t *out_hashes,
+                                                 uint32_t *out_dontcare, hipStream_t stream);
 // ---- the variant of a set of window hashes (window_variant.h) ------------------------------------------------------------------
 // rows [row0, row0 + n_rows) = [first[0], first[n_videos]) of out (and of out_skip, if skip is given) from hashes / zero / skip; variant 0 ... 7
 hipError_t launch_window_variants(const uint64_t *hashes, const uint64_t *zero, const uint32_t *first, uint32_t n_videos, const uint8_t *skip,

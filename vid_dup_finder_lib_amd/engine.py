@@ -101,6 +101,32 @@ def hash_windows_first(n_frames, stride: int = 1) -> np.ndarray:
     return first
 
 
+def _library_rate(rate):
+    """_window_rate, and a ValueError for a rate outside 1 <= den <= num <= 2 den, num <= 65535: the library calls size their output by it."""
+    num, den = _window_rate(rate)
+    if not (1 <= den <= num <= 2 * den and num <= 65535):
+        raise ValueError(f"rate must satisfy 1 <= den <= num <= 2 den and num <= 65535, not {rate!r}")
+    return num, den
+
+
+def hash_windows_first_retimed(n_frames, rate, stride: int = 1) -> np.ndarray:
+    """vdf_hash_windows_clips_first_retimed (host only, no context): first [n_videos + 1] u32 = the prefix sums of the videos' RETIMED window
+    counts at rate = (num, den) - where Engine.hash_windows_clips_retimed puts video i's windows and what align_windows_retimed* reads beside
+    the A side's hashes.  VdfError: a video of fewer frames than a retimed window spans (VDF_E_NOT_ENOUGH_FRAMES), a rate outside the range or
+    2^32 windows or more (VDF_E_INVAL)."""
+    nf = np.asarray(n_frames).reshape(-1)
+    if nf.size and (np.any(nf != nf.astype(np.int64)) or int(nf.min()) < 0 or int(nf.max()) >= 2**32):
+        raise ValueError("frame counts must be integers in 0 .. 2^32 - 1")
+    nf = np.ascontiguousarray(nf, dtype=np.uint32)
+    num, den = _window_rate(rate)
+    first = np.zeros(nf.size + 1, np.uint32)
+    rc = _capi.load().vdf_hash_windows_clips_first_retimed(nf.ctypes.data if nf.size else None, nf.size, _window_stride(stride), num, den, first.ctypes.data)
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_hash_windows_clips_first_retimed: " + ("a video of fewer frames than a retimed window spans" if rc == _capi.VDF_E_NOT_ENOUGH_FRAMES
+                                                                       else "a rate outside the range, or 2^32 windows or more"))
+    return first
+
+
 def _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip):
     """The host arrays of an align call as the C ABI takes them; b_hashes None = self mode.  Returns the arrays (to keep alive) and
     (a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip) as ctypes arguments."""
@@ -774,6 +800,41 @@ class Engine:
         self._check(self.lib.vdf_hash_windows_clips_u8_planes_device(self.ctx, d_buf or None, int(buf_bytes), c.ctypes.data if c.size else None,
                                                                      nf.ctypes.data if nf.size else None, c.size, _window_stride(stride), d_out or None,
                                                                      d_dontcare or None, d_zero or None, stream or None))
+
+    # --------------------------------------------- retimed windows of a whole library in one call (include/vdf.h)
+    def hash_windows_clips_retimed(self, stacks: Sequence[np.ndarray], rate, stride: int = 1, crops=None, want_dontcare: bool = False):
+        """hash_windows_clips at rate = (num, den): the RETIMED windows (hash_windows_retimed) of videos of different frame sizes and lengths in
+        one call (vdf_hash_windows_clips_u8_retimed).  stacks = a list of [F_i >= span, H_i, W_i] u8 arrays, span = (15 * num) // den + 1;
+        crops (optional) = [n, 4] u32 left, right, top, bottom per video, read in place.
+        -> (words [n_total, 16] u64, first [n + 1] u32 [, dontcare [n_total] u32]): video i's windows are rows first[i] ... first[i + 1]
+        (hash_windows_first_retimed), the layout align_windows_retimed* reads.  The words are hash_windows_retimed's for each video alone."""
+        stride = _window_stride(stride)
+        num, den = _library_rate(rate)
+        buf, clips, n_frames = self._pack_videos(stacks, crops)
+        n = len(clips)
+        # a video shorter than a window's span has no window: the library names it (first would not); the buffers are sized without it
+        first = hash_windows_first_retimed(np.maximum(n_frames, (15 * num) // den + 1), (num, den), stride)
+        rows = int(first[-1])
+        out = np.zeros((rows, HASH_WORDS), np.uint64)
+        dc = np.zeros(rows, np.uint32) if want_dontcare else None
+        self._check(self.lib.vdf_hash_windows_clips_u8_retimed(self.ctx, buf.ctypes.data, buf.size, clips.ctypes.data if n else None,
+                                                               n_frames.ctypes.data if n else None, n, stride, num, den, out.ctypes.data,
+                                                               dc.ctypes.data if want_dontcare else None))
+        return (out, first, dc) if want_dontcare else (out, first)
+
+    def hash_windows_clips_retimed_device(self, d_buf: int, buf_bytes: int, clips: np.ndarray, n_frames, stride: int, rate, d_out: int,
+                                          d_dontcare: int = 0, stream: int = 0):
+        """vdf_hash_windows_clips_u8_retimed_device: clips = HOST array of CLIP_DTYPE records (offsets relative to d_buf), n_frames = HOST frame
+        counts; every address is checked against buf_bytes before anything is queued.  d_out: hash_windows_first_retimed(n_frames, rate,
+        stride)[-1] x 16 words; ordered on `stream`."""
+        c = np.ascontiguousarray(clips, dtype=CLIP_DTYPE).reshape(-1)
+        nf = np.ascontiguousarray(n_frames, dtype=np.uint32).reshape(-1)
+        if nf.size != c.size:
+            raise ValueError("one frame count per video")
+        num, den = _window_rate(rate)
+        self._check(self.lib.vdf_hash_windows_clips_u8_retimed_device(self.ctx, d_buf or None, int(buf_bytes), c.ctypes.data if c.size else None,
+                                                                      nf.ctypes.data if nf.size else None, c.size, _window_stride(stride), num, den,
+                                                                      d_out or None, d_dontcare or None, stream or None))
 
     # --------------------------------------------- flipped and reversed stretches (include/vdf.h, DESIGN.md 4.11)
     def window_variants(self, d_hashes: int, d_zero: int, d_first: int, n_videos: int, variant: int, d_out: int, d_skip: int = 0, d_out_skip: int = 0,

@@ -348,6 +348,57 @@ public:
         if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
     }
 
+    // The RETIMED windows of videos of different frame sizes and lengths in one call (vdf_hash_windows_clips_u8_retimed):
+    // hash_windows_clips' videos at hash_windows_retimed's rate.  Per video the VideoHash of its frames k * stride + floor(t * num / den) inside its
+    // box; the words are hash_windows_retimed's for each video alone.  A video shorter than a window's span: not_enough_frames.
+    static std::vector<std::vector<VideoHash>> hash_windows_clips_retimed(const std::vector<Video> &videos, uint32_t stride, uint32_t rate_num,
+                                                                          uint32_t rate_den, Context *ctx_opt = nullptr)
+    {
+        Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+        const size_t n = videos.size();
+        std::vector<vdf_clip> clips(n);
+        std::vector<uint32_t> n_frames(n), first(n + 1);
+        size_t at = 0;
+        for (size_t i = 0; i < n; i++) {
+            const Video &v = videos[i];
+            clips[i] = vdf_clip{at, (uint64_t)v.w * v.h, v.w, v.h, v.crop[0], v.crop[1], v.crop[2], v.crop[3]};
+            n_frames[i] = v.n_frames;
+            at += ((size_t)v.n_frames * v.w * v.h + 63) & ~(size_t)63;
+        }
+        const int rf = vdf_hash_windows_clips_first_retimed(n_frames.data(), n, stride, rate_num, rate_den, first.data());
+        if (rf == VDF_E_NOT_ENOUGH_FRAMES) throw Error::not_enough_frames();
+        if (rf != VDF_OK) throw std::invalid_argument("a window stride of zero, a rate outside 1 <= den <= num <= 2 den, or 2^32 windows or more in one call");
+        std::vector<uint8_t> packed(at);
+        for (size_t i = 0; i < n; i++)
+            std::copy(videos[i].frames, videos[i].frames + (size_t)videos[i].n_frames * videos[i].w * videos[i].h, packed.begin() + (size_t)clips[i].offset);
+        std::vector<uint64_t> words((size_t)first[n] * VDF_HASH_WORDS);
+        const int rc = vdf_hash_windows_clips_u8_retimed(ctx.get(), packed.data(), packed.size(), clips.data(), n_frames.data(), n, stride, rate_num, rate_den,
+                                                         words.data(), nullptr);
+        if (rc == VDF_E_NOT_ENOUGH_FRAMES) throw Error::not_enough_frames();
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+        std::vector<std::vector<VideoHash>> out(n);
+        for (size_t i = 0; i < n; i++)
+            for (size_t r = first[i]; r < first[i + 1]; r++) {
+                std::array<uint64_t, VDF_HASH_WORDS> hw;
+                std::copy(words.begin() + r * VDF_HASH_WORDS, words.begin() + (r + 1) * VDF_HASH_WORDS, hw.begin());
+                out[i].emplace_back(hw, videos[i].src_path, videos[i].duration);
+            }
+        return out;
+    }
+    // The same on device memory: clips and n_frames are HOST arrays; d_out = first[n_videos] x 16 words with first from
+    // vdf_hash_windows_clips_first_retimed, d_dontcare nullable; retimed window k of video i at row first[i] + k.  Ordered on stream.
+    static void hash_windows_clips_retimed_device(Context &ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames,
+                                                  size_t n_videos, uint32_t stride, uint32_t rate_num, uint32_t rate_den, uint64_t *d_out,
+                                                  uint32_t *d_dontcare = nullptr, void *stream = nullptr)
+    {
+        const int rc = vdf_hash_windows_clips_u8_retimed_device(ctx.get(), d_buf, buf_bytes, clips, n_frames, n_videos, stride, rate_num, rate_den, d_out,
+                                                                d_dontcare, stream);
+        if (rc == VDF_E_NOT_ENOUGH_FRAMES) throw Error::not_enough_frames();
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+    }
+
     // Which videos share a stretch, at what offset, for how long (vdf_align_windows): windows_a / windows_b = hash_windows'
     // results (videos may differ in length); windows_b null: the videos of windows_a against each other, every pair a < b once.  At most one
     // record per pair of videos, in (a, b) order: the best run of consecutive windows within tol_int on one diagonal (offset = kb - ka), of at
