@@ -23,6 +23,9 @@
  *     takes host pointers (or, *_shards, one device pointer per GPU of a multi-GPU context).
  *     Stream order is all the ordering there is: work the caller queued on ANOTHER stream - a fill of the output buffer, the
  *     decoder's writes of the frames - is not waited for.  Pass the stream that work is on, or finish it first.
+ *     Calls that only queue work share the context's scratch (the resized frames between the resize and the DCT stage, the work lists and
+ *     counters of the letterbox and search kernels), and nothing orders two such calls on DIFFERENT streams of one context against each
+ *     other: queue a context's _device calls on one stream, or finish one call before starting the next on another stream.
  *   - The search calls need their (candidate) arrays in sorted order and return VDF_E_INVAL when the
  *     durations are not ascending.
  *   - vdf_ctx_create() binds a context to one GPU.  vdf_ctx_create_multi() makes ONE context over several GPUs of
@@ -663,7 +666,8 @@ int vdf_hash_clips_u8_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_byte
  * The hash calls WAIT for their detect (the kernel per box shape is chosen on the host, as for large frames above); a detected box size
  * whose coefficients do not fit the i8 split -> VDF_E_BAD_DIMS, reported after the detect, and no hash is written.  A multi-GPU context
  * refuses all three with VDF_E_INVAL. */
-/* boxes only: d_crops DEVICE [n_clips][4] l, r, t, b, ordered on stream; only queues work */
+/* boxes only: d_crops DEVICE [n_clips][4] l, r, t, b, ordered on stream; queues its kernels and waits for nothing but the upload of its
+ * descriptors (which, in stream order, waits for what the caller queued in front of it) */
 int vdf_cropdetect_letterbox_clips_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, size_t n_clips,
                                           uint32_t frames_per_clip, uint32_t *d_crops, void *stream);
 /* detect + crop + hash; out_crops HOST [n_clips][4], nullable; the call waits for its detect, the hashes are ordered on stream */
