@@ -270,6 +270,54 @@ int vdf_hash_windows_u8_retimed_device(vdf_ctx *ctx, const uint8_t *d_frames, si
                                        uint32_t rate_num, uint32_t rate_den, uint64_t *d_out_hashes, uint32_t *d_out_dontcare,
                                        void *stream);
 
+/* ---- retimed window hashes at several rates from one read of the frames ---------------------------------------------
+ * Whoever looks for retimed copies does not know the rate: they try the usual ones - 1/1, 6/5, 5/4, 3/2, 2/1.  One
+ * vdf_hash_windows_u8_retimed* call per rate reads, resizes and spatially transforms every frame once PER RATE, and only the pass along t
+ * depends on the rate.  These calls take up to VDF_WINDOWS_MAX_RATES rates and do the rest once.  The job:
+ *   frames ... window_stride   as vdf_hash_windows_u8[_device]'s arguments of those names; frames is a host pointer in
+ *                              vdf_hash_windows_u8_rates and a device pointer in vdf_hash_windows_u8_rates_device;
+ *   n_rates, rate_num, rate_den   1 ... 8 rates, each as vdf_hash_windows_u8_retimed takes it; HOST arrays in both forms.  Duplicate and
+ *                              unreduced rates are legal, each listed rate gets its block.  1/1 gives the plain windows (the B side of
+ *                              vdf_align_windows_retimed*) from the same pass;
+ *   out_hashes, out_dontcare   RATE-MAJOR: with n_win_r = vdf_hash_window_count_retimed(frames_per_clip, window_stride, rate_num[r], rate_den[r])
+ *                              and rate_first[r] = n_clips * (n_win_0 + ... + n_win_{r-1}), window k of clip c at rate r is row
+ *                              rate_first[r] + c n_win_r + k: 16 words of out_hashes, one entry of out_dontcare (nullable).  Host pointers in
+ *                              the host form, device pointers in the device form;
+ *   stream                     device form only: the call is ordered on it, NULL = the context's stream.  (It travels in the job: the
+ *                              job is the call's whole argument list.)
+ * Block r is, word for word and count for count, what vdf_hash_windows_u8_retimed[_device] writes for rate r on the same frames.
+ * vdf_hash_window_count_rates: host only; the total number of rows, rate_first (nullable, n_rates + 1 entries, the last one the total) filled
+ * in; 0 rows if n_rates is outside 1 ... 8, a rate array is null, or any rate has no window (vdf_hash_window_count_retimed == 0).
+ * Errors, in this order: a null ctx or job -> VDF_E_INVAL; those of vdf_hash_windows_u8 in its order; n_rates == 0, n_rates >
+ * VDF_WINDOWS_MAX_RATES or a null rate array -> VDF_E_INVAL; the first rate outside the range -> VDF_E_INVAL; the first rate with
+ * frames_per_clip < span -> VDF_E_NOT_ENOUGH_FRAMES (the message names the rate's index); 2^32 rows or more in all -> VDF_E_INVAL; a multi-GPU
+ * context -> VDF_E_INVAL; n_clips == 0 -> VDF_OK, nothing is launched.
+ * The host form uploads the frames ONCE, downloads all blocks and waits.  The device form only queues work; the rate arrays have left the
+ * host when it returns.
+ * Not here: zero planes, videos of different sizes and lengths in one call (vdf_hash_windows_clips_u8_retimed takes one rate), the batching
+ * queue, multi-GPU contexts. */
+#define VDF_WINDOWS_MAX_RATES 8
+typedef struct vdf_windows_rates_job {
+    const uint8_t *frames;
+    size_t n_clips;
+    uint32_t frames_per_clip;
+    uint32_t w;
+    uint32_t h;
+    size_t frame_stride;
+    size_t clip_stride;
+    uint32_t window_stride;
+    uint32_t n_rates;
+    const uint32_t *rate_num;
+    const uint32_t *rate_den;
+    uint64_t *out_hashes;
+    uint32_t *out_dontcare;
+    void *stream;
+} vdf_windows_rates_job;
+size_t vdf_hash_window_count_rates(size_t n_clips, uint32_t frames_per_clip, uint32_t window_stride, uint32_t n_rates,
+                                   const uint32_t *rate_num, const uint32_t *rate_den, size_t *rate_first);
+int vdf_hash_windows_u8_rates(vdf_ctx *ctx, const vdf_windows_rates_job *job);
+int vdf_hash_windows_u8_rates_device(vdf_ctx *ctx, const vdf_windows_rates_job *job);
+
 /* ---- align videos on their window hashes: the longest shared stretch of every pair of videos -------------
  * Which videos share a stretch, at what offset, and for how long.  Two sets of videos, A and B, each the
  * window hashes of its videos one after the other (what vdf_hash_windows_* writes): hashes[n_windows_total][16] and

@@ -117,6 +117,16 @@ ALIGN_RETIMED_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("first_a", "<u4"), 
 ALIGN_RETIMED_MAX_NUM = 32  # VDF_ALIGN_RETIMED_MAX_NUM
 
 
+WINDOWS_MAX_RATES = 8  # VDF_WINDOWS_MAX_RATES
+
+
+class VdfWindowsRatesJob(C.Structure):
+    """The argument list of vdf_hash_windows_u8_rates[_device] (include/vdf.h: vdf_windows_rates_job)."""
+    _fields_ = [("frames", C.c_void_p), ("n_clips", C.c_size_t), ("frames_per_clip", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32),
+                ("frame_stride", C.c_size_t), ("clip_stride", C.c_size_t), ("window_stride", C.c_uint32), ("n_rates", C.c_uint32),
+                ("rate_num", C.c_void_p), ("rate_den", C.c_void_p), ("out_hashes", C.c_void_p), ("out_dontcare", C.c_void_p), ("stream", C.c_void_p)]
+
+
 class VdfVideoPair(C.Structure):
     """One pair of vdf_align_seed_pairs* and of the lists of the *_pairs calls: 8 bytes (the numpy twin is engine.VIDEO_PAIR_DTYPE)."""
     _fields_ = [("a", C.c_uint32), ("b", C.c_uint32)]
@@ -189,6 +199,10 @@ SIGNATURES = {
                                               C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vdf_hash_windows_u8_retimed_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                                      C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # several rates from one read of the frames: (n_clips, frames_per_clip, window_stride, n_rates, rate_num, rate_den, rate_first) / (ctx, job)
+    "vdf_hash_window_count_rates": (C.c_size_t, [C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vdf_hash_windows_u8_rates": (C.c_int, [_ctx, C.POINTER(VdfWindowsRatesJob)]),
+    "vdf_hash_windows_u8_rates_device": (C.c_int, [_ctx, C.POINTER(VdfWindowsRatesJob)]),
     # (ctx, buf, buf_bytes, clips, n_frames, n_videos, window_stride, out_hashes, out_dontcare [, out_zero] [, stream])
     "vdf_hash_windows_clips_first": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "vdf_hash_windows_clips_u8": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),

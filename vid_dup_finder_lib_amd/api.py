@@ -25,7 +25,7 @@ from .engine import (ALIGN_DTYPE, ALIGN_STRETCH_DTYPE, ALIGN_VARIANT_DTYPE, Engi
                      pair_list_problem, VIDEO_PAIR_VARIANT_DTYPE, align_seed_pairs_variants_host, align_windows_variants_pairs_host)
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
-           "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "hash_frame_windows", "locate", "rust_path_key", "sort_order",
+           "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "hash_frame_windows", "align_rates", "best_rates", "locate", "rust_path_key", "sort_order",
            "DEFAULT_SEARCH_TOLERANCE", "TOLERANCE_SCALING_FACTOR"]
 
 
@@ -538,6 +538,23 @@ def _hash_frame_windows_retimed(frames, src_paths, durations, stride, engine, ra
     return [[VideoHash(w[k], src_paths[i], durations[i]) for k in range(len(w))] for i, w in enumerate(words)]
 
 
+def _hash_frame_windows_rates(frames, src_paths, durations, stride, engine, rates) -> dict:
+    """hash_frame_windows at several rates: one Engine.hash_windows_rates call for a 4-D array, one uniform call per video for a list of stacks."""
+    eng = engine or default_engine()
+    rates = [tuple(r) for r in rates]
+    try:
+        if isinstance(frames, (list, tuple)):
+            per_video = [eng.hash_windows_rates(np.asarray(st)[None], rates, stride) for st in frames]
+            words = [[pv[r][0] for pv in per_video] for r in range(len(rates))]
+        else:
+            words = eng.hash_windows_rates(frames, rates, stride)
+    except VdfError as e:
+        if e.code == _capi.VDF_E_NOT_ENOUGH_FRAMES:
+            raise NotEnoughFrames() from e
+        raise
+    return {rate: [[VideoHash(w[k], src_paths[i], durations[i]) for k in range(len(w))] for i, w in enumerate(words[r])] for r, rate in enumerate(rates)}
+
+
 def _hash_frame_windows_retimed_library(stacks, src_paths, durations, stride, engine, rate, crops, letterbox) -> List[List[VideoHash]]:
     """hash_frame_windows(list, rate=, one_call=True): ONE Engine.hash_windows_clips_retimed call for the library, cut into per-video lists at
     first[].  The boxes as _hash_frame_windows_mixed finds them."""
@@ -562,7 +579,7 @@ def _hash_frame_windows_retimed_library(stacks, src_paths, durations, stride, en
 
 def hash_frame_windows(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int], stride: int = 1,
                        engine: Optional[Engine] = None, zero_plane: bool = False, crops: Optional[Sequence] = None,
-                       letterbox: bool = False, rate=None, one_call: bool = False) -> List[List[VideoHash]]:
+                       letterbox: bool = False, rate=None, one_call: bool = False, rates=None):
     """Every 16-frame window of every video (Engine.hash_windows): frames [n_videos, n_frames >= 16, H, W] u8 -> per video the VideoHash of
     frames [k * stride, k * stride + 16) for k = 0 .. (n_frames - 16) // stride, each carrying the video's src_paths[i] and durations[i].
     What finds a duplicate that is shifted in time (`locate`); the reference hashes one 16-frame stack per file (definitions.rs:31-34).
@@ -577,9 +594,17 @@ def hash_frame_windows(frames: np.ndarray, src_paths: Sequence, durations: Seque
     align_retimed aligns the two.  Give it for the side with more frames per second.  No zero planes with a rate; a list of stacks is hashed by
     one call per video, without crops or letterbox.
     one_call=True (a list of stacks and a rate only): the whole library's retimed windows by ONE call (Engine.hash_windows_clips_retimed), the
-    same words; crops and letterbox=True are then taken as the plain list form takes them."""
+    same words; crops and letterbox=True are then taken as the plain list form takes them.
+    rates=[(num, den), ...], up to 8: the retimed windows at EVERY listed rate from one upload, one resize and one spatial transform of the
+    frames (Engine.hash_windows_rates) -> {(num, den): the list rate=(num, den) would return}; (1, 1) gives the plain windows.  For whoever does
+    not know the rate of a copy: align_rates and best_rates take it from there.  Not together with rate=, zero_plane=, one_call=, crops or
+    letterbox; a list of stacks is hashed by one call per video."""
     if len(src_paths) < len(frames) or len(durations) < len(frames):
         raise ValueError("a path and a duration per video")
+    if rates is not None:
+        if rate is not None or zero_plane or one_call or crops is not None or letterbox:
+            raise ValueError("rates= goes with none of rate=, zero_plane=, one_call=, crops= and letterbox=")
+        return _hash_frame_windows_rates(frames, src_paths, durations, stride, engine, rates)
     if one_call and (rate is None or not isinstance(frames, (list, tuple))):
         raise ValueError("one_call=True takes a list of stacks and a rate")
     if rate is not None:
@@ -964,6 +989,33 @@ def align_retimed(windows_a: List[List[VideoHash]], windows_b: List[List[VideoHa
                 best[(al.a, al.b)] = rec
     return [RetimedAlignment(a, b, num, den, fa, fb, (n - 1) * num + span, (n - 1) * den + _capi.DCT_SIZE, n, ds / n, pa[a], pb[b])
             for (a, b), (_, fa, fb, n, ds) in sorted(best.items())]
+
+
+def align_rates(windows_by_rate_a: dict, windows_b: List[List[VideoHash]], tolerance: float = DEFAULT_SEARCH_TOLERANCE, min_run: int = 1,
+                static_a: Optional[dict] = None, static_b=None, engine: Optional[Engine] = None, native: bool = True, seed: bool = False,
+                pairs=None) -> dict:
+    """Which videos of A are a retimed copy of which video of B, at which of several rates?  windows_by_rate_a: {(num, den): windows of A at that
+    rate}, as hash_frame_windows(..., rates=[...]) returns it, stride 1; windows_b: the PLAIN windows of B at stride 1 (the (1, 1) entry of such a
+    dict).  One align_retimed call per rate, in the dict's order, with everything else handed through (static_a: {rate: flags per video} or None)
+    -> {rate: List[RetimedAlignment]}.  best_rates picks one record per pair from it."""
+    return {rate: align_retimed(ws, windows_b, rate, tolerance, min_run=min_run, static_a=None if static_a is None else static_a.get(rate), static_b=static_b,
+                                engine=engine, seed=seed, native=native, pairs=pairs)
+            for rate, ws in windows_by_rate_a.items()}
+
+
+def best_rates(result: dict, tolerance: float = DEFAULT_SEARCH_TOLERANCE) -> List[RetimedAlignment]:
+    """One record per pair (a, b) out of align_rates' result, ordered by (a, b): the one that maximises
+    n_frames_b * (tol_int + 1 - mean_distance) - the frames of B the stretch covers times its margin below the tolerance.  That is comparable
+    across rates, which n_windows is not: a rate with a larger den sub-samples B more coarsely, and the same stretch counts fewer windows.
+    Ties go to the rate that comes first in `result`, the caller's order.  The record's num / den name the rate, in lowest terms."""
+    tol_int = tolerance_int(tolerance)
+    best = {}
+    for recs in result.values():
+        for r in recs:
+            score = r.n_frames_b * (tol_int + 1 - r.mean_distance)
+            if (r.a, r.b) not in best or score > best[(r.a, r.b)][0]:
+                best[(r.a, r.b)] = (score, r)
+    return [best[k][1] for k in sorted(best)]
 
 
 class AlignmentStretch(NamedTuple):

@@ -788,15 +788,13 @@ int windows_checks(vdf_ctx *ctx, const void *frames, size_t n_clips, uint32_t fr
     return VDF_OK;
 }
 
-// windows_checks has passed.  d_zero (nullable): the windows' zero planes as well - the same resize runs and routes, the kernel's PLANES form
-// retimed (nullable; d_zero is null then): the retimed windows of that plan (windows_retimed_plan.h) - the same resize stage, the retimed kernel
-int hash_windows_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h, size_t frame_stride,
-                        size_t clip_stride, uint32_t window_stride, uint64_t *d_out, uint32_t *d_dc, hipStream_t stream, uint64_t *d_zero = nullptr,
-                        const vdf::WindowsRetimedPlan *retimed = nullptr)
+// windows_checks has passed.  The resize stage of every windows launch - plain, retimed, several rates - run once: the cosine table, then the
+// clips' frames as 16 x 16 bytes, *out saying where they are (the caller's own buffer if they are 16 x 16 already).
+int windows_frames_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h, size_t frame_stride,
+                          size_t clip_stride, hipStream_t stream, vdf::WindowsFrames *out)
 {
     VDF_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = ensure_cos_table(ctx, stream)) return rc;
-    const vdf::WindowsPlan plan = vdf::plan_windows(frames_per_clip, window_stride);
     vdf::WindowsFrames wf{};
     if (w == VDF_DCT_SIZE && h == VDF_DCT_SIZE) {  // the resize is a copy: the kernel reads the caller's frames
         wf.base = wf.tail = d_frames;
@@ -824,6 +822,19 @@ int hash_windows_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, u
         wf.tail_first = frames_per_clip - 16;
         wf.dwords = true;
     }
+    *out = wf;
+    return VDF_OK;
+}
+
+// windows_checks has passed.  d_zero (nullable): the windows' zero planes as well - the same resize runs and routes, the kernel's PLANES form
+// retimed (nullable; d_zero is null then): the retimed windows of that plan (windows_retimed_plan.h) - the same resize stage, the retimed kernel
+int hash_windows_locked(vdf_ctx *ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h, size_t frame_stride,
+                        size_t clip_stride, uint32_t window_stride, uint64_t *d_out, uint32_t *d_dc, hipStream_t stream, uint64_t *d_zero = nullptr,
+                        const vdf::WindowsRetimedPlan *retimed = nullptr)
+{
+    vdf::WindowsFrames wf{};
+    if (int rc = windows_frames_locked(ctx, d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, stream, &wf)) return rc;
+    const vdf::WindowsPlan plan = vdf::plan_windows(frames_per_clip, window_stride);
     if (retimed) VDF_HIP(ctx, vdf::launch_dct_hash_windows_retimed(wf, n_clips, *retimed, ctx->cos_table.as<double>(), d_out, d_dc, stream));
     else VDF_HIP(ctx, vdf::launch_dct_hash_windows(wf, n_clips, plan, ctx->cos_table.as<double>(), d_out, d_dc, stream, d_zero));
     return VDF_OK;
@@ -2823,6 +2834,91 @@ int vdf_hash_windows_u8_retimed(vdf_ctx *ctx, const uint8_t *frames, size_t n_cl
         return rc;
     VDF_HIP(ctx, hipMemcpyAsync(out_hashes, ctx->out_hashes.p, n_out * VDF_HASH_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     if (out_dontcare) VDF_HIP(ctx, hipMemcpyAsync(out_dontcare, d_dc, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VDF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VDF_OK;
+}
+
+// ---- retimed window hashes at several rates from one read of the frames (include/vdf.h: vdf_hash_windows_u8_rates[_device]) -------
+size_t vdf_hash_window_count_rates(size_t n_clips, uint32_t frames_per_clip, uint32_t window_stride, uint32_t n_rates, const uint32_t *rate_num,
+                                   const uint32_t *rate_den, size_t *rate_first)
+{
+    const vdf::WindowsRatesPlan p = vdf::plan_windows_rates(n_clips, frames_per_clip, window_stride, n_rates, rate_num, rate_den);
+    if (rate_first && n_rates >= 1 && n_rates <= VDF_WINDOWS_MAX_RATES) {
+        for (uint32_t r = 0; r < n_rates; r++) rate_first[r] = p.ok ? (size_t)p.a.out_first[r] : 0;
+        rate_first[n_rates] = p.ok ? (size_t)p.n_out : 0;
+    }
+    return p.ok ? (size_t)p.n_out : 0;
+}
+
+// the checks of both forms, in the order their codes are reported (include/vdf.h); *run: there is something to hash, and *plan says what
+static int windows_rates_checks(vdf_ctx *ctx, const vdf_windows_rates_job *job, bool *run, vdf::WindowsRatesPlan *plan)
+{
+    bool some;
+    *run = false;
+    if (int rc = windows_checks(ctx, job->frames, job->n_clips, job->frames_per_clip, job->w, job->h, job->frame_stride, job->window_stride, job->out_hashes,
+                                &some))
+        return rc;
+    if (job->n_rates == 0 || job->n_rates > VDF_WINDOWS_MAX_RATES) return fail(ctx, VDF_E_INVAL, "n_rates outside 1 ... 8");
+    if (!job->rate_num || !job->rate_den) return fail(ctx, VDF_E_INVAL, "null rate array");
+    for (uint32_t r = 0; r < job->n_rates; r++)
+        if (!vdf::retimed_rate_ok(job->rate_num[r], job->rate_den[r]))
+            return fail(ctx, VDF_E_INVAL, "rate outside 1 <= den <= num <= 2 den, num <= 65535 (rate " + std::to_string(r) + ")");
+    for (uint32_t r = 0; r < job->n_rates; r++)
+        if (job->frames_per_clip < vdf::retimed_span(job->rate_num[r], job->rate_den[r]))
+            return fail(ctx, VDF_E_NOT_ENOUGH_FRAMES, "fewer frames per clip than a retimed window spans (rate " + std::to_string(r) + ")");
+    *plan = vdf::plan_windows_rates(job->n_clips, job->frames_per_clip, job->window_stride, job->n_rates, job->rate_num, job->rate_den);
+    if (!plan->ok) return fail(ctx, VDF_E_INVAL, "internal: a list of rates that passed the checks was not planned");
+    if (plan->n_out > 0xFFFFFFFFull) return fail(ctx, VDF_E_INVAL, "2^32 windows or more in one call");
+    if (!ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, "the windows calls take a single-device context");
+    *run = some;
+    return VDF_OK;
+}
+
+// windows_rates_checks has passed: hash_windows_locked's resize stage once, then every rate's windows from one launch
+static int hash_windows_rates_locked(vdf_ctx *ctx, const uint8_t *d_frames, const vdf_windows_rates_job *job, const vdf::WindowsRatesPlan &plan, uint64_t *d_out,
+                                     uint32_t *d_dc, hipStream_t stream)
+{
+    vdf::WindowsFrames wf{};
+    if (int rc = windows_frames_locked(ctx, d_frames, job->n_clips, job->frames_per_clip, job->w, job->h, job->frame_stride, job->clip_stride, stream, &wf))
+        return rc;
+    VDF_HIP(ctx, vdf::launch_dct_hash_windows_rates(wf, job->n_clips, plan, ctx->cos_table.as<double>(), d_out, d_dc, stream));
+    return VDF_OK;
+}
+
+int vdf_hash_windows_u8_rates_device(vdf_ctx *ctx, const vdf_windows_rates_job *job)
+{
+    if (!ctx || !job) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    bool run;
+    vdf::WindowsRatesPlan plan;  // the rates travel to the kernel inside it, by value: the caller's arrays are not read after the checks
+    if (int rc = windows_rates_checks(ctx, job, &run, &plan)) return rc;
+    if (!run) return VDF_OK;
+    return hash_windows_rates_locked(ctx, job->frames, job, plan, job->out_hashes, job->out_dontcare, job->stream ? (hipStream_t)job->stream : ctx->stream);
+}
+
+// Host arrays: as vdf_hash_windows_u8_retimed - ONE upload through the context's staging buffer, the device form's work on it, all blocks come down.
+int vdf_hash_windows_u8_rates(vdf_ctx *ctx, const vdf_windows_rates_job *job)
+{
+    if (!ctx || !job) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    bool run;
+    vdf::WindowsRatesPlan plan;
+    if (int rc = windows_rates_checks(ctx, job, &run, &plan)) return rc;
+    if (!run) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n_out = (size_t)plan.n_out;
+    size_t clips_span = 0, frames_span = 0, bytes = 0;  // as vdf_hash_windows_u8: first byte of clip 0 to the last byte of the last clip's last frame
+    if (__builtin_mul_overflow(job->n_clips - 1, job->clip_stride, &clips_span) ||
+        __builtin_mul_overflow((size_t)(job->frames_per_clip - 1), job->frame_stride, &frames_span) || __builtin_add_overflow(clips_span, frames_span, &bytes) ||
+        __builtin_add_overflow(bytes, (size_t)job->w * job->h, &bytes))
+        return fail(ctx, VDF_E_INVAL, "the clips' extent does not fit size_t");
+    if (int rc = upload(ctx, ctx->frames, job->frames, bytes, ctx->stream)) return rc;
+    VDF_HIP(ctx, ctx->out_hashes.reserve(n_out * VDF_HASH_WORDS * sizeof(uint64_t)));
+    if (job->out_dontcare) VDF_HIP(ctx, ctx->out_dc.reserve(n_out * sizeof(uint32_t)));
+    uint32_t *d_dc = job->out_dontcare ? ctx->out_dc.as<uint32_t>() : nullptr;
+    if (int rc = hash_windows_rates_locked(ctx, ctx->frames.as<uint8_t>(), job, plan, ctx->out_hashes.as<uint64_t>(), d_dc, ctx->stream)) return rc;
+    VDF_HIP(ctx, hipMemcpyAsync(job->out_hashes, ctx->out_hashes.p, n_out * VDF_HASH_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (job->out_dontcare) VDF_HIP(ctx, hipMemcpyAsync(job->out_dontcare, d_dc, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     VDF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VDF_OK;
 }

@@ -12,6 +12,7 @@
 #include "windows_mixed_plan.h"
 #include "windows_retimed_plan.h"
 #include "windows_mixed_retimed_plan.h"
+#include "windows_rates_plan.h"
 #include "align_plan.h"
 #include "align_retimed_plan.h"
 
@@ -265,6 +266,10 @@ hipError_t launch_dct_hash_windows_retimed(const WindowsFrames &f, size_t n_clip
 hipError_t launch_dct_hash_windows_mixed_retimed(const uint8_t *small, const WindowsVideoRecord *videos, const uint32_t *seg_first, uint32_t n_videos,
                                                  uint32_t n_groups, const WindowsRetimedPlan &rate, const double *cos_table, uint64_t *out_hashes,
                                                  uint32_t *out_dontcare, hipStream_t stream);
+// ---- retimed window hashes at several rates from one read of the frames (windows_rates_plan.h) -----------------------------------
+// window k of clip c at rate r to row plan.a.out_first[r] + c n_win_r + k of out_hashes (16 words a row) and of out_dontcare (nullable)
+hipError_t launch_dct_hash_windows_rates(const WindowsFrames &f, size_t n_clips, const WindowsRatesPlan &plan, const double *cos_table,
+                                         uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream);
 // ---- the variant of a set of window hashes (window_variant.h) ------------------------------------------------------------------
 // rows [row0, row0 + n_rows) = [first[0], first[n_videos]) of out (and of out_skip, if skip is given) from hashes / zero / skip; variant 0 ... 7
 hipError_t launch_window_variants(const uint64_t *hashes, const uint64_t *zero, const uint32_t *first, uint32_t n_videos, const uint8_t *skip,

@@ -82,6 +82,23 @@ def hash_window_count_retimed(n_frames: int, stride: int, rate) -> int:
     return int(_capi.load().vdf_hash_window_count_retimed(int(n_frames), _window_stride(stride), num, den))
 
 
+def _window_rates(rates):
+    """A list of rates as the C ABI's two uint32_t arrays take it: (num [n] u32, den [n] u32).  How many there may be and which rates are
+    offered is the library's to say."""
+    pairs = [_window_rate(r) for r in rates]
+    return np.array([p[0] for p in pairs], np.uint32), np.array([p[1] for p in pairs], np.uint32)
+
+
+def hash_window_count_rates(n_clips: int, n_frames: int, stride: int, rates):
+    """vdf_hash_window_count_rates (host only, no context): (rows, first [n_rates + 1]) of Engine.hash_windows_rates' rate-major outputs - rate
+    r's windows of clip c are the rows first[r] + c * n_win_r ... .  (0, zeros) if there are no or more than 8 rates, or a rate has no window."""
+    num, den = _window_rates(rates)
+    first = np.zeros(len(num) + 1, np.uintp)
+    total = _capi.load().vdf_hash_window_count_rates(int(n_clips), int(n_frames), _window_stride(stride), len(num), num.ctypes.data if len(num) else None,
+                                                     den.ctypes.data if len(num) else None, first.ctypes.data)
+    return int(total), first.astype(np.int64)
+
+
 # one record of the align calls (include/vdf.h: vdf_alignment, 24 bytes)
 ALIGN_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("offset", "<i4"), ("start_a", "<u4"), ("n_windows", "<u4"), ("dist_sum", "<u4")])
 
@@ -696,6 +713,45 @@ class Engine:
         cs = fs * frames_per_clip if clip_stride is None else clip_stride
         self._check(self.lib.vdf_hash_windows_u8_retimed_device(self.ctx, d_frames, n_clips, frames_per_clip, w, h, fs, cs, stride, num, den, d_out,
                                                                 d_dontcare or None, stream or None))
+
+    # --------------------------------------------- retimed windows at several rates from one read of the frames (include/vdf.h)
+    def _windows_rates_job(self, frames_ptr, n_clips, frames_per_clip, w, h, fs, cs, stride, rates, out_ptr, dc_ptr, stream):
+        """(job, arrays it points to): the caller keeps the arrays alive until the call has returned"""
+        num, den = _window_rates(rates)
+        job = _capi.VdfWindowsRatesJob(frames_ptr or None, n_clips, frames_per_clip, w, h, fs, cs, _window_stride(stride), len(num), num.ctypes.data,
+                                       den.ctypes.data, out_ptr or None, dc_ptr or None, stream or None)
+        return job, (num, den)
+
+    def hash_windows_rates(self, frames: np.ndarray, rates, stride: int = 1, dontcare: bool = False):
+        """hash_windows_retimed at up to 8 rates [(num, den), ...] from ONE upload, one resize and one spatial transform of the frames
+        (vdf_hash_windows_u8_rates) -> a list with one [n_clips, n_win_r, 16] u64 array per listed rate - word for word what
+        hash_windows_retimed(frames, rate, stride) gives; (1, 1) gives the plain windows - and, with dontcare, a second list with the
+        [n_clips, n_win_r] u32 don't-care counts."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if frames.ndim != 4:
+            raise ValueError("frames must be [n_clips, n_frames, H, W]")
+        nc, nf, h, w = frames.shape
+        total, first = hash_window_count_rates(nc, nf, stride, rates)
+        out = np.zeros((total, HASH_WORDS), np.uint64)
+        dc = np.zeros(total, np.uint32) if dontcare else None
+        job, keep = self._windows_rates_job(frames.ctypes.data, nc, nf, w, h, w * h, nf * w * h, stride, rates, out.ctypes.data,
+                                            dc.ctypes.data if dontcare else 0, 0)
+        self._check(self.lib.vdf_hash_windows_u8_rates(self.ctx, C.byref(job)))
+        del keep
+        cut = lambda a, tail: [a[first[r]:first[r + 1]].reshape((nc, -1) + tail) if nc else a[:0].reshape((0, 0) + tail) for r in range(len(first) - 1)]
+        return (cut(out, (HASH_WORDS,)), cut(dc, ())) if dontcare else cut(out, (HASH_WORDS,))
+
+    def hash_windows_rates_device(self, d_frames: int, n_clips: int, frames_per_clip: int, w: int, h: int, stride: int, rates, d_out: int,
+                                  d_dontcare: int = 0, frame_stride: Optional[int] = None, clip_stride: Optional[int] = None, stream: int = 0):
+        """The device form (vdf_hash_windows_u8_rates_device), ordered on `stream`.  d_out: 16 words for each of the rows
+        hash_window_count_rates(n_clips, frames_per_clip, stride, rates) counts, rate-major; d_dontcare (optional): one u32 per row.
+        -> first [n_rates + 1]: rows first[r] ... first[r + 1] are rate r's block, a [n_clips, n_win_r, 16] array in d_out."""
+        fs = w * h if frame_stride is None else frame_stride
+        cs = fs * frames_per_clip if clip_stride is None else clip_stride
+        job, keep = self._windows_rates_job(d_frames, n_clips, frames_per_clip, w, h, fs, cs, stride, rates, d_out, d_dontcare, stream)
+        self._check(self.lib.vdf_hash_windows_u8_rates_device(self.ctx, C.byref(job)))
+        del keep
+        return hash_window_count_rates(n_clips, frames_per_clip, stride, rates)[1]
 
     def hash_windows_planes(self, frames: np.ndarray, stride: int = 1, want_dontcare: bool = False):
         """hash_windows plus the zero plane of every window (vdf_hash_windows_u8_planes): -> (hashes [n_clips, n_win, 16] u64, zero

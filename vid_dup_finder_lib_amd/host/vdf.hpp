@@ -295,6 +295,56 @@ public:
         if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
     }
 
+    // hash_windows_retimed at up to VDF_WINDOWS_MAX_RATES rates from ONE upload, one resize and one spatial transform of the frames
+    // (vdf_hash_windows_u8_rates): out[r] = what hash_windows_retimed gives at rates[r] = {num, den}; {1, 1} gives the plain windows.
+    static std::vector<std::vector<std::vector<VideoHash>>> hash_windows_rates(const uint8_t *frames, size_t n_videos, uint32_t frames_per_video, uint32_t w,
+                                                                               uint32_t h, uint32_t stride, const std::vector<std::array<uint32_t, 2>> &rates,
+                                                                               const std::vector<std::string> &src_paths,
+                                                                               const std::vector<uint32_t> &durations, Context *ctx_opt = nullptr)
+    {
+        if (src_paths.size() < n_videos || durations.size() < n_videos) throw std::invalid_argument("a path and a duration per video");
+        if (rates.empty() || rates.size() > VDF_WINDOWS_MAX_RATES) throw std::invalid_argument("1 ... 8 rates");
+        Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+        const uint32_t n_rates = (uint32_t)rates.size();
+        std::vector<uint32_t> num(n_rates), den(n_rates);
+        for (uint32_t r = 0; r < n_rates; r++) { num[r] = rates[r][0]; den[r] = rates[r][1]; }
+        std::vector<size_t> first(n_rates + 1);
+        const size_t rows = vdf_hash_window_count_rates(n_videos, frames_per_video, stride, n_rates, num.data(), den.data(), first.data()), fs = (size_t)w * h;
+        std::vector<uint64_t> words(rows * VDF_HASH_WORDS);
+        const vdf_windows_rates_job job{frames, n_videos, frames_per_video, w, h, fs, fs * frames_per_video, stride, n_rates, num.data(), den.data(),
+                                        words.data(), nullptr, nullptr};
+        const int rc = vdf_hash_windows_u8_rates(ctx.get(), &job);
+        if (rc == VDF_E_NOT_ENOUGH_FRAMES) throw Error::not_enough_frames();
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+        std::vector<std::vector<std::vector<VideoHash>>> out(n_rates, std::vector<std::vector<VideoHash>>(n_videos));
+        for (uint32_t r = 0; r < n_rates; r++) {
+            const size_t n_win = n_videos ? (first[r + 1] - first[r]) / n_videos : 0;
+            for (size_t i = 0; i < n_videos; i++)
+                for (size_t k = 0; k < n_win; k++) {
+                    const size_t row = first[r] + i * n_win + k;
+                    std::array<uint64_t, VDF_HASH_WORDS> hw;
+                    std::copy(words.begin() + row * VDF_HASH_WORDS, words.begin() + (row + 1) * VDF_HASH_WORDS, hw.begin());
+                    out[r][i].emplace_back(hw, src_paths[i], durations[i]);
+                }
+        }
+        return out;
+    }
+    // The same on device memory, ordered on `stream`: d_out = 16 words for each of vdf_hash_window_count_rates' rows, rate-major.
+    static void hash_windows_rates_device(Context &ctx, const uint8_t *d_frames, size_t n_clips, uint32_t frames_per_clip, uint32_t w, uint32_t h,
+                                          size_t frame_stride, size_t clip_stride, uint32_t stride, const std::vector<std::array<uint32_t, 2>> &rates,
+                                          uint64_t *d_out, uint32_t *d_dontcare = nullptr, void *stream = nullptr)
+    {
+        std::vector<uint32_t> num(rates.size()), den(rates.size());
+        for (size_t r = 0; r < rates.size(); r++) { num[r] = rates[r][0]; den[r] = rates[r][1]; }
+        const vdf_windows_rates_job job{d_frames, n_clips, frames_per_clip, w, h, frame_stride, clip_stride, stride, (uint32_t)rates.size(), num.data(),
+                                        den.data(), d_out, d_dontcare, stream};
+        const int rc = vdf_hash_windows_u8_rates_device(ctx.get(), &job);
+        if (rc == VDF_E_NOT_ENOUGH_FRAMES) throw Error::not_enough_frames();
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+    }
+
     // Every window of videos of DIFFERENT frame sizes and lengths in one call (vdf_hash_windows_clips_u8): video i = n_frames
     // tightly packed gray frames of w x h, with an optional crop box {left, right, top, bottom} read in place.  Per video the VideoHash of
     // frames [k * stride, k * stride + 16); the lists differ in length.  The words are hash_windows' for each video alone.
