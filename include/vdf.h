@@ -294,8 +294,8 @@ int vdf_hash_windows_u8_retimed_device(vdf_ctx *ctx, const uint8_t *d_frames, si
  * context -> VDF_E_INVAL; n_clips == 0 -> VDF_OK, nothing is launched.
  * The host form uploads the frames ONCE, downloads all blocks and waits.  The device form only queues work; the rate arrays have left the
  * host when it returns.
- * Not here: zero planes, videos of different sizes and lengths in one call (vdf_hash_windows_clips_u8_retimed takes one rate), the batching
- * queue, multi-GPU contexts. */
+ * Not here: zero planes, the batching queue, multi-GPU contexts.  Videos of different sizes and lengths at several rates in one call:
+ * vdf_hash_windows_clips_u8_rates[_device] below. */
 #define VDF_WINDOWS_MAX_RATES 8
 typedef struct vdf_windows_rates_job {
     const uint8_t *frames;
@@ -778,7 +778,8 @@ int vdf_hash_windows_clips_u8_planes_device(vdf_ctx *ctx, const uint8_t *d_buf, 
  * vdf_hash_windows_u8_retimed_device with clip_stride = that step.  Everything else is resized once, frame by frame, and hashed by one kernel
  * whose workgroups find their video in a segment table.  The host form uploads the buffer in one piece.  The device form is ordered on `stream`
  * and returns once the descriptors have left the host.
- * Not here: zero planes of retimed windows, the batching queue, multi-GPU contexts. */
+ * Not here: zero planes of retimed windows, the batching queue, multi-GPU contexts.  Several rates from one read of the library:
+ * vdf_hash_windows_clips_u8_rates[_device] below. */
 int vdf_hash_windows_clips_first_retimed(const uint32_t *n_frames, size_t n_videos, uint32_t window_stride, uint32_t rate_num, uint32_t rate_den,
                                          uint32_t *first);
 int vdf_hash_windows_clips_u8_retimed(vdf_ctx *ctx, const uint8_t *buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames,
@@ -787,6 +788,56 @@ int vdf_hash_windows_clips_u8_retimed(vdf_ctx *ctx, const uint8_t *buf, size_t b
 int vdf_hash_windows_clips_u8_retimed_device(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips,
                                              const uint32_t *n_frames, size_t n_videos, uint32_t window_stride, uint32_t rate_num,
                                              uint32_t rate_den, uint64_t *d_out_hashes, uint32_t *d_out_dontcare, void *stream);
+
+/* ---- the retimed windows of a library of different frame sizes and lengths at SEVERAL rates in one call ----------------
+ * vdf_hash_windows_clips_u8_retimed[_device] with the rate list of vdf_hash_windows_u8_rates[_device]: for the owner of a
+ * library who does not know the rate.  Every frame is read, resized and spatially transformed ONCE, whatever the number of rates.  The job:
+ *   buf, buf_bytes, clips, n_frames, n_videos, window_stride   as vdf_hash_windows_clips_u8*'s arguments of those names; buf is a host pointer
+ *                              in vdf_hash_windows_clips_u8_rates and a device pointer in _device; clips and n_frames are HOST arrays;
+ *   n_rates, rate_num, rate_den   1 ... VDF_WINDOWS_MAX_RATES rates, each as vdf_hash_windows_u8_retimed takes it; HOST arrays in both forms.
+ *                              Duplicate and unreduced rates are legal, each listed rate gets its block;
+ *   out_hashes, out_dontcare   RATE-MAJOR, and every block is a library: with first[r][] = the prefix sums of
+ *                              vdf_hash_window_count_retimed(n_frames[i], window_stride, rate_num[r], rate_den[r]) - n_videos + 1 entries, exactly
+ *                              what vdf_hash_windows_clips_first_retimed gives for rate r - and rate_first[r] = the totals of the blocks before r,
+ *                              window k of video i at rate r is row rate_first[r] + first[r][i] + k: 16 words of out_hashes, one entry of
+ *                              out_dontcare (nullable).  Host pointers in the host form, device pointers in the device form;
+ *   stream                     device form only: the call is ordered on it, NULL = the context's stream.
+ * Block r is, word for word and count for count, what vdf_hash_windows_clips_u8_retimed[_device] writes for rate r on the same arguments, also
+ * at the plain taps (1/1, 25/24).  (out_hashes + 16 rate_first[r], first[r]) is, unchanged, the A side of vdf_align_windows_retimed*; the 1/1
+ * block is a B side.
+ * vdf_hash_windows_clips_first_rates: host only, no context; first has n_rates * (n_videos + 1) entries, row r at first + r (n_videos + 1);
+ * rate_first (nullable) has n_rates + 1 entries, the last one the total number of rows.  A null first, window_stride == 0, n_rates outside
+ * 1 ... 8 or a null rate array -> VDF_E_INVAL; an n_frames below 16 -> VDF_E_NOT_ENOUGH_FRAMES; then the rate rules and the row limit below.
+ * Errors of the hash calls, checked on the host before anything is queued (a rejected call launches nothing), in this order: a null ctx or
+ * job -> VDF_E_INVAL; those of vdf_hash_windows_clips_u8*, in that call's order, ending with a multi-GPU context -> VDF_E_INVAL; n_rates
+ * outside 1 ... 8 or a null rate array -> VDF_E_INVAL; the first rate outside 1 <= den <= num <= 2 den, num <= 65535 -> VDF_E_INVAL; in list
+ * order, the first rate for which some n_frames[i] < span -> VDF_E_NOT_ENOUGH_FRAMES (the message names the rate's index and the first such
+ * video: a library call returns no 0-window video at any rate); 2^32 rows or more in all -> VDF_E_INVAL; n_videos == 0 -> VDF_OK, nothing
+ * is launched.
+ * Routes: videos that all share (w, h, frame_stride, n_frames), have no box and sit at offsets one positive step apart take exactly the route
+ * of vdf_hash_windows_u8_rates_device with clip_stride = that step (its rows coincide: first[r][c] = c n_win_r).  Everything else - a one-rate
+ * list and plain-tap rates included - is resized once and hashed by one kernel whose workgroups find their video in a segment table.
+ * The host form uploads the buffer ONCE, downloads all blocks and waits.  The device form only queues work on job->stream and returns once the
+ * descriptors and the rate arrays have left the host.
+ * Not here: zero planes, the batching queue, multi-GPU contexts (VDF_E_INVAL), rates outside [1, 2]. */
+typedef struct vdf_windows_clips_rates_job {
+    const uint8_t *buf;
+    size_t buf_bytes;
+    const vdf_clip *clips;
+    const uint32_t *n_frames;
+    size_t n_videos;
+    uint32_t window_stride;
+    uint32_t n_rates;
+    const uint32_t *rate_num;
+    const uint32_t *rate_den;
+    uint64_t *out_hashes;
+    uint32_t *out_dontcare;
+    void *stream;
+} vdf_windows_clips_rates_job;
+int vdf_hash_windows_clips_first_rates(const uint32_t *n_frames, size_t n_videos, uint32_t window_stride, uint32_t n_rates,
+                                       const uint32_t *rate_num, const uint32_t *rate_den, uint32_t *first, size_t *rate_first);
+int vdf_hash_windows_clips_u8_rates(vdf_ctx *ctx, const vdf_windows_clips_rates_job *job);
+int vdf_hash_windows_clips_u8_rates_device(vdf_ctx *ctx, const vdf_windows_clips_rates_job *job);
 
 /* ---- mirrored, flipped and reversed duplicates from ONE hash pass -------------------------------------
  * The reference cannot see through a horizontal mirror or a flip (vid_dup_finder_lib/src/lib.rs:102-111).  Here the hash of the

@@ -127,6 +127,13 @@ class VdfWindowsRatesJob(C.Structure):
                 ("rate_num", C.c_void_p), ("rate_den", C.c_void_p), ("out_hashes", C.c_void_p), ("out_dontcare", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class VdfWindowsClipsRatesJob(C.Structure):
+    """The argument list of vdf_hash_windows_clips_u8_rates[_device] (include/vdf.h: vdf_windows_clips_rates_job)."""
+    _fields_ = [("buf", C.c_void_p), ("buf_bytes", C.c_size_t), ("clips", C.c_void_p), ("n_frames", C.c_void_p), ("n_videos", C.c_size_t),
+                ("window_stride", C.c_uint32), ("n_rates", C.c_uint32), ("rate_num", C.c_void_p), ("rate_den", C.c_void_p),
+                ("out_hashes", C.c_void_p), ("out_dontcare", C.c_void_p), ("stream", C.c_void_p)]
+
+
 class VdfVideoPair(C.Structure):
     """One pair of vdf_align_seed_pairs* and of the lists of the *_pairs calls: 8 bytes (the numpy twin is engine.VIDEO_PAIR_DTYPE)."""
     _fields_ = [("a", C.c_uint32), ("b", C.c_uint32)]
@@ -218,6 +225,10 @@ SIGNATURES = {
                                                     C.c_void_p, C.c_void_p]),
     "vdf_hash_windows_clips_u8_retimed_device": (C.c_int, [_ctx, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
                                                            C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # a mixed library at several rates: (n_frames, n_videos, window_stride, n_rates, rate_num, rate_den, first, rate_first) / (ctx, job)
+    "vdf_hash_windows_clips_first_rates": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vdf_hash_windows_clips_u8_rates": (C.c_int, [_ctx, C.POINTER(VdfWindowsClipsRatesJob)]),
+    "vdf_hash_windows_clips_u8_rates_device": (C.c_int, [_ctx, C.POINTER(VdfWindowsClipsRatesJob)]),
     "vdf_window_variants_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vdf_window_variants_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),

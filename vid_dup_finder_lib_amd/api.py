@@ -577,6 +577,30 @@ def _hash_frame_windows_retimed_library(stacks, src_paths, durations, stride, en
     return [[VideoHash(words[r], src_paths[i], durations[i]) for r in range(int(first[i]), int(first[i + 1]))] for i in range(len(stacks))]
 
 
+def _hash_frame_windows_rates_library(stacks, src_paths, durations, stride, engine, rates, crops, letterbox) -> dict:
+    """hash_frame_windows(list, rates=, one_call=True): ONE Engine.hash_windows_clips_rates call for the library and all its rates, every block
+    cut into per-video lists at first[r].  The boxes as _hash_frame_windows_retimed_library finds them."""
+    if crops is not None and letterbox:
+        raise ValueError("crops and letterbox=True are two sources of the same boxes")
+    eng = engine or default_engine()
+    stacks = list(stacks)
+    rates = [tuple(r) for r in rates]
+
+    def call():
+        boxes = None
+        if crops is not None:
+            if len(crops) != len(stacks):
+                raise ValueError("a Crop per video")
+            boxes = np.stack([c.as_abi() if isinstance(c, Crop) else np.asarray(c, np.uint32).reshape(4) for c in crops]).reshape(-1, 4) if len(stacks) else None
+        elif letterbox and stacks:  # the boxes of frames 0 and 8 of every video, by the mixed letterbox call
+            boxes = eng.hash_clips_letterbox(stacks)[1]
+        return eng.hash_windows_clips_rates(stacks, rates, stride, crops=boxes)
+
+    words, first = _with_planes(call)
+    return {rate: [[VideoHash(words[r][k], src_paths[i], durations[i]) for k in range(int(first[r, i]), int(first[r, i + 1]))] for i in range(len(stacks))]
+            for r, rate in enumerate(rates)}
+
+
 def hash_frame_windows(frames: np.ndarray, src_paths: Sequence, durations: Sequence[int], stride: int = 1,
                        engine: Optional[Engine] = None, zero_plane: bool = False, crops: Optional[Sequence] = None,
                        letterbox: bool = False, rate=None, one_call: bool = False, rates=None):
@@ -597,13 +621,20 @@ def hash_frame_windows(frames: np.ndarray, src_paths: Sequence, durations: Seque
     same words; crops and letterbox=True are then taken as the plain list form takes them.
     rates=[(num, den), ...], up to 8: the retimed windows at EVERY listed rate from one upload, one resize and one spatial transform of the
     frames (Engine.hash_windows_rates) -> {(num, den): the list rate=(num, den) would return}; (1, 1) gives the plain windows.  For whoever does
-    not know the rate of a copy: align_rates and best_rates take it from there.  Not together with rate=, zero_plane=, one_call=, crops or
-    letterbox; a list of stacks is hashed by one call per video."""
+    not know the rate of a copy: align_rates and best_rates take it from there.  Not together with rate= or zero_plane=; a list of stacks is
+    hashed by one call per video, without crops or letterbox.
+    rates= with one_call=True (a list of stacks only): the whole library at every listed rate by ONE call (Engine.hash_windows_clips_rates) - every
+    frame read, resized and transformed once - the same dict of the same words; crops and letterbox=True are then taken as the plain list form
+    takes them."""
     if len(src_paths) < len(frames) or len(durations) < len(frames):
         raise ValueError("a path and a duration per video")
     if rates is not None:
-        if rate is not None or zero_plane or one_call or crops is not None or letterbox:
-            raise ValueError("rates= goes with none of rate=, zero_plane=, one_call=, crops= and letterbox=")
+        if rate is not None or zero_plane:
+            raise ValueError("rates= goes with neither rate= nor zero_plane=")
+        if one_call and isinstance(frames, (list, tuple)):
+            return _hash_frame_windows_rates_library(frames, src_paths, durations, stride, engine, rates, crops, letterbox)
+        if one_call or crops is not None or letterbox:
+            raise ValueError("rates= takes one_call=, crops= and letterbox= only for a list of stacks with one_call=True")
         return _hash_frame_windows_rates(frames, src_paths, durations, stride, engine, rates)
     if one_call and (rate is None or not isinstance(frames, (list, tuple))):
         raise ValueError("one_call=True takes a list of stacks and a rate")

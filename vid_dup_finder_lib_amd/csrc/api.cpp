@@ -3206,7 +3206,8 @@ static int windows_clips_checks(vdf_ctx *ctx, const void *buf, size_t buf_bytes,
 extern "C++" {
 template <class Plan>
 static int windows_clips_stage(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_bytes, const Plan &plan, size_t n_videos, hipStream_t stream,
-                               const vdf::WindowsVideoRecord **d_videos, const uint32_t **d_seg_first, hipError_t *launched)
+                               const vdf::WindowsVideoRecord **d_videos, const uint32_t **d_seg_first, hipError_t *launched,
+                               const void *extra = nullptr, size_t extra_bytes = 0, const void **d_extra = nullptr)
 {
     VDF_HIP(ctx, hipSetDevice(ctx->device));
     int rc = ensure_cos_table(ctx, stream);
@@ -3214,7 +3215,8 @@ static int windows_clips_stage(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_by
     const auto pad64 = [](size_t b) { return (b + 63) & ~size_t(63); };
     const size_t n_desc = plan.descs.size(), max_entries = 2 * ((size_t)plan.max_w + plan.max_h + 2);
     const size_t off_tab = pad64(n_desc * sizeof(vdf::MixedClipDesc)), off_vid = off_tab + pad64(max_entries * sizeof(vdf::CropTableEntry)),
-                 off_seg = off_vid + pad64(n_videos * sizeof(vdf::WindowsVideoRecord)), blob = off_seg + pad64((n_videos + 1) * sizeof(uint32_t));
+                 off_seg = off_vid + pad64(n_videos * sizeof(vdf::WindowsVideoRecord)), off_extra = off_seg + pad64((n_videos + 1) * sizeof(uint32_t)),
+                 blob = off_extra + pad64(extra_bytes);  // extra: a trailing piece of the caller's in the same copy (none: the blob as it always was)
     if (!ctx->pin_desc.reserve(blob)) return fail(ctx, VDF_E_OOM, "host staging for the video descriptors");
     char *stage = ctx->pin_desc.as<char>();
     vdf::MixedClipDesc *dsc = reinterpret_cast<vdf::MixedClipDesc *>(stage);
@@ -3242,6 +3244,7 @@ static int windows_clips_stage(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_by
         }
     std::memcpy(stage + off_vid, plan.videos.data(), n_videos * sizeof(vdf::WindowsVideoRecord));
     std::memcpy(stage + off_seg, plan.seg_first.data(), (n_videos + 1) * sizeof(uint32_t));
+    if (extra_bytes) std::memcpy(stage + off_extra, extra, extra_bytes);
     VDF_HIP(ctx, ctx->small.reserve(std::max<size_t>(plan.small_bytes, 4096)));
     if ((rc = upload(ctx, ctx->crop_desc2, stage, blob, stream))) return rc;
     VDF_HIP(ctx, hipEventRecord(ctx->ev_mid, stream));
@@ -3256,6 +3259,7 @@ static int windows_clips_stage(vdf_ctx *ctx, const uint8_t *d_buf, size_t buf_by
     }
     *d_videos = reinterpret_cast<const vdf::WindowsVideoRecord *>(d_blob + off_vid);
     *d_seg_first = reinterpret_cast<const uint32_t *>(d_blob + off_seg);
+    if (d_extra) *d_extra = d_blob + off_extra;
     *launched = e;
     return VDF_OK;
 }
@@ -3446,6 +3450,123 @@ int vdf_hash_windows_clips_u8_retimed(vdf_ctx *ctx, const uint8_t *buf, size_t b
         return rc;
     VDF_HIP(ctx, hipMemcpyAsync(out_hashes, ctx->out_hashes.p, hash_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (out_dontcare) VDF_HIP(ctx, hipMemcpyAsync(out_dontcare, d_dc, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    VDF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return VDF_OK;
+}
+
+// ---- retimed window hashes of a mixed library at several rates in one call (include/vdf.h: vdf_hash_windows_clips_u8_rates*) ------
+int vdf_hash_windows_clips_first_rates(const uint32_t *n_frames, size_t n_videos, uint32_t window_stride, uint32_t n_rates, const uint32_t *rate_num,
+                                       const uint32_t *rate_den, uint32_t *first, size_t *rate_first)
+{
+    if (!first || (n_videos && !n_frames) || window_stride == 0 || n_videos >= 0xFFFFFFFFull) return VDF_E_INVAL;
+    if (n_rates == 0 || n_rates > VDF_WINDOWS_MAX_RATES || !rate_num || !rate_den) return VDF_E_INVAL;
+    for (size_t i = 0; i < n_videos; i++)
+        if (n_frames[i] < VDF_DCT_SIZE) return VDF_E_NOT_ENOUGH_FRAMES;
+    switch (vdf::check_windows_mixed_rates(n_frames, n_videos, window_stride, n_rates, rate_num, rate_den).error) {
+    case vdf::WindowsMixedRatesError::kRateCount:
+    case vdf::WindowsMixedRatesError::kBadRate:
+    case vdf::WindowsMixedRatesError::kTooManyRows: return VDF_E_INVAL;
+    case vdf::WindowsMixedRatesError::kShorterThanSpan: return VDF_E_NOT_ENOUGH_FRAMES;
+    case vdf::WindowsMixedRatesError::kNone: break;
+    }
+    uint64_t rf[VDF_WINDOWS_MAX_RATES + 1];
+    if (!vdf::windows_first_rates(n_frames, n_videos, window_stride, n_rates, rate_num, rate_den, first, rf)) return VDF_E_INVAL;
+    for (uint32_t r = 0; rate_first && r <= n_rates; r++) rate_first[r] = (size_t)rf[r];
+    return VDF_OK;
+}
+
+// the rate checks of the several-rates library call, behind windows_clips_checks' (whose window counts are the plain ones, per block)
+static int windows_clips_rates_checks(vdf_ctx *ctx, const vdf_windows_clips_rates_job *job)
+{
+    const vdf::WindowsMixedRatesCheck chk =
+        vdf::check_windows_mixed_rates(job->n_frames, job->n_videos, job->window_stride, job->n_rates, job->rate_num, job->rate_den);
+    switch (chk.error) {
+    case vdf::WindowsMixedRatesError::kRateCount:
+        return fail(ctx, VDF_E_INVAL, job->n_rates == 0 || job->n_rates > VDF_WINDOWS_MAX_RATES ? "n_rates outside 1 ... 8" : "null rate array");
+    case vdf::WindowsMixedRatesError::kBadRate:
+        return fail(ctx, VDF_E_INVAL, "rate outside 1 <= den <= num <= 2 den, num <= 65535 (rate " + std::to_string(chk.rate) + ")");
+    case vdf::WindowsMixedRatesError::kShorterThanSpan:
+        return fail(ctx, VDF_E_NOT_ENOUGH_FRAMES,
+                    "fewer frames than a retimed window spans (rate " + std::to_string(chk.rate) + ", video " + std::to_string(chk.video) + ")");
+    case vdf::WindowsMixedRatesError::kTooManyRows: return fail(ctx, VDF_E_INVAL, "2^32 windows or more in one call");
+    case vdf::WindowsMixedRatesError::kNone: break;
+    }
+    return VDF_OK;
+}
+
+// windows_clips_checks and windows_clips_rates_checks have passed.  Uniform input: the uniform rates call, whose rows coincide.  Otherwise
+// hash_windows_clips_retimed_locked's steps - the one blob through the pinned staging, here with the row table behind the segment table, the mixed
+// whole-line kernels into `small`, the event wait on the staging - with dct_hash_windows_mixed_rates_kernel hashing every rate's windows from there.
+static int hash_windows_clips_rates_locked(vdf_ctx *ctx, const uint8_t *d_buf, const vdf_windows_clips_rates_job *job, const vdf::WindowsMixedRatesPlan &plan,
+                                           uint64_t *d_out, uint32_t *d_dc, hipStream_t stream)
+{
+    const size_t n_videos = job->n_videos;
+    if (plan.kind == vdf::WindowsMixedRatesPlan::kUniform) {
+        vdf_windows_rates_job u{};
+        u.frames = d_buf + plan.offset0;
+        u.n_clips = n_videos;
+        u.frames_per_clip = job->n_frames[0];
+        u.w = job->clips[0].w;
+        u.h = job->clips[0].h;
+        u.frame_stride = (size_t)job->clips[0].frame_stride;
+        u.clip_stride = (size_t)plan.clip_stride;
+        u.window_stride = job->window_stride;
+        if (!plan.uniform.ok) return fail(ctx, VDF_E_INVAL, "internal: a list of rates that passed the checks was not planned");
+        return hash_windows_rates_locked(ctx, u.frames, &u, plan.uniform, d_out, d_dc, stream);
+    }
+    const vdf::WindowsVideoRecord *d_videos = nullptr;
+    const uint32_t *d_seg_first = nullptr;
+    const void *d_row0 = nullptr;
+    hipError_t e = hipSuccess;
+    if (int rc = windows_clips_stage(ctx, d_buf, job->buf_bytes, plan, n_videos, stream, &d_videos, &d_seg_first, &e, plan.row0.data(),
+                                     plan.row0.size() * sizeof(uint32_t), &d_row0))
+        return rc;
+    if (e == hipSuccess)
+        e = vdf::launch_dct_hash_windows_mixed_rates(ctx->small.as<uint8_t>(), d_videos, d_seg_first, static_cast<const uint32_t *>(d_row0), (uint32_t)n_videos,
+                                                     plan.seg_first[n_videos], plan.stride, plan.per_seg, plan.a, ctx->cos_table.as<double>(), d_out, d_dc, stream);
+    return windows_clips_staged_end(ctx, e, "mixed rates windows launch");
+}
+
+int vdf_hash_windows_clips_u8_rates_device(vdf_ctx *ctx, const vdf_windows_clips_rates_job *job)
+{
+    if (!ctx || !job) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    const hipStream_t s = job->stream ? (hipStream_t)job->stream : ctx->stream;
+    bool run;
+    if (int rc = windows_clips_checks(ctx, job->buf, job->buf_bytes, job->clips, job->n_frames, job->n_videos, job->window_stride, job->out_hashes, nullptr, false, s,
+                                      &run))
+        return rc;
+    if (int rc = windows_clips_rates_checks(ctx, job)) return rc;
+    if (!run) return VDF_OK;
+    // the rates travel to the kernel inside the plan, by value, and the row table through the staging: the caller's arrays are not read after this
+    const vdf::WindowsMixedRatesPlan plan = vdf::plan_windows_mixed_rates(reinterpret_cast<const vdf::MixedClip *>(job->clips), job->n_frames, job->n_videos,
+                                                                          job->window_stride, job->n_rates, job->rate_num, job->rate_den);
+    return hash_windows_clips_rates_locked(ctx, job->buf, job, plan, job->out_hashes, job->out_dontcare, s);
+}
+
+// Host arrays: as vdf_hash_windows_clips_u8_retimed - the buffer goes up ONCE, the device form's work runs on it, all blocks come down.
+int vdf_hash_windows_clips_u8_rates(vdf_ctx *ctx, const vdf_windows_clips_rates_job *job)
+{
+    if (!ctx || !job) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    bool run;
+    if (int rc = windows_clips_checks(ctx, job->buf, job->buf_bytes, job->clips, job->n_frames, job->n_videos, job->window_stride, job->out_hashes, nullptr, false,
+                                      ctx->stream, &run))
+        return rc;
+    if (int rc = windows_clips_rates_checks(ctx, job)) return rc;
+    if (!run) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    const vdf::WindowsMixedRatesPlan plan = vdf::plan_windows_mixed_rates(reinterpret_cast<const vdf::MixedClip *>(job->clips), job->n_frames, job->n_videos,
+                                                                          job->window_stride, job->n_rates, job->rate_num, job->rate_den);
+    const size_t n_out = (size_t)plan.rate_first[job->n_rates];
+    const size_t hash_bytes = n_out * VDF_HASH_WORDS * sizeof(uint64_t);
+    if (int rc = upload(ctx, ctx->frames, job->buf, job->buf_bytes, ctx->stream)) return rc;
+    VDF_HIP(ctx, ctx->out_hashes.reserve(hash_bytes));
+    if (job->out_dontcare) VDF_HIP(ctx, ctx->out_dc.reserve(n_out * sizeof(uint32_t)));
+    uint32_t *d_dc = job->out_dontcare ? ctx->out_dc.as<uint32_t>() : nullptr;
+    if (int rc = hash_windows_clips_rates_locked(ctx, ctx->frames.as<uint8_t>(), job, plan, ctx->out_hashes.as<uint64_t>(), d_dc, ctx->stream)) return rc;
+    VDF_HIP(ctx, hipMemcpyAsync(job->out_hashes, ctx->out_hashes.p, hash_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (job->out_dontcare) VDF_HIP(ctx, hipMemcpyAsync(job->out_dontcare, d_dc, n_out * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     VDF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return VDF_OK;
 }

@@ -3648,6 +3648,167 @@ hipError_t launch_dct_hash_windows_rates(const WindowsFrames &f, size_t n_clips,
     return hipGetLastError();
 }
 
+// ---- retimed window hashes of a mixed library at several rates in one launch (vdf_hash_windows_clips_u8_rates[_device]) ---------
+// dct_hash_windows_rates_kernel<true>'s body - WindowsRetimedShared, the chunk load with its three barriers, the ring of 64 frames at slot
+// (f - run) & 63, the inside-out walk: the segment's frames ONCE, chunk by chunk up to f_end, and behind every chunk, rate by rate, the windows
+// [max(k_begin, ready_r(have - 16)), min(k_end_r, ready_r(have))) through rates_windows_ready, NONE while have < span_r - with the three things
+// dct_hash_windows_mixed_retimed_kernel takes from the library instead of kernel arguments: the video is windows_video_of(seg_first, n_videos,
+// group) and one record read; frame f is at small + windows_mixed_frame_offset(vid, f), always on a dword boundary, so there is no byte form; the
+// output row is row0[r n_videos + v] + kk.  The window count is per video AND per rate: n_win_r = (F_v - span_r) / stride + 1 with F_v =
+// tail_first + 16 from the record (every F_v >= every span_r: the planner's check), so f_end - the last tap of the rates that own a window of this
+// segment - is never past the video's last frame.  The ring argument is the rates kernel's word for word: it speaks of one run of frames and of
+// spans up to 31, not of where the frames come from.  Everything indexed by r or v - taps, span, the record, row0 - is workgroup-uniform: scalar
+// loads.  LDS as the retimed kernels': 80 672 bytes.
+__global__ __launch_bounds__(256) void dct_hash_windows_mixed_rates_kernel(const uint8_t *__restrict__ small, const WindowsVideoRecord *__restrict__ videos,
+                                                                           const uint32_t *__restrict__ seg_first, const uint32_t *__restrict__ row0,
+                                                                           uint32_t n_videos, uint32_t stride, WindowsMixedRatesArgs rates, uint32_t per_seg,
+                                                                           uint32_t first_group, const double *__restrict__ cos_table,
+                                                                           uint64_t *__restrict__ out_hashes, uint32_t *__restrict__ out_dontcare)
+{
+    __shared__ WindowsRetimedShared sh;
+    const const_f64_ptr cosv = (const_f64_ptr)(uintptr_t)cos_table;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t group = first_group + blockIdx.x;  // the launcher's grid holds no group past seg_first[n_videos] (below 2^32: windows_mixed_rates_plan.h)
+    const uint32_t v = windows_video_of(seg_first, n_videos, group);
+    const WindowsVideoRecord vid = videos[v];
+    const uint32_t F = windows_mixed_rates_frames(vid);
+    const uint32_t seg = group - vid.seg_first;
+    const uint32_t k_begin = seg * per_seg;  // (n_seg * per_seg < max n_win + per_seg <= 2^32)
+    uint32_t f_end = 0;  // one past the last frame this workgroup reads: at most F, and above run (the rate with the most windows owns one here)
+    for (uint32_t r = 0; r < rates.n_rates; r++) {
+        const uint32_t n_win = (F - rates.span[r]) / stride + 1;
+        const uint32_t k_end = (uint32_t)min((unsigned long long)k_begin + per_seg, (unsigned long long)n_win);
+        if (k_end > k_begin) f_end = max(f_end, (k_end - 1) * stride + rates.span[r]);
+    }
+    DctTw cm;
+#pragma unroll
+    for (int i = 0; i < 4; i++) { cm.t16[i][0] = cosv[256 + 2 * i]; cm.t16[i][1] = cosv[257 + 2 * i]; }
+#pragma unroll
+    for (int i = 0; i < 2; i++) { cm.t8[i][0] = cosv[264 + 2 * i]; cm.t8[i][1] = cosv[265 + 2 * i]; }
+    cm.t4[0] = cosv[268]; cm.t4[1] = cosv[269]; cm.h = cosv[270];
+    if (tid < 128) (&sh.words[0][0][0])[tid] = 0u;  // (the first OR is behind the barriers of the first chunk)
+
+    uint32_t parity = 0;
+    const uint32_t run = k_begin * stride;  // the segment's first frame, slot 0 of the ring: its frames are one contiguous walk
+    uint32_t have = run;  // frames [max(run, have - 64), have) are resident; everything below is workgroup-uniform
+    while (have < f_end) {
+        // ---- the next chunk of 16 frames: frames at or past f_end are not read (their lanes repeat the last frame and store nothing)
+        {
+            const uint32_t t = tid >> 4, g = (tid >> 2) & 3, xq = tid & 3;
+            const uint32_t f = min(have + t, f_end - 1);
+            const uint8_t *p = small + windows_mixed_frame_offset(vid, f) + (4 * g) * 16 + 4 * xq;
+            uint32_t row[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) row[r] = *reinterpret_cast<const uint32_t *>(p + r * 16) ^ 0x80808080u;
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                uint32_t w = 0;
+#pragma unroll
+                for (int r = 0; r < 4; r++) w |= ((row[r] >> (8 * c)) & 255u) << (8 * r);
+                sh.cube[t * 64 + g * 16 + 4 * xq + c] = w;  // (last read: pass y of the previous chunk, two barriers ago)
+            }
+        }
+        __syncthreads();
+        {  // pass y: thread (t, x) owns one 16-pixel column
+            const uint32_t t = tid >> 4, x = tid & 15;
+            double v16[16], o[10];
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int32_t w = (int32_t)sh.cube[t * 64 + g * 16 + x];
+#pragma unroll
+                for (int r = 0; r < 4; r++) v16[4 * g + r] = (double)((w << (24 - 8 * r)) >> 24);
+            }
+            dct16_pruned(v16, o, cm);
+#pragma unroll
+            for (int ky = 0; ky < 10; ky++) sh.b[(t * 10 + ky) * kPadY + x] = o[ky];  // (last read: pass x of the previous chunk, one barrier ago)
+        }
+        __syncthreads();
+        if (tid < 160) {  // pass x: thread (t, ky) -> the frame's slot of the ring (last read: pass t of a window that starts 48 frames or more later)
+            double v16[16], ox[10];
+#pragma unroll
+            for (int x = 0; x < 16; x++) v16[x] = sh.b[tid * kPadY + x];
+            dct16_pruned(v16, ox, cm);
+            const uint32_t t = tid / 10, ky = tid - 10 * t;
+            if (have + t < f_end) {
+                const uint32_t slot = (have + t - run) & 63u;  // chunks begin at slot 0, 16, 32 or 48: dct_hash_block's bank pattern
+#pragma unroll
+                for (int kx = 0; kx < 10; kx++) sh.c[slot * kStrideT + 10 * kx + ky] = ox[kx];
+            }
+        }
+        __syncthreads();
+        have += 16;
+        // ---- pass t + sign + pack, rate by rate, for every window that became whole with this chunk, two at a time
+        for (uint32_t r = 0; r < rates.n_rates; r++) {
+            const uint32_t span = rates.span[r], n_win = (F - span) / stride + 1;
+            const uint64_t taps_lo = rates.taps_lo[r], taps_hi = rates.taps_hi[r];
+            const uint32_t first = row0[(size_t)r * n_videos + v];  // the row of the video's window 0 in block r: rate_first[r] + first[r][v]
+            const uint32_t k_end = (uint32_t)min((unsigned long long)k_begin + per_seg, (unsigned long long)n_win);
+            const uint32_t k_from = max(k_begin, rates_windows_ready(have - 16, span, stride));  // the rate's cursor: what the chunks before made whole
+            const uint32_t k_ready = min(k_end, rates_windows_ready(have, span, stride));          // 0 while have < span
+            for (uint32_t kp = k_from; kp < k_ready; kp += 2) {
+                const uint32_t half = wave >> 1, wv = wave & 1u, kk = kp + half;
+                if (kk < k_ready) {  // wave-uniform
+                    const uint32_t rem = 64u * wv + lane;  // 10 kx + ky; lanes with rem >= 100 idle
+                    const bool live = rem < 100;
+                    const uint32_t at = live ? rem : 0, s0 = kk * stride - run;
+                    double v16[16], o[10];
+#pragma unroll
+                    for (int t = 0; t < 16; t++) {
+                        const uint32_t tap = (uint32_t)((t < 8 ? taps_lo : taps_hi) >> (8 * (t & 7))) & 255u;  // wave-uniform: scalar
+                        v16[t] = sh.c[((s0 + tap) & 63u) * kStrideT + at];
+                    }
+                    dct16_pruned(v16, o, cm);
+                    unsigned long long piece = 0;
+                    uint32_t dc = 0;
+#pragma unroll
+                    for (int kt = 0; kt < 10; kt++) {
+                        const unsigned long long bits = __builtin_amdgcn_ballot_w64(live && o[kt] > 0.0);  // 0.0 and NaN -> 0
+                        const unsigned long long tiny = __builtin_amdgcn_ballot_w64(live && fabs(o[kt]) < 1e-6);
+                        dc += (uint32_t)__builtin_popcountll(tiny);
+                        if (lane == (uint32_t)kt) piece = bits;
+                    }
+                    uint32_t *words = sh.words[parity][half];
+                    if (lane < 10) {
+                        const uint32_t off = 100u * lane + 64u * wv, wi = off >> 5, sh_l = off & 31u;
+                        const uint32_t lo = (uint32_t)piece, hi = (uint32_t)(piece >> 32);
+                        atomicOr(&words[wi], lo << sh_l);
+                        atomicOr(&words[wi + 1], (hi << sh_l) | (sh_l ? lo >> (32u - sh_l) : 0u));
+                        if (sh_l && wi + 2 < 32) atomicOr(&words[wi + 2], hi >> (32u - sh_l));
+                    }
+                    if (lane == 0) sh.dc[parity][half][wv] = dc;
+                }
+                __syncthreads();
+                if ((tid & 127u) < 16) {  // the first 16 lanes of each window's first wave: store the words and clear them for the pair after the next
+                    const uint32_t i = tid & 127u;
+                    uint32_t *words = sh.words[parity][half];
+                    const unsigned long long w = (unsigned long long)words[2 * i] | ((unsigned long long)words[2 * i + 1] << 32);
+                    words[2 * i] = 0u;
+                    words[2 * i + 1] = 0u;
+                    if (kk < k_ready) {
+                        const size_t slot = (size_t)first + kk;  // the row the align calls read in block r
+                        out_hashes[slot * 16 + i] = w;
+                        if (out_dontcare && i == 0) out_dontcare[slot] = sh.dc[parity][half][0] + sh.dc[parity][half][1];
+                    }
+                }
+                parity ^= 1u;
+            }
+        }
+    }
+}
+
+hipError_t launch_dct_hash_windows_mixed_rates(const uint8_t *small, const WindowsVideoRecord *videos, const uint32_t *seg_first, const uint32_t *row0,
+                                               uint32_t n_videos, uint32_t n_groups, uint32_t stride, uint32_t per_seg, const WindowsMixedRatesArgs &rates,
+                                               const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream)
+{
+    if (n_videos == 0 || n_groups == 0 || rates.n_rates == 0) return hipSuccess;
+    for (uint64_t g0 = 0; g0 < n_groups; g0 += kMaxWindowGroupsPerLaunch) {
+        const uint32_t grid = retimed_grid(n_groups, g0);
+        hipLaunchKernelGGL(dct_hash_windows_mixed_rates_kernel, dim3(grid), dim3(256), 0, stream, small, videos, seg_first, row0, n_videos, stride, rates, per_seg,
+                           (uint32_t)g0, cos_table, out_hashes, out_dontcare);
+    }
+    return hipGetLastError();
+}
+
 static MfmaResizeTables make_tables(const MfmaResizeArgs &a)
 {
     MfmaResizeTables T;

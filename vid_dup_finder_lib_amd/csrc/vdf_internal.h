@@ -13,6 +13,7 @@
 #include "windows_retimed_plan.h"
 #include "windows_mixed_retimed_plan.h"
 #include "windows_rates_plan.h"
+#include "windows_mixed_rates_plan.h"
 #include "align_plan.h"
 #include "align_retimed_plan.h"
 
@@ -270,6 +271,13 @@ hipError_t launch_dct_hash_windows_mixed_retimed(const uint8_t *small, const Win
 // window k of clip c at rate r to row plan.a.out_first[r] + c n_win_r + k of out_hashes (16 words a row) and of out_dontcare (nullable)
 hipError_t launch_dct_hash_windows_rates(const WindowsFrames &f, size_t n_clips, const WindowsRatesPlan &plan, const double *cos_table,
                                          uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream);
+// ---- retimed window hashes of a mixed library at several rates (windows_mixed_rates_plan.h) --------------------------------------
+// small, videos, seg_first, n_groups as launch_dct_hash_windows_mixed (the records' n_win and seg_first: of the rate with the most windows); row0:
+// DEVICE copy of the plan's [n_rates][n_videos] table.  Window k of video i at rate r to row row0[r n_videos + i] + k.  Grids are cut at
+// kMaxWindowGroupsPerLaunch.
+hipError_t launch_dct_hash_windows_mixed_rates(const uint8_t *small, const WindowsVideoRecord *videos, const uint32_t *seg_first, const uint32_t *row0,
+                                               uint32_t n_videos, uint32_t n_groups, uint32_t stride, uint32_t per_seg, const WindowsMixedRatesArgs &rates,
+                                               const double *cos_table, uint64_t *out_hashes, uint32_t *out_dontcare, hipStream_t stream);
 // ---- the variant of a set of window hashes (window_variant.h) ------------------------------------------------------------------
 // rows [row0, row0 + n_rows) = [first[0], first[n_videos]) of out (and of out_skip, if skip is given) from hashes / zero / skip; variant 0 ... 7
 hipError_t launch_window_variants(const uint64_t *hashes, const uint64_t *zero, const uint32_t *first, uint32_t n_videos, const uint8_t *skip,

@@ -144,6 +144,28 @@ def hash_windows_first_retimed(n_frames, rate, stride: int = 1) -> np.ndarray:
     return first
 
 
+def hash_windows_first_rates(n_frames, rates, stride: int = 1):
+    """vdf_hash_windows_clips_first_rates (host only, no context): (first [n_rates, n_videos + 1] u32, rate_first [n_rates + 1] int64) of
+    Engine.hash_windows_clips_rates' rate-major outputs.  Row r of first is hash_windows_first_retimed(n_frames, rates[r], stride); window k of
+    video i at rate r is row rate_first[r] + first[r, i] + k, and rate_first[-1] is the number of rows.  VdfError: a video of fewer frames than a
+    window of one of the rates spans (VDF_E_NOT_ENOUGH_FRAMES); no or more than 8 rates, a rate outside the range or 2^32 rows or more
+    (VDF_E_INVAL)."""
+    nf = np.asarray(n_frames).reshape(-1)
+    if nf.size and (np.any(nf != nf.astype(np.int64)) or int(nf.min()) < 0 or int(nf.max()) >= 2**32):
+        raise ValueError("frame counts must be integers in 0 .. 2^32 - 1")
+    nf = np.ascontiguousarray(nf, dtype=np.uint32)
+    num, den = _window_rates(rates)
+    first = np.zeros((max(len(num), 1), nf.size + 1), np.uint32)
+    rate_first = np.zeros(len(num) + 1, np.uintp)
+    rc = _capi.load().vdf_hash_windows_clips_first_rates(nf.ctypes.data if nf.size else None, nf.size, _window_stride(stride), len(num),
+                                                         num.ctypes.data if len(num) else None, den.ctypes.data if len(num) else None, first.ctypes.data,
+                                                         rate_first.ctypes.data)
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_hash_windows_clips_first_rates: " + ("a video of fewer frames than a retimed window spans" if rc == _capi.VDF_E_NOT_ENOUGH_FRAMES
+                                                                     else "no or more than 8 rates, a rate outside the range, or 2^32 rows or more"))
+    return first[:len(num)], rate_first.astype(np.int64)
+
+
 def _align_host_args(a_hashes, a_first, b_hashes, b_first, a_skip, b_skip):
     """The host arrays of an align call as the C ABI takes them; b_hashes None = self mode.  Returns the arrays (to keep alive) and
     (a_hashes, a_first, n_a, a_skip, b_hashes, b_first, n_b, b_skip) as ctypes arguments."""
@@ -891,6 +913,57 @@ class Engine:
         self._check(self.lib.vdf_hash_windows_clips_u8_retimed_device(self.ctx, d_buf or None, int(buf_bytes), c.ctypes.data if c.size else None,
                                                                       nf.ctypes.data if nf.size else None, c.size, _window_stride(stride), num, den,
                                                                       d_out or None, d_dontcare or None, stream or None))
+
+    # --------------------------------------------- retimed windows of a whole library at several rates in one call (include/vdf.h)
+    def _windows_clips_rates_job(self, buf_ptr, buf_bytes, clips, n_frames, stride, rates, out_ptr, dc_ptr, stream):
+        """(job, what it points into): the job of vdf_hash_windows_clips_u8_rates[_device]; the arrays must outlive the call."""
+        num, den = _window_rates(rates)
+        n = int(clips.size)
+        job = _capi.VdfWindowsClipsRatesJob(buf_ptr or None, int(buf_bytes), clips.ctypes.data if n else None, n_frames.ctypes.data if n else None, n,
+                                            _window_stride(stride), len(num), num.ctypes.data if len(num) else None, den.ctypes.data if len(num) else None,
+                                            out_ptr or None, dc_ptr or None, stream or None)
+        return job, (num, den, clips, n_frames)
+
+    def hash_windows_clips_rates(self, stacks: Sequence[np.ndarray], rates, stride: int = 1, crops=None, want_dontcare: bool = False):
+        """hash_windows_clips_retimed at up to 8 rates [(num, den), ...] from ONE upload, one resize and one spatial transform of every frame
+        (vdf_hash_windows_clips_u8_rates).  stacks = a list of [F_i, H_i, W_i] u8 arrays, every F_i at least the longest span of the list; crops
+        (optional) = [n, 4] u32 left, right, top, bottom per video, read in place.
+        -> (words, first [, dontcare]): words = one [n_total_r, 16] u64 array per listed rate, first [n_rates, n + 1] u32 (hash_windows_first_rates),
+        dontcare = one [n_total_r] u32 array per rate.  (words[r], first[r]) is what hash_windows_clips_retimed(stacks, rates[r], stride) gives and
+        what align_windows_retimed* reads as its A side; the (1, 1) block is a B side."""
+        stride = _window_stride(stride)
+        buf, clips, n_frames = self._pack_videos(stacks, crops)
+        # a video shorter than a span has no window at that rate and a bad list has no layout: the library names both (first would not), and
+        # then writes nothing; the buffers are sized without them
+        spans = [(15 * n) // d + 1 for n, d in (_window_rate(r) for r in rates) if 1 <= d <= n <= 2 * d and n <= 65535]
+        try:
+            first, rate_first = hash_windows_first_rates(np.maximum(n_frames, max(spans, default=16)), rates, stride)
+        except VdfError:
+            first, rate_first = np.zeros((0, len(clips) + 1), np.uint32), np.zeros(1, np.int64)
+        rows = int(rate_first[-1])
+        out = np.zeros((rows, HASH_WORDS), np.uint64)
+        dc = np.zeros(rows, np.uint32) if want_dontcare else None
+        job, keep = self._windows_clips_rates_job(buf.ctypes.data, buf.size, clips, n_frames, stride, rates, out.ctypes.data if first.shape[0] else 0,
+                                                  dc.ctypes.data if want_dontcare and first.shape[0] else 0, 0)
+        self._check(self.lib.vdf_hash_windows_clips_u8_rates(self.ctx, C.byref(job)))
+        del keep
+        if first.shape[0] == 0:
+            raise VdfError(_capi.VDF_E_INVAL, "vdf_hash_windows_clips_u8_rates took a list of rates that has no layout")
+        words = [out[rate_first[r]:rate_first[r + 1]] for r in range(first.shape[0])]
+        return (words, first, [dc[rate_first[r]:rate_first[r + 1]] for r in range(first.shape[0])]) if want_dontcare else (words, first)
+
+    def hash_windows_clips_rates_device(self, d_buf: int, buf_bytes: int, clips: np.ndarray, n_frames, stride: int, rates, d_out: int,
+                                        d_dontcare: int = 0, stream: int = 0):
+        """vdf_hash_windows_clips_u8_rates_device: clips = HOST array of CLIP_DTYPE records (offsets relative to d_buf), n_frames = HOST frame
+        counts, rates = HOST list; every address is checked against buf_bytes before anything is queued.  d_out: 16 words for each of the
+        hash_windows_first_rates(n_frames, rates, stride)[1][-1] rows, rate-major; d_dontcare (optional): one u32 per row.  Ordered on `stream`."""
+        c = np.ascontiguousarray(clips, dtype=CLIP_DTYPE).reshape(-1)
+        nf = np.ascontiguousarray(n_frames, dtype=np.uint32).reshape(-1)
+        if nf.size != c.size:
+            raise ValueError("one frame count per video")
+        job, keep = self._windows_clips_rates_job(d_buf, buf_bytes, c, nf, stride, rates, d_out, d_dontcare, stream)
+        self._check(self.lib.vdf_hash_windows_clips_u8_rates_device(self.ctx, C.byref(job)))
+        del keep
 
     # --------------------------------------------- flipped and reversed stretches (include/vdf.h, DESIGN.md 4.11)
     def window_variants(self, d_hashes: int, d_zero: int, d_first: int, n_videos: int, variant: int, d_out: int, d_skip: int = 0, d_out_skip: int = 0,

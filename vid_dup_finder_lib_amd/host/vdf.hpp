@@ -449,6 +449,69 @@ public:
         if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
     }
 
+    // hash_windows_clips_retimed at up to VDF_WINDOWS_MAX_RATES rates from ONE upload, one resize and one spatial transform of every frame
+    // (vdf_hash_windows_clips_u8_rates): out[r] = what hash_windows_clips_retimed gives at rates[r] = {num, den}; {1, 1} gives the
+    // plain windows.  A video shorter than the longest span of the list: not_enough_frames.
+    static std::vector<std::vector<std::vector<VideoHash>>> hash_windows_clips_rates(const std::vector<Video> &videos, uint32_t stride,
+                                                                                     const std::vector<std::array<uint32_t, 2>> &rates,
+                                                                                     Context *ctx_opt = nullptr)
+    {
+        if (rates.empty() || rates.size() > VDF_WINDOWS_MAX_RATES) throw std::invalid_argument("1 ... 8 rates");
+        Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+        const size_t n = videos.size();
+        const uint32_t n_rates = (uint32_t)rates.size();
+        std::vector<uint32_t> num(n_rates), den(n_rates);
+        for (uint32_t r = 0; r < n_rates; r++) { num[r] = rates[r][0]; den[r] = rates[r][1]; }
+        std::vector<vdf_clip> clips(n);
+        std::vector<uint32_t> n_frames(n), first((size_t)n_rates * (n + 1));
+        std::vector<size_t> rate_first(n_rates + 1);
+        size_t at = 0;
+        for (size_t i = 0; i < n; i++) {
+            const Video &v = videos[i];
+            clips[i] = vdf_clip{at, (uint64_t)v.w * v.h, v.w, v.h, v.crop[0], v.crop[1], v.crop[2], v.crop[3]};
+            n_frames[i] = v.n_frames;
+            at += ((size_t)v.n_frames * v.w * v.h + 63) & ~(size_t)63;
+        }
+        const int rf = vdf_hash_windows_clips_first_rates(n_frames.data(), n, stride, n_rates, num.data(), den.data(), first.data(), rate_first.data());
+        if (rf == VDF_E_NOT_ENOUGH_FRAMES) throw Error::not_enough_frames();
+        if (rf != VDF_OK) throw std::invalid_argument("a window stride of zero, a rate outside 1 <= den <= num <= 2 den, or 2^32 windows or more in one call");
+        std::vector<uint8_t> packed(at);
+        for (size_t i = 0; i < n; i++)
+            std::copy(videos[i].frames, videos[i].frames + (size_t)videos[i].n_frames * videos[i].w * videos[i].h, packed.begin() + (size_t)clips[i].offset);
+        std::vector<uint64_t> words(rate_first[n_rates] * VDF_HASH_WORDS);
+        const vdf_windows_clips_rates_job job{packed.data(), packed.size(), clips.data(), n_frames.data(), n, stride, n_rates, num.data(), den.data(),
+                                              words.data(), nullptr, nullptr};
+        const int rc = vdf_hash_windows_clips_u8_rates(ctx.get(), &job);
+        if (rc == VDF_E_NOT_ENOUGH_FRAMES) throw Error::not_enough_frames();
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+        std::vector<std::vector<std::vector<VideoHash>>> out(n_rates, std::vector<std::vector<VideoHash>>(n));
+        for (uint32_t r = 0; r < n_rates; r++)
+            for (size_t i = 0; i < n; i++)
+                for (size_t k = first[(size_t)r * (n + 1) + i]; k < first[(size_t)r * (n + 1) + i + 1]; k++) {
+                    const size_t row = rate_first[r] + k;
+                    std::array<uint64_t, VDF_HASH_WORDS> hw;
+                    std::copy(words.begin() + row * VDF_HASH_WORDS, words.begin() + (row + 1) * VDF_HASH_WORDS, hw.begin());
+                    out[r][i].emplace_back(hw, videos[i].src_path, videos[i].duration);
+                }
+        return out;
+    }
+    // The same on device memory, ordered on `stream`: clips and n_frames are HOST arrays; d_out = 16 words for each of
+    // vdf_hash_windows_clips_first_rates' rows, rate-major: window k of video i at rate r at row rate_first[r] + first[r][i] + k.
+    static void hash_windows_clips_rates_device(Context &ctx, const uint8_t *d_buf, size_t buf_bytes, const vdf_clip *clips, const uint32_t *n_frames,
+                                                size_t n_videos, uint32_t stride, const std::vector<std::array<uint32_t, 2>> &rates, uint64_t *d_out,
+                                                uint32_t *d_dontcare = nullptr, void *stream = nullptr)
+    {
+        std::vector<uint32_t> num(rates.size()), den(rates.size());
+        for (size_t r = 0; r < rates.size(); r++) { num[r] = rates[r][0]; den[r] = rates[r][1]; }
+        const vdf_windows_clips_rates_job job{d_buf, buf_bytes, clips, n_frames, n_videos, stride, (uint32_t)rates.size(), num.data(), den.data(), d_out,
+                                              d_dontcare, stream};
+        const int rc = vdf_hash_windows_clips_u8_rates_device(ctx.get(), &job);
+        if (rc == VDF_E_NOT_ENOUGH_FRAMES) throw Error::not_enough_frames();
+        if (rc == VDF_E_BAD_DIMS) throw Error::vid_proc(vdf_last_error(ctx.get()));
+        if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+    }
+
     // Which videos share a stretch, at what offset, for how long (vdf_align_windows): windows_a / windows_b = hash_windows'
     // results (videos may differ in length); windows_b null: the videos of windows_a against each other, every pair a < b once.  At most one
     // record per pair of videos, in (a, b) order: the best run of consecutive windows within tol_int on one diagonal (offset = kb - ka), of at
