@@ -549,6 +549,72 @@ int vdf_align_windows_retimed_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_has
                                            uint32_t min_run, uint32_t rate_num, uint32_t rate_den, vdf_alignment_retimed *out,
                                            size_t capacity, size_t *n_out, void *stream);
 
+/* ---- the retimed alignment, seeded: the candidates of every phase of up to VDF_WINDOWS_MAX_RATES rates from one pass ----
+ * Which pairs (a, b) can have a record of vdf_align_windows_retimed* at which rate of a list?  A is what vdf_hash_windows_clips_u8_rates*
+ * writes - one block of retimed windows per listed rate, rate-major - B holds plain windows at stride 1 (the 1/1 block of such a call).
+ * Rate r of the list is reduced by its gcd to num / den.  Counted inside their videos,
+ *   - a SEED under r is window ka of video a of block r with (ka / num) % min_run == 0 (integer division): sub-sampled index i = ka / num of
+ *     phase p = ka % num, with i a multiple of min_run;
+ *   - a ROW under r is window kb of video b with kb % den == 0;
+ *   - pair (a, b) is a CANDIDATE UNDER r iff some seed and some row have both skip bytes 0 and a distance over all 16 words <= tol =
+ *     min(tol_int, 1024); with exclude_same != 0 (requires n_a == n_b: a library against itself) a pair with a == b is never a candidate.
+ * A run of >= min_run cells on a diagonal of a phase's sub-matrix holds an i that is a multiple of min_run, so the set holds every pair with a
+ * record of vdf_align_windows_retimed* at r; it is the union over p < num of vdf_align_seed_pairs' set on (windows p, p + num, ... of A's videos;
+ * windows 0, den, ... of B's).  At 1/1 it is vdf_align_seed_pairs' set between the two sets.  There is no self mode (b_hashes == NULL with
+ * n_b > 0 is a null pointer).  Duplicate and unreduced rates are legal, each listed rate gets its slot.
+ * The job - the call's whole argument list, as vdf_windows_clips_rates_job is:
+ *   a_hashes, a_skip (nullable)   the rows of A; a_first: n_rates x (n_a + 1) entries, row r at a_first + r (n_a + 1); a_rate_first: HOST array of
+ *                              n_rates + 1 size_t (only the first n_rates are read), nullable = zeros - what vdf_hash_windows_clips_first_rates
+ *                              fills.  Window k of video i at rate r is row a_rate_first[r] + a_first[r][i] + k of a_hashes and a_skip: a hash
+ *                              call's outputs go in unchanged.  Fewer than 2^32 rows in all;
+ *   b_hashes, b_first, b_skip, n_b   as vdf_align_seed_pairs takes them;
+ *   n_rates, rate_num, rate_den   1 ... VDF_WINDOWS_MAX_RATES rates, HOST arrays in all forms;
+ *   tol_int, min_run, exclude_same;
+ *   out, capacity, n_out       HOST buffer of `capacity` vdf_video_pair_rate triples in (rate, a, b) order - rate is the index into the job's
+ *                              list; *n_out = the number found over all rates, the first `capacity` are valid if it exceeds capacity - VDF_OK;
+ *   stream                     device form only: the call is ordered on it, NULL = the context's stream.
+ * Errors, all VDF_E_INVAL, in this order: a null job or ctx; the checks of vdf_align_seed_pairs in its order of KINDS - null pointers (n_out; out
+ * with capacity > 0; hashes or first array of a side that has videos), min_run == 0, a video above 2^20 windows, a first array that decreases,
+ * 2^32 rows of A or more, more than 2^24 pairs of videos - each kind on B first and then on the blocks of A in list order (the blocks of the first
+ * min(n_rates, VDF_WINDOWS_MAX_RATES) rates); n_rates outside 1 ... VDF_WINDOWS_MAX_RATES or a null rate array; the first rate outside
+ * 1 <= den <= num <= 2 den; the first rate with a reduced num above VDF_ALIGN_RETIMED_MAX_NUM; exclude_same with n_a != n_b; a multi-GPU context.
+ * n_a == 0 or n_b == 0: VDF_OK with *n_out = 0.  The device form makes every check that needs no first array, in that order, reads the first
+ * arrays back, and checks them.
+ * _host: plain C++, no context, no GPU - the CPU-tested statement of the semantics.  vdf_align_seed_pairs_rates: host arrays, uploaded once.
+ * _device: DEVICE arrays (hashes, first arrays, skip bytes); the rate arrays, a_rate_first and out stay on the host; the call waits for its own
+ * work.  The context forms make ONE pass: rates that share a den share their gathered rows of B, and the seeds of every phase of every rate
+ * stream past them in one launch.  Skip bytes of A are read as the other seed calls read them (the aligned 32-bit word).
+ * Not offered: a list-form align over (rate, a, b) triples in one call; zero planes; multi-GPU contexts. */
+typedef struct vdf_video_pair_rate { /* 12 bytes */
+    uint32_t a;                /* video index in A */
+    uint32_t b;                /* video index in B */
+    uint32_t rate;             /* index into the job's rate list */
+} vdf_video_pair_rate;
+typedef struct vdf_align_seed_rates_job {
+    const uint64_t *a_hashes;
+    const uint32_t *a_first;
+    const size_t *a_rate_first;
+    const uint8_t *a_skip;
+    size_t n_a;
+    const uint64_t *b_hashes;
+    const uint32_t *b_first;
+    const uint8_t *b_skip;
+    size_t n_b;
+    uint32_t n_rates;
+    const uint32_t *rate_num;
+    const uint32_t *rate_den;
+    uint32_t tol_int;
+    uint32_t min_run;
+    uint32_t exclude_same;
+    vdf_video_pair_rate *out;
+    size_t capacity;
+    size_t *n_out;
+    void *stream;
+} vdf_align_seed_rates_job;
+int vdf_align_seed_pairs_rates_host(const vdf_align_seed_rates_job *job);
+int vdf_align_seed_pairs_rates(vdf_ctx *ctx, const vdf_align_seed_rates_job *job);
+int vdf_align_seed_pairs_rates_device(vdf_ctx *ctx, const vdf_align_seed_rates_job *job);
+
 /* ---- mirrored, flipped and reversed STRETCHES: window hashes with their zero planes -----------------------
  * A mirrored re-upload with its intro trimmed: the variant search sees only frames 0 ... 15 of a file, the align calls only unflipped
  * stretches.  With the zero plane of every window (vdf_hash_windows_u8_planes*) the window hashes of the flipped video follow from the

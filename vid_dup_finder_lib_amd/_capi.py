@@ -134,6 +134,18 @@ class VdfWindowsClipsRatesJob(C.Structure):
                 ("out_hashes", C.c_void_p), ("out_dontcare", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class VdfAlignSeedRatesJob(C.Structure):
+    """The argument list of vdf_align_seed_pairs_rates[_host|_device] (include/vdf.h: vdf_align_seed_rates_job)."""
+    _fields_ = [("a_hashes", C.c_void_p), ("a_first", C.c_void_p), ("a_rate_first", C.c_void_p), ("a_skip", C.c_void_p), ("n_a", C.c_size_t),
+                ("b_hashes", C.c_void_p), ("b_first", C.c_void_p), ("b_skip", C.c_void_p), ("n_b", C.c_size_t), ("n_rates", C.c_uint32),
+                ("rate_num", C.c_void_p), ("rate_den", C.c_void_p), ("tol_int", C.c_uint32), ("min_run", C.c_uint32), ("exclude_same", C.c_uint32),
+                ("out", C.c_void_p), ("capacity", C.c_size_t), ("n_out", C.POINTER(C.c_size_t)), ("stream", C.c_void_p)]
+
+
+# one (a, b, rate) triple of vdf_align_seed_pairs_rates* (include/vdf.h: vdf_video_pair_rate, 12 bytes); rate = the index into the call's list
+VIDEO_PAIR_RATE_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("rate", "<u4")])
+
+
 class VdfVideoPair(C.Structure):
     """One pair of vdf_align_seed_pairs* and of the lists of the *_pairs calls: 8 bytes (the numpy twin is engine.VIDEO_PAIR_DTYPE)."""
     _fields_ = [("a", C.c_uint32), ("b", C.c_uint32)]
@@ -274,6 +286,10 @@ SIGNATURES = {
     "vdf_align_seed_pairs_host": (C.c_int, _ALIGN_SIDES + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vdf_align_seed_pairs": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vdf_align_seed_pairs_device": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    # the retimed alignment seeded at every rate of a list: (job) / (ctx, job)
+    "vdf_align_seed_pairs_rates_host": (C.c_int, [C.POINTER(VdfAlignSeedRatesJob)]),
+    "vdf_align_seed_pairs_rates": (C.c_int, [_ctx, C.POINTER(VdfAlignSeedRatesJob)]),
+    "vdf_align_seed_pairs_rates_device": (C.c_int, [_ctx, C.POINTER(VdfAlignSeedRatesJob)]),
     "vdf_align_windows_pairs_host": (C.c_int, _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vdf_align_windows_pairs": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                                                    C.POINTER(C.c_size_t)]),

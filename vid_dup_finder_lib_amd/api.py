@@ -22,10 +22,11 @@ from ._capi import DEFAULT_SEARCH_TOLERANCE, HASH_BITS, HASH_WORDS, TOLERANCE_SC
 from .engine import (ALIGN_DTYPE, ALIGN_STRETCH_DTYPE, ALIGN_VARIANT_DTYPE, Engine, align_windows_host, align_windows_stretches_host, align_windows_variants_host, hamming_distance_words, hash_variant,
                      tolerance_int, video_pairs, align_seed_pairs_host, align_windows_pairs_host, align_windows_stretches_pairs_host,
                      ALIGN_RETIMED_DTYPE, VIDEO_PAIR_DTYPE, align_windows_retimed_host, align_windows_retimed_pairs_host,
-                     pair_list_problem, VIDEO_PAIR_VARIANT_DTYPE, align_seed_pairs_variants_host, align_windows_variants_pairs_host)
+                     pair_list_problem, VIDEO_PAIR_VARIANT_DTYPE, align_seed_pairs_variants_host, align_windows_variants_pairs_host,
+                     VIDEO_PAIR_RATE_DTYPE, align_seed_pairs_rates_host)
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
-           "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "hash_frame_windows", "align_rates", "best_rates", "locate", "rust_path_key", "sort_order",
+           "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "hash_frame_windows", "align_rates", "best_rates", "candidate_pairs_rates", "locate", "rust_path_key", "sort_order",
            "DEFAULT_SEARCH_TOLERANCE", "TOLERANCE_SCALING_FACTOR"]
 
 
@@ -1022,13 +1023,158 @@ def align_retimed(windows_a: List[List[VideoHash]], windows_b: List[List[VideoHa
             for (a, b), (_, fa, fb, n, ds) in sorted(best.items())]
 
 
+def _retimed_rate(rate):
+    """(num, den) of a rate in lowest terms, refused as align_retimed refuses it."""
+    try:
+        num, den = (int(x) for x in rate)
+        if (num, den) != tuple(rate):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"rate must be a pair of integers (num, den), not {rate!r}") from None
+    if not 1 <= den <= num <= 2 * den:
+        raise ValueError("rate must have 1 <= den <= num <= 2 den")
+    g = math.gcd(num, den)
+    num, den = num // g, den // g
+    if num > ALIGN_RETIMED_MAX_NUM:
+        raise ValueError(f"align_retimed makes num sub-calls: num = {num} is above {ALIGN_RETIMED_MAX_NUM}")
+    return num, den
+
+
+def _rates_csr(windows_by_rate_a, static_a):
+    """The A side of the seeded retimed call: one CSR per rate (words, first, skip, counts), every rate over the same videos."""
+    rates = list(windows_by_rate_a)
+    if not 1 <= len(rates) <= _capi.WINDOWS_MAX_RATES:
+        raise ValueError(f"1 .. {_capi.WINDOWS_MAX_RATES} rates in one pass, not {len(rates)}")
+    per = [_align_csr(windows_by_rate_a[r], None if static_a is None else static_a.get(r)) for r in rates]
+    if len({len(c[3]) for c in per}) != 1:
+        raise ValueError("every rate holds the windows of the same videos")
+    return rates, per
+
+
+def _rates_block(per, lo, hi):
+    """The videos [lo, hi) of every rate's CSR as ONE rate-major set: (words, first [n_rates, hi - lo + 1], rate_first, skip or None)."""
+    cuts = [(int(f[lo]), int(f[hi])) for _, f, _, _ in per]
+    first = np.stack([f[lo:hi + 1] - f[lo] for _, f, _, _ in per]).astype(np.uint32)
+    rate_first = np.zeros(len(per) + 1, np.int64)
+    rate_first[1:] = np.cumsum([w1 - w0 for w0, w1 in cuts])
+    words = np.concatenate([w[w0:w1] for (w, _, _, _), (w0, w1) in zip(per, cuts)])
+    skip = None
+    if any(k is not None for _, _, k, _ in per):
+        skip = np.concatenate([np.zeros(w1 - w0, np.uint8) if k is None else k[w0:w1] for (_, _, k, _), (w0, w1) in zip(per, cuts)])
+    return words, first, rate_first, skip
+
+
+def _seed_rates_call(engine, A, B, rates, tol_int, min_run, exclude_same):
+    """_seed_call for the seeded retimed call: the (a, b, rate) triples of one call, VIDEO_PAIR_RATE_DTYPE in (rate, a, b) order."""
+    def once(capacity):
+        kw = dict(tol_int=tol_int, min_run=min_run, a_rate_first=A[2], a_skip=A[3], b_skip=B[2], exclude_same=exclude_same, capacity=capacity)
+        call = align_seed_pairs_rates_host if engine is None else engine.align_seed_pairs_rates
+        return call(A[0], A[1], B[0], B[1], rates, **kw)
+    t, found = once(ALIGN_FIRST_CAPACITY)
+    if found > len(t):
+        t, found = once(found)
+    return t
+
+
+def _candidate_blocks_rates(per, csr_b, rates, tol_int, min_run, engine, exclude_same):
+    """Every block of at most ALIGN_MAX_PAIRS pairs of videos with its triples: yields (a0, a1, b0, b1, B block, triples counted inside the block)."""
+    wb, fb, kb, cb = csr_b
+    n_a = len(per[0][3])
+    if exclude_same and n_a != len(cb):
+        raise ValueError("exclude_same takes the same number of videos on both sides")
+    step = max(1, math.isqrt(ALIGN_MAX_PAIRS))
+    for a0 in range(0, n_a, step):
+        a1 = min(a0 + step, n_a)
+        A = _rates_block(per, a0, a1)
+        for b0 in range(0, len(cb), step):
+            b1 = min(b0 + step, len(cb))
+            w0, w1 = int(fb[b0]), int(fb[b1])
+            B = (wb[w0:w1], fb[b0:b1 + 1] - fb[b0], None if kb is None else kb[w0:w1])
+            yield a0, a1, b0, b1, B, _seed_rates_call(engine, A, B, rates, tol_int, min_run, bool(exclude_same) and a0 == b0)
+
+
+def _rates_engine(engine, rates, per, cb):
+    """With no engine given, tiny inputs are walked on the CPU - the rule of align_retimed(native=True), per rate."""
+    if engine is None and any(sum(c[3]) * sum(cb) // _retimed_rate(r)[1] > ALIGN_HOST_CELLS for r, c in zip(rates, per)):
+        return default_engine()
+    return engine
+
+
+def candidate_pairs_rates(windows_by_rate_a: dict, windows_b: List[List[VideoHash]], tolerance: float = DEFAULT_SEARCH_TOLERANCE, min_run: int = 1,
+                          static_a: Optional[dict] = None, static_b=None, engine: Optional[Engine] = None, exclude_same: bool = False) -> dict:
+    """Which pairs of videos can be a retimed copy of each other, at which of several rates?  Arguments as align_rates (at most 8 rates);
+    -> {rate: [(a, b)] in (a, b) order}: the pairs with a window ka of a at that rate, (ka // num) % min_run == 0, and a window kb of b, kb % den
+    == 0, within `tolerance` of each other, neither static (include/vdf.h: vdf_align_seed_pairs_rates).  Every pair align_retimed reports at a
+    rate is among that rate's candidates.  Every phase of every rate is seeded by ONE call per block of at most ALIGN_MAX_PAIRS pairs of videos
+    (DESIGN.md 4.22).  exclude_same: a pair (i, i) is never a candidate - for a library against itself."""
+    tol_int = tolerance_int(tolerance)
+    rates, per = _rates_csr(windows_by_rate_a, static_a)
+    for r in rates:
+        _retimed_rate(r)
+    csr_b = _align_csr(windows_b, static_b)
+    engine = _rates_engine(engine, rates, per, csr_b[3])
+    out = {r: [] for r in rates}
+    for a0, _, b0, _, _, t in _candidate_blocks_rates(per, csr_b, rates, tol_int, int(min_run), engine, exclude_same):
+        for a, b, r in zip(t["a"], t["b"], t["rate"]):
+            out[rates[int(r)]].append((int(a) + a0, int(b) + b0))
+    return {r: sorted(p) for r, p in out.items()}
+
+
+def _align_rates_one_pass(windows_by_rate_a, windows_b, tolerance, min_run, static_a, static_b, engine, pairs):
+    """align_rates(one_pass=True): the CSR of B once and of each rate's A once; per block of videos ONE seed call for all rates
+    (vdf_align_seed_pairs_rates), then one vdf_align_windows_retimed_pairs call per rate that has candidates."""
+    tol_int = tolerance_int(tolerance)
+    rates, per = _rates_csr(windows_by_rate_a, static_a)
+    reduced = [_retimed_rate(r) for r in rates]
+    csr_b = _align_csr(windows_b, static_b)
+    pair_list = _align_pair_list(pairs, len(per[0][3]), len(csr_b[3]), False)
+    engine = _rates_engine(engine, rates, per, csr_b[3])
+    key = lambda p: (p["a"].astype(np.uint64) << np.uint64(32)) | p["b"].astype(np.uint64)
+    parts = [[] for _ in rates]
+    for a0, a1, b0, b1, B, t in _candidate_blocks_rates(per, csr_b, rates, tol_int, int(min_run), engine, False):
+        plist = _block_pairs(engine, None, None, a0, a1, b0, b1, tol_int, int(min_run), pair_list, False)
+        for i, (num, den) in enumerate(reduced):
+            cand = np.zeros(int(np.count_nonzero(t["rate"] == i)), VIDEO_PAIR_DTYPE)
+            cand["a"], cand["b"] = t["a"][t["rate"] == i], t["b"][t["rate"] == i]
+            if plist is not None:
+                cand = plist[np.isin(key(plist), key(cand))]
+            if not len(cand):
+                continue
+            w, f, k, _ = per[i]
+            w0, w1 = int(f[a0]), int(f[a1])
+            A = (w[w0:w1], f[a0:a1 + 1] - f[a0], None if k is None else k[w0:w1])
+            rec = _retimed_call(engine, A, B, tol_int, int(min_run), (num, den), cand).copy()
+            rec["a"] += a0
+            rec["b"] += b0
+            parts[i].append(rec)
+    pb = [ws[0].src_path() if ws else None for ws in windows_b]
+    out = {}
+    for i, (rate, (num, den)) in enumerate(zip(rates, reduced)):
+        rec = np.concatenate(parts[i]) if parts[i] else np.zeros(0, ALIGN_RETIMED_DTYPE)
+        rec = rec[np.lexsort((rec["b"], rec["a"]))]
+        pa = [ws[0].src_path() if ws else None for ws in windows_by_rate_a[rate]]
+        span = (15 * num) // den + 1
+        out[rate] = []
+        for r in rec:
+            a, b, fa, fb, n, ds = (int(r[k]) for k in ("a", "b", "first_a", "first_b", "n_windows", "dist_sum"))
+            out[rate].append(RetimedAlignment(a, b, num, den, fa, fb, (n - 1) * num + span, (n - 1) * den + _capi.DCT_SIZE, n, ds / n, pa[a], pb[b]))
+    return out
+
+
 def align_rates(windows_by_rate_a: dict, windows_b: List[List[VideoHash]], tolerance: float = DEFAULT_SEARCH_TOLERANCE, min_run: int = 1,
                 static_a: Optional[dict] = None, static_b=None, engine: Optional[Engine] = None, native: bool = True, seed: bool = False,
-                pairs=None) -> dict:
+                pairs=None, one_pass: bool = False) -> dict:
     """Which videos of A are a retimed copy of which video of B, at which of several rates?  windows_by_rate_a: {(num, den): windows of A at that
     rate}, as hash_frame_windows(..., rates=[...]) returns it, stride 1; windows_b: the PLAIN windows of B at stride 1 (the (1, 1) entry of such a
     dict).  One align_retimed call per rate, in the dict's order, with everything else handed through (static_a: {rate: flags per video} or None)
-    -> {rate: List[RetimedAlignment]}.  best_rates picks one record per pair from it."""
+    -> {rate: List[RetimedAlignment]}.  best_rates picks one record per pair from it.
+    one_pass=True (needs seed=True and native=True; at most 8 rates): the same dict, but every phase of every rate is seeded by ONE call per block
+    of videos (candidate_pairs_rates' call) instead of num calls per rate on sub-sampled copies, and each rate that has candidates then makes its
+    one align call on them."""
+    if one_pass:
+        if not (seed and native):
+            raise ValueError("one_pass=True needs seed=True and native=True")
+        return _align_rates_one_pass(windows_by_rate_a, windows_b, tolerance, min_run, static_a, static_b, engine, pairs)
     return {rate: align_retimed(ws, windows_b, rate, tolerance, min_run=min_run, static_a=None if static_a is None else static_a.get(rate), static_b=static_b,
                                 engine=engine, seed=seed, native=native, pairs=pairs)
             for rate, ws in windows_by_rate_a.items()}

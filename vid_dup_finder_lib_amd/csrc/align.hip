@@ -21,8 +21,11 @@
 // DESIGN.md 4.14; window_class_layout.h).
 // align_bands_retimed_kernel / align_reduce_retimed_kernel, behind launch_align_chunk: the band walk on the strided rows of a phase's sub-matrix
 // and the two-level reduction bands -> phase-best -> pair record (vdf_align_windows_retimed*; align_retimed_plan.h).
+// align_seed_rates_kernel, at the very end: the seed pass of the retimed alignment, every phase of up to 8 rates on gathered rows of B
+// (vdf_align_seed_pairs_rates*; align_seed_rates_plan.h).
 #include "align_plan.h"
 #include "align_retimed_plan.h"
+#include "align_seed_rates_plan.h"
 #include "vdf_internal.h"
 #include "window_class_layout.h"
 
@@ -911,6 +914,149 @@ hipError_t launch_align_seed_variants_scatter(const AlignSeedVariantsLaunch &L, 
         if (L.variant_mask >> v & 1u) slots |= v << (4 * slot++);
     hipLaunchKernelGGL(align_seed_variants_scatter_kernel, dim3(n_blocks), dim3(256), 0, stream, L.bitmap, L.n_words, L.n_a, L.n_b, slots, block_offset, out,
                        limit);
+    return hipGetLastError();
+}
+
+// ---- seeding the retimed alignment: every phase of up to 8 rates from one pass (include/vdf.h: vdf_align_seed_pairs_rates*; DESIGN.md 4.22;
+// align_seed_rates_plan.h) ------------------------------------------------------------------------------------------------------------------
+// align_seed_rates_kernel: align_seed_kernel's body on the plan of align_seed_rates_plan.h.  One workgroup per unit (chunk of seeds, tile of its
+// class's rows).  The tile's rows are GATHERED: lane row r of the plan is window row_window[r] of b_hashes (the rows den j of B's videos), its
+// skip byte is read at that same window, and a sentinel - the padding of a class's last tile - becomes a zero row with the skip byte set, as
+// the lanes behind n_rows are in the plain kernel; a wave whose first row is a sentinel holds padding only (the sentinels are a suffix of
+// the tile) and leaves.  The seeds stream through SGPRs as there; a seed's slot (its rate's index in the job's list) arrives with it by a scalar
+// load and goes into the bit index (slot n_a + seed_video) n_b + row_video.  exclude_same is tested on the rare path.  The early exit, the
+// seed's skip byte through its aligned dword and the read-before-atomic are the plain kernel's.  No LDS, vector stores only (the atomics).
+template <int R, int CHKW>
+__global__ __launch_bounds__(256) void align_seed_rates_kernel(
+    const uint32_t *__restrict__ a_hashes, const uint8_t *__restrict__ a_skip, const uint32_t *__restrict__ seed_window,
+    const uint32_t *__restrict__ seed_video, const uint32_t *__restrict__ seed_slot, const uint32_t *__restrict__ chunk_first,
+    const uint32_t *__restrict__ b_hashes, const uint8_t *__restrict__ b_skip, const uint32_t *__restrict__ row_window,
+    const uint32_t *__restrict__ row_video, const unsigned long long *__restrict__ unit_offset, const uint32_t *__restrict__ tile_first,
+    uint32_t n_chunks, uint32_t tol, int exclude_same, uint32_t n_a, uint32_t n_b, uint32_t *__restrict__ bitmap, unsigned long long unit_base)
+{
+    constexpr uint32_t TILE_ROWS = 256 * R;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned long long unit = unit_base + blockIdx.x;  // grids above 2^32 work-items are launched in cuts
+    const uint32_t chunk = align_seed_unit_chunk((align_u64_ptr)(uintptr_t)unit_offset, n_chunks, unit);
+    const uint32_t tile = ((align_u32_ptr)(uintptr_t)tile_first)[chunk] + (uint32_t)(unit - ((align_u64_ptr)(uintptr_t)unit_offset)[chunk]);
+    const uint64_t wave_row0 = (uint64_t)tile * TILE_ROWS + wave * (64 * R);  // inside the plan's rows: every class is padded to whole tiles
+    if (((align_u32_ptr)(uintptr_t)row_window)[wave_row0] == kSeedRowSentinel) return;  // wave-uniform: a wave of padding rows only (no barrier below)
+    const uint32_t s0 = ((align_u32_ptr)(uintptr_t)chunk_first)[chunk], s1 = ((align_u32_ptr)(uintptr_t)chunk_first)[chunk + 1];
+
+    // rows -> VGPRs
+    uint32_t rw[R][32];
+    uint32_t rvid[R], rskip[R];
+#pragma unroll
+    for (int k = 0; k < R; k++) {
+        const uint64_t r = wave_row0 + k * 64 + lane;
+        const uint32_t w = row_window[r];
+        if (w != kSeedRowSentinel) {
+            align_load_row(rw[k], b_hashes, w);
+            rvid[k] = row_video[r];
+            rskip[k] = b_skip ? b_skip[w] : 0u;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 32; q++) rw[k][q] = 0u;
+            rvid[k] = 0u;
+            rskip[k] = 1u;
+        }
+    }
+
+    align_u32_ptr a_rows = (align_u32_ptr)(uintptr_t)a_hashes;
+    for (uint32_t s = s0; s < s1; ++s) {
+        const uint32_t sw = ((align_u32_ptr)(uintptr_t)seed_window)[s];
+        align_u32_ptr ap = a_rows + (size_t)sw * 32;
+        uint32_t d[R];
+#pragma unroll
+        for (int k = 0; k < R; k++) d[k] = 0u;
+#pragma unroll
+        for (int w = 0; w < (CHKW < 32 ? CHKW : 32); ++w) {
+            const uint32_t aw = ap[w];  // SGPR
+#pragma unroll
+            for (int k = 0; k < R; k++) d[k] += __builtin_popcount(rw[k][w] ^ aw);
+        }
+        uint32_t m = d[0];
+#pragma unroll
+        for (int k = 1; k < R; k++) m = min(m, d[k]);
+        if (CHKW < 32) {
+            if (__builtin_amdgcn_ballot_w64(m <= tol) == 0ull) continue;  // partial distances only grow
+#pragma unroll
+            for (int w = CHKW; w < 32; ++w) {
+                const uint32_t aw = ap[w];
+#pragma unroll
+                for (int k = 0; k < R; k++) d[k] += __builtin_popcount(rw[k][w] ^ aw);
+            }
+            m = d[0];
+#pragma unroll
+            for (int k = 1; k < R; k++) m = min(m, d[k]);
+        }
+        if (__builtin_amdgcn_ballot_w64(m <= tol) != 0ull) {
+            // rare path: the seed's skip byte (with the aligned dword that holds it, by a scalar load), its video and slot, exclude_same, the bitmap
+            bool a_ok = true;
+            if (a_skip) {
+                const uintptr_t at = (uintptr_t)a_skip + sw;
+                a_ok = ((*(align_u32_ptr)(at & ~(uintptr_t)3) >> (8 * (uint32_t)(at & 3))) & 0xFFu) == 0u;
+            }
+            if (a_ok) {
+                const uint32_t sv = ((align_u32_ptr)(uintptr_t)seed_video)[s];
+                const uint32_t slot = ((align_u32_ptr)(uintptr_t)seed_slot)[s];
+#pragma unroll
+                for (int k = 0; k < R; k++) {
+                    if (d[k] <= tol && rskip[k] == 0u && (!exclude_same || sv != rvid[k])) {
+                        const uint64_t bit = align_seed_rates_bit(slot, sv, rvid[k], n_a, n_b);
+                        uint32_t *word = bitmap + (size_t)(bit >> 5);
+                        const uint32_t mask = 1u << (uint32_t)(bit & 31);
+                        if ((__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & mask) == 0u) atomicOr(word, mask);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// vdf_video_pair_rate has vdf_video_pair_variant's layout, so the triples are scattered by align_seed_variants_scatter_kernel with the identity
+// slot table (4 bits per slot: slot s names rate s)
+static_assert(sizeof(vdf_video_pair_rate) == sizeof(vdf_video_pair_variant) && offsetof(vdf_video_pair_rate, a) == offsetof(vdf_video_pair_variant, a) &&
+                  offsetof(vdf_video_pair_rate, b) == offsetof(vdf_video_pair_variant, b) &&
+                  offsetof(vdf_video_pair_rate, rate) == offsetof(vdf_video_pair_variant, variant) && kSeedRatesMax <= 8,
+              "vdf_video_pair_rate is scattered as vdf_video_pair_variant");
+
+// count, scan and scatter are launched as they are: 8 slots x 2^24 bits are 2^22 words, 2^14 workgroups of 256 threads, 16 block counts per
+// thread of the scan, and a total below 2^27 - all inside 32 bits
+hipError_t launch_align_seed_rates(const AlignSeedRatesLaunch &L, hipStream_t stream)
+{
+    if (L.n_units == 0 || L.n_slots == 0 || L.n_slots > kSeedRatesMax || L.n_words == 0 || L.n_words > kSeedRatesMax * (1u << 19)) return hipErrorInvalidValue;
+    for (const AlignLaunchCut &cut : align_launch_cuts((size_t)L.n_units)) {
+#define VDF_SEED_RATES_LAUNCH(CW)                                                                                                                       \
+    hipLaunchKernelGGL((align_seed_rates_kernel<(int)kSeedRowsPerLane, CW>), dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_skip,          \
+                       L.seed_window, L.seed_video, L.seed_slot, L.chunk_first, L.b_hashes, L.b_skip, L.row_window, L.row_video, L.unit_offset,        \
+                       L.tile_first, L.n_chunks, L.tol, L.exclude_same, L.n_a, L.n_b, L.bitmap, (unsigned long long)cut.group_base)
+        switch (align_seed_check_words(L.tol)) {
+        case 14: VDF_SEED_RATES_LAUNCH(14); break;
+        case 22: VDF_SEED_RATES_LAUNCH(22); break;
+        case 26: VDF_SEED_RATES_LAUNCH(26); break;
+        default: VDF_SEED_RATES_LAUNCH(32); break;
+        }
+#undef VDF_SEED_RATES_LAUNCH
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    const uint32_t n_blocks = (L.n_words + 255) / 256;
+    uint32_t *block_count = static_cast<uint32_t *>(L.scratch), *block_offset = block_count + n_blocks, *total = block_offset + n_blocks;
+    hipLaunchKernelGGL(align_seed_count_kernel, dim3(n_blocks), dim3(256), 0, stream, L.bitmap, L.n_words, block_count);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(align_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, n_blocks, block_offset, total);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    *L.total_out = total;
+    return hipSuccess;
+}
+
+hipError_t launch_align_seed_rates_scatter(const AlignSeedRatesLaunch &L, vdf_video_pair_rate *out, uint32_t limit, hipStream_t stream)
+{
+    const uint32_t n_blocks = (L.n_words + 255) / 256;
+    const uint32_t *block_offset = static_cast<const uint32_t *>(L.scratch) + n_blocks;
+    hipLaunchKernelGGL(align_seed_variants_scatter_kernel, dim3(n_blocks), dim3(256), 0, stream, L.bitmap, L.n_words, L.n_a, L.n_b, 0x76543210u, block_offset,
+                       reinterpret_cast<vdf_video_pair_variant *>(out), limit);
     return hipGetLastError();
 }
 

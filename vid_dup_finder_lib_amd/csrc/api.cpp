@@ -11,6 +11,7 @@
 #include <memory>
 #include <numeric>
 
+#include "align_seed_rates_plan.h"
 #include "host_sort.h"
 #include "vdf_ctx.h"
 #include "window_class_layout.h"
@@ -273,9 +274,10 @@ int search_core(vdf_ctx *ctx, int mode, const uint64_t *d_col_hashes, const uint
         L.cand_capacity = (uint32_t)std::min<uint64_t>(want, 0x40000000ull);
         if (ctx->cand_capacity_override)  // VDF_CAND_CAPACITY (tests: forces the overflow path)
             L.cand_capacity = (uint32_t)std::min<uint64_t>((uint64_t)ctx->cand_capacity_override * ctx->cand_scale, 0x40000000ull);
-        const void *before = ctx->cand.p;
+        // (a buffer that grows is freed and allocated again, and the allocator may hand the old address back: the capacity tells, the pointer does not)
+        const size_t cap_before = ctx->cand.cap;
         VDF_HIP(ctx, ctx->cand.reserve((size_t)L.cand_capacity * 16));
-        if (ctx->cand.p != before) ctx->cand_dirty = SIZE_MAX;  // fresh allocation: fill all of it
+        if (ctx->cand.cap != cap_before) ctx->cand_dirty = SIZE_MAX;  // fresh allocation: fill all of it
         // Only the slots earlier launches may have touched need the empty pattern (0xFF) again - ALL of them, whatever this
         // launch's capacity is: a launch with a smaller queue (after an overflow retry's x4, or a smaller search) must not
         // leave the slots beyond its own capacity stale for a later, larger launch to read as suspects.
@@ -2738,6 +2740,201 @@ int vdf_align_windows_retimed_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_has
 {
     return align_retimed_device_impl(ctx, "vdf_align_windows_retimed_pairs_device", d_a_hashes, d_a_first, n_a, d_a_skip, d_b_hashes, d_b_first, n_b, d_b_skip,
                                      pairs, n_pairs, true, tol_int, min_run, rate_num, rate_den, out, capacity, n_out, stream);
+}
+
+// ---- the retimed alignment, seeded: every phase of up to 8 rates from one pass (include/vdf.h: vdf_align_seed_pairs_rates*; DESIGN.md 4.22;
+// align_seed_rates_plan.h) --------------------------------------------------------------------------------------------------------------------
+// The checks of the three forms, in the header's order: align_checks' kinds, each on B first and then on the blocks of A; then the rate list,
+// exclude_same, the context.  First arrays on the host, or null (the device form before they have come down).  rates: the list in lowest terms.
+static int seed_rates_checks(vdf_ctx *ctx, const char *name, const vdf_align_seed_rates_job *j, const uint32_t *a_first, const uint32_t *b_first,
+                             vdf::AlignSeedRate *rates)
+{
+    const size_t n_a = j->n_a, n_b = j->n_b;
+    const uint32_t n_blocks = std::min<uint32_t>(j->n_rates, VDF_WINDOWS_MAX_RATES);
+    if (!j->n_out || (j->capacity && !j->out) || (n_b && (!j->b_hashes || !j->b_first)) || (n_a && (!j->a_hashes || !j->a_first)))
+        return fail(ctx, VDF_E_INVAL, "null pointer");
+    if (j->min_run == 0) return fail(ctx, VDF_E_INVAL, "min_run of zero");
+    const auto block = [&](uint32_t r) { return a_first + (size_t)r * (n_a + 1); };
+    for (size_t v = 0; b_first && v < n_b; v++)
+        if (b_first[v + 1] >= b_first[v] && b_first[v + 1] - b_first[v] > vdf::kAlignMaxWindows)
+            return fail(ctx, VDF_E_INVAL, "video " + std::to_string(v) + " of B has more than 2^20 windows");
+    for (uint32_t r = 0; a_first && r < n_blocks; r++)
+        for (size_t v = 0; v < n_a; v++)
+            if (block(r)[v + 1] >= block(r)[v] && block(r)[v + 1] - block(r)[v] > vdf::kAlignMaxWindows)
+                return fail(ctx, VDF_E_INVAL, "video " + std::to_string(v) + " of A has more than 2^20 windows at rate " + std::to_string(r));
+    for (size_t v = 0; b_first && v < n_b; v++)
+        if (b_first[v + 1] < b_first[v]) return fail(ctx, VDF_E_INVAL, "the first array of B decreases at video " + std::to_string(v));
+    for (uint32_t r = 0; a_first && r < n_blocks; r++)
+        for (size_t v = 0; v < n_a; v++)
+            if (block(r)[v + 1] < block(r)[v])
+                return fail(ctx, VDF_E_INVAL, "the first array of A decreases at video " + std::to_string(v) + " of rate " + std::to_string(r));
+    for (uint32_t r = 0; a_first && n_a && r < n_blocks; r++) {
+        const uint64_t base = j->a_rate_first ? (uint64_t)j->a_rate_first[r] : 0ull;
+        if (base > 0xFFFFFFFFull || base + block(r)[n_a] > 0xFFFFFFFFull) return fail(ctx, VDF_E_INVAL, "2^32 rows of A or more");
+    }
+    if (n_a > 0xFFFFFFFFull || n_b > 0xFFFFFFFFull || (uint64_t)n_a * n_b > vdf::kAlignMaxPairs)
+        return fail(ctx, VDF_E_INVAL, "more than 2^24 pairs of videos in one call");
+    if (j->n_rates < 1 || j->n_rates > VDF_WINDOWS_MAX_RATES || !j->rate_num || !j->rate_den)
+        return fail(ctx, VDF_E_INVAL, "n_rates outside 1 ... 8 or a null rate array");
+    int worst = 0;
+    for (uint32_t r = 0; r < j->n_rates; r++) {
+        const int rc = vdf::align_retimed_rate(j->rate_num[r], j->rate_den[r], &rates[r].num, &rates[r].den);
+        if (rc == 1) return fail(ctx, VDF_E_INVAL, "rate " + std::to_string(r) + " must have 1 <= den <= num <= 2 den");
+        if (rc == 2 && !worst) worst = (int)r + 1;
+    }
+    if (worst) return fail(ctx, VDF_E_INVAL, "the num of rate " + std::to_string(worst - 1) + " is above 32 in lowest terms (VDF_ALIGN_RETIMED_MAX_NUM)");
+    if (j->exclude_same && n_a != n_b) return fail(ctx, VDF_E_INVAL, "exclude_same takes n_a == n_b");
+    if (ctx && !ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, std::string(name) + " takes a single-device context");
+    return VDF_OK;
+}
+
+int vdf_align_seed_pairs_rates_host(const vdf_align_seed_rates_job *j)
+{
+    if (!j) return VDF_E_INVAL;
+    vdf::AlignSeedRate rates[VDF_WINDOWS_MAX_RATES];
+    if (int rc = seed_rates_checks(nullptr, "vdf_align_seed_pairs_rates_host", j, j->a_first, j->b_first, rates)) return rc;
+    *j->n_out = 0;
+    if (j->n_a == 0 || j->n_b == 0) return VDF_OK;
+    const uint32_t tol = std::min<uint32_t>(j->tol_int, 1024u);
+    size_t found = 0;
+    // the literal definition: every seed of a under r against every row of b under r, XOR + popcount
+    for (uint32_t r = 0; r < j->n_rates; r++) {
+        const uint32_t *fa = j->a_first + (size_t)r * (j->n_a + 1);
+        const size_t base = j->a_rate_first ? j->a_rate_first[r] : 0;
+        for (size_t a = 0; a < j->n_a; a++)
+            for (size_t b = 0; b < j->n_b; b++) {
+                if (j->exclude_same && a == b) continue;
+                const uint32_t Na = fa[a + 1] - fa[a], Nb = j->b_first[b + 1] - j->b_first[b];
+                bool hit = false;
+                for (uint32_t ka = 0; ka < Na && !hit; ka++) {
+                    const size_t ra = base + fa[a] + ka;
+                    if (!vdf::align_seed_rates_is_seed(ka, rates[r].num, j->min_run) || (j->a_skip && j->a_skip[ra])) continue;
+                    for (uint64_t kb = 0; kb < Nb && !hit; kb += rates[r].den) {
+                        const size_t rb = (size_t)j->b_first[b] + kb;
+                        if (j->b_skip && j->b_skip[rb]) continue;
+                        uint32_t dist = 0;
+                        for (int w = 0; w < VDF_HASH_WORDS; w++) dist += (uint32_t)__builtin_popcountll(j->a_hashes[16 * ra + w] ^ j->b_hashes[16 * rb + w]);
+                        hit = dist <= tol;
+                    }
+                }
+                if (!hit) continue;
+                if (found < j->capacity) j->out[found] = vdf_video_pair_rate{(uint32_t)a, (uint32_t)b, r};
+                found++;
+            }
+    }
+    *j->n_out = found;
+    return VDF_OK;
+}
+
+// the checks have passed on the host copies of the first arrays; the hashes and skip bytes are device pointers whose row 0 is row a_shift /
+// b_shift of the caller's arrays.  The plan goes up in one piece, the bitmap is cleared on the call's stream, the seed kernel marks it,
+// count + scan give the total; the host reads it, then the first min(total, capacity) triples.
+static int align_seed_rates_locked(vdf_ctx *ctx, const vdf_align_seed_rates_job *j, const vdf::AlignSeedRate *rates, const uint64_t *d_a_hashes,
+                                   const uint8_t *d_a_skip, const uint32_t *h_first_a, uint64_t a_shift, const uint64_t *d_b_hashes, const uint8_t *d_b_skip,
+                                   const uint32_t *h_first_b, uint64_t b_shift, hipStream_t s)
+{
+    vdf::AlignSeedRatesPlan plan;
+    vdf::align_seed_rates_plan(h_first_a, j->a_rate_first, j->n_a, h_first_b, j->n_b, rates, j->n_rates, j->min_run, a_shift, b_shift, plan);
+    if (plan.n_units() == 0) return VDF_OK;  // no seed or no row of B
+    const uint64_t n_bits = (uint64_t)j->n_rates * j->n_a * j->n_b;  // <= 2^27: the checks
+    const uint32_t n_words = (uint32_t)((n_bits + 31) / 32);
+    const size_t n_seeds = plan.n_seeds(), n_rows = plan.row_window.size(), n_chunks = plan.n_chunks();
+    // one upload, in dwords: seed_window | seed_video | seed_slot | row_window | row_video | chunk_first | tile_first | (pad) | unit_offset
+    const size_t at_video = n_seeds, at_slot = 2 * n_seeds, at_row = 3 * n_seeds, at_rvid = at_row + n_rows, at_chunk = at_rvid + n_rows;
+    const size_t at_tile = at_chunk + n_chunks + 1, at_unit = (at_tile + n_chunks + 1) & ~(size_t)1, n_dwords = at_unit + 2 * (n_chunks + 1);
+    std::vector<uint32_t> blob(n_dwords, 0u);
+    std::copy(plan.seed_window.begin(), plan.seed_window.end(), blob.begin());
+    std::copy(plan.seed_video.begin(), plan.seed_video.end(), blob.begin() + at_video);
+    std::copy(plan.seed_slot.begin(), plan.seed_slot.end(), blob.begin() + at_slot);
+    std::copy(plan.row_window.begin(), plan.row_window.end(), blob.begin() + at_row);
+    std::copy(plan.row_video.begin(), plan.row_video.end(), blob.begin() + at_rvid);
+    std::copy(plan.chunk_first.begin(), plan.chunk_first.end(), blob.begin() + at_chunk);
+    std::copy(plan.tile_first.begin(), plan.tile_first.end(), blob.begin() + at_tile);
+    std::memcpy(blob.data() + at_unit, plan.unit_offset.data(), (n_chunks + 1) * 8);
+    VDF_HIP(ctx, ctx->seed_bitmap.reserve((size_t)n_words * 4));
+    VDF_HIP(ctx, ctx->seed_plan.reserve(n_dwords * 4));
+    VDF_HIP(ctx, ctx->align_scratch.reserve(vdf::align_seed_scratch_bytes(n_words)));
+    const uint32_t *dp = ctx->seed_plan.as<uint32_t>();
+    VDF_HIP(ctx, hipMemsetAsync(ctx->seed_bitmap.p, 0, (size_t)n_words * 4, s));
+    VDF_HIP(ctx, hipMemcpyAsync(ctx->seed_plan.p, blob.data(), n_dwords * 4, hipMemcpyHostToDevice, s));
+    uint32_t *d_total = nullptr;
+    vdf::AlignSeedRatesLaunch L{};
+    L.a_hashes = reinterpret_cast<const uint32_t *>(d_a_hashes); L.a_skip = d_a_skip;
+    L.seed_window = dp; L.seed_video = dp + at_video; L.seed_slot = dp + at_slot; L.chunk_first = dp + at_chunk;
+    L.b_hashes = reinterpret_cast<const uint32_t *>(d_b_hashes); L.b_skip = d_b_skip;
+    L.row_window = dp + at_row; L.row_video = dp + at_rvid;
+    L.unit_offset = reinterpret_cast<const unsigned long long *>(dp + at_unit); L.tile_first = dp + at_tile;
+    L.n_chunks = (uint32_t)n_chunks; L.n_units = plan.n_units();
+    L.tol = std::min<uint32_t>(j->tol_int, 1024u); L.exclude_same = j->exclude_same ? 1 : 0;
+    L.n_slots = j->n_rates; L.n_a = (uint32_t)j->n_a; L.n_b = (uint32_t)j->n_b;
+    L.bitmap = ctx->seed_bitmap.as<uint32_t>(); L.n_words = n_words;
+    L.scratch = ctx->align_scratch.p; L.total_out = &d_total;
+    VDF_HIP(ctx, vdf::launch_align_seed_rates(L, s));
+    uint32_t total = 0;
+    VDF_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));  // also: the plan is free to go
+    if ((uint64_t)total > n_bits) return fail(ctx, VDF_E_HIP, "align seed rates: more triples than bits");
+    const size_t take = std::min<size_t>(total, j->capacity);
+    if (take) {
+        VDF_HIP(ctx, ctx->seed_out.reserve(take * sizeof(vdf_video_pair_rate)));
+        VDF_HIP(ctx, vdf::launch_align_seed_rates_scatter(L, ctx->seed_out.as<vdf_video_pair_rate>(), (uint32_t)take, s));
+        VDF_HIP(ctx, hipMemcpyAsync(j->out, ctx->seed_out.p, take * sizeof(vdf_video_pair_rate), hipMemcpyDeviceToHost, s));
+        VDF_HIP(ctx, hipStreamSynchronize(s));
+    }
+    *j->n_out = total;
+    return VDF_OK;
+}
+
+int vdf_align_seed_pairs_rates_device(vdf_ctx *ctx, const vdf_align_seed_rates_job *j)
+{
+    if (!ctx || !j) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    vdf::AlignSeedRate rates[VDF_WINDOWS_MAX_RATES];
+    // everything that can be said without the first arrays - the multi-GPU refusal last; then they come down and are checked
+    if (int rc = seed_rates_checks(ctx, "vdf_align_seed_pairs_rates_device", j, nullptr, nullptr, rates)) return rc;
+    *j->n_out = 0;
+    if (j->n_a == 0 || j->n_b == 0) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = j->stream ? (hipStream_t)j->stream : ctx->stream;
+    std::vector<uint32_t> fa((size_t)j->n_rates * (j->n_a + 1)), fb(j->n_b + 1);
+    VDF_HIP(ctx, hipMemcpyAsync(fa.data(), j->a_first, fa.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipMemcpyAsync(fb.data(), j->b_first, fb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));
+    if (int rc = seed_rates_checks(ctx, "vdf_align_seed_pairs_rates_device", j, fa.data(), fb.data(), rates)) return rc;
+    return align_seed_rates_locked(ctx, j, rates, j->a_hashes, j->a_skip, fa.data(), 0, j->b_hashes, j->b_skip, fb.data(), 0, s);
+}
+
+// Host arrays: the rows of A that the blocks span and the rows of B go up once through the context's staging buffers, the skip bytes beside
+// them; the device form's core runs on them.
+int vdf_align_seed_pairs_rates(vdf_ctx *ctx, const vdf_align_seed_rates_job *j)
+{
+    if (!ctx || !j) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    vdf::AlignSeedRate rates[VDF_WINDOWS_MAX_RATES];
+    if (int rc = seed_rates_checks(ctx, "vdf_align_seed_pairs_rates", j, j->a_first, j->b_first, rates)) return rc;
+    *j->n_out = 0;
+    if (j->n_a == 0 || j->n_b == 0) return VDF_OK;
+    uint64_t a_lo = ~0ull, a_hi = 0;
+    for (uint32_t r = 0; r < j->n_rates; r++) {
+        const uint32_t *fa = j->a_first + (size_t)r * (j->n_a + 1);
+        const uint64_t base = j->a_rate_first ? (uint64_t)j->a_rate_first[r] : 0ull;
+        a_lo = std::min(a_lo, base + fa[0]);
+        a_hi = std::max(a_hi, base + fa[j->n_a]);
+    }
+    const uint64_t b_lo = j->b_first[0], b_hi = j->b_first[j->n_b];
+    const size_t wa = (size_t)(a_hi - a_lo), wb = (size_t)(b_hi - b_lo);
+    if (wa == 0 || wb == 0) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t ska = j->a_skip ? (wa + 3) & ~(size_t)3 : 0, skb = j->b_skip ? wb : 0;
+    VDF_HIP(ctx, ctx->align_up.reserve(ska + skb + 16));
+    char *up = ctx->align_up.as<char>();
+    if (ska) VDF_HIP(ctx, hipMemcpyAsync(up, j->a_skip + a_lo, wa, hipMemcpyHostToDevice, s));
+    if (skb) VDF_HIP(ctx, hipMemcpyAsync(up + ska, j->b_skip + b_lo, wb, hipMemcpyHostToDevice, s));
+    if (int rc = upload(ctx, ctx->up_hashes, j->a_hashes + 16 * (size_t)a_lo, wa * 16 * sizeof(uint64_t), s)) return rc;
+    if (int rc = upload(ctx, ctx->up_ref_hashes, j->b_hashes + 16 * (size_t)b_lo, wb * 16 * sizeof(uint64_t), s)) return rc;
+    return align_seed_rates_locked(ctx, j, rates, ctx->up_hashes.as<uint64_t>(), ska ? reinterpret_cast<const uint8_t *>(up) : nullptr, j->a_first, a_lo,
+                                   ctx->up_ref_hashes.as<uint64_t>(), skb ? reinterpret_cast<const uint8_t *>(up + ska) : nullptr, j->b_first, b_lo, s);
 }
 
 size_t vdf_hash_window_count(uint32_t frames_per_clip, uint32_t window_stride) { return vdf::window_count(frames_per_clip, window_stride); }

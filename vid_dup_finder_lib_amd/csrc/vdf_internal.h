@@ -362,5 +362,31 @@ hipError_t launch_align_class_layout(const uint32_t *hashes, const uint32_t *zer
                                      const uint32_t *seed_video, uint32_t row_base, uint32_t n, uint32_t *out, hipStream_t stream);
 hipError_t launch_align_seed_variants(const AlignSeedVariantsLaunch &L, hipStream_t stream);
 hipError_t launch_align_seed_variants_scatter(const AlignSeedVariantsLaunch &L, vdf_video_pair_variant *out, uint32_t limit, hipStream_t stream);
+// The seed pass of the retimed alignment (align_seed_rates_plan.h: AlignSeedRatesPlan): every unit's seeds - of every phase of
+// every listed rate - against its tile of gathered rows of B into `bitmap` (n_slots x n_a x n_b bits, cleared by the caller on the stream), then
+// the count and scan of its set bits; the scatter writes the first `limit` triples in (rate, a, b) order.  All pointers are device pointers;
+// scratch holds align_seed_scratch_bytes(n_words).
+struct AlignSeedRatesLaunch {
+    const uint32_t *a_hashes;
+    const uint8_t *a_skip;               // nullable, per window
+    const uint32_t *seed_window, *seed_video, *seed_slot;
+    const uint32_t *chunk_first;         // [n_chunks + 1]
+    const uint32_t *b_hashes;
+    const uint8_t *b_skip;
+    const uint32_t *row_window, *row_video;  // [tiles x kSeedTileRows]
+    const unsigned long long *unit_offset;  // [n_chunks + 1]
+    const uint32_t *tile_first;          // [n_chunks]
+    uint32_t n_chunks;
+    uint64_t n_units;
+    uint32_t tol;
+    int exclude_same;
+    uint32_t n_slots, n_a, n_b;
+    uint32_t *bitmap;
+    uint32_t n_words;
+    void *scratch;
+    uint32_t **total_out;
+};
+hipError_t launch_align_seed_rates(const AlignSeedRatesLaunch &L, hipStream_t stream);
+hipError_t launch_align_seed_rates_scatter(const AlignSeedRatesLaunch &L, vdf_video_pair_rate *out, uint32_t limit, hipStream_t stream);
 
 }  // namespace vdf

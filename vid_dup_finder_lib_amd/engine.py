@@ -425,6 +425,81 @@ def align_windows_retimed_pairs_host(a_hashes, a_first, pairs, b_hashes, b_first
     return out[:min(n.value, out.size)], int(n.value)
 
 
+# one (a, b, rate) triple of the seeded retimed call (include/vdf.h: vdf_video_pair_rate, 12 bytes); rate = the index into the call's list of rates
+VIDEO_PAIR_RATE_DTYPE = _capi.VIDEO_PAIR_RATE_DTYPE
+
+
+def _seed_rates_job(a_hashes, a_first, n_a, a_rate_first, a_skip, b_hashes, b_first, n_b, b_skip, rates, tol_int, min_run, exclude_same, capacity, stream=0):
+    """(job, out, n, what the job points into): the job of vdf_align_seed_pairs_rates[_host|_device].  The array arguments are addresses (0 =
+    NULL) - of host or of device memory, as the form takes them; rates and a_rate_first are host lists."""
+    num, den = _align_rates(rates)
+    rf = None if a_rate_first is None else np.ascontiguousarray(a_rate_first, dtype=np.uintp).reshape(-1)
+    if rf is not None and rf.size < min(len(num), _capi.WINDOWS_MAX_RATES):
+        raise ValueError("a_rate_first has an entry per rate")
+    out = np.zeros(max(int(capacity), 0), VIDEO_PAIR_RATE_DTYPE)
+    n = C.c_size_t(0)
+    job = _capi.VdfAlignSeedRatesJob(a_hashes or None, a_first or None, rf.ctypes.data if rf is not None else None, a_skip or None, int(n_a), b_hashes or None,
+                                     b_first or None, b_skip or None, int(n_b), len(num), num.ctypes.data if len(num) else None,
+                                     den.ctypes.data if len(num) else None, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                     1 if exclude_same else 0, out.ctypes.data if out.size else None, out.size, C.pointer(n), stream or None)
+    return job, out, n, (num, den, rf)
+
+
+def _align_rates(rates):
+    """A list of rates of an align call as two uint32 arrays; the library says how many there may be and which it takes."""
+    pairs = [_align_rate(r) for r in rates]
+    return np.array([p[0] for p in pairs], np.uint32), np.array([p[1] for p in pairs], np.uint32)
+
+
+def _seed_rates_host_args(a_hashes, a_first, a_rate_first, a_skip, b_hashes, b_first, b_skip, n_rates):
+    """The host arrays of a seeded retimed call: A rate-major - hashes [rows, 16], first [n_rates, n_a + 1], rate_first [n_rates (+ 1)] or None
+    (zeros), skip [rows] or None - and B as the align calls take it.  Returns the arrays (to keep alive) and their addresses and counts."""
+    ah = np.ascontiguousarray(a_hashes, dtype=np.uint64).reshape(-1, HASH_WORDS)
+    af = np.ascontiguousarray(a_first, dtype=np.uint32)
+    if af.ndim != 2 or af.shape[1] == 0 or af.shape[0] < min(int(n_rates), _capi.WINDOWS_MAX_RATES):
+        raise ValueError("a_first has one row of n_a + 1 entries per rate")
+    rf = np.zeros(af.shape[0], np.int64) if a_rate_first is None else np.asarray(a_rate_first, dtype=np.int64).reshape(-1)[:af.shape[0]]
+    if rf.size < af.shape[0] or (af.size and int((rf[:, None] + af).max()) > ah.shape[0]):
+        raise ValueError("a first array points behind its hashes")
+    ak = None
+    if a_skip is not None:
+        ak = np.ascontiguousarray(a_skip, dtype=np.uint8).reshape(-1)
+        if ak.size != ah.shape[0]:
+            raise ValueError("one skip byte per window")
+    if b_hashes is None or b_first is None:
+        raise ValueError("the seeded retimed call has no self mode: give b_hashes and b_first")
+    bh = np.ascontiguousarray(b_hashes, dtype=np.uint64).reshape(-1, HASH_WORDS)
+    bf = np.ascontiguousarray(b_first, dtype=np.uint32).reshape(-1)
+    if bf.size == 0:
+        raise ValueError("a first array has n_videos + 1 entries")
+    if int(bf.max()) > bh.shape[0]:
+        raise ValueError("a first array points behind its hashes")
+    bk = None
+    if b_skip is not None:
+        bk = np.ascontiguousarray(b_skip, dtype=np.uint8).reshape(-1)
+        if bk.size != bh.shape[0]:
+            raise ValueError("one skip byte per window")
+    # an empty side must not read as a null pointer: numpy gives an empty array a non-null address
+    args = dict(a_hashes=ah.ctypes.data or af.ctypes.data, a_first=af.ctypes.data, n_a=af.shape[1] - 1, a_skip=ak.ctypes.data if ak is not None else 0,
+                b_hashes=bh.ctypes.data or bf.ctypes.data, b_first=bf.ctypes.data, n_b=bf.size - 1, b_skip=bk.ctypes.data if bk is not None else 0)
+    return (ah, af, ak, bh, bf, bk), args
+
+
+def align_seed_pairs_rates_host(a_hashes, a_first, b_hashes, b_first, rates, tol_int: int = 350, min_run: int = 1, a_rate_first=None, a_skip=None,
+                                b_skip=None, exclude_same: bool = False, capacity: int = 1024):
+    """vdf_align_seed_pairs_rates_host: which pairs (a, b) can have a record of align_windows_retimed at which rate of `rates` - the definition in
+    plain C++ on the CPU.  A is RATE-MAJOR, as Engine.hash_windows_clips_rates writes it: a_hashes [rows, 16], a_first [n_rates, n_a + 1],
+    a_rate_first [n_rates (+ 1)] (None: zeros); window k of video i at rate r is row a_rate_first[r] + a_first[r, i] + k.  B: plain windows.
+    -> (triples [min(found, capacity)] of VIDEO_PAIR_RATE_DTYPE in (rate, a, b) order - rate is the index into `rates` - and found)."""
+    keep, args = _seed_rates_host_args(a_hashes, a_first, a_rate_first, a_skip, b_hashes, b_first, b_skip, len(rates))
+    job, out, n, keep2 = _seed_rates_job(rates=rates, a_rate_first=a_rate_first, tol_int=tol_int, min_run=min_run, exclude_same=exclude_same, capacity=capacity,
+                                         **args)
+    rc = _capi.load().vdf_align_seed_pairs_rates_host(C.byref(job))
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_align_seed_pairs_rates_host: bad argument")
+    return out[:min(n.value, out.size)], int(n.value)
+
+
 # one (variant, a, b) triple (include/vdf.h: vdf_video_pair_variant, 12 bytes): what the seeded variants call returns and the variants-pairs calls take
 VIDEO_PAIR_VARIANT_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("variant", "<u4")])
 
@@ -1134,6 +1209,27 @@ class Engine:
                                                          d_b_first or None, int(n_b), d_b_skip or None, _align_uint32("tol_int", tol_int),
                                                          _align_uint32("min_run", min_run), out.ctypes.data if out.size else None, out.size, C.byref(n),
                                                          stream or None))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_seed_pairs_rates(self, a_hashes, a_first, b_hashes, b_first, rates, tol_int: int = 350, min_run: int = 1, a_rate_first=None, a_skip=None,
+                               b_skip=None, exclude_same: bool = False, capacity: int = 1024):
+        """The candidates of the retimed alignment at every rate of `rates`, every phase, from ONE pass (vdf_align_seed_pairs_rates; DESIGN.md
+        4.22): arguments and result as align_seed_pairs_rates_host - A rate-major, as hash_windows_clips_rates writes it.  found > capacity: call
+        again with a larger capacity."""
+        keep, args = _seed_rates_host_args(a_hashes, a_first, a_rate_first, a_skip, b_hashes, b_first, b_skip, len(rates))
+        job, out, n, keep2 = _seed_rates_job(rates=rates, a_rate_first=a_rate_first, tol_int=tol_int, min_run=min_run, exclude_same=exclude_same,
+                                             capacity=capacity, **args)
+        self._check(self.lib.vdf_align_seed_pairs_rates(self.ctx, C.byref(job)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_seed_pairs_rates_device(self, d_a_hashes: int, d_a_first: int, n_a: int, d_b_hashes: int, d_b_first: int, n_b: int, rates, tol_int: int = 350,
+                                      min_run: int = 1, a_rate_first=None, d_a_skip: int = 0, d_b_skip: int = 0, exclude_same: bool = False,
+                                      capacity: int = 1024, stream: int = 0):
+        """The same on device arrays - d_a_first: n_rates x (n_a + 1) u32; rates and a_rate_first stay HOST lists; the triples come back to the host,
+        the call is ordered on `stream` and waits for its own work."""
+        job, out, n, keep = _seed_rates_job(d_a_hashes, d_a_first, n_a, a_rate_first, d_a_skip, d_b_hashes, d_b_first, n_b, d_b_skip, rates, tol_int, min_run,
+                                            exclude_same, capacity, stream)
+        self._check(self.lib.vdf_align_seed_pairs_rates_device(self.ctx, C.byref(job)))
         return out[:min(n.value, out.size)], int(n.value)
 
     def align_windows_pairs(self, a_hashes, a_first, pairs, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1, a_skip=None, b_skip=None,

@@ -808,6 +808,114 @@ public:
         }
     }
 
+    // ---- the retimed alignment seeded at every rate of a list, every phase, in one pass ----
+    // Which pairs (a, b) can have a record of align_windows_retimed at which rate (vdf_align_seed_pairs_rates): windows_by_rate_a[r] =
+    // hash_windows_retimed' lists of A at rates[r] (every rate over the same videos; what hash_windows_clips_rates returns), windows_b = plain windows
+    // at stride 1; at most VDF_WINDOWS_MAX_RATES rates, duplicate and unreduced ones included.  The triples (a, b, rate index) in (rate, a, b) order:
+    // the pairs with a window ka of a at that rate, (ka / num) % min_run == 0, and a window kb of b, kb % den == 0, within tol_int of each other,
+    // neither skipped.  skip_a: one byte per window of A, rate-major (nullable); exclude_same: pairs (i, i) are never candidates.
+    struct SeedRatesSides {
+        std::vector<uint64_t> wa, wb;
+        std::vector<uint32_t> fa, fb, num, den;  // fa: n_rates x (n_a + 1), every row counted from its block's first window
+        std::vector<size_t> rate_first;
+        size_t n_a = 0, n_b = 0;
+        SeedRatesSides(const std::vector<std::vector<std::vector<VideoHash>>> &windows_by_rate_a, const std::vector<std::vector<VideoHash>> &windows_b,
+                       const std::vector<std::pair<uint32_t, uint32_t>> &rates)
+        {
+            if (windows_by_rate_a.size() != rates.size()) throw std::invalid_argument("one set of windows of A per rate");
+            n_a = rates.empty() ? 0 : windows_by_rate_a[0].size();
+            n_b = windows_b.size();
+            rate_first.assign(1, 0);
+            for (size_t r = 0; r < rates.size(); r++) {
+                if (windows_by_rate_a[r].size() != n_a) throw std::invalid_argument("every rate holds the windows of the same videos");
+                num.push_back(rates[r].first);
+                den.push_back(rates[r].second);
+                uint32_t at = 0;
+                fa.push_back(0u);
+                for (const auto &video : windows_by_rate_a[r]) {
+                    for (const VideoHash &h : video) wa.insert(wa.end(), h.words().begin(), h.words().end());
+                    fa.push_back(at += (uint32_t)video.size());
+                }
+                rate_first.push_back(wa.size() / VDF_HASH_WORDS);
+            }
+            fb.assign(1, 0u);
+            for (const auto &video : windows_b) {
+                for (const VideoHash &h : video) wb.insert(wb.end(), h.words().begin(), h.words().end());
+                fb.push_back((uint32_t)(wb.size() / VDF_HASH_WORDS));
+            }
+            if (wa.empty()) wa.push_back(0);  // a non-null pointer for an empty side
+            if (wb.empty()) wb.push_back(0);
+            if (fa.empty()) fa.push_back(0u);
+        }
+        vdf_align_seed_rates_job job(const std::vector<uint8_t> *skip_a, const std::vector<uint8_t> *skip_b, uint32_t tol_int, uint32_t min_run, bool exclude_same,
+                                     std::vector<vdf_video_pair_rate> &out, size_t *found) const
+        {
+            if (skip_a && skip_a->size() != rate_first.back()) throw std::invalid_argument("one skip byte per window of A, rate-major");
+            if (skip_b && skip_b->size() != fb.back()) throw std::invalid_argument("one skip byte per window of B");
+            return vdf_align_seed_rates_job{wa.data(), fa.data(), rate_first.data(), skip_a && !skip_a->empty() ? skip_a->data() : nullptr, n_a, wb.data(), fb.data(),
+                                            skip_b && !skip_b->empty() ? skip_b->data() : nullptr, n_b, (uint32_t)num.size(), num.empty() ? nullptr : num.data(),
+                                            den.empty() ? nullptr : den.data(), tol_int, min_run, exclude_same ? 1u : 0u, out.data(), out.size(), found, nullptr};
+        }
+    };
+
+    // the definition in plain C++ on the CPU (vdf_align_seed_pairs_rates_host): no context, no GPU
+    static std::vector<vdf_video_pair_rate> align_seed_pairs_rates_host(const std::vector<std::vector<std::vector<VideoHash>>> &windows_by_rate_a,
+                                                                        const std::vector<std::vector<VideoHash>> &windows_b,
+                                                                        const std::vector<std::pair<uint32_t, uint32_t>> &rates, uint32_t tol_int,
+                                                                        uint32_t min_run = 1, const std::vector<uint8_t> *skip_a = nullptr,
+                                                                        const std::vector<uint8_t> *skip_b = nullptr, bool exclude_same = false)
+    {
+        const SeedRatesSides s(windows_by_rate_a, windows_b, rates);
+        std::vector<vdf_video_pair_rate> out(1024);
+        for (;;) {
+            size_t found = 0;
+            const vdf_align_seed_rates_job job = s.job(skip_a, skip_b, tol_int, min_run, exclude_same, out, &found);
+            if (vdf_align_seed_pairs_rates_host(&job) != VDF_OK)
+                throw std::invalid_argument("align_seed_pairs_rates: min_run of 0, a video of more than 2^20 windows, more than 2^24 pairs, no or more than 8 rates, "
+                                            "a rate outside 1 <= den <= num <= 2 den or with num above 32 in lowest terms, or exclude_same between sets of two sizes");
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
+    // one pass of the seed kernel over every phase of every rate (vdf_align_seed_pairs_rates): the host arrays go up once
+    static std::vector<vdf_video_pair_rate> align_seed_pairs_rates(const std::vector<std::vector<std::vector<VideoHash>>> &windows_by_rate_a,
+                                                                   const std::vector<std::vector<VideoHash>> &windows_b,
+                                                                   const std::vector<std::pair<uint32_t, uint32_t>> &rates, uint32_t tol_int, uint32_t min_run = 1,
+                                                                   const std::vector<uint8_t> *skip_a = nullptr, const std::vector<uint8_t> *skip_b = nullptr,
+                                                                   bool exclude_same = false, Context *ctx_opt = nullptr)
+    {
+        const SeedRatesSides s(windows_by_rate_a, windows_b, rates);
+        Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+        std::vector<vdf_video_pair_rate> out(1024);
+        for (;;) {
+            size_t found = 0;
+            const vdf_align_seed_rates_job job = s.job(skip_a, skip_b, tol_int, min_run, exclude_same, out, &found);
+            const int rc = vdf_align_seed_pairs_rates(ctx.get(), &job);
+            if (rc == VDF_E_INVAL) throw std::invalid_argument(vdf_last_error(ctx.get()));
+            if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);
+        }
+    }
+
+    // The same on device memory (vdf_align_seed_pairs_rates_device): the job's array pointers are device pointers - what
+    // hash_windows_clips_rates_device wrote goes in unchanged - rate_num, rate_den and a_rate_first stay on the host; out, capacity and n_out of the
+    // job are set here.  The triples come back to the host and the call waits for its own work on job.stream.
+    static std::vector<vdf_video_pair_rate> align_seed_pairs_rates_device(Context &ctx, vdf_align_seed_rates_job job)
+    {
+        std::vector<vdf_video_pair_rate> out(1024);
+        for (;;) {
+            size_t found = 0;
+            job.out = out.data(); job.capacity = out.size(); job.n_out = &found;
+            const int rc = vdf_align_seed_pairs_rates_device(ctx.get(), &job);
+            if (rc == VDF_E_INVAL) throw std::invalid_argument(vdf_last_error(ctx.get()));
+            if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
     // hash_windows with the zero plane of every window (vdf_hash_windows_u8_planes): the same words, and every VideoHash
     // carries zero() - what align_windows_variants needs of the flipped side.
     static std::vector<std::vector<VideoHash>> hash_windows_planes(const uint8_t *frames, size_t n_videos, uint32_t frames_per_video, uint32_t w, uint32_t h,
