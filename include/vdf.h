@@ -584,7 +584,7 @@ int vdf_align_windows_retimed_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_has
  * _device: DEVICE arrays (hashes, first arrays, skip bytes); the rate arrays, a_rate_first and out stay on the host; the call waits for its own
  * work.  The context forms make ONE pass: rates that share a den share their gathered rows of B, and the seeds of every phase of every rate
  * stream past them in one launch.  Skip bytes of A are read as the other seed calls read them (the aligned 32-bit word).
- * Not offered: a list-form align over (rate, a, b) triples in one call; zero planes; multi-GPU contexts. */
+ * Not offered: zero planes; multi-GPU contexts.  The align call over the triples is vdf_align_windows_rates*, below. */
 typedef struct vdf_video_pair_rate { /* 12 bytes */
     uint32_t a;                /* video index in A */
     uint32_t b;                /* video index in B */
@@ -614,6 +614,70 @@ typedef struct vdf_align_seed_rates_job {
 int vdf_align_seed_pairs_rates_host(const vdf_align_seed_rates_job *job);
 int vdf_align_seed_pairs_rates(vdf_ctx *ctx, const vdf_align_seed_rates_job *job);
 int vdf_align_seed_pairs_rates_device(vdf_ctx *ctx, const vdf_align_seed_rates_job *job);
+
+/* ---- align retimed windows at up to VDF_WINDOWS_MAX_RATES rates in ONE call: (rate, a, b) triples ----------------------------
+ * The third step of the retimed pipeline - hash (vdf_hash_windows_clips_u8_rates*), seed (vdf_align_seed_pairs_rates*), align - with the rate list
+ * in one call, as the first two take it.  A and B are what the seed call takes, unchanged: A rate-major with a_first (n_rates x (n_a + 1)) and the
+ * HOST array a_rate_first (nullable = zeros), window k of video i at rate r in row a_rate_first[r] + a_first[r][i] + k; B plain windows.
+ * The record of a triple (r, a, b) is, field for field, the record vdf_align_windows_retimed_pairs* gives for the pair (a, b) on block r at
+ * rate_num[r] / rate_den[r] - the sub-matrices, the two-level reduction and its tie rules are that call's - with rate = r and
+ * n_frames_b = (n_windows - 1) den + 16 (den in lowest terms) added; where that call gives no record, this one gives none.  Records come in
+ * (rate, a, b) order under the capacity protocol of the align calls (*n_out is always the number found, the first `capacity` are valid).
+ * Duplicate and unreduced rates are legal, each listed rate gets its slot; tol = min(tol_int, 1024).  Which triples are walked:
+ *   triples != NULL            exactly the listed ones: a HOST array in all forms, strictly increasing in (rate, a, b), rate < n_rates, a < n_a,
+ *                              b < n_b; seed and exclude_same must be 0.  What vdf_align_seed_pairs_rates* wrote goes in unchanged;
+ *   triples == NULL, seed == 0 every (r, a, b); with exclude_same != 0 (requires n_a == n_b) without those with a == b;
+ *   triples == NULL, seed != 0 the candidate set of vdf_align_seed_pairs_rates* on the same arguments, found inside the call.  That set holds
+ *                              every pair that has a record, so the output equals the seed == 0 output, record for record.
+ * Limits: n_a x n_b <= 2^24, n_triples <= 2^27, 2^20 windows per video, fewer than 2^32 rows of A.
+ * Errors, all VDF_E_INVAL, in this order: a null job or ctx; the checks of vdf_align_seed_pairs_rates in its order, up to and including the rate
+ * list, each kind on B first and then on the blocks of A; exclude_same with n_a != n_b; a list together with seed or exclude_same; the list
+ * (more than 2^27 entries, then the first bad entry: not strictly increasing, a rate outside the list, a video that does not exist); a
+ * multi-GPU context.  n_a == 0, n_b == 0 or an empty list: VDF_OK with *n_out = 0.
+ * _host: plain C++, no context, no GPU - vdf_align_windows_retimed_pairs_host's definition triple by triple, behind
+ * vdf_align_seed_pairs_rates_host where seed != 0.  vdf_align_windows_rates: host arrays, uploaded ONCE for both the seed pass and the walk.
+ * _device: DEVICE hashes, first arrays and skip bytes; the rate arrays, a_rate_first, triples and out stay on the host; the first arrays are read
+ * back as the seed call reads them; the call is ordered on `stream` (NULL = the context's) and waits for its own work.  In the context forms a
+ * chunk of units may span rates: the triples of all rates are one launch set.
+ * Not offered: the candidates handed to the band kernels on the device (the triples visit the host for planning); several stretches or
+ * flips per triple; a C best_rates; multi-GPU contexts. */
+typedef struct vdf_alignment_rate { /* 32 bytes */
+    uint32_t a;                /* video index in A */
+    uint32_t b;                /* video index in B */
+    uint32_t rate;             /* index into the job's rate list */
+    uint32_t first_a;          /* p + num i0, counted inside video a of block `rate` */
+    uint32_t first_b;          /* den (i0 + offset) */
+    uint32_t n_windows;        /* sub-sampled windows in the run */
+    uint32_t dist_sum;         /* sum of the run's distances */
+    uint32_t n_frames_b;       /* (n_windows - 1) den + 16: the frames of b the run covers, comparable across rates */
+} vdf_alignment_rate;
+typedef struct vdf_align_rates_job {
+    const uint64_t *a_hashes;
+    const uint32_t *a_first;
+    const size_t *a_rate_first;
+    const uint8_t *a_skip;
+    size_t n_a;
+    const uint64_t *b_hashes;
+    const uint32_t *b_first;
+    const uint8_t *b_skip;
+    size_t n_b;
+    uint32_t n_rates;
+    const uint32_t *rate_num;
+    const uint32_t *rate_den;
+    uint32_t tol_int;
+    uint32_t min_run;
+    const vdf_video_pair_rate *triples;
+    size_t n_triples;
+    uint32_t seed;
+    uint32_t exclude_same;
+    vdf_alignment_rate *out;
+    size_t capacity;
+    size_t *n_out;
+    void *stream;
+} vdf_align_rates_job;
+int vdf_align_windows_rates_host(const vdf_align_rates_job *job);
+int vdf_align_windows_rates(vdf_ctx *ctx, const vdf_align_rates_job *job);
+int vdf_align_windows_rates_device(vdf_ctx *ctx, const vdf_align_rates_job *job);
 
 /* ---- mirrored, flipped and reversed STRETCHES: window hashes with their zero planes -----------------------
  * A mirrored re-upload with its intro trimmed: the variant search sees only frames 0 ... 15 of a file, the align calls only unflipped

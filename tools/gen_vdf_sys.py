@@ -33,6 +33,8 @@ GROUPS = [
      r"vdf_align_windows_stretches"),
     ("a copy at another frame rate or speed: retimed windows of A against plain windows of B, every phase of the rate in one call",
      r"vdf_align_windows_retimed"),
+    ("the retimed alignment at up to 8 rates in one call: (rate, a, b) triples - all, a list, or the seed call's candidates found inside the call",
+     r"vdf_align_windows_rates"),
     ("mirrored / flipped / reversed STRETCHES: the variant of a set of window hashes from their zero planes, and alignment against it",
      r"vdf_window_variants|vdf_window_class_layout|vdf_align_windows_variants"),
     ("mirrored / flipped / reversed duplicates, which the crate cannot see (lib.rs:102-111): the flipped clip's hash from the hash and the zero plane of the planes calls",

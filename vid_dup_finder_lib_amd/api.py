@@ -23,7 +23,7 @@ from .engine import (ALIGN_DTYPE, ALIGN_STRETCH_DTYPE, ALIGN_VARIANT_DTYPE, Engi
                      tolerance_int, video_pairs, align_seed_pairs_host, align_windows_pairs_host, align_windows_stretches_pairs_host,
                      ALIGN_RETIMED_DTYPE, VIDEO_PAIR_DTYPE, align_windows_retimed_host, align_windows_retimed_pairs_host,
                      pair_list_problem, VIDEO_PAIR_VARIANT_DTYPE, align_seed_pairs_variants_host, align_windows_variants_pairs_host,
-                     VIDEO_PAIR_RATE_DTYPE, align_seed_pairs_rates_host)
+                     VIDEO_PAIR_RATE_DTYPE, align_seed_pairs_rates_host, ALIGN_RATE_DTYPE, align_windows_rates_host)
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
            "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "hash_frame_windows", "align_rates", "best_rates", "candidate_pairs_rates", "locate", "rust_path_key", "sort_order",
@@ -1161,16 +1161,88 @@ def _align_rates_one_pass(windows_by_rate_a, windows_b, tolerance, min_run, stat
     return out
 
 
+def _rates_call(engine, A, B, rates, tol_int, min_run, triples, seed):
+    """_retimed_call for the call over (rate, a, b) triples: one call of the C ABI (vdf_align_windows_rates[_host]), ALIGN_RATE_DTYPE in
+    (rate, a, b) order.  A: a _rates_block; triples None: all of them, or with seed the candidates found inside the call."""
+    def once(capacity):
+        kw = dict(tol_int=tol_int, min_run=min_run, a_rate_first=A[2], a_skip=A[3], b_skip=B[2], triples=triples, seed=seed, capacity=capacity)
+        call = align_windows_rates_host if engine is None else engine.align_windows_rates
+        return call(A[0], A[1], B[0], B[1], rates, **kw)
+    rec, found = once(ALIGN_FIRST_CAPACITY)
+    if found > len(rec):
+        rec, found = once(found)
+    return rec
+
+
+def _align_rates_one_call(windows_by_rate_a, windows_b, tolerance, min_run, static_a, static_b, engine, pairs, seed):
+    """align_rates(one_call=True): the CSR of B once and of each rate's A once; per block of videos ONE vdf_align_windows_rates call for all rates -
+    on every triple, on the candidates it finds itself (seed), on the listed pairs at every rate (pairs), or on the candidates that are on the
+    list (both: one seed call, intersected as one_pass does, then the list form)."""
+    tol_int = tolerance_int(tolerance)
+    rates, per = _rates_csr(windows_by_rate_a, static_a)
+    reduced = [_retimed_rate(r) for r in rates]
+    wb, fb, kb, cb = csr_b = _align_csr(windows_b, static_b)
+    n_a = len(per[0][3])
+    pair_list = _align_pair_list(pairs, n_a, len(cb), False)
+    engine = _rates_engine(engine, rates, per, cb)
+    key = lambda p: (p["a"].astype(np.uint64) << np.uint64(32)) | p["b"].astype(np.uint64)
+    step = max(1, math.isqrt(ALIGN_MAX_PAIRS))
+    parts = []
+    for a0 in range(0, n_a, step):
+        a1 = min(a0 + step, n_a)
+        A = _rates_block(per, a0, a1)
+        for b0 in range(0, len(cb), step):
+            b1 = min(b0 + step, len(cb))
+            w0, w1 = int(fb[b0]), int(fb[b1])
+            B = (wb[w0:w1], fb[b0:b1 + 1] - fb[b0], None if kb is None else kb[w0:w1])
+            plist = _block_pairs(engine, None, None, a0, a1, b0, b1, tol_int, int(min_run), pair_list, False)
+            triples = None
+            if plist is not None:
+                if seed and len(plist):
+                    t = _seed_rates_call(engine, A, B, rates, tol_int, int(min_run), False)
+                    cand = np.zeros(len(t), VIDEO_PAIR_DTYPE)
+                    cand["a"], cand["b"] = t["a"], t["b"]
+                    triples = t[np.isin(key(cand), key(plist))]
+                else:
+                    triples = np.zeros(len(rates) * len(plist), VIDEO_PAIR_RATE_DTYPE)
+                    triples["a"], triples["b"] = np.tile(plist["a"], len(rates)), np.tile(plist["b"], len(rates))
+                    triples["rate"] = np.repeat(np.arange(len(rates), dtype=np.uint32), len(plist))
+                if not len(triples):
+                    continue
+            rec = _rates_call(engine, A, B, rates, tol_int, int(min_run), triples, bool(seed) and triples is None).copy()
+            rec["a"] += a0
+            rec["b"] += b0
+            parts.append(rec)
+    rec = np.concatenate(parts) if parts else np.zeros(0, ALIGN_RATE_DTYPE)
+    rec = rec[np.lexsort((rec["b"], rec["a"], rec["rate"]))]
+    pb = [ws[0].src_path() if ws else None for ws in windows_b]
+    out = {}
+    for i, (rate, (num, den)) in enumerate(zip(rates, reduced)):
+        pa = [ws[0].src_path() if ws else None for ws in windows_by_rate_a[rate]]
+        span = (15 * num) // den + 1
+        out[rate] = []
+        for r in rec[rec["rate"] == i]:
+            a, b, fa, fb_, n, ds, nfb = (int(r[k]) for k in ("a", "b", "first_a", "first_b", "n_windows", "dist_sum", "n_frames_b"))
+            out[rate].append(RetimedAlignment(a, b, num, den, fa, fb_, (n - 1) * num + span, nfb, n, ds / n, pa[a], pb[b]))
+    return out
+
+
 def align_rates(windows_by_rate_a: dict, windows_b: List[List[VideoHash]], tolerance: float = DEFAULT_SEARCH_TOLERANCE, min_run: int = 1,
                 static_a: Optional[dict] = None, static_b=None, engine: Optional[Engine] = None, native: bool = True, seed: bool = False,
-                pairs=None, one_pass: bool = False) -> dict:
+                pairs=None, one_pass: bool = False, one_call: bool = False) -> dict:
     """Which videos of A are a retimed copy of which video of B, at which of several rates?  windows_by_rate_a: {(num, den): windows of A at that
     rate}, as hash_frame_windows(..., rates=[...]) returns it, stride 1; windows_b: the PLAIN windows of B at stride 1 (the (1, 1) entry of such a
     dict).  One align_retimed call per rate, in the dict's order, with everything else handed through (static_a: {rate: flags per video} or None)
     -> {rate: List[RetimedAlignment]}.  best_rates picks one record per pair from it.
     one_pass=True (needs seed=True and native=True; at most 8 rates): the same dict, but every phase of every rate is seeded by ONE call per block
     of videos (candidate_pairs_rates' call) instead of num calls per rate on sub-sampled copies, and each rate that has candidates then makes its
-    one align call on them."""
+    one align call on them.
+    one_call=True (needs native=True; at most 8 rates): the same dict from ONE vdf_align_windows_rates call per block of videos - the triples of all
+    rates are one launch set, and with seed=True the candidates are found inside the call, on arrays that went up once."""
+    if one_call:
+        if not native or one_pass:
+            raise ValueError("one_call=True needs native=True and excludes one_pass")
+        return _align_rates_one_call(windows_by_rate_a, windows_b, tolerance, min_run, static_a, static_b, engine, pairs, seed)
     if one_pass:
         if not (seed and native):
             raise ValueError("one_pass=True needs seed=True and native=True")

@@ -21,6 +21,8 @@
 // DESIGN.md 4.14; window_class_layout.h).
 // align_bands_retimed_kernel / align_reduce_retimed_kernel, behind launch_align_chunk: the band walk on the strided rows of a phase's sub-matrix
 // and the two-level reduction bands -> phase-best -> pair record (vdf_align_windows_retimed*; align_retimed_plan.h).
+// align_bands_rates_kernel / align_reduce_rates_kernel / align_scatter_rates_kernel, behind launch_align_retimed_chunk: the retimed walk on
+// (rate, a, b) triples of up to 8 rates in one launch, the rate looked up per wave (vdf_align_windows_rates*; align_rates_plan.h).
 // align_seed_rates_kernel, at the very end: the seed pass of the retimed alignment, every phase of up to 8 rates on gathered rows of B
 // (vdf_align_seed_pairs_rates*; align_seed_rates_plan.h).
 #include "align_plan.h"
@@ -533,6 +535,199 @@ hipError_t launch_align_retimed_chunk(const AlignLaunch &L, uint32_t num, uint32
                        block_offset, reinterpret_cast<vdf_alignment *>(dense));
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     *dense_out = dense;
+    *L.total_out = total;
+    return hipSuccess;
+}
+
+// ---- retimed windows at up to 8 rates: the triples of every rate in one launch (include/vdf.h: vdf_align_windows_rates*) ---------
+// align_bands_rates_kernel: align_bands_retimed_kernel's walk as a kernel of its own, so that the retimed kernel's text and code stay what they
+// were.  A unit is (triple, phase, band), and the triple names its rate: everything that differs lies in front of the loop.  The unit's triple
+// is found on unit_offset, (a, b, rate) come by scalar loads from the chunk's triple array (vdf_video_pair_rate's layout), and num, den, the
+// block's first row and its row of a_first come by one scalar load from the slot's 16 bytes of the table (align_rates_plan.h: AlignRatesSlot).
+// The table sits in the chunk's one upload, in front of the triples, not in the kernel arguments: indexed by a run-time slot, a by-value array
+// can end up in scratch, and an s_load from memory cannot.  The slot is uniform per WAVE, not per workgroup - the four waves of a workgroup
+// serve four units that may belong to four rates - so it and everything derived from it (num, den, phase, Na, Nb, d0, the row of A) stay in
+// SGPRs: `unit` is built from readfirstlane(wave) and blockIdx, and every load on it is a scalar load.  The loop body, the run state, the
+// reload, the skip-byte reads and the wave reduction are the retimed kernel's.  No LDS, no scratch, vector stores only.
+__global__ __launch_bounds__(256) void align_bands_rates_kernel(
+    const uint32_t *__restrict__ a_hashes, const uint32_t *__restrict__ a_first, const uint8_t *__restrict__ a_skip,
+    const uint32_t *__restrict__ b_hashes, const uint32_t *__restrict__ b_first, const uint8_t *__restrict__ b_skip,
+    const AlignRatesSlot *__restrict__ table, const AlignRatesTriple *__restrict__ triples, const uint32_t *__restrict__ unit_offset, uint32_t n_triples,
+    uint32_t n_units, uint32_t tol, uint32_t min_run, AlignBandRecord *__restrict__ band_records, uint32_t group_base)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t unit = (blockIdx.x + group_base) * kAlignWaves + wave;  // grids above 2^32 work-items are launched in cuts
+    if (unit >= n_units) return;
+
+    const uint32_t t = align_unit_pair((align_u32_ptr)(uintptr_t)unit_offset, n_triples, unit);
+    align_u32_ptr tp = (align_u32_ptr)(uintptr_t)triples + (size_t)t * 3;
+    const uint32_t va = tp[0], vb = tp[1];
+    const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)tp[2]);  // < kAlignRatesMax: the host's planner wrote it
+    align_u32_ptr sp = (align_u32_ptr)(uintptr_t)table + (size_t)slot * 4;
+    const uint32_t num = sp[0], den = sp[1], row0 = sp[2];
+    align_u32_ptr af = (align_u32_ptr)(uintptr_t)a_first + sp[3];       // the slot's row of a_first
+    const uint32_t fa = row0 + af[va], Na_all = af[va + 1] - af[va];     // 32-bit sum: a row of the hashes the kernel sees (AlignRatesSlot)
+    const uint32_t fb = ((align_u32_ptr)(uintptr_t)b_first)[vb], Nb_all = ((align_u32_ptr)(uintptr_t)b_first)[vb + 1] - fb;
+    uint32_t phase, band;
+    align_retimed_unit(align_retimed_split(Na_all, Nb_all, num, den), unit - ((align_u32_ptr)(uintptr_t)unit_offset)[t], &phase, &band);
+    const uint32_t Na = align_retimed_na(Na_all, num, phase), Nb = align_retimed_nb(Nb_all, den);  // the sub-matrix
+    const int32_t d0 = align_band_d0(Na, band);
+    const uint32_t ka0 = align_ka_begin(d0), ka1 = align_ka_end(Na, Nb, d0);
+
+    const uint32_t *b_rows = b_hashes + (size_t)fb * 32;
+    const uint8_t *b_sk = b_skip ? b_skip + fb : nullptr;
+    align_u32_ptr a_rows = (align_u32_ptr)(uintptr_t)a_hashes + (size_t)fa * 32;
+
+    // this lane's row of B; cells outside the sub-matrix are misses and no address is formed for them
+    uint32_t rw[32];
+    int32_t kb = align_lane_row(lane, ka0, d0);
+    bool row_ok = kb >= 0 && kb < (int32_t)Nb;
+    uint32_t row_skip = 0;  // the row's skip byte: compared where the row is used, so that the load is not waited for where it is issued
+    if (row_ok) {
+        const uint32_t rb = align_retimed_row_b(den, (uint32_t)kb);  // < Nb_all
+        if (b_sk) row_skip = b_sk[rb];
+        align_load_row(rw, b_rows, rb);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 32; q++) rw[q] = 0u;
+    }
+
+    uint32_t len = 0, sum = 0;                                              // the run of the diagonal this lane is on
+    uint32_t best_score = 0, best_start = 0, best_n = 0, best_sum = 0;     // score 0 = none: every run scores at least 1
+    int32_t best_off = 0;
+    for (uint32_t ka = ka0; ka < ka1; ++ka) {
+        const uint32_t ra = align_retimed_row_a(phase, num, ka);  // < Na_all, wave-uniform
+        align_u32_ptr ap = a_rows + (size_t)ra * 32;
+        uint32_t d = 0;
+#pragma unroll
+        for (int w = 0; w < 32; ++w) d += __builtin_popcount(rw[w] ^ ap[w]);  // ap[w]: SGPR
+        bool a_ok = true;  // wave-uniform: the skip byte of A's row comes with the aligned dword that holds it, by a scalar load like the row
+        if (a_skip) {
+            const uintptr_t at = (uintptr_t)a_skip + fa + ra;
+            a_ok = ((*(align_u32_ptr)(at & ~(uintptr_t)3) >> (8 * (uint32_t)(at & 3))) & 0xFFu) == 0u;
+        }
+        const bool match = row_ok && row_skip == 0 && a_ok && d <= tol;
+        if (match) { len += 1; sum += d; }
+        const bool edge = ka + 1 == Na || kb + 1 == (int32_t)Nb;              // the diagonal's last cell
+        const bool ends = len != 0 && (!match || edge);
+        if (__builtin_amdgcn_ballot_w64(ends) != 0ull) {
+            if (ends && len >= min_run) {
+                const uint32_t score = len * (tol + 1) - sum;
+                const uint32_t start = (match ? ka + 1 : ka) - len;
+                const int32_t off = kb - (int32_t)ka;
+                if (align_better(score, off, start, best_score, best_off, best_start)) {
+                    best_score = score; best_off = off; best_start = start; best_n = len; best_sum = sum;
+                }
+            }
+            if (ends) { len = 0; sum = 0; }
+        }
+        // the state follows its diagonal one lane up
+        len = align_rotate_up(len, lane);
+        sum = align_rotate_up(sum, lane);
+        // the lane whose diagonal d0 is done takes the row of diagonal d0 + 63 of the next step
+        if (ka + 1 < ka1 && lane == align_reload_lane(ka, d0)) {
+            kb += (int32_t)kAlignBand;  // = align_reload_row(ka, d0) >= 1, from the lane's own register: the address stays a vector address
+            row_ok = kb < (int32_t)Nb;
+            row_skip = 0;
+            if (row_ok) {
+                const uint32_t rb = align_retimed_row_b(den, (uint32_t)kb);
+                if (b_sk) row_skip = b_sk[rb];
+                align_load_row(rw, b_rows, rb);
+            }
+        }
+    }
+
+    // the wave's best of its 64 lane-bests; every run has its own (score, offset, start)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t o_score = (uint32_t)__shfl_xor((int)best_score, o, 64), o_start = (uint32_t)__shfl_xor((int)best_start, o, 64);
+        const uint32_t o_n = (uint32_t)__shfl_xor((int)best_n, o, 64), o_sum = (uint32_t)__shfl_xor((int)best_sum, o, 64);
+        const int32_t o_off = __shfl_xor(best_off, o, 64);
+        if (align_better(o_score, o_off, o_start, best_score, best_off, best_start)) {
+            best_score = o_score; best_off = o_off; best_start = o_start; best_n = o_n; best_sum = o_sum;
+        }
+    }
+    if (lane == 0) band_records[unit] = AlignBandRecord{best_off, best_start, best_score ? best_n : 0u, best_sum};
+}
+
+static_assert(sizeof(vdf_alignment_rate) == 32 && sizeof(AlignRatesTriple) == sizeof(vdf_video_pair_rate) &&
+                  offsetof(AlignRatesTriple, a) == offsetof(vdf_video_pair_rate, a) && offsetof(AlignRatesTriple, b) == offsetof(vdf_video_pair_rate, b) &&
+                  offsetof(AlignRatesTriple, rate) == offsetof(vdf_video_pair_rate, rate) && sizeof(AlignRatesSlot) == 16 && kAlignRatesMax == VDF_WINDOWS_MAX_RATES,
+              "the chunk's triples are vdf_video_pair_rate, its records vdf_alignment_rate");
+
+// one thread per triple of the chunk: its bands -> align_retimed_reduce with the triple's own split and den (the text the plain C++ definition and
+// align_reduce_retimed_kernel run) -> triple_records with n_frames_b (n_windows = 0: none); block_count[g] = triples with a record
+__global__ __launch_bounds__(256) void align_reduce_rates_kernel(const AlignRatesSlot *__restrict__ table, const AlignRatesTriple *__restrict__ triples,
+                                                                 const uint32_t *__restrict__ unit_offset, uint32_t n_triples,
+                                                                 const uint32_t *__restrict__ a_first, const uint32_t *__restrict__ b_first, uint32_t tol,
+                                                                 const AlignBandRecord *__restrict__ band_records,
+                                                                 vdf_alignment_rate *__restrict__ triple_records, uint32_t *__restrict__ block_count)
+{
+    __shared__ uint32_t s_wave[4];
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    bool has = false;
+    if (p < n_triples) {
+        const AlignRatesTriple t = triples[p];
+        const AlignRatesSlot sl = table[t.rate];
+        const uint32_t *af = a_first + sl.first_at;
+        const AlignRetimedSplit sp = align_retimed_split(af[t.a + 1] - af[t.a], b_first[t.b + 1] - b_first[t.b], sl.num, sl.den);
+        const AlignRetimedBest best = align_retimed_reduce(band_records + unit_offset[p], sp, sl.den, tol);
+        has = best.score != 0;
+        triple_records[p] = vdf_alignment_rate{t.a, t.b, t.rate, best.first_a, best.first_b, has ? best.n_windows : 0u, best.dist_sum,
+                                               has ? (best.n_windows - 1) * sl.den + 16u : 0u};
+    }
+    uint32_t total;
+    (void)align_block_rank(has, s_wave, &total);
+    if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+
+// align_scatter_kernel for the 32-byte records (that kernel is tied to vdf_alignment's 24 bytes and stays as it is)
+__global__ __launch_bounds__(256) void align_scatter_rates_kernel(const vdf_alignment_rate *__restrict__ triple_records, uint32_t n_triples,
+                                                                  const uint32_t *__restrict__ block_offset, vdf_alignment_rate *__restrict__ out)
+{
+    __shared__ uint32_t s_wave[4];
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    vdf_alignment_rate r{};
+    if (p < n_triples) r = triple_records[p];
+    const bool has = r.n_windows != 0;
+    uint32_t total;
+    const uint32_t rank = align_block_rank(has, s_wave, &total);
+    if (has) out[(size_t)block_offset[blockIdx.x] + rank] = r;
+}
+
+hipError_t launch_align_rates_chunk(const AlignRatesLaunch &L, hipStream_t stream)
+{
+    if (L.n_triples == 0 || L.n_units == 0 || !L.plan) return hipErrorInvalidValue;
+    const char *plan = static_cast<const char *>(L.plan);
+    const AlignRatesSlot *table = reinterpret_cast<const AlignRatesSlot *>(plan);
+    const AlignRatesTriple *triples = reinterpret_cast<const AlignRatesTriple *>(plan + align_rates_plan_triples_at());
+    const uint32_t *unit_offset = reinterpret_cast<const uint32_t *>(plan + align_rates_plan_offsets_at(L.n_triples));
+    // scratch: band records | triple records | dense records | block counts | block offsets | total (align_rates_scratch_bytes)
+    char *s = static_cast<char *>(L.scratch);
+    AlignBandRecord *band_records = reinterpret_cast<AlignBandRecord *>(s);
+    s += (size_t)L.n_units * sizeof(AlignBandRecord);
+    vdf_alignment_rate *triple_records = reinterpret_cast<vdf_alignment_rate *>(s);
+    s += (size_t)L.n_triples * sizeof(vdf_alignment_rate);
+    vdf_alignment_rate *dense = reinterpret_cast<vdf_alignment_rate *>(s);
+    s += (size_t)L.n_triples * sizeof(vdf_alignment_rate);
+    const uint32_t n_blocks = (L.n_triples + 255) / 256;
+    uint32_t *block_count = reinterpret_cast<uint32_t *>(s), *block_offset = block_count + n_blocks, *total = block_offset + n_blocks;
+
+    const size_t n_groups = ((size_t)L.n_units + kAlignWaves - 1) / kAlignWaves;
+    for (const AlignLaunchCut &cut : align_launch_cuts(n_groups)) {
+        hipLaunchKernelGGL(align_bands_rates_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_first, L.a_skip, L.b_hashes, L.b_first,
+                           L.b_skip, table, triples, unit_offset, L.n_triples, L.n_units, L.tol, L.min_run, band_records, (uint32_t)cut.group_base);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(align_reduce_rates_kernel, dim3(n_blocks), dim3(256), 0, stream, table, triples, unit_offset, L.n_triples, L.a_first, L.b_first, L.tol,
+                       band_records, triple_records, block_count);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(align_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, n_blocks, block_offset, total);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(align_scatter_rates_kernel, dim3(n_blocks), dim3(256), 0, stream, triple_records, L.n_triples, block_offset, dense);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    *L.dense_out = dense;
     *L.total_out = total;
     return hipSuccess;
 }

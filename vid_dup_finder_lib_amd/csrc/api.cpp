@@ -2747,7 +2747,7 @@ int vdf_align_windows_retimed_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_has
 // The checks of the three forms, in the header's order: align_checks' kinds, each on B first and then on the blocks of A; then the rate list,
 // exclude_same, the context.  First arrays on the host, or null (the device form before they have come down).  rates: the list in lowest terms.
 static int seed_rates_checks(vdf_ctx *ctx, const char *name, const vdf_align_seed_rates_job *j, const uint32_t *a_first, const uint32_t *b_first,
-                             vdf::AlignSeedRate *rates)
+                             vdf::AlignSeedRate *rates, bool ctx_check = true)  // false: vdf_align_windows_rates*, whose list checks come before the context's
 {
     const size_t n_a = j->n_a, n_b = j->n_b;
     const uint32_t n_blocks = std::min<uint32_t>(j->n_rates, VDF_WINDOWS_MAX_RATES);
@@ -2784,7 +2784,7 @@ static int seed_rates_checks(vdf_ctx *ctx, const char *name, const vdf_align_see
     }
     if (worst) return fail(ctx, VDF_E_INVAL, "the num of rate " + std::to_string(worst - 1) + " is above 32 in lowest terms (VDF_ALIGN_RETIMED_MAX_NUM)");
     if (j->exclude_same && n_a != n_b) return fail(ctx, VDF_E_INVAL, "exclude_same takes n_a == n_b");
-    if (ctx && !ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, std::string(name) + " takes a single-device context");
+    if (ctx_check && ctx && !ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, std::string(name) + " takes a single-device context");
     return VDF_OK;
 }
 
@@ -2828,11 +2828,13 @@ int vdf_align_seed_pairs_rates_host(const vdf_align_seed_rates_job *j)
 
 // the checks have passed on the host copies of the first arrays; the hashes and skip bytes are device pointers whose row 0 is row a_shift /
 // b_shift of the caller's arrays.  The plan goes up in one piece, the bitmap is cleared on the call's stream, the seed kernel marks it,
-// count + scan give the total; the host reads it, then the first min(total, capacity) triples.
+// count + scan give the total; the host reads it, then the first min(total, capacity) triples.  all (nullable): the internal entry of
+// vdf_align_windows_rates* - the job's out, capacity and n_out are not touched, and ALL triples come down into *all, which grows to the total.
 static int align_seed_rates_locked(vdf_ctx *ctx, const vdf_align_seed_rates_job *j, const vdf::AlignSeedRate *rates, const uint64_t *d_a_hashes,
                                    const uint8_t *d_a_skip, const uint32_t *h_first_a, uint64_t a_shift, const uint64_t *d_b_hashes, const uint8_t *d_b_skip,
-                                   const uint32_t *h_first_b, uint64_t b_shift, hipStream_t s)
+                                   const uint32_t *h_first_b, uint64_t b_shift, hipStream_t s, std::vector<vdf_video_pair_rate> *all = nullptr)
 {
+    if (all) all->clear();
     vdf::AlignSeedRatesPlan plan;
     vdf::align_seed_rates_plan(h_first_a, j->a_rate_first, j->n_a, h_first_b, j->n_b, rates, j->n_rates, j->min_run, a_shift, b_shift, plan);
     if (plan.n_units() == 0) return VDF_OK;  // no seed or no row of B
@@ -2874,14 +2876,15 @@ static int align_seed_rates_locked(vdf_ctx *ctx, const vdf_align_seed_rates_job 
     VDF_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, s));
     VDF_HIP(ctx, hipStreamSynchronize(s));  // also: the plan is free to go
     if ((uint64_t)total > n_bits) return fail(ctx, VDF_E_HIP, "align seed rates: more triples than bits");
-    const size_t take = std::min<size_t>(total, j->capacity);
+    const size_t take = all ? (size_t)total : std::min<size_t>(total, j->capacity);
+    if (all) all->resize(take);
     if (take) {
         VDF_HIP(ctx, ctx->seed_out.reserve(take * sizeof(vdf_video_pair_rate)));
         VDF_HIP(ctx, vdf::launch_align_seed_rates_scatter(L, ctx->seed_out.as<vdf_video_pair_rate>(), (uint32_t)take, s));
-        VDF_HIP(ctx, hipMemcpyAsync(j->out, ctx->seed_out.p, take * sizeof(vdf_video_pair_rate), hipMemcpyDeviceToHost, s));
+        VDF_HIP(ctx, hipMemcpyAsync(all ? all->data() : j->out, ctx->seed_out.p, take * sizeof(vdf_video_pair_rate), hipMemcpyDeviceToHost, s));
         VDF_HIP(ctx, hipStreamSynchronize(s));
     }
-    *j->n_out = total;
+    if (!all) *j->n_out = total;
     return VDF_OK;
 }
 
@@ -2935,6 +2938,198 @@ int vdf_align_seed_pairs_rates(vdf_ctx *ctx, const vdf_align_seed_rates_job *j)
     if (int rc = upload(ctx, ctx->up_ref_hashes, j->b_hashes + 16 * (size_t)b_lo, wb * 16 * sizeof(uint64_t), s)) return rc;
     return align_seed_rates_locked(ctx, j, rates, ctx->up_hashes.as<uint64_t>(), ska ? reinterpret_cast<const uint8_t *>(up) : nullptr, j->a_first, a_lo,
                                    ctx->up_ref_hashes.as<uint64_t>(), skb ? reinterpret_cast<const uint8_t *>(up + ska) : nullptr, j->b_first, b_lo, s);
+}
+
+// ---- retimed windows aligned at up to 8 rates in one call: (rate, a, b) triples (include/vdf.h: vdf_align_windows_rates*; DESIGN.md 4.23;
+// align_rates_plan.h) ---------------------------------------------------------------------------------------------------------------------------
+// the seed job on an align job's arguments: same arrays, same rates, same tol / min_run / exclude_same; out is only tested for null
+static vdf_align_seed_rates_job align_rates_seed_job(const vdf_align_rates_job *j)
+{
+    vdf_align_seed_rates_job q{};
+    q.a_hashes = j->a_hashes; q.a_first = j->a_first; q.a_rate_first = j->a_rate_first; q.a_skip = j->a_skip; q.n_a = j->n_a;
+    q.b_hashes = j->b_hashes; q.b_first = j->b_first; q.b_skip = j->b_skip; q.n_b = j->n_b;
+    q.n_rates = j->n_rates; q.rate_num = j->rate_num; q.rate_den = j->rate_den;
+    q.tol_int = j->tol_int; q.min_run = j->min_run; q.exclude_same = j->exclude_same;
+    q.out = reinterpret_cast<vdf_video_pair_rate *>(j->out); q.capacity = j->capacity; q.n_out = j->n_out; q.stream = j->stream;
+    return q;
+}
+
+// The checks of the three forms, in the header's order: the seed call's up to and including the rate list and exclude_same (first arrays on the
+// host, or null: the device form before they have come down), a list together with seed or exclude_same, the list, the context.
+static int align_rates_checks(vdf_ctx *ctx, const char *name, const vdf_align_rates_job *j, const uint32_t *a_first, const uint32_t *b_first,
+                              vdf::AlignSeedRate *rates)
+{
+    const vdf_align_seed_rates_job q = align_rates_seed_job(j);
+    if (int rc = seed_rates_checks(ctx, name, &q, a_first, b_first, rates, false)) return rc;
+    if (j->triples) {
+        if (j->seed || j->exclude_same) return fail(ctx, VDF_E_INVAL, "a triple list together with seed or exclude_same");
+        if (j->n_triples > vdf::kAlignRatesMaxTriples) return fail(ctx, VDF_E_INVAL, "more than 2^27 listed triples in one call");
+        size_t at = 0;
+        switch (vdf::align_rates_list_check(j->triples, j->n_triples, j->n_a, j->n_b, j->n_rates, &at)) {
+        case 1: return fail(ctx, VDF_E_INVAL, "the triple list is not strictly increasing in (rate, a, b) at entry " + std::to_string(at));
+        case 2: return fail(ctx, VDF_E_INVAL, "triple " + std::to_string(at) + " of the list names a video that does not exist");
+        case 4: return fail(ctx, VDF_E_INVAL, "triple " + std::to_string(at) + " of the list names a rate that is not in the rate list");
+        default: break;
+        }
+    }
+    if (ctx && !ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, std::string(name) + " takes a single-device context");
+    return VDF_OK;
+}
+
+int vdf_align_windows_rates_host(const vdf_align_rates_job *j)
+{
+    if (!j) return VDF_E_INVAL;
+    vdf::AlignSeedRate rates[VDF_WINDOWS_MAX_RATES];
+    if (int rc = align_rates_checks(nullptr, "vdf_align_windows_rates_host", j, j->a_first, j->b_first, rates)) return rc;
+    *j->n_out = 0;
+    if (j->n_a == 0 || j->n_b == 0 || (j->triples && j->n_triples == 0)) return VDF_OK;
+    const uint32_t tol = std::min<uint32_t>(j->tol_int, 1024u);
+    size_t found = 0;
+    // vdf_align_windows_retimed_pairs_host's definition for the pair (a, b) on block r
+    const auto triple = [&](uint32_t r, uint32_t a, uint32_t b) {
+        const uint32_t *fa = j->a_first + (size_t)r * (j->n_a + 1);
+        const size_t ra = (j->a_rate_first ? j->a_rate_first[r] : 0) + (size_t)fa[a], rb = j->b_first[b];
+        vdf_alignment_retimed rec;
+        align_retimed_pair_host(j->a_hashes + 16 * ra, fa[a + 1] - fa[a], j->a_skip ? j->a_skip + ra : nullptr, j->b_hashes + 16 * rb,
+                                j->b_first[b + 1] - j->b_first[b], j->b_skip ? j->b_skip + rb : nullptr, rates[r].num, rates[r].den, tol, j->min_run, &rec);
+        if (rec.n_windows == 0) return;
+        if (found < j->capacity)
+            j->out[found] = vdf_alignment_rate{a, b, r, rec.first_a, rec.first_b, rec.n_windows, rec.dist_sum, (rec.n_windows - 1) * rates[r].den + 16u};
+        found++;
+    };
+    if (j->triples) {
+        for (size_t i = 0; i < j->n_triples; i++) triple(j->triples[i].rate, j->triples[i].a, j->triples[i].b);
+    } else if (j->seed) {
+        std::vector<vdf_video_pair_rate> cand(1024);
+        size_t n_cand = 0;
+        vdf_align_seed_rates_job q = align_rates_seed_job(j);
+        for (int pass = 0; pass < 2; pass++) {  // its own capacity growth: the second pass has room for everything the first one counted
+            q.out = cand.data(); q.capacity = cand.size(); q.n_out = &n_cand;
+            if (int rc = vdf_align_seed_pairs_rates_host(&q)) return rc;
+            if (n_cand <= cand.size()) break;
+            cand.resize(n_cand);
+        }
+        for (size_t i = 0; i < n_cand; i++) triple(cand[i].rate, cand[i].a, cand[i].b);
+    } else {
+        for (uint32_t r = 0; r < j->n_rates; r++)
+            for (size_t a = 0; a < j->n_a; a++)
+                for (size_t b = 0; b < j->n_b; b++)
+                    if (!(j->exclude_same && a == b)) triple(r, (uint32_t)a, (uint32_t)b);
+    }
+    *j->n_out = found;
+    return VDF_OK;
+}
+
+// The checks have passed on the host copies of the first arrays; hashes, skip bytes and first arrays are device pointers.  Row 0 of d_a_hashes /
+// d_a_skip is row a_shift of the caller's arrays (a host-array call cuts off what no block uses); B's first arrays count from row 0 of d_b_hashes.
+// seed: the candidates come from the seed pass on these same resident arrays (its internal entry: no second upload, all triples come down).
+// Then the chunks: table | triples | unit_offset go up in one copy, the band walk, the reduction, the dense records down.
+static int align_rates_locked(vdf_ctx *ctx, const vdf_align_rates_job *j, const vdf::AlignSeedRate *rates, const uint64_t *d_a_hashes, const uint8_t *d_a_skip,
+                              const uint32_t *d_a_first, const uint32_t *h_first_a, uint64_t a_shift, const uint64_t *d_b_hashes, const uint8_t *d_b_skip,
+                              const uint32_t *d_b_first, const uint32_t *h_first_b, hipStream_t s)
+{
+    std::vector<vdf_video_pair_rate> cand;
+    const vdf_video_pair_rate *list = j->triples;
+    size_t n_list = j->n_triples;
+    if (!list && j->seed) {
+        const vdf_align_seed_rates_job q = align_rates_seed_job(j);
+        if (int rc = align_seed_rates_locked(ctx, &q, rates, d_a_hashes, d_a_skip, h_first_a, a_shift, d_b_hashes, d_b_skip, h_first_b, 0, s, &cand)) return rc;
+        if (cand.empty()) return VDF_OK;
+        list = cand.data();
+        n_list = cand.size();
+    }
+    const vdf::AlignRatesTable table = vdf::align_rates_table(rates, j->n_rates, j->a_rate_first, j->n_a, a_shift);
+    vdf::AlignRatesCursor cur;
+    vdf::AlignRatesChunk ch;
+    size_t found = 0, list_at = 0;
+    while (list ? vdf::align_rates_next_chunk_triples(h_first_a, j->n_a, h_first_b, list, n_list, rates, list_at, ch)
+                : vdf::align_rates_next_chunk(h_first_a, j->n_a, h_first_b, j->n_b, rates, j->n_rates, j->exclude_same != 0, cur, ch)) {
+        const size_t n_triples = ch.n_triples(), n_units = ch.n_units(), plan_bytes = vdf::align_rates_plan_bytes(n_triples);
+        VDF_HIP(ctx, ctx->align_plan.reserve(plan_bytes));
+        VDF_HIP(ctx, ctx->align_scratch.reserve(vdf::align_rates_scratch_bytes(n_triples, n_units)));
+        VDF_HIP(ctx, hipMemcpyAsync(ctx->align_plan.p, ch.seal(table), plan_bytes, hipMemcpyHostToDevice, s));  // the triples go up from where the planner wrote them
+        vdf_alignment_rate *d_dense = nullptr;
+        uint32_t *d_total = nullptr;
+        vdf::AlignRatesLaunch L{};
+        L.a_hashes = reinterpret_cast<const uint32_t *>(d_a_hashes); L.a_first = d_a_first; L.a_skip = d_a_skip;
+        L.b_hashes = reinterpret_cast<const uint32_t *>(d_b_hashes); L.b_first = d_b_first; L.b_skip = d_b_skip;
+        L.plan = ctx->align_plan.p;
+        L.n_triples = (uint32_t)n_triples; L.n_units = (uint32_t)n_units;
+        L.tol = std::min<uint32_t>(j->tol_int, 1024u); L.min_run = j->min_run;
+        L.scratch = ctx->align_scratch.p; L.dense_out = &d_dense; L.total_out = &d_total;
+        VDF_HIP(ctx, vdf::launch_align_rates_chunk(L, s));
+        uint32_t total = 0;
+        VDF_HIP(ctx, hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, s));
+        VDF_HIP(ctx, hipStreamSynchronize(s));  // also: the chunk's plan is free to change
+        if (total > n_triples) return fail(ctx, VDF_E_HIP, "align rates: more records than triples");
+        const size_t room = j->capacity > found ? j->capacity - found : 0, take = std::min<size_t>(total, room);
+        if (take) {
+            VDF_HIP(ctx, hipMemcpyAsync(j->out + found, d_dense, take * sizeof(vdf_alignment_rate), hipMemcpyDeviceToHost, s));
+            VDF_HIP(ctx, hipStreamSynchronize(s));
+        }
+        found += total;
+    }
+    *j->n_out = found;
+    return VDF_OK;
+}
+
+int vdf_align_windows_rates_device(vdf_ctx *ctx, const vdf_align_rates_job *j)
+{
+    if (!ctx || !j) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    vdf::AlignSeedRate rates[VDF_WINDOWS_MAX_RATES];
+    // everything that can be said without the first arrays - the multi-GPU refusal last; then they come down and are checked
+    if (int rc = align_rates_checks(ctx, "vdf_align_windows_rates_device", j, nullptr, nullptr, rates)) return rc;
+    *j->n_out = 0;
+    if (j->n_a == 0 || j->n_b == 0 || (j->triples && j->n_triples == 0)) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = j->stream ? (hipStream_t)j->stream : ctx->stream;
+    std::vector<uint32_t> fa((size_t)j->n_rates * (j->n_a + 1)), fb(j->n_b + 1);
+    VDF_HIP(ctx, hipMemcpyAsync(fa.data(), j->a_first, fa.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipMemcpyAsync(fb.data(), j->b_first, fb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));
+    if (int rc = align_rates_checks(ctx, "vdf_align_windows_rates_device", j, fa.data(), fb.data(), rates)) return rc;
+    return align_rates_locked(ctx, j, rates, j->a_hashes, j->a_skip, j->a_first, fa.data(), 0, j->b_hashes, j->b_skip, j->b_first, fb.data(), s);
+}
+
+// Host arrays: the rows of A that the blocks span and the rows of B go up ONCE through the context's staging buffers, for the seed pass and the
+// walk alike; beside them, in align_up, [first a | first b, rebased to the uploaded rows | skip a | skip b].
+int vdf_align_windows_rates(vdf_ctx *ctx, const vdf_align_rates_job *j)
+{
+    if (!ctx || !j) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    vdf::AlignSeedRate rates[VDF_WINDOWS_MAX_RATES];
+    if (int rc = align_rates_checks(ctx, "vdf_align_windows_rates", j, j->a_first, j->b_first, rates)) return rc;
+    *j->n_out = 0;
+    if (j->n_a == 0 || j->n_b == 0 || (j->triples && j->n_triples == 0)) return VDF_OK;
+    uint64_t a_lo = ~0ull, a_hi = 0;
+    for (uint32_t r = 0; r < j->n_rates; r++) {
+        const uint32_t *fa = j->a_first + (size_t)r * (j->n_a + 1);
+        const uint64_t base = j->a_rate_first ? (uint64_t)j->a_rate_first[r] : 0ull;
+        a_lo = std::min(a_lo, base + fa[0]);
+        a_hi = std::max(a_hi, base + fa[j->n_a]);
+    }
+    const uint64_t b_lo = j->b_first[0], b_hi = j->b_first[j->n_b];
+    const size_t wa = (size_t)(a_hi - a_lo), wb = (size_t)(b_hi - b_lo);
+    if (wa == 0 || wb == 0) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    std::vector<uint32_t> fb(j->n_b + 1);
+    for (size_t v = 0; v <= j->n_b; v++) fb[v] = j->b_first[v] - j->b_first[0];
+    const size_t fa_bytes = (size_t)j->n_rates * (j->n_a + 1) * sizeof(uint32_t), fb_bytes = fb.size() * sizeof(uint32_t);
+    const size_t ska = j->a_skip ? (wa + 3) & ~(size_t)3 : 0, skb = j->b_skip ? wb : 0;
+    VDF_HIP(ctx, ctx->align_up.reserve(fa_bytes + fb_bytes + ska + skb + 16));
+    char *up = ctx->align_up.as<char>();
+    VDF_HIP(ctx, hipMemcpyAsync(up, j->a_first, fa_bytes, hipMemcpyHostToDevice, s));
+    VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes, fb.data(), fb_bytes, hipMemcpyHostToDevice, s));
+    if (ska) VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes + fb_bytes, j->a_skip + a_lo, wa, hipMemcpyHostToDevice, s));
+    if (skb) VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes + fb_bytes + ska, j->b_skip + b_lo, wb, hipMemcpyHostToDevice, s));
+    if (int rc = upload(ctx, ctx->up_hashes, j->a_hashes + 16 * (size_t)a_lo, wa * 16 * sizeof(uint64_t), s)) return rc;
+    if (int rc = upload(ctx, ctx->up_ref_hashes, j->b_hashes + 16 * (size_t)b_lo, wb * 16 * sizeof(uint64_t), s)) return rc;
+    return align_rates_locked(ctx, j, rates, ctx->up_hashes.as<uint64_t>(), ska ? reinterpret_cast<const uint8_t *>(up + fa_bytes + fb_bytes) : nullptr,
+                              reinterpret_cast<const uint32_t *>(up), j->a_first, a_lo, ctx->up_ref_hashes.as<uint64_t>(),
+                              skb ? reinterpret_cast<const uint8_t *>(up + fa_bytes + fb_bytes + ska) : nullptr,
+                              reinterpret_cast<const uint32_t *>(up + fa_bytes), fb.data(), s);
 }
 
 size_t vdf_hash_window_count(uint32_t frames_per_clip, uint32_t window_stride) { return vdf::window_count(frames_per_clip, window_stride); }

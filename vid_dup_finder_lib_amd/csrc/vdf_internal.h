@@ -16,6 +16,7 @@
 #include "windows_mixed_rates_plan.h"
 #include "align_plan.h"
 #include "align_retimed_plan.h"
+#include "align_rates_plan.h"
 
 namespace vdf {
 
@@ -388,5 +389,22 @@ struct AlignSeedRatesLaunch {
 };
 hipError_t launch_align_seed_rates(const AlignSeedRatesLaunch &L, hipStream_t stream);
 hipError_t launch_align_seed_rates_scatter(const AlignSeedRatesLaunch &L, vdf_video_pair_rate *out, uint32_t limit, hipStream_t stream);
+// One chunk of a call over (rate, a, b) triples (align_rates_plan.h: AlignRatesChunk): the band walk of every (triple, phase,
+// band) unit, the two-level reduction per triple, the dense list in (rate, a, b) order.  plan: the chunk's one upload (table | triples |
+// unit_offset, align_rates_plan_bytes); a_first: n_rates x (n_a + 1); scratch holds align_rates_scratch_bytes(n_triples, n_units).  *dense_out /
+// *total_out: where in scratch the records and their number are once the stream has run.
+struct AlignRatesLaunch {
+    const uint32_t *a_hashes, *a_first;
+    const uint8_t *a_skip;               // nullable, per window
+    const uint32_t *b_hashes, *b_first;
+    const uint8_t *b_skip;
+    const void *plan;
+    uint32_t n_triples, n_units;
+    uint32_t tol, min_run;
+    void *scratch;
+    vdf_alignment_rate **dense_out;
+    uint32_t **total_out;
+};
+hipError_t launch_align_rates_chunk(const AlignRatesLaunch &L, hipStream_t stream);
 
 }  // namespace vdf

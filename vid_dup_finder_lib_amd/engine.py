@@ -500,6 +500,59 @@ def align_seed_pairs_rates_host(a_hashes, a_first, b_hashes, b_first, rates, tol
     return out[:min(n.value, out.size)], int(n.value)
 
 
+# one record of the align call over (rate, a, b) triples (include/vdf.h: vdf_alignment_rate, 32 bytes)
+ALIGN_RATE_DTYPE = _capi.ALIGN_RATE_DTYPE
+
+
+def video_pair_rates(triples) -> np.ndarray:
+    """A list of (rate, a, b) - VIDEO_PAIR_RATE_DTYPE records (what the seeded retimed call returns), or anything numpy reads as [n, 3] integers in
+    that order - as the C ABI takes it."""
+    if isinstance(triples, np.ndarray) and triples.dtype == VIDEO_PAIR_RATE_DTYPE:
+        return np.ascontiguousarray(triples).reshape(-1)
+    t = np.asarray(triples, dtype=np.int64).reshape(-1, 3)
+    if t.size and (t.min() < 0 or t.max() > 0xFFFFFFFF):
+        raise ValueError("rate and video indices are unsigned 32-bit")
+    out = np.zeros(len(t), VIDEO_PAIR_RATE_DTYPE)
+    out["rate"], out["a"], out["b"] = t[:, 0], t[:, 1], t[:, 2]
+    return out
+
+
+def _align_rates_job(a_hashes, a_first, n_a, a_rate_first, a_skip, b_hashes, b_first, n_b, b_skip, rates, tol_int, min_run, triples, seed, exclude_same,
+                     capacity, stream=0):
+    """(job, out, n, what the job points into): the job of vdf_align_windows_rates[_host|_device].  The array arguments are addresses (0 = NULL) -
+    of host or of device memory, as the form takes them; rates, a_rate_first and triples (None: no list) are host data."""
+    num, den = _align_rates(rates)
+    rf = None if a_rate_first is None else np.ascontiguousarray(a_rate_first, dtype=np.uintp).reshape(-1)
+    if rf is not None and rf.size < min(len(num), _capi.WINDOWS_MAX_RATES):
+        raise ValueError("a_rate_first has an entry per rate")
+    t = None if triples is None else video_pair_rates(triples)
+    out = np.zeros(max(int(capacity), 0), ALIGN_RATE_DTYPE)
+    n = C.c_size_t(0)
+    # an empty list must not read as "no list": numpy gives an empty array a non-null address
+    job = _capi.VdfAlignRatesJob(a_hashes or None, a_first or None, rf.ctypes.data if rf is not None else None, a_skip or None, int(n_a), b_hashes or None,
+                                 b_first or None, b_skip or None, int(n_b), len(num), num.ctypes.data if len(num) else None,
+                                 den.ctypes.data if len(num) else None, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                 None if t is None else (t.ctypes.data or out.ctypes.data or num.ctypes.data), 0 if t is None else t.size, 1 if seed else 0,
+                                 1 if exclude_same else 0, out.ctypes.data if out.size else None, out.size, C.pointer(n), stream or None)
+    return job, out, n, (num, den, rf, t)
+
+
+def align_windows_rates_host(a_hashes, a_first, b_hashes, b_first, rates, tol_int: int = 350, min_run: int = 1, a_rate_first=None, a_skip=None, b_skip=None,
+                             triples=None, seed: bool = False, exclude_same: bool = False, capacity: int = 1024):
+    """vdf_align_windows_rates_host: the retimed alignment at every rate of `rates` in one call - the definition in plain C++ on the CPU.  A is
+    RATE-MAJOR as align_seed_pairs_rates_host takes it, B plain windows.  triples: only these (rate, a, b) are walked (strictly increasing;
+    what align_seed_pairs_rates returns goes in unchanged); None: all of them - without a == b under exclude_same - or, with seed=True, the
+    candidates of the seed call, found inside the call: the same records.
+    -> (records [min(found, capacity)] of ALIGN_RATE_DTYPE in (rate, a, b) order - rate is the index into `rates` - and found)."""
+    keep, args = _seed_rates_host_args(a_hashes, a_first, a_rate_first, a_skip, b_hashes, b_first, b_skip, len(rates))
+    job, out, n, keep2 = _align_rates_job(rates=rates, a_rate_first=a_rate_first, tol_int=tol_int, min_run=min_run, triples=triples, seed=seed,
+                                          exclude_same=exclude_same, capacity=capacity, **args)
+    rc = _capi.load().vdf_align_windows_rates_host(C.byref(job))
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_align_windows_rates_host: bad argument")
+    return out[:min(n.value, out.size)], int(n.value)
+
+
 # one (variant, a, b) triple (include/vdf.h: vdf_video_pair_variant, 12 bytes): what the seeded variants call returns and the variants-pairs calls take
 VIDEO_PAIR_VARIANT_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("variant", "<u4")])
 
@@ -1230,6 +1283,27 @@ class Engine:
         job, out, n, keep = _seed_rates_job(d_a_hashes, d_a_first, n_a, a_rate_first, d_a_skip, d_b_hashes, d_b_first, n_b, d_b_skip, rates, tol_int, min_run,
                                             exclude_same, capacity, stream)
         self._check(self.lib.vdf_align_seed_pairs_rates_device(self.ctx, C.byref(job)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_rates(self, a_hashes, a_first, b_hashes, b_first, rates, tol_int: int = 350, min_run: int = 1, a_rate_first=None, a_skip=None,
+                            b_skip=None, triples=None, seed: bool = False, exclude_same: bool = False, capacity: int = 1024):
+        """The retimed alignment at every rate of `rates` in ONE call (vdf_align_windows_rates): arguments and result as
+        align_windows_rates_host.  The arrays go up once - with seed=True for the seed pass and the band walk alike - and the triples of all rates
+        are one launch set.  found > capacity: call again with a larger capacity."""
+        keep, args = _seed_rates_host_args(a_hashes, a_first, a_rate_first, a_skip, b_hashes, b_first, b_skip, len(rates))
+        job, out, n, keep2 = _align_rates_job(rates=rates, a_rate_first=a_rate_first, tol_int=tol_int, min_run=min_run, triples=triples, seed=seed,
+                                              exclude_same=exclude_same, capacity=capacity, **args)
+        self._check(self.lib.vdf_align_windows_rates(self.ctx, C.byref(job)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_rates_device(self, d_a_hashes: int, d_a_first: int, n_a: int, d_b_hashes: int, d_b_first: int, n_b: int, rates, tol_int: int = 350,
+                                   min_run: int = 1, a_rate_first=None, d_a_skip: int = 0, d_b_skip: int = 0, triples=None, seed: bool = False,
+                                   exclude_same: bool = False, capacity: int = 1024, stream: int = 0):
+        """The same on device arrays - d_a_first: n_rates x (n_a + 1) u32; rates, a_rate_first and triples stay HOST data; the records come back to
+        the host, the call is ordered on `stream` and waits for its own work."""
+        job, out, n, keep = _align_rates_job(d_a_hashes, d_a_first, n_a, a_rate_first, d_a_skip, d_b_hashes, d_b_first, n_b, d_b_skip, rates, tol_int, min_run,
+                                             triples, seed, exclude_same, capacity, stream)
+        self._check(self.lib.vdf_align_windows_rates_device(self.ctx, C.byref(job)))
         return out[:min(n.value, out.size)], int(n.value)
 
     def align_windows_pairs(self, a_hashes, a_first, pairs, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1, a_skip=None, b_skip=None,

@@ -916,6 +916,84 @@ public:
         }
     }
 
+    // ---- the retimed alignment at every rate of a list in ONE call: (rate, a, b) triples ----
+    // Which video of A is a copy of which video of B at which rate of the list, and where (vdf_align_windows_rates): the sides as
+    // align_seed_pairs_rates takes them.  triples (nullable): only these, strictly increasing in (rate, a, b) - what align_seed_pairs_rates returned
+    // goes in unchanged; null: every triple - without a == b under exclude_same - or, with seed, the candidates of the seed call, found inside the
+    // call on arrays that went up once: the same records.  One vdf_alignment_rate per triple at most, in (rate, a, b) order.
+    static vdf_align_rates_job align_rates_job(const SeedRatesSides &s, const std::vector<uint8_t> *skip_a, const std::vector<uint8_t> *skip_b, uint32_t tol_int,
+                                               uint32_t min_run, const std::vector<vdf_video_pair_rate> *triples, bool seed, bool exclude_same,
+                                               std::vector<vdf_alignment_rate> &out, size_t *found)
+    {
+        static const vdf_video_pair_rate no_triple{};  // an empty list must not read as "no list"
+        std::vector<vdf_video_pair_rate> none;
+        const vdf_align_seed_rates_job q = s.job(skip_a, skip_b, tol_int, min_run, exclude_same, none, found);
+        return vdf_align_rates_job{q.a_hashes, q.a_first, q.a_rate_first, q.a_skip, q.n_a, q.b_hashes, q.b_first, q.b_skip, q.n_b, q.n_rates, q.rate_num, q.rate_den,
+                                   tol_int, min_run, triples ? (triples->empty() ? &no_triple : triples->data()) : nullptr, triples ? triples->size() : 0,
+                                   seed ? 1u : 0u, exclude_same ? 1u : 0u, out.data(), out.size(), found, nullptr};
+    }
+
+    // the definition in plain C++ on the CPU (vdf_align_windows_rates_host): no context, no GPU
+    static std::vector<vdf_alignment_rate> align_windows_rates_host(const std::vector<std::vector<std::vector<VideoHash>>> &windows_by_rate_a,
+                                                                    const std::vector<std::vector<VideoHash>> &windows_b,
+                                                                    const std::vector<std::pair<uint32_t, uint32_t>> &rates, uint32_t tol_int, uint32_t min_run = 1,
+                                                                    const std::vector<vdf_video_pair_rate> *triples = nullptr, bool seed = false,
+                                                                    const std::vector<uint8_t> *skip_a = nullptr, const std::vector<uint8_t> *skip_b = nullptr,
+                                                                    bool exclude_same = false)
+    {
+        const SeedRatesSides s(windows_by_rate_a, windows_b, rates);
+        std::vector<vdf_alignment_rate> out(1024);
+        for (;;) {
+            size_t found = 0;
+            const vdf_align_rates_job job = align_rates_job(s, skip_a, skip_b, tol_int, min_run, triples, seed, exclude_same, out, &found);
+            if (vdf_align_windows_rates_host(&job) != VDF_OK)
+                throw std::invalid_argument("align_windows_rates: min_run of 0, a video of more than 2^20 windows, more than 2^24 pairs, no or more than 8 rates, "
+                                            "a rate outside 1 <= den <= num <= 2 den or with num above 32 in lowest terms, exclude_same between sets of two sizes, "
+                                            "a list together with seed or exclude_same, or a list that is not strictly increasing in (rate, a, b) or names what is not there");
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
+    // through a context (vdf_align_windows_rates): the host arrays go up once, for the seed pass and the band walk alike
+    static std::vector<vdf_alignment_rate> align_windows_rates(const std::vector<std::vector<std::vector<VideoHash>>> &windows_by_rate_a,
+                                                               const std::vector<std::vector<VideoHash>> &windows_b,
+                                                               const std::vector<std::pair<uint32_t, uint32_t>> &rates, uint32_t tol_int, uint32_t min_run = 1,
+                                                               const std::vector<vdf_video_pair_rate> *triples = nullptr, bool seed = false,
+                                                               const std::vector<uint8_t> *skip_a = nullptr, const std::vector<uint8_t> *skip_b = nullptr,
+                                                               bool exclude_same = false, Context *ctx_opt = nullptr)
+    {
+        const SeedRatesSides s(windows_by_rate_a, windows_b, rates);
+        Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+        std::vector<vdf_alignment_rate> out(1024);
+        for (;;) {
+            size_t found = 0;
+            const vdf_align_rates_job job = align_rates_job(s, skip_a, skip_b, tol_int, min_run, triples, seed, exclude_same, out, &found);
+            const int rc = vdf_align_windows_rates(ctx.get(), &job);
+            if (rc == VDF_E_INVAL) throw std::invalid_argument(vdf_last_error(ctx.get()));
+            if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);
+        }
+    }
+
+    // The same on device memory (vdf_align_windows_rates_device): the job's hashes, first arrays and skip bytes are device pointers - what
+    // hash_windows_clips_rates_device wrote goes in unchanged - rate_num, rate_den, a_rate_first and triples stay on the host; out, capacity and n_out
+    // of the job are set here.  The records come back to the host and the call waits for its own work on job.stream.
+    static std::vector<vdf_alignment_rate> align_windows_rates_device(Context &ctx, vdf_align_rates_job job)
+    {
+        std::vector<vdf_alignment_rate> out(1024);
+        for (;;) {
+            size_t found = 0;
+            job.out = out.data(); job.capacity = out.size(); job.n_out = &found;
+            const int rc = vdf_align_windows_rates_device(ctx.get(), &job);
+            if (rc == VDF_E_INVAL) throw std::invalid_argument(vdf_last_error(ctx.get()));
+            if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
     // hash_windows with the zero plane of every window (vdf_hash_windows_u8_planes): the same words, and every VideoHash
     // carries zero() - what align_windows_variants needs of the flipped side.
     static std::vector<std::vector<VideoHash>> hash_windows_planes(const uint8_t *frames, size_t n_videos, uint32_t frames_per_video, uint32_t w, uint32_t h,
