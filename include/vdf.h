@@ -511,7 +511,8 @@ int vdf_align_windows_stretches_pairs_device(vdf_ctx *ctx, const uint64_t *d_a_h
  * behind the align checks and before the list.  Each in the usual three forms: _host (plain C++, no context, no GPU: the CPU-tested
  * statement of the semantics), host arrays through a context (uploaded as vdf_align_windows uploads them), _device (DEVICE arrays, out
  * on the host; the call waits for its own work).  Skip bytes are read as the other align calls read them (the aligned 32-bit word).
- * Not offered: window starts of B that are not multiples of den; several stretches per pair or flips; rates above 2. */
+ * Not offered: window starts of B that are not multiples of den; flips; rates above 2.  Several stretches per pair:
+ * vdf_align_windows_rates_stretches* below (a one-rate list is this call's pair). */
 #define VDF_ALIGN_RETIMED_MAX_NUM 32
 typedef struct vdf_alignment_retimed { /* 24 bytes */
     uint32_t a;                /* video index in A */
@@ -639,8 +640,8 @@ int vdf_align_seed_pairs_rates_device(vdf_ctx *ctx, const vdf_align_seed_rates_j
  * _device: DEVICE hashes, first arrays and skip bytes; the rate arrays, a_rate_first, triples and out stay on the host; the first arrays are read
  * back as the seed call reads them; the call is ordered on `stream` (NULL = the context's) and waits for its own work.  In the context forms a
  * chunk of units may span rates: the triples of all rates are one launch set.
- * Not offered: the candidates handed to the band kernels on the device (the triples visit the host for planning); several stretches or
- * flips per triple; a C best_rates; multi-GPU contexts. */
+ * Not offered: the candidates handed to the band kernels on the device (the triples visit the host for planning); flips per triple; a C
+ * best_rates; multi-GPU contexts.  Several stretches per triple: vdf_align_windows_rates_stretches*, below. */
 typedef struct vdf_alignment_rate { /* 32 bytes */
     uint32_t a;                /* video index in A */
     uint32_t b;                /* video index in B */
@@ -678,6 +679,81 @@ typedef struct vdf_align_rates_job {
 int vdf_align_windows_rates_host(const vdf_align_rates_job *job);
 int vdf_align_windows_rates(vdf_ctx *ctx, const vdf_align_rates_job *job);
 int vdf_align_windows_rates_device(vdf_ctx *ctx, const vdf_align_rates_job *job);
+
+/* ---- EVERY stretch of a retimed pair, ranked, at up to VDF_WINDOWS_MAX_RATES rates in one call ---------------------------------
+ * A re-upload that was converted to another frame rate or sped up is usually edited as well: an ad break cut out (two stretches at two lines
+ * first_b - first_a den / num), a scene replaced (two runs on one line), a source used twice.  vdf_align_windows_rates* reports one record per
+ * triple; these calls report up to max_stretches, ranked - vdf_align_windows_stretches* for (rate, a, b) triples.  The inputs are exactly those of
+ * vdf_align_windows_rates*: A rate-major with a_first (n_rates x (n_a + 1)) and the HOST array a_rate_first, B plain windows at stride 1, the rate
+ * list, tol_int, min_run, and the three triple modes (a HOST list; every triple, with or without exclude_same; seed != 0).
+ * For one triple (r, a, b), rate r reduced to num / den, Na rows of a in block r, Nb rows of b:
+ *   - RANK 0 is the record vdf_align_windows_rates* reports for the triple, field for field;
+ *   - after a stretch (first_a, first_b, n) is reported, its RECTANGLE counts as non-matching for all later ranks of this triple.  It is kept in
+ *     the ROWS OF THE TWO VIDEOS, not in a phase's sub-matrix: rows [max(0, first_a - ga), min(Na, first_a + num (n - 1) + 1 + ga)) of a with
+ *     ga = ceil(guard num / den), rows [max(0, first_b - guard), min(Nb, first_b + den (n - 1) + 1 + guard)) of b; bounds in 64-bit arithmetic;
+ *   - cell (i, j) of the sub-matrix of ANY phase p is masked iff row p + num i lies in the rows of a AND row den j in the rows of b of the same
+ *     rectangle.  The rectangle masks all phases: otherwise rank 1 would be the same stretch seen from the neighbouring phase.  The same rows
+ *     of a against another part of b stay visible;
+ *   - a masked cell ends a run exactly as a non-matching cell does;
+ *   - RANK k is vdf_align_windows_retimed*'s record on the matrix masked by the rectangles of ranks 0 ... k - 1: the phase-bests by the align
+ *     rule, then the two-level reduction with its tie rules;
+ *   - a triple stops at the first rank without a record, or after max_stretches ranks.
+ * max_stretches: 1 ... 8.  guard: 0 ... 2^20, counted in rows of B - B holds plain windows at stride 1, so frames of b.
+ * At rate 1/1 the rectangle is vdf_align_windows_stretches'; a one-rate list at 1/1 gives vdf_align_windows_stretches_pairs*' records with
+ * first_a = start_a, first_b = start_a + offset.  seed != 0 seeds ONCE, in front of rank 0: a triple without a rank-0 record has no later rank,
+ * so the candidate set is still exact and the output equals the seed == 0 output record for record.
+ * The job: the fields of vdf_align_rates_job with their meaning, max_stretches and guard, and out of the record type below.  Records come in
+ * (rate, a, b, rank) order under the capacity protocol of the align calls (*n_out is always the number found, the first `capacity` are valid).
+ * With max_stretches == 1 the records are vdf_align_windows_rates*', with rank 0.
+ * Errors, all VDF_E_INVAL, in this order: those of vdf_align_windows_rates* in their order, up to and including the list; max_stretches outside
+ * 1 ... 8; guard above 2^20; a multi-GPU context.  n_a == 0, n_b == 0 or an empty list: VDF_OK with *n_out = 0.
+ * _host: plain C++, no context, no GPU - the definition above triple by triple, the CPU-tested statement of the semantics.
+ * vdf_align_windows_rates_stretches: host arrays - hashes, first arrays and skip bytes go up ONCE, for the seed pass and all rounds.
+ * _device: DEVICE hashes, first arrays and skip bytes; the rate arrays, a_rate_first, triples and out stay on the host; the call is ordered on
+ * `stream` (NULL = the context's) and waits for its own work.  In the context forms round 0 of a chunk is vdf_align_windows_rates*' launch;
+ * round k >= 1 walks only the triples that had a record in round k - 1, so a call whose triples have no record launches nothing more.
+ * Not offered: a round loop on the device (the records of a round visit the host, which appends the rectangles); flips; a C best_rates;
+ * multi-GPU contexts; rates outside [1, 2]. */
+typedef struct vdf_alignment_rate_stretch { /* 36 bytes */
+    uint32_t a;                /* the eight fields of vdf_alignment_rate */
+    uint32_t b;
+    uint32_t rate;
+    uint32_t first_a;
+    uint32_t first_b;
+    uint32_t n_windows;
+    uint32_t dist_sum;
+    uint32_t n_frames_b;
+    uint32_t rank;             /* 0 ... max_stretches - 1: 0 is the triple's best stretch */
+} vdf_alignment_rate_stretch;
+typedef struct vdf_align_rates_stretches_job {
+    const uint64_t *a_hashes;
+    const uint32_t *a_first;
+    const size_t *a_rate_first;
+    const uint8_t *a_skip;
+    size_t n_a;
+    const uint64_t *b_hashes;
+    const uint32_t *b_first;
+    const uint8_t *b_skip;
+    size_t n_b;
+    uint32_t n_rates;
+    const uint32_t *rate_num;
+    const uint32_t *rate_den;
+    uint32_t tol_int;
+    uint32_t min_run;
+    const vdf_video_pair_rate *triples;
+    size_t n_triples;
+    uint32_t seed;
+    uint32_t exclude_same;
+    uint32_t max_stretches;
+    uint32_t guard;
+    vdf_alignment_rate_stretch *out;
+    size_t capacity;
+    size_t *n_out;
+    void *stream;
+} vdf_align_rates_stretches_job;
+int vdf_align_windows_rates_stretches_host(const vdf_align_rates_stretches_job *job);
+int vdf_align_windows_rates_stretches(vdf_ctx *ctx, const vdf_align_rates_stretches_job *job);
+int vdf_align_windows_rates_stretches_device(vdf_ctx *ctx, const vdf_align_rates_stretches_job *job);
 
 /* ---- mirrored, flipped and reversed STRETCHES: window hashes with their zero planes -----------------------
  * A mirrored re-upload with its intro trimmed: the variant search sees only frames 0 ... 15 of a file, the align calls only unflipped

@@ -160,6 +160,19 @@ ALIGN_RATE_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("rate", "<u4"), ("firs
                              ("dist_sum", "<u4"), ("n_frames_b", "<u4")])
 
 
+class VdfAlignRatesStretchesJob(C.Structure):
+    """The argument list of vdf_align_windows_rates_stretches[_host|_device] (include/vdf.h: vdf_align_rates_stretches_job)."""
+    _fields_ = [("a_hashes", C.c_void_p), ("a_first", C.c_void_p), ("a_rate_first", C.c_void_p), ("a_skip", C.c_void_p), ("n_a", C.c_size_t),
+                ("b_hashes", C.c_void_p), ("b_first", C.c_void_p), ("b_skip", C.c_void_p), ("n_b", C.c_size_t), ("n_rates", C.c_uint32),
+                ("rate_num", C.c_void_p), ("rate_den", C.c_void_p), ("tol_int", C.c_uint32), ("min_run", C.c_uint32), ("triples", C.c_void_p),
+                ("n_triples", C.c_size_t), ("seed", C.c_uint32), ("exclude_same", C.c_uint32), ("max_stretches", C.c_uint32), ("guard", C.c_uint32),
+                ("out", C.c_void_p), ("capacity", C.c_size_t), ("n_out", C.POINTER(C.c_size_t)), ("stream", C.c_void_p)]
+
+
+# one record of vdf_align_windows_rates_stretches* (include/vdf.h: vdf_alignment_rate_stretch, 36 bytes): ALIGN_RATE_DTYPE's fields, then the rank
+ALIGN_RATE_STRETCH_DTYPE = np.dtype(ALIGN_RATE_DTYPE.descr + [("rank", "<u4")])
+
+
 class VdfVideoPair(C.Structure):
     """One pair of vdf_align_seed_pairs* and of the lists of the *_pairs calls: 8 bytes (the numpy twin is engine.VIDEO_PAIR_DTYPE)."""
     _fields_ = [("a", C.c_uint32), ("b", C.c_uint32)]
@@ -307,6 +320,9 @@ SIGNATURES = {
     "vdf_align_windows_rates_host": (C.c_int, [C.POINTER(VdfAlignRatesJob)]),
     "vdf_align_windows_rates": (C.c_int, [_ctx, C.POINTER(VdfAlignRatesJob)]),
     "vdf_align_windows_rates_device": (C.c_int, [_ctx, C.POINTER(VdfAlignRatesJob)]),
+    "vdf_align_windows_rates_stretches_host": (C.c_int, [C.POINTER(VdfAlignRatesStretchesJob)]),
+    "vdf_align_windows_rates_stretches": (C.c_int, [_ctx, C.POINTER(VdfAlignRatesStretchesJob)]),
+    "vdf_align_windows_rates_stretches_device": (C.c_int, [_ctx, C.POINTER(VdfAlignRatesStretchesJob)]),
     "vdf_align_windows_pairs_host": (C.c_int, _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "vdf_align_windows_pairs": (C.c_int, [_ctx] + _ALIGN_SIDES + [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                                                    C.POINTER(C.c_size_t)]),

@@ -23,10 +23,11 @@ from .engine import (ALIGN_DTYPE, ALIGN_STRETCH_DTYPE, ALIGN_VARIANT_DTYPE, Engi
                      tolerance_int, video_pairs, align_seed_pairs_host, align_windows_pairs_host, align_windows_stretches_pairs_host,
                      ALIGN_RETIMED_DTYPE, VIDEO_PAIR_DTYPE, align_windows_retimed_host, align_windows_retimed_pairs_host,
                      pair_list_problem, VIDEO_PAIR_VARIANT_DTYPE, align_seed_pairs_variants_host, align_windows_variants_pairs_host,
-                     VIDEO_PAIR_RATE_DTYPE, align_seed_pairs_rates_host, ALIGN_RATE_DTYPE, align_windows_rates_host)
+                     VIDEO_PAIR_RATE_DTYPE, align_seed_pairs_rates_host, ALIGN_RATE_DTYPE, align_windows_rates_host, ALIGN_RATE_STRETCH_DTYPE,
+                     align_windows_rates_stretches_host)
 
 __all__ = ["Crop", "Cropdetect", "cropdetect_letterbox", "gen_hashes", "VideoHash", "MatchGroup", "Error", "NotEnoughFrames", "NotVideo", "VidProc", "TooFewEntries", "search",
-           "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "hash_frame_windows", "align_rates", "best_rates", "candidate_pairs_rates", "locate", "rust_path_key", "sort_order",
+           "search_with_references", "search_flipped", "Flip", "default_engine", "hash_frame_stacks", "hash_frame_windows", "align_rates", "best_rates", "align_rates_all", "best_rates_all", "RetimedAlignmentStretch", "candidate_pairs_rates", "locate", "rust_path_key", "sort_order",
            "DEFAULT_SEARCH_TOLERANCE", "TOLERANCE_SCALING_FACTOR"]
 
 
@@ -1265,6 +1266,120 @@ def best_rates(result: dict, tolerance: float = DEFAULT_SEARCH_TOLERANCE) -> Lis
             if (r.a, r.b) not in best or score > best[(r.a, r.b)][0]:
                 best[(r.a, r.b)] = (score, r)
     return [best[k][1] for k in sorted(best)]
+
+
+class RetimedAlignmentStretch(NamedTuple):
+    """One of the stretches a video shares with a copy at num / den of its frames (align_rates_all): RetimedAlignment's fields plus the rank - 0
+    is the pair's best stretch at that rate, the one align_rates reports; rank r is the best outside the rectangles of the ranks before it."""
+    a: int
+    b: int
+    num: int
+    den: int
+    first_frame_a: int
+    first_frame_b: int
+    n_frames_a: int        # (n_windows - 1) * num + span
+    n_frames_b: int        # (n_windows - 1) * den + 16
+    n_windows: int
+    mean_distance: float
+    path_a: object = None
+    path_b: object = None
+    rank: int = 0
+
+
+ALIGN_RATES_ALL_GUARD = 15  # frames of b: windows less than 16 frames apart share frames (align_all's default guard at stride 1)
+
+
+def _rates_stretches_call(engine, A, B, rates, tol_int, min_run, max_stretches, guard, triples, seed):
+    """_rates_call for the stretches call: one call of the C ABI (vdf_align_windows_rates_stretches[_host]), ALIGN_RATE_STRETCH_DTYPE in (rate, a, b,
+    rank) order."""
+    def once(capacity):
+        kw = dict(tol_int=tol_int, min_run=min_run, max_stretches=max_stretches, guard=guard, a_rate_first=A[2], a_skip=A[3], b_skip=B[2], triples=triples,
+                  seed=seed, capacity=capacity)
+        call = align_windows_rates_stretches_host if engine is None else engine.align_windows_rates_stretches
+        return call(A[0], A[1], B[0], B[1], rates, **kw)
+    rec, found = once(ALIGN_FIRST_CAPACITY)
+    if found > len(rec):
+        rec, found = once(found)
+    return rec
+
+
+def align_rates_all(windows_by_rate_a: dict, windows_b: List[List[VideoHash]], tolerance: float = DEFAULT_SEARCH_TOLERANCE, min_run: int = 1,
+                    max_stretches: int = 4, guard: Optional[int] = None, static_a: Optional[dict] = None, static_b=None, engine: Optional[Engine] = None,
+                    pairs=None, seed: bool = False) -> dict:
+    """EVERY stretch a video of A shares with a video of B at each of several rates, not only the best one: a copy that was converted to another
+    frame rate or sped up AND had an ad break cut out shares two stretches with its source, one that had a scene replaced two runs on one line.
+    Arguments as align_rates(one_call=True); per (rate, a, b) up to max_stretches (1 ... 8) RetimedAlignmentStretch
+    -> {rate: [RetimedAlignmentStretch] ordered by (a, b, rank)}.  Rank 0 is the record align_rates reports; after every reported stretch its
+    rectangle - its frames of a x its frames of b, widened by `guard` frames of b (and guard * num / den of a) - counts as non-matching in EVERY
+    phase, and the next rank is the best record of what is left (include/vdf.h: vdf_align_windows_rates_stretches).  guard None: 15 frames.
+    One call of the C ABI per block of at most ALIGN_MAX_PAIRS pairs of videos, for all rates; with no engine given, tiny inputs are walked on the
+    CPU.  pairs / seed: as in align_rates(one_call=True).  best_rates_all picks one rate per pair from the result."""
+    if guard is None:
+        guard = ALIGN_RATES_ALL_GUARD
+    tol_int = tolerance_int(tolerance)
+    rates, per = _rates_csr(windows_by_rate_a, static_a)
+    reduced = [_retimed_rate(r) for r in rates]
+    wb, fb, kb, cb = _align_csr(windows_b, static_b)
+    n_a = len(per[0][3])
+    pair_list = _align_pair_list(pairs, n_a, len(cb), False)
+    engine = _rates_engine(engine, rates, per, cb)
+    key = lambda p: (p["a"].astype(np.uint64) << np.uint64(32)) | p["b"].astype(np.uint64)
+    step = max(1, math.isqrt(ALIGN_MAX_PAIRS))
+    parts = []
+    for a0 in range(0, n_a, step):
+        a1 = min(a0 + step, n_a)
+        A = _rates_block(per, a0, a1)
+        for b0 in range(0, len(cb), step):
+            b1 = min(b0 + step, len(cb))
+            w0, w1 = int(fb[b0]), int(fb[b1])
+            B = (wb[w0:w1], fb[b0:b1 + 1] - fb[b0], None if kb is None else kb[w0:w1])
+            plist = _block_pairs(engine, None, None, a0, a1, b0, b1, tol_int, int(min_run), pair_list, False)
+            triples = None
+            if plist is not None:
+                if seed and len(plist):
+                    t = _seed_rates_call(engine, A, B, rates, tol_int, int(min_run), False)
+                    cand = np.zeros(len(t), VIDEO_PAIR_DTYPE)
+                    cand["a"], cand["b"] = t["a"], t["b"]
+                    triples = t[np.isin(key(cand), key(plist))]
+                else:
+                    triples = np.zeros(len(rates) * len(plist), VIDEO_PAIR_RATE_DTYPE)
+                    triples["a"], triples["b"] = np.tile(plist["a"], len(rates)), np.tile(plist["b"], len(rates))
+                    triples["rate"] = np.repeat(np.arange(len(rates), dtype=np.uint32), len(plist))
+                if not len(triples):
+                    continue
+            rec = _rates_stretches_call(engine, A, B, rates, tol_int, int(min_run), int(max_stretches), int(guard), triples, bool(seed) and triples is None).copy()
+            rec["a"] += a0
+            rec["b"] += b0
+            parts.append(rec)
+    rec = np.concatenate(parts) if parts else np.zeros(0, ALIGN_RATE_STRETCH_DTYPE)
+    rec = rec[np.lexsort((rec["rank"], rec["b"], rec["a"], rec["rate"]))]
+    pb = [ws[0].src_path() if ws else None for ws in windows_b]
+    out = {}
+    for i, (rate, (num, den)) in enumerate(zip(rates, reduced)):
+        pa = [ws[0].src_path() if ws else None for ws in windows_by_rate_a[rate]]
+        span = (15 * num) // den + 1
+        out[rate] = []
+        for r in rec[rec["rate"] == i]:
+            a, b, fa, fb_, n, ds, nfb, rank = (int(r[k]) for k in ("a", "b", "first_a", "first_b", "n_windows", "dist_sum", "n_frames_b", "rank"))
+            out[rate].append(RetimedAlignmentStretch(a, b, num, den, fa, fb_, (n - 1) * num + span, nfb, n, ds / n, pa[a], pb[b], rank))
+    return out
+
+
+def best_rates_all(result: dict, tolerance: float = DEFAULT_SEARCH_TOLERANCE) -> dict:
+    """One rate per pair (a, b) out of align_rates_all's result -> {(a, b): [RetimedAlignmentStretch]} with the keys in (a, b) order and the chosen
+    rate's stretches by rank: the rate whose stretches TOGETHER maximise the sum of n_frames_b * (tol_int + 1 - mean_distance) - best_rates' score,
+    added up over the stretches, so that a cut copy is judged by all of its parts.  Ties go to the rate that comes first in `result`."""
+    tol_int = tolerance_int(tolerance)
+    best = {}
+    for recs in result.values():
+        per_pair = {}
+        for r in recs:
+            per_pair.setdefault((r.a, r.b), []).append(r)
+        for k, rs in per_pair.items():
+            score = sum(r.n_frames_b * (tol_int + 1 - r.mean_distance) for r in rs)
+            if k not in best or score > best[k][0]:
+                best[k] = (score, sorted(rs, key=lambda r: r.rank))
+    return {k: best[k][1] for k in sorted(best)}
 
 
 class AlignmentStretch(NamedTuple):

@@ -23,9 +23,13 @@
 // and the two-level reduction bands -> phase-best -> pair record (vdf_align_windows_retimed*; align_retimed_plan.h).
 // align_bands_rates_kernel / align_reduce_rates_kernel / align_scatter_rates_kernel, behind launch_align_retimed_chunk: the retimed walk on
 // (rate, a, b) triples of up to 8 rates in one launch, the rate looked up per wave (vdf_align_windows_rates*; align_rates_plan.h).
+// align_bands_rates_masked_kernel, behind launch_align_rates_chunk: the rates kernel's walk with the cells of a triple's rectangles - kept in rows
+// of the two videos, so that they mask every phase - as misses: the rounds r >= 1 of vdf_align_windows_rates_stretches* (DESIGN.md 4.24;
+// align_rates_stretch_plan.h).
 // align_seed_rates_kernel, at the very end: the seed pass of the retimed alignment, every phase of up to 8 rates on gathered rows of B
 // (vdf_align_seed_pairs_rates*; align_seed_rates_plan.h).
 #include "align_plan.h"
+#include "align_rates_stretch_plan.h"
 #include "align_retimed_plan.h"
 #include "align_seed_rates_plan.h"
 #include "vdf_internal.h"
@@ -718,6 +722,169 @@ hipError_t launch_align_rates_chunk(const AlignRatesLaunch &L, hipStream_t strea
     for (const AlignLaunchCut &cut : align_launch_cuts(n_groups)) {
         hipLaunchKernelGGL(align_bands_rates_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_first, L.a_skip, L.b_hashes, L.b_first,
                            L.b_skip, table, triples, unit_offset, L.n_triples, L.n_units, L.tol, L.min_run, band_records, (uint32_t)cut.group_base);
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(align_reduce_rates_kernel, dim3(n_blocks), dim3(256), 0, stream, table, triples, unit_offset, L.n_triples, L.a_first, L.b_first, L.tol,
+                       band_records, triple_records, block_count);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(align_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, n_blocks, block_offset, total);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(align_scatter_rates_kernel, dim3(n_blocks), dim3(256), 0, stream, triple_records, L.n_triples, block_offset, dense);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    *L.dense_out = dense;
+    *L.total_out = total;
+    return hipSuccess;
+}
+
+// The rates kernel's walk with the cells of the triple's rectangles as misses: the rounds r >= 1 of vdf_align_windows_rates_stretches* (DESIGN.md
+// 4.24).  A kernel of its own, so that the plain, masked, retimed and rates kernels keep their text and code.  The unit's triple has n_rects = r
+// rectangles at rects[triple * n_rects] (align_rates_stretch_plan.h), in ROWS OF THE TWO VIDEOS: [a_lo, a_hi) counts the rows of video a in the
+// slot's block, [b_lo, b_hi) the rows of video b.  A cell (ka, kb) of phase p's sub-matrix is masked iff one rectangle holds ra = p + num ka and
+// rb = den kb - so a stretch found in one phase masks its neighbourhood in every phase.  As in align_bands_masked_kernel the rectangles are
+// wave-uniform: scalar loads into SGPRs in front of the walk (the slots behind n_rects are empty rectangles), the test on ra is scalar, and the
+// test on rb - one multiply per lane, two compares per rectangle and lane - runs only in steps whose ra lies in a rectangle's rows of A.  A lane whose
+// kb is outside the sub-matrix has row_ok false: what the test makes of its rb is not used.  No LDS, no scratch, vector stores only.
+__global__ __launch_bounds__(256) void align_bands_rates_masked_kernel(
+    const uint32_t *__restrict__ a_hashes, const uint32_t *__restrict__ a_first, const uint8_t *__restrict__ a_skip,
+    const uint32_t *__restrict__ b_hashes, const uint32_t *__restrict__ b_first, const uint8_t *__restrict__ b_skip,
+    const AlignRatesSlot *__restrict__ table, const AlignRatesTriple *__restrict__ triples, const uint32_t *__restrict__ unit_offset, uint32_t n_triples,
+    uint32_t n_units, uint32_t tol, uint32_t min_run, AlignBandRecord *__restrict__ band_records, uint32_t group_base,
+    const AlignRect *__restrict__ rects, uint32_t n_rects)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t unit = (blockIdx.x + group_base) * kAlignWaves + wave;  // grids above 2^32 work-items are launched in cuts
+    if (unit >= n_units) return;
+
+    const uint32_t t = align_unit_pair((align_u32_ptr)(uintptr_t)unit_offset, n_triples, unit);
+    align_u32_ptr tp = (align_u32_ptr)(uintptr_t)triples + (size_t)t * 3;
+    const uint32_t va = tp[0], vb = tp[1];
+    const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)tp[2]);  // < kAlignRatesMax: the host's planner wrote it
+    align_u32_ptr sp = (align_u32_ptr)(uintptr_t)table + (size_t)slot * 4;
+    const uint32_t num = sp[0], den = sp[1], row0 = sp[2];
+    align_u32_ptr af = (align_u32_ptr)(uintptr_t)a_first + sp[3];       // the slot's row of a_first
+    const uint32_t fa = row0 + af[va], Na_all = af[va + 1] - af[va];     // 32-bit sum: a row of the hashes the kernel sees (AlignRatesSlot)
+    const uint32_t fb = ((align_u32_ptr)(uintptr_t)b_first)[vb], Nb_all = ((align_u32_ptr)(uintptr_t)b_first)[vb + 1] - fb;
+    uint32_t phase, band;
+    align_retimed_unit(align_retimed_split(Na_all, Nb_all, num, den), unit - ((align_u32_ptr)(uintptr_t)unit_offset)[t], &phase, &band);
+    const uint32_t Na = align_retimed_na(Na_all, num, phase), Nb = align_retimed_nb(Nb_all, den);  // the sub-matrix
+    const int32_t d0 = align_band_d0(Na, band);
+    const uint32_t ka0 = align_ka_begin(d0), ka1 = align_ka_end(Na, Nb, d0);
+    AlignRect rc[kAlignMaxStretches - 1];  // in rows of video a of the slot's block and rows of video b, not in sub-matrix cells
+    align_u32_ptr rp = (align_u32_ptr)(uintptr_t)rects + (size_t)t * n_rects * 4;
+#pragma unroll
+    for (uint32_t i = 0; i < kAlignMaxStretches - 1; i++) {
+        if (i < n_rects) rc[i] = AlignRect{rp[4 * i], rp[4 * i + 1], rp[4 * i + 2], rp[4 * i + 3]};
+        else rc[i] = AlignRect{0u, 0u, 0u, 0u};
+    }
+
+    const uint32_t *b_rows = b_hashes + (size_t)fb * 32;
+    const uint8_t *b_sk = b_skip ? b_skip + fb : nullptr;
+    align_u32_ptr a_rows = (align_u32_ptr)(uintptr_t)a_hashes + (size_t)fa * 32;
+
+    // this lane's row of B; cells outside the sub-matrix are misses and no address is formed for them
+    uint32_t rw[32];
+    int32_t kb = align_lane_row(lane, ka0, d0);
+    bool row_ok = kb >= 0 && kb < (int32_t)Nb;
+    uint32_t row_skip = 0;  // the row's skip byte: compared where the row is used, so that the load is not waited for where it is issued
+    if (row_ok) {
+        const uint32_t rb = align_retimed_row_b(den, (uint32_t)kb);  // < Nb_all
+        if (b_sk) row_skip = b_sk[rb];
+        align_load_row(rw, b_rows, rb);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 32; q++) rw[q] = 0u;
+    }
+
+    uint32_t len = 0, sum = 0;                                              // the run of the diagonal this lane is on
+    uint32_t best_score = 0, best_start = 0, best_n = 0, best_sum = 0;     // score 0 = none: every run scores at least 1
+    int32_t best_off = 0;
+    for (uint32_t ka = ka0; ka < ka1; ++ka) {
+        const uint32_t ra = align_retimed_row_a(phase, num, ka);  // < Na_all, wave-uniform
+        align_u32_ptr ap = a_rows + (size_t)ra * 32;
+        uint32_t d = 0;
+#pragma unroll
+        for (int w = 0; w < 32; ++w) d += __builtin_popcount(rw[w] ^ ap[w]);  // ap[w]: SGPR
+        bool a_ok = true;  // wave-uniform: the skip byte of A's row comes with the aligned dword that holds it, by a scalar load like the row
+        if (a_skip) {
+            const uintptr_t at = (uintptr_t)a_skip + fa + ra;
+            a_ok = ((*(align_u32_ptr)(at & ~(uintptr_t)3) >> (8 * (uint32_t)(at & 3))) & 0xFFu) == 0u;
+        }
+        bool match = row_ok && row_skip == 0 && a_ok && d <= tol;
+        bool in_a = false;  // wave-uniform: the rectangles and ra are
+#pragma unroll
+        for (uint32_t i = 0; i < kAlignMaxStretches - 1; i++) in_a = in_a || align_rect_has_a(rc[i], ra);
+        if (in_a) match = match && !align_cell_masked(rc, kAlignMaxStretches - 1, ra, align_retimed_row_b(den, (uint32_t)kb));
+        if (match) { len += 1; sum += d; }
+        const bool edge = ka + 1 == Na || kb + 1 == (int32_t)Nb;              // the diagonal's last cell
+        const bool ends = len != 0 && (!match || edge);
+        if (__builtin_amdgcn_ballot_w64(ends) != 0ull) {
+            if (ends && len >= min_run) {
+                const uint32_t score = len * (tol + 1) - sum;
+                const uint32_t start = (match ? ka + 1 : ka) - len;
+                const int32_t off = kb - (int32_t)ka;
+                if (align_better(score, off, start, best_score, best_off, best_start)) {
+                    best_score = score; best_off = off; best_start = start; best_n = len; best_sum = sum;
+                }
+            }
+            if (ends) { len = 0; sum = 0; }
+        }
+        // the state follows its diagonal one lane up
+        len = align_rotate_up(len, lane);
+        sum = align_rotate_up(sum, lane);
+        // the lane whose diagonal d0 is done takes the row of diagonal d0 + 63 of the next step
+        if (ka + 1 < ka1 && lane == align_reload_lane(ka, d0)) {
+            kb += (int32_t)kAlignBand;  // = align_reload_row(ka, d0) >= 1, from the lane's own register: the address stays a vector address
+            row_ok = kb < (int32_t)Nb;
+            row_skip = 0;
+            if (row_ok) {
+                const uint32_t rb = align_retimed_row_b(den, (uint32_t)kb);
+                if (b_sk) row_skip = b_sk[rb];
+                align_load_row(rw, b_rows, rb);
+            }
+        }
+    }
+
+    // the wave's best of its 64 lane-bests; every run has its own (score, offset, start)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t o_score = (uint32_t)__shfl_xor((int)best_score, o, 64), o_start = (uint32_t)__shfl_xor((int)best_start, o, 64);
+        const uint32_t o_n = (uint32_t)__shfl_xor((int)best_n, o, 64), o_sum = (uint32_t)__shfl_xor((int)best_sum, o, 64);
+        const int32_t o_off = __shfl_xor(best_off, o, 64);
+        if (align_better(o_score, o_off, o_start, best_score, best_off, best_start)) {
+            best_score = o_score; best_off = o_off; best_start = o_start; best_n = o_n; best_sum = o_sum;
+        }
+    }
+    if (lane == 0) band_records[unit] = AlignBandRecord{best_off, best_start, best_score ? best_n : 0u, best_sum};
+}
+
+// launch_align_rates_chunk with the masked band kernel: L.plan is the round's upload (align_rates_round_plan_bytes: table | triples | unit_offset
+// | rects), n_rects in 1 ... kAlignMaxStretches - 1.  The reduction, the scan and the 32-byte scatter are the plain chunk's, as they are: the
+// rank of a round's records is the round's number, which the host adds.
+hipError_t launch_align_rates_masked_chunk(const AlignRatesLaunch &L, uint32_t n_rects, hipStream_t stream)
+{
+    if (L.n_triples == 0 || L.n_units == 0 || !L.plan || n_rects == 0 || n_rects >= kAlignMaxStretches) return hipErrorInvalidValue;
+    const char *plan = static_cast<const char *>(L.plan);
+    const AlignRatesSlot *table = reinterpret_cast<const AlignRatesSlot *>(plan);
+    const AlignRatesTriple *triples = reinterpret_cast<const AlignRatesTriple *>(plan + align_rates_plan_triples_at());
+    const uint32_t *unit_offset = reinterpret_cast<const uint32_t *>(plan + align_rates_plan_offsets_at(L.n_triples));
+    const AlignRect *rects = reinterpret_cast<const AlignRect *>(plan + align_rates_plan_rects_at(L.n_triples));
+    // scratch: band records | triple records | dense records | block counts | block offsets | total (align_rates_scratch_bytes)
+    char *s = static_cast<char *>(L.scratch);
+    AlignBandRecord *band_records = reinterpret_cast<AlignBandRecord *>(s);
+    s += (size_t)L.n_units * sizeof(AlignBandRecord);
+    vdf_alignment_rate *triple_records = reinterpret_cast<vdf_alignment_rate *>(s);
+    s += (size_t)L.n_triples * sizeof(vdf_alignment_rate);
+    vdf_alignment_rate *dense = reinterpret_cast<vdf_alignment_rate *>(s);
+    s += (size_t)L.n_triples * sizeof(vdf_alignment_rate);
+    const uint32_t n_blocks = (L.n_triples + 255) / 256;
+    uint32_t *block_count = reinterpret_cast<uint32_t *>(s), *block_offset = block_count + n_blocks, *total = block_offset + n_blocks;
+
+    const size_t n_groups = ((size_t)L.n_units + kAlignWaves - 1) / kAlignWaves;
+    for (const AlignLaunchCut &cut : align_launch_cuts(n_groups)) {
+        hipLaunchKernelGGL(align_bands_rates_masked_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_first, L.a_skip, L.b_hashes,
+                           L.b_first, L.b_skip, table, triples, unit_offset, L.n_triples, L.n_units, L.tol, L.min_run, band_records, (uint32_t)cut.group_base,
+                           rects, n_rects);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(align_reduce_rates_kernel, dim3(n_blocks), dim3(256), 0, stream, table, triples, unit_offset, L.n_triples, L.a_first, L.b_first, L.tol,

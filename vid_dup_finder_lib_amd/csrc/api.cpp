@@ -1999,6 +1999,50 @@ void align_retimed_pair_host(const uint64_t *A, uint32_t Na, const uint8_t *skip
     best->first_a = pair.first_a; best->first_b = pair.first_b; best->n_windows = pair.score ? pair.n_windows : 0u; best->dist_sum = pair.dist_sum;
 }
 
+// align_retimed_pair_host with rectangles (vdf_align_windows_rates_stretches*): the same walk, and a cell whose rows - row
+// p + num i of a, row den j of b - lie in one of the n_rects rectangles is a miss.  The rectangles are in rows of the two videos, so each masks
+// the cells of every phase.  best->n_windows = 0: no competing run
+void align_retimed_pair_masked_host(const uint64_t *A, uint32_t Na, const uint8_t *skip_a, const uint64_t *B, uint32_t Nb, const uint8_t *skip_b, uint32_t num,
+                                    uint32_t den, uint32_t tol, uint32_t min_run, const vdf::AlignRect *rects, uint32_t n_rects, vdf_alignment_retimed *best)
+{
+    const uint32_t nb0 = vdf::align_retimed_nb(Nb, den);
+    vdf::AlignRetimedBest pair{0u, 0u, 0u, 0u, 0u};
+    for (uint32_t p = 0; p < num; p++) {
+        const uint32_t na = vdf::align_retimed_na(Na, num, p);
+        if (na == 0 || nb0 == 0) continue;
+        vdf_alignment ph{};  // the phase-best
+        uint32_t ph_score = 0;
+        for (int64_t d = -((int64_t)na - 1); d <= (int64_t)nb0 - 1; d++) {
+            const int64_t i0 = std::max<int64_t>(0, -d), i1 = std::min<int64_t>(na, (int64_t)nb0 - d);
+            uint32_t len = 0, sum = 0;
+            for (int64_t i = i0; i <= i1; i++) {  // i1: the cell behind the diagonal's last, a miss
+                bool match = false;
+                uint32_t dist = 0;
+                if (i < i1) {
+                    const size_t ra = vdf::align_retimed_row_a(p, num, (uint32_t)i), rb = vdf::align_retimed_row_b(den, (uint32_t)(i + d));
+                    if (!(skip_a && skip_a[ra]) && !(skip_b && skip_b[rb]) && !vdf::align_cell_masked(rects, n_rects, (uint32_t)ra, (uint32_t)rb)) {
+                        const uint64_t *x = A + 16 * ra, *y = B + 16 * rb;
+                        for (int w = 0; w < VDF_HASH_WORDS; w++) dist += (uint32_t)__builtin_popcountll(x[w] ^ y[w]);
+                        match = dist <= tol;
+                    }
+                }
+                if (match) { len++; sum += dist; continue; }
+                if (len >= min_run) {
+                    const uint32_t score = len * (tol + 1) - sum, start = (uint32_t)(i - len);
+                    if (vdf::align_better(score, (int32_t)d, start, ph_score, ph.offset, ph.start_a)) {
+                        ph_score = score; ph.offset = (int32_t)d; ph.start_a = start; ph.n_windows = len; ph.dist_sum = sum;
+                    }
+                }
+                len = 0; sum = 0;
+            }
+        }
+        if (ph_score == 0) continue;
+        const uint32_t first_a = vdf::align_retimed_row_a(p, num, ph.start_a), first_b = vdf::align_retimed_row_b(den, (uint32_t)((int32_t)ph.start_a + ph.offset));
+        if (vdf::align_retimed_better(ph_score, first_a, first_b, pair)) pair = vdf::AlignRetimedBest{ph_score, first_a, first_b, ph.n_windows, ph.dist_sum};
+    }
+    best->first_a = pair.first_a; best->first_b = pair.first_b; best->n_windows = pair.score ? pair.n_windows : 0u; best->dist_sum = pair.dist_sum;
+}
+
 // align_locked for the retimed call: the chunks hold (pair, phase, band) units; num / den in lowest terms.  `in` is never self.
 int align_retimed_locked(vdf_ctx *ctx, const AlignSides &in, uint32_t tol_int, uint32_t min_run, uint32_t num, uint32_t den, vdf_alignment_retimed *out,
                          size_t capacity, size_t *n_out, hipStream_t s, const vdf_video_pair *list = nullptr, size_t n_list = 0)
@@ -3130,6 +3174,252 @@ int vdf_align_windows_rates(vdf_ctx *ctx, const vdf_align_rates_job *j)
                               reinterpret_cast<const uint32_t *>(up), j->a_first, a_lo, ctx->up_ref_hashes.as<uint64_t>(),
                               skb ? reinterpret_cast<const uint8_t *>(up + fa_bytes + fb_bytes + ska) : nullptr,
                               reinterpret_cast<const uint32_t *>(up + fa_bytes), fb.data(), s);
+}
+
+// ---- every stretch of a retimed pair, ranked, at up to 8 rates in one call (include/vdf.h: vdf_align_windows_rates_stretches*; DESIGN.md 4.24;
+// align_rates_stretch_plan.h) -------------------------------------------------------------------------------------------------------------------
+// the align job on a stretches job's arguments: same arrays, rates, tol / min_run, triple mode; out is only tested for null
+static vdf_align_rates_job align_rates_stretches_plain_job(const vdf_align_rates_stretches_job *j)
+{
+    vdf_align_rates_job q{};
+    q.a_hashes = j->a_hashes; q.a_first = j->a_first; q.a_rate_first = j->a_rate_first; q.a_skip = j->a_skip; q.n_a = j->n_a;
+    q.b_hashes = j->b_hashes; q.b_first = j->b_first; q.b_skip = j->b_skip; q.n_b = j->n_b;
+    q.n_rates = j->n_rates; q.rate_num = j->rate_num; q.rate_den = j->rate_den;
+    q.tol_int = j->tol_int; q.min_run = j->min_run; q.triples = j->triples; q.n_triples = j->n_triples; q.seed = j->seed; q.exclude_same = j->exclude_same;
+    q.out = reinterpret_cast<vdf_alignment_rate *>(j->out); q.capacity = j->capacity; q.n_out = j->n_out; q.stream = j->stream;
+    return q;
+}
+
+// The checks of the three forms, in the header's order: those of vdf_align_windows_rates* up to and including the list (first arrays on the host,
+// or null: the device form before they have come down), max_stretches, guard, the context.
+static int align_rates_stretches_checks(vdf_ctx *ctx, const char *name, const vdf_align_rates_stretches_job *sj, const uint32_t *a_first, const uint32_t *b_first,
+                                        vdf::AlignSeedRate *rates)
+{
+    const vdf_align_rates_job j = align_rates_stretches_plain_job(sj);
+    const vdf_align_seed_rates_job q = align_rates_seed_job(&j);
+    if (int rc = seed_rates_checks(ctx, name, &q, a_first, b_first, rates, false)) return rc;
+    if (j.triples) {
+        if (j.seed || j.exclude_same) return fail(ctx, VDF_E_INVAL, "a triple list together with seed or exclude_same");
+        if (j.n_triples > vdf::kAlignRatesMaxTriples) return fail(ctx, VDF_E_INVAL, "more than 2^27 listed triples in one call");
+        size_t at = 0;
+        switch (vdf::align_rates_list_check(j.triples, j.n_triples, j.n_a, j.n_b, j.n_rates, &at)) {
+        case 1: return fail(ctx, VDF_E_INVAL, "the triple list is not strictly increasing in (rate, a, b) at entry " + std::to_string(at));
+        case 2: return fail(ctx, VDF_E_INVAL, "triple " + std::to_string(at) + " of the list names a video that does not exist");
+        case 4: return fail(ctx, VDF_E_INVAL, "triple " + std::to_string(at) + " of the list names a rate that is not in the rate list");
+        default: break;
+        }
+    }
+    if (int rc = align_stretches_checks(ctx, sj->max_stretches, sj->guard)) return rc;
+    if (ctx && !ctx->subs.empty()) return fail(ctx, VDF_E_INVAL, std::string(name) + " takes a single-device context");
+    return VDF_OK;
+}
+
+static vdf_alignment_rate_stretch rate_stretch_of(const vdf_alignment_rate &r, uint32_t rank)
+{
+    return vdf_alignment_rate_stretch{r.a, r.b, r.rate, r.first_a, r.first_b, r.n_windows, r.dist_sum, r.n_frames_b, rank};
+}
+
+int vdf_align_windows_rates_stretches_host(const vdf_align_rates_stretches_job *sj)
+{
+    if (!sj) return VDF_E_INVAL;
+    vdf::AlignSeedRate rates[VDF_WINDOWS_MAX_RATES];
+    if (int rc = align_rates_stretches_checks(nullptr, "vdf_align_windows_rates_stretches_host", sj, sj->a_first, sj->b_first, rates)) return rc;
+    const vdf_align_rates_job plain = align_rates_stretches_plain_job(sj), *j = &plain;
+    *j->n_out = 0;
+    if (j->n_a == 0 || j->n_b == 0 || (j->triples && j->n_triples == 0)) return VDF_OK;
+    const uint32_t tol = std::min<uint32_t>(j->tol_int, 1024u);
+    size_t found = 0;
+    // the definition for one triple: rank k on the matrix masked by the rectangles of ranks 0 ... k - 1
+    const auto triple = [&](uint32_t r, uint32_t a, uint32_t b) {
+        const uint32_t *fa = j->a_first + (size_t)r * (j->n_a + 1);
+        const size_t ra = (j->a_rate_first ? j->a_rate_first[r] : 0) + (size_t)fa[a], rb = j->b_first[b];
+        const uint32_t Na = fa[a + 1] - fa[a], Nb = j->b_first[b + 1] - j->b_first[b];
+        vdf::AlignRect rects[vdf::kAlignMaxStretches];
+        for (uint32_t rank = 0; rank < sj->max_stretches; rank++) {
+            vdf_alignment_retimed rec;
+            align_retimed_pair_masked_host(j->a_hashes + 16 * ra, Na, j->a_skip ? j->a_skip + ra : nullptr, j->b_hashes + 16 * rb, Nb,
+                                           j->b_skip ? j->b_skip + rb : nullptr, rates[r].num, rates[r].den, tol, j->min_run, rects, rank, &rec);
+            if (rec.n_windows == 0) return;
+            if (found < sj->capacity)
+                sj->out[found] = vdf_alignment_rate_stretch{a, b, r, rec.first_a, rec.first_b, rec.n_windows, rec.dist_sum, (rec.n_windows - 1) * rates[r].den + 16u, rank};
+            found++;
+            rects[rank] = vdf::align_rates_rect_of(rec.first_a, rec.first_b, rec.n_windows, rates[r].num, rates[r].den, sj->guard, Na, Nb);
+        }
+    };
+    if (j->triples) {
+        for (size_t i = 0; i < j->n_triples; i++) triple(j->triples[i].rate, j->triples[i].a, j->triples[i].b);
+    } else if (j->seed) {
+        std::vector<vdf_video_pair_rate> cand(1024);
+        size_t n_cand = 0;
+        vdf_align_seed_rates_job q = align_rates_seed_job(j);
+        for (int pass = 0; pass < 2; pass++) {  // its own capacity growth: the second pass has room for everything the first one counted
+            q.out = cand.data(); q.capacity = cand.size(); q.n_out = &n_cand;
+            if (int rc = vdf_align_seed_pairs_rates_host(&q)) return rc;
+            if (n_cand <= cand.size()) break;
+            cand.resize(n_cand);
+        }
+        for (size_t i = 0; i < n_cand; i++) triple(cand[i].rate, cand[i].a, cand[i].b);
+    } else {
+        for (uint32_t r = 0; r < j->n_rates; r++)
+            for (size_t a = 0; a < j->n_a; a++)
+                for (size_t b = 0; b < j->n_b; b++)
+                    if (!(j->exclude_same && a == b)) triple(r, (uint32_t)a, (uint32_t)b);
+    }
+    *sj->n_out = found;
+    return VDF_OK;
+}
+
+// one round of a chunk: the round's one upload, the band walk (masked from round 1 on) and the reductions; *total = the round's records, of
+// which the first min(*total, limit) come down into recs
+static int align_rates_run_round(vdf_ctx *ctx, vdf::AlignRatesLaunch L, vdf::AlignRatesRound &round, const vdf::AlignRatesTable &table, size_t limit,
+                                 std::vector<vdf_alignment_rate> &recs, uint32_t *total, hipStream_t s)
+{
+    const size_t n_triples = round.chunk.n_triples(), n_units = round.chunk.n_units();
+    const size_t plan_bytes = vdf::align_rates_round_plan_bytes(n_triples, round.n_rects);
+    VDF_HIP(ctx, ctx->align_plan.reserve(plan_bytes));
+    VDF_HIP(ctx, ctx->align_scratch.reserve(vdf::align_rates_scratch_bytes(n_triples, n_units)));
+    VDF_HIP(ctx, hipMemcpyAsync(ctx->align_plan.p, vdf::align_rates_round_seal(round, table), plan_bytes, hipMemcpyHostToDevice, s));
+    vdf_alignment_rate *d_dense = nullptr;
+    uint32_t *d_total = nullptr;
+    L.plan = ctx->align_plan.p;
+    L.n_triples = (uint32_t)n_triples; L.n_units = (uint32_t)n_units;
+    L.scratch = ctx->align_scratch.p; L.dense_out = &d_dense; L.total_out = &d_total;
+    if (round.n_rects) VDF_HIP(ctx, vdf::launch_align_rates_masked_chunk(L, round.n_rects, s));
+    else VDF_HIP(ctx, vdf::launch_align_rates_chunk(L, s));
+    *total = 0;
+    VDF_HIP(ctx, hipMemcpyAsync(total, d_total, sizeof(*total), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));  // also: the round's plan is free to change
+    if (*total > n_triples) return fail(ctx, VDF_E_HIP, "align rates: more records than triples");
+    recs.resize(std::min<size_t>(*total, limit));
+    if (!recs.empty()) {
+        VDF_HIP(ctx, hipMemcpyAsync(recs.data(), d_dense, recs.size() * sizeof(vdf_alignment_rate), hipMemcpyDeviceToHost, s));
+        VDF_HIP(ctx, hipStreamSynchronize(s));
+    }
+    return VDF_OK;
+}
+
+// align_rates_locked with rounds.  Per chunk: round 0 is the plain launch; round k walks the masked kernel on the triples that had a record in
+// round k - 1 (align_rates_stretch_plan.h), until a round has no record or max_stretches rounds have run; the rounds are merged into (rate, a, b,
+// rank) order.  Chunks arrive in (rate, a, b) order and each is finished before the next, so the first `capacity` records of the call are the ones
+// written.  The seed pass runs once, in front of everything.  The rank is added here, on the host: the rounds scatter vdf_alignment_rate records.
+static int align_rates_stretches_locked(vdf_ctx *ctx, const vdf_align_rates_stretches_job *sj, const vdf::AlignSeedRate *rates, const uint64_t *d_a_hashes,
+                                        const uint8_t *d_a_skip, const uint32_t *d_a_first, const uint32_t *h_first_a, uint64_t a_shift, const uint64_t *d_b_hashes,
+                                        const uint8_t *d_b_skip, const uint32_t *d_b_first, const uint32_t *h_first_b, hipStream_t s)
+{
+    const vdf_align_rates_job plain = align_rates_stretches_plain_job(sj), *j = &plain;
+    std::vector<vdf_video_pair_rate> cand;
+    const vdf_video_pair_rate *list = j->triples;
+    size_t n_list = j->n_triples;
+    if (!list && j->seed) {
+        const vdf_align_seed_rates_job q = align_rates_seed_job(j);
+        if (int rc = align_seed_rates_locked(ctx, &q, rates, d_a_hashes, d_a_skip, h_first_a, a_shift, d_b_hashes, d_b_skip, h_first_b, 0, s, &cand)) return rc;
+        if (cand.empty()) return VDF_OK;
+        list = cand.data();
+        n_list = cand.size();
+    }
+    const vdf::AlignRatesTable table = vdf::align_rates_table(rates, j->n_rates, j->a_rate_first, j->n_a, a_shift);
+    vdf::AlignRatesLaunch L{};
+    L.a_hashes = reinterpret_cast<const uint32_t *>(d_a_hashes); L.a_first = d_a_first; L.a_skip = d_a_skip;
+    L.b_hashes = reinterpret_cast<const uint32_t *>(d_b_hashes); L.b_first = d_b_first; L.b_skip = d_b_skip;
+    L.tol = std::min<uint32_t>(j->tol_int, 1024u); L.min_run = j->min_run;
+    vdf::AlignRatesCursor cur;
+    vdf::AlignRatesRound round, next;
+    std::vector<std::vector<vdf_alignment_rate>> rounds;
+    size_t found = 0, list_at = 0;
+    while (list ? vdf::align_rates_next_chunk_triples(h_first_a, j->n_a, h_first_b, list, n_list, rates, list_at, round.chunk)
+                : vdf::align_rates_next_chunk(h_first_a, j->n_a, h_first_b, j->n_b, rates, j->n_rates, j->exclude_same != 0, cur, round.chunk)) {
+        round.rects.clear();
+        round.n_rects = 0;
+        rounds.clear();
+        size_t uncopied = 0;  // max_stretches == 1: the records behind the capacity are counted, not fetched
+        for (uint32_t r = 0;; r++) {
+            rounds.emplace_back();
+            uint32_t total = 0;
+            const bool last = r + 1 >= sj->max_stretches;
+            const size_t room = sj->capacity > found ? sj->capacity - found : 0;
+            if (int rc = align_rates_run_round(ctx, L, round, table, last && r == 0 ? room : ~(size_t)0, rounds.back(), &total, s)) return rc;
+            uncopied = total - rounds.back().size();
+            if (!vdf::align_rates_more_rounds(r, total, sj->max_stretches)) break;
+            if (!vdf::align_rates_next_round(round, rounds.back().data(), rounds.back().size(), h_first_a, j->n_a, h_first_b, rates, sj->guard, next))
+                return fail(ctx, VDF_E_HIP, "align rates: a round's records do not belong to its triples");
+            std::swap(round, next);
+        }
+        std::vector<size_t> at(rounds.size(), 0);
+        for (const vdf_alignment_rate &r0 : rounds[0]) {
+            if (found < sj->capacity) sj->out[found] = rate_stretch_of(r0, 0);
+            found++;
+            for (size_t r = 1; r < rounds.size(); r++) {
+                if (at[r] == rounds[r].size()) break;
+                const vdf_alignment_rate &x = rounds[r][at[r]];
+                if (x.rate != r0.rate || x.a != r0.a || x.b != r0.b) break;
+                if (found < sj->capacity) sj->out[found] = rate_stretch_of(x, (uint32_t)r);
+                found++;
+                at[r]++;
+            }
+        }
+        found += uncopied;
+    }
+    *sj->n_out = found;
+    return VDF_OK;
+}
+
+int vdf_align_windows_rates_stretches_device(vdf_ctx *ctx, const vdf_align_rates_stretches_job *j)
+{
+    if (!ctx || !j) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    vdf::AlignSeedRate rates[VDF_WINDOWS_MAX_RATES];
+    // everything that can be said without the first arrays - the multi-GPU refusal last; then they come down and are checked
+    if (int rc = align_rates_stretches_checks(ctx, "vdf_align_windows_rates_stretches_device", j, nullptr, nullptr, rates)) return rc;
+    *j->n_out = 0;
+    if (j->n_a == 0 || j->n_b == 0 || (j->triples && j->n_triples == 0)) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = j->stream ? (hipStream_t)j->stream : ctx->stream;
+    std::vector<uint32_t> fa((size_t)j->n_rates * (j->n_a + 1)), fb(j->n_b + 1);
+    VDF_HIP(ctx, hipMemcpyAsync(fa.data(), j->a_first, fa.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipMemcpyAsync(fb.data(), j->b_first, fb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    VDF_HIP(ctx, hipStreamSynchronize(s));
+    if (int rc = align_rates_stretches_checks(ctx, "vdf_align_windows_rates_stretches_device", j, fa.data(), fb.data(), rates)) return rc;
+    return align_rates_stretches_locked(ctx, j, rates, j->a_hashes, j->a_skip, j->a_first, fa.data(), 0, j->b_hashes, j->b_skip, j->b_first, fb.data(), s);
+}
+
+// Host arrays: vdf_align_windows_rates' upload - the rows of A that the blocks span, the rows of B, [first a | first b, rebased | skip a | skip b]
+// in align_up - made ONCE, for the seed pass and every round.
+int vdf_align_windows_rates_stretches(vdf_ctx *ctx, const vdf_align_rates_stretches_job *j)
+{
+    if (!ctx || !j) return VDF_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    vdf::AlignSeedRate rates[VDF_WINDOWS_MAX_RATES];
+    if (int rc = align_rates_stretches_checks(ctx, "vdf_align_windows_rates_stretches", j, j->a_first, j->b_first, rates)) return rc;
+    *j->n_out = 0;
+    if (j->n_a == 0 || j->n_b == 0 || (j->triples && j->n_triples == 0)) return VDF_OK;
+    uint64_t a_lo = ~0ull, a_hi = 0;
+    for (uint32_t r = 0; r < j->n_rates; r++) {
+        const uint32_t *fa = j->a_first + (size_t)r * (j->n_a + 1);
+        const uint64_t base = j->a_rate_first ? (uint64_t)j->a_rate_first[r] : 0ull;
+        a_lo = std::min(a_lo, base + fa[0]);
+        a_hi = std::max(a_hi, base + fa[j->n_a]);
+    }
+    const uint64_t b_lo = j->b_first[0], b_hi = j->b_first[j->n_b];
+    const size_t wa = (size_t)(a_hi - a_lo), wb = (size_t)(b_hi - b_lo);
+    if (wa == 0 || wb == 0) return VDF_OK;
+    VDF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    std::vector<uint32_t> fb(j->n_b + 1);
+    for (size_t v = 0; v <= j->n_b; v++) fb[v] = j->b_first[v] - j->b_first[0];
+    const size_t fa_bytes = (size_t)j->n_rates * (j->n_a + 1) * sizeof(uint32_t), fb_bytes = fb.size() * sizeof(uint32_t);
+    const size_t ska = j->a_skip ? (wa + 3) & ~(size_t)3 : 0, skb = j->b_skip ? wb : 0;
+    VDF_HIP(ctx, ctx->align_up.reserve(fa_bytes + fb_bytes + ska + skb + 16));
+    char *up = ctx->align_up.as<char>();
+    VDF_HIP(ctx, hipMemcpyAsync(up, j->a_first, fa_bytes, hipMemcpyHostToDevice, s));
+    VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes, fb.data(), fb_bytes, hipMemcpyHostToDevice, s));
+    if (ska) VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes + fb_bytes, j->a_skip + a_lo, wa, hipMemcpyHostToDevice, s));
+    if (skb) VDF_HIP(ctx, hipMemcpyAsync(up + fa_bytes + fb_bytes + ska, j->b_skip + b_lo, wb, hipMemcpyHostToDevice, s));
+    if (int rc = upload(ctx, ctx->up_hashes, j->a_hashes + 16 * (size_t)a_lo, wa * 16 * sizeof(uint64_t), s)) return rc;
+    if (int rc = upload(ctx, ctx->up_ref_hashes, j->b_hashes + 16 * (size_t)b_lo, wb * 16 * sizeof(uint64_t), s)) return rc;
+    return align_rates_stretches_locked(ctx, j, rates, ctx->up_hashes.as<uint64_t>(), ska ? reinterpret_cast<const uint8_t *>(up + fa_bytes + fb_bytes) : nullptr,
+                                        reinterpret_cast<const uint32_t *>(up), j->a_first, a_lo, ctx->up_ref_hashes.as<uint64_t>(),
+                                        skb ? reinterpret_cast<const uint8_t *>(up + fa_bytes + fb_bytes + ska) : nullptr,
+                                        reinterpret_cast<const uint32_t *>(up + fa_bytes), fb.data(), s);
 }
 
 size_t vdf_hash_window_count(uint32_t frames_per_clip, uint32_t window_stride) { return vdf::window_count(frames_per_clip, window_stride); }

@@ -17,6 +17,7 @@
 #include "align_plan.h"
 #include "align_retimed_plan.h"
 #include "align_rates_plan.h"
+#include "align_rates_stretch_plan.h"
 
 namespace vdf {
 
@@ -406,5 +407,9 @@ struct AlignRatesLaunch {
     uint32_t **total_out;
 };
 hipError_t launch_align_rates_chunk(const AlignRatesLaunch &L, hipStream_t stream);
+// A masked round of such a chunk (align_rates_stretch_plan.h: AlignRatesRound): L as above on the round's triples, L.plan the round's
+// upload with n_rects rectangles per triple behind unit_offset (align_rates_round_plan_bytes), n_rects in 1 ... kAlignMaxStretches - 1.  The same
+// scratch and the same 32-byte records: the rank is the round's number.
+hipError_t launch_align_rates_masked_chunk(const AlignRatesLaunch &L, uint32_t n_rects, hipStream_t stream);
 
 }  // namespace vdf

@@ -553,6 +553,47 @@ def align_windows_rates_host(a_hashes, a_first, b_hashes, b_first, rates, tol_in
     return out[:min(n.value, out.size)], int(n.value)
 
 
+# one record of the stretches call over (rate, a, b) triples (include/vdf.h: vdf_alignment_rate_stretch, 36 bytes)
+ALIGN_RATE_STRETCH_DTYPE = _capi.ALIGN_RATE_STRETCH_DTYPE
+
+
+def _align_rates_stretches_job(a_hashes, a_first, n_a, a_rate_first, a_skip, b_hashes, b_first, n_b, b_skip, rates, tol_int, min_run, triples, seed, exclude_same,
+                               max_stretches, guard, capacity, stream=0):
+    """(job, out, n, what the job points into): the job of vdf_align_windows_rates_stretches[_host|_device] - _align_rates_job with max_stretches, guard
+    and the 36-byte records."""
+    num, den = _align_rates(rates)
+    rf = None if a_rate_first is None else np.ascontiguousarray(a_rate_first, dtype=np.uintp).reshape(-1)
+    if rf is not None and rf.size < min(len(num), _capi.WINDOWS_MAX_RATES):
+        raise ValueError("a_rate_first has an entry per rate")
+    t = None if triples is None else video_pair_rates(triples)
+    out = np.zeros(max(int(capacity), 0), ALIGN_RATE_STRETCH_DTYPE)
+    n = C.c_size_t(0)
+    # an empty list must not read as "no list": numpy gives an empty array a non-null address
+    job = _capi.VdfAlignRatesStretchesJob(a_hashes or None, a_first or None, rf.ctypes.data if rf is not None else None, a_skip or None, int(n_a), b_hashes or None,
+                                          b_first or None, b_skip or None, int(n_b), len(num), num.ctypes.data if len(num) else None,
+                                          den.ctypes.data if len(num) else None, _align_uint32("tol_int", tol_int), _align_uint32("min_run", min_run),
+                                          None if t is None else (t.ctypes.data or out.ctypes.data or num.ctypes.data), 0 if t is None else t.size,
+                                          1 if seed else 0, 1 if exclude_same else 0, _align_uint32("max_stretches", max_stretches), _align_uint32("guard", guard),
+                                          out.ctypes.data if out.size else None, out.size, C.pointer(n), stream or None)
+    return job, out, n, (num, den, rf, t)
+
+
+def align_windows_rates_stretches_host(a_hashes, a_first, b_hashes, b_first, rates, tol_int: int = 350, min_run: int = 1, max_stretches: int = 4, guard: int = 15,
+                                       a_rate_first=None, a_skip=None, b_skip=None, triples=None, seed: bool = False, exclude_same: bool = False,
+                                       capacity: int = 1024):
+    """vdf_align_windows_rates_stretches_host: EVERY stretch of every (rate, a, b) triple, ranked - align_windows_rates_host's record as rank 0, then per
+    rank the best record of the triple's matrix with the rectangles of the ranks before it masked, in the rows of the two videos and so in every
+    phase; guard counts rows of B.  The definition in plain C++ on the CPU; arguments as align_windows_rates_host.
+    -> (records [min(found, capacity)] of ALIGN_RATE_STRETCH_DTYPE in (rate, a, b, rank) order, and found)."""
+    keep, args = _seed_rates_host_args(a_hashes, a_first, a_rate_first, a_skip, b_hashes, b_first, b_skip, len(rates))
+    job, out, n, keep2 = _align_rates_stretches_job(rates=rates, a_rate_first=a_rate_first, tol_int=tol_int, min_run=min_run, triples=triples, seed=seed,
+                                                    exclude_same=exclude_same, max_stretches=max_stretches, guard=guard, capacity=capacity, **args)
+    rc = _capi.load().vdf_align_windows_rates_stretches_host(C.byref(job))
+    if rc != _capi.VDF_OK:
+        raise VdfError(rc, "vdf_align_windows_rates_stretches_host: bad argument")
+    return out[:min(n.value, out.size)], int(n.value)
+
+
 # one (variant, a, b) triple (include/vdf.h: vdf_video_pair_variant, 12 bytes): what the seeded variants call returns and the variants-pairs calls take
 VIDEO_PAIR_VARIANT_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("variant", "<u4")])
 
@@ -1304,6 +1345,29 @@ class Engine:
         job, out, n, keep = _align_rates_job(d_a_hashes, d_a_first, n_a, a_rate_first, d_a_skip, d_b_hashes, d_b_first, n_b, d_b_skip, rates, tol_int, min_run,
                                              triples, seed, exclude_same, capacity, stream)
         self._check(self.lib.vdf_align_windows_rates_device(self.ctx, C.byref(job)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_rates_stretches(self, a_hashes, a_first, b_hashes, b_first, rates, tol_int: int = 350, min_run: int = 1, max_stretches: int = 4,
+                                      guard: int = 15, a_rate_first=None, a_skip=None, b_skip=None, triples=None, seed: bool = False,
+                                      exclude_same: bool = False, capacity: int = 1024):
+        """Every stretch of every (rate, a, b) triple, ranked, in ONE call (vdf_align_windows_rates_stretches): arguments and result as
+        align_windows_rates_stretches_host.  The arrays go up once, for the seed pass and every round; round k walks only the triples that had a
+        record in round k - 1.  found > capacity: call again with a larger capacity."""
+        keep, args = _seed_rates_host_args(a_hashes, a_first, a_rate_first, a_skip, b_hashes, b_first, b_skip, len(rates))
+        job, out, n, keep2 = _align_rates_stretches_job(rates=rates, a_rate_first=a_rate_first, tol_int=tol_int, min_run=min_run, triples=triples, seed=seed,
+                                                        exclude_same=exclude_same, max_stretches=max_stretches, guard=guard, capacity=capacity, **args)
+        self._check(self.lib.vdf_align_windows_rates_stretches(self.ctx, C.byref(job)))
+        return out[:min(n.value, out.size)], int(n.value)
+
+    def align_windows_rates_stretches_device(self, d_a_hashes: int, d_a_first: int, n_a: int, d_b_hashes: int, d_b_first: int, n_b: int, rates,
+                                             tol_int: int = 350, min_run: int = 1, max_stretches: int = 4, guard: int = 15, a_rate_first=None,
+                                             d_a_skip: int = 0, d_b_skip: int = 0, triples=None, seed: bool = False, exclude_same: bool = False,
+                                             capacity: int = 1024, stream: int = 0):
+        """The same on device arrays - d_a_first: n_rates x (n_a + 1) u32; rates, a_rate_first and triples stay HOST data; the records come back to
+        the host, the call is ordered on `stream` and waits for its own work."""
+        job, out, n, keep = _align_rates_stretches_job(d_a_hashes, d_a_first, n_a, a_rate_first, d_a_skip, d_b_hashes, d_b_first, n_b, d_b_skip, rates, tol_int,
+                                                       min_run, triples, seed, exclude_same, max_stretches, guard, capacity, stream)
+        self._check(self.lib.vdf_align_windows_rates_stretches_device(self.ctx, C.byref(job)))
         return out[:min(n.value, out.size)], int(n.value)
 
     def align_windows_pairs(self, a_hashes, a_first, pairs, b_hashes=None, b_first=None, tol_int: int = 350, min_run: int = 1, a_skip=None, b_skip=None,

@@ -994,6 +994,83 @@ public:
         }
     }
 
+    // ---- EVERY stretch of a retimed pair, ranked, at every rate of a list in one call ----
+    // align_windows_rates with up to max_stretches (1 ... 8) records per triple (vdf_align_windows_rates_stretches): rank 0 is that call's record;
+    // after every reported stretch its rectangle - in the rows of the two videos, widened by guard rows of b and ceil(guard num / den) of a -
+    // counts as non-matching in EVERY phase, and the next rank is the best record of what is left.  Records in (rate, a, b, rank) order.
+    static vdf_align_rates_stretches_job align_rates_stretches_job(const SeedRatesSides &s, const std::vector<uint8_t> *skip_a, const std::vector<uint8_t> *skip_b,
+                                                                   uint32_t tol_int, uint32_t min_run, uint32_t max_stretches, uint32_t guard,
+                                                                   const std::vector<vdf_video_pair_rate> *triples, bool seed, bool exclude_same,
+                                                                   std::vector<vdf_alignment_rate_stretch> &out, size_t *found)
+    {
+        std::vector<vdf_alignment_rate> none;
+        const vdf_align_rates_job q = align_rates_job(s, skip_a, skip_b, tol_int, min_run, triples, seed, exclude_same, none, found);
+        return vdf_align_rates_stretches_job{q.a_hashes, q.a_first, q.a_rate_first, q.a_skip, q.n_a, q.b_hashes, q.b_first, q.b_skip, q.n_b, q.n_rates, q.rate_num,
+                                             q.rate_den, tol_int, min_run, q.triples, q.n_triples, q.seed, q.exclude_same, max_stretches, guard, out.data(), out.size(),
+                                             found, nullptr};
+    }
+
+    // the definition in plain C++ on the CPU (vdf_align_windows_rates_stretches_host): no context, no GPU
+    static std::vector<vdf_alignment_rate_stretch> align_windows_rates_stretches_host(const std::vector<std::vector<std::vector<VideoHash>>> &windows_by_rate_a,
+                                                                                     const std::vector<std::vector<VideoHash>> &windows_b,
+                                                                                     const std::vector<std::pair<uint32_t, uint32_t>> &rates, uint32_t tol_int,
+                                                                                     uint32_t min_run = 1, uint32_t max_stretches = 4, uint32_t guard = 15,
+                                                                                     const std::vector<vdf_video_pair_rate> *triples = nullptr, bool seed = false,
+                                                                                     const std::vector<uint8_t> *skip_a = nullptr,
+                                                                                     const std::vector<uint8_t> *skip_b = nullptr, bool exclude_same = false)
+    {
+        const SeedRatesSides s(windows_by_rate_a, windows_b, rates);
+        std::vector<vdf_alignment_rate_stretch> out(1024);
+        for (;;) {
+            size_t found = 0;
+            const vdf_align_rates_stretches_job job = align_rates_stretches_job(s, skip_a, skip_b, tol_int, min_run, max_stretches, guard, triples, seed, exclude_same, out, &found);
+            if (vdf_align_windows_rates_stretches_host(&job) != VDF_OK)
+                throw std::invalid_argument("align_windows_rates_stretches: what align_windows_rates refuses, max_stretches outside 1 ... 8, or guard above 2^20");
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
+    // through a context (vdf_align_windows_rates_stretches): the host arrays go up once, for the seed pass and every round
+    static std::vector<vdf_alignment_rate_stretch> align_windows_rates_stretches(const std::vector<std::vector<std::vector<VideoHash>>> &windows_by_rate_a,
+                                                                                const std::vector<std::vector<VideoHash>> &windows_b,
+                                                                                const std::vector<std::pair<uint32_t, uint32_t>> &rates, uint32_t tol_int,
+                                                                                uint32_t min_run = 1, uint32_t max_stretches = 4, uint32_t guard = 15,
+                                                                                const std::vector<vdf_video_pair_rate> *triples = nullptr, bool seed = false,
+                                                                                const std::vector<uint8_t> *skip_a = nullptr, const std::vector<uint8_t> *skip_b = nullptr,
+                                                                                bool exclude_same = false, Context *ctx_opt = nullptr)
+    {
+        const SeedRatesSides s(windows_by_rate_a, windows_b, rates);
+        Context &ctx = ctx_opt ? *ctx_opt : Context::default_context();
+        std::vector<vdf_alignment_rate_stretch> out(1024);
+        for (;;) {
+            size_t found = 0;
+            const vdf_align_rates_stretches_job job = align_rates_stretches_job(s, skip_a, skip_b, tol_int, min_run, max_stretches, guard, triples, seed, exclude_same, out, &found);
+            const int rc = vdf_align_windows_rates_stretches(ctx.get(), &job);
+            if (rc == VDF_E_INVAL) throw std::invalid_argument(vdf_last_error(ctx.get()));
+            if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);
+        }
+    }
+
+    // The same on device memory (vdf_align_windows_rates_stretches_device): the job's hashes, first arrays and skip bytes are device pointers; rate_num,
+    // rate_den, a_rate_first and triples stay on the host; out, capacity and n_out of the job are set here.  The records come back to the host and
+    // the call waits for its own work on job.stream.
+    static std::vector<vdf_alignment_rate_stretch> align_windows_rates_stretches_device(Context &ctx, vdf_align_rates_stretches_job job)
+    {
+        std::vector<vdf_alignment_rate_stretch> out(1024);
+        for (;;) {
+            size_t found = 0;
+            job.out = out.data(); job.capacity = out.size(); job.n_out = &found;
+            const int rc = vdf_align_windows_rates_stretches_device(ctx.get(), &job);
+            if (rc == VDF_E_INVAL) throw std::invalid_argument(vdf_last_error(ctx.get()));
+            if (rc != VDF_OK) throw Error(Error::Device, vdf_last_error(ctx.get()));
+            if (found <= out.size()) { out.resize(found); return out; }
+            out.resize(found);  // the buffer was too small: once more with room for all
+        }
+    }
+
     // hash_windows with the zero plane of every window (vdf_hash_windows_u8_planes): the same words, and every VideoHash
     // carries zero() - what align_windows_variants needs of the flipped side.
     static std::vector<std::vector<VideoHash>> hash_windows_planes(const uint8_t *frames, size_t n_videos, uint32_t frames_per_video, uint32_t w, uint32_t h,
