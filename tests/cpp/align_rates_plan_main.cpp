@@ -2,7 +2,7 @@
 // -fsanitize=address,undefined by tests/test_align_rates_plan.py.  One call: 71 videos of A against 71 of B, 0 .. 70 windows each, with all of
 // 1/1, 2/1, 3/2, 5/4, 6/5, 31/16 and 32/17 in ONE rate list, the window counts of A another permutation of 0 .. 70 in every rate's block, every
 // block of A some rows into its rows, and the hashes cut off in front as a host-array call cuts them (so that a slot's row0 wraps).  Every unit
-// of every chunk is walked step by step and lane by lane as the kernel walks it (csrc/align.hip: align_bands_rates_kernel) - the triple from
+// of every chunk is walked step by step and lane by lane as the kernel walks it (csrc/align.hip: align_bands_kernel<AlignTripleUnits, false>) - the triple from
 // unit_offset, the slot from the triple, num / den / row0 / the row of a_first from the table - on a synthetic distance of the ABSOLUTE rows, and
 //   - every cell of every phase of every triple is visited exactly once;
 //   - no row is at or behind Na or Nb of the triple's own block;

@@ -2,7 +2,7 @@
 // -fsanitize=address,undefined by tests/test_align_rates_stretch_plan.py.  One call: 40 videos of A against 40 of B, 0 .. 70 windows each, with
 // 1/1, 2/1, 3/2, 6/5 and 32/17 in ONE rate list and another window count of A in every rate's block.  Every chunk runs rounds 0 .. 3: round 0 on
 // the chunk as align_rates_next_chunk made it, round k on what align_rates_next_round makes of round k - 1 and its records.  Every unit of every
-// round is walked step by step and lane by lane as the kernels walk it (csrc/align.hip: align_bands_rates_kernel, align_bands_rates_masked_kernel)
+// round is walked step by step and lane by lane as the kernels walk it (csrc/align.hip: align_bands_kernel<AlignTripleUnits, false>, align_bands_kernel<AlignTripleUnits, true>)
 // - the triple from unit_offset, the slot from the triple, the rectangles from the round's sealed UPLOAD, at the offset the launch reads them - and
 //   - every cell of every phase of every triple of the round is visited exactly once per round, masked or not;
 //   - a cell is a miss by masking in exactly the rounds behind its rectangle: the mask the walk reads from the upload equals, cell by cell, the

@@ -1,7 +1,7 @@
 // The planner of the retimed align calls (csrc/align_retimed_plan.h) replayed on the CPU, built with
 // -fsanitize=address,undefined by tests/test_align_retimed_plan.py.  For every (Na, Nb) in 0 .. 140 x 0 .. 140 and seven rates every unit
 // (phase, band) of the pair is walked step by step and lane by lane with the header's own functions - the kernel (csrc/align.hip:
-// align_bands_retimed_kernel) calls the same ones - on a synthetic distance function, and
+// align_bands_kernel<AlignPairUnits<true>, false>) calls the same ones - on a synthetic distance function, and
 //   - every cell of every phase's sub-matrix is visited exactly once, and nothing else;
 //   - no row index behind a visited cell reaches Na or Nb;
 //   - the band records, reduced by the header's two-level reduction, give the record of a brute-force twin that walks every diagonal of every

@@ -2,7 +2,7 @@
 // replayed on the CPU, built with -fsanitize=address,undefined by tests/test_align_stretch_plan.py.  For every (Na, Nb) in 0 .. 140 x 0 .. 140,
 // with stretches in every corner, on every edge and inside the matrix, at guards that clamp nowhere, somewhere and everywhere:
 //   - the rectangle rule: align_rect_of against the definition written out cell by cell, and at the ends of the 32-bit ranges (nothing wraps);
-//   - the band walk with the mask: the masked kernel's walk (csrc/align.hip: align_bands_masked_kernel), lane by lane with the header's own
+//   - the band walk with the mask: the masked kernel's walk (csrc/align.hip: align_bands_kernel<AlignPairUnits<false>, true>), lane by lane with the header's own
 //     functions, over a synthetic distance matrix with up to three rectangles, reduced over lanes and bands - against a direct walk of every
 //     diagonal in which a masked cell is a miss;
 //   - the round builder: for pair lists of mixed lengths in both modes, three rounds of survivors - their order, their unit offsets, exactly r
@@ -46,7 +46,7 @@ static void check_rect(const Stretch &s, uint32_t guard, uint32_t Na, uint32_t N
     (*rects)++;
 }
 
-// ---- the band walk with the mask: what align_bands_masked_kernel does, lane by lane --------------------------------------------------------------
+// ---- the band walk with the mask: what align_bands_kernel<AlignPairUnits<false>, true> does, lane by lane --------------------------------------------------------------
 static Run walk_bands(uint32_t Na, uint32_t Nb, const AlignRect *rects, uint32_t n_rects, uint32_t min_run, unsigned long long *steps)
 {
     AlignRect rc[kAlignMaxStretches - 1];  // the kernel's slots: those behind n_rects are empty

@@ -1,4 +1,4 @@
-"""vdf_align_windows_retimed[_device] and their _pairs forms (csrc/align.hip: align_bands_retimed_kernel and the two-level reduction)
+"""vdf_align_windows_retimed[_device] and their _pairs forms (csrc/align.hip: align_bands_kernel<AlignPairUnits<true>, false> and the two-level reduction)
 against the numpy twin of tests/retimedaligngen.py, records equal field for field and `found` equal: the device form on device arrays of exactly their
 size and the host-array form, on every problem tests/test_align_retimed_native_host.py gives the plain C++ definition - sub-matrices of 67 x 65 cells
 in three bands with the reload wrap, phases with p >= Na and empty videos, planted lines at the four matrix edges, on the two sides of a band

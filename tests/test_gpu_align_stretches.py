@@ -1,4 +1,4 @@
-"""vdf_align_windows_stretches[_device] (csrc/align.hip: align_bands_masked_kernel behind the plain kernel's round 0) against the numpy
+"""vdf_align_windows_stretches[_device] (csrc/align.hip: align_bands_kernel<AlignPairUnits<false>, true> behind the plain kernel's round 0) against the numpy
 twin of tests/stretchgen.py, records equal field for field: the device form on device arrays and the host-array form, on every problem
 tests/test_align_stretches_host.py gives the plain C++ definition - an ad break removed, a source used twice, two runs on one diagonal, static
 videos tiled rank by rank, slowly changing content with and without the guard, a rectangle across three bands and the 64-row reload wrap that

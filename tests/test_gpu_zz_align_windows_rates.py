@@ -1,4 +1,4 @@
-"""vdf_align_windows_rates[_device] (csrc/align.hip: align_bands_rates_kernel, align_reduce_rates_kernel and the 32-byte scatter on the plan of
+"""vdf_align_windows_rates[_device] (csrc/align.hip: align_bands_kernel<AlignTripleUnits, false>, align_reduce_rates_kernel and the 32-byte scatter on the plan of
 csrc/align_rates_plan.h) against the twin of tests/ratealigngen.py, records equal: the device form on device arrays and the
 host-array form, on the problems tests/test_align_windows_rates_host.py gives the plain C++ definition.  Four rates in one workgroup (a list whose
 first four triples are one unit each, at 1/1, 3/2, 6/5 and 32/17; videos of 1, 2, 3 and 130 windows against 1, 2 and 129, other counts per rate,

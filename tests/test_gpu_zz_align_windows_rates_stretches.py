@@ -1,4 +1,4 @@
-"""vdf_align_windows_rates_stretches[_device] (csrc/align.hip: align_bands_rates_masked_kernel behind the rates kernel's round 0, on the rounds of
+"""vdf_align_windows_rates_stretches[_device] (csrc/align.hip: align_bands_kernel<AlignTripleUnits, true> behind the rates kernel's round 0, on the rounds of
 csrc/align_rates_stretch_plan.h) against the plain C++ definition (vdf_align_windows_rates_stretches_host) and the numpy twin of
 tests/ratestretchgen.py, records equal: the device form on device arrays and the host-array form.  Four rates whose units share one workgroup,
 each wave with its own rectangles; a triple at 3/2 with 200 x 134 windows and tolerance 500 - three bands per phase, a rectangle across the band

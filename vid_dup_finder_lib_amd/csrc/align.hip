@@ -2,8 +2,8 @@
 // (include/vdf.h: vdf_align_windows[_device]).  The answer is a reduction along the diagonals of each pair's distance
 // matrix, so nothing here emits a hit list and the cost does not depend on how dense the matches are.
 //
-// align_bands_kernel (and align_bands_masked_kernel, the same walk with the cells of a pair's rectangles as misses: DESIGN.md 4.12): one wave
-// per (pair, band of 64 diagonals d0 ... d0 + 63), four waves per workgroup.  The wave walks ka upward:
+// align_bands_kernel<Unit, MASKED>: ONE band walk for every alignment call.  One wave per unit = band of 64 diagonals d0 ... d0 + 63 of one
+// sub-matrix, four waves per workgroup.  The wave walks ka upward:
 //   - the row of A is wave-uniform: scalar loads, the SGPR operand of v_xor_b32, v_bcnt_u32_b32 accumulates - the inner loop of the
 //     VALU search backend (hamming.hip: hamming_tile_kernel), 64 VALU lane-ops per cell;
 //   - lane kb mod 64 keeps row kb of B in 32 VGPRs; the 64 rows a step needs slide by one per step, so one lane reloads one row
@@ -11,23 +11,27 @@
 //   - the run state of a diagonal (length, dist_sum) moves one lane up per step: two wave rotates (ds_bpermute_b32), the only cross-lane traffic.
 //     No LDS, no carry between waves: a diagonal never leaves its wave;
 //   - a run ends at a non-matching cell or at the matrix edge; the lane that sees the end folds it into its own best.
-// The lane-ownership rules are align_plan.h's (shared with the CPU replay in tests/cpp/align_plan_main.cpp).
-// align_reduce_kernel / align_scan_kernel / align_scatter_kernel: the bands of each pair -> one record, the pairs that have one -> a
-// dense list in (a, b) order (flag + scan: the pairs of a chunk are enumerated in that order).
-// align_seed_kernel / align_seed_count_kernel / align_seed_scatter_kernel, at the end of the file: which pairs of videos can have a record at
-// all (vdf_align_seed_pairs*), so that the band kernels run on those pairs only.
-// align_class_layout_kernel / align_seed_variants_kernel / align_seed_variants_scatter_kernel, behind them: the same question against the
-// mirrored, flipped and reversed variants of B, every requested variant from one pass over the seeds (vdf_align_seed_pairs_variants*;
-// DESIGN.md 4.14; window_class_layout.h).
-// align_bands_retimed_kernel / align_reduce_retimed_kernel, behind launch_align_chunk: the band walk on the strided rows of a phase's sub-matrix
-// and the two-level reduction bands -> phase-best -> pair record (vdf_align_windows_retimed*; align_retimed_plan.h).
-// align_bands_rates_kernel / align_reduce_rates_kernel / align_scatter_rates_kernel, behind launch_align_retimed_chunk: the retimed walk on
-// (rate, a, b) triples of up to 8 rates in one launch, the rate looked up per wave (vdf_align_windows_rates*; align_rates_plan.h).
-// align_bands_rates_masked_kernel, behind launch_align_rates_chunk: the rates kernel's walk with the cells of a triple's rectangles - kept in rows
-// of the two videos, so that they mask every phase - as misses: the rounds r >= 1 of vdf_align_windows_rates_stretches* (DESIGN.md 4.24;
-// align_rates_stretch_plan.h).
+// The lane-ownership rules are align_plan.h's (shared with the CPU replay in tests/cpp/align_plan_main.cpp).  What differs between the calls
+// lies in front of the loop and is a Unit policy's:
+//   - AlignPairUnits<false>: (pair, band) on the pair's own matrix - vdf_align_windows* and, MASKED (the cells of a pair's rectangles are
+//     misses), the rounds r >= 1 of vdf_align_windows_stretches* (DESIGN.md 4.12);
+//   - AlignPairUnits<true>: (pair, phase, band) on the strided rows of a phase's sub-matrix at the call's one rate - vdf_align_windows_retimed*
+//     (align_retimed_plan.h);
+//   - AlignTripleUnits: (triple, phase, band), the rate looked up per wave from the triple's slot - vdf_align_windows_rates* (DESIGN.md 4.23;
+//     align_rates_plan.h) and, MASKED with rectangles in rows of the two videos so that they mask every phase, the rounds r >= 1 of
+//     vdf_align_windows_rates_stretches* (align_rates_stretch_plan.h).
+// Why the walk is a __global__ template with its text inside it, and not a device function that five kernels call: DESIGN.md 4.25.
+// align_run_chunk: ONE chunk pipeline - the walk in launch cuts, the call's reduction (align_reduce_kernel: the bands of a pair -> one record;
+// align_reduce_retimed_kernel / align_reduce_rates_kernel: bands -> phase-best -> record), align_scan_kernel and align_scatter_kernel<Record>: the
+// items that have a record -> a dense list in the chunk's order (flag + scan).
+// align_seed_kernel / align_seed_count_kernel / align_seed_scatter_kernel: which pairs of videos can have a record at all (vdf_align_seed_pairs*;
+// DESIGN.md 4.13), so that the walk runs on those pairs only.
+// align_class_layout_kernel / align_seed_variants_kernel / align_seed_variants_scatter_kernel: the same question against the mirrored, flipped and
+// reversed variants of B, every requested variant from one pass over the seeds (vdf_align_seed_pairs_variants*; DESIGN.md 4.14;
+// window_class_layout.h).
 // align_seed_rates_kernel, at the very end: the seed pass of the retimed alignment, every phase of up to 8 rates on gathered rows of B
-// (vdf_align_seed_pairs_rates*; align_seed_rates_plan.h).
+// (vdf_align_seed_pairs_rates*; align_seed_rates_plan.h).  It is align_seed_kernel's body, and a COPY of it on purpose: folded into
+// one template the two instantiations with 14 check words did not keep the parent's seed loop.
 #include "align_plan.h"
 #include "align_rates_stretch_plan.h"
 #include "align_retimed_plan.h"
@@ -59,141 +63,129 @@ __device__ __forceinline__ void align_load_row(uint32_t (&rw)[32], const uint32_
     }
 }
 
-__global__ __launch_bounds__(256) void align_bands_kernel(
-    const uint32_t *__restrict__ a_hashes, const uint32_t *__restrict__ a_first, const uint8_t *__restrict__ a_skip,
-    const uint32_t *__restrict__ b_hashes, const uint32_t *__restrict__ b_first, const uint8_t *__restrict__ b_skip,
-    const AlignPair *__restrict__ pairs, const uint32_t *__restrict__ unit_offset, uint32_t n_pairs, uint32_t n_units, uint32_t tol,
-    uint32_t min_run, AlignBandRecord *__restrict__ band_records, uint32_t group_base)
+// ---- the units of a walk: what a wave finds in front of the loop ---------------------------------------------------------------------------------
+// What every walk's kernel reads.  n_items counts the chunk's pairs or triples (unit_offset has n_items + 1 entries); rects / n_rects are read by
+// the masked instantiations only: item i has n_rects rectangles at rects[i * n_rects] (align_plan.h: AlignRect).
+struct AlignBandsArgs {
+    const uint32_t *a_hashes, *a_first;
+    const uint8_t *a_skip;
+    const uint32_t *b_hashes, *b_first;
+    const uint8_t *b_skip;
+    const uint32_t *unit_offset;
+    uint32_t n_items, n_units, tol, min_run;
+    AlignBandRecord *band_records;
+    const AlignRect *rects;
+    uint32_t n_rects;
+};
+// where a unit's walk runs: its item, the first rows of its videos, the sub-matrix (Na x Nb cells, cell (i, j) = row phase + num i of a, row den j
+// of b) and its band.  Everything is wave-uniform and stays in SGPRs.
+struct AlignUnitAt { uint32_t item, fa, fb, Na, Nb, phase, num, den, band; };
+
+// Pair units.  RETIMED false: (pair, band) on the pair's whole matrix (vdf_align_windows*; masked: the rounds r >= 1 of
+// vdf_align_windows_stretches*) - the identity mapping is a compile-time fact, so that no multiply is left in the walk.
+// RETIMED true: (pair, phase, band) at the call's one rate num / den (vdf_align_windows_retimed*; align_retimed_plan.h).
+template <bool RETIMED> struct AlignPairUnits {
+    static constexpr bool kRetimed = RETIMED;
+    struct Args : AlignBandsArgs {  // every instantiation carries num, den, rects and n_rects, read or not: the SGPR counts were matched on this layout
+        const AlignPair *pairs;
+        uint32_t num, den;  // read if RETIMED
+    };
+    static __device__ __forceinline__ AlignUnitAt locate(const Args &k, uint32_t unit)
+    {
+        const uint32_t p = align_unit_pair((align_u32_ptr)(uintptr_t)k.unit_offset, k.n_items, unit);
+        const uint32_t u = unit - ((align_u32_ptr)(uintptr_t)k.unit_offset)[p];
+        const uint32_t va = ((align_u32_ptr)(uintptr_t)k.pairs)[2 * p], vb = ((align_u32_ptr)(uintptr_t)k.pairs)[2 * p + 1];
+        const uint32_t fa = ((align_u32_ptr)(uintptr_t)k.a_first)[va], Na_all = ((align_u32_ptr)(uintptr_t)k.a_first)[va + 1] - fa;
+        const uint32_t fb = ((align_u32_ptr)(uintptr_t)k.b_first)[vb], Nb_all = ((align_u32_ptr)(uintptr_t)k.b_first)[vb + 1] - fb;
+        if (!RETIMED) return AlignUnitAt{p, fa, fb, Na_all, Nb_all, 0u, 1u, 1u, u};
+        uint32_t phase, band;
+        align_retimed_unit(align_retimed_split(Na_all, Nb_all, k.num, k.den), u, &phase, &band);
+        return AlignUnitAt{p, fa, fb, align_retimed_na(Na_all, k.num, phase), align_retimed_nb(Nb_all, k.den), phase, k.num, k.den, band};
+    }
+};
+
+// Triple units: (triple, phase, band), the triple names its rate (vdf_align_windows_rates*; masked: the rounds r >= 1 of
+// vdf_align_windows_rates_stretches*; align_rates_plan.h).  (a, b, rate) come by scalar loads from the chunk's triple array
+// (vdf_video_pair_rate's layout), and num, den, the block's first row and its row of a_first come by one scalar load from the slot's 16 bytes of
+// the table (AlignRatesSlot).  The table sits in the chunk's one upload, in front of the triples, not in the kernel arguments: indexed by a
+// run-time slot, a by-value array can end up in scratch, and an s_load from memory cannot.  The slot is uniform per WAVE, not per workgroup - the
+// four waves of a workgroup serve four units that may belong to four rates - so it and everything derived from it (num, den, phase, Na, Nb, d0,
+// the row of A) stay in SGPRs: `unit` is built from readfirstlane(wave) and blockIdx, and every load on it is a scalar load.
+struct AlignTripleUnits {
+    static constexpr bool kRetimed = true;
+    struct Args : AlignBandsArgs {
+        const AlignRatesSlot *table;
+        const AlignRatesTriple *triples;
+    };
+    static __device__ __forceinline__ AlignUnitAt locate(const Args &k, uint32_t unit)
+    {
+        const uint32_t t = align_unit_pair((align_u32_ptr)(uintptr_t)k.unit_offset, k.n_items, unit);
+        align_u32_ptr tp = (align_u32_ptr)(uintptr_t)k.triples + (size_t)t * 3;
+        const uint32_t va = tp[0], vb = tp[1];
+        const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)tp[2]);  // < kAlignRatesMax: the host's planner wrote it
+        align_u32_ptr sp = (align_u32_ptr)(uintptr_t)k.table + (size_t)slot * 4;
+        const uint32_t num = sp[0], den = sp[1], row0 = sp[2];
+        align_u32_ptr af = (align_u32_ptr)(uintptr_t)k.a_first + sp[3];      // the slot's row of a_first
+        const uint32_t fa = row0 + af[va], Na_all = af[va + 1] - af[va];     // 32-bit sum: a row of the hashes the kernel sees (AlignRatesSlot)
+        const uint32_t fb = ((align_u32_ptr)(uintptr_t)k.b_first)[vb], Nb_all = ((align_u32_ptr)(uintptr_t)k.b_first)[vb + 1] - fb;
+        uint32_t phase, band;
+        align_retimed_unit(align_retimed_split(Na_all, Nb_all, num, den), unit - ((align_u32_ptr)(uintptr_t)k.unit_offset)[t], &phase, &band);
+        return AlignUnitAt{t, fa, fb, align_retimed_na(Na_all, num, phase), align_retimed_nb(Nb_all, den), phase, num, den, band};
+    }
+};
+
+// the row of b behind row kb of the sub-matrix: den kb, or - the identity - kb itself in its own signed type, which the plain walk indexes with
+__device__ __forceinline__ int32_t align_row_b(std::false_type, uint32_t, int32_t kb) { return kb; }
+__device__ __forceinline__ uint32_t align_row_b(std::true_type, uint32_t den, int32_t kb) { return align_retimed_row_b(den, (uint32_t)kb); }
+
+// ---- the band walk, once -----------------------------------------------------------------------------------------------------------------------
+// The walk's text stays inside this __global__ template: moved into an inlined device function it compiles to a slower inner product (DESIGN.md
+// 4.25).  ka, kb, d0, the lanes, the rotation and the reload are in sub-matrix coordinates; the rows behind a cell are ra = phase + num ka
+// (wave-uniform: scalar loads) and rb = den kb, and the skip bytes are read at those same rows - A's with the aligned dword that holds it, which
+// the stride lands on any of its four bytes.  The band record holds (offset = j - i, i0, n, sum) of the sub-matrix; the phases meet in the
+// reduction.  MASKED: the cells of the item's rectangles are misses.  The rectangles are in ROWS OF THE TWO VIDEOS, so a stretch found in one
+// phase masks its neighbourhood in every phase: a cell is masked iff one rectangle holds ra and rb.  They are wave-uniform: scalar loads into
+// SGPRs in front of the walk (the slots behind n_rects are empty rectangles), the test on ra is scalar, and the test on rb - two compares per
+// rectangle and lane - runs only in steps whose ra lies in a rectangle's rows of A.  A lane whose kb is outside the sub-matrix has row_ok false:
+// what the test makes of its rb is not used.  The branch holds nothing else: the rotates and the reload run in every step.
+template <class Unit, bool MASKED>
+__global__ __launch_bounds__(256) void align_bands_kernel(typename Unit::Args k, uint32_t group_base)
 {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t unit = (blockIdx.x + group_base) * kAlignWaves + wave;  // grids above 2^32 work-items are launched in cuts
-    if (unit >= n_units) return;
+    if (unit >= k.n_units) return;
 
-    const uint32_t p = align_unit_pair((align_u32_ptr)(uintptr_t)unit_offset, n_pairs, unit);
-    const uint32_t band = unit - ((align_u32_ptr)(uintptr_t)unit_offset)[p];
-    const uint32_t va = ((align_u32_ptr)(uintptr_t)pairs)[2 * p], vb = ((align_u32_ptr)(uintptr_t)pairs)[2 * p + 1];
-    const uint32_t fa = ((align_u32_ptr)(uintptr_t)a_first)[va], Na = ((align_u32_ptr)(uintptr_t)a_first)[va + 1] - fa;
-    const uint32_t fb = ((align_u32_ptr)(uintptr_t)b_first)[vb], Nb = ((align_u32_ptr)(uintptr_t)b_first)[vb + 1] - fb;
-    const int32_t d0 = align_band_d0(Na, band);
-    const uint32_t ka0 = align_ka_begin(d0), ka1 = align_ka_end(Na, Nb, d0);
-
-    const uint32_t *b_rows = b_hashes + (size_t)fb * 32;
-    const uint8_t *b_sk = b_skip ? b_skip + fb : nullptr;
-    align_u32_ptr a_rows = (align_u32_ptr)(uintptr_t)a_hashes + (size_t)fa * 32;
-
-    // this lane's row of B; cells outside the matrix are misses and no address is formed for them
-    uint32_t rw[32];
-    int32_t kb = align_lane_row(lane, ka0, d0);
-    bool row_ok = kb >= 0 && kb < (int32_t)Nb;
-    uint32_t row_skip = 0;  // the row's skip byte: compared where the row is used, so that the load is not waited for where it is issued
-    if (row_ok) {
-        if (b_sk) row_skip = b_sk[kb];
-        align_load_row(rw, b_rows, (uint32_t)kb);
-    } else {
-#pragma unroll
-        for (int q = 0; q < 32; q++) rw[q] = 0u;
-    }
-
-    uint32_t len = 0, sum = 0;                                              // the run of the diagonal this lane is on
-    uint32_t best_score = 0, best_start = 0, best_n = 0, best_sum = 0;     // score 0 = none: every run scores at least 1
-    int32_t best_off = 0;
-    for (uint32_t ka = ka0; ka < ka1; ++ka) {
-        align_u32_ptr ap = a_rows + (size_t)ka * 32;
-        uint32_t d = 0;
-#pragma unroll
-        for (int w = 0; w < 32; ++w) d += __builtin_popcount(rw[w] ^ ap[w]);  // ap[w]: SGPR
-        bool a_ok = true;  // wave-uniform: the skip byte of A's row comes with the aligned dword that holds it, by a scalar load like the row
-        if (a_skip) {
-            const uintptr_t at = (uintptr_t)a_skip + fa + ka;
-            a_ok = ((*(align_u32_ptr)(at & ~(uintptr_t)3) >> (8 * (uint32_t)(at & 3))) & 0xFFu) == 0u;
-        }
-        const bool match = row_ok && row_skip == 0 && a_ok && d <= tol;
-        if (match) { len += 1; sum += d; }
-        const bool edge = ka + 1 == Na || kb + 1 == (int32_t)Nb;              // the diagonal's last cell
-        const bool ends = len != 0 && (!match || edge);
-        if (__builtin_amdgcn_ballot_w64(ends) != 0ull) {
-            if (ends && len >= min_run) {
-                const uint32_t score = len * (tol + 1) - sum;
-                const uint32_t start = (match ? ka + 1 : ka) - len;
-                const int32_t off = kb - (int32_t)ka;
-                if (align_better(score, off, start, best_score, best_off, best_start)) {
-                    best_score = score; best_off = off; best_start = start; best_n = len; best_sum = sum;
-                }
-            }
-            if (ends) { len = 0; sum = 0; }
-        }
-        // the state follows its diagonal one lane up
-        len = align_rotate_up(len, lane);
-        sum = align_rotate_up(sum, lane);
-        // the lane whose diagonal d0 is done takes the row of diagonal d0 + 63 of the next step
-        if (ka + 1 < ka1 && lane == align_reload_lane(ka, d0)) {
-            kb += (int32_t)kAlignBand;  // = align_reload_row(ka, d0) >= 1, from the lane's own register: the address stays a vector address
-            row_ok = kb < (int32_t)Nb;
-            row_skip = 0;
-            if (row_ok) {
-                if (b_sk) row_skip = b_sk[kb];
-                align_load_row(rw, b_rows, (uint32_t)kb);
-            }
-        }
-    }
-
-    // the wave's best of its 64 lane-bests; every run has its own (score, offset, start)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t o_score = (uint32_t)__shfl_xor((int)best_score, o, 64), o_start = (uint32_t)__shfl_xor((int)best_start, o, 64);
-        const uint32_t o_n = (uint32_t)__shfl_xor((int)best_n, o, 64), o_sum = (uint32_t)__shfl_xor((int)best_sum, o, 64);
-        const int32_t o_off = __shfl_xor(best_off, o, 64);
-        if (align_better(o_score, o_off, o_start, best_score, best_off, best_start)) {
-            best_score = o_score; best_off = o_off; best_start = o_start; best_n = o_n; best_sum = o_sum;
-        }
-    }
-    if (lane == 0) band_records[unit] = AlignBandRecord{best_off, best_start, best_score ? best_n : 0u, best_sum};
-}
-
-// The plain kernel's walk with the cells of the pair's rectangles as misses: the rounds r >= 1 of vdf_align_windows_stretches* (DESIGN.md 4.12).
-// A kernel of its own, so that the plain kernel's text and code stay what they were.  The unit's pair has n_rects = r rectangles at
-// rects[pair * n_rects] (align_plan.h: AlignRect).  They are wave-uniform: scalar loads into SGPRs before the walk (the slots behind n_rects
-// are empty rectangles), the ka test of a step is scalar, and the kb test - two compares per rectangle and lane - runs only in steps whose ka
-// lies in a rectangle's rows of A.  The branch holds nothing else: the rotates and the reload run in every step as in the plain kernel.
-__global__ __launch_bounds__(256) void align_bands_masked_kernel(
-    const uint32_t *__restrict__ a_hashes, const uint32_t *__restrict__ a_first, const uint8_t *__restrict__ a_skip,
-    const uint32_t *__restrict__ b_hashes, const uint32_t *__restrict__ b_first, const uint8_t *__restrict__ b_skip,
-    const AlignPair *__restrict__ pairs, const uint32_t *__restrict__ unit_offset, uint32_t n_pairs, uint32_t n_units, uint32_t tol,
-    uint32_t min_run, AlignBandRecord *__restrict__ band_records, uint32_t group_base, const AlignRect *__restrict__ rects, uint32_t n_rects)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t unit = (blockIdx.x + group_base) * kAlignWaves + wave;  // grids above 2^32 work-items are launched in cuts
-    if (unit >= n_units) return;
-
-    const uint32_t p = align_unit_pair((align_u32_ptr)(uintptr_t)unit_offset, n_pairs, unit);
-    const uint32_t band = unit - ((align_u32_ptr)(uintptr_t)unit_offset)[p];
-    const uint32_t va = ((align_u32_ptr)(uintptr_t)pairs)[2 * p], vb = ((align_u32_ptr)(uintptr_t)pairs)[2 * p + 1];
-    const uint32_t fa = ((align_u32_ptr)(uintptr_t)a_first)[va], Na = ((align_u32_ptr)(uintptr_t)a_first)[va + 1] - fa;
-    const uint32_t fb = ((align_u32_ptr)(uintptr_t)b_first)[vb], Nb = ((align_u32_ptr)(uintptr_t)b_first)[vb + 1] - fb;
-    const int32_t d0 = align_band_d0(Na, band);
+    const AlignUnitAt at_unit = Unit::locate(k, unit);
+    const uint32_t fa = at_unit.fa, fb = at_unit.fb, Na = at_unit.Na, Nb = at_unit.Nb, phase = at_unit.phase, num = at_unit.num, den = at_unit.den;
+    const uint32_t tol = k.tol, min_run = k.min_run;
+    const uint8_t *a_skip = k.a_skip;
+    constexpr std::integral_constant<bool, Unit::kRetimed> retimed{};
+    const int32_t d0 = align_band_d0(Na, at_unit.band);
     const uint32_t ka0 = align_ka_begin(d0), ka1 = align_ka_end(Na, Nb, d0);
     AlignRect rc[kAlignMaxStretches - 1];
-    align_u32_ptr rp = (align_u32_ptr)(uintptr_t)rects + (size_t)p * n_rects * 4;
+    if (MASKED) {
+        align_u32_ptr rp = (align_u32_ptr)(uintptr_t)k.rects + (size_t)at_unit.item * k.n_rects * 4;
 #pragma unroll
-    for (uint32_t i = 0; i < kAlignMaxStretches - 1; i++) {
-        if (i < n_rects) rc[i] = AlignRect{rp[4 * i], rp[4 * i + 1], rp[4 * i + 2], rp[4 * i + 3]};
-        else rc[i] = AlignRect{0u, 0u, 0u, 0u};
+        for (uint32_t i = 0; i < kAlignMaxStretches - 1; i++) {
+            if (i < k.n_rects) rc[i] = AlignRect{rp[4 * i], rp[4 * i + 1], rp[4 * i + 2], rp[4 * i + 3]};
+            else rc[i] = AlignRect{0u, 0u, 0u, 0u};
+        }
     }
 
-    const uint32_t *b_rows = b_hashes + (size_t)fb * 32;
-    const uint8_t *b_sk = b_skip ? b_skip + fb : nullptr;
-    align_u32_ptr a_rows = (align_u32_ptr)(uintptr_t)a_hashes + (size_t)fa * 32;
+    const uint32_t *b_rows = k.b_hashes + (size_t)fb * 32;
+    const uint8_t *b_sk = k.b_skip ? k.b_skip + fb : nullptr;
+    align_u32_ptr a_rows = (align_u32_ptr)(uintptr_t)k.a_hashes + (size_t)fa * 32;
 
-    // this lane's row of B; cells outside the matrix are misses and no address is formed for them
+    // this lane's row of B; cells outside the sub-matrix are misses and no address is formed for them
     uint32_t rw[32];
     int32_t kb = align_lane_row(lane, ka0, d0);
     bool row_ok = kb >= 0 && kb < (int32_t)Nb;
     uint32_t row_skip = 0;  // the row's skip byte: compared where the row is used, so that the load is not waited for where it is issued
     if (row_ok) {
-        if (b_sk) row_skip = b_sk[kb];
-        align_load_row(rw, b_rows, (uint32_t)kb);
+        const auto rb = align_row_b(retimed, den, kb);  // < Nb of the whole video
+        if (b_sk) row_skip = b_sk[rb];
+        align_load_row(rw, b_rows, (uint32_t)rb);
     } else {
 #pragma unroll
         for (int q = 0; q < 32; q++) rw[q] = 0u;
@@ -203,20 +195,23 @@ __global__ __launch_bounds__(256) void align_bands_masked_kernel(
     uint32_t best_score = 0, best_start = 0, best_n = 0, best_sum = 0;     // score 0 = none: every run scores at least 1
     int32_t best_off = 0;
     for (uint32_t ka = ka0; ka < ka1; ++ka) {
-        align_u32_ptr ap = a_rows + (size_t)ka * 32;
+        const uint32_t ra = Unit::kRetimed ? align_retimed_row_a(phase, num, ka) : ka;  // < Na of the whole video, wave-uniform
+        align_u32_ptr ap = a_rows + (size_t)ra * 32;
         uint32_t d = 0;
 #pragma unroll
         for (int w = 0; w < 32; ++w) d += __builtin_popcount(rw[w] ^ ap[w]);  // ap[w]: SGPR
         bool a_ok = true;  // wave-uniform: the skip byte of A's row comes with the aligned dword that holds it, by a scalar load like the row
         if (a_skip) {
-            const uintptr_t at = (uintptr_t)a_skip + fa + ka;
+            const uintptr_t at = (uintptr_t)a_skip + fa + ra;
             a_ok = ((*(align_u32_ptr)(at & ~(uintptr_t)3) >> (8 * (uint32_t)(at & 3))) & 0xFFu) == 0u;
         }
         bool match = row_ok && row_skip == 0 && a_ok && d <= tol;
-        bool in_a = false;  // wave-uniform
+        if (MASKED) {
+            bool in_a = false;  // wave-uniform: the rectangles and ra are
 #pragma unroll
-        for (uint32_t i = 0; i < kAlignMaxStretches - 1; i++) in_a = in_a || align_rect_has_a(rc[i], ka);
-        if (in_a) match = match && !align_cell_masked(rc, kAlignMaxStretches - 1, ka, (uint32_t)kb);
+            for (uint32_t i = 0; i < kAlignMaxStretches - 1; i++) in_a = in_a || align_rect_has_a(rc[i], ra);
+            if (in_a) match = match && !align_cell_masked(rc, kAlignMaxStretches - 1, ra, (uint32_t)align_row_b(retimed, den, kb));
+        }
         if (match) { len += 1; sum += d; }
         const bool edge = ka + 1 == Na || kb + 1 == (int32_t)Nb;              // the diagonal's last cell
         const bool ends = len != 0 && (!match || edge);
@@ -240,8 +235,9 @@ __global__ __launch_bounds__(256) void align_bands_masked_kernel(
             row_ok = kb < (int32_t)Nb;
             row_skip = 0;
             if (row_ok) {
-                if (b_sk) row_skip = b_sk[kb];
-                align_load_row(rw, b_rows, (uint32_t)kb);
+                const auto rb = align_row_b(retimed, den, kb);
+                if (b_sk) row_skip = b_sk[rb];
+                align_load_row(rw, b_rows, (uint32_t)rb);
             }
         }
     }
@@ -256,7 +252,7 @@ __global__ __launch_bounds__(256) void align_bands_masked_kernel(
             best_score = o_score; best_off = o_off; best_start = o_start; best_n = o_n; best_sum = o_sum;
         }
     }
-    if (lane == 0) band_records[unit] = AlignBandRecord{best_off, best_start, best_score ? best_n : 0u, best_sum};
+    if (lane == 0) k.band_records[unit] = AlignBandRecord{best_off, best_start, best_score ? best_n : 0u, best_sum};
 }
 
 __device__ __forceinline__ uint32_t align_block_rank(bool has, uint32_t *s_wave, uint32_t *block_total)
@@ -323,12 +319,14 @@ __global__ __launch_bounds__(1024) void align_scan_kernel(const uint32_t *__rest
     if (tid == 1023) *total = s_part[1023];
 }
 
-__global__ __launch_bounds__(256) void align_scatter_kernel(const vdf_alignment *__restrict__ pair_records, uint32_t n_pairs,
-                                                            const uint32_t *__restrict__ block_offset, vdf_alignment *__restrict__ out)
+// the records with n_windows != 0, in their order; Record: vdf_alignment, vdf_alignment_retimed or vdf_alignment_rate
+template <class Record>
+__global__ __launch_bounds__(256) void align_scatter_kernel(const Record *__restrict__ pair_records, uint32_t n_pairs,
+                                                            const uint32_t *__restrict__ block_offset, Record *__restrict__ out)
 {
     __shared__ uint32_t s_wave[4];
     const uint32_t p = blockIdx.x * 256 + threadIdx.x;
-    vdf_alignment r{};
+    Record r{};
     if (p < n_pairs) r = pair_records[p];
     const bool has = r.n_windows != 0;
     uint32_t total;
@@ -342,147 +340,59 @@ size_t align_scratch_bytes(size_t n_pairs, size_t n_units)
     return n_units * sizeof(AlignBandRecord) + 2 * n_pairs * sizeof(vdf_alignment) + (2 * n_blocks + 4) * sizeof(uint32_t) + 64;
 }
 
-hipError_t launch_align_chunk(const AlignLaunch &L, hipStream_t stream)
+// One chunk of any alignment call: the band walk of k's units in launch cuts, the call's own reduction - reduce(band_records, item_records,
+// block_count, n_blocks) launches it: one thread per item, block_count[g] = the items of workgroup g with a record - then the scan and the
+// scatter.  k.band_records is set here.  Record is the call's record type; align_scratch_bytes / align_rates_scratch_bytes size the scratch.
+template <class Unit, bool MASKED, class Record, class Reduce>
+static hipError_t align_run_chunk(typename Unit::Args k, void *scratch, Record **dense_out, uint32_t **total_out, hipStream_t stream, Reduce reduce)
 {
-    if (L.n_pairs == 0 || L.n_units == 0 || L.n_rects >= kAlignMaxStretches || (L.n_rects && !L.rects)) return hipErrorInvalidValue;
-    // scratch: band records | pair records | dense records | block counts | block offsets | total
-    char *s = static_cast<char *>(L.scratch);
-    AlignBandRecord *band_records = reinterpret_cast<AlignBandRecord *>(s);
-    s += (size_t)L.n_units * sizeof(AlignBandRecord);
-    vdf_alignment *pair_records = reinterpret_cast<vdf_alignment *>(s);
-    s += (size_t)L.n_pairs * sizeof(vdf_alignment);
-    vdf_alignment *dense = reinterpret_cast<vdf_alignment *>(s);
-    s += (size_t)L.n_pairs * sizeof(vdf_alignment);
-    const uint32_t n_blocks = (L.n_pairs + 255) / 256;
+    // scratch: band records | item records | dense records | block counts | block offsets | total
+    char *s = static_cast<char *>(scratch);
+    k.band_records = reinterpret_cast<AlignBandRecord *>(s);
+    s += (size_t)k.n_units * sizeof(AlignBandRecord);
+    Record *item_records = reinterpret_cast<Record *>(s);
+    s += (size_t)k.n_items * sizeof(Record);
+    Record *dense = reinterpret_cast<Record *>(s);
+    s += (size_t)k.n_items * sizeof(Record);
+    const uint32_t n_blocks = (k.n_items + 255) / 256;
     uint32_t *block_count = reinterpret_cast<uint32_t *>(s), *block_offset = block_count + n_blocks, *total = block_offset + n_blocks;
 
-    const size_t n_groups = ((size_t)L.n_units + kAlignWaves - 1) / kAlignWaves;
+    const size_t n_groups = ((size_t)k.n_units + kAlignWaves - 1) / kAlignWaves;
     for (const AlignLaunchCut &cut : align_launch_cuts(n_groups)) {
-        if (L.n_rects)
-            hipLaunchKernelGGL(align_bands_masked_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_first, L.a_skip, L.b_hashes,
-                               L.b_first, L.b_skip, L.pairs, L.unit_offset, L.n_pairs, L.n_units, L.tol, L.min_run, band_records,
-                               (uint32_t)cut.group_base, L.rects, L.n_rects);
-        else
-            hipLaunchKernelGGL(align_bands_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_first, L.a_skip, L.b_hashes, L.b_first,
-                               L.b_skip, L.pairs, L.unit_offset, L.n_pairs, L.n_units, L.tol, L.min_run, band_records, (uint32_t)cut.group_base);
+        hipLaunchKernelGGL((align_bands_kernel<Unit, MASKED>), dim3((uint32_t)cut.n), dim3(256), 0, stream, k, (uint32_t)cut.group_base);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(align_reduce_kernel, dim3(n_blocks), dim3(256), 0, stream, L.pairs, L.unit_offset, L.n_pairs, L.tol, band_records, pair_records,
-                       block_count);
+    reduce(k.band_records, item_records, block_count, n_blocks);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     hipLaunchKernelGGL(align_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, n_blocks, block_offset, total);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(align_scatter_kernel, dim3(n_blocks), dim3(256), 0, stream, pair_records, L.n_pairs, block_offset, dense);
+    hipLaunchKernelGGL(align_scatter_kernel<Record>, dim3(n_blocks), dim3(256), 0, stream, item_records, k.n_items, block_offset, dense);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    *L.dense_out = dense;
-    *L.total_out = total;
+    *dense_out = dense;
+    *total_out = total;
     return hipSuccess;
 }
 
-// ---- retimed windows: every phase's sub-matrix of every pair in one launch (include/vdf.h: vdf_align_windows_retimed*; DESIGN.md 4.17) -----------
-// align_bands_retimed_kernel: the plain kernel's walk on the sub-matrix of one phase p of one pair (align_retimed_plan.h) - a kernel of its own,
-// so that the plain kernel's text and code stay what they were.  A unit is (pair, phase, band): one wave serves one band of 64 diagonals of
-// the Na_p x Nb_0 cells (i, j) = (row p + num i of a, row den j of b).  ka, kb, d0, the lanes, the rotation and the reload are the plain
-// kernel's in sub-matrix coordinates; only the addresses differ: the row of A at step ka is fa + p + num ka (wave-uniform: scalar loads),
-// lane kb mod 64 holds row fb + den kb, and the skip bytes are read at those same rows - A's with the aligned dword that holds it, which the
-// stride lands on any of its four bytes.  The band record holds (offset = j - i, i0, n, sum) of the sub-matrix; the phases meet in the reduction.
-__global__ __launch_bounds__(256) void align_bands_retimed_kernel(
-    const uint32_t *__restrict__ a_hashes, const uint32_t *__restrict__ a_first, const uint8_t *__restrict__ a_skip,
-    const uint32_t *__restrict__ b_hashes, const uint32_t *__restrict__ b_first, const uint8_t *__restrict__ b_skip,
-    const AlignPair *__restrict__ pairs, const uint32_t *__restrict__ unit_offset, uint32_t n_pairs, uint32_t n_units, uint32_t tol,
-    uint32_t min_run, AlignBandRecord *__restrict__ band_records, uint32_t group_base, uint32_t num, uint32_t den)
+static AlignBandsArgs align_pair_args(const AlignLaunch &L)
 {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t unit = (blockIdx.x + group_base) * kAlignWaves + wave;  // grids above 2^32 work-items are launched in cuts
-    if (unit >= n_units) return;
-
-    const uint32_t p = align_unit_pair((align_u32_ptr)(uintptr_t)unit_offset, n_pairs, unit);
-    const uint32_t va = ((align_u32_ptr)(uintptr_t)pairs)[2 * p], vb = ((align_u32_ptr)(uintptr_t)pairs)[2 * p + 1];
-    const uint32_t fa = ((align_u32_ptr)(uintptr_t)a_first)[va], Na_all = ((align_u32_ptr)(uintptr_t)a_first)[va + 1] - fa;
-    const uint32_t fb = ((align_u32_ptr)(uintptr_t)b_first)[vb], Nb_all = ((align_u32_ptr)(uintptr_t)b_first)[vb + 1] - fb;
-    uint32_t phase, band;
-    align_retimed_unit(align_retimed_split(Na_all, Nb_all, num, den), unit - ((align_u32_ptr)(uintptr_t)unit_offset)[p], &phase, &band);
-    const uint32_t Na = align_retimed_na(Na_all, num, phase), Nb = align_retimed_nb(Nb_all, den);  // the sub-matrix
-    const int32_t d0 = align_band_d0(Na, band);
-    const uint32_t ka0 = align_ka_begin(d0), ka1 = align_ka_end(Na, Nb, d0);
-
-    const uint32_t *b_rows = b_hashes + (size_t)fb * 32;
-    const uint8_t *b_sk = b_skip ? b_skip + fb : nullptr;
-    align_u32_ptr a_rows = (align_u32_ptr)(uintptr_t)a_hashes + (size_t)fa * 32;
-
-    // this lane's row of B; cells outside the sub-matrix are misses and no address is formed for them
-    uint32_t rw[32];
-    int32_t kb = align_lane_row(lane, ka0, d0);
-    bool row_ok = kb >= 0 && kb < (int32_t)Nb;
-    uint32_t row_skip = 0;  // the row's skip byte: compared where the row is used, so that the load is not waited for where it is issued
-    if (row_ok) {
-        const uint32_t rb = align_retimed_row_b(den, (uint32_t)kb);  // < Nb_all
-        if (b_sk) row_skip = b_sk[rb];
-        align_load_row(rw, b_rows, rb);
-    } else {
-#pragma unroll
-        for (int q = 0; q < 32; q++) rw[q] = 0u;
-    }
-
-    uint32_t len = 0, sum = 0;                                              // the run of the diagonal this lane is on
-    uint32_t best_score = 0, best_start = 0, best_n = 0, best_sum = 0;     // score 0 = none: every run scores at least 1
-    int32_t best_off = 0;
-    for (uint32_t ka = ka0; ka < ka1; ++ka) {
-        const uint32_t ra = align_retimed_row_a(phase, num, ka);  // < Na_all, wave-uniform
-        align_u32_ptr ap = a_rows + (size_t)ra * 32;
-        uint32_t d = 0;
-#pragma unroll
-        for (int w = 0; w < 32; ++w) d += __builtin_popcount(rw[w] ^ ap[w]);  // ap[w]: SGPR
-        bool a_ok = true;  // wave-uniform: the skip byte of A's row comes with the aligned dword that holds it, by a scalar load like the row
-        if (a_skip) {
-            const uintptr_t at = (uintptr_t)a_skip + fa + ra;
-            a_ok = ((*(align_u32_ptr)(at & ~(uintptr_t)3) >> (8 * (uint32_t)(at & 3))) & 0xFFu) == 0u;
-        }
-        const bool match = row_ok && row_skip == 0 && a_ok && d <= tol;
-        if (match) { len += 1; sum += d; }
-        const bool edge = ka + 1 == Na || kb + 1 == (int32_t)Nb;              // the diagonal's last cell
-        const bool ends = len != 0 && (!match || edge);
-        if (__builtin_amdgcn_ballot_w64(ends) != 0ull) {
-            if (ends && len >= min_run) {
-                const uint32_t score = len * (tol + 1) - sum;
-                const uint32_t start = (match ? ka + 1 : ka) - len;
-                const int32_t off = kb - (int32_t)ka;
-                if (align_better(score, off, start, best_score, best_off, best_start)) {
-                    best_score = score; best_off = off; best_start = start; best_n = len; best_sum = sum;
-                }
-            }
-            if (ends) { len = 0; sum = 0; }
-        }
-        // the state follows its diagonal one lane up
-        len = align_rotate_up(len, lane);
-        sum = align_rotate_up(sum, lane);
-        // the lane whose diagonal d0 is done takes the row of diagonal d0 + 63 of the next step
-        if (ka + 1 < ka1 && lane == align_reload_lane(ka, d0)) {
-            kb += (int32_t)kAlignBand;  // = align_reload_row(ka, d0) >= 1, from the lane's own register: the address stays a vector address
-            row_ok = kb < (int32_t)Nb;
-            row_skip = 0;
-            if (row_ok) {
-                const uint32_t rb = align_retimed_row_b(den, (uint32_t)kb);
-                if (b_sk) row_skip = b_sk[rb];
-                align_load_row(rw, b_rows, rb);
-            }
-        }
-    }
-
-    // the wave's best of its 64 lane-bests; every run has its own (score, offset, start)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t o_score = (uint32_t)__shfl_xor((int)best_score, o, 64), o_start = (uint32_t)__shfl_xor((int)best_start, o, 64);
-        const uint32_t o_n = (uint32_t)__shfl_xor((int)best_n, o, 64), o_sum = (uint32_t)__shfl_xor((int)best_sum, o, 64);
-        const int32_t o_off = __shfl_xor(best_off, o, 64);
-        if (align_better(o_score, o_off, o_start, best_score, best_off, best_start)) {
-            best_score = o_score; best_off = o_off; best_start = o_start; best_n = o_n; best_sum = o_sum;
-        }
-    }
-    if (lane == 0) band_records[unit] = AlignBandRecord{best_off, best_start, best_score ? best_n : 0u, best_sum};
+    return AlignBandsArgs{L.a_hashes, L.a_first, L.a_skip, L.b_hashes, L.b_first, L.b_skip, L.unit_offset, L.n_pairs, L.n_units, L.tol, L.min_run,
+                          nullptr, L.rects, L.n_rects};
 }
 
+hipError_t launch_align_chunk(const AlignLaunch &L, hipStream_t stream)
+{
+    if (L.n_pairs == 0 || L.n_units == 0 || L.n_rects >= kAlignMaxStretches || (L.n_rects && !L.rects)) return hipErrorInvalidValue;
+    using Unit = AlignPairUnits<false>;
+    const Unit::Args k{align_pair_args(L), L.pairs, 1u, 1u};
+    const auto reduce = [&](const AlignBandRecord *band_records, vdf_alignment *pair_records, uint32_t *block_count, uint32_t n_blocks) {
+        hipLaunchKernelGGL(align_reduce_kernel, dim3(n_blocks), dim3(256), 0, stream, L.pairs, L.unit_offset, L.n_pairs, L.tol, band_records, pair_records,
+                           block_count);
+    };
+    if (L.n_rects) return align_run_chunk<Unit, true>(k, L.scratch, L.dense_out, L.total_out, stream, reduce);
+    return align_run_chunk<Unit, false>(k, L.scratch, L.dense_out, L.total_out, stream, reduce);
+}
+
+// ---- retimed windows: every phase's sub-matrix of every pair in one launch (include/vdf.h: vdf_align_windows_retimed*; DESIGN.md 4.17) -----------
 // one thread per pair of the chunk: its bands -> the best of every phase (align_better) -> the best of the phase-bests (align_retimed_plan.h:
 // align_retimed_reduce, the text the plain C++ definition runs) -> pair_records (n_windows = 0: none); block_count[g] = pairs with a record
 __global__ __launch_bounds__(256) void align_reduce_retimed_kernel(const AlignPair *__restrict__ pairs, const uint32_t *__restrict__ unit_offset,
@@ -506,155 +416,21 @@ __global__ __launch_bounds__(256) void align_reduce_retimed_kernel(const AlignPa
     if (threadIdx.x == 0) block_count[blockIdx.x] = total;
 }
 
-// vdf_alignment_retimed is vdf_alignment with (first_a, first_b) where (offset, start_a) are: the scan and the scatter run on it as they are
-static_assert(sizeof(vdf_alignment_retimed) == sizeof(vdf_alignment) && offsetof(vdf_alignment_retimed, n_windows) == offsetof(vdf_alignment, n_windows),
-              "align_scatter_kernel reads n_windows of either record");
-
 hipError_t launch_align_retimed_chunk(const AlignLaunch &L, uint32_t num, uint32_t den, vdf_alignment_retimed **dense_out, hipStream_t stream)
 {
     if (L.n_pairs == 0 || L.n_units == 0 || L.n_rects || num == 0 || den == 0 || num > kAlignRetimedMaxNum) return hipErrorInvalidValue;
-    // scratch: band records | pair records | dense records | block counts | block offsets | total (align_scratch_bytes)
-    char *s = static_cast<char *>(L.scratch);
-    AlignBandRecord *band_records = reinterpret_cast<AlignBandRecord *>(s);
-    s += (size_t)L.n_units * sizeof(AlignBandRecord);
-    vdf_alignment_retimed *pair_records = reinterpret_cast<vdf_alignment_retimed *>(s);
-    s += (size_t)L.n_pairs * sizeof(vdf_alignment_retimed);
-    vdf_alignment_retimed *dense = reinterpret_cast<vdf_alignment_retimed *>(s);
-    s += (size_t)L.n_pairs * sizeof(vdf_alignment_retimed);
-    const uint32_t n_blocks = (L.n_pairs + 255) / 256;
-    uint32_t *block_count = reinterpret_cast<uint32_t *>(s), *block_offset = block_count + n_blocks, *total = block_offset + n_blocks;
-
-    const size_t n_groups = ((size_t)L.n_units + kAlignWaves - 1) / kAlignWaves;
-    for (const AlignLaunchCut &cut : align_launch_cuts(n_groups)) {
-        hipLaunchKernelGGL(align_bands_retimed_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_first, L.a_skip, L.b_hashes, L.b_first,
-                           L.b_skip, L.pairs, L.unit_offset, L.n_pairs, L.n_units, L.tol, L.min_run, band_records, (uint32_t)cut.group_base, num, den);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(align_reduce_retimed_kernel, dim3(n_blocks), dim3(256), 0, stream, L.pairs, L.unit_offset, L.n_pairs, L.a_first, L.b_first, num, den,
-                       L.tol, band_records, pair_records, block_count);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(align_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, n_blocks, block_offset, total);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(align_scatter_kernel, dim3(n_blocks), dim3(256), 0, stream, reinterpret_cast<const vdf_alignment *>(pair_records), L.n_pairs,
-                       block_offset, reinterpret_cast<vdf_alignment *>(dense));
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    *dense_out = dense;
-    *L.total_out = total;
-    return hipSuccess;
+    using Unit = AlignPairUnits<true>;
+    const Unit::Args k{align_pair_args(L), L.pairs, num, den};
+    return align_run_chunk<Unit, false>(
+        k, L.scratch, dense_out, L.total_out, stream,
+        [&](const AlignBandRecord *band_records, vdf_alignment_retimed *pair_records, uint32_t *block_count, uint32_t n_blocks) {
+            hipLaunchKernelGGL(align_reduce_retimed_kernel, dim3(n_blocks), dim3(256), 0, stream, L.pairs, L.unit_offset, L.n_pairs, L.a_first, L.b_first, num,
+                               den, L.tol, band_records, pair_records, block_count);
+        });
 }
 
-// ---- retimed windows at up to 8 rates: the triples of every rate in one launch (include/vdf.h: vdf_align_windows_rates*) ---------
-// align_bands_rates_kernel: align_bands_retimed_kernel's walk as a kernel of its own, so that the retimed kernel's text and code stay what they
-// were.  A unit is (triple, phase, band), and the triple names its rate: everything that differs lies in front of the loop.  The unit's triple
-// is found on unit_offset, (a, b, rate) come by scalar loads from the chunk's triple array (vdf_video_pair_rate's layout), and num, den, the
-// block's first row and its row of a_first come by one scalar load from the slot's 16 bytes of the table (align_rates_plan.h: AlignRatesSlot).
-// The table sits in the chunk's one upload, in front of the triples, not in the kernel arguments: indexed by a run-time slot, a by-value array
-// can end up in scratch, and an s_load from memory cannot.  The slot is uniform per WAVE, not per workgroup - the four waves of a workgroup
-// serve four units that may belong to four rates - so it and everything derived from it (num, den, phase, Na, Nb, d0, the row of A) stay in
-// SGPRs: `unit` is built from readfirstlane(wave) and blockIdx, and every load on it is a scalar load.  The loop body, the run state, the
-// reload, the skip-byte reads and the wave reduction are the retimed kernel's.  No LDS, no scratch, vector stores only.
-__global__ __launch_bounds__(256) void align_bands_rates_kernel(
-    const uint32_t *__restrict__ a_hashes, const uint32_t *__restrict__ a_first, const uint8_t *__restrict__ a_skip,
-    const uint32_t *__restrict__ b_hashes, const uint32_t *__restrict__ b_first, const uint8_t *__restrict__ b_skip,
-    const AlignRatesSlot *__restrict__ table, const AlignRatesTriple *__restrict__ triples, const uint32_t *__restrict__ unit_offset, uint32_t n_triples,
-    uint32_t n_units, uint32_t tol, uint32_t min_run, AlignBandRecord *__restrict__ band_records, uint32_t group_base)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t unit = (blockIdx.x + group_base) * kAlignWaves + wave;  // grids above 2^32 work-items are launched in cuts
-    if (unit >= n_units) return;
-
-    const uint32_t t = align_unit_pair((align_u32_ptr)(uintptr_t)unit_offset, n_triples, unit);
-    align_u32_ptr tp = (align_u32_ptr)(uintptr_t)triples + (size_t)t * 3;
-    const uint32_t va = tp[0], vb = tp[1];
-    const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)tp[2]);  // < kAlignRatesMax: the host's planner wrote it
-    align_u32_ptr sp = (align_u32_ptr)(uintptr_t)table + (size_t)slot * 4;
-    const uint32_t num = sp[0], den = sp[1], row0 = sp[2];
-    align_u32_ptr af = (align_u32_ptr)(uintptr_t)a_first + sp[3];       // the slot's row of a_first
-    const uint32_t fa = row0 + af[va], Na_all = af[va + 1] - af[va];     // 32-bit sum: a row of the hashes the kernel sees (AlignRatesSlot)
-    const uint32_t fb = ((align_u32_ptr)(uintptr_t)b_first)[vb], Nb_all = ((align_u32_ptr)(uintptr_t)b_first)[vb + 1] - fb;
-    uint32_t phase, band;
-    align_retimed_unit(align_retimed_split(Na_all, Nb_all, num, den), unit - ((align_u32_ptr)(uintptr_t)unit_offset)[t], &phase, &band);
-    const uint32_t Na = align_retimed_na(Na_all, num, phase), Nb = align_retimed_nb(Nb_all, den);  // the sub-matrix
-    const int32_t d0 = align_band_d0(Na, band);
-    const uint32_t ka0 = align_ka_begin(d0), ka1 = align_ka_end(Na, Nb, d0);
-
-    const uint32_t *b_rows = b_hashes + (size_t)fb * 32;
-    const uint8_t *b_sk = b_skip ? b_skip + fb : nullptr;
-    align_u32_ptr a_rows = (align_u32_ptr)(uintptr_t)a_hashes + (size_t)fa * 32;
-
-    // this lane's row of B; cells outside the sub-matrix are misses and no address is formed for them
-    uint32_t rw[32];
-    int32_t kb = align_lane_row(lane, ka0, d0);
-    bool row_ok = kb >= 0 && kb < (int32_t)Nb;
-    uint32_t row_skip = 0;  // the row's skip byte: compared where the row is used, so that the load is not waited for where it is issued
-    if (row_ok) {
-        const uint32_t rb = align_retimed_row_b(den, (uint32_t)kb);  // < Nb_all
-        if (b_sk) row_skip = b_sk[rb];
-        align_load_row(rw, b_rows, rb);
-    } else {
-#pragma unroll
-        for (int q = 0; q < 32; q++) rw[q] = 0u;
-    }
-
-    uint32_t len = 0, sum = 0;                                              // the run of the diagonal this lane is on
-    uint32_t best_score = 0, best_start = 0, best_n = 0, best_sum = 0;     // score 0 = none: every run scores at least 1
-    int32_t best_off = 0;
-    for (uint32_t ka = ka0; ka < ka1; ++ka) {
-        const uint32_t ra = align_retimed_row_a(phase, num, ka);  // < Na_all, wave-uniform
-        align_u32_ptr ap = a_rows + (size_t)ra * 32;
-        uint32_t d = 0;
-#pragma unroll
-        for (int w = 0; w < 32; ++w) d += __builtin_popcount(rw[w] ^ ap[w]);  // ap[w]: SGPR
-        bool a_ok = true;  // wave-uniform: the skip byte of A's row comes with the aligned dword that holds it, by a scalar load like the row
-        if (a_skip) {
-            const uintptr_t at = (uintptr_t)a_skip + fa + ra;
-            a_ok = ((*(align_u32_ptr)(at & ~(uintptr_t)3) >> (8 * (uint32_t)(at & 3))) & 0xFFu) == 0u;
-        }
-        const bool match = row_ok && row_skip == 0 && a_ok && d <= tol;
-        if (match) { len += 1; sum += d; }
-        const bool edge = ka + 1 == Na || kb + 1 == (int32_t)Nb;              // the diagonal's last cell
-        const bool ends = len != 0 && (!match || edge);
-        if (__builtin_amdgcn_ballot_w64(ends) != 0ull) {
-            if (ends && len >= min_run) {
-                const uint32_t score = len * (tol + 1) - sum;
-                const uint32_t start = (match ? ka + 1 : ka) - len;
-                const int32_t off = kb - (int32_t)ka;
-                if (align_better(score, off, start, best_score, best_off, best_start)) {
-                    best_score = score; best_off = off; best_start = start; best_n = len; best_sum = sum;
-                }
-            }
-            if (ends) { len = 0; sum = 0; }
-        }
-        // the state follows its diagonal one lane up
-        len = align_rotate_up(len, lane);
-        sum = align_rotate_up(sum, lane);
-        // the lane whose diagonal d0 is done takes the row of diagonal d0 + 63 of the next step
-        if (ka + 1 < ka1 && lane == align_reload_lane(ka, d0)) {
-            kb += (int32_t)kAlignBand;  // = align_reload_row(ka, d0) >= 1, from the lane's own register: the address stays a vector address
-            row_ok = kb < (int32_t)Nb;
-            row_skip = 0;
-            if (row_ok) {
-                const uint32_t rb = align_retimed_row_b(den, (uint32_t)kb);
-                if (b_sk) row_skip = b_sk[rb];
-                align_load_row(rw, b_rows, rb);
-            }
-        }
-    }
-
-    // the wave's best of its 64 lane-bests; every run has its own (score, offset, start)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t o_score = (uint32_t)__shfl_xor((int)best_score, o, 64), o_start = (uint32_t)__shfl_xor((int)best_start, o, 64);
-        const uint32_t o_n = (uint32_t)__shfl_xor((int)best_n, o, 64), o_sum = (uint32_t)__shfl_xor((int)best_sum, o, 64);
-        const int32_t o_off = __shfl_xor(best_off, o, 64);
-        if (align_better(o_score, o_off, o_start, best_score, best_off, best_start)) {
-            best_score = o_score; best_off = o_off; best_start = o_start; best_n = o_n; best_sum = o_sum;
-        }
-    }
-    if (lane == 0) band_records[unit] = AlignBandRecord{best_off, best_start, best_score ? best_n : 0u, best_sum};
-}
-
+// ---- retimed windows at up to 8 rates: the triples of every rate in one launch (include/vdf.h: vdf_align_windows_rates*), and
+// the masked rounds of vdf_align_windows_rates_stretches* (align_rates_stretch_plan.h) ------------------------------------------
 static_assert(sizeof(vdf_alignment_rate) == 32 && sizeof(AlignRatesTriple) == sizeof(vdf_video_pair_rate) &&
                   offsetof(AlignRatesTriple, a) == offsetof(vdf_video_pair_rate, a) && offsetof(AlignRatesTriple, b) == offsetof(vdf_video_pair_rate, b) &&
                   offsetof(AlignRatesTriple, rate) == offsetof(vdf_video_pair_rate, rate) && sizeof(AlignRatesSlot) == 16 && kAlignRatesMax == VDF_WINDOWS_MAX_RATES,
@@ -686,217 +462,37 @@ __global__ __launch_bounds__(256) void align_reduce_rates_kernel(const AlignRate
     if (threadIdx.x == 0) block_count[blockIdx.x] = total;
 }
 
-// align_scatter_kernel for the 32-byte records (that kernel is tied to vdf_alignment's 24 bytes and stays as it is)
-__global__ __launch_bounds__(256) void align_scatter_rates_kernel(const vdf_alignment_rate *__restrict__ triple_records, uint32_t n_triples,
-                                                                  const uint32_t *__restrict__ block_offset, vdf_alignment_rate *__restrict__ out)
+// a chunk over triples: L.plan is the chunk's one upload (table | triples | unit_offset, and | rects behind them in a masked round)
+template <bool MASKED> static hipError_t align_run_rates_chunk(const AlignRatesLaunch &L, uint32_t n_rects, hipStream_t stream)
 {
-    __shared__ uint32_t s_wave[4];
-    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
-    vdf_alignment_rate r{};
-    if (p < n_triples) r = triple_records[p];
-    const bool has = r.n_windows != 0;
-    uint32_t total;
-    const uint32_t rank = align_block_rank(has, s_wave, &total);
-    if (has) out[(size_t)block_offset[blockIdx.x] + rank] = r;
+    const char *plan = static_cast<const char *>(L.plan);
+    const AlignRatesSlot *table = reinterpret_cast<const AlignRatesSlot *>(plan);
+    const AlignRatesTriple *triples = reinterpret_cast<const AlignRatesTriple *>(plan + align_rates_plan_triples_at());
+    const uint32_t *unit_offset = reinterpret_cast<const uint32_t *>(plan + align_rates_plan_offsets_at(L.n_triples));
+    const AlignRect *rects = MASKED ? reinterpret_cast<const AlignRect *>(plan + align_rates_plan_rects_at(L.n_triples)) : nullptr;
+    const AlignTripleUnits::Args k{AlignBandsArgs{L.a_hashes, L.a_first, L.a_skip, L.b_hashes, L.b_first, L.b_skip, unit_offset, L.n_triples, L.n_units, L.tol,
+                                                  L.min_run, nullptr, rects, n_rects},
+                                   table, triples};
+    return align_run_chunk<AlignTripleUnits, MASKED>(
+        k, L.scratch, L.dense_out, L.total_out, stream,
+        [&](const AlignBandRecord *band_records, vdf_alignment_rate *triple_records, uint32_t *block_count, uint32_t n_blocks) {
+            hipLaunchKernelGGL(align_reduce_rates_kernel, dim3(n_blocks), dim3(256), 0, stream, table, triples, unit_offset, L.n_triples, L.a_first, L.b_first,
+                               L.tol, band_records, triple_records, block_count);
+        });
 }
 
 hipError_t launch_align_rates_chunk(const AlignRatesLaunch &L, hipStream_t stream)
 {
     if (L.n_triples == 0 || L.n_units == 0 || !L.plan) return hipErrorInvalidValue;
-    const char *plan = static_cast<const char *>(L.plan);
-    const AlignRatesSlot *table = reinterpret_cast<const AlignRatesSlot *>(plan);
-    const AlignRatesTriple *triples = reinterpret_cast<const AlignRatesTriple *>(plan + align_rates_plan_triples_at());
-    const uint32_t *unit_offset = reinterpret_cast<const uint32_t *>(plan + align_rates_plan_offsets_at(L.n_triples));
-    // scratch: band records | triple records | dense records | block counts | block offsets | total (align_rates_scratch_bytes)
-    char *s = static_cast<char *>(L.scratch);
-    AlignBandRecord *band_records = reinterpret_cast<AlignBandRecord *>(s);
-    s += (size_t)L.n_units * sizeof(AlignBandRecord);
-    vdf_alignment_rate *triple_records = reinterpret_cast<vdf_alignment_rate *>(s);
-    s += (size_t)L.n_triples * sizeof(vdf_alignment_rate);
-    vdf_alignment_rate *dense = reinterpret_cast<vdf_alignment_rate *>(s);
-    s += (size_t)L.n_triples * sizeof(vdf_alignment_rate);
-    const uint32_t n_blocks = (L.n_triples + 255) / 256;
-    uint32_t *block_count = reinterpret_cast<uint32_t *>(s), *block_offset = block_count + n_blocks, *total = block_offset + n_blocks;
-
-    const size_t n_groups = ((size_t)L.n_units + kAlignWaves - 1) / kAlignWaves;
-    for (const AlignLaunchCut &cut : align_launch_cuts(n_groups)) {
-        hipLaunchKernelGGL(align_bands_rates_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_first, L.a_skip, L.b_hashes, L.b_first,
-                           L.b_skip, table, triples, unit_offset, L.n_triples, L.n_units, L.tol, L.min_run, band_records, (uint32_t)cut.group_base);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(align_reduce_rates_kernel, dim3(n_blocks), dim3(256), 0, stream, table, triples, unit_offset, L.n_triples, L.a_first, L.b_first, L.tol,
-                       band_records, triple_records, block_count);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(align_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, n_blocks, block_offset, total);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(align_scatter_rates_kernel, dim3(n_blocks), dim3(256), 0, stream, triple_records, L.n_triples, block_offset, dense);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    *L.dense_out = dense;
-    *L.total_out = total;
-    return hipSuccess;
+    return align_run_rates_chunk<false>(L, 0, stream);
 }
 
-// The rates kernel's walk with the cells of the triple's rectangles as misses: the rounds r >= 1 of vdf_align_windows_rates_stretches* (DESIGN.md
-// 4.24).  A kernel of its own, so that the plain, masked, retimed and rates kernels keep their text and code.  The unit's triple has n_rects = r
-// rectangles at rects[triple * n_rects] (align_rates_stretch_plan.h), in ROWS OF THE TWO VIDEOS: [a_lo, a_hi) counts the rows of video a in the
-// slot's block, [b_lo, b_hi) the rows of video b.  A cell (ka, kb) of phase p's sub-matrix is masked iff one rectangle holds ra = p + num ka and
-// rb = den kb - so a stretch found in one phase masks its neighbourhood in every phase.  As in align_bands_masked_kernel the rectangles are
-// wave-uniform: scalar loads into SGPRs in front of the walk (the slots behind n_rects are empty rectangles), the test on ra is scalar, and the
-// test on rb - one multiply per lane, two compares per rectangle and lane - runs only in steps whose ra lies in a rectangle's rows of A.  A lane whose
-// kb is outside the sub-matrix has row_ok false: what the test makes of its rb is not used.  No LDS, no scratch, vector stores only.
-__global__ __launch_bounds__(256) void align_bands_rates_masked_kernel(
-    const uint32_t *__restrict__ a_hashes, const uint32_t *__restrict__ a_first, const uint8_t *__restrict__ a_skip,
-    const uint32_t *__restrict__ b_hashes, const uint32_t *__restrict__ b_first, const uint8_t *__restrict__ b_skip,
-    const AlignRatesSlot *__restrict__ table, const AlignRatesTriple *__restrict__ triples, const uint32_t *__restrict__ unit_offset, uint32_t n_triples,
-    uint32_t n_units, uint32_t tol, uint32_t min_run, AlignBandRecord *__restrict__ band_records, uint32_t group_base,
-    const AlignRect *__restrict__ rects, uint32_t n_rects)
-{
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t unit = (blockIdx.x + group_base) * kAlignWaves + wave;  // grids above 2^32 work-items are launched in cuts
-    if (unit >= n_units) return;
-
-    const uint32_t t = align_unit_pair((align_u32_ptr)(uintptr_t)unit_offset, n_triples, unit);
-    align_u32_ptr tp = (align_u32_ptr)(uintptr_t)triples + (size_t)t * 3;
-    const uint32_t va = tp[0], vb = tp[1];
-    const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)tp[2]);  // < kAlignRatesMax: the host's planner wrote it
-    align_u32_ptr sp = (align_u32_ptr)(uintptr_t)table + (size_t)slot * 4;
-    const uint32_t num = sp[0], den = sp[1], row0 = sp[2];
-    align_u32_ptr af = (align_u32_ptr)(uintptr_t)a_first + sp[3];       // the slot's row of a_first
-    const uint32_t fa = row0 + af[va], Na_all = af[va + 1] - af[va];     // 32-bit sum: a row of the hashes the kernel sees (AlignRatesSlot)
-    const uint32_t fb = ((align_u32_ptr)(uintptr_t)b_first)[vb], Nb_all = ((align_u32_ptr)(uintptr_t)b_first)[vb + 1] - fb;
-    uint32_t phase, band;
-    align_retimed_unit(align_retimed_split(Na_all, Nb_all, num, den), unit - ((align_u32_ptr)(uintptr_t)unit_offset)[t], &phase, &band);
-    const uint32_t Na = align_retimed_na(Na_all, num, phase), Nb = align_retimed_nb(Nb_all, den);  // the sub-matrix
-    const int32_t d0 = align_band_d0(Na, band);
-    const uint32_t ka0 = align_ka_begin(d0), ka1 = align_ka_end(Na, Nb, d0);
-    AlignRect rc[kAlignMaxStretches - 1];  // in rows of video a of the slot's block and rows of video b, not in sub-matrix cells
-    align_u32_ptr rp = (align_u32_ptr)(uintptr_t)rects + (size_t)t * n_rects * 4;
-#pragma unroll
-    for (uint32_t i = 0; i < kAlignMaxStretches - 1; i++) {
-        if (i < n_rects) rc[i] = AlignRect{rp[4 * i], rp[4 * i + 1], rp[4 * i + 2], rp[4 * i + 3]};
-        else rc[i] = AlignRect{0u, 0u, 0u, 0u};
-    }
-
-    const uint32_t *b_rows = b_hashes + (size_t)fb * 32;
-    const uint8_t *b_sk = b_skip ? b_skip + fb : nullptr;
-    align_u32_ptr a_rows = (align_u32_ptr)(uintptr_t)a_hashes + (size_t)fa * 32;
-
-    // this lane's row of B; cells outside the sub-matrix are misses and no address is formed for them
-    uint32_t rw[32];
-    int32_t kb = align_lane_row(lane, ka0, d0);
-    bool row_ok = kb >= 0 && kb < (int32_t)Nb;
-    uint32_t row_skip = 0;  // the row's skip byte: compared where the row is used, so that the load is not waited for where it is issued
-    if (row_ok) {
-        const uint32_t rb = align_retimed_row_b(den, (uint32_t)kb);  // < Nb_all
-        if (b_sk) row_skip = b_sk[rb];
-        align_load_row(rw, b_rows, rb);
-    } else {
-#pragma unroll
-        for (int q = 0; q < 32; q++) rw[q] = 0u;
-    }
-
-    uint32_t len = 0, sum = 0;                                              // the run of the diagonal this lane is on
-    uint32_t best_score = 0, best_start = 0, best_n = 0, best_sum = 0;     // score 0 = none: every run scores at least 1
-    int32_t best_off = 0;
-    for (uint32_t ka = ka0; ka < ka1; ++ka) {
-        const uint32_t ra = align_retimed_row_a(phase, num, ka);  // < Na_all, wave-uniform
-        align_u32_ptr ap = a_rows + (size_t)ra * 32;
-        uint32_t d = 0;
-#pragma unroll
-        for (int w = 0; w < 32; ++w) d += __builtin_popcount(rw[w] ^ ap[w]);  // ap[w]: SGPR
-        bool a_ok = true;  // wave-uniform: the skip byte of A's row comes with the aligned dword that holds it, by a scalar load like the row
-        if (a_skip) {
-            const uintptr_t at = (uintptr_t)a_skip + fa + ra;
-            a_ok = ((*(align_u32_ptr)(at & ~(uintptr_t)3) >> (8 * (uint32_t)(at & 3))) & 0xFFu) == 0u;
-        }
-        bool match = row_ok && row_skip == 0 && a_ok && d <= tol;
-        bool in_a = false;  // wave-uniform: the rectangles and ra are
-#pragma unroll
-        for (uint32_t i = 0; i < kAlignMaxStretches - 1; i++) in_a = in_a || align_rect_has_a(rc[i], ra);
-        if (in_a) match = match && !align_cell_masked(rc, kAlignMaxStretches - 1, ra, align_retimed_row_b(den, (uint32_t)kb));
-        if (match) { len += 1; sum += d; }
-        const bool edge = ka + 1 == Na || kb + 1 == (int32_t)Nb;              // the diagonal's last cell
-        const bool ends = len != 0 && (!match || edge);
-        if (__builtin_amdgcn_ballot_w64(ends) != 0ull) {
-            if (ends && len >= min_run) {
-                const uint32_t score = len * (tol + 1) - sum;
-                const uint32_t start = (match ? ka + 1 : ka) - len;
-                const int32_t off = kb - (int32_t)ka;
-                if (align_better(score, off, start, best_score, best_off, best_start)) {
-                    best_score = score; best_off = off; best_start = start; best_n = len; best_sum = sum;
-                }
-            }
-            if (ends) { len = 0; sum = 0; }
-        }
-        // the state follows its diagonal one lane up
-        len = align_rotate_up(len, lane);
-        sum = align_rotate_up(sum, lane);
-        // the lane whose diagonal d0 is done takes the row of diagonal d0 + 63 of the next step
-        if (ka + 1 < ka1 && lane == align_reload_lane(ka, d0)) {
-            kb += (int32_t)kAlignBand;  // = align_reload_row(ka, d0) >= 1, from the lane's own register: the address stays a vector address
-            row_ok = kb < (int32_t)Nb;
-            row_skip = 0;
-            if (row_ok) {
-                const uint32_t rb = align_retimed_row_b(den, (uint32_t)kb);
-                if (b_sk) row_skip = b_sk[rb];
-                align_load_row(rw, b_rows, rb);
-            }
-        }
-    }
-
-    // the wave's best of its 64 lane-bests; every run has its own (score, offset, start)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t o_score = (uint32_t)__shfl_xor((int)best_score, o, 64), o_start = (uint32_t)__shfl_xor((int)best_start, o, 64);
-        const uint32_t o_n = (uint32_t)__shfl_xor((int)best_n, o, 64), o_sum = (uint32_t)__shfl_xor((int)best_sum, o, 64);
-        const int32_t o_off = __shfl_xor(best_off, o, 64);
-        if (align_better(o_score, o_off, o_start, best_score, best_off, best_start)) {
-            best_score = o_score; best_off = o_off; best_start = o_start; best_n = o_n; best_sum = o_sum;
-        }
-    }
-    if (lane == 0) band_records[unit] = AlignBandRecord{best_off, best_start, best_score ? best_n : 0u, best_sum};
-}
-
-// launch_align_rates_chunk with the masked band kernel: L.plan is the round's upload (align_rates_round_plan_bytes: table | triples | unit_offset
-// | rects), n_rects in 1 ... kAlignMaxStretches - 1.  The reduction, the scan and the 32-byte scatter are the plain chunk's, as they are: the
-// rank of a round's records is the round's number, which the host adds.
+// launch_align_rates_chunk with the masked walk: L.plan is the round's upload (align_rates_round_plan_bytes), n_rects in 1 ... kAlignMaxStretches
+// - 1.  The reduction, the scan and the scatter are the plain chunk's: the rank of a round's records is the round's number, which the host adds.
 hipError_t launch_align_rates_masked_chunk(const AlignRatesLaunch &L, uint32_t n_rects, hipStream_t stream)
 {
     if (L.n_triples == 0 || L.n_units == 0 || !L.plan || n_rects == 0 || n_rects >= kAlignMaxStretches) return hipErrorInvalidValue;
-    const char *plan = static_cast<const char *>(L.plan);
-    const AlignRatesSlot *table = reinterpret_cast<const AlignRatesSlot *>(plan);
-    const AlignRatesTriple *triples = reinterpret_cast<const AlignRatesTriple *>(plan + align_rates_plan_triples_at());
-    const uint32_t *unit_offset = reinterpret_cast<const uint32_t *>(plan + align_rates_plan_offsets_at(L.n_triples));
-    const AlignRect *rects = reinterpret_cast<const AlignRect *>(plan + align_rates_plan_rects_at(L.n_triples));
-    // scratch: band records | triple records | dense records | block counts | block offsets | total (align_rates_scratch_bytes)
-    char *s = static_cast<char *>(L.scratch);
-    AlignBandRecord *band_records = reinterpret_cast<AlignBandRecord *>(s);
-    s += (size_t)L.n_units * sizeof(AlignBandRecord);
-    vdf_alignment_rate *triple_records = reinterpret_cast<vdf_alignment_rate *>(s);
-    s += (size_t)L.n_triples * sizeof(vdf_alignment_rate);
-    vdf_alignment_rate *dense = reinterpret_cast<vdf_alignment_rate *>(s);
-    s += (size_t)L.n_triples * sizeof(vdf_alignment_rate);
-    const uint32_t n_blocks = (L.n_triples + 255) / 256;
-    uint32_t *block_count = reinterpret_cast<uint32_t *>(s), *block_offset = block_count + n_blocks, *total = block_offset + n_blocks;
-
-    const size_t n_groups = ((size_t)L.n_units + kAlignWaves - 1) / kAlignWaves;
-    for (const AlignLaunchCut &cut : align_launch_cuts(n_groups)) {
-        hipLaunchKernelGGL(align_bands_rates_masked_kernel, dim3((uint32_t)cut.n), dim3(256), 0, stream, L.a_hashes, L.a_first, L.a_skip, L.b_hashes,
-                           L.b_first, L.b_skip, table, triples, unit_offset, L.n_triples, L.n_units, L.tol, L.min_run, band_records, (uint32_t)cut.group_base,
-                           rects, n_rects);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(align_reduce_rates_kernel, dim3(n_blocks), dim3(256), 0, stream, table, triples, unit_offset, L.n_triples, L.a_first, L.b_first, L.tol,
-                       band_records, triple_records, block_count);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(align_scan_kernel, dim3(1), dim3(1024), 0, stream, block_count, n_blocks, block_offset, total);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(align_scatter_rates_kernel, dim3(n_blocks), dim3(256), 0, stream, triple_records, L.n_triples, block_offset, dense);
-    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    *L.dense_out = dense;
-    *L.total_out = total;
-    return hipSuccess;
+    return align_run_rates_chunk<true>(L, n_rects, stream);
 }
 
 // ---- seeding: the pairs of videos that have a matching (seed, row) cell (include/vdf.h: vdf_align_seed_pairs*) -------------------

@@ -3,7 +3,7 @@
 // row den j of b); inside it everything is align_plan.h's: bands of 64 diagonals, the ka range of a band, the lane-ownership rules, align_better.
 // This header adds what the phases add: the sub-matrix sizes, the rows behind (i, j), which (phase, band) a unit of a pair is, the reduction
 // over the phases, and the chunks of a call with up to num x bands units per pair - as __host__ __device__ inline functions, so that the kernel
-// (align.hip: align_bands_retimed_kernel), the plain C++ definition (api.cpp) and the CPU replay (tests/cpp/align_retimed_plan_main.cpp) share
+// (align.hip: align_bands_kernel<AlignPairUnits<true>, false>), the plain C++ definition (api.cpp) and the CPU replay (tests/cpp/align_retimed_plan_main.cpp) share
 // one text.  No HIP calls.
 #pragma once
 #include "align_plan.h"
